@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- CG iterations/s and SpMV effective HBM GB/s of the hip target.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W warm-up steps, times exactly K steps, optionally writes
+the outputs of its last step (--dump-outputs) and prints the result line.  --full
+adds everything else: the K timed steps repeated as 5 blocks (median reported),
+the streaming-copy probe, the CPU baseline, the short legs on the other
+BASELINE.json configurations and, for N > 1, the one-process rr check.
 
 A "step" is one CG iteration driven through the C ABI exactly as the reference
 driver drives a backend (cg.cpp:97-112): spmv, dot, calc_xr, calc_p, with the
@@ -21,6 +27,13 @@ all-reduce of the ranks' exit codes.
 Rank 0 prints ONE JSON line; see the keys at the bottom.  The matrix, vectors and
 the CPU baseline are built outside the timed region; inputs are resident in HBM
 when the clock starts.
+
+--dump-outputs DIR (N = 1) writes what the timed loop computed by its last step as
+float64 .npy files: x.npy, r.npy, p.npy, w.npy (the iterate, the residual, the
+search direction and w = A p; for N > 2^20 the same fixed, seeded sample of 2^20
+rows of each: sample_rows.npy) and rr.npy (r.r after the last step).  N > 1 (the
+C++ driver keeps its vectors): rr.npy only.  The inputs depend on the arguments
+alone, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -32,8 +45,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); measured copy peak reported beside it
-BLOCKS = 5              # N = 1: the K timed steps are repeated this many times; the median block is reported
+BLOCKS = 5              # --full: the K timed steps are repeated this many times; the median block is reported
 CPU_RUNS = 5            # CPU baseline: runs per figure (reference run_benchmark:3,19-25: mean (min / max))
+DUMP_ROWS = 1 << 20     # --dump-outputs: rows sampled per vector when N is larger (4 vectors x 8 MiB)
+DUMP_SEED = 20240917    # fixed: the same rows on every run
 
 
 def parse():
@@ -53,8 +68,38 @@ def parse():
     ap.add_argument("--no-probe", dest="probe", action="store_false",
                     help="skip the streaming-copy bandwidth probe (the measured-peak denominator beside 8 TB/s)")
     ap.add_argument("--no-extras", dest="extras", action="store_false",
-                    help="N = 1: skip the short legs on the other BASELINE.json configurations")
+                    help="--full: skip the short legs on the other BASELINE.json configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: 5 blocks of the timed steps, the copy probe, "
+                         "the CPU baseline, the extra legs and (N > 1) the one-process rr check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64)")
     return ap.parse_args()
+
+
+def blocks(args):
+    return BLOCKS if args.full else 1
+
+
+def value_is(nblocks, steps):
+    if nblocks == 1:
+        return "%d timed steps after the warm-up steps, one block" % steps
+    return "median of %d blocks of %d timed steps (every block: r = b, the warm-up steps, the timed steps)" % (nblocks, steps)
+
+
+def dump_outputs(path, arrays):
+    """{name: 1-D array} -> path/<name>.npy as float64; vectors longer than DUMP_ROWS keep the same seeded
+    sample of rows (written beside them as sample_rows.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = max(len(a) for a in arrays.values())
+    rows = None
+    if n > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+        np.save(os.path.join(path, "sample_rows.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        np.save(os.path.join(path, name + ".npy"), a[rows] if rows is not None and len(a) == n else a)
 
 
 # The other single-GPU configurations of BASELINE.json (north_star's SpMV+ECC target is quoted
@@ -153,10 +198,8 @@ def single(args):
     A = ctx.create_matrix(cols, rows, vals, n, nnz)
     b, x, r, p, w = (ctx.create_vector(n) for _ in range(5))
     ctx.upload(b, generators.reference_rhs(n))  # glibc rand(), default seed: the reference's b (cg.cpp:66-74)
-    ctx.upload(x, np.zeros(n))
-    ctx.copy_vector(r, b)
-    ctx.copy_vector(p, r)
-    state = {"rr": ctx.dot(r, r)}
+    x0 = np.zeros(n)
+    state = {}
 
     def step():
         ctx.spmv(A, p, w)
@@ -167,7 +210,8 @@ def single(args):
         state["rr"] = rr_new
 
     def restart():
-        # r = b; p = r; rr = r.r (cg.cpp:87-91), then the warm-up steps
+        # x = 0; r = b; p = r; rr = r.r (cg.cpp:87-91), then the warm-up steps
+        ctx.upload(x, x0)
         ctx.copy_vector(r, b)
         ctx.copy_vector(p, r)
         state["rr"] = ctx.dot(r, r)
@@ -181,12 +225,12 @@ def single(args):
         # or more often when the run is short, so that at least ~25 launches are averaged
         stride = 1 if args.profile_all else max(1, min(4, args.steps // 25))
         ctx.profile(0xF if args.profile_all else 1 << capi.K_SPMV, stride=stride)
-    # The timed region: exactly `steps` iterations between two synchronisations -- BLOCKS times (a 5 ms window
-    # is shorter than this pool's run-to-run spread), every block the whole run again (r = b, warm-up, timed
-    # steps: rr at the end is rr after warmup + steps iterations, whatever BLOCKS is): `value` comes from the
-    # median block, the fastest and the slowest ride along as value_max / value_min.
+    # The timed region: exactly `steps` iterations between two synchronisations.  --full: BLOCKS times (a 5 ms
+    # window is shorter than the run-to-run spread), every block the whole run again (x = 0, r = b, warm-up, timed
+    # steps: x and rr at the end are those after warmup + steps iterations, whatever the number of blocks):
+    # `value` comes from the median block, the fastest and the slowest ride along as value_max / value_min.
     block_dt = []
-    for blk in range(BLOCKS):
+    for blk in range(blocks(args)):
         if blk:
             restart()
         ctx.synchronize()
@@ -198,6 +242,9 @@ def single(args):
         torch.cuda.synchronize()
         block_dt.append(time.perf_counter() - t0)
     dt = sorted(block_dt)[len(block_dt) // 2]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": ctx.download(x), "r": ctx.download(r), "p": ctx.download(p),
+                                         "w": ctx.download(w), "rr": [state["rr"]]})
 
     roof = None
     kernels = {}
@@ -225,7 +272,7 @@ def single(args):
                     "traffic_source": "profiles/pmc_summary.json (committed; profiles/collect_r04.sh regenerates it)",
                     "avg_launch_us": kernels["spmv"]["avg_us"], "algorithmic_bytes_per_launch": byts["spmv"]}
     probe = None
-    if args.probe:
+    if args.full and args.probe:
         c, rd = ctx.stream_probe(1 << 30, 10)
         probe = {"copy_GBps": round(c, 1), "read_GBps": round(rd, 1)}
         if roof:
@@ -244,7 +291,7 @@ def single(args):
 
     # ---- the other single-GPU configurations, outside the headline's timed loop ----
     extras = None
-    if args.extras and not args.no_profile:
+    if args.full and args.extras and not args.no_profile:
         extras = {}
         for key, spec, fmt, mode, what in EXTRA_LEGS:
             same = spec == args.spec
@@ -266,7 +313,7 @@ def single(args):
             try:
                 job = cpp_job(args, spec, mode, fmt, False)
                 leg = {"workload": "cg-%s -t hip -m %s --bench %d,%d,%d, synthetic %s, one process"
-                                   % (fmt, mode, args.warmup, args.steps, BLOCKS, spec)}
+                                   % (fmt, mode, args.warmup, args.steps, blocks(args), spec)}
                 leg.update(block_stats(job, args.steps))
                 leg.update({"N": job["N"], "nnz": job["nnz"], "graph_replay": job["graph_replay"], "stands_for": what})
                 if "first_attempt" in job:
@@ -276,7 +323,7 @@ def single(args):
                 extras[key] = {"error": str(e)[:300], "stands_for": what}
 
     cpu = None
-    if args.cpu_iters > 0 and args.fmt == "csr":
+    if args.full and args.cpu_iters > 0 and args.fmt == "csr":
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import baseline  # the CPU checker, timed as a baseline only
         # the reference's protocol (run_benchmark:3,19-25): NUM_RUNS = 5 runs, mean (min / max) -- here of
@@ -375,7 +422,7 @@ def cpp_job(args, spec, mode, fmt, profile):
     env = dict(os.environ)
     if profile:
         env["ABFT_BENCH_PROFILE"] = "1"
-    cmd = [exe, "-t", "hip", "-m", mode, "-s", spec, "--bench", "%d,%d,%d" % (args.warmup, args.steps, BLOCKS), "-q"]
+    cmd = [exe, "-t", "hip", "-m", mode, "-s", spec, "--bench", "%d,%d,%d" % (args.warmup, args.steps, blocks(args)), "-q"]
     rank = os.environ.get("RANK", "0")
     first_cmd = cmd
     if os.environ.get("ABFT_BENCH_INJECT_FAILURE") == rank:
@@ -414,7 +461,7 @@ def one_rank_rr(args, spec, mode, fmt):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "ABFT_COMM_FORCE", "ABFT_HIP_GPUS", "ABFT_BENCH_PROFILE",
                         "TORCHELASTIC_USE_AGENT_STORE")}
     env.setdefault("ABFT_HIP_DEVICE", os.environ.get("LOCAL_RANK", "0"))
-    p = run_cpp([exe, "-t", "hip", "-m", mode, "-s", spec, "--bench", "%d,%d,%d" % (args.warmup, args.steps, BLOCKS), "-q"], env)
+    p = run_cpp([exe, "-t", "hip", "-m", mode, "-s", spec, "--bench", "%d,%d,%d" % (args.warmup, args.steps, blocks(args)), "-q"], env)
     if p.returncode != 0:
         return {"error": "one-rank run exited with status %d: %s" % (p.returncode, p.stderr[-600:])}
     return parse_cpp(p)
@@ -425,8 +472,7 @@ def block_stats(job, steps):
     bs = job.get("block_seconds") or [job["seconds"]]
     return {"it_per_s": round(steps / job["seconds"], 2), "ms_per_step": round(job["seconds"] / steps * 1e3, 4),
             "blocks": len(bs), "it_per_s_min": round(steps / max(bs), 2), "it_per_s_max": round(steps / min(bs), 2),
-            "value_is": "median of %d blocks of %d timed steps (every block: r = b, the warm-up steps, the timed steps)"
-                        % (len(bs), steps),
+            "value_is": value_is(len(bs), steps),
             "iterations_per_block": job.get("iterations_per_block"), "rr_after_last_step": job["rr"]}
 
 
@@ -440,7 +486,7 @@ def multi(args):
         raise SystemExit("--gpus %d needs WORLD_SIZE=%d (launch with torch.distributed.run)" % (args.gpus, args.gpus))
     head = cpp_job(args, args.spec, args.mode, args.fmt, not args.no_profile)
     extra = None
-    if args.extras:
+    if args.full and args.extras:
         # the configuration the multi-GPU target is quoted on (BASELINE.json configs[3]): same path
         extra = cpp_job(args, EXTRA_SPEC_MULTI, "secded", "csr", not args.no_profile)
     if rank != 0:
@@ -452,7 +498,7 @@ def multi(args):
         d["transport_by_rank"] = job.get("transport", [])
         if "first_attempt" in job:
             d["first_attempt"] = job["first_attempt"]
-        if world > 1 and os.environ.get("ABFT_BENCH_RR_CHECK", "1") != "0":
+        if args.full and world > 1 and os.environ.get("ABFT_BENCH_RR_CHECK", "1") != "0":
             # self-validation: the same iterations by one process on rank 0's GPU
             one = one_rank_rr(args, spec, mode, fmt)
             if "rr" in one:
@@ -485,8 +531,7 @@ def main():
         out.update({"value": round(args.steps / dt, 2), "ms_per_step": round(dt / args.steps * 1e3, 4),
                     "blocks": len(block_dt), "value_min": round(args.steps / max(block_dt), 2),
                     "value_max": round(args.steps / min(block_dt), 2),
-                    "value_is": "median of %d blocks of %d timed steps (every block: r = b, the warm-up steps, the timed steps)"
-                                % (len(block_dt), args.steps),
+                    "value_is": value_is(len(block_dt), args.steps),
                     "config": {"workload": "cg-csr -t hip -m %s, synthetic %s" % (args.mode, args.spec)
                                if args.fmt == "csr" else "cg-coo -t hip -m %s, synthetic %s" % (args.mode, args.spec),
                                "N": n, "nnz": nnz, "format": args.fmt, "mode": args.mode, "parallelism": "1 GPU",
@@ -510,6 +555,8 @@ def main():
         pass
     if res is not None:
         head, hl, xl = res
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"rr": [hl["rr_after_last_step"]]})
         out = dict(base)
         sp = hl.get("spmv_rank0")
         roof = None

@@ -9,7 +9,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/prof_r01
 rm -rf $O; mkdir -p $O
-B="python3 bench.py --cpu-iters 0"
+B="python3 bench.py --full --cpu-iters 0"
 rocprofv3 --kernel-trace --stats -f csv -d $O/trace -- $B --steps 100 > $O/bench_under_trace.json 2> $O/trace.err
 python3 profiles/summarize.py trace $O/trace $O/kernel_trace_laplace_none.md
 rocprofv3 --kernel-trace --stats -f csv -d $O/trace_secded -- $B --steps 100 --mode secded > $O/bench_under_trace_secded.json 2> $O/trace2.err

@@ -11,6 +11,7 @@ import re
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -466,10 +467,10 @@ def test_run_benchmark_script(fmt):
 
 
 def test_bench_py_one_gpu_line_carries_the_contract_keys():
-    """`python bench.py` at N = 1 on a small matrix: ONE JSON line with the driver's keys, `roofline` (bound, achieved,
-    peak, frac, traffic) and `cpu_baseline` (value, unit, cores, kind, sample: mean / min / max of 5 runs, one
+    """`python bench.py --full` at N = 1 on a small matrix: ONE JSON line with the driver's keys, `roofline` (bound,
+    achieved, peak, frac, traffic) and `cpu_baseline` (value, unit, cores, kind, sample: mean / min / max of 5 runs, one
     core beside all), the K timed steps as 5 blocks with the median reported, and the like-for-like graph loop."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--spec",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "12", "--warmup", "3", "--spec",
                         "laplace5:400,400", "--cpu-iters", "20", "--no-probe"], capture_output=True, text=True,
                        timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-500:] + p.stderr[-1500:]
@@ -499,6 +500,41 @@ def test_bench_py_one_gpu_line_carries_the_contract_keys():
     assert legs["config4_shard1"]["layout"] == "sweep" and legs["config5"]["layout"] == "panels"
 
 
+def test_bench_py_plain_run_times_exactly_the_steps_and_dumps_its_outputs(tmp_path):
+    """A plain `python bench.py` (no --full): the headline keys only -- one block of exactly K timed steps, no CPU
+    baseline, probe or extra legs -- and --dump-outputs writes the last step's x, r, p, w and rr as float64 .npy.
+    Two runs with the same arguments start from the same inputs and end with the same residual; x is the CG
+    iterate after W + K iterations from x0 = 0 (the oracle's, to the reductions' tolerance)."""
+    from _oracle import CSR, OracleMatrix
+    from abft_sparse_cg_amd import generators
+
+    lines = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "9", "--warmup",
+                            "2", "--spec", "laplace5:40,40", "--dump-outputs", str(tmp_path / run)], capture_output=True,
+                           text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stdout[-500:] + p.stderr[-1500:]
+        out = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "config"):
+        assert k in d, k
+    assert d["steps"] == 9 and d["warmup"] == 2 and d["blocks"] == 1 and d["config"]["iterations_per_block"] == 11
+    assert d["value"] > 0 and abs(d["ms_per_step"] - 1e3 / d["value"]) <= 1e-3 * d["ms_per_step"] + 1e-4
+    assert d["cpu_baseline"] is None and "extra_legs" not in d and "stream_probe" not in d
+    got = {run: {k: np.load(str(tmp_path / run / (k + ".npy"))) for k in ("x", "r", "p", "w", "rr")} for run in "ab"}
+    for k, v in got["a"].items():
+        assert v.dtype == np.float64 and v.shape == ((1,) if k == "rr" else (1600,)), k
+        assert np.allclose(v, got["b"][k], rtol=1e-10, atol=0), k
+    rr = float(got["a"]["rr"][0])
+    assert rr == d["config"]["rr_after_last_step"] and abs(rr - float(got["a"]["r"] @ got["a"]["r"])) <= 1e-10 * rr
+    cols, rows, vals, n = generators.generate("laplace5:40,40")
+    it, hist, x_o, _ = OracleMatrix(CSR, "none", cols, rows, vals, n).cg(generators.reference_rhs(n), max_itrs=11, conv=0.0)
+    assert it == 11 and abs(rr - hist[-1]) <= 1e-10 * hist[-1]
+    assert np.abs(got["a"]["x"] - x_o).max() <= 1e-10 * np.abs(x_o).max()
+
+
 def test_bench_py_multi_rank_path_runs_the_cpp_driver():
     """bench.py --gpus N (N > 1 under the launcher) starts host/cg-csr --bench per rank; here the
     same code path with one rank (collectives forced onto RCCL), small matrix, no extra leg."""
@@ -522,7 +558,7 @@ def test_bench_py_under_the_launcher_two_ranks_two_jobs():
     on the same rendezvous port (headline + the extra leg), rank 0 prints one JSON line."""
     env = dict(os.environ, ABFT_COMM="tcp", ABFT_HIP_DEVICE="0", ABFT_BENCH_EXTRA_SPEC="random:16384,12,3")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(23000 + os.getpid() % 6000), os.path.join(ROOT, "bench.py"), "--gpus", "2",
+           "127.0.0.1", "--master-port", str(23000 + os.getpid() % 6000), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2",
            "--steps", "8", "--warmup", "3", "--spec", "laplace5:200,200", "--mode", "secded"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-800:] + p.stderr[-2500:]
@@ -545,7 +581,7 @@ def test_bench_py_failed_first_attempt_is_agreed_on_and_recorded():
     carries the failed attempt -- statuses by rank and rank 0's stderr tail -- as `first_attempt`."""
     env = dict(os.environ, ABFT_COMM="tcp", ABFT_HIP_DEVICE="0", ABFT_BENCH_INJECT_FAILURE="1", ABFT_COMM_TIMEOUT="8")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(24000 + os.getpid() % 5000), os.path.join(ROOT, "bench.py"), "--gpus", "2",
+           "127.0.0.1", "--master-port", str(24000 + os.getpid() % 5000), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2",
            "--steps", "6", "--warmup", "3", "--spec", "laplace5:150,150", "--mode", "secded", "--no-extras"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-800:] + p.stderr[-2500:]
@@ -659,7 +695,7 @@ def test_bench_py_under_the_launcher_at_full_size():
     env = dict(os.environ, ABFT_COMM="tcp", ABFT_HIP_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(RANKS_ONE_GPU),
            "--master-addr", "127.0.0.1", "--master-port", str(25000 + os.getpid() % 4000), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(RANKS_ONE_GPU), "--steps", "4", "--warmup", "3"]
+           "--full", "--gpus", str(RANKS_ONE_GPU), "--steps", "4", "--warmup", "3"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-800:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

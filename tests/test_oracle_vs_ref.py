@@ -1,7 +1,15 @@
 """Pins oracle/abft_oracle.c against the REFERENCE's own CPUContext objects
-(oracle/_ref/, built from /root/reference by oracle/Makefile).  Skipped when
-that build is absent; tests/test_golden.py then pins the oracle through the
-committed fixtures the same build produced."""
+(oracle/_ref/, built from the reference tree by oracle/Makefile).  Where that
+build is absent, the reference's side of every comparison comes from
+tests/golden/oracle_vs_ref.npz: what the same calls returned in the reference
+build, recorded with
+
+    ABFT_RECORD_REF=1 python -m pytest tests/test_oracle_vs_ref.py
+
+(which needs oracle/_ref and rewrites the fixture)."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -9,7 +17,91 @@ from _capture import run_captured
 from _oracle import (COO, CSR, MODES, Oracle, OracleMatrix, Ref, event_lines, have_ref, laplace5,
                      ora_calc_p, ora_calc_xr, ora_dot, random_spd, ref_cg, ref_flip_spmv, ref_inject_rand, rhs)
 
-pytestmark = [pytest.mark.ref, pytest.mark.skipif(not have_ref(), reason="oracle/_ref not built")]
+pytestmark = pytest.mark.ref
+
+STORE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vs_ref.npz")
+RECORD = os.environ.get("ABFT_RECORD_REF") == "1"
+_recorded = {}
+_stored = None
+
+
+def _pack(obj, arrays):
+    """nested tuples / lists of arrays and scalars -> JSON-able tree; arrays go to `arrays`, a leaf names its dtype,
+    its shape and the earlier array of the same dtype and shape it is stored against (-1: none)"""
+    if isinstance(obj, np.ndarray):
+        obj = np.ascontiguousarray(obj)
+        base = max((i for i, a in enumerate(arrays) if a.dtype == obj.dtype and a.shape == obj.shape), default=-1)
+        arrays.append(obj)
+        return {"@": [obj.dtype.str, list(obj.shape), base]}
+    if isinstance(obj, (list, tuple)):
+        return [_pack(v, arrays) for v in obj]
+    if isinstance(obj, np.generic):
+        return obj.item()
+    return obj
+
+
+def _leaves(tree):
+    if isinstance(tree, dict):
+        yield tree["@"]
+    elif isinstance(tree, list):
+        for v in tree:
+            yield from _leaves(v)
+
+
+def _unpack(tree, it):
+    if isinstance(tree, dict):
+        return next(it)
+    if isinstance(tree, list):
+        return [_unpack(v, it) for v in tree]
+    return tree
+
+
+def _write_store(records):
+    """Every array is stored as its bytes XOR those of its base (the results of neighbouring cases differ in a few
+    elements), all in one compressed blob."""
+    arrays = []
+    tree = {k: _pack(v, arrays) for k, v in sorted(records.items())}
+    raw = [np.frombuffer(a.tobytes(), dtype=np.uint8) for a in arrays]
+    leaves = [l for k in sorted(tree) for l in _leaves(tree[k])]
+    blob = [r ^ raw[base] if base >= 0 else r for r, (_, _, base) in zip(raw, leaves)]
+    np.savez_compressed(STORE, tree=np.frombuffer(json.dumps(tree, sort_keys=True).encode(), dtype=np.uint8),
+                        blob=np.concatenate(blob) if blob else np.zeros(0, np.uint8))
+
+
+def _read_store():
+    with np.load(STORE) as z:
+        tree, blob = json.loads(z["tree"].tobytes().decode()), z["blob"]
+    leaves = [l for k in sorted(tree) for l in _leaves(tree[k])]
+    raw, off = [], 0
+    for dt, shape, base in leaves:
+        n = int(np.prod(shape, dtype=np.int64)) * np.dtype(dt).itemsize
+        raw.append(blob[off:off + n] ^ raw[base] if base >= 0 else blob[off:off + n])
+        off += n
+    assert off == len(blob)
+    it = iter(np.frombuffer(r.tobytes(), dtype=dt).reshape(shape) for r, (dt, shape, _) in zip(raw, leaves))
+    return {k: _unpack(tree[k], it) for k in sorted(tree)}
+
+
+def ref_side(key, fn, *args):
+    """The reference's result of fn(*args): computed live where oracle/_ref is built, else the recorded one."""
+    if have_ref():
+        res = fn(*args)
+        if RECORD:
+            _recorded[key] = res
+        return res
+    global _stored
+    if _stored is None:
+        _stored = _read_store()
+    return _stored[key]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _record_store():
+    yield
+    if RECORD and _recorded:
+        assert have_ref()
+        _write_store(_recorded)
+
 
 FMTS = [CSR, COO]
 NBITS = {CSR: 96, COO: 128}
@@ -26,24 +118,33 @@ def _rand_words(fmt, rng):
 @pytest.mark.parametrize("fmt", FMTS)
 def test_syndrome_parity_match_reference_on_random_words(fmt):
     rng = np.random.default_rng(7)
-    L = Ref.lib(fmt)
-    for _ in range(2000):
-        n = 3 if fmt == CSR else 4
-        w = rng.integers(0, 2**32, size=n, dtype=np.uint64).astype(np.uint32)
-        p = w.ctypes.data_as(__import__("ctypes").POINTER(__import__("ctypes").c_uint32))
-        assert Oracle.syndrome(fmt, w) == L.ref_ecc_syndrome(p)
-        assert Oracle.parity(fmt, w) == L.ref_ecc_parity(p)
+    n = 3 if fmt == CSR else 4
+    words = [rng.integers(0, 2**32, size=n, dtype=np.uint64).astype(np.uint32) for _ in range(2000)]
+
+    def ref_words():
+        import ctypes
+        L = Ref.lib(fmt)
+        ptrs = [w.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) for w in words]
+        return [L.ref_ecc_syndrome(p) for p in ptrs], [L.ref_ecc_parity(p) for p in ptrs]
+
+    syn, par = ref_side("syndrome_parity/%d" % fmt, ref_words)
+    for w, s, p in zip(words, syn, par):
+        assert Oracle.syndrome(fmt, w) == s
+        assert Oracle.parity(fmt, w) == p
 
 
 @pytest.mark.parametrize("fmt", FMTS)
 def test_flipped_bit_matches_reference_for_every_syndrome(fmt):
-    L = Ref.lib(fmt)
+    syns = []
     for h in range(1, 128):
         s = 0
         for p in range(1, 8):
             if (h >> (p - 1)) & 1:
                 s |= 1 << (32 - p)
-        assert Oracle.flipped_bit(fmt, s) == L.ref_ecc_flipped_bit(s), h
+        syns.append(s)
+    bits = ref_side("flipped_bit/%d" % fmt, lambda: [Ref.lib(fmt).ref_ecc_flipped_bit(s) for s in syns])
+    for h, s, b in zip(range(1, 128), syns, bits):
+        assert Oracle.flipped_bit(fmt, s) == b, h
 
 
 @pytest.mark.parametrize("fmt", FMTS)
@@ -51,20 +152,26 @@ def test_flipped_bit_matches_reference_for_every_syndrome(fmt):
 def test_encoded_matrix_identical(fmt, mode):
     cols, rows, vals, n = random_spd(60, 6, seed=3)
     o = OracleMatrix(fmt, mode, cols, rows, vals, n)
-    r = Ref(fmt, mode, cols, rows, vals, n)
-    assert np.array_equal(o.stored_words(), r.stored_words())
+
+    def ref_encoded():
+        r = Ref(fmt, mode, cols, rows, vals, n)
+        return r.stored_words(), (r.rowptr() if fmt == CSR else None)
+
+    words, rowptr = ref_side("encoded/%d/%s" % (fmt, mode), ref_encoded)
+    assert np.array_equal(o.stored_words(), words)
     if fmt == CSR:
-        assert np.array_equal(o.csr_arrays()[1], r.rowptr())
+        assert np.array_equal(o.csr_arrays()[1], rowptr)
 
 
 @pytest.mark.parametrize("fmt", FMTS)
 @pytest.mark.parametrize("mode", MODES)
 def test_spmv_bit_identical_no_faults(fmt, mode):
-    for mat in (laplace5(9, 7), random_spd(80, 8, seed=5)):
+    for i, mat in enumerate((laplace5(9, 7), random_spd(80, 8, seed=5))):
         cols, rows, vals, n = mat
         x = rhs(n, 11) - 0.5
         o = OracleMatrix(fmt, mode, cols, rows, vals, n)
-        code, text, ((y_ref,), _) = run_captured(ref_flip_spmv, fmt, mode, mat, 0, [], x, 1)
+        code, text, ((y_ref,), _) = ref_side("spmv/%d/%s/%d" % (fmt, mode, i), run_captured, ref_flip_spmv, fmt, mode, mat,
+                                             0, [], x, 1)
         assert code == 0 and text == ""
         y = o.spmv(x)
         assert np.array_equal(y.view(np.uint64), y_ref.view(np.uint64))
@@ -79,7 +186,8 @@ def test_every_single_flip_same_events_and_result(fmt, mode):
     x = rhs(n, 2) + 0.25
     index = len(vals) // 2
     for bit in range(NBITS[fmt]):
-        code, text, res = run_captured(ref_flip_spmv, fmt, mode, mat, index, [bit], x)
+        code, text, res = ref_side("single_flip/%d/%s/%d" % (fmt, mode, bit), run_captured, ref_flip_spmv, fmt, mode, mat,
+                                   index, [bit], x)
         o = OracleMatrix(fmt, mode, cols, rows, vals, n)
         o.inject(index, [bit])
         y1 = o.spmv(x)
@@ -110,7 +218,8 @@ def test_double_flips_same_behaviour(fmt, mode):
     for _ in range(60):
         b1, b2 = rng.choice(NBITS[fmt], size=2, replace=False)
         # a double flip that changes the gather index beyond the vector is UB in the reference
-        code, text, res = run_captured(ref_flip_spmv, fmt, mode, mat, index, [b1, b2], x, 1)
+        code, text, res = ref_side("double_flip/%d/%s/%d_%d" % (fmt, mode, b1, b2), run_captured, ref_flip_spmv, fmt, mode,
+                                   mat, index, [b1, b2], x, 1)
         o = OracleMatrix(fmt, mode, cols, rows, vals, n)
         o.inject(index, [b1, b2])
         y = o.spmv(x)
@@ -133,7 +242,8 @@ def test_constraints_violations_match(fmt):
     hit = 0
     for index in (0, 5, len(vals) - 1, len(vals) // 3):
         for bit in idx_bits:
-            code, text, res = run_captured(ref_flip_spmv, fmt, "constraints", mat, index, [bit], x, 1)
+            code, text, res = ref_side("constraints/%d/%d/%d" % (fmt, index, bit), run_captured, ref_flip_spmv, fmt,
+                                       "constraints", mat, index, [bit], x, 1)
             if code not in (0, 1):
                 continue  # reference faulted on an out-of-range gather before any check fired
             o = OracleMatrix(fmt, "constraints", cols, rows, vals, n)
@@ -150,17 +260,23 @@ def test_constraints_violations_match(fmt):
 
 def test_vector_kernels_bit_identical():
     cols, rows, vals, n = laplace5(5, 5)
-    r = Ref(CSR, "none", cols, rows, vals, n)
     rng = np.random.default_rng(0)
     a, b = rng.standard_normal(1000), rng.standard_normal(1000)
-    assert ora_dot(a, b) == r.dot(a, b)
     x1, r1, p1, w1 = (rng.standard_normal(1000) for _ in range(4))
-    x2, r2 = x1.copy(), r1.copy()
-    assert ora_calc_xr(x1, r1, p1, w1, 0.37) == r.calc_xr(x2, r2, p1, w1, 0.37)
+
+    def ref_vectors():
+        r = Ref(CSR, "none", cols, rows, vals, n)
+        x2, r2, p2 = x1.copy(), r1.copy(), p1.copy()
+        d = r.dot(a, b)
+        rr = r.calc_xr(x2, r2, p1, w1, 0.37)
+        r.calc_p(p2, r2, 1.7)
+        return d, rr, x2, r2, p2
+
+    d, rr, x2, r2, p2 = ref_side("vector_kernels", ref_vectors)
+    assert ora_dot(a, b) == d
+    assert ora_calc_xr(x1, r1, p1, w1, 0.37) == rr
     assert np.array_equal(x1, x2) and np.array_equal(r1, r2)
-    p2 = p1.copy()
     ora_calc_p(p1, r1, 1.7)
-    r.calc_p(p2, r2, 1.7)
     assert np.array_equal(p1, p2)
 
 
@@ -172,7 +288,7 @@ def test_cg_history_bit_identical(fmt, mode):
     b = rhs(n, 1)
     o = OracleMatrix(fmt, mode, cols, rows, vals, n)
     it_o, h_o, x_o, fatal = o.cg(b)
-    code, text, (it_r, h_r, x_r) = run_captured(ref_cg, fmt, mode, mat, b)
+    code, text, (it_r, h_r, x_r) = ref_side("cg/%d/%s" % (fmt, mode), run_captured, ref_cg, fmt, mode, mat, b)
     assert code == 0 and not fatal
     assert it_o == it_r and it_o > 10
     assert np.array_equal(h_o.view(np.uint64), h_r.view(np.uint64))
@@ -189,7 +305,8 @@ def test_inject_rand_draws_like_reference(fmt):
 
     for kind in (0, 1, 2):
         for flips in (1, 2, 3):
-            code, text, words = run_captured(ref_inject_rand, fmt, mat, 1234, kind, flips)
+            code, text, words = ref_side("inject_rand/%d/%d/%d" % (fmt, kind, flips), run_captured, ref_inject_rand, fmt, mat,
+                                         1234, kind, flips)
             assert code == 0
             libc.srand(1234)
             o = OracleMatrix(fmt, "none", cols, rows, vals, n)
