@@ -19,6 +19,7 @@ FMT_CSR, FMT_COO = 0, 1
 FLIP_ANY, FLIP_VALUE, FLIP_INDEX = 0, 1, 2
 PART_ALL, PART_INTERIOR, PART_BOUNDARY = 0, 1, 2
 K_SPMV, K_DOT, K_CALC_XR, K_CALC_P = 0, 1, 2, 3
+MAX_RHS = 8  # block right-hand sides per call (include/abft_hip.h)
 
 u32p = C.POINTER(C.c_uint32)
 f64p = C.POINTER(C.c_double)
@@ -75,6 +76,11 @@ SIGNATURES = {
     "abft_hip_calc_xr": (C.c_int, [vp, vp, vp, vp, vp, C.c_double, f64p]),
     "abft_hip_calc_p": (C.c_int, [vp, vp, vp, C.c_double]),
     "abft_hip_spmv": (C.c_int, [vp, vp, vp, vp]),
+    "abft_hip_matrix_create_csr_stream": (C.c_int, [vp, C.c_int, u32p, u32p, f64p, C.c_int, C.c_int, vpp]),
+    "abft_hip_spmm": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+    "abft_hip_dot_block": (C.c_int, [vp, vp, vp, C.c_int, f64p]),
+    "abft_hip_calc_xr_block": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, f64p, C.c_uint32, f64p]),
+    "abft_hip_calc_p_block": (C.c_int, [vp, vp, vp, C.c_int, f64p, C.c_uint32]),
     "abft_hip_dot_dev": (C.c_int, [vp, vp, vp, vp]),
     "abft_hip_calc_xr_dev": (C.c_int, [vp, vp, vp, vp, vp, C.c_double, vp]),
     "abft_hip_read_pair": (C.c_int, [vp, vp, f64p, f64p]),

@@ -48,6 +48,9 @@ Additional options of this build:
       --seed            N     Seed for the -x draws (default: time)
       --flip-at  I:B[,B...]   Flip the given bit(s) of matrix element I (may be repeated)
   -q  --quiet                 Do not print the per-iteration residual
+      --rhs             K     Solve K right-hand sides (1-8) at once, one pass over the
+                              matrix per iteration (CSR only); column j of b is the
+                              reference's b drawn with seed 1+j
 
 """
 
@@ -59,7 +62,8 @@ def fail(msg):
 
 def parse(argv):
     o = dict(num_blocks=25, max_itrs=1000, conv=0.001, matrix_file=DEFAULT_MTX, synthetic=None, target="cpu",
-             mode="none", flips=0, kind="ANY", seed=None, quiet=False, flip_at=None, fmt="csr", list=False)
+             mode="none", flips=0, kind="ANY", seed=None, quiet=False, flip_at=None, fmt="csr", list=False,
+             rhs=1)
 
     def num(s, conv):
         try:
@@ -124,6 +128,10 @@ def parse(argv):
                 o["flip_at"] = (o["flip_at"] or []) + [(int(idx), [int(b) for b in bits.split(",")])]  # repeatable: one element each
             except ValueError:
                 fail("Invalid --flip-at (want INDEX:BIT[,BIT...])")
+        elif a == "--rhs":
+            o["rhs"] = num(arg("Invalid number of right-hand sides"), int)
+            if not 1 <= o["rhs"] <= 8:
+                fail("Invalid number of right-hand sides")
         elif a in ("--quiet", "-q"):
             o["quiet"] = True
         elif a in ("--help", "-h"):
@@ -181,6 +189,10 @@ def main(argv=None):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         fail("several ranks: run host/cg-csr or host/cg-coo under this launcher (--no-python); "
              "this Python driver is single-GPU")
+    if o["rhs"] > 1:
+        if o["fmt"] != "csr":
+            fail("--rhs with more than one right-hand side needs --format csr")
+        return run_block(o)
     return run_single(o)
 
 
@@ -246,6 +258,49 @@ def run_single(o):
     err = np.abs(ctx.download(b) - ctx.download(r))
     print("total error = %f" % math.sqrt(float((err * err).sum())))
     print("max error   = %f" % (float(err.max()) if n else 0.0))
+    print()
+    ctx.destroy_matrix(A)
+    ctx.close()
+    return 0
+
+
+def run_block(o):
+    """run_single for o["rhs"] right-hand sides at once (cg_solve_block): the matrix in the streaming
+    layout, one line of K residuals per iteration, a `ran for` line and the errors per column."""
+    from . import HIPContext, generators
+    from .context import cg_solve_block
+    K = o["rhs"]
+    cols, rows, vals, n, block = load_matrix(o)
+    nnz = len(vals)
+    ctx = HIPContext(o["mode"], "csr")
+    A = ctx.create_matrix(cols, rows, vals, n, nnz, layout="stream")
+    del cols, rows, vals
+    header(o, n, block, nnz)
+    b, x, r, p, w = (ctx.create_block(n, K) for _ in range(5))
+    ctx.upload(b, np.stack([generators.reference_rhs(n, seed=1 + j) for j in range(K)], axis=1))
+    ctx.upload(x, np.zeros((n, K)))
+    for index, bits in draw_flips(o, nnz):
+        for bit in bits:
+            print("*** flipping bit %d at index %d ***" % (bit, index))
+        ctx.inject_at(A, index, bits)
+
+    def line(itr, rr, active):
+        if not o["quiet"]:
+            print("iteration %5u :  rr = %s" % (itr, " ".join("%12.4f" % v for v in rr)))
+
+    t0 = time.perf_counter()
+    itrs, _ = cg_solve_block(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line)
+    ms = (time.perf_counter() - t0) * 1e3
+    print()
+    for j in range(K):
+        print("rhs %u: ran for %u iterations" % (j, itrs[j]))
+    print("\ntime taken = %7.2f ms (%u right-hand sides)\n" % (ms, K))
+    ctx.spmm(A, x, r, K)
+    err = np.abs(ctx.download(b) - ctx.download(r))
+    for j in range(K):
+        e = err[:, j]
+        print("rhs %u: total error = %f" % (j, math.sqrt(float((e * e).sum()))))
+        print("rhs %u: max error   = %f" % (j, float(e.max()) if n else 0.0))
     print()
     ctx.destroy_matrix(A)
     ctx.close()

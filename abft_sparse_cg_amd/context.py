@@ -33,8 +33,9 @@ class Matrix:
 
 
 class Vector:
-    def __init__(self, ctx, handle, n):
+    def __init__(self, ctx, handle, n, k=None):
         self.ctx, self.h, self.N = ctx, handle, n
+        self.K = k  # block vectors (create_block): N*K entries, (i, j) at i*K + j
         self._dptr = None
 
     @property
@@ -93,14 +94,27 @@ class HIPContext:
             pass
 
     # ---- matrix -----------------------------------------------------------
-    def create_matrix(self, columns, rows, values, N, nnz, n_in=None, index_base=0):
-        """reference CGContext.h:15-18.  n_in/index_base make a row-block shard."""
+    def create_matrix(self, columns, rows, values, N, nnz, n_in=None, index_base=0, layout=None):
+        """reference CGContext.h:15-18.  n_in/index_base make a row-block shard.
+        layout="stream": CSR, whole matrix, always in the streaming row-block layout -- the
+        one spmm runs on (abft_hip_matrix_create_csr_stream); None: the library's choice."""
         columns = np.ascontiguousarray(columns, dtype=np.uint32)
         rows = np.ascontiguousarray(rows, dtype=np.uint32)
         values = np.ascontiguousarray(values, dtype=np.float64)
         assert len(columns) >= nnz and len(rows) >= nnz and len(values) >= nnz
-        n_in = N if n_in is None else n_in
+        if layout not in (None, "stream"):
+            raise ValueError("layout must be None or 'stream', not %r" % (layout,))
         h = C.c_void_p()
+        if layout == "stream":
+            if self.fmt != FMT_CSR or (n_in is not None and n_in != N) or index_base:
+                raise ValueError("layout='stream' takes a whole CSR matrix")
+            check(self.L.abft_hip_matrix_create_csr_stream(
+                self.h, self.mode_id, columns.ctypes.data_as(capi.u32p), rows.ctypes.data_as(capi.u32p),
+                values.ctypes.data_as(capi.f64p), N, nnz, C.byref(h)))
+            m = Matrix(self, h, self.fmt, self.mode, N, N, nnz)
+            self._live.append(m)
+            return m
+        n_in = N if n_in is None else n_in
         check(self.L.abft_hip_matrix_create_shard(
             self.h, self.fmt, self.mode_id, columns.ctypes.data_as(capi.u32p), rows.ctypes.data_as(capi.u32p),
             values.ctypes.data_as(capi.f64p), N, n_in, nnz, index_base, C.byref(h)))
@@ -141,6 +155,14 @@ class HIPContext:
         self._live.append(v)
         return v
 
+    def create_block(self, N, K):
+        """a block vector of N rows and K columns (1 <= K <= 8): one vector of N*K entries, row-major"""
+        if not 1 <= K <= capi.MAX_RHS:
+            raise ValueError("K = %d outside [1, %d]" % (K, capi.MAX_RHS))
+        v = self.create_vector(N * K)
+        v.K = K
+        return v
+
     def view_vector(self, parent, offset, N):
         h = C.c_void_p()
         check(self.L.abft_hip_vector_view(parent.h, offset, N, C.byref(h)))
@@ -170,14 +192,16 @@ class HIPContext:
         check(self.L.abft_hip_vector_copy(dst.h, src.h))
 
     def upload(self, v, array):
+        """array: (N,), or (N, K) for a block vector (stored row-major)"""
         h = self.map_vector(v)
-        h[:] = array
+        h[:] = np.ascontiguousarray(array, dtype=np.float64).reshape(-1)
         self.unmap_vector(v, h)
 
     def download(self, v):
+        """-> (N,), or (N, K) for a block vector made by create_block"""
         h = self.map_vector(v)
         out = h.copy()
-        return out
+        return out.reshape(-1, v.K) if v.K else out
 
     # ---- kernels ----------------------------------------------------------
     def dot(self, a, b):
@@ -200,6 +224,39 @@ class HIPContext:
             check(self.L.abft_hip_spmv(self.h, mat.h, vec.h, result.h))
         else:
             check(self.L.abft_hip_spmv_part(self.h, mat.h, vec.h, result.h, part))
+
+    # ---- block right-hand sides (K columns per call; include/abft_hip.h) ----
+    def spmm(self, mat, X, Y, k, drain=True):
+        """Y = A X for k columns, one pass over the matrix.  Events as after spmv: drained and
+        printed (FatalEvent on a fatal one) -- at once, or with drain=False by the next call
+        that reads a result (the CG loop's dot_block), as the spmv of cg_solve is."""
+        check(self.L.abft_hip_spmm(self.h, mat.h, X.h, Y.h, k))
+        if drain:
+            self._drain()
+
+    def dot_block(self, a, b, k):
+        """-> np.ndarray of k dots a[:, j] . b[:, j]"""
+        out = np.zeros(k)
+        check(self.L.abft_hip_dot_block(self.h, a.h, b.h, k, out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return out
+
+    def calc_xr_block(self, x, r, p, w, k, alpha, active):
+        """x[:, j] += alpha[j] p[:, j]; r[:, j] -= alpha[j] w[:, j] for the columns j set in `active`
+        (bit mask); -> np.ndarray of k values r[:, j] . r[:, j]"""
+        a = np.zeros(capi.MAX_RHS)
+        a[:k] = alpha
+        out = np.zeros(k)
+        check(self.L.abft_hip_calc_xr_block(self.h, x.h, r.h, p.h, w.h, k, a.ctypes.data_as(capi.f64p), int(active),
+                                            out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return out
+
+    def calc_p_block(self, p, r, k, beta, active):
+        """p[:, j] = r[:, j] + beta[j] p[:, j] for the columns j set in `active`"""
+        b = np.zeros(capi.MAX_RHS)
+        b[:k] = beta
+        check(self.L.abft_hip_calc_p_block(self.h, p.h, r.h, k, b.ctypes.data_as(capi.f64p), int(active)))
 
     def matrix_info(self, mat):
         """-> (layout: 'stream' | 'panels' | 'sweep' | 'slice', kernel launches per spmv) -- measurement only"""
@@ -345,3 +402,46 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
             on_iteration(itr, rr)
         itr += 1
     return itr, rr
+
+
+def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None):
+    """cg_solve for the K columns of block vectors (ctx.create_block) at once: per column j exactly
+    cg_solve's control flow -- column j iterates while itrs[j] < max_itrs and rr[j] > conv_threshold --
+    on one spmm / dot_block / calc_xr_block / calc_p_block per iteration.  A column that has stopped
+    is frozen through the active mask (its x, r, p are not touched again); the loop ends when no
+    column is active.  on_iteration(itr, rr, active): after every iteration, rr of all K columns and
+    the mask of the columns that iteration updated.  -> (itrs[K], rr[K])"""
+    k = B.K
+    if not k:
+        raise ValueError("cg_solve_block wants block vectors (create_block)")
+    ctx.copy_vector(R, B)
+    ctx.copy_vector(P, R)
+    rr = np.array(ctx.dot_block(R, R, k), dtype=np.float64)
+    itrs = [0] * k
+    noted = {}
+    for j in range(k):
+        note_threshold(rr[j], conv_threshold, noted)
+
+    def still(j):
+        return itrs[j] < max_itrs and rr[j] > conv_threshold
+
+    active = sum(1 << j for j in range(k) if still(j))
+    itr = 0
+    while active:
+        on = [(active >> j) & 1 for j in range(k)]
+        ctx.spmm(A, P, W, k, drain=False)
+        pw = ctx.dot_block(P, W, k)
+        alpha = [fdiv(rr[j], pw[j]) if on[j] else 0.0 for j in range(k)]
+        rr_new = ctx.calc_xr_block(X, R, P, W, k, alpha, active)
+        beta = [fdiv(rr_new[j], rr[j]) if on[j] else 0.0 for j in range(k)]
+        ctx.calc_p_block(P, R, k, beta, active)
+        for j in range(k):
+            if on[j]:
+                rr[j] = rr_new[j]
+                itrs[j] += 1
+                note_threshold(rr[j], conv_threshold, noted)
+        if on_iteration is not None:
+            on_iteration(itr, rr.copy(), active)
+        itr += 1
+        active = sum(1 << j for j in range(k) if on[j] and still(j))
+    return itrs, rr

@@ -112,6 +112,10 @@ struct abft_hip_ctx {
     double alpha = 0.0;
   } defer;
   double *alpha_dev = nullptr;  // alpha of the deferred update when it was formed on the device
+  // block right-hand sides (abft_hip_dot_block, abft_hip_calc_xr_block): allocated by the first such call
+  double *bpartials = nullptr;          // ABFT_MAX_RHS * ABFT_MAX_PARTIALS doubles
+  HostSlotK *bslot = nullptr, *bslot_dev = nullptr;  // pinned K-wide result slot, its device alias
+  uint32_t bseq = 0;                    // last sequence number handed to a block reduction
   unsigned prof = 0;  // bit k: bracket launches of kernel k with HIP events
   unsigned prof_stride = 1, prof_seen[ABFT_K_COUNT] = {};  // ... every prof_stride-th launch of it
   ProfSlot prof_k[ABFT_K_COUNT];
@@ -423,6 +427,8 @@ extern "C" int abft_hip_shutdown(abft_hip_ctx *ctx) {
               0.01 * (double)(w[45] - w[40]), 0.01 * (double)(w[46] - w[40]), 0.01 * (double)(w[47] - w[40]));
   }
   (void)hipFree(ctx->tail_sync);
+  (void)hipFree(ctx->bpartials);
+  if (ctx->bslot) (void)hipHostFree(ctx->bslot);
   if (getenv("ABFT_HIP_VERBOSE") && (ctx->spec.commits || ctx->spec.drops))
     fprintf(stderr, "hip: speculated iterations: %ld taken over, %ld dropped\n", ctx->spec.commits, ctx->spec.drops);
   for (double *b : ctx->spec.shadow) (void)hipFree(b);
@@ -951,7 +957,7 @@ static int finish_slice(abft_hip_matrix *m, const SliceBuild &sb, uint32_t waves
 
 static int create_csr(abft_hip_ctx *ctx, int mode, const uint32_t *columns, const uint32_t *rows,
                       const double *values, int n_out, int n_in, int nnz, uint32_t index_base,
-                      abft_hip_matrix **out) {
+                      abft_hip_matrix **out, bool force_stream) {
   // validate: a bad index must fail here, loudly, not fault a kernel later
   for (int i = 0; i < nnz; i++) {
     if (rows[i] >= (uint32_t)n_out)
@@ -990,12 +996,12 @@ static int create_csr(abft_hip_ctx *ctx, int mode, const uint32_t *columns, cons
   // ---- (ABFT_HIP_LAYOUT=panels: its chunked-launch predecessor, kept for A/B runs) ----
   SliceBuild lb;
   auto slice_waves = [&](uint32_t lg) { return (uint64_t)spmv_slice_blocks_per_cu(mode, lg) * 4u * (uint64_t)ctx->num_cus; };
-  const bool slice = plan_slice(mode, columns, rows, n_out, n_in, nnz, slice_waves, lb);
+  const bool slice = !force_stream && plan_slice(mode, columns, rows, n_out, n_in, nnz, slice_waves, lb);
   SweepBuild sb;
   auto cap = [&](int rpt) { return (uint64_t)spmv_sweep_blocks_per_cu(mode, rpt) * (uint64_t)ctx->num_cus; };
-  const bool sweep = !slice && plan_sweep(mode, columns, rows, n_out, n_in, nnz, cap, sb);
+  const bool sweep = !force_stream && !slice && plan_sweep(mode, columns, rows, n_out, n_in, nnz, cap, sb);
   PanelBuild pb;
-  const bool panels = !slice && !sweep && plan_panels(mode, columns, rows, n_out, n_in, nnz, pb);
+  const bool panels = !force_stream && !slice && !sweep && plan_panels(mode, columns, rows, n_out, n_in, nnz, pb);
   if (slice) {
     std::vector<uint32_t> pcols((size_t)nnz);
     std::vector<double> pvals((size_t)nnz);
@@ -1201,7 +1207,7 @@ static int create_coo(abft_hip_ctx *ctx, int mode, const uint32_t *columns, cons
 
 static int create_any(abft_hip_ctx *ctx, int format, int mode, const uint32_t *columns,
                       const uint32_t *rows, const double *values, int n_out, int n_in, int nnz,
-                      uint32_t index_base, abft_hip_matrix **out) {
+                      uint32_t index_base, abft_hip_matrix **out, bool force_stream = false) {
   if (int rc = bind(ctx)) return rc;
   if (!out) return set_err(ABFT_ERR_INVALID, "null out");
   *out = nullptr;
@@ -1209,7 +1215,7 @@ static int create_any(abft_hip_ctx *ctx, int format, int mode, const uint32_t *c
   if (n_out < 0 || n_in < 0 || nnz < 0) return set_err(ABFT_ERR_INVALID, "negative size");
   if (nnz && (!columns || !rows || !values)) return set_err(ABFT_ERR_INVALID, "null input array");
   int rc;
-  if (format == ABFT_FMT_CSR) rc = create_csr(ctx, mode, columns, rows, values, n_out, n_in, nnz, index_base, out);
+  if (format == ABFT_FMT_CSR) rc = create_csr(ctx, mode, columns, rows, values, n_out, n_in, nnz, index_base, out, force_stream);
   else if (format == ABFT_FMT_COO) rc = create_coo(ctx, mode, columns, rows, values, n_out, n_in, nnz, index_base, out);
   else return set_err(ABFT_ERR_INVALID, "unknown format %d", format);
   if (rc != ABFT_OK) return rc;
@@ -1274,6 +1280,12 @@ extern "C" int abft_hip_matrix_create_csr(abft_hip_ctx *ctx, int mode, const uin
                                           const uint32_t *rows, const double *values, int N, int nnz,
                                           abft_hip_matrix **mat) {
   return create_any(ctx, ABFT_FMT_CSR, mode, columns, rows, values, N, N, nnz, 0, mat);
+}
+
+extern "C" int abft_hip_matrix_create_csr_stream(abft_hip_ctx *ctx, int mode, const uint32_t *columns,
+                                                 const uint32_t *rows, const double *values, int N, int nnz,
+                                                 abft_hip_matrix **mat) {
+  return create_any(ctx, ABFT_FMT_CSR, mode, columns, rows, values, N, N, nnz, 0, mat, true);
 }
 
 extern "C" int abft_hip_matrix_create_coo(abft_hip_ctx *ctx, int mode, const uint32_t *columns,
@@ -1559,15 +1571,14 @@ static ReduceOut reduce_out(abft_hip_ctx *ctx, double *dev_out, bool to_host) {
 // result in the pinned slot.  Polling the slot costs a couple of microseconds
 // once the value lands; hipStreamSynchronize costs tens.  The stream is queried
 // now and then so that a failed kernel ends the wait with an error instead of a hang.
-static int scalar_from_host_slot(abft_hip_ctx *ctx, uint32_t seq, double *result) {
-  HostSlot *slot = ctx->host_slot + (seq % ABFT_HOST_SLOTS);
+static int wait_published(abft_hip_ctx *ctx, const uint32_t *slot_seq, uint32_t seq) {
   if (!ctx->spin_wait) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
   } else {
     for (;;) {
       bool ready = false;
       for (int i = 0; i < 4096 && !ready; i++) {
-        ready = __atomic_load_n(&slot->seq, __ATOMIC_ACQUIRE) == seq;
+        ready = __atomic_load_n(slot_seq, __ATOMIC_ACQUIRE) == seq;
         if (!ready) __builtin_ia32_pause();
       }
       if (ready) break;
@@ -1577,9 +1588,15 @@ static int scalar_from_host_slot(abft_hip_ctx *ctx, uint32_t seq, double *result
         return set_err(ABFT_ERR_HIP, "stream failed while waiting for a reduction: %s", hipGetErrorString(q));
     }
   }
-  if (__atomic_load_n(&slot->seq, __ATOMIC_ACQUIRE) != seq)
-    return set_err(ABFT_ERR_HIP, "reduction %u finished without publishing its result (slot holds %u)", seq,
-                   slot->seq);
+  const uint32_t got = __atomic_load_n(slot_seq, __ATOMIC_ACQUIRE);
+  if (got != seq)
+    return set_err(ABFT_ERR_HIP, "reduction %u finished without publishing its result (slot holds %u)", seq, got);
+  return ABFT_OK;
+}
+
+static int scalar_from_host_slot(abft_hip_ctx *ctx, uint32_t seq, double *result) {
+  HostSlot *slot = ctx->host_slot + (seq % ABFT_HOST_SLOTS);
+  if (int rc = wait_published(ctx, &slot->seq, seq)) return rc;
   *result = slot->value;
   return ABFT_OK;
 }
@@ -2464,6 +2481,136 @@ extern "C" int abft_hip_spmv_dot_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, co
   return spmv_common(ctx, mat, vec, result, vec_offset, dev_result);
 }
 
+// ---- block right-hand sides: K vectors per pass, as one row-major block vector of N * K entries ----
+
+// the block vectors of one call: k in range, every length N * k, 16-byte aligned where k is even
+// (the kernels move pairs of entries)
+static int check_block(const char *what, int k, int N, std::initializer_list<const abft_hip_vector *> vs) {
+  if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "%s: k = %d outside [1, %d]", what, k, ABFT_MAX_RHS);
+  if (N < 0 || (int64_t)N * k >= ((int64_t)1 << 31))
+    return set_err(ABFT_ERR_INVALID, "%s: %d rows x %d columns does not fit a block vector", what, N, k);
+  for (const abft_hip_vector *v : vs) {
+    if (!v) return set_err(ABFT_ERR_INVALID, "%s: null vector", what);
+    if ((int64_t)v->n != (int64_t)N * k)
+      return set_err(ABFT_ERR_INVALID, "%s: a vector of length %d is not a block of %d rows x %d columns", what, v->n,
+                     N, k);
+    if (k % 2 == 0 && ((uintptr_t)v->d & 15u))
+      return set_err(ABFT_ERR_INVALID, "%s: a block vector with an even k must start 16-byte aligned (a view at an "
+                     "odd offset does not)", what);
+  }
+  return ABFT_OK;
+}
+
+// the prologue of every block call: what abft_hip_spmv / abft_hip_dot start with (a pending x update
+// applied, a speculation voided), and -- since block calls write vectors the single calls' caches
+// may name -- the fused product and the learned iteration forgotten
+static int bind_block(abft_hip_ctx *ctx) {
+  if (int rc = bind(ctx)) return rc;
+  ctx->fused.valid = false;
+  spec_forget(ctx);
+  return ABFT_OK;
+}
+
+static int block_slot(abft_hip_ctx *ctx) {
+  if (ctx->bslot) return ABFT_OK;
+  HIPCHK(hipMalloc((void **)&ctx->bpartials, (size_t)ABFT_MAX_RHS * ABFT_MAX_PARTIALS * sizeof(double)));
+  HIPCHK(hipHostMalloc((void **)&ctx->bslot, sizeof(HostSlotK), hipHostMallocMapped | hipHostMallocCoherent));
+  memset(ctx->bslot, 0, sizeof(HostSlotK));
+  HIPCHK(hipHostGetDevicePointer((void **)&ctx->bslot_dev, ctx->bslot, 0));
+  return ABFT_OK;
+}
+
+static ReduceOutK reduce_out_k(abft_hip_ctx *ctx) {
+  ReduceOutK o{};
+  o.partials = ctx->bpartials;
+  o.ticket = ctx->ticket;
+  o.host = ctx->bslot_dev;
+  o.ev_count = ctx->ring.count;
+  o.seq = ++ctx->bseq;
+  return o;
+}
+
+// one device-to-host read for all k results
+static int results_from_block_slot(abft_hip_ctx *ctx, uint32_t seq, int k, double *out) {
+  if (int rc = wait_published(ctx, &ctx->bslot->seq, seq)) return rc;
+  for (int j = 0; j < k; j++) out[j] = ctx->bslot->value[j];
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_spmm(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *X, abft_hip_vector *Y,
+                             int k) {
+  if (int rc = bind_block(ctx)) return rc;
+  if (!mat || !X || !Y) return set_err(ABFT_ERR_INVALID, "spmm: null argument");
+  if (mat->fmt != ABFT_FMT_CSR)
+    return set_err(ABFT_ERR_INVALID, "spmm: COO matrices have no block SpMV; create the matrix as CSR with "
+                   "abft_hip_matrix_create_csr_stream");
+  if (mat->use_panels || mat->use_sweep || mat->use_slice)
+    return set_err(ABFT_ERR_INVALID, "spmm: the matrix is stored in the %s layout; the block SpMV runs on the "
+                   "streaming row-block layout: create the matrix with abft_hip_matrix_create_csr_stream",
+                   mat->use_slice ? "slice" : mat->use_sweep ? "sweep" : "panel");
+  if (mat->csr.n_in != mat->csr.n_out || mat->csr.index_base != 0 || mat->csr.gidx)
+    return set_err(ABFT_ERR_INVALID, "spmm: the matrix is a shard; the block SpMV takes a whole square matrix");
+  const int N = (int)mat->csr.n_out;
+  if (int rc = check_block("spmm", k, N, {X, Y})) return rc;
+  if (!disjoint(X, Y)) return set_err(ABFT_ERR_INVALID, "spmm: input and output overlap");
+  if (k == 1) return spmv_common(ctx, mat, X, Y, 0, nullptr);  // the single kernel, fused product and all
+  KernelTimer t(ctx, ABFT_K_SPMV);
+  HIPCHK(launch_spmm_csr(mat->mode, k, mat->csr, X->d, Y->d, ctx->ring, ctx->stream));
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_dot_block(abft_hip_ctx *ctx, const abft_hip_vector *a, const abft_hip_vector *b, int k,
+                                  double *out) {
+  if (int rc = bind_block(ctx)) return rc;
+  if (!a || !b || !out) return set_err(ABFT_ERR_INVALID, "dot_block: null argument");
+  if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "dot_block: k = %d outside [1, %d]", k, ABFT_MAX_RHS);
+  const int N = a->n / k;
+  if (int rc = check_block("dot_block", k, N, {a, b})) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_dot_block(a->d, b->d, N, k, o, ctx->stream));
+  }
+  return results_from_block_slot(ctx, o.seq, k, out);
+}
+
+extern "C" int abft_hip_calc_xr_block(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r,
+                                      const abft_hip_vector *p, const abft_hip_vector *w, int k, const double *alpha,
+                                      uint32_t active, double *rr_out) {
+  if (int rc = bind_block(ctx)) return rc;
+  if (!x || !r || !p || !w || !alpha || !rr_out) return set_err(ABFT_ERR_INVALID, "calc_xr_block: null argument");
+  if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "calc_xr_block: k = %d outside [1, %d]", k, ABFT_MAX_RHS);
+  const int N = x->n / k;
+  if (int rc = check_block("calc_xr_block", k, N, {x, r, p, w})) return rc;
+  if (!disjoint(x, r) || !disjoint(x, p) || !disjoint(x, w) || !disjoint(r, p) || !disjoint(r, w))
+    return set_err(ABFT_ERR_INVALID, "calc_xr_block: x and r must not overlap each other or p, w");
+  if (int rc = block_slot(ctx)) return rc;
+  BlockScalars a{};
+  for (int j = 0; j < k; j++) a.v[j] = alpha[j];
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_xr_block(x->d, r->d, p->d, w->d, N, k, a, active, o, ctx->stream));
+  }
+  return results_from_block_slot(ctx, o.seq, k, rr_out);
+}
+
+extern "C" int abft_hip_calc_p_block(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, int k,
+                                     const double *beta, uint32_t active) {
+  if (int rc = bind_block(ctx)) return rc;
+  if (!p || !r || !beta) return set_err(ABFT_ERR_INVALID, "calc_p_block: null argument");
+  if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "calc_p_block: k = %d outside [1, %d]", k, ABFT_MAX_RHS);
+  const int N = p->n / k;
+  if (int rc = check_block("calc_p_block", k, N, {p, r})) return rc;
+  if (!disjoint(p, r)) return set_err(ABFT_ERR_INVALID, "calc_p_block: p and r overlap");
+  BlockScalars b{};
+  for (int j = 0; j < k; j++) b.v[j] = beta[j];
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_p_block(p->d, r->d, N, k, b, active, ctx->stream));
+  return ABFT_OK;
+}
+
 extern "C" int abft_hip_matrix_panels(abft_hip_matrix *mat, int *npanels, int *width) {
   if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
   if (npanels) *npanels = mat->use_sweep ? (int)mat->sweep.npanels : mat->use_slice ? (int)mat->slice.npanels : 1;
@@ -2692,10 +2839,12 @@ extern "C" int abft_hip_pending_events(abft_hip_ctx *ctx) {
   uint32_t n = 0;
   if (ctx)
     for (uint32_t k = 0; k < ABFT_HOST_SLOTS; k++) n = std::max(n, ctx->host_slot[k].evcount);
+  if (ctx && ctx->bslot) n = std::max(n, ctx->bslot->evcount);
   return (int)n;
 }
 static void clear_pending_events(abft_hip_ctx *ctx) {
   for (uint32_t k = 0; k < ABFT_HOST_SLOTS; k++) ctx->host_slot[k].evcount = 0;
+  if (ctx->bslot) ctx->bslot->evcount = 0;
 }
 
 extern "C" int abft_hip_drain_events(abft_hip_ctx *ctx, abft_event *buf, int cap, int *count, int *fatal) {

@@ -377,6 +377,33 @@ hipError_t launch_calc_px(double *p, const double *r, double *x, double beta, co
                           double alpha, const double *alpha_ptr, int n, hipStream_t s, double *p_out = nullptr,
                           double *x_out = nullptr);
 hipError_t launch_axpy(double *x, const double *p, double alpha, const double *alpha_ptr, int n, hipStream_t s);
+
+// ---- block right-hand sides (abft_hip_spmm and the *_block vector calls; 1 <= K <= 8) ----
+#define ABFT_MAX_RHS 8
+// the K-wide form of HostSlot: K results of one reduction, published by `seq`
+struct HostSlotK {
+  double value[ABFT_MAX_RHS];
+  uint32_t evcount;
+  uint32_t seq;
+};
+struct ReduceOutK {
+  double *partials;          // ABFT_MAX_RHS * ABFT_MAX_PARTIALS doubles: column j's block partials at j * ABFT_MAX_PARTIALS
+  uint32_t *ticket;          // as ReduceOut::ticket
+  HostSlotK *host;           // device alias of the pinned slot
+  const uint32_t *ev_count;
+  uint32_t seq;
+};
+struct BlockScalars {
+  double v[ABFT_MAX_RHS];
+};
+// Y = A X on the streaming row-block CSR layout, k in [2, 8] (k = 1 is launch_spmv_csr)
+hipError_t launch_spmm_csr(int mode, int k, const CsrDev &A, const double *x, double *y, EventRing ev, hipStream_t s);
+// n = rows of the block vectors (n * k doubles each)
+hipError_t launch_dot_block(const double *a, const double *b, int n, int k, const ReduceOutK &out, hipStream_t s);
+hipError_t launch_calc_xr_block(double *x, double *r, const double *p, const double *w, int n, int k,
+                                const BlockScalars &alpha, uint32_t active, const ReduceOutK &out, hipStream_t s);
+hipError_t launch_calc_p_block(double *p, const double *r, int n, int k, const BlockScalars &beta, uint32_t active,
+                               hipStream_t s);
 hipError_t launch_publish_pair(const double *pair, HostSlot *host, uint32_t seq, hipStream_t s);
 
 // window exchange over shared host memory (see kernels.hip, peer_exchange_kernel): a 4 KB header

@@ -547,6 +547,30 @@ __device__ __forceinline__ void csr_stage(const CsrDev &A, const double *__restr
   csr_consume<MODE, EPT>(A, x, ev, base, lo, hi, t, s_prod, s_col, false, 0u, 0u, unused);
 }
 
+// Constraints mode: the reference's two checks of element i (CSR/CPUContext.cpp:186-200) on
+// the staged columns -- its column against the vector's size, then against its row successor's
+// (read from the matrix when element i is the last one staged).  Returns false if a fatal event
+// was queued.  (csr_row_sum and the block SpMV, spmm_row_sum, run the same checks.)
+__device__ __forceinline__ bool csr_check_element(const CsrDev &A, const EventRing &ev, uint32_t base, uint32_t i,
+                                                  uint32_t re, uint32_t row_end, const uint32_t *s_col,
+                                                  uint32_t row) {
+  const uint32_t k = i - base;
+  const uint32_t col = s_col[k];
+  if (col >= A.n_in) {
+    push_event(ev, ABFT_EV_COL_SIZE, A.index_base + i, row, FMT_CSR);  // `bit` = row: the drain's sort key
+    return false;
+  }
+  if (i + 1u < row_end) {
+    // the next column is in the tile unless this is the last staged element
+    const uint32_t nxt = (i + 1u < re) ? s_col[k + 1u] : A.cols[i + 1u];
+    if (nxt <= col) {
+      push_event(ev, ABFT_EV_COL_ORDER, A.index_base + i, row, FMT_CSR);
+      return false;
+    }
+  }
+  return true;
+}
+
 // Sum one row from the staged products, in ascending element order.  In
 // constraints mode also runs the reference's structural checks in that order
 // (CSR/CPUContext.cpp:186-200).  Returns false if a fatal event was queued.
@@ -582,21 +606,8 @@ __device__ __forceinline__ bool csr_row_sum(const CsrDev &A, const EventRing &ev
     return true;
   }
   for (uint32_t i = rs; i < re; i++) {
-    const uint32_t k = i - base;
-    const uint32_t col = s_col[k];
-    if (col >= A.n_in) {
-      push_event(ev, ABFT_EV_COL_SIZE, A.index_base + i, row, FMT_CSR);  // `bit` = row: the drain's sort key
-      return false;
-    }
-    if (i + 1u < row_end) {
-      // the next column is in the tile unless this is the last staged element
-      const uint32_t nxt = (i + 1u < re) ? s_col[k + 1u] : A.cols[i + 1u];
-      if (nxt <= col) {
-        push_event(ev, ABFT_EV_COL_ORDER, A.index_base + i, row, FMT_CSR);
-        return false;
-      }
-    }
-    acc += s_prod[k];
+    if (!csr_check_element(A, ev, base, i, re, row_end, s_col, row)) return false;
+    acc += s_prod[i - base];
   }
   return true;
 }
@@ -840,6 +851,246 @@ hipError_t launch_spmv_csr(int mode, const CsrDev &A, const TileSpan &span, cons
     case MODE_SEC7: return launch_spmv_csr_mode<MODE_SEC7>(A, span, x, y, ev, fuse, s);
     case MODE_SEC8: return launch_spmv_csr_mode<MODE_SEC8>(A, span, x, y, ev, fuse, s);
     case MODE_SECDED: return launch_spmv_csr_mode<MODE_SECDED>(A, span, x, y, ev, fuse, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// ------------------------------------------------------- CSR block SpMV (SpMM) --
+// Y = A X for K right-hand sides at once (2 <= K <= 8; K = 1 is abft_hip_spmv).  A block
+// vector is row-major: entry (i, j) at i*K + j, so the K entries a matrix element multiplies
+// sit in one 8K-byte run.  Same row blocks and the same branch-free coalesced load phase
+// (csr_issue_loads) as spmv_csr_kernel, so every element is loaded and ECC-checked ONCE per
+// pass whatever K is; what goes to LDS is the CHECKED element -- its value and column, 12 B --
+// not K products (TILE * K doubles would be 64 KB at K = 8).  Phase 2 gives each row to one
+// thread, which gathers the K-wide rows of X (16-byte loads) and keeps K running sums, each
+// added in ascending element order with separate multiply and add: column j of Y is the
+// bits abft_hip_spmv gives for column j of X.  The cases spmv_csr_kernel stages a special
+// product for, staged here so that value * x is that product for every column:
+//   element outside the tile range  -> never summed (the rows' ranges exclude it)
+//   fatal element (given up)        -> value +0.0, column ~0u: +0.0 * 0.0 = +0.0, as staged there
+//   column >= n_in (mode none)      -> x taken as 0.0: value * 0.0, as there
+#define SPMM_NO_COL 0xffffffffu
+
+// ECC check of a tile whose loads were issued into `t`; the checked elements -> LDS.
+// The cold path (repair + write-back, or give up) runs once per element per pass.
+template <int MODE, int EPT>
+__device__ __forceinline__ void spmm_stage(const CsrDev &A, const EventRing &ev, uint32_t base, uint32_t lo,
+                                           uint32_t hi, double *s_val, uint32_t *s_col) {
+  constexpr int STEPS = EPT / 2;
+  CsrTileRegs<EPT> t;
+  csr_issue_loads<EPT>(A, base, hi, t);
+  uint32_t col[EPT];
+  double val[EPT];
+  uint32_t bad = 0u;
+#pragma unroll
+  for (int j = 0; j < EPT; j++) {
+    const int s = j >> 1;
+    const uint32_t i = base + 2u * threadIdx.x + (uint32_t)s * (2u * ABFT_BLOCK) + (uint32_t)(j & 1);
+    const double d = (j & 1) ? t.v[s].y : t.v[s].x;
+    uint32_t w[3] = {(uint32_t)__double2loint(d), (uint32_t)__double2hiint(d), (j & 1) ? t.c[s].y : t.c[s].x};
+    const bool valid = i >= lo && i < hi;
+    if (MODE >= MODE_SED) {
+      if (valid && ecc_suspect<FMT_CSR, MODE>(w) != 0) bad |= 1u << j;
+      w[2] &= ABFT_COLMASK;  // reference CSR/CPUContext.cpp:238, 282, 338, 404
+    }
+    col[j] = valid ? w[2] : SPMM_NO_COL;
+    val[j] = valid ? as_double(w[0], w[1]) : 0.0;
+  }
+#pragma unroll
+  for (int s = 0; s < STEPS; s++) {
+    const uint32_t k = 2u * threadIdx.x + (uint32_t)s * (2u * ABFT_BLOCK);
+    *reinterpret_cast<double2 *>(s_val + k) = make_double2(val[2 * s], val[2 * s + 1]);
+    *reinterpret_cast<uint2 *>(s_col + k) = make_uint2(col[2 * s], col[2 * s + 1]);
+  }
+  if (MODE >= MODE_SED && __builtin_expect(bad != 0u, 0)) {
+    // as in csr_consume: the noted elements again, from memory, through the cold path
+#pragma unroll 1
+    for (uint32_t j = 0; j < (uint32_t)EPT; j++) {
+      if (!((bad >> j) & 1u)) continue;
+      const uint32_t i = base + 2u * threadIdx.x + (j >> 1) * (2u * ABFT_BLOCK) + (j & 1u);
+      const double d = A.vals[i];
+      EccWords<FMT_CSR> e;
+      e.w[0] = (uint32_t)__double2loint(d); e.w[1] = (uint32_t)__double2hiint(d); e.w[2] = A.cols[i]; e.rc = 0;
+      e = ecc_cold<FMT_CSR, MODE>(e, event_index(A, i), ev);
+      double v = 0.0;
+      uint32_t c = SPMM_NO_COL;
+      if (e.rc > 0) {
+        A.vals[i] = as_double(e.w[0], e.w[1]);
+        A.cols[i] = e.w[2];
+        v = as_double(e.w[0], e.w[1]);
+        c = e.w[2] & ABFT_COLMASK;
+      }
+      s_val[i - base] = v;
+      s_col[i - base] = c;
+    }
+  }
+}
+
+// the K entries of row c of a block vector (0.0 for a column past the vector: x taken as 0)
+template <int K>
+__device__ __forceinline__ void spmm_gather(const double *__restrict__ x, uint32_t c, uint32_t n_in, double *xv) {
+  const bool in = c < n_in;  // a corrupted index must never fault the GPU
+  const double *p = x + (size_t)(in ? c : 0u) * K;
+  if (K % 2 == 0) {
+#pragma unroll
+    for (int j = 0; j < K; j += 2) {
+      const double2 v = *reinterpret_cast<const double2 *>(p + j);
+      xv[j] = in ? v.x : 0.0;
+      xv[j + 1] = in ? v.y : 0.0;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < K; j++) xv[j] = in ? p[j] : 0.0;
+  }
+}
+
+// Row sums of elements [rs, re) from the staged elements, K columns, ascending element order.
+// Constraints mode runs csr_row_sum's checks (csr_check_element) in the same order, so the
+// same events are queued; returns false if a fatal one was.
+template <int MODE, int K>
+__device__ __forceinline__ bool spmm_row_sum(const CsrDev &A, const EventRing &ev, const double *__restrict__ x,
+                                             uint32_t base, uint32_t rs, uint32_t re, uint32_t row_end,
+                                             const double *s_val, const uint32_t *s_col, double *acc,
+                                             uint32_t row) {
+  if (MODE == MODE_CONSTRAINTS) {
+    for (uint32_t i = rs; i < re; i++) {
+      if (!csr_check_element(A, ev, base, i, re, row_end, s_col, row)) return false;
+      double xv[K];
+      spmm_gather<K>(x, s_col[i - base], A.n_in, xv);
+      const double v = s_val[i - base];
+#pragma unroll
+      for (int j = 0; j < K; j++) acc[j] += v * xv[j];
+    }
+    return true;
+  }
+  // U elements' gathers in flight, then their adds in element order; a lane past its row's end
+  // re-reads its last slot and skips the add (no "+ 0.0": that could turn a -0.0 sum into +0.0)
+  constexpr int U = K <= 4 ? 4 : 2;
+  for (uint32_t i = rs; i < re; i += U) {
+    const uint32_t k = i - base, last = re - 1u - base;
+    double v[U], xv[U][K];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const uint32_t ku = min(k + (uint32_t)u, last);
+      v[u] = s_val[ku];
+      spmm_gather<K>(x, s_col[ku], A.n_in, xv[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      if (u == 0 || i + (uint32_t)u < re) {
+#pragma unroll
+        for (int j = 0; j < K; j++) acc[j] += v[u] * xv[u][j];
+      }
+    }
+  }
+  return true;
+}
+
+template <int K>
+__device__ __forceinline__ void spmm_store_row(double *__restrict__ y, uint32_t row, const double *acc) {
+  double *p = y + (size_t)row * K;
+  if (K % 2 == 0) {
+#pragma unroll
+    for (int j = 0; j < K; j += 2) *reinterpret_cast<double2 *>(p + j) = make_double2(acc[j], acc[j + 1]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < K; j++) p[j] = acc[j];
+  }
+}
+
+// The block form of spmv_csr_kernel, whole matrix (reference lines as there).
+template <int MODE, int EPT, int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void spmm_csr_kernel(CsrDev A, const double *__restrict__ x,
+                                                              double *__restrict__ y, EventRing ev) {
+  constexpr uint32_t TILE = ABFT_BLOCK * EPT;
+  __shared__ __attribute__((aligned(16))) double s_val[TILE];
+  __shared__ __attribute__((aligned(16))) uint32_t s_col[TILE];
+  const uint32_t t = xcd_tile(blockIdx.x, A.nblk);
+  const uint4 desc = A.blk[t];
+  const bool uniform = ABFT_CFG_UNIFORM_ROWS && MODE != MODE_CONSTRAINTS && (desc.y >> 31) != 0u;
+  const uint32_t row0 = desc.x, row1 = desc.y & 0x7fffffffu, e0 = desc.z, e1 = desc.w;
+  const uint32_t base = e0 & ~1u;
+
+  if (e1 >= e0 && e1 - base <= TILE) {
+    const uint32_t r = row0 + threadIdx.x;
+    uint32_t rs = 0, re = 0;
+    if (r < row1) {
+      if (uniform) {
+        const uint32_t len = (e1 - e0) / (row1 - row0);
+        rs = e0 + len * threadIdx.x; re = rs + len;
+      } else {
+        rs = A.rowptr[r]; re = A.rowptr[r + 1];
+      }
+    }
+    spmm_stage<MODE, EPT>(A, ev, base, e0, e1, s_val, s_col);
+    __syncthreads();
+    for (uint32_t row = r; row < row1; row += ABFT_BLOCK) {
+      if (row != r) { rs = A.rowptr[row]; re = A.rowptr[row + 1]; }
+      if (MODE == MODE_CONSTRAINTS) {  // reference CSR/CPUContext.cpp:173-182
+        if (re > A.nnz) { push_event(ev, ABFT_EV_ROW_SIZE, row, row, FMT_CSR); continue; }
+        if (re < rs) { push_event(ev, ABFT_EV_ROW_ORDER, row, row, FMT_CSR); continue; }
+      }
+      if (rs < e0 || re > e1 || re < rs) continue;  // inconsistent row pointers: never touch LDS out of range
+      double acc[K];
+#pragma unroll
+      for (int j = 0; j < K; j++) acc[j] = 0.0;
+      if (spmm_row_sum<MODE, K>(A, ev, x, base, rs, re, re, s_val, s_col, acc, row)) spmm_store_row<K>(y, row, acc);
+    }
+  } else {
+    // long row (or inconsistent pointers): rows of this block one at a time, tile by tile, the K
+    // running sums carried by thread 0
+    for (uint32_t row = row0; row < row1; row++) {
+      const uint32_t rs = A.rowptr[row], re = A.rowptr[row + 1];
+      if (MODE == MODE_CONSTRAINTS) {
+        if (re > A.nnz) { if (threadIdx.x == 0) push_event(ev, ABFT_EV_ROW_SIZE, row, row, FMT_CSR); continue; }
+        if (re < rs) { if (threadIdx.x == 0) push_event(ev, ABFT_EV_ROW_ORDER, row, row, FMT_CSR); continue; }
+      }
+      if (re > A.nnz || re < rs) continue;
+      double acc[K];
+#pragma unroll
+      for (int j = 0; j < K; j++) acc[j] = 0.0;
+      bool ok = true;
+      for (uint32_t lo = rs; lo < re;) {
+        const uint32_t b = lo & ~1u;
+        const uint32_t hi = min(re, b + TILE);
+        __syncthreads();
+        spmm_stage<MODE, EPT>(A, ev, b, lo, hi, s_val, s_col);
+        __syncthreads();
+        if (threadIdx.x == 0 && ok) ok = spmm_row_sum<MODE, K>(A, ev, x, b, lo, hi, re, s_val, s_col, acc, row);
+        lo = hi;
+      }
+      if (threadIdx.x == 0 && ok) spmm_store_row<K>(y, row, acc);
+    }
+  }
+}
+
+template <int MODE>
+static hipError_t launch_spmm_csr_mode(int k, const CsrDev &A, const double *x, double *y, EventRing ev,
+                                       hipStream_t s) {
+  const dim3 g(A.nblk), b(ABFT_BLOCK);
+  switch (k) {
+    case 2: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 2>), g, b, 0, s, A, x, y, ev); break;
+    case 3: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 3>), g, b, 0, s, A, x, y, ev); break;
+    case 4: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 4>), g, b, 0, s, A, x, y, ev); break;
+    case 5: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 5>), g, b, 0, s, A, x, y, ev); break;
+    case 6: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 6>), g, b, 0, s, A, x, y, ev); break;
+    case 7: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 7>), g, b, 0, s, A, x, y, ev); break;
+    case 8: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 8>), g, b, 0, s, A, x, y, ev); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_spmm_csr(int mode, int k, const CsrDev &A, const double *x, double *y, EventRing ev,
+                           hipStream_t s) {
+  if (A.nblk == 0) return hipSuccess;
+  switch (mode) {
+    case MODE_NONE: return launch_spmm_csr_mode<MODE_NONE>(k, A, x, y, ev, s);
+    case MODE_CONSTRAINTS: return launch_spmm_csr_mode<MODE_CONSTRAINTS>(k, A, x, y, ev, s);
+    case MODE_SED: return launch_spmm_csr_mode<MODE_SED>(k, A, x, y, ev, s);
+    case MODE_SEC7: return launch_spmm_csr_mode<MODE_SEC7>(k, A, x, y, ev, s);
+    case MODE_SEC8: return launch_spmm_csr_mode<MODE_SEC8>(k, A, x, y, ev, s);
+    case MODE_SECDED: return launch_spmm_csr_mode<MODE_SECDED>(k, A, x, y, ev, s);
     default: return hipErrorInvalidValue;
   }
 }
@@ -2771,26 +3022,31 @@ int reduce_blocks(int n) {
 // (s_waitcnt vmcnt(0)) before its relaxed agent-scope ticket add; only the last
 // arriver pays one agent-scope acquire, drained before the workgroup barrier
 // that lets the other lanes read the partials (with sc1 loads).
+// The arrival itself (thread 0, its partials already drained): 1 for the block that arrives last.
+__device__ __forceinline__ uint32_t reduce_take_ticket(uint32_t *ticket) {
+  // two-level arrival: atomics on one address retire one per ~12 ns, so 2048
+  // blocks on a single counter cost ~25 us; 32 per group counter (the groups run
+  // in parallel) and one top-level add per group cost ~1 us
+  const uint32_t g = blockIdx.x / ABFT_TICKET_GROUP, ngroups = (gridDim.x + ABFT_TICKET_GROUP - 1u) / ABFT_TICKET_GROUP;
+  const uint32_t gsize = min((uint32_t)ABFT_TICKET_GROUP, gridDim.x - g * ABFT_TICKET_GROUP);
+  uint32_t last = 0u;
+  if (__hip_atomic_fetch_add(ticket + 1u + g, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1u) {
+    __hip_atomic_store(ticket + 1u + g, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ngroups - 1u ? 1u : 0u;
+  }
+  if (last) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  return last;
+}
+
 __device__ __forceinline__ void reduce_finish(double block_value, const ReduceOut &o, double *s_w) {
   __shared__ uint32_t s_last;
   if (threadIdx.x == 0) {
     __hip_atomic_store(o.partials + blockIdx.x, block_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // two-level arrival: atomics on one address retire one per ~12 ns, so 2048
-    // blocks on a single counter cost ~25 us; 32 per group counter (the groups run
-    // in parallel) and one top-level add per group cost ~1 us
-    const uint32_t g = blockIdx.x / ABFT_TICKET_GROUP, ngroups = (gridDim.x + ABFT_TICKET_GROUP - 1u) / ABFT_TICKET_GROUP;
-    const uint32_t gsize = min((uint32_t)ABFT_TICKET_GROUP, gridDim.x - g * ABFT_TICKET_GROUP);
-    uint32_t last = 0u;
-    if (__hip_atomic_fetch_add(o.ticket + 1u + g, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1u) {
-      __hip_atomic_store(o.ticket + 1u + g, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last = __hip_atomic_fetch_add(o.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ngroups - 1u ? 1u : 0u;
-    }
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    s_last = last;
+    s_last = reduce_take_ticket(o.ticket);
   }
   __syncthreads();
   if (!s_last) return;
@@ -3121,6 +3377,184 @@ hipError_t launch_axpy(double *x, const double *p, double alpha, const double *a
     hipLaunchKernelGGL(axpy_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, alpha, alpha_ptr, n);
   else
     hipLaunchKernelGGL(axpy_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, alpha, alpha_ptr, n);
+  return hipGetLastError();
+}
+
+// ---- block vectors (K right-hand sides, row-major: entry (i, j) at i*K + j) ----
+// One thread per row i walks rows exactly as the single kernels' threads walk elements (grid
+// reduce_blocks(n rows)); per column the same operations with the same roundings, so an active
+// column's elements are the bits calc_xr_kernel / calc_p_kernel give for it.  A column whose bit
+// is clear in `active` is written back with the bits it was read with (a select, never an
+// arithmetic operation: inf and NaN payloads survive).  The K reductions have ONE shape: per
+// thread a serial sum over its rows, block_sum, then the last-arriving block's fixed-order fold
+// of the block partials -- so scaling a column by a power of two scales its sum by the same
+// power exactly.  Results: K doubles + the queued-event count in a K-wide pinned slot.
+template <int K>
+__device__ __forceinline__ void block_load(const double *p, double *v) {
+  if (K % 2 == 0) {
+#pragma unroll
+    for (int j = 0; j < K; j += 2) {
+      const double2 t = *reinterpret_cast<const double2 *>(p + j);
+      v[j] = t.x; v[j + 1] = t.y;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < K; j++) v[j] = p[j];
+  }
+}
+
+template <int K>
+__device__ __forceinline__ void block_store(double *p, const double *v) {
+  if (K % 2 == 0) {
+#pragma unroll
+    for (int j = 0; j < K; j += 2) *reinterpret_cast<double2 *>(p + j) = make_double2(v[j], v[j + 1]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < K; j++) p[j] = v[j];
+  }
+}
+
+// reduce_finish for K values: K partials per block, one ticket, K fixed-order folds
+template <int K>
+__device__ __forceinline__ void reduce_finish_k(const double *value, const ReduceOutK &o, double *s_w) {
+  __shared__ uint32_t s_last;
+  double bv[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) bv[j] = block_sum(value[j], s_w + 4 * j);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < K; j++)
+      __hip_atomic_store(o.partials + (size_t)j * ABFT_MAX_PARTIALS + blockIdx.x, bv[j], __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    s_last = reduce_take_ticket(o.ticket);
+  }
+  __syncthreads();
+  if (!s_last) return;
+  double tot[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    double acc = 0.0;
+    for (uint32_t i = threadIdx.x; i < gridDim.x; i += ABFT_BLOCK)  // fixed order
+      acc += __hip_atomic_load(o.partials + (size_t)j * ABFT_MAX_PARTIALS + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tot[j] = block_sum(acc, s_w + 4 * (K + j));
+  }
+  if (threadIdx.x == 0) {
+    const uint32_t nev = __hip_atomic_load(o.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(o.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+#pragma unroll
+    for (int j = 0; j < K; j++)
+      __hip_atomic_store(&o.host->value[j], tot[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&o.host->evcount, nev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store(&o.host->seq, o.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void dot_block_kernel(const double *__restrict__ a,
+                                                               const double *__restrict__ b, int n, ReduceOutK out) {
+  __shared__ double s_w[8 * K];
+  double acc[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) acc[j] = 0.0;
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double av[K], bv[K];
+    block_load<K>(a + i * K, av);
+    block_load<K>(b + i * K, bv);
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] += av[j] * bv[j];
+  }
+  reduce_finish_k<K>(acc, out, s_w);
+}
+
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_xr_block_kernel(double *__restrict__ x, double *__restrict__ r,
+                                                                   const double *__restrict__ p,
+                                                                   const double *__restrict__ w, BlockScalars alpha,
+                                                                   uint32_t active, int n, ReduceOutK out) {
+  __shared__ double s_w[8 * K];
+  double acc[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) acc[j] = 0.0;
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double xv[K], rv[K], pv[K], wv[K];
+    block_load<K>(x + i * K, xv);
+    block_load<K>(r + i * K, rv);
+    block_load<K>(p + i * K, pv);
+    block_load<K>(w + i * K, wv);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const bool on = (active >> j) & 1u;
+      const double xs = xv[j] + alpha.v[j] * pv[j];  // calc_xr_kernel's two roundings
+      const double rs = rv[j] - alpha.v[j] * wv[j];
+      xv[j] = on ? xs : xv[j];
+      rv[j] = on ? rs : rv[j];
+      acc[j] += rv[j] * rv[j];
+    }
+    block_store<K>(x + i * K, xv);
+    block_store<K>(r + i * K, rv);
+  }
+  reduce_finish_k<K>(acc, out, s_w);
+}
+
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_p_block_kernel(double *__restrict__ p, const double *__restrict__ r,
+                                                                  BlockScalars beta, uint32_t active, int n) {
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double pv[K], rv[K];
+    block_load<K>(p + i * K, pv);
+    block_load<K>(r + i * K, rv);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const double ps = rv[j] + beta.v[j] * pv[j];
+      pv[j] = ((active >> j) & 1u) ? ps : pv[j];
+    }
+    block_store<K>(p + i * K, pv);
+  }
+}
+
+#define ABFT_BLOCK_K_DISPATCH(OP) \
+  switch (k) {                    \
+    case 1: OP(1); break;         \
+    case 2: OP(2); break;         \
+    case 3: OP(3); break;         \
+    case 4: OP(4); break;         \
+    case 5: OP(5); break;         \
+    case 6: OP(6); break;         \
+    case 7: OP(7); break;         \
+    case 8: OP(8); break;         \
+    default: return hipErrorInvalidValue; \
+  }
+
+hipError_t launch_dot_block(const double *a, const double *b, int n, int k, const ReduceOutK &out, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K) hipLaunchKernelGGL(dot_block_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, a, b, n, out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_xr_block(double *x, double *r, const double *p, const double *w, int n, int k,
+                                const BlockScalars &alpha, uint32_t active, const ReduceOutK &out, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K) \
+  hipLaunchKernelGGL(calc_xr_block_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, r, p, w, alpha, active, n, out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_p_block(double *p, const double *r, int n, int k, const BlockScalars &beta, uint32_t active,
+                               hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K) hipLaunchKernelGGL(calc_p_block_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, active, n)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
   return hipGetLastError();
 }
 

@@ -211,6 +211,42 @@ int abft_hip_calc_p(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector
 int abft_hip_spmv(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
                   abft_hip_vector *result);
 
+/* ---- block right-hand sides: K solves share one pass over the matrix ------
+ * A block vector is an ordinary vector of N*K entries, row-major: entry (i, j)
+ * at i*K + j (1 <= K <= 8, N*K < 2^31; with an even K it must start 16-byte
+ * aligned, which every vector from abft_hip_vector_create does).  Every block
+ * call takes k and checks the lengths (ABFT_ERR_INVALID on a mismatch).  Column
+ * j of every result is, bit for bit, what the single call gives for column j,
+ * except the reductions (dot_block, calc_xr_block's r.r), which are tree sums of
+ * one shape for every column.  The block calls start like the single ones (a
+ * pending x update is applied) and forget what the single calls cached (the
+ * fused product, a learned iteration). */
+
+/* CSR only: like abft_hip_matrix_create_csr, but always in the streaming
+ * row-block layout (ignores ABFT_HIP_LAYOUT) -- the layout abft_hip_spmm runs on. */
+int abft_hip_matrix_create_csr_stream(abft_hip_ctx *ctx, int mode, const uint32_t *columns,
+                                      const uint32_t *rows, const double *values, int N, int nnz,
+                                      abft_hip_matrix **mat);
+/* Y = A X for k columns: the matrix is streamed, and every element ECC-checked
+ * (and repaired or given up) once per call whatever k is -- one spmm queues the
+ * events one spmv on the same matrix state would.  k == 1 is abft_hip_spmv.
+ * Refused (ABFT_ERR_INVALID): COO matrices, CSR matrices in the panel, sweep or
+ * slice layout, shards. */
+int abft_hip_spmm(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *X,
+                  abft_hip_vector *Y, int k);
+/* out[j] = a[:, j] . b[:, j]; one synchronisation for all k */
+int abft_hip_dot_block(abft_hip_ctx *ctx, const abft_hip_vector *a, const abft_hip_vector *b,
+                       int k, double *out);
+/* for every column j whose bit is set in `active`: x[:, j] += alpha[j] p[:, j],
+ * r[:, j] -= alpha[j] w[:, j]; other columns of x and r are left untouched.
+ * rr_out[j] = r[:, j] . r[:, j] for every column (active or not). */
+int abft_hip_calc_xr_block(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r,
+                           const abft_hip_vector *p, const abft_hip_vector *w, int k,
+                           const double *alpha, uint32_t active, double *rr_out);
+/* p[:, j] = r[:, j] + beta[j] p[:, j] for the columns active in `active` */
+int abft_hip_calc_p_block(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, int k,
+                          const double *beta, uint32_t active);
+
 /* Shard-local forms for the row-partitioned solver: same kernels, but the
  * result stays on the device so a collective can sum it across ranks before
  * the host reads it.  `dev_result` is a device pointer to TWO doubles:
