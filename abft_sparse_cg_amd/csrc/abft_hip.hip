@@ -174,6 +174,9 @@ struct abft_hip_matrix {
   // made of interior rows only (abft_hip_matrix_set_interior; empty by default)
   std::vector<uint4> blk_host;
   uint32_t t_lo = 0, t_hi = 0;
+  // mode none on that layout: the compact column offsets (see CsrCompact) and a host copy of the bases
+  CsrCompact compact{};
+  std::vector<uint32_t> cbase_host;
   std::vector<void *> allocs;
 };
 
@@ -617,6 +620,74 @@ static void flag_uniform_blocks(const uint32_t *ptr, uint32_t tile, std::vector<
     for (uint32_t r = b.x; same && r < b.y; r++) same = ptr[r + 1] - ptr[r] == len;
     if (same) b.y |= 0x80000000u;
   }
+}
+
+// Mode none, streaming layout: the compact column offsets (see CsrCompact).  A block the SpMV
+// stages as one tile whose columns span at most 65536 values gets its smallest column as base
+// and every column as a 16-bit offset from it; every other block stays wide.  Config 2: a block
+// of ~204 rows of the 3162-wide band spans ~6 530 columns.  ABFT_HIP_COMPACT_COLS=0: all wide,
+// nothing allocated (A/B runs in one build).
+static int build_compact_cols(abft_hip_matrix *m, const uint32_t *columns, const std::vector<uint4> &blk,
+                              size_t padded) {
+  if (const char *e = getenv("ABFT_HIP_COMPACT_COLS"))
+    if (!strcmp(e, "0")) return ABFT_OK;
+  std::vector<uint32_t> cbase(blk.size(), ABFT_CBASE_WIDE);
+  std::vector<uint16_t> c16(padded + 2, 0);  // the kernel's 8-byte load at the last even index reads 2 past cols' padding
+  bool any = false;
+  for (size_t b = 0; b < blk.size(); b++) {
+    const uint32_t e0 = blk[b].z, e1 = blk[b].w;
+    if (e1 < e0 || e1 - (e0 & ~1u) > (uint32_t)ABFT_CSR_TILE) continue;  // walked tile by tile: reads cols
+    uint32_t lo = 0, hi = 0;
+    if (e1 > e0) lo = hi = columns[e0];
+    for (uint32_t i = e0; i < e1; i++) {
+      lo = std::min(lo, columns[i]);
+      hi = std::max(hi, columns[i]);
+    }
+    if (hi - lo > 0xFFFFu) continue;
+    cbase[b] = lo;
+    for (uint32_t i = e0; i < e1; i++) c16[i] = (uint16_t)(columns[i] - lo);
+    any = true;
+  }
+  if (!any) return ABFT_OK;
+  uint16_t *d16 = nullptr;
+  uint32_t *dbase = nullptr;
+  int rc;
+  if ((rc = dev_upload(m, &d16, c16.data(), c16.size(), c16.size())) ||
+      (rc = dev_upload(m, &dbase, cbase.data(), cbase.size(), cbase.size())))
+    return rc;
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // c16 / cbase go out of scope
+  m->compact.cols16 = d16;
+  m->compact.cbase = dbase;
+  m->cbase_host = std::move(cbase);
+  return ABFT_OK;
+}
+
+// After an inject into element `pos` of a matrix with compact columns: keep its block's
+// invariant -- rewrite the offset if the new column is still in [base, base + 65535], else
+// mark the block wide (its SpMV then reads cols, as for any wide block, columns >= N included).
+static int compact_after_inject(abft_hip_matrix *m, uint32_t pos) {
+  const std::vector<uint4> &blk = m->blk_host;
+  // the block holding pos: the last one starting at or before it (an empty block that starts at
+  // pos comes before the one holding pos)
+  auto it = std::upper_bound(blk.begin(), blk.end(), pos, [](uint32_t p, const uint4 &d) { return p < d.z; });
+  if (it == blk.begin()) return ABFT_OK;
+  const size_t b = (size_t)(it - blk.begin()) - 1;
+  if (pos >= blk[b].w || m->cbase_host[b] == ABFT_CBASE_WIDE) return ABFT_OK;
+  hipStream_t s = m->ctx->stream;
+  uint32_t col = 0;
+  HIPCHK(hipMemcpyAsync(&col, m->csr.cols + pos, sizeof(col), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const uint32_t off = col - m->cbase_host[b];  // (a column below the base wraps to a large offset)
+  if (off <= 0xFFFFu) {
+    const uint16_t o = (uint16_t)off;
+    HIPCHK(hipMemcpyAsync(const_cast<uint16_t *>(m->compact.cols16) + pos, &o, sizeof(o), hipMemcpyHostToDevice, s));
+  } else {
+    m->cbase_host[b] = ABFT_CBASE_WIDE;
+    HIPCHK(hipMemcpyAsync(const_cast<uint32_t *>(m->compact.cbase) + b, &m->cbase_host[b], sizeof(uint32_t),
+                          hipMemcpyHostToDevice, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));  // `o` is on the stack
+  return ABFT_OK;
 }
 
 // ---- panel layout planning (host) ----------------------------------------------
@@ -1090,6 +1161,10 @@ static int create_csr(abft_hip_ctx *ctx, int mode, const uint32_t *columns, cons
   A.rowptr = d_rowptr;
   A.blk = d_blk;
   if (!panels && !sweep && !slice) m->blk_host = blk;
+  if (!panels && !sweep && !slice && mode == ABFT_MODE_NONE && (rc = build_compact_cols(m, columns, blk, padded))) {
+    matrix_free(m);
+    return rc;
+  }
   hipError_t e = launch_encode_csr(mode, A.cols, A.vals, A.nnz, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // host arrays may be freed on return
   if (e != hipSuccess) {
@@ -1349,6 +1424,37 @@ extern "C" int abft_hip_matrix_info(abft_hip_matrix *mat, int *layout, int *laun
   return ABFT_OK;
 }
 
+extern "C" int abft_hip_matrix_compact_stats(abft_hip_matrix *mat, uint32_t *compact_tiles, uint32_t *tiles,
+                                             uint32_t *mismatches) {
+  if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
+  if (int rc = bind(mat->ctx)) return rc;
+  const bool stream = mat->fmt == ABFT_FMT_CSR && !mat->use_panels && !mat->use_sweep && !mat->use_slice;
+  uint32_t nc = 0, bad = 0;
+  const std::vector<uint4> &blk = mat->blk_host;
+  if (stream && mat->compact.cbase) {
+    // from the device copies, not the host's bookkeeping: what the SpMV reads
+    const CsrDev &A = mat->csr;
+    hipStream_t s = mat->ctx->stream;
+    std::vector<uint32_t> cbase(blk.size()), cols(A.nnz);
+    std::vector<uint16_t> c16(A.nnz);
+    HIPCHK(hipMemcpyAsync(cbase.data(), mat->compact.cbase, blk.size() * 4, hipMemcpyDeviceToHost, s));
+    if (A.nnz) {
+      HIPCHK(hipMemcpyAsync(cols.data(), A.cols, (size_t)A.nnz * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(c16.data(), mat->compact.cols16, (size_t)A.nnz * 2, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t b = 0; b < blk.size(); b++) {
+      if (cbase[b] == ABFT_CBASE_WIDE) continue;
+      nc++;
+      for (uint32_t i = blk[b].z; i < blk[b].w && i < A.nnz; i++) bad += cbase[b] + c16[i] != cols[i];
+    }
+  }
+  if (compact_tiles) *compact_tiles = nc;
+  if (tiles) *tiles = stream ? (uint32_t)blk.size() : 0u;
+  if (mismatches) *mismatches = bad;
+  return ABFT_OK;
+}
+
 extern "C" int abft_hip_matrix_destroy(abft_hip_matrix *mat) {
   if (!mat) return ABFT_OK;
   if (int rc = bind(mat->ctx)) return rc;
@@ -1440,6 +1546,10 @@ extern "C" int abft_hip_inject(abft_hip_matrix *mat, uint32_t index, const int *
                      : launch_inject_coo(mat->coo.elems, mat->coo.pos_of_orig, index, ctx->bits_dev, nbits, ctx->stream);
   HIPCHK(e);
   HIPCHK(hipStreamSynchronize(ctx->stream));  // `bits` is the caller's
+  // a flipped column bit (bits 64-95 of the CSR word) changes cols[index]: the compact copy follows
+  bool col_bit = false;
+  for (int k = 0; k < nbits; k++) col_bit = col_bit || bits[k] >= 64;
+  if (mat->fmt == ABFT_FMT_CSR && mat->compact.cbase && col_bit) return compact_after_inject(mat, index);
   return ABFT_OK;
 }
 
@@ -2431,8 +2541,8 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
         HIPCHK(launch_spmv_coo_panels(mat->mode, mat->coo, mat->panels, vec->d, result->d, ctx->ring,
                                       do_fuse ? &fuse : nullptr, mat->panel_grid, mat->panel_chunk, ctx->stream));
     } else if (mat->fmt == ABFT_FMT_CSR)
-      HIPCHK(launch_spmv_csr(mat->mode, mat->csr, span, vec->d, result->d, ctx->ring, do_fuse ? &fuse : nullptr,
-                             ctx->stream));
+      HIPCHK(launch_spmv_csr(mat->mode, mat->csr, mat->compact, span, vec->d, result->d, ctx->ring,
+                             do_fuse ? &fuse : nullptr, ctx->stream));
     else
       HIPCHK(launch_spmv_coo(mat->mode, mat->coo, vec->d, result->d, ctx->ring, do_fuse ? &fuse : nullptr, ctx->stream));
     // COO: products whose stored column was silently corrupted go where the reference puts them --

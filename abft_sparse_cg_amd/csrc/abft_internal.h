@@ -29,6 +29,19 @@ struct CsrDev {
   const uint32_t *gidx;         // shards whose elements are not one run of the caller's: global index of local element k
 };
 
+// Mode none, streaming row-block layout: the columns a second time, as 16-bit offsets from a
+// per-block base, for the blocks the SpMV stages as one tile and whose columns span at most
+// 65536 values (banded matrices: all of them).  The SpMV then streams 2 bytes per column
+// instead of 4.  `cols` stays the authoritative copy (read back, inject, every other kernel and
+// mode); every writer of a column keeps cbase[b] + cols16[i] == cols[i] for the elements of a
+// compact block b, or marks the block wide.  Kept out of CsrDev, which every CSR kernel takes
+// by value: there two more pointers would move the argument offsets of all of them.
+#define ABFT_CBASE_WIDE 0xFFFFFFFFu
+struct CsrCompact {
+  const uint16_t *cols16;  // cols' padded length + 2 (8-byte loads at every even index), or NULL: none compact
+  const uint32_t *cbase;   // nblk: the block's smallest column, or ABFT_CBASE_WIDE (read through cols)
+};
+
 // Panel ("column-blocked") layout for matrices whose columns are scattered over
 // a vector much larger than an XCD's 4 MB L2 (random / unstructured).  Rows are
 // cut into groups of ABFT_PANEL_ROWS, columns into panels of `width` entries
@@ -314,8 +327,8 @@ hipError_t launch_spmv_coo_panels(int mode, const CooDev &A, const CsrPanels &P,
 // (`big`: where a multi-workgroup fold of many partials meets; see fold_partials_kernel)
 struct FixArgs;
 hipError_t launch_fuse_finalize(const FuseOut &f, uint32_t nblk, const ReduceOut &big, const FixArgs *fix, hipStream_t s);
-hipError_t launch_spmv_csr(int mode, const CsrDev &A, const TileSpan &span, const double *x, double *y, EventRing ev,
-                           const FuseOut *fuse, hipStream_t s);
+hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const TileSpan &span, const double *x,
+                           double *y, EventRing ev, const FuseOut *fuse, hipStream_t s);
 hipError_t launch_spmv_coo(int mode, const CooDev &A, const double *x, double *y, EventRing ev,
                            const FuseOut *fuse, hipStream_t s);
 // behind every COO SpMV: see MovedList.  With a fused product the fix-up runs inside the fold

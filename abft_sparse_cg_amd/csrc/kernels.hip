@@ -547,6 +547,47 @@ __device__ __forceinline__ void csr_stage(const CsrDev &A, const double *__restr
   csr_consume<MODE, EPT>(A, x, ev, base, lo, hi, t, s_prod, s_col, false, 0u, 0u, unused);
 }
 
+// Mode none, one tile (see CsrCompact): the loads of csr_stage, with the column source chosen per
+// workgroup -- for a compact tile (cb != ABFT_CBASE_WIDE) the u16 offsets from the block's base
+// `cb`, 2 bytes per element instead of 4, else the u32 columns.  Branch-free like csr_issue_loads:
+// each step issues ONE 8-byte column load either way, from a uniformly selected address (compact:
+// the lane's two offsets in its low dword; the high dword, the next lane's pair, is not used --
+// cols16 is padded for it, and a wave's column loads still cover one contiguous run of 260 bytes).
+// A branch into two staged paths was tried first and dropped on its ISA: hipcc hoisted the value
+// loads above the branch and rejoined the paths before the gathers, so the wait for the columns
+// also drained the value loads.  When e0 is odd, slot `base` holds the previous block's element, whose offset is
+// relative to that block's base: it is masked invalid, as in csr_stage.
+typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+template <int EPT>
+__device__ __forceinline__ void csr_stage_none(const CsrDev &A, const CsrCompact &cc, uint32_t cb,
+                                               const double *__restrict__ x, const EventRing &ev, uint32_t base,
+                                               uint32_t lo, uint32_t hi, double *s_prod, uint32_t *s_col) {
+  const bool compact = cb != ABFT_CBASE_WIDE;  // workgroup-uniform
+  CsrTileRegs<EPT> t, unused;
+  u32x2 raw[EPT / 2];
+  uint32_t ii[EPT / 2];
+  // the column loads first: the gathers wait for them only, not for the value loads behind them
+#pragma unroll
+  for (int s = 0; s < EPT / 2; s++) {
+    const uint32_t i = base + 2u * threadIdx.x + (uint32_t)s * (2u * ABFT_BLOCK);
+    ii[s] = i < hi ? i : base;  // always a valid, even element index
+    const u32x2_a4 *pc = compact ? reinterpret_cast<const u32x2_a4 *>(cc.cols16 + ii[s])
+                                 : reinterpret_cast<const u32x2_a4 *>(A.cols + ii[s]);
+    raw[s] = STREAM_LOAD(pc);
+  }
+#pragma unroll
+  for (int s = 0; s < EPT / 2; s++) t.v[s] = STREAM_LOAD(reinterpret_cast<const f64x2 *>(A.vals + ii[s]));
+#if ABFT_CFG_SCHED_BARRIER
+  __builtin_amdgcn_sched_barrier(0);  // as in csr_issue_loads; the offsets are widened behind it
+#endif
+#pragma unroll
+  for (int s = 0; s < EPT / 2; s++) {
+    t.c[s].x = compact ? cb + (raw[s].x & 0xFFFFu) : raw[s].x;
+    t.c[s].y = compact ? cb + (raw[s].x >> 16) : raw[s].y;
+  }
+  csr_consume<MODE_NONE, EPT>(A, x, ev, base, lo, hi, t, s_prod, s_col, false, 0u, 0u, unused);
+}
+
 // Constraints mode: the reference's two checks of element i (CSR/CPUContext.cpp:186-200) on
 // the staged columns -- its column against the vector's size, then against its row successor's
 // (read from the matrix when element i is the last one staged).  Returns false if a fatal event
@@ -623,13 +664,15 @@ __device__ __forceinline__ bool csr_row_sum(const CsrDev &A, const EventRing &ev
 template <int MODE, int EPT, bool FUSE>
 __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const double *__restrict__ x,
                                                               double *__restrict__ y, EventRing ev,
-                                                              FuseOut fuse, TileSpan span) {
+                                                              FuseOut fuse, TileSpan span, CsrCompact cc) {
   constexpr uint32_t TILE = ABFT_BLOCK * EPT;
   __shared__ __attribute__((aligned(16))) double s_prod[TILE];
   __shared__ __attribute__((aligned(16))) uint32_t s_col[MODE == MODE_CONSTRAINTS ? TILE : 2];
   const uint32_t b = xcd_tile(blockIdx.x, span.count);
   const uint32_t t = span.first + b + (b >= span.cut ? span.skip : 0u);
   const uint4 desc = A.blk[t];  // one scalar load instead of two dependent pairs
+  // mode none: this tile's column base (by tile, not workgroup: span cut / skip), uniform
+  const uint32_t cb = (MODE == MODE_NONE && cc.cbase) ? cc.cbase[t] : ABFT_CBASE_WIDE;
   // bit 31 of the second word: every row of this block has the same length (banded
   // matrices: nearly all blocks), so the row pointers need not be read at all
   const bool uniform = ABFT_CFG_UNIFORM_ROWS && MODE != MODE_CONSTRAINTS && (desc.y >> 31) != 0u;
@@ -651,7 +694,10 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
       }
       if (FUSE) xr = x[fuse.x_off + r];
     }
-    csr_stage<MODE, EPT>(A, x, ev, base, e0, e1, s_prod, s_col);
+    if (MODE == MODE_NONE)
+      csr_stage_none<EPT>(A, cc, cb, x, ev, base, e0, e1, s_prod, s_col);
+    else
+      csr_stage<MODE, EPT>(A, x, ev, base, e0, e1, s_prod, s_col);
     __syncthreads();
     for (uint32_t row = r; row < row1; row += ABFT_BLOCK) {
       if (row != r) {
@@ -828,29 +874,31 @@ int spmv_csr_panels_blocks_per_cu(int mode, bool fuse) {
 }
 
 template <int MODE>
-static hipError_t launch_spmv_csr_mode(const CsrDev &A, const TileSpan &span, const double *x, double *y,
-                                       EventRing ev, const FuseOut *fuse, hipStream_t s) {
+static hipError_t launch_spmv_csr_mode(const CsrDev &A, const CsrCompact &cc, const TileSpan &span, const double *x,
+                                       double *y, EventRing ev, const FuseOut *fuse, hipStream_t s) {
   if (fuse) {
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
-                       x, y, ev, *fuse, span);
+                       x, y, ev, *fuse, span, cc);
   } else
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, false>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
-                       x, y, ev, FuseOut{}, span);
+                       x, y, ev, FuseOut{}, span, cc);
   return hipGetLastError();
 }
 
-hipError_t launch_spmv_csr(int mode, const CsrDev &A, const TileSpan &span, const double *x, double *y,
-                           EventRing ev, const FuseOut *fuse, hipStream_t s) {
+hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const TileSpan &span, const double *x,
+                           double *y, EventRing ev, const FuseOut *fuse, hipStream_t s) {
   // every tile the span maps to must exist: checked here, on the host
   if (span.count == 0) return hipSuccess;
   if ((uint64_t)span.first + span.count + span.skip > A.nblk || span.cut > span.count) return hipErrorInvalidValue;
+  // compact columns only in mode none, and then both arrays
+  if ((cc.cbase || cc.cols16) && (mode != MODE_NONE || !cc.cbase || !cc.cols16)) return hipErrorInvalidValue;
   switch (mode) {
-    case MODE_NONE: return launch_spmv_csr_mode<MODE_NONE>(A, span, x, y, ev, fuse, s);
-    case MODE_CONSTRAINTS: return launch_spmv_csr_mode<MODE_CONSTRAINTS>(A, span, x, y, ev, fuse, s);
-    case MODE_SED: return launch_spmv_csr_mode<MODE_SED>(A, span, x, y, ev, fuse, s);
-    case MODE_SEC7: return launch_spmv_csr_mode<MODE_SEC7>(A, span, x, y, ev, fuse, s);
-    case MODE_SEC8: return launch_spmv_csr_mode<MODE_SEC8>(A, span, x, y, ev, fuse, s);
-    case MODE_SECDED: return launch_spmv_csr_mode<MODE_SECDED>(A, span, x, y, ev, fuse, s);
+    case MODE_NONE: return launch_spmv_csr_mode<MODE_NONE>(A, cc, span, x, y, ev, fuse, s);
+    case MODE_CONSTRAINTS: return launch_spmv_csr_mode<MODE_CONSTRAINTS>(A, cc, span, x, y, ev, fuse, s);
+    case MODE_SED: return launch_spmv_csr_mode<MODE_SED>(A, cc, span, x, y, ev, fuse, s);
+    case MODE_SEC7: return launch_spmv_csr_mode<MODE_SEC7>(A, cc, span, x, y, ev, fuse, s);
+    case MODE_SEC8: return launch_spmv_csr_mode<MODE_SEC8>(A, cc, span, x, y, ev, fuse, s);
+    case MODE_SECDED: return launch_spmv_csr_mode<MODE_SECDED>(A, cc, span, x, y, ev, fuse, s);
     default: return hipErrorInvalidValue;
   }
 }

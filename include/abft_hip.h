@@ -138,6 +138,12 @@ int abft_hip_matrix_destroy(abft_hip_matrix *mat);
  * 1 column panels (chunked launches), 2 sweep (one persistent launch); *launches_per_spmv = kernel launches one abft_hip_spmv enqueues (what
  * ABFT_K_SPMV's bracket spans), without the fold of a fused product. */
 int abft_hip_matrix_info(abft_hip_matrix *mat, int *layout, int *launches_per_spmv);
+/* Mode none, streaming row-block CSR layout (measurement and tests only): *tiles = row blocks of the
+ * layout (0 for any other layout or format), *compact_tiles = those whose columns the SpMV reads as
+ * 16-bit offsets from a per-block base, *mismatches = elements of compact blocks whose base + offset
+ * differs from the stored column (0 unless the copies have come apart).  Any pointer may be NULL. */
+int abft_hip_matrix_compact_stats(abft_hip_matrix *mat, uint32_t *compact_tiles, uint32_t *tiles,
+                                  uint32_t *mismatches);
 
 /* Read back the stored (ECC-encoded) arrays in the caller's element order.
  * CSR: cols[nnz], rowptr[nrows+1], values[nnz].  Any pointer may be NULL. */
