@@ -82,6 +82,12 @@ SIGNATURES = {
     "abft_hip_dot_block": (C.c_int, [vp, vp, vp, C.c_int, f64p]),
     "abft_hip_calc_xr_block": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, f64p, C.c_uint32, f64p]),
     "abft_hip_calc_p_block": (C.c_int, [vp, vp, vp, C.c_int, f64p, C.c_uint32]),
+    "abft_hip_vector_flip": (C.c_int, [vp, C.c_int, i32p, C.c_int]),
+    "abft_hip_residual_gap": (C.c_int, [vp, vp, vp, vp, vp, vp, f64p]),
+    "abft_hip_residual_restart": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, f64p]),
+    "abft_hip_residual_gap_block": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, f64p]),
+    "abft_hip_residual_restart_block": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, f64p]),
+    "abft_hip_copy_block": (C.c_int, [vp, vp, vp, C.c_int, C.c_uint32]),
     "abft_hip_dot_dev": (C.c_int, [vp, vp, vp, vp]),
     "abft_hip_calc_xr_dev": (C.c_int, [vp, vp, vp, vp, vp, C.c_double, vp]),
     "abft_hip_read_pair": (C.c_int, [vp, vp, f64p, f64p]),

@@ -51,6 +51,15 @@ Additional options of this build:
       --rhs             K     Solve K right-hand sides (1-8) at once, one pass over the
                               matrix per iteration (CSR only); column j of b is the
                               reference's b drawn with seed 1+j
+      --check-every     N     Check r against b - Ax every N iterations and before
+                              stopping; roll back to the last good x on a failure
+                              (0 = off, the default)
+      --check-tol       T     A check fails when ||b - Ax - r|| > T ||b|| (default 1e-7)
+      --max-rollbacks   M     Give up (exit 1) after more than M failed checks (default 3)
+      --flip-vector I:V:J:B[,B...]
+                              After iteration I, flip bit(s) B (0-63) of entry J of
+                              vector V (x, r or p; with --rhs K, J = row * K + column)
+                              (may be repeated)
 
 """
 
@@ -63,7 +72,7 @@ def fail(msg):
 def parse(argv):
     o = dict(num_blocks=25, max_itrs=1000, conv=0.001, matrix_file=DEFAULT_MTX, synthetic=None, target="cpu",
              mode="none", flips=0, kind="ANY", seed=None, quiet=False, flip_at=None, fmt="csr", list=False,
-             rhs=1)
+             rhs=1, check_every=0, check_tol=1e-7, max_rollbacks=3, flip_vector=[])
 
     def num(s, conv):
         try:
@@ -132,6 +141,28 @@ def parse(argv):
             o["rhs"] = num(arg("Invalid number of right-hand sides"), int)
             if not 1 <= o["rhs"] <= 8:
                 fail("Invalid number of right-hand sides")
+        elif a == "--check-every":
+            o["check_every"] = num(arg("Invalid residual check interval"), int)
+            if o["check_every"] < 0:
+                fail("Invalid residual check interval")
+        elif a == "--check-tol":
+            o["check_tol"] = num(arg("Invalid residual check tolerance"), float)
+            if not (0 < o["check_tol"] < math.inf):
+                fail("Invalid residual check tolerance")
+        elif a == "--max-rollbacks":
+            o["max_rollbacks"] = num(arg("Invalid number of rollbacks"), int)
+            if o["max_rollbacks"] < 0:
+                fail("Invalid number of rollbacks")
+        elif a == "--flip-vector":
+            msg = "Invalid --flip-vector (want ITER:VEC:INDEX:BIT[,BIT...], VEC one of x, r, p)"
+            try:
+                itr, vec, idx, bits = arg(msg).split(":")
+                flip = (int(itr), vec, int(idx), [int(b) for b in bits.split(",")])
+            except ValueError:
+                fail(msg)
+            if flip[0] < 0 or flip[1] not in ("x", "r", "p") or flip[2] < 0 or not all(0 <= b < 64 for b in flip[3]):
+                fail(msg)
+            o["flip_vector"] = o["flip_vector"] + [flip]
         elif a in ("--quiet", "-q"):
             o["quiet"] = True
         elif a in ("--help", "-h"):
@@ -171,6 +202,35 @@ def draw_flips(o, nnz):
     index = libc.rand() % nnz
     lo, hi = bit_range(o["fmt"], o["kind"])
     return [(index, [libc.rand() % (hi - lo) + lo for _ in range(o["flips"])])]
+
+
+def vector_flips(o, length, vecs):
+    """--flip-vector's flips as {iteration: [(vector, index, bits)]}, each index checked against the length"""
+    out = {}
+    for itr, name, index, bits in o["flip_vector"]:
+        if index >= length:
+            fail("Invalid --flip-vector: index %d outside a vector of %d entries" % (index, length))
+        out.setdefault(itr, []).append((name, vecs[name], index, bits))
+    return out
+
+
+def apply_vector_flips(ctx, flips, itr):
+    for name, v, index, bits in flips.get(itr, ()):
+        for bit in bits:
+            print("*** flipping bit %d of %s[%d] ***" % (bit, name, index))
+        ctx.flip_vector(v, index, bits)
+
+
+def report_check(checks, prefix, itr, gap, ok, back, bound):
+    """one line per failed residual check; the counts for print_check_summary"""
+    checks[ok] = checks.get(ok, 0) + 1
+    if not ok:
+        print("%s[ABFT] residual check failed at iteration %d: gap %.1e > %.1e; rolled back to %s"
+              % (prefix, itr, gap, bound, "the start" if back < 0 else "iteration %d" % back))
+
+
+def print_check_summary(checks):
+    print("residual checks: %d passed, %d failed" % (checks.get(True, 0), checks.get(False, 0)))
 
 
 def main(argv=None):
@@ -219,7 +279,7 @@ def load_matrix(o, row0=0, row1=None):
 
 def run_single(o):
     from . import HIPContext, generators
-    from .context import fdiv, note_threshold
+    from .context import ResidualCheckFailed, cg_solve
     cols, rows, vals, n, block = load_matrix(o)
     nnz = len(vals)
     ctx = HIPContext(o["mode"], o["fmt"])
@@ -233,26 +293,28 @@ def run_single(o):
         for bit in bits:
             print("*** flipping bit %d at index %d ***" % (bit, index))
         ctx.inject_at(A, index, bits)
-    t0 = time.perf_counter()
-    ctx.copy_vector(r, b)
-    ctx.copy_vector(p, r)
-    rr = ctx.dot(r, r)
-    itr = 0
-    noted = {}
-    note_threshold(rr, o["conv"], noted)
-    while itr < o["max_itrs"] and rr > o["conv"]:
-        ctx.spmv(A, p, w)
-        pw = ctx.dot(p, w)
-        alpha = fdiv(rr, pw)
-        rr_new = ctx.calc_xr(x, r, p, w, alpha)
-        ctx.calc_p(p, r, fdiv(rr_new, rr))
-        rr = rr_new
-        note_threshold(rr, o["conv"], noted)
+    vecs = vector_flips(o, n, {"x": x, "r": r, "p": p})
+    bound = o["check_tol"] * float(np.linalg.norm(generators.reference_rhs(n)))
+    checks = {}
+
+    def line(itr, rr):
         if not o["quiet"]:
             print("iteration %5u :  rr = %12.4f" % (itr, rr))
-        itr += 1
+        apply_vector_flips(ctx, vecs, itr)
+
+    t0 = time.perf_counter()
+    try:
+        itr, rr = cg_solve(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
+                           check_every=o["check_every"], check_tol=o["check_tol"], max_rollbacks=o["max_rollbacks"],
+                           on_check=lambda i, gap, ok, back: report_check(checks, "", i, gap, ok, back, bound))
+    except ResidualCheckFailed as e:
+        print("[ABFT] %s" % e)
+        ctx.close()
+        return 1
     ms = (time.perf_counter() - t0) * 1e3
     print("\nran for %u iterations" % itr)
+    if o["check_every"]:
+        print_check_summary(checks)
     print("\ntime taken = %7.2f ms\n" % ms)
     ctx.spmv(A, x, r)
     err = np.abs(ctx.download(b) - ctx.download(r))
@@ -268,7 +330,7 @@ def run_block(o):
     """run_single for o["rhs"] right-hand sides at once (cg_solve_block): the matrix in the streaming
     layout, one line of K residuals per iteration, a `ran for` line and the errors per column."""
     from . import HIPContext, generators
-    from .context import cg_solve_block
+    from .context import ResidualCheckFailed, cg_solve_block
     K = o["rhs"]
     cols, rows, vals, n, block = load_matrix(o)
     nnz = len(vals)
@@ -284,16 +346,33 @@ def run_block(o):
             print("*** flipping bit %d at index %d ***" % (bit, index))
         ctx.inject_at(A, index, bits)
 
+    vecs = vector_flips(o, n * K, {"x": x, "r": r, "p": p})
+    bounds = [o["check_tol"] * float(np.linalg.norm(generators.reference_rhs(n, seed=1 + j))) for j in range(K)]
+    checks = {}
+
     def line(itr, rr, active):
         if not o["quiet"]:
             print("iteration %5u :  rr = %s" % (itr, " ".join("%12.4f" % v for v in rr)))
+        apply_vector_flips(ctx, vecs, itr)
+
+    def on_check(i, gap, ok, back, j):
+        report_check(checks, "rhs %u: " % j, i, gap, ok, back, bounds[j])
 
     t0 = time.perf_counter()
-    itrs, _ = cg_solve_block(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line)
+    try:
+        itrs, _ = cg_solve_block(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
+                                 check_every=o["check_every"], check_tol=o["check_tol"],
+                                 max_rollbacks=o["max_rollbacks"], on_check=on_check)
+    except ResidualCheckFailed as e:
+        print("[ABFT] %s" % e)
+        ctx.close()
+        return 1
     ms = (time.perf_counter() - t0) * 1e3
     print()
     for j in range(K):
         print("rhs %u: ran for %u iterations" % (j, itrs[j]))
+    if o["check_every"]:
+        print_check_summary(checks)
     print("\ntime taken = %7.2f ms (%u right-hand sides)\n" % (ms, K))
     ctx.spmm(A, x, r, K)
     err = np.abs(ctx.download(b) - ctx.download(r))

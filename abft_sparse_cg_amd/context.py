@@ -8,6 +8,7 @@ include/abft_hip.h; the C++ HIPContext under host/ binds the same ABI for the
 cg-csr / cg-coo executables.
 """
 import ctypes as C
+import math
 import sys
 
 import numpy as np
@@ -24,6 +25,16 @@ class FatalEvent(SystemExit):
     def __init__(self, events):
         super().__init__(1)
         self.events = events
+
+
+class ResidualCheckFailed(RuntimeError):
+    """A residual check failed more than max_rollbacks times, or failed at max_itrs: the
+    solve cannot vouch for x (which holds the last checkpoint that passed).  `checks` is the
+    record of every check of the solve: (itr, gap, ok, rolled_back_to[, rhs]) as on_check saw it."""
+
+    def __init__(self, message, checks):
+        super().__init__(message)
+        self.checks = checks
 
 
 class Matrix:
@@ -258,6 +269,47 @@ class HIPContext:
         b[:k] = beta
         check(self.L.abft_hip_calc_p_block(self.h, p.h, r.h, k, b.ctypes.data_as(capi.f64p), int(active)))
 
+    # ---- residual checks (include/abft_hip.h) ----
+    def flip_vector(self, v, index, bits):
+        """XOR the given bits (0-63) into the double v[index] (for a block vector: row * K + column)"""
+        b = np.ascontiguousarray(bits, dtype=np.int32)
+        check(self.L.abft_hip_vector_flip(v.h, int(index), b.ctypes.data_as(capi.i32p), len(b)))
+
+    def residual_gap(self, mat, b, x, r, scratch):
+        """scratch = A x; -> (sum ((b - Ax) - r)^2, sum (b - Ax)^2).  Events as after spmv + dot."""
+        out = np.zeros(2)
+        check(self.L.abft_hip_residual_gap(self.h, mat.h, b.h, x.h, r.h, scratch.h, out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return float(out[0]), float(out[1])
+
+    def residual_restart(self, mat, b, x, r, p, scratch):
+        """r = b - A x, p = r; -> r . r (the bits dot(r, r) gives)"""
+        out = C.c_double()
+        check(self.L.abft_hip_residual_restart(self.h, mat.h, b.h, x.h, r.h, p.h, scratch.h, C.byref(out)))
+        self._drain_if_pending()
+        return out.value
+
+    def residual_gap_block(self, mat, B, X, R, scratch, k, active):
+        """-> (gap2[k], tt2[k]) for the columns set in `active` (0.0 elsewhere)"""
+        out = np.zeros(2 * k)
+        check(self.L.abft_hip_residual_gap_block(self.h, mat.h, B.h, X.h, R.h, scratch.h, k, int(active),
+                                                 out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return out[0::2].copy(), out[1::2].copy()
+
+    def residual_restart_block(self, mat, B, X, R, P, scratch, k, mask):
+        """R[:, j] = B[:, j] - (A X)[:, j], P[:, j] = R[:, j] for the columns set in `mask`;
+        -> np.ndarray of k values R[:, j] . R[:, j] (every column)"""
+        out = np.zeros(k)
+        check(self.L.abft_hip_residual_restart_block(self.h, mat.h, B.h, X.h, R.h, P.h, scratch.h, k, int(mask),
+                                                     out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return out
+
+    def copy_block(self, dst, src, k, mask):
+        """dst[:, j] = src[:, j] for the columns set in `mask`"""
+        check(self.L.abft_hip_copy_block(self.h, dst.h, src.h, k, int(mask)))
+
     def matrix_info(self, mat):
         """-> (layout: 'stream' | 'panels' | 'sweep' | 'slice', kernel launches per spmv) -- measurement only"""
         lay, n = C.c_int(0), C.c_int(0)
@@ -381,36 +433,121 @@ def note_threshold(rr, conv_threshold, state):
                          "one iteration more or fewer\n" % (float(rr).hex(), conv_threshold))
 
 
-def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None):
-    """The reference driver's CG loop, call for call (cg.cpp:87-118)."""
+def _check_passes(gap2, tt2, bb, check_tol):
+    """the pass rule: gap2 <= check_tol^2 ||b||^2 with both sums finite (NaN fails the comparison)"""
+    return (gap2 <= check_tol * check_tol * bb) and math.isfinite(gap2) and math.isfinite(tt2)
+
+
+def _ckpt_name(itr):
+    return "the start" if itr < 0 else "iteration %d" % itr
+
+
+def _check_args(check_every, check_tol, max_rollbacks):
+    if check_every < 0 or int(check_every) != check_every:
+        raise ValueError("check_every must be a whole number >= 0, not %r" % (check_every,))
+    if not check_tol > 0 or not math.isfinite(check_tol):
+        raise ValueError("check_tol must be a positive number, not %r" % (check_tol,))
+    if max_rollbacks < 0:
+        raise ValueError("max_rollbacks must be >= 0, not %r" % (max_rollbacks,))
+
+
+def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None, check_every=0,
+             check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None):
+    """The reference driver's CG loop, call for call (cg.cpp:87-118).
+
+    check_every > 0 adds residual checks: after iteration i when (i + 1) %
+    check_every == 0, and whenever the loop is about to stop on a state no check has seen, the
+    recurrence's r is compared with b - A x (ctx.residual_gap, w as the scratch vector).  A check passes
+    when ||b - A x - r|| <= check_tol ||b||; then x is copied to the checkpoint x_ckpt (a vector of x's
+    length, made here when None).  A failed check copies the checkpoint back into x and restarts the
+    recurrence from it (r = b - A x, p = r: ctx.residual_restart).  More than max_rollbacks failures, or a
+    failure at max_itrs, raise ResidualCheckFailed.  on_check(itr, gap, ok, rolled_back_to): itr the
+    iteration the check follows (-1: the start), gap = ||b - A x - r||, rolled_back_to the iteration of
+    the restored checkpoint (-1: the start) or None.  itr counts every iteration run, repeated ones
+    included.  With check_every=0 the calls are exactly the loop's above."""
+    _check_args(check_every, check_tol, max_rollbacks)
     ctx.copy_vector(r, b)
     ctx.copy_vector(p, r)
     rr = ctx.dot(r, r)
     itr = 0
     noted = {}
     note_threshold(rr, conv_threshold, noted)
-    while itr < max_itrs and rr > conv_threshold:
-        ctx.spmv(A, p, w)
-        pw = ctx.dot(p, w)
-        alpha = fdiv(rr, pw)
-        rr_new = ctx.calc_xr(x, r, p, w, alpha)
-        beta = fdiv(rr_new, rr)
-        ctx.calc_p(p, r, beta)
-        rr = rr_new
-        note_threshold(rr, conv_threshold, noted)
-        if on_iteration is not None:
-            on_iteration(itr, rr)
-        itr += 1
+    if check_every:
+        bb = rr  # r = b: ||b||^2
+        own_ckpt = x_ckpt is None
+        if own_ckpt:
+            x_ckpt = ctx.create_vector(x.N)
+        ctx.copy_vector(x_ckpt, x)
+        st = dict(checked=False, ckpt=-1, fails=0, records=[])
+
+        def check():
+            nonlocal rr
+            gap2, tt2 = ctx.residual_gap(A, b, x, r, w)
+            ok = _check_passes(gap2, tt2, bb, check_tol)
+            gap = math.sqrt(gap2) if gap2 >= 0 else gap2
+            back = None
+            if ok:
+                ctx.copy_vector(x_ckpt, x)
+                st["ckpt"] = itr - 1
+            else:
+                st["fails"] += 1
+                back = st["ckpt"]
+                ctx.copy_vector(x, x_ckpt)
+                rr = ctx.residual_restart(A, b, x, r, p, w)
+                note_threshold(rr, conv_threshold, noted)
+            st["checked"] = True
+            st["records"].append((itr - 1, gap, ok, back))
+            if on_check is not None:
+                on_check(itr - 1, gap, ok, back)
+            if not ok and (st["fails"] > max_rollbacks or itr >= max_itrs):
+                raise ResidualCheckFailed(
+                    "residual check failed at iteration %d (gap %.3e > %.3e) %s; x holds the checkpoint of %s"
+                    % (itr - 1, gap, check_tol * math.sqrt(bb),
+                       "after %d rollbacks" % (st["fails"] - 1) if itr < max_itrs else "at max_itrs",
+                       _ckpt_name(back)), st["records"])
+    try:
+        while True:
+            if not (itr < max_itrs and rr > conv_threshold):
+                if not check_every or st["checked"]:
+                    break
+                check()  # the final state (a failure restarts the loop from the checkpoint)
+                continue
+            ctx.spmv(A, p, w)
+            pw = ctx.dot(p, w)
+            alpha = fdiv(rr, pw)
+            rr_new = ctx.calc_xr(x, r, p, w, alpha)
+            beta = fdiv(rr_new, rr)
+            ctx.calc_p(p, r, beta)
+            rr = rr_new
+            note_threshold(rr, conv_threshold, noted)
+            if on_iteration is not None:
+                on_iteration(itr, rr)
+            itr += 1
+            if check_every:
+                st["checked"] = False
+                if itr % check_every == 0:
+                    check()
+    finally:
+        if check_every and own_ckpt:
+            ctx.destroy_vector(x_ckpt)
     return itr, rr
 
 
-def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None):
+def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None, check_every=0,
+                   check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None):
     """cg_solve for the K columns of block vectors (ctx.create_block) at once: per column j exactly
     cg_solve's control flow -- column j iterates while itrs[j] < max_itrs and rr[j] > conv_threshold --
     on one spmm / dot_block / calc_xr_block / calc_p_block per iteration.  A column that has stopped
     is frozen through the active mask (its x, r, p are not touched again); the loop ends when no
     column is active.  on_iteration(itr, rr, active): after every iteration, rr of all K columns and
-    the mask of the columns that iteration updated.  -> (itrs[K], rr[K])"""
+    the mask of the columns that iteration updated.  -> (itrs[K], rr[K])
+
+    Residual checks (check_every > 0) as in cg_solve, per column: the columns due for a check share one
+    residual_gap_block; a failed column alone is restored (copy_block from x_ckpt, a block vector made
+    here when None) and restarted (residual_restart_block with its bit in the mask); the other columns'
+    x, r, p keep their bits.  on_check(itr, gap, ok, rolled_back_to, rhs), itr counting column rhs's
+    iterations."""
+    _check_args(check_every, check_tol, max_rollbacks)
     k = B.K
     if not k:
         raise ValueError("cg_solve_block wants block vectors (create_block)")
@@ -425,23 +562,83 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
     def still(j):
         return itrs[j] < max_itrs and rr[j] > conv_threshold
 
-    active = sum(1 << j for j in range(k) if still(j))
+    if check_every:
+        bb = rr.copy()  # R = B: ||b_j||^2
+        own_ckpt = x_ckpt is None
+        if own_ckpt:
+            x_ckpt = ctx.create_block(B.N // k, k)
+        ctx.copy_vector(x_ckpt, X)
+        checked, ckpt, fails, records = [False] * k, [-1] * k, [0] * k, []
+
+        def check(due):
+            gap2, tt2 = ctx.residual_gap_block(A, B, X, R, W, k, due)
+            passed = failed = 0
+            events = []
+            for j in range(k):
+                if not (due >> j) & 1:
+                    continue
+                ok = _check_passes(gap2[j], tt2[j], bb[j], check_tol)
+                gap = math.sqrt(gap2[j]) if gap2[j] >= 0 else float(gap2[j])
+                events.append((itrs[j] - 1, gap, ok, None if ok else ckpt[j], j))
+                checked[j] = True
+                if ok:
+                    passed |= 1 << j
+                    ckpt[j] = itrs[j] - 1
+                else:
+                    failed |= 1 << j
+                    fails[j] += 1
+            if passed:
+                ctx.copy_block(x_ckpt, X, k, passed)
+            if failed:
+                ctx.copy_block(X, x_ckpt, k, failed)
+                rr_new = ctx.residual_restart_block(A, B, X, R, P, W, k, failed)
+                for j in range(k):
+                    if (failed >> j) & 1:
+                        rr[j] = rr_new[j]
+                        note_threshold(rr[j], conv_threshold, noted)
+            for e in events:
+                records.append(e)
+                if on_check is not None:
+                    on_check(*e)
+            for i, gap, ok, back, j in events:
+                if not ok and (fails[j] > max_rollbacks or itrs[j] >= max_itrs):
+                    raise ResidualCheckFailed(
+                        "rhs %d: residual check failed at iteration %d (gap %.3e > %.3e) %s; x holds the "
+                        "checkpoint of %s" % (j, i, gap, check_tol * math.sqrt(bb[j]),
+                                              "after %d rollbacks" % (fails[j] - 1) if itrs[j] < max_itrs
+                                              else "at max_itrs", _ckpt_name(back)), records)
+
     itr = 0
-    while active:
-        on = [(active >> j) & 1 for j in range(k)]
-        ctx.spmm(A, P, W, k, drain=False)
-        pw = ctx.dot_block(P, W, k)
-        alpha = [fdiv(rr[j], pw[j]) if on[j] else 0.0 for j in range(k)]
-        rr_new = ctx.calc_xr_block(X, R, P, W, k, alpha, active)
-        beta = [fdiv(rr_new[j], rr[j]) if on[j] else 0.0 for j in range(k)]
-        ctx.calc_p_block(P, R, k, beta, active)
-        for j in range(k):
-            if on[j]:
-                rr[j] = rr_new[j]
-                itrs[j] += 1
-                note_threshold(rr[j], conv_threshold, noted)
-        if on_iteration is not None:
-            on_iteration(itr, rr.copy(), active)
-        itr += 1
-        active = sum(1 << j for j in range(k) if on[j] and still(j))
+    try:
+        while True:
+            if check_every:
+                # due: every column that has just finished a multiple of check_every iterations, and every
+                # column about to stop on a state no check has seen
+                due = sum(1 << j for j in range(k)
+                          if not checked[j] and (not still(j) or (itrs[j] and itrs[j] % check_every == 0)))
+                if due:
+                    check(due)
+            active = sum(1 << j for j in range(k) if still(j))
+            if not active:
+                break
+            on = [(active >> j) & 1 for j in range(k)]
+            ctx.spmm(A, P, W, k, drain=False)
+            pw = ctx.dot_block(P, W, k)
+            alpha = [fdiv(rr[j], pw[j]) if on[j] else 0.0 for j in range(k)]
+            rr_new = ctx.calc_xr_block(X, R, P, W, k, alpha, active)
+            beta = [fdiv(rr_new[j], rr[j]) if on[j] else 0.0 for j in range(k)]
+            ctx.calc_p_block(P, R, k, beta, active)
+            for j in range(k):
+                if on[j]:
+                    rr[j] = rr_new[j]
+                    itrs[j] += 1
+                    note_threshold(rr[j], conv_threshold, noted)
+                    if check_every:
+                        checked[j] = False
+            if on_iteration is not None:
+                on_iteration(itr, rr.copy(), active)
+            itr += 1
+    finally:
+        if check_every and own_ckpt:
+            ctx.destroy_vector(x_ckpt)
     return itrs, rr

@@ -113,8 +113,9 @@ struct abft_hip_ctx {
   } defer;
   double *alpha_dev = nullptr;  // alpha of the deferred update when it was formed on the device
   // block right-hand sides (abft_hip_dot_block, abft_hip_calc_xr_block): allocated by the first such call
-  double *bpartials = nullptr;          // ABFT_MAX_RHS * ABFT_MAX_PARTIALS doubles
+  double *bpartials = nullptr;          // 2 * ABFT_MAX_RHS * ABFT_MAX_PARTIALS doubles (the 2K sums of a block check)
   HostSlotK *bslot = nullptr, *bslot_dev = nullptr;  // pinned K-wide result slot, its device alias
+  HostSlotW *wslot = nullptr, *wslot_dev = nullptr;  // ... and the 2K-wide one of abft_hip_residual_gap_block
   uint32_t bseq = 0;                    // last sequence number handed to a block reduction
   unsigned prof = 0;  // bit k: bracket launches of kernel k with HIP events
   unsigned prof_stride = 1, prof_seen[ABFT_K_COUNT] = {};  // ... every prof_stride-th launch of it
@@ -432,6 +433,7 @@ extern "C" int abft_hip_shutdown(abft_hip_ctx *ctx) {
   (void)hipFree(ctx->tail_sync);
   (void)hipFree(ctx->bpartials);
   if (ctx->bslot) (void)hipHostFree(ctx->bslot);
+  if (ctx->wslot) (void)hipHostFree(ctx->wslot);
   if (getenv("ABFT_HIP_VERBOSE") && (ctx->spec.commits || ctx->spec.drops))
     fprintf(stderr, "hip: speculated iterations: %ld taken over, %ld dropped\n", ctx->spec.commits, ctx->spec.drops);
   for (double *b : ctx->spec.shadow) (void)hipFree(b);
@@ -2623,7 +2625,10 @@ static int bind_block(abft_hip_ctx *ctx) {
 
 static int block_slot(abft_hip_ctx *ctx) {
   if (ctx->bslot) return ABFT_OK;
-  HIPCHK(hipMalloc((void **)&ctx->bpartials, (size_t)ABFT_MAX_RHS * ABFT_MAX_PARTIALS * sizeof(double)));
+  HIPCHK(hipMalloc((void **)&ctx->bpartials, (size_t)2 * ABFT_MAX_RHS * ABFT_MAX_PARTIALS * sizeof(double)));
+  HIPCHK(hipHostMalloc((void **)&ctx->wslot, sizeof(HostSlotW), hipHostMallocMapped | hipHostMallocCoherent));
+  memset(ctx->wslot, 0, sizeof(HostSlotW));
+  HIPCHK(hipHostGetDevicePointer((void **)&ctx->wslot_dev, ctx->wslot, 0));
   HIPCHK(hipHostMalloc((void **)&ctx->bslot, sizeof(HostSlotK), hipHostMallocMapped | hipHostMallocCoherent));
   memset(ctx->bslot, 0, sizeof(HostSlotK));
   HIPCHK(hipHostGetDevicePointer((void **)&ctx->bslot_dev, ctx->bslot, 0));
@@ -2718,6 +2723,147 @@ extern "C" int abft_hip_calc_p_block(abft_hip_ctx *ctx, abft_hip_vector *p, cons
   for (int j = 0; j < k; j++) b.v[j] = beta[j];
   KernelTimer t(ctx, ABFT_K_CALC_P);
   HIPCHK(launch_calc_p_block(p->d, r->d, N, k, b, active, ctx->stream));
+  return ABFT_OK;
+}
+
+// ---- residual checks (include/abft_hip.h): vector fault injection, b - A x against r, restart ----
+// Every entry starts with bind_block: a deferred x += alpha p is applied (a flip or a check sees the
+// real x), a speculation is voided, and the fused product is forgotten; the check's SpMV writes the
+// scratch vector, so the fused product is forgotten again behind it.
+
+extern "C" int abft_hip_vector_flip(abft_hip_vector *v, int index, const int *bits, int nbits) {
+  if (!v) return set_err(ABFT_ERR_INVALID, "vector_flip: null vector");
+  if (int rc = bind_block(v->ctx)) return rc;
+  if (index < 0 || index >= v->n) return set_err(ABFT_ERR_INVALID, "vector_flip: index %d outside [0,%d)", index, v->n);
+  if (nbits < 0 || nbits > 64 || (nbits && !bits)) return set_err(ABFT_ERR_INVALID, "vector_flip: bad bit list");
+  unsigned long long mask = 0;
+  for (int k = 0; k < nbits; k++) {
+    if (bits[k] < 0 || bits[k] >= 64) return set_err(ABFT_ERR_INVALID, "vector_flip: bit %d outside [0,64)", bits[k]);
+    mask ^= 1ull << bits[k];
+  }
+  if (!mask) return ABFT_OK;
+  HIPCHK(launch_flip_vector(v->d + index, mask, v->ctx->stream));
+  return ABFT_OK;
+}
+
+// the vectors of a single check: x has the matrix's input length, the others its output length, the
+// scratch overlaps none of them; `out1` / `out2` (restart: r, p) overlap nothing else either
+static int check_residual_args(const char *what, abft_hip_matrix *A, const abft_hip_vector *b, const abft_hip_vector *x,
+                               const abft_hip_vector *r, const abft_hip_vector *scratch, const abft_hip_vector *p) {
+  if (!A || !b || !x || !r || !scratch) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
+  const int n_out = (int)(A->fmt == ABFT_FMT_CSR ? A->csr.n_out : A->coo.n_out);
+  const int n_in = (int)(A->fmt == ABFT_FMT_CSR ? A->csr.n_in : A->coo.n_in);
+  if (x->n != n_in) return set_err(ABFT_ERR_INVALID, "%s: x has %d entries, the matrix %d columns", what, x->n, n_in);
+  for (const abft_hip_vector *v : {b, r, scratch})
+    if (v->n != n_out) return set_err(ABFT_ERR_INVALID, "%s: a vector of %d entries for %d rows", what, v->n, n_out);
+  if (p && p->n != n_out) return set_err(ABFT_ERR_INVALID, "%s: p has %d entries for %d rows", what, p->n, n_out);
+  if (!disjoint(scratch, b) || !disjoint(scratch, x) || !disjoint(scratch, r) || (p && !disjoint(scratch, p)))
+    return set_err(ABFT_ERR_INVALID, "%s: the scratch vector overlaps an operand", what);
+  if (p && (!disjoint(r, b) || !disjoint(r, x) || !disjoint(r, p) || !disjoint(p, b) || !disjoint(p, x)))
+    return set_err(ABFT_ERR_INVALID, "%s: r and p must not overlap each other, b or x", what);
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_residual_gap(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *b,
+                                     const abft_hip_vector *x, const abft_hip_vector *r, abft_hip_vector *scratch,
+                                     double out[2]) {
+  if (int rc = bind_block(ctx)) return rc;
+  if (!out) return set_err(ABFT_ERR_INVALID, "residual_gap: null result");
+  if (int rc = check_residual_args("residual_gap", A, b, x, r, scratch, nullptr)) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  if (int rc = spmv_common(ctx, A, x, scratch, 0, nullptr)) return rc;
+  ctx->fused.valid = false;
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_residual_gap(b->d, scratch->d, r->d, b->n, o, ctx->stream));
+  }
+  return results_from_block_slot(ctx, o.seq, 2, out);
+}
+
+extern "C" int abft_hip_residual_restart(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *b,
+                                         const abft_hip_vector *x, abft_hip_vector *r, abft_hip_vector *p,
+                                         abft_hip_vector *scratch, double *rr) {
+  if (int rc = bind_block(ctx)) return rc;
+  if (!rr) return set_err(ABFT_ERR_INVALID, "residual_restart: null result");
+  if (int rc = check_residual_args("residual_restart", A, b, x, r, scratch, p)) return rc;
+  if (int rc = spmv_common(ctx, A, x, scratch, 0, nullptr)) return rc;
+  ctx->fused.valid = false;
+  const ReduceOut o = reduce_out(ctx, nullptr, true);
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_residual_restart(b->d, scratch->d, r->d, p->d, r->n, o, ctx->stream));
+  }
+  return scalar_from_host_slot(ctx, o.seq, rr);
+}
+
+// the block vectors of a block check, against a matrix of N rows (spmm refuses what it cannot run
+// before it enqueues anything)
+static int check_residual_block_args(const char *what, abft_hip_matrix *A, int k,
+                                     std::initializer_list<const abft_hip_vector *> vs, const abft_hip_vector *scratch) {
+  if (!A) return set_err(ABFT_ERR_INVALID, "%s: null matrix", what);
+  const int N = (int)(A->fmt == ABFT_FMT_CSR ? A->csr.n_out : A->coo.n_out);
+  if (int rc = check_block(what, k, N, vs)) return rc;
+  if (int rc = check_block(what, k, N, {scratch})) return rc;
+  for (const abft_hip_vector *v : vs)
+    if (!disjoint(scratch, v)) return set_err(ABFT_ERR_INVALID, "%s: the scratch vector overlaps an operand", what);
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_residual_gap_block(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *B,
+                                           const abft_hip_vector *X, const abft_hip_vector *R,
+                                           abft_hip_vector *scratch, int k, uint32_t active, double *out) {
+  if (int rc = bind_block(ctx)) return rc;
+  if (!out) return set_err(ABFT_ERR_INVALID, "residual_gap_block: null result");
+  if (int rc = check_residual_block_args("residual_gap_block", A, k, {B, X, R}, scratch)) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  if (int rc = abft_hip_spmm(ctx, A, X, scratch, k)) return rc;
+  ctx->fused.valid = false;
+  ReduceOutW o{};
+  o.partials = ctx->bpartials;
+  o.ticket = ctx->ticket;
+  o.host = ctx->wslot_dev;
+  o.ev_count = ctx->ring.count;
+  o.seq = ++ctx->bseq;
+  const int N = B->n / k;
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_residual_gap_block(B->d, scratch->d, R->d, N, k, active, o, ctx->stream));
+  }
+  if (int rc = wait_published(ctx, &ctx->wslot->seq, o.seq)) return rc;
+  for (int j = 0; j < 2 * k; j++) out[j] = ctx->wslot->value[j];
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_residual_restart_block(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *B,
+                                               const abft_hip_vector *X, abft_hip_vector *R, abft_hip_vector *P,
+                                               abft_hip_vector *scratch, int k, uint32_t mask, double *rr) {
+  if (int rc = bind_block(ctx)) return rc;
+  if (!rr) return set_err(ABFT_ERR_INVALID, "residual_restart_block: null result");
+  if (int rc = check_residual_block_args("residual_restart_block", A, k, {B, X, R, P}, scratch)) return rc;
+  if (!disjoint(R, B) || !disjoint(R, X) || !disjoint(R, P) || !disjoint(P, B) || !disjoint(P, X))
+    return set_err(ABFT_ERR_INVALID, "residual_restart_block: R and P must not overlap each other, B or X");
+  if (int rc = block_slot(ctx)) return rc;
+  if (int rc = abft_hip_spmm(ctx, A, X, scratch, k)) return rc;
+  ctx->fused.valid = false;
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_residual_restart_block(B->d, scratch->d, R->d, P->d, B->n / k, k, mask, o, ctx->stream));
+  }
+  return results_from_block_slot(ctx, o.seq, k, rr);
+}
+
+extern "C" int abft_hip_copy_block(abft_hip_ctx *ctx, abft_hip_vector *dst, const abft_hip_vector *src, int k,
+                                   uint32_t mask) {
+  if (int rc = bind_block(ctx)) return rc;
+  if (!dst || !src) return set_err(ABFT_ERR_INVALID, "copy_block: null vector");
+  if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "copy_block: k = %d outside [1, %d]", k, ABFT_MAX_RHS);
+  const int N = dst->n / k;
+  if (int rc = check_block("copy_block", k, N, {dst, src})) return rc;
+  if (dst->d == src->d) return ABFT_OK;
+  if (!disjoint(dst, src)) return set_err(ABFT_ERR_INVALID, "copy_block: dst and src overlap");
+  HIPCHK(launch_copy_block(dst->d, src->d, N, k, mask, ctx->stream));
   return ABFT_OK;
 }
 
@@ -2950,11 +3096,13 @@ extern "C" int abft_hip_pending_events(abft_hip_ctx *ctx) {
   if (ctx)
     for (uint32_t k = 0; k < ABFT_HOST_SLOTS; k++) n = std::max(n, ctx->host_slot[k].evcount);
   if (ctx && ctx->bslot) n = std::max(n, ctx->bslot->evcount);
+  if (ctx && ctx->wslot) n = std::max(n, ctx->wslot->evcount);
   return (int)n;
 }
 static void clear_pending_events(abft_hip_ctx *ctx) {
   for (uint32_t k = 0; k < ABFT_HOST_SLOTS; k++) ctx->host_slot[k].evcount = 0;
   if (ctx->bslot) ctx->bslot->evcount = 0;
+  if (ctx->wslot) ctx->wslot->evcount = 0;
 }
 
 extern "C" int abft_hip_drain_events(abft_hip_ctx *ctx, abft_event *buf, int cap, int *count, int *fatal) {

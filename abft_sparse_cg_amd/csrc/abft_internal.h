@@ -417,6 +417,32 @@ hipError_t launch_calc_xr_block(double *x, double *r, const double *p, const dou
                                 const BlockScalars &alpha, uint32_t active, const ReduceOutK &out, hipStream_t s);
 hipError_t launch_calc_p_block(double *p, const double *r, int n, int k, const BlockScalars &beta, uint32_t active,
                                hipStream_t s);
+// residual checks (abft_hip_residual_*): 2k sums of a block check come back in one wide slot
+struct HostSlotW {
+  double value[2 * ABFT_MAX_RHS];
+  uint32_t evcount;
+  uint32_t seq;
+};
+struct ReduceOutW {
+  double *partials;          // 2 * ABFT_MAX_RHS * ABFT_MAX_PARTIALS doubles, value j's at j * ABFT_MAX_PARTIALS
+  uint32_t *ticket;          // as ReduceOut::ticket
+  HostSlotW *host;           // device alias of the pinned slot
+  const uint32_t *ev_count;
+  uint32_t seq;
+};
+hipError_t launch_flip_vector(double *v, unsigned long long mask, hipStream_t s);
+// {gap2, tt2} = {sum ((b - y) - r)^2, sum (b - y)^2} through the K-wide slot (values 0, 1)
+hipError_t launch_residual_gap(const double *b, const double *y, const double *r, int n, const ReduceOutK &out,
+                               hipStream_t s);
+// r = b - y, p = r; r.r as launch_dot(r, r) forms it
+hipError_t launch_residual_restart(const double *b, const double *y, double *r, double *p, int n, const ReduceOut &out,
+                                   hipStream_t s);
+// n = rows of the block vectors; out value 2j: gap2 of column j, 2j + 1: tt2 (0 for columns not in `active`)
+hipError_t launch_residual_gap_block(const double *b, const double *y, const double *r, int n, int k, uint32_t active,
+                                     const ReduceOutW &out, hipStream_t s);
+hipError_t launch_residual_restart_block(const double *b, const double *y, double *r, double *p, int n, int k,
+                                         uint32_t mask, const ReduceOutK &out, hipStream_t s);
+hipError_t launch_copy_block(double *dst, const double *src, int n, int k, uint32_t mask, hipStream_t s);
 hipError_t launch_publish_pair(const double *pair, HostSlot *host, uint32_t seq, hipStream_t s);
 
 // window exchange over shared host memory (see kernels.hip, peer_exchange_kernel): a 4 KB header

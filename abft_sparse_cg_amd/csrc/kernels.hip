@@ -3463,8 +3463,9 @@ __device__ __forceinline__ void block_store(double *p, const double *v) {
 }
 
 // reduce_finish for K values: K partials per block, one ticket, K fixed-order folds
-template <int K>
-__device__ __forceinline__ void reduce_finish_k(const double *value, const ReduceOutK &o, double *s_w) {
+// (Out: ReduceOutK, or ReduceOutW for the 2K sums of a block residual check)
+template <int K, class Out = ReduceOutK>
+__device__ __forceinline__ void reduce_finish_k(const double *value, const Out &o, double *s_w) {
   __shared__ uint32_t s_last;
   double bv[K];
 #pragma unroll
@@ -3601,6 +3602,219 @@ hipError_t launch_calc_p_block(double *p, const double *r, int n, int k, const B
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
 #define ABFT_OP(K) hipLaunchKernelGGL(calc_p_block_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, active, n)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+// ---- residual checks: the recurrence's r against the true residual b - A x ----
+// The SpMV half of a check is the ordinary one (y = A x into the dead w); these kernels are the
+// one pass behind it.  Single vectors walk elements exactly as dot_kernel<VEC> does, block vectors
+// walk rows exactly as dot_block_kernel<K> does, with the same reductions.
+
+// XOR `mask` into one double (fault injection into a vector: tests and the CLI's --flip-vector)
+__global__ void flip_vector_kernel(double *v, unsigned long long mask) {
+  *v = __longlong_as_double(__double_as_longlong(*v) ^ (long long)mask);
+}
+
+// {gap2, tt2} = {sum ((b - y) - r)^2, sum (b - y)^2}.  (b - y) - r in that order: with r equal to the
+// rounded b - y the gap of every element is exactly 0.
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void residual_gap_kernel(const double *__restrict__ b,
+                                                                  const double *__restrict__ y,
+                                                                  const double *__restrict__ r, int n,
+                                                                  ReduceOutK out) {
+  __shared__ double s_w[16];
+  double acc[2] = {0.0, 0.0};
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      const double2 bv = *reinterpret_cast<const double2 *>(b + i);
+      const double2 yv = *reinterpret_cast<const double2 *>(y + i);
+      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const double tx = bv.x - yv.x, ty = bv.y - yv.y;
+      const double gx = tx - rv.x, gy = ty - rv.y;
+      acc[0] += gx * gx;
+      acc[0] += gy * gy;
+      acc[1] += tx * tx;
+      acc[1] += ty * ty;
+    } else {
+      const double t = b[i] - y[i];
+      const double g = t - r[i];
+      acc[0] += g * g;
+      acc[1] += t * t;
+    }
+  }
+  reduce_finish_k<2>(acc, out, s_w);
+}
+
+// r = b - y, p = r, and r.r.  VEC is the element walk of dot_kernel<VEC> on r (the grid too:
+// reduce_blocks(n)), so r.r is abft_hip_dot(r, r) bit for bit; PAIRS: every operand 16-byte
+// aligned (VEC = 2 without it loads the pairs one by one, same order of additions).
+template <int VEC, bool PAIRS>
+__global__ __launch_bounds__(ABFT_BLOCK) void residual_restart_kernel(const double *__restrict__ b,
+                                                                      const double *__restrict__ y,
+                                                                      double *__restrict__ r, double *__restrict__ p,
+                                                                      int n, ReduceOut out) {
+  __shared__ double s_w[4];
+  double acc = 0.0;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      double2 rv;
+      if (PAIRS) {
+        const double2 bv = *reinterpret_cast<const double2 *>(b + i);
+        const double2 yv = *reinterpret_cast<const double2 *>(y + i);
+        rv = make_double2(bv.x - yv.x, bv.y - yv.y);
+        *reinterpret_cast<double2 *>(r + i) = rv;
+        *reinterpret_cast<double2 *>(p + i) = rv;
+      } else {
+        rv = make_double2(b[i] - y[i], b[i + 1] - y[i + 1]);
+        r[i] = rv.x; r[i + 1] = rv.y;
+        p[i] = rv.x; p[i + 1] = rv.y;
+      }
+      acc += rv.x * rv.x;
+      acc += rv.y * rv.y;
+    } else {
+      const double rs = b[i] - y[i];
+      r[i] = rs;
+      p[i] = rs;
+      acc += rs * rs;
+    }
+  }
+  acc = block_sum(acc, s_w);
+  reduce_finish(acc, out, s_w);
+}
+
+// per column j: out[2j] = gap2, out[2j + 1] = tt2 as residual_gap_kernel forms them; 0 for a column
+// whose bit is clear in `active`
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void residual_gap_block_kernel(const double *__restrict__ b,
+                                                                        const double *__restrict__ y,
+                                                                        const double *__restrict__ r, uint32_t active,
+                                                                        int n, ReduceOutW out) {
+  __shared__ double s_w[16 * K];
+  double acc[2 * K];
+#pragma unroll
+  for (int j = 0; j < 2 * K; j++) acc[j] = 0.0;
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double bv[K], yv[K], rv[K];
+    block_load<K>(b + i * K, bv);
+    block_load<K>(y + i * K, yv);
+    block_load<K>(r + i * K, rv);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const bool on = (active >> j) & 1u;
+      const double t = bv[j] - yv[j];
+      const double g = t - rv[j];
+      acc[2 * j] += on ? g * g : 0.0;
+      acc[2 * j + 1] += on ? t * t : 0.0;
+    }
+  }
+  reduce_finish_k<2 * K>(acc, out, s_w);
+}
+
+// R[:, j] = B[:, j] - Y[:, j], P[:, j] = R[:, j] for the columns set in `mask` (the others keep their
+// bits); rr[j] = R[:, j] . R[:, j] for every column, in dot_block_kernel<K>'s shape
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void residual_restart_block_kernel(const double *__restrict__ b,
+                                                                            const double *__restrict__ y,
+                                                                            double *__restrict__ r,
+                                                                            double *__restrict__ p, uint32_t mask,
+                                                                            int n, ReduceOutK out) {
+  __shared__ double s_w[8 * K];
+  double acc[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) acc[j] = 0.0;
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double bv[K], yv[K], rv[K], pv[K];
+    block_load<K>(b + i * K, bv);
+    block_load<K>(y + i * K, yv);
+    block_load<K>(r + i * K, rv);
+    block_load<K>(p + i * K, pv);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const bool on = (mask >> j) & 1u;
+      const double rs = bv[j] - yv[j];
+      rv[j] = on ? rs : rv[j];
+      pv[j] = on ? rs : pv[j];
+      acc[j] += rv[j] * rv[j];
+    }
+    block_store<K>(r + i * K, rv);
+    block_store<K>(p + i * K, pv);
+  }
+  reduce_finish_k<K>(acc, out, s_w);
+}
+
+// dst[:, j] = src[:, j] for the columns set in `mask` (a select: inf and NaN are copied as they are)
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void copy_block_kernel(double *__restrict__ dst,
+                                                                const double *__restrict__ src, uint32_t mask,
+                                                                int n) {
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double dv[K], sv[K];
+    block_load<K>(dst + i * K, dv);
+    block_load<K>(src + i * K, sv);
+#pragma unroll
+    for (int j = 0; j < K; j++) dv[j] = ((mask >> j) & 1u) ? sv[j] : dv[j];
+    block_store<K>(dst + i * K, dv);
+  }
+}
+
+hipError_t launch_flip_vector(double *v, unsigned long long mask, hipStream_t s) {
+  hipLaunchKernelGGL(flip_vector_kernel, dim3(1), dim3(1), 0, s, v, mask);
+  return hipGetLastError();
+}
+
+hipError_t launch_residual_gap(const double *b, const double *y, const double *r, int n, const ReduceOutK &out,
+                               hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  if (aligned16(b, y, r))
+    hipLaunchKernelGGL(residual_gap_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, n, out);
+  else
+    hipLaunchKernelGGL(residual_gap_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_residual_restart(const double *b, const double *y, double *r, double *p, int n, const ReduceOut &out,
+                                   hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  if (!aligned16(r))  // launch_dot(r, r) would run dot_kernel<1>
+    hipLaunchKernelGGL((residual_restart_kernel<1, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, p, n, out);
+  else if (aligned16(b, y, p))
+    hipLaunchKernelGGL((residual_restart_kernel<2, true>), dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, p, n, out);
+  else
+    hipLaunchKernelGGL((residual_restart_kernel<2, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, p, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_residual_gap_block(const double *b, const double *y, const double *r, int n, int k, uint32_t active,
+                                     const ReduceOutW &out, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K) \
+  hipLaunchKernelGGL(residual_gap_block_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, active, n, out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_residual_restart_block(const double *b, const double *y, double *r, double *p, int n, int k,
+                                         uint32_t mask, const ReduceOutK &out, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K) \
+  hipLaunchKernelGGL(residual_restart_block_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, p, mask, n, out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_copy_block(double *dst, const double *src, int n, int k, uint32_t mask, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K) hipLaunchKernelGGL(copy_block_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, dst, src, mask, n)
   ABFT_BLOCK_K_DISPATCH(ABFT_OP)
 #undef ABFT_OP
   return hipGetLastError();

@@ -253,6 +253,41 @@ int abft_hip_calc_xr_block(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vecto
 int abft_hip_calc_p_block(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, int k,
                           const double *beta, uint32_t active);
 
+/* ---- residual checks: silent corruption of the CG vectors --------------
+ * The matrix is protected element by element; x, r, p and w are not.  A
+ * periodic check compares the recurrence's r with the true residual b - A x
+ * (one SpMV into a scratch vector -- w is dead between calc_p and the next
+ * SpMV -- and one pass over b, A x and r); a failed check lets the caller
+ * restore x from a checkpoint and restart the recurrence from it.  Every entry
+ * starts like the block calls (a pending x update applied, cached results
+ * forgotten); the SpMV is abft_hip_spmv (abft_hip_spmm for the block forms)
+ * with its events.  Sums are tree sums. */
+
+/* XOR bits[0..nbits) (each in [0, 64)) into the double v[index]: fault injection */
+int abft_hip_vector_flip(abft_hip_vector *v, int index, const int *bits, int nbits);
+/* scratch = A x; out[0] = sum ((b - scratch) - r)^2, out[1] = sum (b - scratch)^2 */
+int abft_hip_residual_gap(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *b,
+                          const abft_hip_vector *x, const abft_hip_vector *r,
+                          abft_hip_vector *scratch, double out[2]);
+/* scratch = A x; r = b - scratch; p = r; *rr = r . r, bit for bit what abft_hip_dot(r, r)
+ * returns -- from x = 0 this is the start of the CG loop (copy r <- b, copy p <- r, dot) */
+int abft_hip_residual_restart(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *b,
+                              const abft_hip_vector *x, abft_hip_vector *r, abft_hip_vector *p,
+                              abft_hip_vector *scratch, double *rr);
+/* block form (abft_hip_spmm's matrices): out[2j], out[2j + 1] = the two sums of column j,
+ * 0.0 for a column whose bit is clear in `active` */
+int abft_hip_residual_gap_block(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *B,
+                                const abft_hip_vector *X, const abft_hip_vector *R,
+                                abft_hip_vector *scratch, int k, uint32_t active, double *out);
+/* block form: R and P are rewritten in the columns set in `mask` only (the others keep their
+ * bits); rr[j] = R[:, j] . R[:, j] for every column, bit for bit abft_hip_dot_block(R, R) */
+int abft_hip_residual_restart_block(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *B,
+                                    const abft_hip_vector *X, abft_hip_vector *R, abft_hip_vector *P,
+                                    abft_hip_vector *scratch, int k, uint32_t mask, double *rr);
+/* dst[:, j] = src[:, j] for the columns set in `mask` (checkpoints of block vectors) */
+int abft_hip_copy_block(abft_hip_ctx *ctx, abft_hip_vector *dst, const abft_hip_vector *src, int k,
+                        uint32_t mask);
+
 /* Shard-local forms for the row-partitioned solver: same kernels, but the
  * result stays on the device so a collective can sum it across ranks before
  * the host reads it.  `dev_result` is a device pointer to TWO doubles:
