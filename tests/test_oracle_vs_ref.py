@@ -313,3 +313,87 @@ def test_inject_rand_draws_like_reference(fmt):
             idx, bits = o.inject_rand(kind, flips)
             assert text == "".join("*** flipping bit %d at index %d ***\n" % (b, idx) for b in bits)
             assert np.array_equal(o.stored_words(), words)
+
+
+# ---- IEEE special values (tests/_ieee.py): both sides on the x86 host, so every bit is compared, NaN bits included
+
+def _special():
+    import _ieee
+    return _ieee.special_matrix(n=300, seed=1, long_len=260, boundaries=(16, 64, 257))
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+@pytest.mark.parametrize("mode", MODES)
+def test_spmv_special_values_bit_identical(fmt, mode):
+    B = _special()
+    mat = B.mat(fmt)
+    o = OracleMatrix(fmt, mode, *mat)
+    code, text, ((r1, r2), words) = ref_side("special_spmv/%d/%s" % (fmt, mode), run_captured, ref_flip_spmv, fmt, mode,
+                                             mat, 0, [], B.x, 2)
+    assert code == 0 and text == ""
+    assert np.array_equal(o.stored_words(), words)  # ECC words of NaN, Inf and subnormal values too
+    y1, y2 = o.spmv(B.x), o.spmv(B.x)
+    assert np.array_equal(y1.view(np.uint64), r1.view(np.uint64))
+    assert np.array_equal(y2.view(np.uint64), r2.view(np.uint64))
+    assert np.isnan(y1).any() and np.isinf(y1).any() and (y1.view(np.uint64) == 0).any()
+    assert o.events() == ([], False)
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+@pytest.mark.parametrize("mode", ["sec7", "secded"])
+def test_flip_on_nonfinite_value_same_repair(fmt, mode):
+    B = _special()
+    mat = B.mat(fmt)
+    vals = mat[2]
+    vbit0 = 0 if fmt == CSR else 64
+    for index in np.flatnonzero(~np.isfinite(vals)).tolist():
+        for bit in (vbit0 + 3, vbit0 + 51, vbit0 + 63):
+            code, text, res = ref_side("special_flip/%d/%s/%d/%d" % (fmt, mode, index, bit), run_captured, ref_flip_spmv,
+                                       fmt, mode, mat, index, [bit], B.x)
+            o = OracleMatrix(fmt, mode, *mat)
+            o.inject(index, [bit])
+            y1 = o.spmv(B.x)
+            ev1, fatal = o.events()
+            y2 = o.spmv(B.x)
+            ev2, _ = o.events()
+            assert code == 0 and not fatal and len(ev1) == 1
+            assert ev2 == [] and text == "".join(event_lines(ev1, fmt)), (index, bit)  # repaired once, written back
+            (r1, r2), words = res
+            assert np.array_equal(y1.view(np.uint64), r1.view(np.uint64))
+            assert np.array_equal(y2.view(np.uint64), r2.view(np.uint64))
+            assert np.array_equal(o.stored_words(), words)
+
+
+def test_vector_kernels_special_values_bit_identical():
+    import _ieee
+    cols, rows, vals, n = laplace5(5, 5)
+    m = 777
+    # no NaN inputs here: x86 returns the first operand's payload when both are NaN, and the two builds may
+    # commute a reduction's add, so a NaN input payload beside a generated default NaN has no fixed bits
+    kinds = [v for v in _ieee.ALL_SPECIALS if v == v]
+    a, b, x1, r1, p1, w1 = (_ieee.special_vector(m, s, kinds) for s in range(6))
+    ia, ib = _ieee.exact_pair(m, 1, "negzero")
+    sa, sb = _ieee.exact_pair(m, 2, "sub")
+
+    def ref_vectors():
+        r = Ref(CSR, "none", cols, rows, vals, n)
+        # scalars as arrays: the fixture keeps an array's bytes, a scalar only as a JSON number
+        out = [np.array([r.dot(a, b), r.dot(ia, ib), r.dot(sa, sb)])]
+        for alpha, beta in ((0.37, 1.7), (-0.0, _ieee.INF), (_ieee.INF, -0.0)):
+            x2, r2, p2 = x1.copy(), r1.copy(), p1.copy()
+            rr = r.calc_xr(x2, r2, p1, w1, alpha)
+            r.calc_p(p2, r2, beta)
+            out.append((np.array([rr]), x2, r2, p2))
+        return out
+
+    got = ref_side("special_vectors", ref_vectors)
+    with np.errstate(all="ignore"):
+        assert np.array_equal(np.asarray(got[0]).view(np.uint64),
+                              np.array([ora_dot(a, b), ora_dot(ia, ib), ora_dot(sa, sb)]).view(np.uint64))
+        for (alpha, beta), (rr, x2, r2, p2) in zip(((0.37, 1.7), (-0.0, _ieee.INF), (_ieee.INF, -0.0)), got[1:]):
+            x3, r3, p3 = x1.copy(), r1.copy(), p1.copy()
+            rr3 = ora_calc_xr(x3, r3, p1, w1, alpha)
+            ora_calc_p(p3, r3, beta)
+            assert np.array_equal(np.array([rr3]).view(np.uint64), np.asarray(rr).view(np.uint64))
+            for mine, theirs in ((x3, x2), (r3, r2), (p3, p2)):
+                assert np.array_equal(mine.view(np.uint64), theirs.view(np.uint64))
