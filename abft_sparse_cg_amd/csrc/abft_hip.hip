@@ -4,6 +4,7 @@
 // kernels.hip.  Nothing here prints or exits; nothing here falls back to a CPU
 // path -- a failing HIP call surfaces as ABFT_ERR_HIP.
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -178,6 +179,13 @@ struct abft_hip_matrix {
   // mode none on that layout: the compact column offsets (see CsrCompact) and a host copy of the bases
   CsrCompact compact{};
   std::vector<uint32_t> cbase_host;
+  // ... and the packed codes (see CsrPacked): host copies of the descriptors and the palette pool,
+  // each palette's place in the pool by its 16 entries, and the pool's device capacity (entries)
+  CsrPacked packed{};
+  std::vector<uint2> pdesc_host;
+  std::vector<uint64_t> pal_host;
+  std::map<std::array<uint64_t, ABFT_PAL_ENTRIES>, uint32_t> pal_index;
+  size_t pal_cap = 0;
   std::vector<void *> allocs;
 };
 
@@ -692,6 +700,139 @@ static int compact_after_inject(abft_hip_matrix *m, uint32_t pos) {
   return ABFT_OK;
 }
 
+// Mode none, streaming layout: the one planner of a packed block (see CsrPacked), at create and
+// after an inject.  Elements [e0, e1) with columns c[] and value bits v[] (indexed from e0): true
+// if the block packs, with its base, shift, padded palette (value patterns ascending, zeros behind)
+// and codes[0, e1 - e0).  A block that packs is one the SpMV stages as one tile (as for compact
+// columns) with at most 16 distinct value patterns whose column span fits the bits left over.
+static bool plan_packed_block(uint32_t e0, uint32_t e1, const uint32_t *c, const uint64_t *v, uint32_t &cbase,
+                              uint32_t &shift, std::array<uint64_t, ABFT_PAL_ENTRIES> &pal, uint16_t *codes) {
+  if (e1 < e0 || e1 - (e0 & ~1u) > (uint32_t)ABFT_CSR_TILE) return false;  // walked tile by tile
+  const uint32_t n = e1 - e0;
+  uint32_t nv = 0, lo = n ? c[0] : 0u, hi = lo;
+  pal.fill(0);
+  for (uint32_t i = 0; i < n; i++) {
+    lo = std::min(lo, c[i]);
+    hi = std::max(hi, c[i]);
+    if (std::find(pal.begin(), pal.begin() + nv, v[i]) == pal.begin() + nv) {
+      if (nv == ABFT_PAL_ENTRIES) return false;
+      pal[nv++] = v[i];
+    }
+  }
+  uint32_t k = 0;
+  while ((1u << k) < nv) k++;
+  shift = 16u - k;
+  if (hi - lo >= (1u << shift)) return false;
+  std::sort(pal.begin(), pal.begin() + nv);
+  cbase = lo;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t idx = (uint32_t)(std::lower_bound(pal.begin(), pal.begin() + nv, v[i]) - pal.begin());
+    codes[i] = (uint16_t)((idx << shift) | (c[i] - lo));
+  }
+  return true;
+}
+
+// palettes the pool holds beyond those of create (one per re-planned block at most)
+#define ABFT_PAL_SPARE 1024u
+
+// the descriptor of a packed block whose palette is `pal`: the palette's place in the pool, appended
+// to the host pool if it is new (the caller uploads the pool)
+static uint2 packed_desc(abft_hip_matrix *m, uint32_t cbase, uint32_t shift,
+                         const std::array<uint64_t, ABFT_PAL_ENTRIES> &pal) {
+  auto it = m->pal_index.find(pal);
+  uint32_t no;
+  if (it != m->pal_index.end()) {
+    no = it->second;
+  } else {
+    no = (uint32_t)(m->pal_host.size() / ABFT_PAL_ENTRIES);
+    m->pal_index.emplace(pal, no);
+    m->pal_host.insert(m->pal_host.end(), pal.begin(), pal.end());
+  }
+  return make_uint2(cbase, no << 5 | shift);
+}
+
+// Mode none, streaming layout, at create: packed codes for every block that packs.
+// ABFT_HIP_PACKED=0: none packed, nothing allocated (A/B runs in one build).
+static int build_packed(abft_hip_matrix *m, const uint32_t *columns, const double *values,
+                        const std::vector<uint4> &blk, size_t padded) {
+  if (const char *e = getenv("ABFT_HIP_PACKED"))
+    if (!strcmp(e, "0")) return ABFT_OK;
+  std::vector<uint2> pdesc(blk.size(), make_uint2(0u, 0u));
+  std::vector<uint16_t> codes(padded + 2, 0);  // as cols16: the kernel's loads at even indices stay inside
+  std::array<uint64_t, ABFT_PAL_ENTRIES> pal;
+  std::vector<uint64_t> vb;
+  bool any = false;
+  for (size_t b = 0; b < blk.size(); b++) {
+    const uint32_t e0 = blk[b].z, e1 = blk[b].w;
+    if (e1 < e0 || e1 - (e0 & ~1u) > (uint32_t)ABFT_CSR_TILE) continue;
+    vb.resize(e1 - e0);
+    if (e1 > e0) memcpy(vb.data(), values + e0, (size_t)(e1 - e0) * 8);
+    uint32_t cbase, shift;
+    if (!plan_packed_block(e0, e1, columns + e0, vb.data(), cbase, shift, pal, codes.data() + e0)) continue;
+    pdesc[b] = packed_desc(m, cbase, shift, pal);
+    any = true;
+  }
+  if (!any) {
+    m->pal_host.clear();
+    m->pal_index.clear();
+    return ABFT_OK;
+  }
+  uint16_t *dcode = nullptr;
+  uint2 *ddesc = nullptr;
+  uint64_t *dpal = nullptr;
+  // room for the palettes injects add: sized once, so the pointer every SpMV (and any captured graph)
+  // holds never changes; an inject that would need more demotes its block instead
+  const size_t cap = m->pal_host.size() + ABFT_PAL_SPARE * ABFT_PAL_ENTRIES;
+  int rc;
+  if ((rc = dev_upload(m, &dcode, codes.data(), codes.size(), codes.size())) ||
+      (rc = dev_upload(m, &ddesc, pdesc.data(), pdesc.size(), pdesc.size())) ||
+      (rc = dev_upload(m, &dpal, m->pal_host.data(), m->pal_host.size(), cap)))
+    return rc;
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // codes / pdesc go out of scope
+  m->packed.code16 = dcode;
+  m->packed.pdesc = ddesc;
+  m->packed.pal = reinterpret_cast<const double *>(dpal);
+  m->pal_cap = cap;
+  m->pdesc_host = std::move(pdesc);
+  return ABFT_OK;
+}
+
+// After an inject into element `pos` of a packed block: re-plan the block from the device's
+// vals / cols (the words the SpMV would otherwise read) -- packed anew, with its codes and
+// palette rewritten, or left to the compact / wide path, which compact_after_inject keeps right.
+static int packed_after_inject(abft_hip_matrix *m, uint32_t pos) {
+  const std::vector<uint4> &blk = m->blk_host;
+  auto it = std::upper_bound(blk.begin(), blk.end(), pos, [](uint32_t p, const uint4 &d) { return p < d.z; });
+  if (it == blk.begin()) return ABFT_OK;
+  const size_t b = (size_t)(it - blk.begin()) - 1;
+  if (pos >= blk[b].w || m->pdesc_host[b].y == 0u) return ABFT_OK;
+  const uint32_t e0 = blk[b].z, e1 = blk[b].w, n = e1 - e0;
+  hipStream_t s = m->ctx->stream;
+  std::vector<uint32_t> c(n);
+  std::vector<uint64_t> v(n);
+  std::vector<uint16_t> codes(n);
+  HIPCHK(hipMemcpyAsync(c.data(), m->csr.cols + e0, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(v.data(), m->csr.vals + e0, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  uint32_t cbase, shift;
+  std::array<uint64_t, ABFT_PAL_ENTRIES> pal;
+  uint2 d = make_uint2(0u, 0u);  // demoted unless it packs and its palette fits the pool
+  if (plan_packed_block(e0, e1, c.data(), v.data(), cbase, shift, pal, codes.data()) &&
+      (m->pal_index.count(pal) || m->pal_host.size() + ABFT_PAL_ENTRIES <= m->pal_cap)) {
+    const size_t had = m->pal_host.size();
+    d = packed_desc(m, cbase, shift, pal);
+    if (m->pal_host.size() > had)
+      HIPCHK(hipMemcpyAsync(const_cast<double *>(m->packed.pal) + had, m->pal_host.data() + had,
+                            (m->pal_host.size() - had) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(const_cast<uint16_t *>(m->packed.code16) + e0, codes.data(), (size_t)n * 2,
+                          hipMemcpyHostToDevice, s));
+  }
+  HIPCHK(hipMemcpyAsync(const_cast<uint2 *>(m->packed.pdesc) + b, &d, sizeof(uint2), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));  // `codes` and `d` are local
+  m->pdesc_host[b] = d;  // only once the device holds it
+  return ABFT_OK;
+}
+
 // ---- panel layout planning (host) ----------------------------------------------
 
 struct PanelBuild {
@@ -1163,7 +1304,8 @@ static int create_csr(abft_hip_ctx *ctx, int mode, const uint32_t *columns, cons
   A.rowptr = d_rowptr;
   A.blk = d_blk;
   if (!panels && !sweep && !slice) m->blk_host = blk;
-  if (!panels && !sweep && !slice && mode == ABFT_MODE_NONE && (rc = build_compact_cols(m, columns, blk, padded))) {
+  if (!panels && !sweep && !slice && mode == ABFT_MODE_NONE &&
+      ((rc = build_compact_cols(m, columns, blk, padded)) || (rc = build_packed(m, columns, values, blk, padded)))) {
     matrix_free(m);
     return rc;
   }
@@ -1457,6 +1599,48 @@ extern "C" int abft_hip_matrix_compact_stats(abft_hip_matrix *mat, uint32_t *com
   return ABFT_OK;
 }
 
+extern "C" int abft_hip_matrix_packed_stats(abft_hip_matrix *mat, uint32_t *packed_tiles, uint32_t *tiles,
+                                            uint32_t *mismatches) {
+  if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
+  if (int rc = bind(mat->ctx)) return rc;
+  const bool stream = mat->fmt == ABFT_FMT_CSR && !mat->use_panels && !mat->use_sweep && !mat->use_slice;
+  uint32_t np = 0, bad = 0;
+  const std::vector<uint4> &blk = mat->blk_host;
+  if (stream && mat->packed.pdesc) {
+    // decoded from the device copies, not the host's bookkeeping: what the SpMV reads
+    const CsrDev &A = mat->csr;
+    hipStream_t s = mat->ctx->stream;
+    std::vector<uint2> pdesc(blk.size());
+    std::vector<uint32_t> cols(A.nnz);
+    std::vector<uint64_t> vals(A.nnz), pal(mat->pal_host.size());
+    std::vector<uint16_t> code(A.nnz);
+    HIPCHK(hipMemcpyAsync(pdesc.data(), mat->packed.pdesc, blk.size() * sizeof(uint2), hipMemcpyDeviceToHost, s));
+    if (!pal.empty())
+      HIPCHK(hipMemcpyAsync(pal.data(), mat->packed.pal, pal.size() * 8, hipMemcpyDeviceToHost, s));
+    if (A.nnz) {
+      HIPCHK(hipMemcpyAsync(cols.data(), A.cols, (size_t)A.nnz * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(vals.data(), A.vals, (size_t)A.nnz * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(code.data(), mat->packed.code16, (size_t)A.nnz * 2, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t b = 0; b < blk.size(); b++) {
+      if (pdesc[b].y == 0u) continue;
+      np++;
+      const uint32_t shift = pdesc[b].y & 31u, pbase = (pdesc[b].y >> 5) * ABFT_PAL_ENTRIES;
+      const bool sane = shift >= 12u && shift <= 16u && (size_t)pbase + ABFT_PAL_ENTRIES <= pal.size();
+      for (uint32_t i = blk[b].z; i < blk[b].w && i < A.nnz; i++) {
+        if (!sane) { bad++; continue; }
+        const uint32_t c = pdesc[b].x + (code[i] & ((1u << shift) - 1u));
+        bad += c != cols[i] || pal[pbase + (code[i] >> shift)] != vals[i];
+      }
+    }
+  }
+  if (packed_tiles) *packed_tiles = np;
+  if (tiles) *tiles = stream ? (uint32_t)blk.size() : 0u;
+  if (mismatches) *mismatches = bad;
+  return ABFT_OK;
+}
+
 extern "C" int abft_hip_matrix_destroy(abft_hip_matrix *mat) {
   if (!mat) return ABFT_OK;
   if (int rc = bind(mat->ctx)) return rc;
@@ -1551,7 +1735,10 @@ extern "C" int abft_hip_inject(abft_hip_matrix *mat, uint32_t index, const int *
   // a flipped column bit (bits 64-95 of the CSR word) changes cols[index]: the compact copy follows
   bool col_bit = false;
   for (int k = 0; k < nbits; k++) col_bit = col_bit || bits[k] >= 64;
-  if (mat->fmt == ABFT_FMT_CSR && mat->compact.cbase && col_bit) return compact_after_inject(mat, index);
+  if (mat->fmt == ABFT_FMT_CSR && mat->compact.cbase && col_bit)
+    if (int rc = compact_after_inject(mat, index)) return rc;
+  // any flipped bit of an element of a packed block: the block is planned anew
+  if (mat->fmt == ABFT_FMT_CSR && mat->packed.pdesc) return packed_after_inject(mat, index);
   return ABFT_OK;
 }
 
@@ -2543,7 +2730,7 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
         HIPCHK(launch_spmv_coo_panels(mat->mode, mat->coo, mat->panels, vec->d, result->d, ctx->ring,
                                       do_fuse ? &fuse : nullptr, mat->panel_grid, mat->panel_chunk, ctx->stream));
     } else if (mat->fmt == ABFT_FMT_CSR)
-      HIPCHK(launch_spmv_csr(mat->mode, mat->csr, mat->compact, span, vec->d, result->d, ctx->ring,
+      HIPCHK(launch_spmv_csr(mat->mode, mat->csr, mat->compact, mat->packed, span, vec->d, result->d, ctx->ring,
                              do_fuse ? &fuse : nullptr, ctx->stream));
     else
       HIPCHK(launch_spmv_coo(mat->mode, mat->coo, vec->d, result->d, ctx->ring, do_fuse ? &fuse : nullptr, ctx->stream));

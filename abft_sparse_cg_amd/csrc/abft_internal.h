@@ -42,6 +42,22 @@ struct CsrCompact {
   const uint32_t *cbase;   // nblk: the block's smallest column, or ABFT_CBASE_WIDE (read through cols)
 };
 
+// Mode none, streaming row-block layout: *packed* blocks, whose elements the SpMV reads as one
+// u16 code each -- column and value together, 2 bytes instead of 10 -- for the blocks it stages
+// as one tile that hold at most 16 distinct values (by 64-bit pattern) and whose columns fit the
+// bits the palette index leaves: k = ceil(log2(#values)), shift = 16 - k, max - min col < 2^shift.
+//   col = cbase + (code & ((1 << shift) - 1)),   val = pal[pbase + (code >> shift)]
+// Palettes are padded to 16 entries (any index a code can hold stays inside its own palette) and
+// shared by every block with the same value set (config 2: one palette of {-1, 4}).  `vals` and
+// `cols` stay authoritative; abft_hip_inject re-plans a packed block it flips (packed anew, or the
+// compact / wide path).  Kept apart from CsrDev and CsrCompact for the same reason as CsrCompact.
+#define ABFT_PAL_ENTRIES 16u
+struct CsrPacked {
+  const uint16_t *code16;  // cols' padded length + 2, or NULL: none packed
+  const uint2 *pdesc;      // nblk: {cbase, (pbase / 16) << 5 | shift}; .y == 0: not packed (shift is 12..16)
+  const double *pal;       // the palette pool, ABFT_PAL_ENTRIES per palette
+};
+
 // Panel ("column-blocked") layout for matrices whose columns are scattered over
 // a vector much larger than an XCD's 4 MB L2 (random / unstructured).  Rows are
 // cut into groups of ABFT_PANEL_ROWS, columns into panels of `width` entries
@@ -159,6 +175,9 @@ struct CooDev {
 // Tuning knobs (overridable with -D for A/B builds; defaults are the measured best)
 #ifndef ABFT_CFG_CSR_EPT
 #define ABFT_CFG_CSR_EPT 4
+#endif
+#ifndef ABFT_CFG_PACKED_PAL
+#define ABFT_CFG_PACKED_PAL 0  // packed tiles' palette lookup: 0 ds_bpermute, 1 scalar-loaded + selects, 2 vector load
 #endif
 #ifndef ABFT_CFG_COO_EPT
 #define ABFT_CFG_COO_EPT 4
@@ -327,8 +346,8 @@ hipError_t launch_spmv_coo_panels(int mode, const CooDev &A, const CsrPanels &P,
 // (`big`: where a multi-workgroup fold of many partials meets; see fold_partials_kernel)
 struct FixArgs;
 hipError_t launch_fuse_finalize(const FuseOut &f, uint32_t nblk, const ReduceOut &big, const FixArgs *fix, hipStream_t s);
-hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const TileSpan &span, const double *x,
-                           double *y, EventRing ev, const FuseOut *fuse, hipStream_t s);
+hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
+                           const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s);
 hipError_t launch_spmv_coo(int mode, const CooDev &A, const double *x, double *y, EventRing ev,
                            const FuseOut *fuse, hipStream_t s);
 // behind every COO SpMV: see MovedList.  With a fused product the fix-up runs inside the fold

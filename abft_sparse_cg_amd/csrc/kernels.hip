@@ -588,6 +588,79 @@ __device__ __forceinline__ void csr_stage_none(const CsrDev &A, const CsrCompact
   csr_consume<MODE_NONE, EPT>(A, x, ev, base, lo, hi, t, s_prod, s_col, false, 0u, 0u, unused);
 }
 
+// Mode none, one packed tile (see CsrPacked): the only streamed load is the u16 code, one dword
+// (two codes) per step at the slots csr_stage uses, so the LDS layout and everything behind the
+// barrier stay as they are.  The palette is wave-held: lane l loads entry l & 15 (an L2 hit: the
+// pool is a few hundred bytes), and each element's value comes from the lane its index names by
+// ds_bpermute -- no LDS traffic, no barrier, no select chain.  The product is the same v_mul_f64
+// of the same two operands as csr_consume's, so y is bit-identical.  The slot before e0 (odd e0)
+// holds the previous block's code: masked invalid like in csr_stage; its index reads this
+// block's palette all the same (padded to 16 entries) and its column gathers nothing.
+template <int EPT>
+__device__ __forceinline__ void csr_stage_packed(const CsrDev &A, const CsrPacked &cp, uint2 pd,
+                                                 const double *__restrict__ x, uint32_t base, uint32_t lo,
+                                                 uint32_t hi, double *s_prod) {
+  constexpr int STEPS = EPT / 2;
+  const uint32_t shift = pd.y & 31u, mask = (1u << shift) - 1u;  // uniform
+  const uint32_t pbase = (pd.y >> 5) * ABFT_PAL_ENTRIES;
+#if ABFT_CFG_PACKED_PAL == 0
+  const double pal = cp.pal[pbase + (threadIdx.x & (ABFT_PAL_ENTRIES - 1u))];
+  const int pal_lo = __double2loint(pal), pal_hi = __double2hiint(pal);
+#elif ABFT_CFG_PACKED_PAL == 1
+  double pal[ABFT_PAL_ENTRIES];  // uniform: scalar loads
+#pragma unroll
+  for (uint32_t e = 0; e < ABFT_PAL_ENTRIES; e++) pal[e] = cp.pal[pbase + e];
+#endif
+  uint32_t raw[STEPS];
+#pragma unroll
+  for (int s = 0; s < STEPS; s++) {
+    const uint32_t i = base + 2u * threadIdx.x + (uint32_t)s * (2u * ABFT_BLOCK);
+    const uint32_t ii = i < hi ? i : base;  // always a valid, even element index
+    raw[s] = STREAM_LOAD(reinterpret_cast<const uint32_t *>(cp.code16 + ii));
+  }
+  uint32_t col[EPT];
+  double val[EPT];
+  bool ok[EPT];
+#pragma unroll
+  for (int j = 0; j < EPT; j++) {
+    const int s = j >> 1;
+    const uint32_t i = base + 2u * threadIdx.x + (uint32_t)s * (2u * ABFT_BLOCK) + (uint32_t)(j & 1);
+    const uint32_t code = (j & 1) ? raw[s] >> 16 : raw[s] & 0xFFFFu;
+    const uint32_t idx = code >> shift;  // <= 15
+    col[j] = pd.x + (code & mask);
+#if ABFT_CFG_PACKED_PAL == 0
+    const int src = (int)(idx << 2);  // byte address of the palette lane
+    val[j] = as_double((uint32_t)__builtin_amdgcn_ds_bpermute(src, pal_lo),
+                       (uint32_t)__builtin_amdgcn_ds_bpermute(src, pal_hi));
+#elif ABFT_CFG_PACKED_PAL == 1
+    double l1[8], l2[4], l3[2];  // select tree on the index bits
+#pragma unroll
+    for (int e = 0; e < 8; e++) l1[e] = (idx & 1u) ? pal[2 * e + 1] : pal[2 * e];
+#pragma unroll
+    for (int e = 0; e < 4; e++) l2[e] = (idx & 2u) ? l1[2 * e + 1] : l1[2 * e];
+#pragma unroll
+    for (int e = 0; e < 2; e++) l3[e] = (idx & 4u) ? l2[2 * e + 1] : l2[2 * e];
+    val[j] = (idx & 8u) ? l3[1] : l3[0];
+#else
+    val[j] = cp.pal[pbase + idx];  // a per-lane load of the (cache-resident) palette
+#endif
+    ok[j] = i >= lo && i < hi;
+  }
+  double xv[EPT];
+#pragma unroll
+  for (int j = 0; j < EPT; j++) {
+    const bool in = ok[j] && col[j] < A.n_in;  // a corrupted index must never fault the GPU
+    xv[j] = gather_load(x + (in ? col[j] : 0u));
+    if (!in) xv[j] = 0.0;
+  }
+#pragma unroll
+  for (int s = 0; s < STEPS; s++) {
+    const uint32_t k = 2u * threadIdx.x + (uint32_t)s * (2u * ABFT_BLOCK);
+    const double p0 = val[2 * s] * xv[2 * s], p1 = val[2 * s + 1] * xv[2 * s + 1];
+    *reinterpret_cast<double2 *>(s_prod + k) = make_double2(ok[2 * s] ? p0 : 0.0, ok[2 * s + 1] ? p1 : 0.0);
+  }
+}
+
 // Constraints mode: the reference's two checks of element i (CSR/CPUContext.cpp:186-200) on
 // the staged columns -- its column against the vector's size, then against its row successor's
 // (read from the matrix when element i is the last one staged).  Returns false if a fatal event
@@ -664,7 +737,8 @@ __device__ __forceinline__ bool csr_row_sum(const CsrDev &A, const EventRing &ev
 template <int MODE, int EPT, bool FUSE>
 __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const double *__restrict__ x,
                                                               double *__restrict__ y, EventRing ev,
-                                                              FuseOut fuse, TileSpan span, CsrCompact cc) {
+                                                              FuseOut fuse, TileSpan span, CsrCompact cc,
+                                                              CsrPacked cp) {
   constexpr uint32_t TILE = ABFT_BLOCK * EPT;
   __shared__ __attribute__((aligned(16))) double s_prod[TILE];
   __shared__ __attribute__((aligned(16))) uint32_t s_col[MODE == MODE_CONSTRAINTS ? TILE : 2];
@@ -673,6 +747,8 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
   const uint4 desc = A.blk[t];  // one scalar load instead of two dependent pairs
   // mode none: this tile's column base (by tile, not workgroup: span cut / skip), uniform
   const uint32_t cb = (MODE == MODE_NONE && cc.cbase) ? cc.cbase[t] : ABFT_CBASE_WIDE;
+  // ... and its packed-code descriptor (.y == 0: not packed), uniform as well
+  const uint2 pd = (MODE == MODE_NONE && cp.pdesc) ? cp.pdesc[t] : make_uint2(0u, 0u);
   // bit 31 of the second word: every row of this block has the same length (banded
   // matrices: nearly all blocks), so the row pointers need not be read at all
   const bool uniform = ABFT_CFG_UNIFORM_ROWS && MODE != MODE_CONSTRAINTS && (desc.y >> 31) != 0u;
@@ -694,7 +770,9 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
       }
       if (FUSE) xr = x[fuse.x_off + r];
     }
-    if (MODE == MODE_NONE)
+    if (MODE == MODE_NONE && pd.y != 0u)
+      csr_stage_packed<EPT>(A, cp, pd, x, base, e0, e1, s_prod);
+    else if (MODE == MODE_NONE)
       csr_stage_none<EPT>(A, cc, cb, x, ev, base, e0, e1, s_prod, s_col);
     else
       csr_stage<MODE, EPT>(A, x, ev, base, e0, e1, s_prod, s_col);
@@ -874,31 +952,34 @@ int spmv_csr_panels_blocks_per_cu(int mode, bool fuse) {
 }
 
 template <int MODE>
-static hipError_t launch_spmv_csr_mode(const CsrDev &A, const CsrCompact &cc, const TileSpan &span, const double *x,
-                                       double *y, EventRing ev, const FuseOut *fuse, hipStream_t s) {
+static hipError_t launch_spmv_csr_mode(const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
+                                       const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s) {
   if (fuse) {
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
-                       x, y, ev, *fuse, span, cc);
+                       x, y, ev, *fuse, span, cc, cp);
   } else
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, false>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
-                       x, y, ev, FuseOut{}, span, cc);
+                       x, y, ev, FuseOut{}, span, cc, cp);
   return hipGetLastError();
 }
 
-hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const TileSpan &span, const double *x,
-                           double *y, EventRing ev, const FuseOut *fuse, hipStream_t s) {
+hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
+                           const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s) {
   // every tile the span maps to must exist: checked here, on the host
   if (span.count == 0) return hipSuccess;
   if ((uint64_t)span.first + span.count + span.skip > A.nblk || span.cut > span.count) return hipErrorInvalidValue;
   // compact columns only in mode none, and then both arrays
   if ((cc.cbase || cc.cols16) && (mode != MODE_NONE || !cc.cbase || !cc.cols16)) return hipErrorInvalidValue;
+  // packed codes likewise, and then all three arrays
+  if ((cp.code16 || cp.pdesc || cp.pal) && (mode != MODE_NONE || !cp.code16 || !cp.pdesc || !cp.pal))
+    return hipErrorInvalidValue;
   switch (mode) {
-    case MODE_NONE: return launch_spmv_csr_mode<MODE_NONE>(A, cc, span, x, y, ev, fuse, s);
-    case MODE_CONSTRAINTS: return launch_spmv_csr_mode<MODE_CONSTRAINTS>(A, cc, span, x, y, ev, fuse, s);
-    case MODE_SED: return launch_spmv_csr_mode<MODE_SED>(A, cc, span, x, y, ev, fuse, s);
-    case MODE_SEC7: return launch_spmv_csr_mode<MODE_SEC7>(A, cc, span, x, y, ev, fuse, s);
-    case MODE_SEC8: return launch_spmv_csr_mode<MODE_SEC8>(A, cc, span, x, y, ev, fuse, s);
-    case MODE_SECDED: return launch_spmv_csr_mode<MODE_SECDED>(A, cc, span, x, y, ev, fuse, s);
+    case MODE_NONE: return launch_spmv_csr_mode<MODE_NONE>(A, cc, cp, span, x, y, ev, fuse, s);
+    case MODE_CONSTRAINTS: return launch_spmv_csr_mode<MODE_CONSTRAINTS>(A, cc, cp, span, x, y, ev, fuse, s);
+    case MODE_SED: return launch_spmv_csr_mode<MODE_SED>(A, cc, cp, span, x, y, ev, fuse, s);
+    case MODE_SEC7: return launch_spmv_csr_mode<MODE_SEC7>(A, cc, cp, span, x, y, ev, fuse, s);
+    case MODE_SEC8: return launch_spmv_csr_mode<MODE_SEC8>(A, cc, cp, span, x, y, ev, fuse, s);
+    case MODE_SECDED: return launch_spmv_csr_mode<MODE_SECDED>(A, cc, cp, span, x, y, ev, fuse, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -144,6 +144,12 @@ int abft_hip_matrix_info(abft_hip_matrix *mat, int *layout, int *launches_per_sp
  * differs from the stored column (0 unless the copies have come apart).  Any pointer may be NULL. */
 int abft_hip_matrix_compact_stats(abft_hip_matrix *mat, uint32_t *compact_tiles, uint32_t *tiles,
                                   uint32_t *mismatches);
+/* Mode none, streaming row-block CSR layout (measurement and tests only): *tiles as above, *packed_tiles =
+ * row blocks whose elements the SpMV reads as one 16-bit code each (column offset and value palette index),
+ * *mismatches = elements of packed blocks whose decoded (column, value) differs bitwise from the stored
+ * (cols, vals) (0 unless the copies have come apart).  Any pointer may be NULL. */
+int abft_hip_matrix_packed_stats(abft_hip_matrix *mat, uint32_t *packed_tiles, uint32_t *tiles,
+                                 uint32_t *mismatches);
 
 /* Read back the stored (ECC-encoded) arrays in the caller's element order.
  * CSR: cols[nnz], rowptr[nrows+1], values[nnz].  Any pointer may be NULL. */
