@@ -2,8 +2,10 @@
 formats, ABFT modes, layouts (streaming / forced panels), SpMV in one or two parts, single
 and double bit flips -- stored words, y (bit for bit, two passes) and event streams against
 the CPU oracle.  The long form (`python tools/fuzz_parity.py 300`: ~20 000 cases) is run by
-hand; its last result is quoted in DESIGN.md."""
+hand; its last result is quoted in DESIGN.md.  The same for its packed family and for the
+call-sequence campaign, without and with injects."""
 import os
+import re
 import subprocess
 import sys
 
@@ -28,3 +30,33 @@ def test_short_call_sequence_campaign():
                        capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-1000:]
     assert " 0 failures" in p.stdout
+
+
+def test_short_call_sequence_campaign_with_injects():
+    """The same with ABFT_FUZZ_SEQ_INJECT=1: in mode none an `inject` operation flips bits of an element
+    between the other calls (in a packed block that re-plans the block); the fused dot, the deferred x
+    update and the device-scalar iteration must hold across it."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_sequence.py"), "15", "700000"],
+                       capture_output=True, text=True, timeout=300, env=dict(os.environ, ABFT_FUZZ_SEQ_INJECT="1"))
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-1000:]
+    assert " 0 failures" in p.stdout
+    assert int(re.search(r"injects: (\d+)", p.stdout).group(1)) > 100, p.stdout[-500:]
+
+
+def test_short_packed_family_campaign():
+    """tools/fuzz_parity.py with ABFT_FUZZ_FAMILY=packed: matrices whose row blocks pack, spans around
+    every threshold of the planner, shards, up to 40 flips that re-plan blocks, the block SpMV.  A
+    campaign that stops reaching one of the classes its summary counts is a failure too, and so is
+    one that skips a mode-none case, or more than half of the others (a fatal event ends a case: the
+    reference stops there; tests/test_fuzz_generator.py measures that share from the oracle alone)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_parity.py"), "20", "100000"],
+                       capture_output=True, text=True, timeout=300, env=dict(os.environ, ABFT_FUZZ_FAMILY="packed"))
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-1000:]
+    assert " 0 failures" in p.stdout
+    reached = dict(re.findall(r"(\w+)=(\d+)", re.search(r"^reached: (.*)$", p.stdout, re.M).group(1)))
+    assert set(reached) == {"packed_at_creation", "k0", "k1", "k2", "k3", "k4", "replan_kept", "demoted_by_palette",
+                            "demoted_by_span", "inject_before_parts", "shard", "spmm"}
+    assert all(int(v) > 0 for v in reached.values()), reached
+    skipped, others = (int(v) for v in re.search(r"skipped after a fatal event: (\d+) of the (\d+) cases in other modes",
+                                                 p.stdout).groups())
+    assert "none of the" in p.stdout and others > 0 and 2 * skipped <= others, p.stdout[-500:]

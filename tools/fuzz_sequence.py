@@ -5,7 +5,11 @@ is the state the library keeps across calls -- the dot fused into the SpMV and t
 deferred from calc_xr into calc_p must be invisible under every interleaving: vectors
 bit-identical to the model whenever they are read, scalars within the reductions' tolerance.
 
-    python tools/fuzz_sequence.py [seconds] [first_seed]"""
+    python tools/fuzz_sequence.py [seconds] [first_seed]
+
+ABFT_FUZZ_SEQ_INJECT=1 adds an operation (its own meaning of the seeds): in mode none, `inject` flips
+bits of an element in the library's matrix and in the oracle's -- in a packed block that re-plans the
+block -- and everything after it must hold as before.  The summary then counts the injects made."""
 import os
 import sys
 import time
@@ -15,7 +19,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 from _oracle import CSR, OracleMatrix, laplace5, random_spd  # noqa: E402
+
+import fuzz_gen  # noqa: E402
 
 import abft_sparse_cg_amd as amd  # noqa: E402
 from abft_sparse_cg_amd import capi  # noqa: E402
@@ -25,8 +32,14 @@ def bits_equal(a, b):
     return np.array_equal(np.asarray(a).view(np.uint64), np.asarray(b).view(np.uint64))
 
 
+INJECTS = [0]
+
+
 def one_case(seed):
     rng = np.random.default_rng(seed)
+    inject = os.environ.get("ABFT_FUZZ_SEQ_INJECT") == "1"
+    ops = ["spmv", "dot", "calc_xr", "calc_p", "copy", "download", "upload", "cgstep", "devstep"] + (["inject", "inject"] if inject else [])
+    flipped = []
     if os.environ.get("ABFT_FUZZ_SEQ_GRID"):  # e.g. 12,19: every case on that Laplacian (hunting a size-specific failure)
         g, h = (int(v) for v in os.environ["ABFT_FUZZ_SEQ_GRID"].split(","))
         cols, rows, vals, n = laplace5(g, h)
@@ -78,7 +91,7 @@ def one_case(seed):
                         d = np.nonzero(a.view(np.uint32) != b.view(np.uint32))[0]
                         return ("seed %d step %d: the ORACLE's %s changed behind %s (n %d, nnz %d, mode %s): words %s were %s are %s"
                                 % (seed, step, name, last_op, n, len(vals), mode, d[:8], a.view(np.uint32)[d[:8]], b.view(np.uint32)[d[:8]]))
-            op = str(rng.choice(["spmv", "dot", "calc_xr", "calc_p", "copy", "download", "upload", "cgstep", "devstep"]))
+            op = str(rng.choice(ops))
             ids = [int(i) for i in rng.permutation(NV)]
             trace.append((op, ids[:4]))
             last_op = "%s %s (after %s)" % (op, ids[:4], trace[-3:-1])
@@ -136,6 +149,18 @@ def one_case(seed):
                         return "seed %d step %d %s: devstep r.r %r vs %r" % (seed, step, trace[-6:], got[2], want_rr)
                     beta = np.float64(got[2]) / np.float64(cur)
                     model[p] = model[r] + beta * model[p]
+            elif op == "inject":
+                if mode == "none":  # (the other modes would detect it: events, and the end of the reference's run)
+                    oc, _, ov = o.csr_arrays()
+                    near = flipped[-1][0] + int(rng.integers(0, 8)) if flipped and rng.random() < 0.5 else int(rng.integers(0, len(vals)))
+                    i, bits = fuzz_gen.sequence_flip(rng, oc, ov.view(np.uint64), min(len(vals) - 1, near), n, flipped)
+                    o.inject(i, bits)
+                    ctx.inject_at(A, i, bits)
+                    flipped.append((i, bits))
+                    INJECTS[0] += 1
+                    trace[-1] = (op, [i] + bits)
+                    if watch:
+                        image = o.csr_arrays()
             elif op == "calc_p":
                 p, r = ids[:2]
                 beta = float(rng.uniform(-0.9, 0.9))
@@ -182,6 +207,8 @@ def main():
         seed += 1
         if done % 5000 == 0:
             print("... %d sequences, %d failures, %.0f s" % (done, bad, time.time() - t0), flush=True)
+    if os.environ.get("ABFT_FUZZ_SEQ_INJECT") == "1":
+        print("injects: %d" % INJECTS[0], flush=True)
     print("fuzz_sequence: %d sequences, %d failures" % (done, bad), flush=True)
     return 1 if bad else 0
 
