@@ -89,6 +89,13 @@ SIGNATURES = {
     "abft_hip_residual_gap_block": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, f64p]),
     "abft_hip_residual_restart_block": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, f64p]),
     "abft_hip_copy_block": (C.c_int, [vp, vp, vp, C.c_int, C.c_uint32]),
+    "abft_hip_matrix_diag_inverse": (C.c_int, [vp, vp, vp, u32p]),
+    "abft_hip_precond_start": (C.c_int, [vp, vp, vp, vp, f64p]),
+    "abft_hip_calc_xr_precond": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_double, f64p]),
+    "abft_hip_calc_p_precond": (C.c_int, [vp, vp, vp, vp, C.c_double]),
+    "abft_hip_precond_start_block": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_uint32, f64p]),
+    "abft_hip_calc_xr_precond_block": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, f64p, C.c_uint32, f64p]),
+    "abft_hip_calc_p_precond_block": (C.c_int, [vp, vp, vp, vp, C.c_int, f64p, C.c_uint32]),
     "abft_hip_dot_dev": (C.c_int, [vp, vp, vp, vp]),
     "abft_hip_calc_xr_dev": (C.c_int, [vp, vp, vp, vp, vp, C.c_double, vp]),
     "abft_hip_read_pair": (C.c_int, [vp, vp, f64p, f64p]),

@@ -60,6 +60,8 @@ Additional options of this build:
                               After iteration I, flip bit(s) B (0-63) of entry J of
                               vector V (x, r or p; with --rhs K, J = row * K + column)
                               (may be repeated)
+      --precond         P     Preconditioner: none (default) or jacobi (the inverse
+                              diagonal of A, applied inside the vector kernels)
 
 """
 
@@ -72,7 +74,7 @@ def fail(msg):
 def parse(argv):
     o = dict(num_blocks=25, max_itrs=1000, conv=0.001, matrix_file=DEFAULT_MTX, synthetic=None, target="cpu",
              mode="none", flips=0, kind="ANY", seed=None, quiet=False, flip_at=None, fmt="csr", list=False,
-             rhs=1, check_every=0, check_tol=1e-7, max_rollbacks=3, flip_vector=[])
+             rhs=1, check_every=0, check_tol=1e-7, max_rollbacks=3, flip_vector=[], precond="none")
 
     def num(s, conv):
         try:
@@ -163,6 +165,10 @@ def parse(argv):
             if flip[0] < 0 or flip[1] not in ("x", "r", "p") or flip[2] < 0 or not all(0 <= b < 64 for b in flip[3]):
                 fail(msg)
             o["flip_vector"] = o["flip_vector"] + [flip]
+        elif a == "--precond":
+            o["precond"] = arg("Invalid preconditioner (want none or jacobi)")
+            if o["precond"] not in ("none", "jacobi"):
+                fail("Invalid preconditioner (want none or jacobi)")
         elif a in ("--quiet", "-q"):
             o["quiet"] = True
         elif a in ("--help", "-h"):
@@ -233,6 +239,19 @@ def print_check_summary(checks):
     print("residual checks: %d passed, %d failed" % (checks.get(True, 0), checks.get(False, 0)))
 
 
+def make_preconditioner(o, ctx, A):
+    """--precond: None, or the Jacobi vector (after the injected flips: it sees the matrix the solve runs on)"""
+    if o["precond"] == "none":
+        return None
+    try:
+        dinv = ctx.jacobi(A)
+    except ValueError as e:
+        ctx.close()
+        fail(str(e))
+    print("preconditioner: jacobi")
+    return dinv
+
+
 def main(argv=None):
     argv = sys.argv if argv is None else argv
     o = parse(argv)
@@ -294,6 +313,7 @@ def run_single(o):
             print("*** flipping bit %d at index %d ***" % (bit, index))
         ctx.inject_at(A, index, bits)
     vecs = vector_flips(o, n, {"x": x, "r": r, "p": p})
+    dinv = make_preconditioner(o, ctx, A)
     bound = o["check_tol"] * float(np.linalg.norm(generators.reference_rhs(n)))
     checks = {}
 
@@ -306,7 +326,8 @@ def run_single(o):
     try:
         itr, rr = cg_solve(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
                            check_every=o["check_every"], check_tol=o["check_tol"], max_rollbacks=o["max_rollbacks"],
-                           on_check=lambda i, gap, ok, back: report_check(checks, "", i, gap, ok, back, bound))
+                           on_check=lambda i, gap, ok, back: report_check(checks, "", i, gap, ok, back, bound),
+                           precond=dinv)
     except ResidualCheckFailed as e:
         print("[ABFT] %s" % e)
         ctx.close()
@@ -347,6 +368,7 @@ def run_block(o):
         ctx.inject_at(A, index, bits)
 
     vecs = vector_flips(o, n * K, {"x": x, "r": r, "p": p})
+    dinv = make_preconditioner(o, ctx, A)
     bounds = [o["check_tol"] * float(np.linalg.norm(generators.reference_rhs(n, seed=1 + j))) for j in range(K)]
     checks = {}
 
@@ -362,7 +384,7 @@ def run_block(o):
     try:
         itrs, _ = cg_solve_block(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
                                  check_every=o["check_every"], check_tol=o["check_tol"],
-                                 max_rollbacks=o["max_rollbacks"], on_check=on_check)
+                                 max_rollbacks=o["max_rollbacks"], on_check=on_check, precond=dinv)
     except ResidualCheckFailed as e:
         print("[ABFT] %s" % e)
         ctx.close()

@@ -310,6 +310,69 @@ class HIPContext:
         """dst[:, j] = src[:, j] for the columns set in `mask`"""
         check(self.L.abft_hip_copy_block(self.h, dst.h, src.h, k, int(mask)))
 
+    # ---- Jacobi preconditioning (include/abft_hip.h) ----
+    def jacobi(self, mat, strict=True):
+        """-> a new Vector dinv, dinv[i] = 1 / (sum of the diagonal elements of row i), the Jacobi
+        preconditioner of cg_solve(..., precond=dinv).  Rows without a positive finite diagonal get 1.0;
+        their number is dinv.bad, and with strict they raise ValueError (Jacobi wants a positive diagonal)."""
+        dinv = self.create_vector(mat.n_out)
+        bad = C.c_uint32(0)
+        try:
+            check(self.L.abft_hip_matrix_diag_inverse(self.h, mat.h, dinv.h, C.byref(bad)))
+        except capi.AbftError:
+            self.destroy_vector(dinv)
+            raise
+        dinv.bad = bad.value
+        if strict and bad.value:
+            self.destroy_vector(dinv)
+            raise ValueError("jacobi: %d of %d rows have no positive finite diagonal (strict=False sets their "
+                             "entries to 1.0)" % (bad.value, mat.n_out))
+        return dinv
+
+    def precond_start(self, r, dinv, p):
+        """p = z = dinv * r; -> (r . z, r . r), the second the bits dot(r, r) gives"""
+        out = np.zeros(2)
+        check(self.L.abft_hip_precond_start(self.h, r.h, dinv.h, p.h, out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return float(out[0]), float(out[1])
+
+    def calc_xr_precond(self, x, r, p, w, dinv, alpha):
+        """x += alpha p; r -= alpha w; -> (r . z, r . r) of the new r, z = dinv * r"""
+        out = np.zeros(2)
+        check(self.L.abft_hip_calc_xr_precond(self.h, x.h, r.h, p.h, w.h, dinv.h, alpha,
+                                              out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return float(out[0]), float(out[1])
+
+    def calc_p_precond(self, p, r, dinv, beta):
+        """p = dinv * r + beta p"""
+        check(self.L.abft_hip_calc_p_precond(self.h, p.h, r.h, dinv.h, beta))
+
+    def precond_start_block(self, R, dinv, P, k, mask):
+        """P[:, j] = dinv * R[:, j] for the columns set in `mask`; -> (rz[k], rr[k]) of every column"""
+        out = np.zeros(2 * k)
+        check(self.L.abft_hip_precond_start_block(self.h, R.h, dinv.h, P.h, k, int(mask),
+                                                  out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return out[0::2].copy(), out[1::2].copy()
+
+    def calc_xr_precond_block(self, x, r, p, w, dinv, k, alpha, active):
+        """calc_xr_block with one dinv for all columns; -> (rz[k], rr[k]) of every column"""
+        a = np.zeros(capi.MAX_RHS)
+        a[:k] = alpha
+        out = np.zeros(2 * k)
+        check(self.L.abft_hip_calc_xr_precond_block(self.h, x.h, r.h, p.h, w.h, dinv.h, k, a.ctypes.data_as(capi.f64p),
+                                                    int(active), out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return out[0::2].copy(), out[1::2].copy()
+
+    def calc_p_precond_block(self, p, r, dinv, k, beta, active):
+        """p[:, j] = dinv * r[:, j] + beta[j] p[:, j] for the columns j set in `active`"""
+        b = np.zeros(capi.MAX_RHS)
+        b[:k] = beta
+        check(self.L.abft_hip_calc_p_precond_block(self.h, p.h, r.h, dinv.h, k, b.ctypes.data_as(capi.f64p),
+                                                   int(active)))
+
     def matrix_info(self, mat):
         """-> (layout: 'stream' | 'panels' | 'sweep' | 'slice', kernel launches per spmv) -- measurement only"""
         lay, n = C.c_int(0), C.c_int(0)
@@ -452,7 +515,7 @@ def _check_args(check_every, check_tol, max_rollbacks):
 
 
 def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None, check_every=0,
-             check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None):
+             check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None, precond=None):
     """The reference driver's CG loop, call for call (cg.cpp:87-118).
 
     check_every > 0 adds residual checks: after iteration i when (i + 1) %
@@ -464,11 +527,21 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
     failure at max_itrs, raise ResidualCheckFailed.  on_check(itr, gap, ok, rolled_back_to): itr the
     iteration the check follows (-1: the start), gap = ||b - A x - r||, rolled_back_to the iteration of
     the restored checkpoint (-1: the start) or None.  itr counts every iteration run, repeated ones
-    included.  With check_every=0 the calls are exactly the loop's above."""
+    included.  With check_every=0 the calls are exactly the loop's above.
+
+    precond: a vector dinv (ctx.jacobi(A)) turns the loop into Jacobi-preconditioned CG (DESIGN.md section
+    5d): z = dinv * r is formed inside precond_start / calc_xr_precond / calc_p_precond, which replace
+    copy p <- r + dot, calc_xr and calc_p; alpha = r.z / p.w, beta = r.z_new / r.z.  The stop test, on_iteration
+    and the residual checks stay on r.r and on r against b - A x (neither depends on M); a restart is followed
+    by precond_start on the restarted r.  With precond=None the calls are exactly those without it."""
     _check_args(check_every, check_tol, max_rollbacks)
     ctx.copy_vector(r, b)
-    ctx.copy_vector(p, r)
-    rr = ctx.dot(r, r)
+    rz = None
+    if precond is None:
+        ctx.copy_vector(p, r)
+        rr = ctx.dot(r, r)
+    else:
+        rz, rr = ctx.precond_start(r, precond, p)
     itr = 0
     noted = {}
     note_threshold(rr, conv_threshold, noted)
@@ -481,7 +554,7 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
         st = dict(checked=False, ckpt=-1, fails=0, records=[])
 
         def check():
-            nonlocal rr
+            nonlocal rr, rz
             gap2, tt2 = ctx.residual_gap(A, b, x, r, w)
             ok = _check_passes(gap2, tt2, bb, check_tol)
             gap = math.sqrt(gap2) if gap2 >= 0 else gap2
@@ -494,6 +567,8 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
                 back = st["ckpt"]
                 ctx.copy_vector(x, x_ckpt)
                 rr = ctx.residual_restart(A, b, x, r, p, w)
+                if precond is not None:
+                    rz, rr = ctx.precond_start(r, precond, p)  # p = z of the restarted r
                 note_threshold(rr, conv_threshold, noted)
             st["checked"] = True
             st["records"].append((itr - 1, gap, ok, back))
@@ -514,10 +589,16 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
                 continue
             ctx.spmv(A, p, w)
             pw = ctx.dot(p, w)
-            alpha = fdiv(rr, pw)
-            rr_new = ctx.calc_xr(x, r, p, w, alpha)
-            beta = fdiv(rr_new, rr)
-            ctx.calc_p(p, r, beta)
+            if precond is None:
+                alpha = fdiv(rr, pw)
+                rr_new = ctx.calc_xr(x, r, p, w, alpha)
+                beta = fdiv(rr_new, rr)
+                ctx.calc_p(p, r, beta)
+            else:
+                alpha = fdiv(rz, pw)
+                rz_new, rr_new = ctx.calc_xr_precond(x, r, p, w, precond, alpha)
+                ctx.calc_p_precond(p, r, precond, fdiv(rz_new, rz))
+                rz = rz_new
             rr = rr_new
             note_threshold(rr, conv_threshold, noted)
             if on_iteration is not None:
@@ -534,7 +615,7 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
 
 
 def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None, check_every=0,
-                   check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None):
+                   check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None, precond=None):
     """cg_solve for the K columns of block vectors (ctx.create_block) at once: per column j exactly
     cg_solve's control flow -- column j iterates while itrs[j] < max_itrs and rr[j] > conv_threshold --
     on one spmm / dot_block / calc_xr_block / calc_p_block per iteration.  A column that has stopped
@@ -546,14 +627,22 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
     residual_gap_block; a failed column alone is restored (copy_block from x_ckpt, a block vector made
     here when None) and restarted (residual_restart_block with its bit in the mask); the other columns'
     x, r, p keep their bits.  on_check(itr, gap, ok, rolled_back_to, rhs), itr counting column rhs's
-    iterations."""
+    iterations.
+
+    precond: as in cg_solve, one N-entry dinv for all K columns (one operator), through the *_precond_block
+    calls; after a rollback precond_start_block rewrites P in the rolled-back columns only."""
     _check_args(check_every, check_tol, max_rollbacks)
     k = B.K
     if not k:
         raise ValueError("cg_solve_block wants block vectors (create_block)")
     ctx.copy_vector(R, B)
-    ctx.copy_vector(P, R)
-    rr = np.array(ctx.dot_block(R, R, k), dtype=np.float64)
+    rz = None
+    if precond is None:
+        ctx.copy_vector(P, R)
+        rr = np.array(ctx.dot_block(R, R, k), dtype=np.float64)
+    else:
+        rz, rr = ctx.precond_start_block(R, precond, P, k, (1 << k) - 1)
+        rz, rr = np.array(rz, dtype=np.float64), np.array(rr, dtype=np.float64)
     itrs = [0] * k
     noted = {}
     for j in range(k):
@@ -592,6 +681,11 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
             if failed:
                 ctx.copy_block(X, x_ckpt, k, failed)
                 rr_new = ctx.residual_restart_block(A, B, X, R, P, W, k, failed)
+                if precond is not None:
+                    rz_new, rr_new = ctx.precond_start_block(R, precond, P, k, failed)
+                    for j in range(k):
+                        if (failed >> j) & 1:
+                            rz[j] = rz_new[j]
                 for j in range(k):
                     if (failed >> j) & 1:
                         rr[j] = rr_new[j]
@@ -624,12 +718,20 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
             on = [(active >> j) & 1 for j in range(k)]
             ctx.spmm(A, P, W, k, drain=False)
             pw = ctx.dot_block(P, W, k)
-            alpha = [fdiv(rr[j], pw[j]) if on[j] else 0.0 for j in range(k)]
-            rr_new = ctx.calc_xr_block(X, R, P, W, k, alpha, active)
-            beta = [fdiv(rr_new[j], rr[j]) if on[j] else 0.0 for j in range(k)]
-            ctx.calc_p_block(P, R, k, beta, active)
+            if precond is None:
+                alpha = [fdiv(rr[j], pw[j]) if on[j] else 0.0 for j in range(k)]
+                rr_new = ctx.calc_xr_block(X, R, P, W, k, alpha, active)
+                beta = [fdiv(rr_new[j], rr[j]) if on[j] else 0.0 for j in range(k)]
+                ctx.calc_p_block(P, R, k, beta, active)
+            else:
+                alpha = [fdiv(rz[j], pw[j]) if on[j] else 0.0 for j in range(k)]
+                rz_new, rr_new = ctx.calc_xr_precond_block(X, R, P, W, precond, k, alpha, active)
+                beta = [fdiv(rz_new[j], rz[j]) if on[j] else 0.0 for j in range(k)]
+                ctx.calc_p_precond_block(P, R, precond, k, beta, active)
             for j in range(k):
                 if on[j]:
+                    if precond is not None:
+                        rz[j] = rz_new[j]
                     rr[j] = rr_new[j]
                     itrs[j] += 1
                     note_threshold(rr[j], conv_threshold, noted)

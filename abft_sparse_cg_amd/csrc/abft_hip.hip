@@ -3054,6 +3054,249 @@ extern "C" int abft_hip_copy_block(abft_hip_ctx *ctx, abft_hip_vector *dst, cons
   return ABFT_OK;
 }
 
+// ---- Jacobi preconditioning (include/abft_hip.h): the inverse diagonal, and the vector kernels with ----
+// z = dinv * r fused in.  The arguments are checked before anything is enqueued (dinv overlapping a
+// vector the call writes: ABFT_ERR_INVALID).  The vector entries then start like the residual entries
+// -- a speculation is voided, the fused product and the learned iteration are forgotten: they write
+// vectors those caches may name -- and a pending x += alpha p is applied, except by the
+// calc_p_precond that can absorb it.
+
+static bool is_shard(const abft_hip_matrix *m) {
+  return m->fmt == ABFT_FMT_CSR ? (m->csr.n_in != m->csr.n_out || m->csr.index_base != 0 || m->csr.gidx)
+                                : (m->coo.n_in != m->coo.n_out || m->coo.index_base != 0 || m->coo.gidx);
+}
+
+// cold path of the permuted layouts (panels, sweep, slice): the caller-order read-back, summed on the host
+static int diag_from_readback(abft_hip_matrix *mat, uint32_t colmask, std::vector<double> &d) {
+  const uint32_t N = (uint32_t)d.size();
+  if (mat->fmt == ABFT_FMT_CSR) {
+    const uint32_t nnz = mat->csr.nnz;
+    std::vector<uint32_t> cols((size_t)nnz + 1), rowptr((size_t)N + 1);
+    std::vector<double> vals((size_t)nnz + 1);
+    if (int rc = abft_hip_matrix_read_csr(mat, cols.data(), rowptr.data(), vals.data())) return rc;
+    for (uint32_t row = 0; row < N; row++) {
+      const uint32_t hi = std::min(rowptr[row + 1], nnz), lo = std::min(rowptr[row], hi);
+      for (uint32_t e = lo; e < hi; e++)
+        if ((cols[e] & colmask) == row) d[row] += vals[e];
+    }
+    return ABFT_OK;
+  }
+  const uint32_t nnz = mat->coo.nnz;
+  std::vector<uint4> el((size_t)nnz + 1);
+  if (int rc = abft_hip_matrix_read_coo(mat, el.data())) return rc;
+  for (uint32_t e = 0; e < nnz; e++) {
+    const uint32_t c = el[e].x & colmask;
+    if (c == el[e].y && c < N) {
+      double v;
+      memcpy(&v, &el[e].z, sizeof(v));
+      d[c] += v;
+    }
+  }
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_matrix_diag_inverse(abft_hip_ctx *ctx, abft_hip_matrix *mat, abft_hip_vector *dinv,
+                                            uint32_t *bad) {
+  if (!mat || !dinv || !bad) return set_err(ABFT_ERR_INVALID, "diag_inverse: null argument");
+  if (is_shard(mat))
+    return set_err(ABFT_ERR_INVALID, "diag_inverse: the matrix is a shard; the diagonal is taken from a whole square matrix");
+  const uint32_t N = mat->fmt == ABFT_FMT_CSR ? mat->csr.n_out : mat->coo.n_out;
+  if ((uint32_t)dinv->n != N)
+    return set_err(ABFT_ERR_INVALID, "diag_inverse: a vector of %d entries for %u rows", dinv->n, N);
+  if (int rc = bind(ctx)) return rc;
+  ctx->fused.valid = false;
+  spec_forget(ctx);
+  *bad = 0;
+  if (!N) return ABFT_OK;
+  hipStream_t s = ctx->stream;
+  const uint32_t colmask = mat->mode >= ABFT_MODE_SED ? ABFT_COLMASK_HOST : 0xFFFFFFFFu;
+  if (mat->use_panels || mat->use_sweep || mat->use_slice) {
+    std::vector<double> d(N, 0.0);
+    if (int rc = diag_from_readback(mat, colmask, d)) return rc;
+    uint32_t nbad = 0;
+    for (uint32_t i = 0; i < N; i++) {
+      if (d[i] > 0.0 && std::isfinite(d[i])) {
+        d[i] = 1.0 / d[i];
+      } else {
+        d[i] = 1.0;
+        nbad++;
+      }
+    }
+    HIPCHK(hipMemcpyAsync(dinv->d, d.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));  // `d` goes out of scope
+    *bad = nbad;
+    return ABFT_OK;
+  }
+  uint32_t *count = reinterpret_cast<uint32_t *>(ctx->bits_dev);  // inject's scratch words: free between calls
+  HIPCHK(hipMemsetAsync(count, 0, sizeof(uint32_t), s));
+  HIPCHK(mat->fmt == ABFT_FMT_CSR ? launch_diag_csr(mat->csr, colmask, dinv->d, count, s)
+                                  : launch_diag_coo(mat->coo, colmask, dinv->d, count, s));
+  HIPCHK(hipMemcpyAsync(bad, count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return ABFT_OK;
+}
+
+// the prologue of the preconditioned vector entries (see above)
+static int bind_precond(abft_hip_ctx *ctx, bool keep_deferred = false) {
+  if (int rc = bind(ctx, keep_deferred)) return rc;
+  ctx->fused.valid = false;
+  spec_forget(ctx);
+  return ABFT_OK;
+}
+
+static int check_precond(const char *what, std::initializer_list<const abft_hip_vector *> reads,
+                         std::initializer_list<const abft_hip_vector *> writes, const abft_hip_vector *dinv) {
+  if (!dinv) return set_err(ABFT_ERR_INVALID, "%s: null vector", what);
+  for (const abft_hip_vector *v : reads)
+    if (int rc = check_same(v, dinv, what)) return rc;
+  for (const abft_hip_vector *v : writes) {
+    if (int rc = check_same(v, dinv, what)) return rc;
+    if (dinv->n && !disjoint(v, dinv))
+      return set_err(ABFT_ERR_INVALID, "%s: dinv overlaps a vector the call writes", what);
+  }
+  return ABFT_OK;
+}
+
+static int pair_from_block_slot(abft_hip_ctx *ctx, uint32_t seq, double out[2]) {
+  return results_from_block_slot(ctx, seq, 2, out);
+}
+
+extern "C" int abft_hip_precond_start(abft_hip_ctx *ctx, const abft_hip_vector *r, const abft_hip_vector *dinv,
+                                      abft_hip_vector *p, double out[2]) {
+  if (!out) return set_err(ABFT_ERR_INVALID, "precond_start: null result");
+  if (int rc = check_precond("precond_start", {r}, {p}, dinv)) return rc;
+  if (r->n && !disjoint(r, p)) return set_err(ABFT_ERR_INVALID, "precond_start: r and p overlap");
+  if (int rc = bind_precond(ctx)) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_precond_start(r->d, dinv->d, p->d, r->n, o, ctx->stream));
+  }
+  return pair_from_block_slot(ctx, o.seq, out);
+}
+
+extern "C" int abft_hip_calc_xr_precond(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r,
+                                        const abft_hip_vector *p, const abft_hip_vector *w,
+                                        const abft_hip_vector *dinv, double alpha, double out[2]) {
+  if (!out) return set_err(ABFT_ERR_INVALID, "calc_xr_precond: null result");
+  if (int rc = check_precond("calc_xr_precond", {p, w}, {x, r}, dinv)) return rc;
+  if (int rc = bind_precond(ctx)) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  // the x half waits for the calc_p_precond that reads the same p next, under calc_xr's own rule
+  // (calc_xr_launch): x aliased by no other operand, its raw pointer never handed out
+  const bool defer = ctx->defer_enabled && x->n > 0 && !(x->root ? x->root : x)->exposed && disjoint(x, r) &&
+                     disjoint(x, p) && disjoint(x, w) && disjoint(r, p);
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_xr_precond(defer ? nullptr : x->d, r->d, p->d, w->d, dinv->d, alpha, x->n, o, ctx->stream));
+  }
+  if (defer) {
+    ctx->defer.active = true;
+    ctx->defer.on_dev = false;
+    ctx->defer.x = x->d; ctx->defer.p = p->d; ctx->defer.n = x->n; ctx->defer.alpha = alpha;
+  }
+  return pair_from_block_slot(ctx, o.seq, out);
+}
+
+extern "C" int abft_hip_calc_p_precond(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r,
+                                       const abft_hip_vector *dinv, double beta) {
+  if (int rc = check_precond("calc_p_precond", {r}, {p}, dinv)) return rc;
+  if (int rc = bind_precond(ctx, true)) return rc;
+  if (ctx->defer.active) {
+    abft_hip_vector xv;  // just the range, for the overlap tests
+    xv.d = ctx->defer.x; xv.n = ctx->defer.n;
+    if (ctx->defer.p == p->d && ctx->defer.n == p->n && !ctx->defer.on_dev && disjoint(&xv, r) && disjoint(&xv, dinv)) {
+      ctx->defer.active = false;
+      KernelTimer t(ctx, ABFT_K_CALC_P);
+      HIPCHK(launch_calc_p_precond(p->d, r->d, dinv->d, ctx->defer.x, beta, ctx->defer.alpha, p->n, ctx->stream));
+      return ABFT_OK;
+    }
+    if (int rc = flush_deferred(ctx)) return rc;
+  }
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_p_precond(p->d, r->d, dinv->d, nullptr, beta, 0.0, p->n, ctx->stream));
+  return ABFT_OK;
+}
+
+// the block vectors of a preconditioned block call and its N-entry dinv, which no written block may overlap
+static int check_precond_block(const char *what, int k, std::initializer_list<const abft_hip_vector *> reads,
+                               std::initializer_list<const abft_hip_vector *> writes, const abft_hip_vector *dinv) {
+  if (!dinv) return set_err(ABFT_ERR_INVALID, "%s: null vector", what);
+  if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "%s: k = %d outside [1, %d]", what, k, ABFT_MAX_RHS);
+  const int N = dinv->n;
+  if (int rc = check_block(what, k, N, reads)) return rc;
+  if (int rc = check_block(what, k, N, writes)) return rc;
+  for (const abft_hip_vector *v : writes)
+    if (N && !disjoint(v, dinv)) return set_err(ABFT_ERR_INVALID, "%s: dinv overlaps a vector the call writes", what);
+  return ABFT_OK;
+}
+
+static ReduceOutW reduce_out_w(abft_hip_ctx *ctx) {
+  ReduceOutW o{};
+  o.partials = ctx->bpartials;
+  o.ticket = ctx->ticket;
+  o.host = ctx->wslot_dev;
+  o.ev_count = ctx->ring.count;
+  o.seq = ++ctx->bseq;
+  return o;
+}
+
+static int results_from_wide_slot(abft_hip_ctx *ctx, uint32_t seq, int count, double *out) {
+  if (int rc = wait_published(ctx, &ctx->wslot->seq, seq)) return rc;
+  for (int j = 0; j < count; j++) out[j] = ctx->wslot->value[j];
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_precond_start_block(abft_hip_ctx *ctx, const abft_hip_vector *R, const abft_hip_vector *dinv,
+                                            abft_hip_vector *P, int k, uint32_t mask, double *out) {
+  if (!out) return set_err(ABFT_ERR_INVALID, "precond_start_block: null result");
+  if (int rc = check_precond_block("precond_start_block", k, {R}, {P}, dinv)) return rc;
+  if (R->n && !disjoint(R, P)) return set_err(ABFT_ERR_INVALID, "precond_start_block: R and P overlap");
+  if (int rc = bind_precond(ctx)) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  const ReduceOutW o = reduce_out_w(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_precond_start_block(R->d, dinv->d, P->d, dinv->n, k, mask, o, ctx->stream));
+  }
+  return results_from_wide_slot(ctx, o.seq, 2 * k, out);
+}
+
+extern "C" int abft_hip_calc_xr_precond_block(abft_hip_ctx *ctx, abft_hip_vector *X, abft_hip_vector *R,
+                                              const abft_hip_vector *P, const abft_hip_vector *W,
+                                              const abft_hip_vector *dinv, int k, const double *alpha, uint32_t active,
+                                              double *out) {
+  if (!alpha || !out) return set_err(ABFT_ERR_INVALID, "calc_xr_precond_block: null argument");
+  if (int rc = check_precond_block("calc_xr_precond_block", k, {P, W}, {X, R}, dinv)) return rc;
+  if (X->n && (!disjoint(X, R) || !disjoint(X, P) || !disjoint(X, W) || !disjoint(R, P) || !disjoint(R, W)))
+    return set_err(ABFT_ERR_INVALID, "calc_xr_precond_block: x and r must not overlap each other or p, w");
+  if (int rc = bind_precond(ctx)) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  BlockScalars a{};
+  for (int j = 0; j < k; j++) a.v[j] = alpha[j];
+  const ReduceOutW o = reduce_out_w(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_xr_precond_block(X->d, R->d, P->d, W->d, dinv->d, dinv->n, k, a, active, o, ctx->stream));
+  }
+  return results_from_wide_slot(ctx, o.seq, 2 * k, out);
+}
+
+extern "C" int abft_hip_calc_p_precond_block(abft_hip_ctx *ctx, abft_hip_vector *P, const abft_hip_vector *R,
+                                             const abft_hip_vector *dinv, int k, const double *beta, uint32_t active) {
+  if (!beta) return set_err(ABFT_ERR_INVALID, "calc_p_precond_block: null argument");
+  if (int rc = check_precond_block("calc_p_precond_block", k, {R}, {P}, dinv)) return rc;
+  if (P->n && !disjoint(P, R)) return set_err(ABFT_ERR_INVALID, "calc_p_precond_block: p and r overlap");
+  if (int rc = bind_precond(ctx)) return rc;
+  BlockScalars b{};
+  for (int j = 0; j < k; j++) b.v[j] = beta[j];
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_p_precond_block(P->d, R->d, dinv->d, dinv->n, k, b, active, ctx->stream));
+  return ABFT_OK;
+}
+
 extern "C" int abft_hip_matrix_panels(abft_hip_matrix *mat, int *npanels, int *width) {
   if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
   if (npanels) *npanels = mat->use_sweep ? (int)mat->sweep.npanels : mat->use_slice ? (int)mat->slice.npanels : 1;

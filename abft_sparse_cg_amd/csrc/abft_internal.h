@@ -462,6 +462,27 @@ hipError_t launch_residual_gap_block(const double *b, const double *y, const dou
 hipError_t launch_residual_restart_block(const double *b, const double *y, double *r, double *p, int n, int k,
                                          uint32_t mask, const ReduceOutK &out, hipStream_t s);
 hipError_t launch_copy_block(double *dst, const double *src, int n, int k, uint32_t mask, hipStream_t s);
+// Jacobi preconditioning (abft_hip_*_precond*): z = dinv * r formed in registers; {r.z, r.r} through the K-wide
+// slot (values 0, 1), the block forms' 2k sums (2j: r.z, 2j + 1: r.r of column j) through the wide one
+hipError_t launch_precond_start(const double *r, const double *dinv, double *p, int n, const ReduceOutK &out,
+                                hipStream_t s);
+// x == nullptr: r -= alpha w alone (x += alpha p is deferred to launch_calc_p_precond)
+hipError_t launch_calc_xr_precond(double *x, double *r, const double *p, const double *w, const double *dinv,
+                                  double alpha, int n, const ReduceOutK &out, hipStream_t s);
+// p = z + beta p; x != nullptr: and x += alpha p with p as it was
+hipError_t launch_calc_p_precond(double *p, const double *r, const double *dinv, double *x, double beta, double alpha,
+                                 int n, hipStream_t s);
+hipError_t launch_precond_start_block(const double *r, const double *dinv, double *p, int n, int k, uint32_t mask,
+                                      const ReduceOutW &out, hipStream_t s);
+hipError_t launch_calc_xr_precond_block(double *x, double *r, const double *p, const double *w, const double *dinv,
+                                        int n, int k, const BlockScalars &alpha, uint32_t active, const ReduceOutW &out,
+                                        hipStream_t s);
+hipError_t launch_calc_p_precond_block(double *p, const double *r, const double *dinv, int n, int k,
+                                       const BlockScalars &beta, uint32_t active, hipStream_t s);
+// dinv[i] = 1 / (sum of row i's diagonal elements) over the stored arrays of the streaming CSR / grouped COO
+// layout; *bad (device) counts the rows left at 1.0
+hipError_t launch_diag_csr(const CsrDev &A, uint32_t colmask, double *dinv, uint32_t *bad, hipStream_t s);
+hipError_t launch_diag_coo(const CooDev &A, uint32_t colmask, double *dinv, uint32_t *bad, hipStream_t s);
 hipError_t launch_publish_pair(const double *pair, HostSlot *host, uint32_t seq, hipStream_t s);
 
 // window exchange over shared host memory (see kernels.hip, peer_exchange_kernel): a 4 KB header

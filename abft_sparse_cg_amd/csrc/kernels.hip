@@ -3901,6 +3901,366 @@ hipError_t launch_copy_block(double *dst, const double *src, int n, int k, uint3
   return hipGetLastError();
 }
 
+// ---- Jacobi preconditioning: z = dinv * r, one rounded product formed in registers, never stored ----
+// The preconditioned forms of the vector kernels above.  Each walks the vectors exactly as the kernel
+// it stands in for (same grid reduce_blocks(n), same stride, VEC by the alignment of the SAME operands;
+// PAIRS: dinv -- and p where it is only written -- are 16-byte aligned too, else their pairs move one
+// entry at a time, same order of operations), and every reduction has that kernel's shape: per thread a
+// serial sum, block_sum, the last block's fixed-order fold.  With dinv == 1.0 in every entry z is r bit
+// for bit, so both sums are the bits the plain kernel returns.  Two sums per call, {sum r z, sum r r},
+// through the K-wide slot as residual_gap_kernel returns its two.
+template <bool PAIRS>
+__device__ __forceinline__ double2 pair_load(const double *v, long i) {
+  if (PAIRS) return *reinterpret_cast<const double2 *>(v + i);
+  return make_double2(v[i], v[i + 1]);
+}
+template <bool PAIRS>
+__device__ __forceinline__ void pair_store(double *v, long i, double2 t) {
+  if (PAIRS) {
+    *reinterpret_cast<double2 *>(v + i) = t;
+  } else {
+    v[i] = t.x; v[i + 1] = t.y;
+  }
+}
+
+// p = z; {r.z, r.r}.  Walks r as dot_kernel<VEC> does on dot(r, r).
+template <int VEC, bool PAIRS>
+__global__ __launch_bounds__(ABFT_BLOCK) void precond_start_kernel(const double *__restrict__ r,
+                                                                   const double *__restrict__ dinv,
+                                                                   double *__restrict__ p, int n, ReduceOutK out) {
+  __shared__ double s_w[16];
+  double acc[2] = {0.0, 0.0};
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const double2 dv = pair_load<PAIRS>(dinv, i);
+      const double2 zv = make_double2(dv.x * rv.x, dv.y * rv.y);
+      pair_store<PAIRS>(p, i, zv);
+      acc[0] += rv.x * zv.x;
+      acc[0] += rv.y * zv.y;
+      acc[1] += rv.x * rv.x;
+      acc[1] += rv.y * rv.y;
+    } else {
+      const double rs = r[i];
+      const double z = dinv[i] * rs;
+      p[i] = z;
+      acc[0] += rs * z;
+      acc[1] += rs * rs;
+    }
+  }
+  reduce_finish_k<2>(acc, out, s_w);
+}
+
+// r -= alpha w; {r.z, r.r} of the new r.  XHALF = false walks as calc_r_kernel<VEC> does (x += alpha p
+// is left to the calc_p_precond that follows), XHALF = true as calc_xr_kernel<VEC> with x += alpha p.
+// (x, r: no __restrict__ -- operands that alias each other take the XHALF form)
+template <int VEC, bool PAIRS, bool XHALF>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_xr_precond_kernel(double *x, double *r, const double *p,
+                                                                     const double *w,
+                                                                     const double *__restrict__ dinv, double alpha,
+                                                                     int n, ReduceOutK out) {
+  __shared__ double s_w[16];
+  double acc[2] = {0.0, 0.0};
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const double2 wv = *reinterpret_cast<const double2 *>(w + i);
+      const double2 dv = pair_load<PAIRS>(dinv, i);
+      if (XHALF) {
+        double2 xv = *reinterpret_cast<const double2 *>(x + i);
+        const double2 pv = *reinterpret_cast<const double2 *>(p + i);
+        xv.x += alpha * pv.x; xv.y += alpha * pv.y;
+        *reinterpret_cast<double2 *>(x + i) = xv;
+      }
+      rv.x -= alpha * wv.x; rv.y -= alpha * wv.y;
+      *reinterpret_cast<double2 *>(r + i) = rv;
+      const double zx = dv.x * rv.x, zy = dv.y * rv.y;
+      acc[0] += rv.x * zx;
+      acc[0] += rv.y * zy;
+      acc[1] += rv.x * rv.x;
+      acc[1] += rv.y * rv.y;
+    } else {
+      const double d = dinv[i];
+      const double rs = r[i] - alpha * w[i];
+      if (XHALF) x[i] = x[i] + alpha * p[i];
+      r[i] = rs;
+      const double z = d * rs;
+      acc[0] += rs * z;
+      acc[1] += rs * rs;
+    }
+  }
+  reduce_finish_k<2>(acc, out, s_w);
+}
+
+// p = z + beta p, z recomputed from the operands calc_xr_precond multiplied (the same bits).  XHALF:
+// with the x += alpha p the preceding calc_xr_precond left behind, walking as calc_px_kernel<VEC> does
+// (p as calc_xr saw it); else as calc_p_kernel<VEC>.
+template <int VEC, bool PAIRS, bool XHALF>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_p_precond_kernel(double *__restrict__ p,
+                                                                    const double *__restrict__ r,
+                                                                    const double *__restrict__ dinv,
+                                                                    double *__restrict__ x, double beta, double alpha,
+                                                                    int n) {
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      double2 pv = *reinterpret_cast<const double2 *>(p + i);
+      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const double2 dv = pair_load<PAIRS>(dinv, i);
+      if (XHALF) {
+        double2 xv = *reinterpret_cast<const double2 *>(x + i);
+        xv.x += alpha * pv.x; xv.y += alpha * pv.y;
+        *reinterpret_cast<double2 *>(x + i) = xv;
+      }
+      const double zx = dv.x * rv.x, zy = dv.y * rv.y;
+      pv.x = zx + beta * pv.x;
+      pv.y = zy + beta * pv.y;
+      *reinterpret_cast<double2 *>(p + i) = pv;
+    } else {
+      const double ps = p[i];
+      const double z = dinv[i] * r[i];
+      if (XHALF) x[i] = x[i] + alpha * ps;
+      p[i] = z + beta * ps;
+    }
+  }
+}
+
+// VEC and PAIRS of one launch: `vec2` the alignment test of the plain kernel's operands, `pairs` that of the rest
+#define ABFT_PRECOND_DISPATCH(KERNEL, XH, ...)                                                              \
+  do {                                                                                                      \
+    if (!vec2)                                                                                              \
+      hipLaunchKernelGGL((KERNEL<1, false, XH>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);            \
+    else if (pairs)                                                                                         \
+      hipLaunchKernelGGL((KERNEL<2, true, XH>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);             \
+    else                                                                                                    \
+      hipLaunchKernelGGL((KERNEL<2, false, XH>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);            \
+  } while (0)
+
+hipError_t launch_precond_start(const double *r, const double *dinv, double *p, int n, const ReduceOutK &out,
+                                hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  if (!aligned16(r))  // launch_dot(r, r) would run dot_kernel<1>
+    hipLaunchKernelGGL((precond_start_kernel<1, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, r, dinv, p, n, out);
+  else if (aligned16(dinv, p))
+    hipLaunchKernelGGL((precond_start_kernel<2, true>), dim3(nb), dim3(ABFT_BLOCK), 0, s, r, dinv, p, n, out);
+  else
+    hipLaunchKernelGGL((precond_start_kernel<2, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, r, dinv, p, n, out);
+  return hipGetLastError();
+}
+
+// x == nullptr: the r half alone (launch_calc_r's walk), else launch_calc_xr's
+hipError_t launch_calc_xr_precond(double *x, double *r, const double *p, const double *w, const double *dinv,
+                                  double alpha, int n, const ReduceOutK &out, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  const bool pairs = aligned16(dinv);
+  if (x) {
+    const bool vec2 = aligned16(x, r, p, w);
+    ABFT_PRECOND_DISPATCH(calc_xr_precond_kernel, true, x, r, p, w, dinv, alpha, n, out);
+  } else {
+    const bool vec2 = aligned16(r, w);
+    ABFT_PRECOND_DISPATCH(calc_xr_precond_kernel, false, x, r, p, w, dinv, alpha, n, out);
+  }
+  return hipGetLastError();
+}
+
+// x == nullptr: p = z + beta p alone (launch_calc_p's walk), else with x += alpha p (launch_calc_px's)
+hipError_t launch_calc_p_precond(double *p, const double *r, const double *dinv, double *x, double beta, double alpha,
+                                 int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+  const bool pairs = aligned16(dinv);
+  if (x) {
+    const bool vec2 = aligned16(p, r, x);
+    ABFT_PRECOND_DISPATCH(calc_p_precond_kernel, true, p, r, dinv, x, beta, alpha, n);
+  } else {
+    const bool vec2 = aligned16(p, r);
+    ABFT_PRECOND_DISPATCH(calc_p_precond_kernel, false, p, r, dinv, x, beta, alpha, n);
+  }
+  return hipGetLastError();
+}
+#undef ABFT_PRECOND_DISPATCH
+
+// Block forms: one thread per row over the K columns, as the block kernels above; dinv[i] is loaded
+// once per row (one operator for all columns).  A column whose bit is clear keeps its bits (a
+// select).  Sums in dot_block_kernel<K>'s shape, value 2j = column j's r.z, 2j + 1 its r.r, for every
+// column, through the 2K-wide slot.
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void precond_start_block_kernel(const double *__restrict__ r,
+                                                                         const double *__restrict__ dinv,
+                                                                         double *__restrict__ p, uint32_t mask, int n,
+                                                                         ReduceOutW out) {
+  __shared__ double s_w[16 * K];
+  double acc[2 * K];
+#pragma unroll
+  for (int j = 0; j < 2 * K; j++) acc[j] = 0.0;
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double rv[K], pv[K];
+    const double d = dinv[i];
+    block_load<K>(r + i * K, rv);
+    block_load<K>(p + i * K, pv);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const double z = d * rv[j];
+      pv[j] = ((mask >> j) & 1u) ? z : pv[j];
+      acc[2 * j] += rv[j] * z;
+      acc[2 * j + 1] += rv[j] * rv[j];
+    }
+    block_store<K>(p + i * K, pv);
+  }
+  reduce_finish_k<2 * K>(acc, out, s_w);
+}
+
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_xr_precond_block_kernel(double *__restrict__ x,
+                                                                           double *__restrict__ r,
+                                                                           const double *__restrict__ p,
+                                                                           const double *__restrict__ w,
+                                                                           const double *__restrict__ dinv,
+                                                                           BlockScalars alpha, uint32_t active, int n,
+                                                                           ReduceOutW out) {
+  __shared__ double s_w[16 * K];
+  double acc[2 * K];
+#pragma unroll
+  for (int j = 0; j < 2 * K; j++) acc[j] = 0.0;
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double xv[K], rv[K], pv[K], wv[K];
+    const double d = dinv[i];
+    block_load<K>(x + i * K, xv);
+    block_load<K>(r + i * K, rv);
+    block_load<K>(p + i * K, pv);
+    block_load<K>(w + i * K, wv);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const bool on = (active >> j) & 1u;
+      const double xs = xv[j] + alpha.v[j] * pv[j];  // calc_xr_block_kernel's two roundings
+      const double rs = rv[j] - alpha.v[j] * wv[j];
+      xv[j] = on ? xs : xv[j];
+      rv[j] = on ? rs : rv[j];
+      const double z = d * rv[j];
+      acc[2 * j] += rv[j] * z;
+      acc[2 * j + 1] += rv[j] * rv[j];
+    }
+    block_store<K>(x + i * K, xv);
+    block_store<K>(r + i * K, rv);
+  }
+  reduce_finish_k<2 * K>(acc, out, s_w);
+}
+
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_p_precond_block_kernel(double *__restrict__ p,
+                                                                          const double *__restrict__ r,
+                                                                          const double *__restrict__ dinv,
+                                                                          BlockScalars beta, uint32_t active, int n) {
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double pv[K], rv[K];
+    const double d = dinv[i];
+    block_load<K>(p + i * K, pv);
+    block_load<K>(r + i * K, rv);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const double z = d * rv[j];
+      const double ps = z + beta.v[j] * pv[j];
+      pv[j] = ((active >> j) & 1u) ? ps : pv[j];
+    }
+    block_store<K>(p + i * K, pv);
+  }
+}
+
+hipError_t launch_precond_start_block(const double *r, const double *dinv, double *p, int n, int k, uint32_t mask,
+                                      const ReduceOutW &out, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K) \
+  hipLaunchKernelGGL(precond_start_block_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, dinv, p, mask, n, out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_xr_precond_block(double *x, double *r, const double *p, const double *w, const double *dinv,
+                                        int n, int k, const BlockScalars &alpha, uint32_t active, const ReduceOutW &out,
+                                        hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K)                                                                                                  \
+  hipLaunchKernelGGL(calc_xr_precond_block_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, r, p, w, dinv, alpha, active, \
+                     n, out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_p_precond_block(double *p, const double *r, const double *dinv, int n, int k,
+                                       const BlockScalars &beta, uint32_t active, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K) \
+  hipLaunchKernelGGL(calc_p_precond_block_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, dinv, beta, active, n)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+// ---- the inverse diagonal (abft_hip_matrix_diag_inverse) over the stored arrays ----
+// d = the sum, in storage order, of the values of a row's (COO: an output group's) elements that sit on
+// the diagonal; in these two layouts storage order inside a row / group is the caller's.  The column is
+// the stored word under `colmask` (the ECC byte off in the ECC modes, as the SpMV reads it); nothing is
+// checked or repaired here.  Element ranges are clamped to nnz: a damaged row pointer must not send a
+// read outside the arrays.  No usable diagonal (none stored: d = 0; not finite; <= 0): 1.0, counted.
+__device__ __forceinline__ double diag_invert(double d, uint32_t *bad) {
+  if (d > 0.0 && d <= 1.7976931348623157e308) return 1.0 / d;
+  atomicAdd(bad, 1u);
+  return 1.0;
+}
+
+__global__ __launch_bounds__(ABFT_BLOCK) void diag_csr_kernel(const uint32_t *__restrict__ rowptr,
+                                                              const uint32_t *__restrict__ cols,
+                                                              const double *__restrict__ vals, uint32_t n, uint32_t nnz,
+                                                              uint32_t colmask, double *__restrict__ dinv,
+                                                              uint32_t *bad) {
+  for (uint32_t row = blockIdx.x * ABFT_BLOCK + threadIdx.x; row < n; row += gridDim.x * ABFT_BLOCK) {
+    const uint32_t hi = min(rowptr[row + 1], nnz), lo = min(rowptr[row], hi);
+    double d = 0.0;
+    for (uint32_t e = lo; e < hi; e++)
+      if ((cols[e] & colmask) == row) d += vals[e];
+    dinv[row] = diag_invert(d, bad);
+  }
+}
+
+__global__ __launch_bounds__(ABFT_BLOCK) void diag_coo_kernel(const uint32_t *__restrict__ grp_ptr,
+                                                              const uint4 *__restrict__ elems, uint32_t n, uint32_t nnz,
+                                                              uint32_t colmask, double *__restrict__ dinv,
+                                                              uint32_t *bad) {
+  for (uint32_t c = blockIdx.x * ABFT_BLOCK + threadIdx.x; c < n; c += gridDim.x * ABFT_BLOCK) {
+    const uint32_t hi = min(grp_ptr[c + 1], nnz), lo = min(grp_ptr[c], hi);
+    double d = 0.0;
+    for (uint32_t e = lo; e < hi; e++) {
+      const uint4 el = elems[e];
+      if ((el.x & colmask) == c && el.y == c) d += as_double(el.z, el.w);
+    }
+    dinv[c] = diag_invert(d, bad);
+  }
+}
+
+hipError_t launch_diag_csr(const CsrDev &A, uint32_t colmask, double *dinv, uint32_t *bad, hipStream_t s) {
+  if (!A.n_out) return hipSuccess;
+  const int nb = reduce_blocks((int)A.n_out);
+  hipLaunchKernelGGL(diag_csr_kernel, dim3(nb), dim3(ABFT_BLOCK), 0, s, A.rowptr, A.cols, A.vals, A.n_out, A.nnz,
+                     colmask, dinv, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_diag_coo(const CooDev &A, uint32_t colmask, double *dinv, uint32_t *bad, hipStream_t s) {
+  if (!A.n_out) return hipSuccess;
+  const int nb = reduce_blocks((int)A.n_out);
+  hipLaunchKernelGGL(diag_coo_kernel, dim3(nb), dim3(ABFT_BLOCK), 0, s, A.grp_ptr, A.elems, A.n_out, A.nnz, colmask,
+                     dinv, bad);
+  return hipGetLastError();
+}
+
 // ---- the tail of a CG iteration in ONE launch (fixed-iteration loop, scalars on the device) ----
 // Behind the SpMV the loop of cg.cpp:100-112 runs three small kernels -- the fold of the fused p.w partials,
 // calc_r (r -= alpha w, r.r), calc_px (x += alpha p, p = r + beta p) -- each ending in a reduction and, across

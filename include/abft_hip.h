@@ -294,6 +294,56 @@ int abft_hip_residual_restart_block(abft_hip_ctx *ctx, abft_hip_matrix *A, const
 int abft_hip_copy_block(abft_hip_ctx *ctx, abft_hip_vector *dst, const abft_hip_vector *src, int k,
                         uint32_t mask);
 
+/* ---- Jacobi (diagonal) preconditioning ------------------------------------
+ * M^-1 = diag(dinv) is one more N-vector; z = dinv * r is one rounded product formed
+ * inside the kernels that already stream r and never stored.  The loop:
+ *   copy r <- b;  {rz, rr} = precond_start(r, dinv, p)
+ *   while rr > threshold:  spmv(A, p, w);  alpha = rz / dot(p, w)
+ *                          {rz_new, rr} = calc_xr_precond(x, r, p, w, dinv, alpha)
+ *                          calc_p_precond(p, r, dinv, rz_new / rz);  rz = rz_new
+ * Every multiply and add is separate.  Each entry walks the vectors and folds its sums
+ * exactly as its plain counterpart (dot, calc_xr, calc_p and their block forms), so with
+ * dinv == 1.0 everywhere it leaves and returns the plain call's bits.  Every length is
+ * checked, and a dinv that overlaps a vector the call writes is refused
+ * (ABFT_ERR_INVALID) before anything is enqueued.  dinv carries no ECC words: damage to
+ * it changes M, hence the rate of convergence, never the consistency of r with b - A x
+ * that the residual checks verify. */
+
+/* dinv[i] = 1.0 / d[i], d[i] = the sum, in the caller's element order, of the values of the
+ * elements whose row and column are both i (the column as that mode's SpMV decodes it: ECC
+ * bits masked off; no ECC check, no repair, no event -- the SpMV checks the matrix).  A row
+ * with no diagonal element, or whose d[i] is not finite or <= 0, gets 1.0 and is counted in
+ * *bad.  CSR and COO, every one-GPU layout (a device kernel over the stored arrays for the
+ * streaming CSR and the grouped COO layout -- there a COO element whose stored column no
+ * longer names the group it is stored in is not on any diagonal --, the caller-order read-back
+ * for the permuted layouts); shards: ABFT_ERR_INVALID. */
+int abft_hip_matrix_diag_inverse(abft_hip_ctx *ctx, abft_hip_matrix *mat, abft_hip_vector *dinv,
+                                 uint32_t *bad);
+/* p = z; out = {sum r z, sum r r}; out[1] is abft_hip_dot(r, r) bit for bit */
+int abft_hip_precond_start(abft_hip_ctx *ctx, const abft_hip_vector *r, const abft_hip_vector *dinv,
+                           abft_hip_vector *p, double out[2]);
+/* x += alpha p; r -= alpha w; out = {sum r z, sum r r} of the new r.  The x half may be
+ * carried out by the abft_hip_calc_p_precond that follows, under abft_hip_calc_xr's rules
+ * (any other call applies it first; ABFT_HIP_FUSE_X=0 turns it off). */
+int abft_hip_calc_xr_precond(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r,
+                             const abft_hip_vector *p, const abft_hip_vector *w,
+                             const abft_hip_vector *dinv, double alpha, double out[2]);
+/* p = z + beta p, z formed again from the same operands (the same bits) */
+int abft_hip_calc_p_precond(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r,
+                            const abft_hip_vector *dinv, double beta);
+/* Block forms (k <= 8 columns, row-major as above; ONE dinv of N entries for all columns: one
+ * operator).  out[2j], out[2j + 1] = column j's two sums, for every column.  P is rewritten in
+ * the columns set in `mask` only; `active` as in abft_hip_calc_xr_block / _calc_p_block: a
+ * column whose bit is clear keeps its bits. */
+int abft_hip_precond_start_block(abft_hip_ctx *ctx, const abft_hip_vector *R, const abft_hip_vector *dinv,
+                                 abft_hip_vector *P, int k, uint32_t mask, double *out);
+int abft_hip_calc_xr_precond_block(abft_hip_ctx *ctx, abft_hip_vector *X, abft_hip_vector *R,
+                                   const abft_hip_vector *P, const abft_hip_vector *W,
+                                   const abft_hip_vector *dinv, int k, const double *alpha, uint32_t active,
+                                   double *out);
+int abft_hip_calc_p_precond_block(abft_hip_ctx *ctx, abft_hip_vector *P, const abft_hip_vector *R,
+                                  const abft_hip_vector *dinv, int k, const double *beta, uint32_t active);
+
 /* Shard-local forms for the row-partitioned solver: same kernels, but the
  * result stays on the device so a collective can sum it across ranks before
  * the host reads it.  `dev_result` is a device pointer to TWO doubles:
