@@ -19,6 +19,8 @@ FMT_CSR, FMT_COO = 0, 1
 FLIP_ANY, FLIP_VALUE, FLIP_INDEX = 0, 1, 2
 PART_ALL, PART_INTERIOR, PART_BOUNDARY = 0, 1, 2
 K_SPMV, K_DOT, K_CALC_XR, K_CALC_P = 0, 1, 2, 3
+EV_VEC_CORRECTED, EV_VEC_DOUBLE = 10, 11  # protected vectors: bit = word bit | operand << 8
+FMT_VECTOR = 2
 MAX_RHS = 8  # block right-hand sides per call (include/abft_hip.h)
 
 u32p = C.POINTER(C.c_uint32)
@@ -84,6 +86,12 @@ SIGNATURES = {
     "abft_hip_calc_xr_block": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, f64p, C.c_uint32, f64p]),
     "abft_hip_calc_p_block": (C.c_int, [vp, vp, vp, C.c_int, f64p, C.c_uint32]),
     "abft_hip_vector_flip": (C.c_int, [vp, C.c_int, i32p, C.c_int]),
+    "abft_hip_vector_encode": (C.c_int, [vp, vp]),
+    "abft_hip_vector_scrub": (C.c_int, [vp, vp, i32p, i32p]),
+    "abft_hip_spmv_vecc": (C.c_int, [vp, vp, vp, vp]),
+    "abft_hip_dot_vecc": (C.c_int, [vp, vp, vp, f64p]),
+    "abft_hip_calc_xr_vecc": (C.c_int, [vp, vp, vp, vp, vp, C.c_double, f64p]),
+    "abft_hip_calc_p_vecc": (C.c_int, [vp, vp, vp, C.c_double]),
     "abft_hip_residual_gap": (C.c_int, [vp, vp, vp, vp, vp, vp, f64p]),
     "abft_hip_residual_restart": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, f64p]),
     "abft_hip_residual_gap_block": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, f64p]),
@@ -204,7 +212,7 @@ def check(rc):
 
 def is_fatal(kind):
     """same rule as abft_event_is_fatal"""
-    return kind in (1, 4) or kind >= 5
+    return kind in (1, 4, EV_VEC_DOUBLE) or 5 <= kind <= 9
 
 
 def format_event(kind, index, bit, fmt):

@@ -58,12 +58,18 @@ Additional options of this build:
       --max-rollbacks   M     Give up (exit 1) after more than M failed checks (default 3)
       --flip-vector I:V:J:B[,B...]
                               After iteration I, flip bit(s) B (0-63) of entry J of
-                              vector V (x, r or p; with --rhs K, J = row * K + column)
-                              (may be repeated)
+                              vector V (x, r or p; with --rhs K, J = row * K + column;
+                              with --vector-ecc secded also w or b) (may be repeated)
       --precond         P     Preconditioner: none (default) or jacobi (the inverse
                               diagonal of A, applied inside the vector kernels)
+      --vector-ecc      E     Protect the CG vectors: none (default) or secded, a (64, 57)
+                              code in each double's low 7 mantissa bits (CSR, one
+                              right-hand side, no --precond / --check-every)
 
 """
+
+
+FLIP_VECTOR_MSG = "Invalid --flip-vector (want ITER:VEC:INDEX:BIT[,BIT...], VEC one of x, r, p)"
 
 
 def fail(msg):
@@ -74,7 +80,8 @@ def fail(msg):
 def parse(argv):
     o = dict(num_blocks=25, max_itrs=1000, conv=0.001, matrix_file=DEFAULT_MTX, synthetic=None, target="cpu",
              mode="none", flips=0, kind="ANY", seed=None, quiet=False, flip_at=None, fmt="csr", list=False,
-             rhs=1, check_every=0, check_tol=1e-7, max_rollbacks=3, flip_vector=[], precond="none")
+             rhs=1, check_every=0, check_tol=1e-7, max_rollbacks=3, flip_vector=[], precond="none",
+             vector_ecc="none")
 
     def num(s, conv):
         try:
@@ -156,19 +163,24 @@ def parse(argv):
             if o["max_rollbacks"] < 0:
                 fail("Invalid number of rollbacks")
         elif a == "--flip-vector":
-            msg = "Invalid --flip-vector (want ITER:VEC:INDEX:BIT[,BIT...], VEC one of x, r, p)"
+            msg = FLIP_VECTOR_MSG
             try:
                 itr, vec, idx, bits = arg(msg).split(":")
                 flip = (int(itr), vec, int(idx), [int(b) for b in bits.split(",")])
             except ValueError:
                 fail(msg)
-            if flip[0] < 0 or flip[1] not in ("x", "r", "p") or flip[2] < 0 or not all(0 <= b < 64 for b in flip[3]):
-                fail(msg)
+            if flip[0] < 0 or flip[1] not in ("x", "r", "p", "w", "b") or flip[2] < 0 or \
+                    not all(0 <= b < 64 for b in flip[3]):
+                fail(msg)  # (w and b: only with --vector-ecc secded, checked once every argument is read)
             o["flip_vector"] = o["flip_vector"] + [flip]
         elif a == "--precond":
             o["precond"] = arg("Invalid preconditioner (want none or jacobi)")
             if o["precond"] not in ("none", "jacobi"):
                 fail("Invalid preconditioner (want none or jacobi)")
+        elif a == "--vector-ecc":
+            o["vector_ecc"] = arg("Invalid vector protection (want none or secded)")
+            if o["vector_ecc"] not in ("none", "secded"):
+                fail("Invalid vector protection (want none or secded)")
         elif a in ("--quiet", "-q"):
             o["quiet"] = True
         elif a in ("--help", "-h"):
@@ -177,6 +189,14 @@ def parse(argv):
         else:
             fail("Unrecognized argument '%s' (try '--help')" % a)
         i += 1
+    if o["vector_ecc"] == "none":
+        if any(f[1] in ("w", "b") for f in o["flip_vector"]):
+            fail(FLIP_VECTOR_MSG)  # (known only here: --vector-ecc may follow --flip-vector)
+    else:
+        for flag, on in (("--rhs", o["rhs"] > 1), ("--precond", o["precond"] != "none"),
+                         ("--check-every", o["check_every"] > 0), ("--format coo", o["fmt"] != "csr")):
+            if on:
+                fail("--vector-ecc secded cannot be combined with %s" % flag)
     return o
 
 
@@ -302,7 +322,9 @@ def run_single(o):
     cols, rows, vals, n, block = load_matrix(o)
     nnz = len(vals)
     ctx = HIPContext(o["mode"], o["fmt"])
-    A = ctx.create_matrix(cols, rows, vals, n, nnz)
+    ecc = o["vector_ecc"] == "secded"
+    # (protected vectors run on the streaming layout only)
+    A = ctx.create_matrix(cols, rows, vals, n, nnz, layout="stream" if ecc else None)
     del cols, rows, vals
     header(o, n, block, nnz)
     b, x, r, p, w = (ctx.create_vector(n) for _ in range(5))
@@ -312,8 +334,10 @@ def run_single(o):
         for bit in bits:
             print("*** flipping bit %d at index %d ***" % (bit, index))
         ctx.inject_at(A, index, bits)
-    vecs = vector_flips(o, n, {"x": x, "r": r, "p": p})
+    vecs = vector_flips(o, n, {"x": x, "r": r, "p": p, "w": w, "b": b})
     dinv = make_preconditioner(o, ctx, A)
+    if ecc:
+        print("vector protection: secded (64, 57)")
     bound = o["check_tol"] * float(np.linalg.norm(generators.reference_rhs(n)))
     checks = {}
 
@@ -327,7 +351,7 @@ def run_single(o):
         itr, rr = cg_solve(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
                            check_every=o["check_every"], check_tol=o["check_tol"], max_rollbacks=o["max_rollbacks"],
                            on_check=lambda i, gap, ok, back: report_check(checks, "", i, gap, ok, back, bound),
-                           precond=dinv)
+                           precond=dinv, **({"vector_ecc": True} if ecc else {}))
     except ResidualCheckFailed as e:
         print("[ABFT] %s" % e)
         ctx.close()
@@ -337,8 +361,13 @@ def run_single(o):
     if o["check_every"]:
         print_check_summary(checks)
     print("\ntime taken = %7.2f ms\n" % ms)
-    ctx.spmv(A, x, r)
-    err = np.abs(ctx.download(b) - ctx.download(r))
+    if ecc:
+        from .context import vecc_strip
+        ctx.spmv_vecc(A, x, r)
+        err = np.abs(vecc_strip(ctx.download(b)) - vecc_strip(ctx.download(r)))
+    else:
+        ctx.spmv(A, x, r)
+        err = np.abs(ctx.download(b) - ctx.download(r))
     print("total error = %f" % math.sqrt(float((err * err).sum())))
     print("max error   = %f" % (float(err.max()) if n else 0.0))
     print()

@@ -310,6 +310,41 @@ class HIPContext:
         """dst[:, j] = src[:, j] for the columns set in `mask`"""
         check(self.L.abft_hip_copy_block(self.h, dst.h, src.h, k, int(mask)))
 
+    # ---- protected vectors (include/abft_hip.h; DESIGN.md section 5e) ----
+    def encode_vector(self, v):
+        """v[i] <- the (64, 57) codeword of v[i], in place (the double loses its low 7 mantissa bits)"""
+        check(self.L.abft_hip_vector_encode(self.h, v.h))
+
+    def scrub_vector(self, v):
+        """check every word of v and write repaired ones back; -> (corrected, uncorrectable).  Events as
+        after any call that reads a result (FatalEvent on an uncorrectable word)."""
+        c, u = C.c_int(0), C.c_int(0)
+        check(self.L.abft_hip_vector_scrub(self.h, v.h, C.byref(c), C.byref(u)))
+        self._drain()
+        return c.value, u.value
+
+    def spmv_vecc(self, mat, vec, result):
+        check(self.L.abft_hip_spmv_vecc(self.h, mat.h, vec.h, result.h))
+
+    def dot_vecc(self, a, b):
+        r = C.c_double()
+        check(self.L.abft_hip_dot_vecc(self.h, a.h, b.h, C.byref(r)))
+        self._drain_if_pending()
+        return r.value
+
+    def calc_xr_vecc(self, x, r, p, w, alpha):
+        out = C.c_double()
+        check(self.L.abft_hip_calc_xr_vecc(self.h, x.h, r.h, p.h, w.h, alpha, C.byref(out)))
+        self._drain_if_pending()
+        return out.value
+
+    def calc_p_vecc(self, p, r, beta):
+        check(self.L.abft_hip_calc_p_vecc(self.h, p.h, r.h, beta))
+
+    def vecc_supported(self, mat):
+        """spmv_vecc runs on CSR matrices in the streaming layout only"""
+        return mat.fmt == FMT_CSR and self.matrix_info(mat)[0] == "stream"
+
     # ---- Jacobi preconditioning (include/abft_hip.h) ----
     def jacobi(self, mat, strict=True):
         """-> a new Vector dinv, dinv[i] = 1 / (sum of the diagonal elements of row i), the Jacobi
@@ -470,6 +505,12 @@ def _libc_rand():
     return _libc.rand()
 
 
+def vecc_strip(array):
+    """a downloaded protected vector -> its values: bits 0..6 (the code bits) of every word cleared"""
+    words = np.ascontiguousarray(array, dtype=np.float64).view(np.uint64) & np.uint64(0xFFFFFFFFFFFFFF80)
+    return words.view(np.float64)
+
+
 def fdiv(a, b):
     """a / b as the reference's C++ computes it (cg.cpp:102, 109): IEEE-754, so a zero
     denominator gives inf / nan instead of Python's ZeroDivisionError"""
@@ -515,7 +556,7 @@ def _check_args(check_every, check_tol, max_rollbacks):
 
 
 def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None, check_every=0,
-             check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None, precond=None):
+             check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None, precond=None, vector_ecc=False):
     """The reference driver's CG loop, call for call (cg.cpp:87-118).
 
     check_every > 0 adds residual checks: after iteration i when (i + 1) %
@@ -533,8 +574,27 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
     5d): z = dinv * r is formed inside precond_start / calc_xr_precond / calc_p_precond, which replace
     copy p <- r + dot, calc_xr and calc_p; alpha = r.z / p.w, beta = r.z_new / r.z.  The stop test, on_iteration
     and the residual checks stay on r.r and on r against b - A x (neither depends on M); a restart is followed
-    by precond_start on the restarted r.  With precond=None the calls are exactly those without it."""
+    by precond_start on the restarted r.  With precond=None the calls are exactly those without it.
+
+    vector_ecc=True runs the loop on protected vectors: b and x are encoded in place,
+    once; r <- b is a copy of codewords that is scrubbed at once (b is read there and nowhere else: a flip
+    in it is repaired in r, reported, and left in b); the loop makes the same calls in their protected
+    forms (spmv_vecc, dot_vecc, calc_xr_vecc, calc_p_vecc), each of which repairs a flipped bit of any
+    operand in registers; x and b are scrubbed before returning, so what the caller downloads is repaired
+    (vecc_strip gives the values).  Stop test, on_iteration and the return value are as without it; a word
+    with two flipped bits raises FatalEvent.  Refused (ValueError, before anything runs) with check_every > 0,
+    with precond, and for a matrix spmv_vecc does not run on: those kernels write unencoded vectors.
+    With vector_ecc=False the calls are exactly those made without the argument."""
     _check_args(check_every, check_tol, max_rollbacks)
+    if vector_ecc:
+        if check_every:
+            raise ValueError("vector_ecc with check_every > 0: the residual kernels write unencoded vectors")
+        if precond is not None:
+            raise ValueError("vector_ecc with precond: the preconditioned kernels write unencoded vectors")
+        if not ctx.vecc_supported(A):
+            raise ValueError("vector_ecc needs a CSR matrix in the streaming layout (this one: %s)"
+                             % ("COO" if A.fmt != FMT_CSR else ctx.matrix_info(A)[0]))
+        return _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration)
     ctx.copy_vector(r, b)
     rz = None
     if precond is None:
@@ -611,6 +671,32 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
     finally:
         if check_every and own_ckpt:
             ctx.destroy_vector(x_ckpt)
+    return itr, rr
+
+
+def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration):
+    """cg_solve(vector_ecc=True): the loop of cg_solve on protected vectors"""
+    ctx.encode_vector(b)
+    ctx.encode_vector(x)
+    ctx.copy_vector(r, b)
+    ctx.scrub_vector(r)  # the one read of b: repaired in r, b itself stays as it is until the end
+    ctx.copy_vector(p, r)
+    rr = ctx.dot_vecc(r, r)
+    itr = 0
+    noted = {}
+    note_threshold(rr, conv_threshold, noted)
+    while itr < max_itrs and rr > conv_threshold:
+        ctx.spmv_vecc(A, p, w)
+        pw = ctx.dot_vecc(p, w)
+        rr_new = ctx.calc_xr_vecc(x, r, p, w, fdiv(rr, pw))
+        ctx.calc_p_vecc(p, r, fdiv(rr_new, rr))
+        rr = rr_new
+        note_threshold(rr, conv_threshold, noted)
+        if on_iteration is not None:
+            on_iteration(itr, rr)
+        itr += 1
+    ctx.scrub_vector(x)
+    ctx.scrub_vector(b)
     return itr, rr
 
 

@@ -97,6 +97,7 @@ struct abft_hip_ctx {
   bool fuse_enabled = true;
   struct {
     bool valid = false, have_value = false;
+    bool vecc = false;  // made by abft_hip_spmv_vecc: serves abft_hip_dot_vecc only (and a plain product a plain dot only)
     const double *x = nullptr, *y = nullptr;
     int n = 0;
     uint32_t seq = 0;
@@ -1911,7 +1912,7 @@ extern "C" int abft_hip_dot(abft_hip_ctx *ctx, const abft_hip_vector *a, const a
   if (int rc = check_same(a, b, "dot")) { spec_drop(ctx); return rc; }
   if (!result) { spec_drop(ctx); return set_err(ABFT_ERR_INVALID, "null result"); }
   // dot(p, w) right after spmv(A, p, w): the SpMV already formed it
-  if (ctx->fused.valid && a->n == ctx->fused.n &&
+  if (ctx->fused.valid && !ctx->fused.vecc && a->n == ctx->fused.n &&
       ((a->d == ctx->fused.x && b->d == ctx->fused.y) || (a->d == ctx->fused.y && b->d == ctx->fused.x))) {
     if (!ctx->fused.have_value) {
       if (int rc = scalar_from_host_slot(ctx, ctx->fused.seq, &ctx->fused.value)) return rc;
@@ -2654,9 +2655,18 @@ struct HeldFold {
 
 static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
                        abft_hip_vector *result, int vec_offset, double *dev_pair, int part = ABFT_PART_ALL,
-                       int c0 = 0, int c1 = -1, HeldFold *hold = nullptr) {
+                       int c0 = 0, int c1 = -1, HeldFold *hold = nullptr, bool vecc = false) {
   if (int rc = bind(ctx)) return rc;
   if (!mat || !vec || !result) return set_err(ABFT_ERR_INVALID, "spmv: null argument");
+  if (vecc) {  // protected vectors: the streaming CSR kernel only; the iteration they are part of is not speculated
+    spec_forget(ctx);
+    const char *layout = mat->fmt != ABFT_FMT_CSR ? "COO" : mat->use_slice ? "slice" : mat->use_sweep ? "sweep"
+                         : mat->use_panels ? "panel" : nullptr;
+    if (layout)
+      return set_err(ABFT_ERR_INVALID, "spmv_vecc: a matrix in the %s layout (protected vectors run on CSR matrices "
+                     "in the streaming layout only)", layout);
+    if (!disjoint(vec, result)) return set_err(ABFT_ERR_INVALID, "spmv_vecc: input and output overlap");
+  }
   if (part < ABFT_PART_ALL || part > ABFT_PART_BOUNDARY) return set_err(ABFT_ERR_INVALID, "spmv: unknown part %d", part);
   const uint32_t n_out = mat->fmt == ABFT_FMT_CSR ? mat->csr.n_out : mat->coo.n_out;
   const uint32_t n_in = mat->fmt == ABFT_FMT_CSR ? mat->csr.n_in : mat->coo.n_in;
@@ -2731,7 +2741,7 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
                                       do_fuse ? &fuse : nullptr, mat->panel_grid, mat->panel_chunk, ctx->stream));
     } else if (mat->fmt == ABFT_FMT_CSR)
       HIPCHK(launch_spmv_csr(mat->mode, mat->csr, mat->compact, mat->packed, span, vec->d, result->d, ctx->ring,
-                             do_fuse ? &fuse : nullptr, ctx->stream));
+                             do_fuse ? &fuse : nullptr, ctx->stream, vecc));
     else
       HIPCHK(launch_spmv_coo(mat->mode, mat->coo, vec->d, result->d, ctx->ring, do_fuse ? &fuse : nullptr, ctx->stream));
     // COO: products whose stored column was silently corrupted go where the reference puts them --
@@ -2760,11 +2770,12 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
   if (to_host && do_fuse) {
     ctx->fused.valid = true;
     ctx->fused.have_value = false;
+    ctx->fused.vecc = vecc;
     ctx->fused.x = vec->d;
     ctx->fused.y = result->d;
     ctx->fused.n = vec->n;
     ctx->fused.seq = fuse.seq;
-    if (whole && part == ABFT_PART_ALL) (void)spec_launch(ctx, vec, result);
+    if (whole && part == ABFT_PART_ALL && !vecc) (void)spec_launch(ctx, vec, result);
   }
   return ABFT_OK;
 }
@@ -2930,6 +2941,93 @@ extern "C" int abft_hip_vector_flip(abft_hip_vector *v, int index, const int *bi
   }
   if (!mask) return ABFT_OK;
   HIPCHK(launch_flip_vector(v->d + index, mask, v->ctx->stream));
+  return ABFT_OK;
+}
+
+// ---- protected vectors (include/abft_hip.h): encode, scrub and the four CG calls on codewords ----
+// Every entry starts with bind (a deferred x += alpha p applied, a speculation voided) and forgets the
+// learned iteration: a protected loop is never speculated.  An entry that writes a vector also forgets
+// the fused product.  Lengths and overlaps are checked before anything of the call is enqueued.
+
+static int bind_vecc(abft_hip_ctx *ctx, bool writes) {
+  if (int rc = bind(ctx)) return rc;
+  spec_forget(ctx);
+  if (writes) ctx->fused.valid = false;
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_vector_encode(abft_hip_ctx *ctx, abft_hip_vector *v) {
+  if (int rc = bind_vecc(ctx, true)) return rc;
+  if (!v) return set_err(ABFT_ERR_INVALID, "vector_encode: null vector");
+  HIPCHK(launch_vector_encode(v->d, v->n, ctx->stream));
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_vector_scrub(abft_hip_ctx *ctx, abft_hip_vector *v, int *corrected, int *uncorrectable) {
+  if (int rc = bind_vecc(ctx, true)) return rc;
+  if (!v) return set_err(ABFT_ERR_INVALID, "vector_scrub: null vector");
+  uint32_t counts[2] = {0u, 0u};
+  uint32_t *dev = reinterpret_cast<uint32_t *>(ctx->bits_dev);  // (the injection scratch: idle between calls)
+  HIPCHK(hipMemsetAsync(dev, 0, sizeof(counts), ctx->stream));
+  HIPCHK(launch_vector_scrub(v->d, v->n, dev, ctx->ring, ctx->stream));
+  HIPCHK(hipMemcpyAsync(counts, dev, sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (corrected) *corrected = (int)counts[0];
+  if (uncorrectable) *uncorrectable = (int)counts[1];
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_spmv_vecc(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                  abft_hip_vector *result) {
+  return spmv_common(ctx, mat, vec, result, 0, nullptr, ABFT_PART_ALL, 0, -1, nullptr, true);
+}
+
+extern "C" int abft_hip_dot_vecc(abft_hip_ctx *ctx, const abft_hip_vector *a, const abft_hip_vector *b, double *out) {
+  if (int rc = bind_vecc(ctx, false)) return rc;
+  if (int rc = check_same(a, b, "dot_vecc")) return rc;
+  if (!out) return set_err(ABFT_ERR_INVALID, "dot_vecc: null result");
+  // dot_vecc(p, w) right after spmv_vecc(A, p, w): the SpMV already formed it (never a plain product)
+  if (ctx->fused.valid && ctx->fused.vecc && a->n == ctx->fused.n &&
+      ((a->d == ctx->fused.x && b->d == ctx->fused.y) || (a->d == ctx->fused.y && b->d == ctx->fused.x))) {
+    if (!ctx->fused.have_value) {
+      if (int rc = scalar_from_host_slot(ctx, ctx->fused.seq, &ctx->fused.value)) return rc;
+      ctx->fused.have_value = true;
+    }
+    *out = ctx->fused.value;
+    return ABFT_OK;
+  }
+  if (!ctx->fused.have_value) ctx->fused.valid = false;  // the slot is about to be reused
+  const ReduceOut o = reduce_out(ctx, nullptr, true);
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_dot_vecc(a->d, b->d, a->n, o, ctx->ring, ctx->stream));
+  }
+  return scalar_from_host_slot(ctx, o.seq, out);
+}
+
+extern "C" int abft_hip_calc_xr_vecc(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r,
+                                     const abft_hip_vector *p, const abft_hip_vector *w, double alpha, double *rr) {
+  if (int rc = bind_vecc(ctx, true)) return rc;
+  if (!rr) return set_err(ABFT_ERR_INVALID, "calc_xr_vecc: null result");
+  if (int rc = check_same(x, r, "calc_xr_vecc")) return rc;
+  if (int rc = check_same(x, p, "calc_xr_vecc")) return rc;
+  if (int rc = check_same(x, w, "calc_xr_vecc")) return rc;
+  if (!disjoint(x, r) || !disjoint(x, p) || !disjoint(x, w) || !disjoint(r, p) || !disjoint(r, w))
+    return set_err(ABFT_ERR_INVALID, "calc_xr_vecc: x and r must not overlap each other, p or w");
+  const ReduceOut o = reduce_out(ctx, nullptr, true);
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_xr_vecc(x->d, r->d, p->d, w->d, alpha, x->n, o, ctx->ring, ctx->stream));
+  }
+  return scalar_from_host_slot(ctx, o.seq, rr);
+}
+
+extern "C" int abft_hip_calc_p_vecc(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, double beta) {
+  if (int rc = bind_vecc(ctx, true)) return rc;
+  if (int rc = check_same(p, r, "calc_p_vecc")) return rc;
+  if (!disjoint(p, r)) return set_err(ABFT_ERR_INVALID, "calc_p_vecc: p and r overlap");
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_p_vecc(p->d, r->d, beta, p->n, ctx->ring, ctx->stream));
   return ABFT_OK;
 }
 
@@ -3490,7 +3588,8 @@ extern "C" int abft_hip_graph_destroy(abft_hip_graph *g) {
 // ------------------------------------------------------------------- events --
 
 extern "C" int abft_event_is_fatal(uint32_t kind) {
-  return kind == ABFT_EV_SED_DETECTED || kind == ABFT_EV_DOUBLE_BIT || kind >= ABFT_EV_ROW_SIZE;
+  return kind == ABFT_EV_SED_DETECTED || kind == ABFT_EV_DOUBLE_BIT || kind == ABFT_EV_VEC_DOUBLE ||
+         (kind >= ABFT_EV_ROW_SIZE && kind <= ABFT_EV_MOVED_OVERFLOW);
 }
 
 extern "C" int abft_format_event(const abft_event *ev, char *buf, size_t cap) {
@@ -3516,6 +3615,12 @@ extern "C" int abft_format_event(const abft_event *ev, char *buf, size_t cap) {
                                     : "column order constraint violated at index %d\n", i);
     case ABFT_EV_MOVED_OVERFLOW:
       return snprintf(buf, cap, "hip: more than %d COO elements carry a silently corrupted column\n", i);
+    case ABFT_EV_VEC_CORRECTED:
+      return snprintf(buf, cap, "[ECC] corrected bit %u of vector operand %u at index %d\n", ev->bit & 0xffu,
+                      (ev->bit >> 8) & 0xffu, i);
+    case ABFT_EV_VEC_DOUBLE:
+      return snprintf(buf, cap, "[ECC] double-bit error detected in vector operand %u at index %d\n",
+                      (ev->bit >> 8) & 0xffu, i);
     default: return snprintf(buf, cap, "unknown event %u\n", ev->kind);
   }
 }
@@ -3566,6 +3671,19 @@ extern "C" int abft_hip_drain_events(abft_hip_ctx *ctx, abft_event *buf, int cap
   });
   for (abft_event &e : ev)
     if (csr_check(e)) e.bit = 0;
+  // vector events equal in all four fields are one flip seen by several gatherers: reported once per drain
+  // (the sort keeps equal index and kind together; between them the bits may interleave, hence the look back)
+  {
+    uint32_t kept = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      bool dup = false;
+      if (ev[i].fmt == ABFT_FMT_VECTOR)
+        for (uint32_t j = kept; j-- > 0 && ev[j].index == ev[i].index && ev[j].kind == ev[i].kind && !dup;)
+          dup = ev[j].fmt == ABFT_FMT_VECTOR && ev[j].bit == ev[i].bit;
+      if (!dup) ev[kept++] = ev[i];
+    }
+    n = kept;
+  }
   // the reference stops at its first fatal line: look at ALL queued events for it, then
   // hand over what precedes it (a short caller buffer must not hide a fatal event)
   uint32_t want = n;

@@ -346,8 +346,10 @@ hipError_t launch_spmv_coo_panels(int mode, const CooDev &A, const CsrPanels &P,
 // (`big`: where a multi-workgroup fold of many partials meets; see fold_partials_kernel)
 struct FixArgs;
 hipError_t launch_fuse_finalize(const FuseOut &f, uint32_t nblk, const ReduceOut &big, const FixArgs *fix, hipStream_t s);
+// vecc: x and y hold protected elements (abft_hip_spmv_vecc)
 hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
-                           const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s);
+                           const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s,
+                           bool vecc = false);
 hipError_t launch_spmv_coo(int mode, const CooDev &A, const double *x, double *y, EventRing ev,
                            const FuseOut *fuse, hipStream_t s);
 // behind every COO SpMV: see MovedList.  With a fused product the fix-up runs inside the fold
@@ -450,6 +452,14 @@ struct ReduceOutW {
   uint32_t seq;
 };
 hipError_t launch_flip_vector(double *v, unsigned long long mask, hipStream_t s);
+// ---- protected vectors (abft_hip_*_vecc): the words of ecc_device.h's (64, 57) code ----
+hipError_t launch_vector_encode(double *v, int n, hipStream_t s);
+// counts[0] += repaired words, counts[1] += uncorrectable ones
+hipError_t launch_vector_scrub(double *v, int n, uint32_t *counts, EventRing ev, hipStream_t s);
+hipError_t launch_dot_vecc(const double *a, const double *b, int n, const ReduceOut &out, EventRing ev, hipStream_t s);
+hipError_t launch_calc_xr_vecc(double *x, double *r, const double *p, const double *w, double alpha, int n,
+                               const ReduceOut &out, EventRing ev, hipStream_t s);
+hipError_t launch_calc_p_vecc(double *p, const double *r, double beta, int n, EventRing ev, hipStream_t s);
 // {gap2, tt2} = {sum ((b - y) - r)^2, sum (b - y)^2} through the K-wide slot (values 0, 1)
 hipError_t launch_residual_gap(const double *b, const double *y, const double *r, int n, const ReduceOutK &out,
                                hipStream_t s);

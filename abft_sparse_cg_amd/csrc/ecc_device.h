@@ -136,3 +136,79 @@ __device__ __forceinline__ void ecc_encode(int mode, uint32_t *w) {
     if (mode != MODE_SEC7) w[EW] |= ecc_parity<FMT>(w) << 24;
   }
 }
+
+// ------------------------------------------------- protected vector elements --
+// The (64, 57) extended Hamming code of a CG vector element.  One 64-bit
+// word, bit 0 the least significant:
+//   bits 7..63  data: sign, exponent and the top 45 mantissa bits of the double
+//   bits 1..6   Hamming check bit k (0..5) at bit 1 + k, Hamming position 2^k
+//   bit  0      overall parity
+// Data bit d = 7, 8, ..., 63 takes the next Hamming position that is no power of two, from 3 on
+// (ecc_mask's rule): 57 positions, so all 63 are used.  Every check bit makes the parity of the
+// bits whose position has bit k set, itself included, even; bit 0 makes the whole word's even.
+// The masks are generated here and end up as instruction immediates; tests/ hold the constants.
+constexpr uint64_t vecc_mask(int k) {
+  uint64_t out = 1ull << (1 + k);
+  uint32_t pos = 3;
+  for (int d = 7; d < 64; d++) {
+    if (ecc_is_pow2(pos)) pos++;
+    if ((pos >> k) & 1u) out |= 1ull << d;
+    pos++;
+  }
+  return out;
+}
+#define ABFT_VECC_CODE_BITS 0x7Full
+
+// XOR-fold of the two halves under check bit K's mask (as ecc_fold): the popcount's low bit is the parity
+template <int K>
+__device__ __forceinline__ uint32_t vecc_fold(uint32_t lo, uint32_t hi) {
+  constexpr uint32_t m0 = (uint32_t)vecc_mask(K), m1 = (uint32_t)(vecc_mask(K) >> 32);
+#if ABFT_CFG_BITOP3 && defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_bitop3_b32(hi, lo & m0, m1, 0x6c);  // acc ^ (word & mask) in one instruction
+#else
+  return (lo & m0) ^ (hi & m1);
+#endif
+}
+
+// Hot-path test: non-zero iff a check bit or the overall parity fails.
+__device__ __forceinline__ uint32_t vecc_suspect(uint64_t word) {
+  const uint32_t lo = (uint32_t)word, hi = (uint32_t)(word >> 32);
+  const uint32_t a = popc(vecc_fold<0>(lo, hi)) | popc(vecc_fold<1>(lo, hi)) | popc(vecc_fold<2>(lo, hi));
+  const uint32_t b = popc(vecc_fold<3>(lo, hi)) | popc(vecc_fold<4>(lo, hi)) | popc(vecc_fold<5>(lo, hi));
+  return (a | b | popc(lo ^ hi)) & 1u;
+}
+
+// the six recomputed parities: the Hamming position of a single flipped bit (cold path)
+__device__ __forceinline__ uint32_t vecc_syndrome(uint64_t word) {
+  const uint32_t lo = (uint32_t)word, hi = (uint32_t)(word >> 32);
+  return ((popc(vecc_fold<0>(lo, hi)) & 1u) << 0) | ((popc(vecc_fold<1>(lo, hi)) & 1u) << 1) |
+         ((popc(vecc_fold<2>(lo, hi)) & 1u) << 2) | ((popc(vecc_fold<3>(lo, hi)) & 1u) << 3) |
+         ((popc(vecc_fold<4>(lo, hi)) & 1u) << 4) | ((popc(vecc_fold<5>(lo, hi)) & 1u) << 5);
+}
+
+// Hamming position (1..63) -> bit of the word: a power of two 2^k is check bit k at bit 1 + k,
+// anything else data bit 7 + (h - floor(log2 h) - 2)
+__device__ __forceinline__ uint32_t vecc_position_to_bit(uint32_t h) {
+  const uint32_t lg = 31u - (uint32_t)__builtin_clz(h);
+  return ecc_is_pow2(h) ? 1u + lg : 5u + h - lg;
+}
+
+// the value a kernel computes with: the word without its code bits
+__device__ __forceinline__ double vecc_value(uint64_t word) {
+  return __longlong_as_double((long long)(word & ~ABFT_VECC_CODE_BITS));
+}
+
+// Encode: truncate toward zero (a NaN whose payload lay in the cut bits keeps bit 51), then the 7 code bits.
+__device__ __forceinline__ uint64_t vecc_encode(double v) {
+  uint64_t w = (uint64_t)__double_as_longlong(v);
+  const bool nan = v != v;
+  w &= ~ABFT_VECC_CODE_BITS;
+  if (nan && (w & 0x000FFFFFFFFFFFFFull) == 0) w |= 1ull << 51;
+  const uint32_t lo = (uint32_t)w, hi = (uint32_t)(w >> 32);
+  // the own bits are clear, so a fold over the full mask is the parity of the data bits under it
+  const uint32_t c = ((popc(vecc_fold<0>(lo, hi)) & 1u) << 1) | ((popc(vecc_fold<1>(lo, hi)) & 1u) << 2) |
+                     ((popc(vecc_fold<2>(lo, hi)) & 1u) << 3) | ((popc(vecc_fold<3>(lo, hi)) & 1u) << 4) |
+                     ((popc(vecc_fold<4>(lo, hi)) & 1u) << 5) | ((popc(vecc_fold<5>(lo, hi)) & 1u) << 6);
+  const uint32_t par = popc(lo ^ hi ^ c) & 1u;
+  return w | c | par;
+}

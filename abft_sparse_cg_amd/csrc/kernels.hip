@@ -142,6 +142,71 @@ __device__ __forceinline__ uint32_t ecc_suspect(const uint32_t *w) {
   return 0;
 }
 
+// ---- protected vector elements (ecc_device.h "protected vector elements") ----
+// Cold path: the word failed vecc_suspect.  One flipped bit (odd parity) is located by the syndrome --
+// bit 0 itself when the syndrome is clear --, flipped back and reported: rc 1.  A set syndrome under even
+// parity is two flips: fatal, the word stays as it is, rc -1.  `operand`: the vector's ordinal in the
+// entry's argument list, `index` the element inside it.
+struct VeccWord { uint64_t w; int rc; };
+
+__device__ __noinline__ VeccWord vecc_cold(uint64_t word, uint32_t index, uint32_t operand, EventRing ev) {
+  VeccWord o;
+  o.w = word; o.rc = 0;
+  const uint32_t s = vecc_syndrome(word);
+  if (popc((uint32_t)word ^ (uint32_t)(word >> 32)) & 1u) {
+    const uint32_t bit = s ? vecc_position_to_bit(s) : 0u;
+    o.w = word ^ (1ull << bit);
+    o.rc = 1;
+    push_event(ev, ABFT_EV_VEC_CORRECTED, index, bit | (operand << 8), ABFT_FMT_VECTOR);
+  } else if (s) {
+    o.rc = -1;
+    push_event(ev, ABFT_EV_VEC_DOUBLE, index, operand << 8, ABFT_FMT_VECTOR);
+  }
+  return o;
+}
+
+__device__ __forceinline__ uint64_t vecc_bits(double v) { return (uint64_t)__double_as_longlong(v); }
+__device__ __forceinline__ double vecc_double(uint64_t w) { return __longlong_as_double((long long)w); }
+
+// full decode of one word outside any load loop: check, repair in registers, event
+__device__ __forceinline__ double vecc_decode_cold_ok(const double *p, uint32_t index, uint32_t operand,
+                                                      const EventRing &ev) {
+  uint64_t w = vecc_bits(*p);
+  if (__builtin_expect(vecc_suspect(w) != 0u, 0)) w = vecc_cold(w, index, operand, ev).w;
+  return vecc_value(w);
+}
+
+// The protected SpMV's gathers: the gathered words -> the values to multiply with; bit j of the result is
+// set when entry j failed its check.  As for the matrix elements (csr_consume), a failing entry is only
+// NOTED here ...
+template <int EPT>
+__device__ __forceinline__ uint32_t vecc_decode_gathers(double *xv) {
+  uint32_t xbad = 0u;
+#pragma unroll
+  for (int j = 0; j < EPT; j++) {
+    const uint64_t w = vecc_bits(xv[j]);
+    xbad |= vecc_suspect(w) << j;
+    xv[j] = vecc_value(w);
+  }
+  return xbad;
+}
+
+// ... and behind the tile's LDS writes the noted entries are read again, repaired in registers by
+// vecc_cold (the vector is not written back: many threads gather the same entry, and the kernel that
+// next rewrites it repairs it) and their products staged anew.  Unrolled with static selects, so col
+// and val stay in registers.
+template <int EPT>
+__device__ __forceinline__ void vecc_redo_gathers(uint32_t xbad, const double *__restrict__ x, const uint32_t *col,
+                                                  const double *val, const EventRing &ev, double *s_prod) {
+#pragma unroll
+  for (int j = 0; j < EPT; j++) {
+    if ((xbad >> j) & 1u) {
+      const VeccWord r = vecc_cold(vecc_bits(x[col[j]]), col[j], 0u, ev);
+      s_prod[2u * threadIdx.x + (uint32_t)(j >> 1) * (2u * ABFT_BLOCK) + (uint32_t)(j & 1)] = val[j] * vecc_value(r.w);
+    }
+  }
+}
+
 // One step of a cross-lane reduction on the DPP path (the operand is permuted
 // inside the VALU, nothing goes through LDS): lanes whose source is out of range
 // or whose row is masked off read 0.0.  __shfl_down on a double compiles to two
@@ -449,7 +514,7 @@ __device__ __forceinline__ void csr_issue_loads(const CsrDev &A, uint32_t base, 
 // kernel built on this was measured and dropped: 180 us vs 151 us for one tile
 // per workgroup (config 2) -- 8 resident workgroups per CU already overlap each
 // other's phases, and the extra registers cost occupancy.
-template <int MODE, int EPT>
+template <int MODE, int EPT, bool VECC = false>
 __device__ __forceinline__ void csr_consume(const CsrDev &A, const double *__restrict__ x,
                                             const EventRing &ev, uint32_t base, uint32_t lo,
                                             uint32_t hi, const CsrTileRegs<EPT> &t, double *s_prod,
@@ -496,6 +561,8 @@ __device__ __forceinline__ void csr_consume(const CsrDev &A, const double *__res
 #endif
     if (!in) xv[j] = 0.0;
   }
+  uint32_t xbad = 0u;  // VECC: bit j: the gathered entry of element j failed its check
+  if (VECC) xbad = vecc_decode_gathers<EPT>(xv) & ~bad;  // (an element noted in `bad` gathers again below)
   // no branch around the prefetch: with one, hipcc drains the whole memory queue
   // (vmcnt(0)) at the join and the overlap is gone; a caller with nothing to
   // prefetch passes nhi == nbase, which makes every lane re-read one resident pair
@@ -508,6 +575,7 @@ __device__ __forceinline__ void csr_consume(const CsrDev &A, const double *__res
     if (MODE == MODE_CONSTRAINTS)
       *reinterpret_cast<uint2 *>(s_col + k) = make_uint2(col[2 * s], col[2 * s + 1]);
   }
+  if (VECC && __builtin_expect(xbad != 0u, 0)) vecc_redo_gathers<EPT>(xbad, x, col, val, ev, s_prod);
 #ifndef ABFT_DBG_NOCOLD  // (timing-only build without the repairs: wrong results for an element that fails its check)
   if (MODE >= MODE_SED && __builtin_expect(bad != 0u, 0)) {
     // the noted elements again, from memory: repaired (and written back: reference CSR/CPUContext.cpp:275-276,
@@ -528,7 +596,10 @@ __device__ __forceinline__ void csr_consume(const CsrDev &A, const double *__res
 #ifdef ABFT_DBG_NOGATHER
         p = as_double(e.w[0], e.w[1]) * (double)c;
 #else
-        p = as_double(e.w[0], e.w[1]) * (c < A.n_in ? gather_load(x + c) : 0.0);
+        if (VECC)
+          p = as_double(e.w[0], e.w[1]) * (c < A.n_in ? vecc_decode_cold_ok(x + c, c, 0u, ev) : 0.0);
+        else
+          p = as_double(e.w[0], e.w[1]) * (c < A.n_in ? gather_load(x + c) : 0.0);
 #endif
       }
       s_prod[i - base] = p;
@@ -538,13 +609,13 @@ __device__ __forceinline__ void csr_consume(const CsrDev &A, const double *__res
 }
 
 // load + consume of one tile (the non-pipelined form)
-template <int MODE, int EPT>
+template <int MODE, int EPT, bool VECC = false>
 __device__ __forceinline__ void csr_stage(const CsrDev &A, const double *__restrict__ x,
                                           const EventRing &ev, uint32_t base, uint32_t lo,
                                           uint32_t hi, double *s_prod, uint32_t *s_col) {
   CsrTileRegs<EPT> t, unused;
   csr_issue_loads<EPT>(A, base, hi, t);
-  csr_consume<MODE, EPT>(A, x, ev, base, lo, hi, t, s_prod, s_col, false, 0u, 0u, unused);
+  csr_consume<MODE, EPT, VECC>(A, x, ev, base, lo, hi, t, s_prod, s_col, false, 0u, 0u, unused);
 }
 
 // Mode none, one tile (see CsrCompact): the loads of csr_stage, with the column source chosen per
@@ -558,7 +629,7 @@ __device__ __forceinline__ void csr_stage(const CsrDev &A, const double *__restr
 // also drained the value loads.  When e0 is odd, slot `base` holds the previous block's element, whose offset is
 // relative to that block's base: it is masked invalid, as in csr_stage.
 typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-template <int EPT>
+template <int EPT, bool VECC = false>
 __device__ __forceinline__ void csr_stage_none(const CsrDev &A, const CsrCompact &cc, uint32_t cb,
                                                const double *__restrict__ x, const EventRing &ev, uint32_t base,
                                                uint32_t lo, uint32_t hi, double *s_prod, uint32_t *s_col) {
@@ -585,7 +656,7 @@ __device__ __forceinline__ void csr_stage_none(const CsrDev &A, const CsrCompact
     t.c[s].x = compact ? cb + (raw[s].x & 0xFFFFu) : raw[s].x;
     t.c[s].y = compact ? cb + (raw[s].x >> 16) : raw[s].y;
   }
-  csr_consume<MODE_NONE, EPT>(A, x, ev, base, lo, hi, t, s_prod, s_col, false, 0u, 0u, unused);
+  csr_consume<MODE_NONE, EPT, VECC>(A, x, ev, base, lo, hi, t, s_prod, s_col, false, 0u, 0u, unused);
 }
 
 // Mode none, one packed tile (see CsrPacked): the only streamed load is the u16 code, one dword
@@ -596,10 +667,10 @@ __device__ __forceinline__ void csr_stage_none(const CsrDev &A, const CsrCompact
 // of the same two operands as csr_consume's, so y is bit-identical.  The slot before e0 (odd e0)
 // holds the previous block's code: masked invalid like in csr_stage; its index reads this
 // block's palette all the same (padded to 16 entries) and its column gathers nothing.
-template <int EPT>
+template <int EPT, bool VECC = false>
 __device__ __forceinline__ void csr_stage_packed(const CsrDev &A, const CsrPacked &cp, uint2 pd,
-                                                 const double *__restrict__ x, uint32_t base, uint32_t lo,
-                                                 uint32_t hi, double *s_prod) {
+                                                 const double *__restrict__ x, const EventRing &ev, uint32_t base,
+                                                 uint32_t lo, uint32_t hi, double *s_prod) {
   constexpr int STEPS = EPT / 2;
   const uint32_t shift = pd.y & 31u, mask = (1u << shift) - 1u;  // uniform
   const uint32_t pbase = (pd.y >> 5) * ABFT_PAL_ENTRIES;
@@ -653,12 +724,15 @@ __device__ __forceinline__ void csr_stage_packed(const CsrDev &A, const CsrPacke
     xv[j] = gather_load(x + (in ? col[j] : 0u));
     if (!in) xv[j] = 0.0;
   }
+  uint32_t xbad = 0u;
+  if (VECC) xbad = vecc_decode_gathers<EPT>(xv);
 #pragma unroll
   for (int s = 0; s < STEPS; s++) {
     const uint32_t k = 2u * threadIdx.x + (uint32_t)s * (2u * ABFT_BLOCK);
     const double p0 = val[2 * s] * xv[2 * s], p1 = val[2 * s + 1] * xv[2 * s + 1];
     *reinterpret_cast<double2 *>(s_prod + k) = make_double2(ok[2 * s] ? p0 : 0.0, ok[2 * s + 1] ? p1 : 0.0);
   }
+  if (VECC && __builtin_expect(xbad != 0u, 0)) vecc_redo_gathers<EPT>(xbad, x, col, val, ev, s_prod);
 }
 
 // Constraints mode: the reference's two checks of element i (CSR/CPUContext.cpp:186-200) on
@@ -734,7 +808,10 @@ __device__ __forceinline__ bool csr_row_sum(const CsrDev &A, const EventRing &ev
 // running sum carried by thread 0 (same order, so still bit-exact).
 //   reference: CSR/CPUContext.cpp:115-133 (none), :162-207 (constraints),
 //              :214-245 (sed), :252-289 (sec7), :297-345 (sec8), :353-411 (secded)
-template <int MODE, int EPT, bool FUSE>
+// VECC (abft_hip_spmv_vecc): x and y hold protected elements.  Every gathered x and
+// the fused product's x[row] get the full check (repaired in registers, reported, x itself not written
+// back); y[row] is stored encoded and the fused product uses the decoded x[row] and the truncated sum.
+template <int MODE, int EPT, bool FUSE, bool VECC = false>
 __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const double *__restrict__ x,
                                                               double *__restrict__ y, EventRing ev,
                                                               FuseOut fuse, TileSpan span, CsrCompact cc,
@@ -771,11 +848,11 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
       if (FUSE) xr = x[fuse.x_off + r];
     }
     if (MODE == MODE_NONE && pd.y != 0u)
-      csr_stage_packed<EPT>(A, cp, pd, x, base, e0, e1, s_prod);
+      csr_stage_packed<EPT, VECC>(A, cp, pd, x, ev, base, e0, e1, s_prod);
     else if (MODE == MODE_NONE)
-      csr_stage_none<EPT>(A, cc, cb, x, ev, base, e0, e1, s_prod, s_col);
+      csr_stage_none<EPT, VECC>(A, cc, cb, x, ev, base, e0, e1, s_prod, s_col);
     else
-      csr_stage<MODE, EPT>(A, x, ev, base, e0, e1, s_prod, s_col);
+      csr_stage<MODE, EPT, VECC>(A, x, ev, base, e0, e1, s_prod, s_col);
     __syncthreads();
     for (uint32_t row = r; row < row1; row += ABFT_BLOCK) {
       if (row != r) {
@@ -789,8 +866,18 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
       if (rs < e0 || re > e1 || re < rs) continue;  // inconsistent row pointers: never touch LDS out of range
       double acc = 0.0;
       if (csr_row_sum<MODE>(A, ev, base, rs, re, re, s_prod, s_col, acc, row)) {
-        y[row] = acc;
-        if (FUSE) dsum += xr * acc;
+        if (VECC) {
+          const uint64_t yw = vecc_encode(acc);
+          y[row] = vecc_double(yw);
+          if (FUSE) {
+            uint64_t xw = vecc_bits(xr);
+            if (__builtin_expect(vecc_suspect(xw) != 0u, 0)) xw = vecc_cold(xw, fuse.x_off + row, 0u, ev).w;
+            dsum += vecc_value(xw) * vecc_value(yw);
+          }
+        } else {
+          y[row] = acc;
+          if (FUSE) dsum += xr * acc;
+        }
       }
     }
   } else {
@@ -808,14 +895,20 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
         const uint32_t b = lo & ~1u;
         const uint32_t hi = min(re, b + TILE);
         __syncthreads();
-        csr_stage<MODE, EPT>(A, x, ev, b, lo, hi, s_prod, s_col);
+        csr_stage<MODE, EPT, VECC>(A, x, ev, b, lo, hi, s_prod, s_col);
         __syncthreads();
         if (threadIdx.x == 0 && ok) ok = csr_row_sum<MODE>(A, ev, b, lo, hi, re, s_prod, s_col, acc, row);
         lo = hi;
       }
       if (threadIdx.x == 0 && ok) {
-        y[row] = acc;
-        if (FUSE) dsum += x[fuse.x_off + row] * acc;
+        if (VECC) {
+          const uint64_t yw = vecc_encode(acc);
+          y[row] = vecc_double(yw);
+          if (FUSE) dsum += vecc_decode_cold_ok(x + fuse.x_off + row, fuse.x_off + row, 0u, ev) * vecc_value(yw);
+        } else {
+          y[row] = acc;
+          if (FUSE) dsum += x[fuse.x_off + row] * acc;
+        }
       }
     }
   }
@@ -953,8 +1046,15 @@ int spmv_csr_panels_blocks_per_cu(int mode, bool fuse) {
 
 template <int MODE>
 static hipError_t launch_spmv_csr_mode(const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
-                                       const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s) {
-  if (fuse) {
+                                       const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s,
+                                       bool vecc) {
+  if (vecc && fuse)
+    hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true, true>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
+                       x, y, ev, *fuse, span, cc, cp);
+  else if (vecc)
+    hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, false, true>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
+                       x, y, ev, FuseOut{}, span, cc, cp);
+  else if (fuse) {
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
                        x, y, ev, *fuse, span, cc, cp);
   } else
@@ -964,7 +1064,7 @@ static hipError_t launch_spmv_csr_mode(const CsrDev &A, const CsrCompact &cc, co
 }
 
 hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
-                           const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s) {
+                           const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s, bool vecc) {
   // every tile the span maps to must exist: checked here, on the host
   if (span.count == 0) return hipSuccess;
   if ((uint64_t)span.first + span.count + span.skip > A.nblk || span.cut > span.count) return hipErrorInvalidValue;
@@ -974,12 +1074,12 @@ hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, cons
   if ((cp.code16 || cp.pdesc || cp.pal) && (mode != MODE_NONE || !cp.code16 || !cp.pdesc || !cp.pal))
     return hipErrorInvalidValue;
   switch (mode) {
-    case MODE_NONE: return launch_spmv_csr_mode<MODE_NONE>(A, cc, cp, span, x, y, ev, fuse, s);
-    case MODE_CONSTRAINTS: return launch_spmv_csr_mode<MODE_CONSTRAINTS>(A, cc, cp, span, x, y, ev, fuse, s);
-    case MODE_SED: return launch_spmv_csr_mode<MODE_SED>(A, cc, cp, span, x, y, ev, fuse, s);
-    case MODE_SEC7: return launch_spmv_csr_mode<MODE_SEC7>(A, cc, cp, span, x, y, ev, fuse, s);
-    case MODE_SEC8: return launch_spmv_csr_mode<MODE_SEC8>(A, cc, cp, span, x, y, ev, fuse, s);
-    case MODE_SECDED: return launch_spmv_csr_mode<MODE_SECDED>(A, cc, cp, span, x, y, ev, fuse, s);
+    case MODE_NONE: return launch_spmv_csr_mode<MODE_NONE>(A, cc, cp, span, x, y, ev, fuse, s, vecc);
+    case MODE_CONSTRAINTS: return launch_spmv_csr_mode<MODE_CONSTRAINTS>(A, cc, cp, span, x, y, ev, fuse, s, vecc);
+    case MODE_SED: return launch_spmv_csr_mode<MODE_SED>(A, cc, cp, span, x, y, ev, fuse, s, vecc);
+    case MODE_SEC7: return launch_spmv_csr_mode<MODE_SEC7>(A, cc, cp, span, x, y, ev, fuse, s, vecc);
+    case MODE_SEC8: return launch_spmv_csr_mode<MODE_SEC8>(A, cc, cp, span, x, y, ev, fuse, s, vecc);
+    case MODE_SECDED: return launch_spmv_csr_mode<MODE_SECDED>(A, cc, cp, span, x, y, ev, fuse, s, vecc);
     default: return hipErrorInvalidValue;
   }
 }
@@ -4988,5 +5088,268 @@ hipError_t launch_stream_copy(double *dst, const double *src, size_t n, hipStrea
 hipError_t launch_stream_read(const double *src, size_t n, double *sink, hipStream_t s) {
   hipLaunchKernelGGL(stream_read_kernel, dim3(256 * 8), dim3(ABFT_BLOCK), 0, s, (const double2 *)src, n / 2,
                      sink);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------- protected vectors --
+// The vector kernels of the abft_hip_*_vecc entries (the code: ecc_device.h).
+// Each walks its vectors exactly as its plain counterpart does -- same grid, stride, VEC by alignment,
+// block_sum and last-block fold --, decodes every word it loads, computes in full fp64 with separate
+// multiply and add, and encodes every word it stores; sums are over the values as stored.
+//
+// The hot loops hold no call (section 4, "Round 4, late"): a step with a word that fails its check is
+// only NOTED -- nothing of it is stored or summed -- and behind the loop a thread with a noted step walks
+// its chain once more.  There a step that is clean has been carried out (its outputs are codewords
+// again, its read-only inputs always were) and adds the stored values it left; a step that still fails is
+// the noted one: vecc_cold repairs its words in registers (an input that is only read is not written
+// back), the step is carried out and adds what it stores.  Same operands and the same order of adds as an
+// undamaged call, so every vector and the sum have the undamaged call's bits.
+
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void vector_encode_kernel(double *__restrict__ v, int n) {
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      double2 t = *reinterpret_cast<double2 *>(v + i);
+      t.x = vecc_double(vecc_encode(t.x));
+      t.y = vecc_double(vecc_encode(t.y));
+      *reinterpret_cast<double2 *>(v + i) = t;
+    } else {
+      v[i] = vecc_double(vecc_encode(v[i]));
+    }
+  }
+}
+
+// counts[0] += words repaired (and written back), counts[1] += words with two flipped bits (left as they are)
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void vector_scrub_kernel(double *__restrict__ v, int n, uint32_t *counts,
+                                                                  EventRing ev) {
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
+  uint32_t bad = 0u;
+  for (long i = first; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      const double2 t = *reinterpret_cast<const double2 *>(v + i);
+      bad |= vecc_suspect(vecc_bits(t.x)) | vecc_suspect(vecc_bits(t.y));
+    } else {
+      bad |= vecc_suspect(vecc_bits(v[i]));
+    }
+  }
+  if (__builtin_expect(bad != 0u, 0)) {
+    uint32_t fixed = 0u, lost = 0u;
+    for (long i = first; i < n; i += stride) {
+      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
+      for (int k = 0; k < m; k++) {
+        const uint64_t w = vecc_bits(v[i + k]);
+        if (!vecc_suspect(w)) continue;
+        const VeccWord o = vecc_cold(w, (uint32_t)(i + k), 0u, ev);
+        if (o.rc > 0) { v[i + k] = vecc_double(o.w); fixed++; }
+        else lost++;
+      }
+    }
+    if (fixed) atomicAdd(counts, fixed);
+    if (lost) atomicAdd(counts + 1, lost);
+  }
+}
+
+// dot on protected vectors: operands 0 (a) and 1 (b), neither written back
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void dot_vecc_kernel(const double *__restrict__ a,
+                                                              const double *__restrict__ b, int n,
+                                                              ReduceOut out, EventRing ev) {
+  __shared__ double s_w[4];
+  double acc = 0.0;
+  uint32_t bad = 0u;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
+  for (long i = first; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      const double2 av = *reinterpret_cast<const double2 *>(a + i);
+      const double2 bv = *reinterpret_cast<const double2 *>(b + i);
+      const uint64_t a0 = vecc_bits(av.x), a1 = vecc_bits(av.y), b0 = vecc_bits(bv.x), b1 = vecc_bits(bv.y);
+      bad |= (vecc_suspect(a0) | vecc_suspect(a1)) | (vecc_suspect(b0) | vecc_suspect(b1));
+      acc += vecc_value(a0) * vecc_value(b0);
+      acc += vecc_value(a1) * vecc_value(b1);
+    } else {
+      const uint64_t a0 = vecc_bits(a[i]), b0 = vecc_bits(b[i]);
+      bad |= vecc_suspect(a0) | vecc_suspect(b0);
+      acc += vecc_value(a0) * vecc_value(b0);
+    }
+  }
+  if (__builtin_expect(bad != 0u, 0)) {  // nothing was stored: the whole chain again, with the repairs
+    acc = 0.0;
+    for (long i = first; i < n; i += stride) {
+      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
+      for (int k = 0; k < m; k++) {
+        const uint32_t j = (uint32_t)(i + k);
+        const double av = vecc_decode_cold_ok(a + i + k, j, 0u, ev);
+        acc += av * vecc_decode_cold_ok(b + i + k, j, 1u, ev);
+      }
+    }
+  }
+  acc = block_sum(acc, s_w);
+  reduce_finish(acc, out, s_w);
+}
+
+// calc_xr on protected vectors: x += alpha p; r -= alpha w (operands 0..3); r.r over the r it stores
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_xr_vecc_kernel(double *__restrict__ x, double *__restrict__ r,
+                                                                  const double *__restrict__ p,
+                                                                  const double *__restrict__ w, double alpha, int n,
+                                                                  ReduceOut out, EventRing ev) {
+  __shared__ double s_w[4];
+  double acc = 0.0;
+  uint32_t bad = 0u;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
+  for (long i = first; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      const double2 xv = *reinterpret_cast<const double2 *>(x + i);
+      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const double2 pv = *reinterpret_cast<const double2 *>(p + i);
+      const double2 wv = *reinterpret_cast<const double2 *>(w + i);
+      const uint64_t x0 = vecc_bits(xv.x), x1 = vecc_bits(xv.y), r0 = vecc_bits(rv.x), r1 = vecc_bits(rv.y);
+      const uint64_t p0 = vecc_bits(pv.x), p1 = vecc_bits(pv.y), w0 = vecc_bits(wv.x), w1 = vecc_bits(wv.y);
+      const uint32_t sus = (vecc_suspect(x0) | vecc_suspect(x1)) | (vecc_suspect(r0) | vecc_suspect(r1)) |
+                           (vecc_suspect(p0) | vecc_suspect(p1)) | (vecc_suspect(w0) | vecc_suspect(w1));
+      bad |= sus;
+      if (!sus) {
+        const uint64_t xs0 = vecc_encode(vecc_value(x0) + alpha * vecc_value(p0));
+        const uint64_t xs1 = vecc_encode(vecc_value(x1) + alpha * vecc_value(p1));
+        const uint64_t rs0 = vecc_encode(vecc_value(r0) - alpha * vecc_value(w0));
+        const uint64_t rs1 = vecc_encode(vecc_value(r1) - alpha * vecc_value(w1));
+        *reinterpret_cast<double2 *>(x + i) = make_double2(vecc_double(xs0), vecc_double(xs1));
+        *reinterpret_cast<double2 *>(r + i) = make_double2(vecc_double(rs0), vecc_double(rs1));
+        acc += vecc_value(rs0) * vecc_value(rs0);
+        acc += vecc_value(rs1) * vecc_value(rs1);
+      }
+    } else {
+      const uint64_t x0 = vecc_bits(x[i]), r0 = vecc_bits(r[i]), p0 = vecc_bits(p[i]), w0 = vecc_bits(w[i]);
+      const uint32_t sus = (vecc_suspect(x0) | vecc_suspect(r0)) | (vecc_suspect(p0) | vecc_suspect(w0));
+      bad |= sus;
+      if (!sus) {
+        const uint64_t xs = vecc_encode(vecc_value(x0) + alpha * vecc_value(p0));
+        const uint64_t rs = vecc_encode(vecc_value(r0) - alpha * vecc_value(w0));
+        x[i] = vecc_double(xs);
+        r[i] = vecc_double(rs);
+        acc += vecc_value(rs) * vecc_value(rs);
+      }
+    }
+  }
+  if (__builtin_expect(bad != 0u, 0)) {
+    acc = 0.0;
+    for (long i = first; i < n; i += stride) {
+      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
+      uint32_t sus = 0u;
+      for (int k = 0; k < m; k++)
+        sus |= (vecc_suspect(vecc_bits(x[i + k])) | vecc_suspect(vecc_bits(r[i + k]))) |
+               (vecc_suspect(vecc_bits(p[i + k])) | vecc_suspect(vecc_bits(w[i + k])));
+      for (int k = 0; k < m; k++) {
+        uint64_t rs = vecc_bits(r[i + k]);  // a step carried out above: what it stored
+        if (sus) {
+          const uint32_t j = (uint32_t)(i + k);
+          const double xo = vecc_decode_cold_ok(x + i + k, j, 0u, ev);
+          const double ro = vecc_decode_cold_ok(r + i + k, j, 1u, ev);
+          const double po = vecc_decode_cold_ok(p + i + k, j, 2u, ev);
+          const double wo = vecc_decode_cold_ok(w + i + k, j, 3u, ev);
+          rs = vecc_encode(ro - alpha * wo);
+          x[i + k] = vecc_double(vecc_encode(xo + alpha * po));
+          r[i + k] = vecc_double(rs);
+        }
+        acc += vecc_value(rs) * vecc_value(rs);
+      }
+    }
+  }
+  acc = block_sum(acc, s_w);
+  reduce_finish(acc, out, s_w);
+}
+
+// calc_p on protected vectors: p = r + beta p (operands 0: p, 1: r); p is left repaired, r not written back
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_p_vecc_kernel(double *__restrict__ p, const double *__restrict__ r,
+                                                                 double beta, int n, EventRing ev) {
+  uint32_t bad = 0u;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
+  for (long i = first; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      const double2 pv = *reinterpret_cast<const double2 *>(p + i);
+      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const uint64_t p0 = vecc_bits(pv.x), p1 = vecc_bits(pv.y), r0 = vecc_bits(rv.x), r1 = vecc_bits(rv.y);
+      const uint32_t sus = (vecc_suspect(p0) | vecc_suspect(p1)) | (vecc_suspect(r0) | vecc_suspect(r1));
+      bad |= sus;
+      if (!sus) {
+        const uint64_t q0 = vecc_encode(vecc_value(r0) + beta * vecc_value(p0));
+        const uint64_t q1 = vecc_encode(vecc_value(r1) + beta * vecc_value(p1));
+        *reinterpret_cast<double2 *>(p + i) = make_double2(vecc_double(q0), vecc_double(q1));
+      }
+    } else {
+      const uint64_t p0 = vecc_bits(p[i]), r0 = vecc_bits(r[i]);
+      const uint32_t sus = vecc_suspect(p0) | vecc_suspect(r0);
+      bad |= sus;
+      if (!sus) p[i] = vecc_double(vecc_encode(vecc_value(r0) + beta * vecc_value(p0)));
+    }
+  }
+  if (__builtin_expect(bad != 0u, 0)) {
+    for (long i = first; i < n; i += stride) {
+      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
+      uint32_t sus = 0u;
+      for (int k = 0; k < m; k++) sus |= vecc_suspect(vecc_bits(p[i + k])) | vecc_suspect(vecc_bits(r[i + k]));
+      if (!sus) continue;  // carried out above
+      for (int k = 0; k < m; k++) {
+        const uint32_t j = (uint32_t)(i + k);
+        const double po = vecc_decode_cold_ok(p + i + k, j, 0u, ev), ro = vecc_decode_cold_ok(r + i + k, j, 1u, ev);
+        p[i + k] = vecc_double(vecc_encode(ro + beta * po));
+      }
+    }
+  }
+}
+
+hipError_t launch_vector_encode(double *v, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+  if (aligned16(v))
+    hipLaunchKernelGGL(vector_encode_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, v, n);
+  else
+    hipLaunchKernelGGL(vector_encode_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, v, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_vector_scrub(double *v, int n, uint32_t *counts, EventRing ev, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+  if (aligned16(v))
+    hipLaunchKernelGGL(vector_scrub_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, v, n, counts, ev);
+  else
+    hipLaunchKernelGGL(vector_scrub_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, v, n, counts, ev);
+  return hipGetLastError();
+}
+
+hipError_t launch_dot_vecc(const double *a, const double *b, int n, const ReduceOut &out, EventRing ev, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  if (aligned16(a, b))
+    hipLaunchKernelGGL(dot_vecc_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, a, b, n, out, ev);
+  else
+    hipLaunchKernelGGL(dot_vecc_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, a, b, n, out, ev);
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_xr_vecc(double *x, double *r, const double *p, const double *w, double alpha, int n,
+                               const ReduceOut &out, EventRing ev, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  if (aligned16(x, r, p, w))
+    hipLaunchKernelGGL(calc_xr_vecc_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, r, p, w, alpha, n, out, ev);
+  else
+    hipLaunchKernelGGL(calc_xr_vecc_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, r, p, w, alpha, n, out, ev);
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_p_vecc(double *p, const double *r, double beta, int n, EventRing ev, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+  if (aligned16(p, r))
+    hipLaunchKernelGGL(calc_p_vecc_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, n, ev);
+  else
+    hipLaunchKernelGGL(calc_p_vecc_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, n, ev);
   return hipGetLastError();
 }

@@ -67,14 +67,20 @@ typedef enum {
   /* not a reference line: more COO elements carry a silently corrupted column than the
    * engine's list holds (index = its capacity); results past this point are not the
    * reference's, so the event is fatal */
-  ABFT_EV_MOVED_OVERFLOW = 9
+  ABFT_EV_MOVED_OVERFLOW = 9,
+  /* protected vectors (the abft_hip_*_vecc entries; fmt = ABFT_FMT_VECTOR): `index` is the element
+   * inside the operand, `bit` holds the word bit in bits 0..7 and the operand's ordinal among the
+   * entry's vector arguments, from 0, in bits 8..15 */
+  ABFT_EV_VEC_CORRECTED = 10, /* "[ECC] corrected bit %u of vector operand %u at index %d"            */
+  ABFT_EV_VEC_DOUBLE = 11     /* "[ECC] double-bit error detected in vector operand %u at index %d" fatal */
 } abft_event_kind;
+#define ABFT_FMT_VECTOR 2 /* abft_event.fmt of the two vector events */
 
 typedef struct {
   uint32_t kind;  /* abft_event_kind                                             */
   uint32_t index; /* element index i (or row, for the CSR row events), global    */
   uint32_t bit;   /* corrected bit for ABFT_EV_CORRECTED_BIT, else 0             */
-  uint32_t fmt;   /* abft_format of the matrix that raised it                    */
+  uint32_t fmt;   /* abft_format of the matrix that raised it (ABFT_FMT_VECTOR: a vector) */
 } abft_event;
 
 typedef struct abft_hip_ctx abft_hip_ctx;
@@ -293,6 +299,45 @@ int abft_hip_residual_restart_block(abft_hip_ctx *ctx, abft_hip_matrix *A, const
 /* dst[:, j] = src[:, j] for the columns set in `mask` (checkpoints of block vectors) */
 int abft_hip_copy_block(abft_hip_ctx *ctx, abft_hip_vector *dst, const abft_hip_vector *src, int k,
                         uint32_t mask);
+
+/* ---- protected vectors: a SECDED code in each double's low mantissa bits ----
+ * Opt-in.  A protected element is one 64-bit word: bits 7..63 are the double's sign, exponent
+ * and top 45 mantissa bits, bits 1..6 the check bits of the (64, 57) extended Hamming code
+ * (check bit k at bit 1 + k, Hamming position 2^k; data bit 7, 8, ... at positions 3, 5, 6, 7,
+ * 9, ...), bit 0 the overall parity.  Every *_vecc entry decodes each operand element it loads
+ * -- a single flipped bit is repaired in registers and reported (ABFT_EV_VEC_CORRECTED), two are
+ * fatal (ABFT_EV_VEC_DOUBLE) -- computes in full fp64 with separate multiply and add on the
+ * words without their code bits, and encodes every element it stores (truncation toward zero).
+ * Sums are taken over the values as stored.  Vectors a call only reads are not written back.
+ * Each entry walks its vectors and folds its sum as its plain counterpart does, starts like
+ * every other entry (a pending x update applied, a speculation voided) and checks every length
+ * and overlap before it enqueues anything.  abft_hip_vector_copy / _map / _unmap / _flip move
+ * stored words as they are: a copy of a codeword is a codeword.  The loop:
+ *   encode b, x;  copy r <- b;  copy p <- r;  rr = dot_vecc(r, r)
+ *   while rr > threshold:  spmv_vecc(A, p, w);  alpha = rr / dot_vecc(p, w)
+ *                          rr_new = calc_xr_vecc(x, r, p, w, alpha);  calc_p_vecc(p, r, rr_new / rr)
+ *   scrub x (and b) before downloading them. */
+
+/* v[i] <- the codeword of the double v[i] (a NaN whose payload lay in bits 0..6 keeps bit 51) */
+int abft_hip_vector_encode(abft_hip_ctx *ctx, abft_hip_vector *v);
+/* check every word of v, write repaired words back, queue the events (operand 0); the counts of
+ * repaired and of uncorrectable (left as they are) words go to *corrected / *uncorrectable */
+int abft_hip_vector_scrub(abft_hip_ctx *ctx, abft_hip_vector *v, int *corrected, int *uncorrectable);
+/* result = A vec on protected vectors (operands 0, 1): every gathered vec entry decoded, result
+ * stored encoded.  CSR matrices in the streaming row-block layout only, all six modes; anything
+ * else: ABFT_ERR_INVALID.  On a square matrix the product vec . result (decoded vec, truncated
+ * result) is formed in the same pass and serves the abft_hip_dot_vecc(vec, result) that
+ * follows; a plain abft_hip_dot is never served from it, nor a protected dot from abft_hip_spmv. */
+int abft_hip_spmv_vecc(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                       abft_hip_vector *result);
+/* *out = a . b (operands 0, 1) */
+int abft_hip_dot_vecc(abft_hip_ctx *ctx, const abft_hip_vector *a, const abft_hip_vector *b, double *out);
+/* x += alpha p; r -= alpha w (operands 0..3); *rr = abft_hip_dot_vecc(r, r) of the r it leaves.
+ * Both halves run in this call (no deferred x update).  x and r may overlap no other operand. */
+int abft_hip_calc_xr_vecc(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r, const abft_hip_vector *p,
+                          const abft_hip_vector *w, double alpha, double *rr);
+/* p = r + beta p (operands 0, 1); p may not overlap r */
+int abft_hip_calc_p_vecc(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, double beta);
 
 /* ---- Jacobi (diagonal) preconditioning ------------------------------------
  * M^-1 = diag(dinv) is one more N-vector; z = dinv * r is one rounded product formed
@@ -546,7 +591,9 @@ int abft_hip_graph_destroy(abft_hip_graph *graph);
 /* Synchronise, then move the queued events to `buf` (at most `cap`), sorted
  * by (index, kind) and cut after the first fatal one -- the order a
  * single-threaded reference run prints them in.  *count = events returned,
- * *fatal = 1 if the last one is fatal (the reference would have exit(1)ed). */
+ * *fatal = 1 if the last one is fatal (the reference would have exit(1)ed).
+ * Vector events (ABFT_FMT_VECTOR) equal in all four fields are reported once per
+ * drain: every gatherer of one vector entry sees the same flip. */
 int abft_hip_drain_events(abft_hip_ctx *ctx, abft_event *buf, int cap, int *count, int *fatal);
 /* Capacity of the device event queue = the `cap` with which drain never truncates.
  * drain returns ABFT_ERR_RANGE (after filling buf / count / fatal) if the device queued
