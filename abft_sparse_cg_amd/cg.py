@@ -62,6 +62,8 @@ Additional options of this build:
                               with --vector-ecc secded also w or b) (may be repeated)
       --precond         P     Preconditioner: none (default) or jacobi (the inverse
                               diagonal of A, applied inside the vector kernels)
+      --block-fused           With --rhs K: the fused block iteration (P.W formed inside
+                              the SpMM, x and p updated in one pass)
       --vector-ecc      E     Protect the CG vectors: none (default) or secded, a (64, 57)
                               code in each double's low 7 mantissa bits (CSR, one
                               right-hand side, no --precond / --check-every)
@@ -81,7 +83,7 @@ def parse(argv):
     o = dict(num_blocks=25, max_itrs=1000, conv=0.001, matrix_file=DEFAULT_MTX, synthetic=None, target="cpu",
              mode="none", flips=0, kind="ANY", seed=None, quiet=False, flip_at=None, fmt="csr", list=False,
              rhs=1, check_every=0, check_tol=1e-7, max_rollbacks=3, flip_vector=[], precond="none",
-             vector_ecc="none")
+             vector_ecc="none", block_fused=False)
 
     def num(s, conv):
         try:
@@ -181,6 +183,8 @@ def parse(argv):
             o["vector_ecc"] = arg("Invalid vector protection (want none or secded)")
             if o["vector_ecc"] not in ("none", "secded"):
                 fail("Invalid vector protection (want none or secded)")
+        elif a == "--block-fused":
+            o["block_fused"] = True
         elif a in ("--quiet", "-q"):
             o["quiet"] = True
         elif a in ("--help", "-h"):
@@ -189,6 +193,8 @@ def parse(argv):
         else:
             fail("Unrecognized argument '%s' (try '--help')" % a)
         i += 1
+    if o["block_fused"] and o["rhs"] < 2:
+        fail("--block-fused needs --rhs K with K of 2 to 8: it selects the block loop's fused iteration")
     if o["vector_ecc"] == "none":
         if any(f[1] in ("w", "b") for f in o["flip_vector"]):
             fail(FLIP_VECTOR_MSG)  # (known only here: --vector-ecc may follow --flip-vector)
@@ -398,6 +404,8 @@ def run_block(o):
 
     vecs = vector_flips(o, n * K, {"x": x, "r": r, "p": p})
     dinv = make_preconditioner(o, ctx, A)
+    if o["block_fused"]:
+        print("block iteration: fused")
     bounds = [o["check_tol"] * float(np.linalg.norm(generators.reference_rhs(n, seed=1 + j))) for j in range(K)]
     checks = {}
 
@@ -413,7 +421,8 @@ def run_block(o):
     try:
         itrs, _ = cg_solve_block(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
                                  check_every=o["check_every"], check_tol=o["check_tol"],
-                                 max_rollbacks=o["max_rollbacks"], on_check=on_check, precond=dinv)
+                                 max_rollbacks=o["max_rollbacks"], on_check=on_check, precond=dinv,
+                                 **({"fused": True} if o["block_fused"] else {}))
     except ResidualCheckFailed as e:
         print("[ABFT] %s" % e)
         ctx.close()

@@ -269,6 +269,50 @@ class HIPContext:
         b[:k] = beta
         check(self.L.abft_hip_calc_p_block(self.h, p.h, r.h, k, b.ctypes.data_as(capi.f64p), int(active)))
 
+    # ---- the fused block iteration (include/abft_hip.h): cg_solve_block(..., fused=True) ----
+    def spmm_dot(self, mat, P, W, k, drain=True):
+        """W = A P as spmm, and -> np.ndarray of the k products P[:, j] . W[:, j], formed inside the
+        SpMM from W's rows (no separate dot pass).  The sums are read here, so events pending after
+        the call are drained as after dot_block; drain=True drains in any case, as spmm does."""
+        out = np.zeros(k)
+        check(self.L.abft_hip_spmm_dot(self.h, mat.h, P.h, W.h, k, out.ctypes.data_as(capi.f64p)))
+        if drain:
+            self._drain()
+        else:
+            self._drain_if_pending()
+        return out
+
+    def calc_r_block(self, R, W, k, alpha, active, dinv=None):
+        """R[:, j] -= alpha[j] W[:, j] for the columns set in `active`; -> rr[k], or with dinv
+        (rz[k], rr[k]), of every column: the bits calc_xr_block / calc_xr_precond_block give"""
+        a = np.zeros(capi.MAX_RHS)
+        a[:k] = alpha
+        if dinv is None:
+            out = np.zeros(k)
+            check(self.L.abft_hip_calc_r_block(self.h, R.h, W.h, k, a.ctypes.data_as(capi.f64p), int(active),
+                                               out.ctypes.data_as(capi.f64p)))
+            self._drain_if_pending()
+            return out
+        out = np.zeros(2 * k)
+        check(self.L.abft_hip_calc_r_precond_block(self.h, R.h, W.h, dinv.h, k, a.ctypes.data_as(capi.f64p),
+                                                   int(active), out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return out[0::2].copy(), out[1::2].copy()
+
+    def calc_px_block(self, X, P, R, k, alpha, beta, active, dinv=None):
+        """for the columns set in `active`: X[:, j] += alpha[j] P[:, j], then P[:, j] = R[:, j] + beta[j] P[:, j]
+        (with dinv: dinv * R[:, j] in R[:, j]'s place), P read once"""
+        a = np.zeros(capi.MAX_RHS)
+        a[:k] = alpha
+        b = np.zeros(capi.MAX_RHS)
+        b[:k] = beta
+        if dinv is None:
+            check(self.L.abft_hip_calc_px_block(self.h, X.h, P.h, R.h, k, a.ctypes.data_as(capi.f64p),
+                                                b.ctypes.data_as(capi.f64p), int(active)))
+        else:
+            check(self.L.abft_hip_calc_px_precond_block(self.h, X.h, P.h, R.h, dinv.h, k, a.ctypes.data_as(capi.f64p),
+                                                        b.ctypes.data_as(capi.f64p), int(active)))
+
     # ---- residual checks (include/abft_hip.h) ----
     def flip_vector(self, v, index, bits):
         """XOR the given bits (0-63) into the double v[index] (for a block vector: row * K + column)"""
@@ -701,7 +745,7 @@ def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration
 
 
 def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None, check_every=0,
-                   check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None, precond=None):
+                   check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None, precond=None, fused=False):
     """cg_solve for the K columns of block vectors (ctx.create_block) at once: per column j exactly
     cg_solve's control flow -- column j iterates while itrs[j] < max_itrs and rr[j] > conv_threshold --
     on one spmm / dot_block / calc_xr_block / calc_p_block per iteration.  A column that has stopped
@@ -716,7 +760,12 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
     iterations.
 
     precond: as in cg_solve, one N-entry dinv for all K columns (one operator), through the *_precond_block
-    calls; after a rollback precond_start_block rewrites P in the rolled-back columns only."""
+    calls; after a rollback precond_start_block rewrites P in the rolled-back columns only.
+
+    fused: the iteration in three calls -- spmm_dot (P . W out of the SpMM), calc_r_block (r and its sums),
+    calc_px_block (x and p in one pass over p) -- instead of spmm / dot_block / calc_xr_block / calc_p_block:
+    64 N K bytes of vectors behind the SpMM instead of 88 N K.  Control flow, masks and checks are the same;
+    x, r and p get the same operations, and only P . W is summed in another order."""
     _check_args(check_every, check_tol, max_rollbacks)
     k = B.K
     if not k:
@@ -802,14 +851,26 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
             if not active:
                 break
             on = [(active >> j) & 1 for j in range(k)]
-            ctx.spmm(A, P, W, k, drain=False)
-            pw = ctx.dot_block(P, W, k)
-            if precond is None:
+            num = rr if precond is None else rz
+            extra = () if precond is None else (precond,)
+            if fused:
+                pw = ctx.spmm_dot(A, P, W, k, drain=False)
+                alpha = [fdiv(num[j], pw[j]) if on[j] else 0.0 for j in range(k)]
+                sums = ctx.calc_r_block(R, W, k, alpha, active, *extra)
+                rz_new, rr_new = (None, sums) if precond is None else sums
+                num_new = rr_new if precond is None else rz_new
+                beta = [fdiv(num_new[j], num[j]) if on[j] else 0.0 for j in range(k)]
+                ctx.calc_px_block(X, P, R, k, alpha, beta, active, *extra)
+            elif precond is None:
+                ctx.spmm(A, P, W, k, drain=False)
+                pw = ctx.dot_block(P, W, k)
                 alpha = [fdiv(rr[j], pw[j]) if on[j] else 0.0 for j in range(k)]
                 rr_new = ctx.calc_xr_block(X, R, P, W, k, alpha, active)
                 beta = [fdiv(rr_new[j], rr[j]) if on[j] else 0.0 for j in range(k)]
                 ctx.calc_p_block(P, R, k, beta, active)
             else:
+                ctx.spmm(A, P, W, k, drain=False)
+                pw = ctx.dot_block(P, W, k)
                 alpha = [fdiv(rz[j], pw[j]) if on[j] else 0.0 for j in range(k)]
                 rz_new, rr_new = ctx.calc_xr_precond_block(X, R, P, W, precond, k, alpha, active)
                 beta = [fdiv(rz_new[j], rz[j]) if on[j] else 0.0 for j in range(k)]

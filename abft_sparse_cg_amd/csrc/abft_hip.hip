@@ -119,6 +119,8 @@ struct abft_hip_ctx {
   HostSlotK *bslot = nullptr, *bslot_dev = nullptr;  // pinned K-wide result slot, its device alias
   HostSlotW *wslot = nullptr, *wslot_dev = nullptr;  // ... and the 2K-wide one of abft_hip_residual_gap_block
   uint32_t bseq = 0;                    // last sequence number handed to a block reduction
+  double *dotparts = nullptr;           // abft_hip_spmm_dot: k * nblk row-block partials, grown on demand
+  size_t dotparts_cap = 0;
   unsigned prof = 0;  // bit k: bracket launches of kernel k with HIP events
   unsigned prof_stride = 1, prof_seen[ABFT_K_COUNT] = {};  // ... every prof_stride-th launch of it
   ProfSlot prof_k[ABFT_K_COUNT];
@@ -441,6 +443,7 @@ extern "C" int abft_hip_shutdown(abft_hip_ctx *ctx) {
   }
   (void)hipFree(ctx->tail_sync);
   (void)hipFree(ctx->bpartials);
+  (void)hipFree(ctx->dotparts);
   if (ctx->bslot) (void)hipHostFree(ctx->bslot);
   if (ctx->wslot) (void)hipHostFree(ctx->wslot);
   if (getenv("ABFT_HIP_VERBOSE") && (ctx->spec.commits || ctx->spec.drops))
@@ -3393,6 +3396,138 @@ extern "C" int abft_hip_calc_p_precond_block(abft_hip_ctx *ctx, abft_hip_vector 
   KernelTimer t(ctx, ABFT_K_CALC_P);
   HIPCHK(launch_calc_p_precond_block(P->d, R->d, dinv->d, dinv->n, k, b, active, ctx->stream));
   return ABFT_OK;
+}
+
+// ---- the fused block iteration: P.W out of the SpMM, r and its sums, then x and p in one pass ----
+// Nothing is carried from one call to the next: every sum comes back through the call that forms it.
+
+extern "C" int abft_hip_spmm_dot(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *P,
+                                 abft_hip_vector *W, int k, double *out) {
+  if (int rc = bind_block(ctx)) return rc;
+  if (!mat || !P || !W || !out) return set_err(ABFT_ERR_INVALID, "spmm_dot: null argument");
+  if (mat->fmt != ABFT_FMT_CSR)
+    return set_err(ABFT_ERR_INVALID, "spmm_dot: COO matrices have no block SpMV; create the matrix as CSR with "
+                   "abft_hip_matrix_create_csr_stream");
+  if (mat->use_panels || mat->use_sweep || mat->use_slice)
+    return set_err(ABFT_ERR_INVALID, "spmm_dot: the matrix is stored in the %s layout; the block SpMV runs on the "
+                   "streaming row-block layout: create the matrix with abft_hip_matrix_create_csr_stream",
+                   mat->use_slice ? "slice" : mat->use_sweep ? "sweep" : "panel");
+  if (mat->csr.index_base != 0 || mat->csr.gidx)
+    return set_err(ABFT_ERR_INVALID, "spmm_dot: the matrix is a shard; the block SpMV takes a whole square matrix");
+  if (mat->csr.n_in != mat->csr.n_out)
+    return set_err(ABFT_ERR_INVALID, "spmm_dot: the matrix is not square (%u x %u): P . (A P) needs as many rows "
+                   "as columns", mat->csr.n_out, mat->csr.n_in);
+  const int N = (int)mat->csr.n_out;
+  if (int rc = check_block("spmm_dot", k, N, {P, W})) return rc;
+  if (!disjoint(P, W)) return set_err(ABFT_ERR_INVALID, "spmm_dot: input and output overlap");
+  if (int rc = block_slot(ctx)) return rc;
+  const size_t need = (size_t)k * mat->csr.nblk;
+  if (need > ctx->dotparts_cap) {
+    (void)hipFree(ctx->dotparts);
+    ctx->dotparts = nullptr;
+    ctx->dotparts_cap = 0;
+    HIPCHK(hipMalloc((void **)&ctx->dotparts, (size_t)ABFT_MAX_RHS * mat->csr.nblk * sizeof(double)));
+    ctx->dotparts_cap = (size_t)ABFT_MAX_RHS * mat->csr.nblk;
+  }
+  {
+    KernelTimer t(ctx, ABFT_K_SPMV);
+    HIPCHK(launch_spmm_dot_csr(mat->mode, k, mat->csr, P->d, W->d, ctx->ring, ctx->dotparts, ctx->stream));
+  }
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_spmm_fold(ctx->dotparts, mat->csr.nblk, k, o, ctx->stream));
+  }
+  return results_from_block_slot(ctx, o.seq, k, out);
+}
+
+// the operands of calc_r_block / calc_px_block (dinv: null for the plain forms): lengths, k, overlaps
+static int check_fused_block(const char *what, int k, std::initializer_list<const abft_hip_vector *> reads,
+                             std::initializer_list<const abft_hip_vector *> writes, const abft_hip_vector *dinv,
+                             bool precond) {
+  for (const abft_hip_vector *v : reads)
+    if (!v) return set_err(ABFT_ERR_INVALID, "%s: null vector", what);
+  for (const abft_hip_vector *v : writes)
+    if (!v) return set_err(ABFT_ERR_INVALID, "%s: null vector", what);
+  if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "%s: k = %d outside [1, %d]", what, k, ABFT_MAX_RHS);
+  if (precond) {
+    if (int rc = check_precond_block(what, k, reads, writes, dinv)) return rc;
+  } else {
+    const int N = (*writes.begin())->n / k;
+    if (int rc = check_block(what, k, N, reads)) return rc;
+    if (int rc = check_block(what, k, N, writes)) return rc;
+  }
+  if ((*writes.begin())->n == 0) return ABFT_OK;
+  for (const abft_hip_vector *v : writes) {
+    for (const abft_hip_vector *u : reads)
+      if (!disjoint(v, u)) return set_err(ABFT_ERR_INVALID, "%s: a vector the call writes overlaps one it reads", what);
+    for (const abft_hip_vector *u : writes)
+      if (u != v && !disjoint(v, u))
+        return set_err(ABFT_ERR_INVALID, "%s: the vectors the call writes overlap each other", what);
+  }
+  return ABFT_OK;
+}
+
+static int calc_r_block_common(abft_hip_ctx *ctx, const char *what, abft_hip_vector *R, const abft_hip_vector *W,
+                               const abft_hip_vector *dinv, bool precond, int k, const double *alpha, uint32_t active,
+                               double *out) {
+  if (int rc = bind_block(ctx)) return rc;
+  if (!alpha || !out) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
+  if (int rc = check_fused_block(what, k, {W}, {R}, dinv, precond)) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  const int N = R->n / k;
+  BlockScalars a{};
+  for (int j = 0; j < k; j++) a.v[j] = alpha[j];
+  if (precond) {
+    const ReduceOutW o = reduce_out_w(ctx);
+    {
+      KernelTimer t(ctx, ABFT_K_CALC_XR);
+      HIPCHK(launch_calc_r_precond_block(R->d, W->d, dinv->d, N, k, a, active, o, ctx->stream));
+    }
+    return results_from_wide_slot(ctx, o.seq, 2 * k, out);
+  }
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_r_block(R->d, W->d, N, k, a, active, o, ctx->stream));
+  }
+  return results_from_block_slot(ctx, o.seq, k, out);
+}
+
+static int calc_px_block_common(abft_hip_ctx *ctx, const char *what, abft_hip_vector *X, abft_hip_vector *P,
+                                const abft_hip_vector *R, const abft_hip_vector *dinv, bool precond, int k,
+                                const double *alpha, const double *beta, uint32_t active) {
+  if (int rc = bind_block(ctx)) return rc;
+  if (!alpha || !beta) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
+  if (int rc = check_fused_block(what, k, {R}, {X, P}, dinv, precond)) return rc;
+  BlockScalars a{}, b{};
+  for (int j = 0; j < k; j++) { a.v[j] = alpha[j]; b.v[j] = beta[j]; }
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_px_block(X->d, P->d, R->d, precond ? dinv->d : nullptr, X->n / k, k, a, b, active, ctx->stream));
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_calc_r_block(abft_hip_ctx *ctx, abft_hip_vector *R, const abft_hip_vector *W, int k,
+                                     const double *alpha, uint32_t active, double *rr_out) {
+  return calc_r_block_common(ctx, "calc_r_block", R, W, nullptr, false, k, alpha, active, rr_out);
+}
+
+extern "C" int abft_hip_calc_px_block(abft_hip_ctx *ctx, abft_hip_vector *X, abft_hip_vector *P,
+                                      const abft_hip_vector *R, int k, const double *alpha, const double *beta,
+                                      uint32_t active) {
+  return calc_px_block_common(ctx, "calc_px_block", X, P, R, nullptr, false, k, alpha, beta, active);
+}
+
+extern "C" int abft_hip_calc_r_precond_block(abft_hip_ctx *ctx, abft_hip_vector *R, const abft_hip_vector *W,
+                                             const abft_hip_vector *dinv, int k, const double *alpha, uint32_t active,
+                                             double *out) {
+  return calc_r_block_common(ctx, "calc_r_precond_block", R, W, dinv, true, k, alpha, active, out);
+}
+
+extern "C" int abft_hip_calc_px_precond_block(abft_hip_ctx *ctx, abft_hip_vector *X, abft_hip_vector *P,
+                                              const abft_hip_vector *R, const abft_hip_vector *dinv, int k,
+                                              const double *alpha, const double *beta, uint32_t active) {
+  return calc_px_block_common(ctx, "calc_px_precond_block", X, P, R, dinv, true, k, alpha, beta, active);
 }
 
 extern "C" int abft_hip_matrix_panels(abft_hip_matrix *mat, int *npanels, int *width) {

@@ -438,6 +438,17 @@ hipError_t launch_calc_xr_block(double *x, double *r, const double *p, const dou
                                 const BlockScalars &alpha, uint32_t active, const ReduceOutK &out, hipStream_t s);
 hipError_t launch_calc_p_block(double *p, const double *r, int n, int k, const BlockScalars &beta, uint32_t active,
                                hipStream_t s);
+// as launch_spmm_csr, k in [1, 8], on a square matrix; and column j's product x[:, j] . y[:, j] as A.nblk
+// partials at dotp + j * A.nblk (plain stores), which launch_spmm_fold sums and publishes in the K-wide slot
+hipError_t launch_spmm_dot_csr(int mode, int k, const CsrDev &A, const double *x, double *y, EventRing ev,
+                               double *dotp, hipStream_t s);
+hipError_t launch_spmm_fold(const double *parts, uint32_t nblk, int k, const ReduceOutK &out, hipStream_t s);
+// r -= alpha w alone (the r half of launch_calc_xr_block, its sums)
+hipError_t launch_calc_r_block(double *r, const double *w, int n, int k, const BlockScalars &alpha, uint32_t active,
+                               const ReduceOutK &out, hipStream_t s);
+// x += alpha p; p = r + beta p, or with dinv p = dinv * r + beta p
+hipError_t launch_calc_px_block(double *x, double *p, const double *r, const double *dinv, int n, int k,
+                                const BlockScalars &alpha, const BlockScalars &beta, uint32_t active, hipStream_t s);
 // residual checks (abft_hip_residual_*): 2k sums of a block check come back in one wide slot
 struct HostSlotW {
   double value[2 * ABFT_MAX_RHS];
@@ -489,6 +500,9 @@ hipError_t launch_calc_xr_precond_block(double *x, double *r, const double *p, c
                                         hipStream_t s);
 hipError_t launch_calc_p_precond_block(double *p, const double *r, const double *dinv, int n, int k,
                                        const BlockScalars &beta, uint32_t active, hipStream_t s);
+hipError_t launch_calc_r_precond_block(double *r, const double *w, const double *dinv, int n, int k,
+                                       const BlockScalars &alpha, uint32_t active, const ReduceOutW &out,
+                                       hipStream_t s);
 // dinv[i] = 1 / (sum of row i's diagonal elements) over the stored arrays of the streaming CSR / grouped COO
 // layout; *bad (device) counts the rows left at 1.0
 hipError_t launch_diag_csr(const CsrDev &A, uint32_t colmask, double *dinv, uint32_t *bad, hipStream_t s);

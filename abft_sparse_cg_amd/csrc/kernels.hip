@@ -1227,13 +1227,35 @@ __device__ __forceinline__ void spmm_store_row(double *__restrict__ y, uint32_t 
   }
 }
 
+// this thread's share of the K column products: dsum[j] += x[row, j] * y[row, j], y's row in registers
+// (separate multiply and add; the row of x by the gathers' 16-byte loads)
+template <int K>
+__device__ __forceinline__ void spmm_dot_row(const double *__restrict__ x, uint32_t row, uint32_t n_in,
+                                             const double *acc, double *dsum) {
+  double xr[K];
+  spmm_gather<K>(x, row, n_in, xr);
+#pragma unroll
+  for (int j = 0; j < K; j++) dsum[j] += xr[j] * acc[j];
+}
+
 // The block form of spmv_csr_kernel, whole matrix (reference lines as there).
-template <int MODE, int EPT, int K>
+// DOT (abft_hip_spmm_dot): a square matrix; the thread that stores y[row, 0..K)
+// also adds x[row, j] * y[row, j] to its K running products -- a row of a long-row block once, when
+// thread 0's carried sums are complete.  The workgroup leaves K partials (block_sum's shape per column),
+// column j's at dotp[j * A.nblk + tile], with plain stores and exits, as fused_dot_finish does: no ticket
+// here.  spmm_fold_kernel, launched behind, folds them in a fixed order.
+template <int MODE, int EPT, int K, bool DOT = false>
 __global__ __launch_bounds__(ABFT_BLOCK) void spmm_csr_kernel(CsrDev A, const double *__restrict__ x,
-                                                              double *__restrict__ y, EventRing ev) {
+                                                              double *__restrict__ y, EventRing ev,
+                                                              double *__restrict__ dotp) {
   constexpr uint32_t TILE = ABFT_BLOCK * EPT;
   __shared__ __attribute__((aligned(16))) double s_val[TILE];
   __shared__ __attribute__((aligned(16))) uint32_t s_col[TILE];
+  double dsum[K];
+  if (DOT) {
+#pragma unroll
+    for (int j = 0; j < K; j++) dsum[j] = 0.0;
+  }
   const uint32_t t = xcd_tile(blockIdx.x, A.nblk);
   const uint4 desc = A.blk[t];
   const bool uniform = ABFT_CFG_UNIFORM_ROWS && MODE != MODE_CONSTRAINTS && (desc.y >> 31) != 0u;
@@ -1263,7 +1285,10 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmm_csr_kernel(CsrDev A, const do
       double acc[K];
 #pragma unroll
       for (int j = 0; j < K; j++) acc[j] = 0.0;
-      if (spmm_row_sum<MODE, K>(A, ev, x, base, rs, re, re, s_val, s_col, acc, row)) spmm_store_row<K>(y, row, acc);
+      if (spmm_row_sum<MODE, K>(A, ev, x, base, rs, re, re, s_val, s_col, acc, row)) {
+        spmm_store_row<K>(y, row, acc);
+        if (DOT) spmm_dot_row<K>(x, row, A.n_in, acc, dsum);
+      }
     }
   } else {
     // long row (or inconsistent pointers): rows of this block one at a time, tile by tile, the K
@@ -1288,40 +1313,67 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmm_csr_kernel(CsrDev A, const do
         if (threadIdx.x == 0 && ok) ok = spmm_row_sum<MODE, K>(A, ev, x, b, lo, hi, re, s_val, s_col, acc, row);
         lo = hi;
       }
-      if (threadIdx.x == 0 && ok) spmm_store_row<K>(y, row, acc);
+      if (threadIdx.x == 0 && ok) {
+        spmm_store_row<K>(y, row, acc);
+        if (DOT) spmm_dot_row<K>(x, row, A.n_in, acc, dsum);
+      }
+    }
+  }
+  if (DOT) {
+    __shared__ double s_w[4 * K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const double bsum = block_sum(dsum[j], s_w + 4 * j);
+      if (threadIdx.x == 0) dotp[(size_t)j * A.nblk + t] = bsum;
     }
   }
 }
 
-template <int MODE>
+template <int MODE, bool DOT>
 static hipError_t launch_spmm_csr_mode(int k, const CsrDev &A, const double *x, double *y, EventRing ev,
-                                       hipStream_t s) {
+                                       double *dotp, hipStream_t s) {
   const dim3 g(A.nblk), b(ABFT_BLOCK);
+#define ABFT_OP(K) hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, K, DOT>), g, b, 0, s, A, x, y, ev, dotp)
   switch (k) {
-    case 2: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 2>), g, b, 0, s, A, x, y, ev); break;
-    case 3: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 3>), g, b, 0, s, A, x, y, ev); break;
-    case 4: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 4>), g, b, 0, s, A, x, y, ev); break;
-    case 5: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 5>), g, b, 0, s, A, x, y, ev); break;
-    case 6: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 6>), g, b, 0, s, A, x, y, ev); break;
-    case 7: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 7>), g, b, 0, s, A, x, y, ev); break;
-    case 8: hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, 8>), g, b, 0, s, A, x, y, ev); break;
+    case 1:  // without DOT, k = 1 is launch_spmv_csr
+      if constexpr (DOT) { ABFT_OP(1); break; }
+      return hipErrorInvalidValue;
+    case 2: ABFT_OP(2); break;
+    case 3: ABFT_OP(3); break;
+    case 4: ABFT_OP(4); break;
+    case 5: ABFT_OP(5); break;
+    case 6: ABFT_OP(6); break;
+    case 7: ABFT_OP(7); break;
+    case 8: ABFT_OP(8); break;
     default: return hipErrorInvalidValue;
   }
+#undef ABFT_OP
   return hipGetLastError();
+}
+
+template <bool DOT>
+static hipError_t launch_spmm_csr_any(int mode, int k, const CsrDev &A, const double *x, double *y, EventRing ev,
+                                      double *dotp, hipStream_t s) {
+  if (A.nblk == 0) return hipSuccess;
+  switch (mode) {
+    case MODE_NONE: return launch_spmm_csr_mode<MODE_NONE, DOT>(k, A, x, y, ev, dotp, s);
+    case MODE_CONSTRAINTS: return launch_spmm_csr_mode<MODE_CONSTRAINTS, DOT>(k, A, x, y, ev, dotp, s);
+    case MODE_SED: return launch_spmm_csr_mode<MODE_SED, DOT>(k, A, x, y, ev, dotp, s);
+    case MODE_SEC7: return launch_spmm_csr_mode<MODE_SEC7, DOT>(k, A, x, y, ev, dotp, s);
+    case MODE_SEC8: return launch_spmm_csr_mode<MODE_SEC8, DOT>(k, A, x, y, ev, dotp, s);
+    case MODE_SECDED: return launch_spmm_csr_mode<MODE_SECDED, DOT>(k, A, x, y, ev, dotp, s);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 hipError_t launch_spmm_csr(int mode, int k, const CsrDev &A, const double *x, double *y, EventRing ev,
                            hipStream_t s) {
-  if (A.nblk == 0) return hipSuccess;
-  switch (mode) {
-    case MODE_NONE: return launch_spmm_csr_mode<MODE_NONE>(k, A, x, y, ev, s);
-    case MODE_CONSTRAINTS: return launch_spmm_csr_mode<MODE_CONSTRAINTS>(k, A, x, y, ev, s);
-    case MODE_SED: return launch_spmm_csr_mode<MODE_SED>(k, A, x, y, ev, s);
-    case MODE_SEC7: return launch_spmm_csr_mode<MODE_SEC7>(k, A, x, y, ev, s);
-    case MODE_SEC8: return launch_spmm_csr_mode<MODE_SEC8>(k, A, x, y, ev, s);
-    case MODE_SECDED: return launch_spmm_csr_mode<MODE_SECDED>(k, A, x, y, ev, s);
-    default: return hipErrorInvalidValue;
-  }
+  return launch_spmm_csr_any<false>(mode, k, A, x, y, ev, nullptr, s);
+}
+
+hipError_t launch_spmm_dot_csr(int mode, int k, const CsrDev &A, const double *x, double *y, EventRing ev,
+                               double *dotp, hipStream_t s) {
+  return launch_spmm_csr_any<true>(mode, k, A, x, y, ev, dotp, s);
 }
 
 // ----------------------------------------------------------------- COO SpMV --
@@ -4299,6 +4351,150 @@ hipError_t launch_calc_p_precond_block(double *p, const double *r, const double 
   const int nb = reduce_blocks(n);
 #define ABFT_OP(K) \
   hipLaunchKernelGGL(calc_p_precond_block_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, dinv, beta, active, n)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+// ---- the fused block iteration (abft_hip_spmm_dot, abft_hip_calc_r_block, abft_hip_calc_px_block) ----
+// Fold of the K * nblk partials spmm_csr_kernel<.., DOT> left (column j's at parts + j * n): fold_partials_kernel's
+// shape per column -- every workgroup adds a contiguous chunk in a fixed order -- and the chunk sums meet through
+// reduce_finish_k, which publishes the K totals in the K-wide pinned slot.
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void spmm_fold_kernel(const double *__restrict__ parts, uint32_t n,
+                                                               uint32_t chunk, ReduceOutK out) {
+  __shared__ double s_w[8 * K];
+  const uint32_t lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
+  double acc[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    const double *pj = parts + (size_t)j * n;
+    double a = 0.0;
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += 4u * ABFT_BLOCK) {
+      double v[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const uint32_t q = i + (uint32_t)u * ABFT_BLOCK;
+        v[u] = q < hi ? pj[q] : 0.0;
+      }
+      a += (v[0] + v[1]) + (v[2] + v[3]);
+    }
+    acc[j] = a;
+  }
+  reduce_finish_k<K>(acc, out, s_w);
+}
+
+hipError_t launch_spmm_fold(const double *parts, uint32_t nblk, int k, const ReduceOutK &out, hipStream_t s) {
+  uint32_t nb = (nblk + 2047u) / 2048u;
+  if (nb < 1u) nb = 1u;
+  if (nb > 64u) nb = 64u;
+  const uint32_t chunk = (nblk + nb - 1u) / nb;
+#define ABFT_OP(K) hipLaunchKernelGGL(spmm_fold_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, parts, nblk, chunk, out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+// The r half of calc_xr_block_kernel / calc_xr_precond_block_kernel alone: the same grid, walk, operations
+// and reduction, so with the same alpha and mask R and the sums are theirs bit for bit.  Reads r, w (dinv),
+// writes r.
+template <bool PRECOND> struct BlockSumsOut { typedef ReduceOutK type; };
+template <> struct BlockSumsOut<true> { typedef ReduceOutW type; };
+
+template <int K, bool PRECOND>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_kernel(double *__restrict__ r, const double *__restrict__ w,
+                                                                  const double *__restrict__ dinv, BlockScalars alpha,
+                                                                  uint32_t active, int n,
+                                                                  typename BlockSumsOut<PRECOND>::type out) {
+  constexpr int S = PRECOND ? 2 * K : K;
+  __shared__ double s_w[8 * S];
+  double acc[S];
+#pragma unroll
+  for (int j = 0; j < S; j++) acc[j] = 0.0;
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double rv[K], wv[K];
+    const double d = PRECOND ? dinv[i] : 0.0;
+    block_load<K>(r + i * K, rv);
+    block_load<K>(w + i * K, wv);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const double rs = rv[j] - alpha.v[j] * wv[j];  // calc_xr_block_kernel's two roundings
+      rv[j] = ((active >> j) & 1u) ? rs : rv[j];
+      if (PRECOND) {
+        const double z = d * rv[j];
+        acc[2 * j] += rv[j] * z;
+        acc[2 * j + 1] += rv[j] * rv[j];
+      } else {
+        acc[j] += rv[j] * rv[j];
+      }
+    }
+    block_store<K>(r + i * K, rv);
+  }
+  reduce_finish_k<S>(acc, out, s_w);
+}
+
+// x += alpha p and p = r + beta p (PRECOND: p = dinv * r + beta p) in one pass, p read once: the x half of
+// calc_xr_block_kernel and calc_p_block_kernel (or their precond forms), the same operands and roundings.
+template <int K, bool PRECOND>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_kernel(double *__restrict__ x, double *__restrict__ p,
+                                                                   const double *__restrict__ r,
+                                                                   const double *__restrict__ dinv, BlockScalars alpha,
+                                                                   BlockScalars beta, uint32_t active, int n) {
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double xv[K], pv[K], rv[K];
+    const double d = PRECOND ? dinv[i] : 0.0;
+    block_load<K>(x + i * K, xv);
+    block_load<K>(p + i * K, pv);
+    block_load<K>(r + i * K, rv);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const bool on = (active >> j) & 1u;
+      const double xs = xv[j] + alpha.v[j] * pv[j];
+      const double z = PRECOND ? d * rv[j] : rv[j];
+      const double ps = z + beta.v[j] * pv[j];
+      xv[j] = on ? xs : xv[j];
+      pv[j] = on ? ps : pv[j];
+    }
+    block_store<K>(x + i * K, xv);
+    block_store<K>(p + i * K, pv);
+  }
+}
+
+hipError_t launch_calc_r_block(double *r, const double *w, int n, int k, const BlockScalars &alpha, uint32_t active,
+                               const ReduceOutK &out, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K)                                                                                               \
+  hipLaunchKernelGGL((calc_r_block_kernel<K, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, (const double *)nullptr, \
+                     alpha, active, n, out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_r_precond_block(double *r, const double *w, const double *dinv, int n, int k,
+                                       const BlockScalars &alpha, uint32_t active, const ReduceOutW &out,
+                                       hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K) \
+  hipLaunchKernelGGL((calc_r_block_kernel<K, true>), dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, dinv, alpha, active, n, out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_px_block(double *x, double *p, const double *r, const double *dinv, int n, int k,
+                                const BlockScalars &alpha, const BlockScalars &beta, uint32_t active, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K)                                                                                                  \
+  if (dinv)                                                                                                         \
+    hipLaunchKernelGGL((calc_px_block_kernel<K, true>), dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, dinv, alpha, beta, \
+                       active, n);                                                                                  \
+  else                                                                                                              \
+    hipLaunchKernelGGL((calc_px_block_kernel<K, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, dinv, alpha, beta, \
+                       active, n)
   ABFT_BLOCK_K_DISPATCH(ABFT_OP)
 #undef ABFT_OP
   return hipGetLastError();

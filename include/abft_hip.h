@@ -389,6 +389,38 @@ int abft_hip_calc_xr_precond_block(abft_hip_ctx *ctx, abft_hip_vector *X, abft_h
 int abft_hip_calc_p_precond_block(abft_hip_ctx *ctx, abft_hip_vector *P, const abft_hip_vector *R,
                                   const abft_hip_vector *dinv, int k, const double *beta, uint32_t active);
 
+/* ---- the fused block iteration ------------------------------------------
+ * The block CG loop in three calls instead of four, 64 N k bytes of vectors behind the SpMM
+ * instead of 88 N k.  Nothing is carried between calls: every sum comes back through the call
+ * that forms it.  Each entry starts like the other block calls, checks every length, k and
+ * overlap before anything is queued, and leaves every operand untouched when it refuses. */
+
+/* W = A P as abft_hip_spmm (k in [1, 8]; the same bits, the same events), and
+ * out[j] = P[:, j] . W[:, j], formed from W's rows while they are in registers: per row block
+ * a tree sum of one shape, the row blocks' partials folded in a fixed order (so two calls give
+ * the same bits, and a column scaled by a power of two gives the scaled sum).  Refused: what
+ * abft_hip_spmm refuses, and a matrix that is not square. */
+int abft_hip_spmm_dot(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *P,
+                      abft_hip_vector *W, int k, double *out);
+/* the r half of abft_hip_calc_xr_block: r[:, j] -= alpha[j] w[:, j] for the active columns;
+ * rr_out[j] = r[:, j] . r[:, j] for every column.  R and the sums are, bit for bit, those of
+ * abft_hip_calc_xr_block with the same alpha and mask. */
+int abft_hip_calc_r_block(abft_hip_ctx *ctx, abft_hip_vector *R, const abft_hip_vector *W, int k,
+                          const double *alpha, uint32_t active, double *rr_out);
+/* for the active columns x[:, j] += alpha[j] p[:, j], then p[:, j] = r[:, j] + beta[j] p[:, j],
+ * p read once: the bits the x half of abft_hip_calc_xr_block and abft_hip_calc_p_block give */
+int abft_hip_calc_px_block(abft_hip_ctx *ctx, abft_hip_vector *X, abft_hip_vector *P,
+                           const abft_hip_vector *R, int k, const double *alpha, const double *beta,
+                           uint32_t active);
+/* the Jacobi forms (one dinv of N entries): out[2j], out[2j + 1] = column j's r.z and r.r, as
+ * abft_hip_calc_xr_precond_block; p[:, j] = dinv * r[:, j] + beta[j] p[:, j] */
+int abft_hip_calc_r_precond_block(abft_hip_ctx *ctx, abft_hip_vector *R, const abft_hip_vector *W,
+                                  const abft_hip_vector *dinv, int k, const double *alpha, uint32_t active,
+                                  double *out);
+int abft_hip_calc_px_precond_block(abft_hip_ctx *ctx, abft_hip_vector *X, abft_hip_vector *P,
+                                   const abft_hip_vector *R, const abft_hip_vector *dinv, int k,
+                                   const double *alpha, const double *beta, uint32_t active);
+
 /* Shard-local forms for the row-partitioned solver: same kernels, but the
  * result stays on the device so a collective can sum it across ranks before
  * the host reads it.  `dev_result` is a device pointer to TWO doubles:
