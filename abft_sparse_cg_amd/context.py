@@ -534,6 +534,14 @@ class HIPContext:
         check(self.L.abft_hip_stream_probe(self.h, nbytes, reps, C.byref(c), C.byref(r)))
         return c.value, r.value
 
+    def tail_stats(self):
+        """what the last abft_hip_cg_iteration_dev ran behind its SpMV -> (path, grid, want, counts[4]): path 0 the three
+        kernels, 1 / 2 / 3 the one launch as cg_tail_kernel<1, false> / <2, false> / <2, true> (include/abft_hip.h)"""
+        path, grid, want = C.c_int(0), C.c_int(0), C.c_int(0)
+        counts = (C.c_long * 4)()
+        check(self.L.abft_hip_tail_stats(self.h, C.byref(path), C.byref(grid), C.byref(want), counts))
+        return path.value, grid.value, want.value, list(counts)
+
     @property
     def stream(self):
         return self.L.abft_hip_get_stream(self.h)

@@ -62,6 +62,9 @@ struct abft_hip_ctx {
   bool tail_enabled = true;       // ABFT_HIP_TAIL=0: the iteration's tail as its three kernels
   int tail_cap[3][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}};  // [q: 1, 2, 4 blocks per workgroup][<1>, <2>, <2, fast>]: resident workgroups (asked once)
   int sharers = 1;                // processes that run this library on this device at the same time (abft_hip_set_sharers)
+  // what the last abft_hip_cg_iteration_dev took (abft_hip_tail_stats; host counters only): 0 the three kernels,
+  // 1 cg_tail_kernel<1, false>, 2 <2, false>, 3 <2, true>; the grid launched and the uncapped one; calls per path
+  struct { int path = 0; uint32_t grid = 0, want = 0; long counts[4] = {0, 0, 0, 0}; } tail_stats;
   uint32_t seq = 0;            // last sequence number handed to a reduction
   bool spin_wait = true;       // wait for scalars by polling the pinned slot
   // pinned, device-visible: a ring of result slots, slot seq % ABFT_HOST_SLOTS for the reduction numbered seq (two
@@ -1966,7 +1969,7 @@ static int calc_xr_launch(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector
                      disjoint(x, p) && disjoint(x, w) && disjoint(r, p);
   KernelTimer t(ctx, ABFT_K_CALC_XR);
   if (defer) {
-    HIPCHK(launch_calc_r(r->d, w->d, alpha, num, den, num ? ctx->alpha_dev : nullptr, x->n, o, ctx->stream));
+    HIPCHK(launch_calc_r(r->d, w->d, alpha, num, den, num ? ctx->alpha_dev : nullptr, x->n, o, ctx->stream, nullptr, x->d, p->d));
     ctx->defer.active = true;
     ctx->defer.on_dev = num != nullptr;
     ctx->defer.x = x->d; ctx->defer.p = p->d; ctx->defer.n = x->n; ctx->defer.alpha = alpha;
@@ -2638,7 +2641,7 @@ static int spec_launch(abft_hip_ctx *ctx, const abft_hip_vector *vec, const abft
   const ReduceOut o = reduce_out(ctx, rr_new, true);  // {r.r, events} to the host ring AND to the device
   {
     KernelTimer t(ctx, ABFT_K_CALC_XR);
-    HIPCHK(launch_calc_r(S.r->d, S.w->d, 0.0, rr, pw, ctx->alpha_dev, n, o, ctx->stream, S.shadow[0]));
+    HIPCHK(launch_calc_r(S.r->d, S.w->d, 0.0, rr, pw, ctx->alpha_dev, n, o, ctx->stream, S.shadow[0], S.x->d, S.p->d));
   }
   // (the x / p half follows when calc_xr has been taken over: from then on x += alpha p is DUE, so x is updated in
   // place and only p -- whose beta the caller has yet to name -- goes to a shadow.  Both halves out of place from
@@ -3562,6 +3565,16 @@ extern "C" int abft_hip_speculation_stats(abft_hip_ctx *ctx, long *taken, long *
   return ABFT_OK;
 }
 
+extern "C" int abft_hip_tail_stats(abft_hip_ctx *ctx, int *path, int *grid, int *want, long counts[4]) {
+  if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");
+  if (path) *path = ctx->tail_stats.path;
+  if (grid) *grid = (int)ctx->tail_stats.grid;
+  if (want) *want = (int)ctx->tail_stats.want;
+  if (counts)
+    for (int k = 0; k < 4; k++) counts[k] = ctx->tail_stats.counts[k];
+  return ABFT_OK;
+}
+
 extern "C" int abft_hip_set_sharers(abft_hip_ctx *ctx, int processes) {
   if (!ctx || processes < 1) return set_err(ABFT_ERR_INVALID, "set_sharers: bad argument");
   ctx->sharers = processes;
@@ -3600,6 +3613,7 @@ extern "C" int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat
   const uint32_t nbv = (uint32_t)reduce_blocks(n);
   bool fast = false;
   int q = 4;
+  uint32_t want_wg = 0;
   if (merged) {
     // workgroups of q virtual blocks.  1024 threads (q = 4) at every length: smaller workgroups put one on more CUs for
     // the mid-size vectors, but every grid-wide point then has that many more arrivals on one line of counters and
@@ -3621,7 +3635,12 @@ extern "C" int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat
     fast = vec2 && !hold.fix.on && (long long)n <= (long long)nbv * 2048 && (int)want <= cap_of(2);  // (the COO fix-up rewrites entries of w: no early loads)
     grid = fast ? want : std::min<uint32_t>(want, (uint32_t)std::max(cap_of(vec2 ? 1 : 0), 0));
     merged = grid > 0;
+    want_wg = want;
   }
+  ctx->tail_stats.path = !merged ? 0 : fast ? 3 : vec2 ? 2 : 1;
+  ctx->tail_stats.grid = merged ? grid : 0u;
+  ctx->tail_stats.want = merged ? want_wg : 0u;
+  ctx->tail_stats.counts[ctx->tail_stats.path]++;
   if (!merged) {
     if (hold.held) {
       KernelTimer t(ctx, ABFT_K_DOT);

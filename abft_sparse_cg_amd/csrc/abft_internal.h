@@ -406,7 +406,8 @@ hipError_t launch_calc_xr(double *x, double *r, const double *p, const double *w
 hipError_t launch_calc_p(double *p, const double *r, double beta, const double *num, const double *den, int n,
                          hipStream_t s);
 hipError_t launch_calc_r(double *r, const double *w, double alpha, const double *num, const double *den,
-                         double *alpha_out, int n, const ReduceOut &out, hipStream_t s, double *r_out = nullptr);
+                         double *alpha_out, int n, const ReduceOut &out, hipStream_t s, double *r_out = nullptr,
+                         const double *x = nullptr, const double *p = nullptr);
 hipError_t launch_calc_px(double *p, const double *r, double *x, double beta, const double *num, const double *den,
                           double alpha, const double *alpha_ptr, int n, hipStream_t s, double *p_out = nullptr,
                           double *x_out = nullptr);

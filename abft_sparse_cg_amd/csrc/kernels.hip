@@ -3627,11 +3627,15 @@ __global__ __launch_bounds__(ABFT_BLOCK) void axpy_kernel(double *__restrict__ x
   }
 }
 
+// (x, p: the operands of the calc_xr this is the r half of.  The kernel does not touch them, but the order in which r.r
+// is summed follows the walk, and the walk is chosen over all four operands -- as calc_xr_kernel's and cg_tail_kernel's
+// is -- so that the sum has the same bits whichever of the three runs the call)
 hipError_t launch_calc_r(double *r, const double *w, double alpha, const double *num, const double *den,
-                         double *alpha_out, int n, const ReduceOut &out, hipStream_t s, double *r_out) {
+                         double *alpha_out, int n, const ReduceOut &out, hipStream_t s, double *r_out, const double *x,
+                         const double *p) {
   const int nb = reduce_blocks(n);
   if (!r_out) r_out = r;
-  if (aligned16(r, w, r_out))
+  if (aligned16(r, w, r_out) && aligned16(x, p))
     hipLaunchKernelGGL(calc_r_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, alpha, num, den, alpha_out, n, out, r_out);
   else
     hipLaunchKernelGGL(calc_r_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, alpha, num, den, alpha_out, n, out, r_out);

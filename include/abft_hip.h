@@ -529,7 +529,13 @@ int abft_hip_peer_exchange_attach_device(abft_hip_ctx *ctx, void *const *regions
  *                       in the gathered vector; 0 on one GPU)
  *   calc_xr_ratio_dev   calc_xr with alpha = *dev_num / *dev_den  (cg.cpp:102)
  *   calc_p_ratio_dev    calc_p  with beta  = *dev_num / *dev_den  (cg.cpp:109)
- * All three are asynchronous; every pointer is device memory. */
+ * All three are asynchronous; every pointer is device memory.
+ * calc_xr_ratio_dev's r.r (like calc_xr's, and abft_hip_cg_iteration_dev's) is summed in the order of
+ * the call's walk: by pairs of entries when x, r, p and w are ALL 16-byte aligned, entry by entry when
+ * any of them is not (a view at an odd offset) -- whichever kernels run the call.  It therefore equals
+ * abft_hip_dot(r, r) on the resulting r bit for bit when r's alignment matches the call's (all four
+ * aligned, or r itself unaligned); with r aligned beside an unaligned x, p or w, abft_hip_dot(r, r)
+ * adds the same products in the other order. */
 int abft_hip_spmv_dot_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
                           abft_hip_vector *result, int vec_offset, double *dev_result);
 int abft_hip_calc_xr_ratio_dev(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r,
@@ -597,10 +603,19 @@ int abft_hip_set_sharers(abft_hip_ctx *ctx, int processes);
  * two board all-reduces -- is ONE launch of co-resident workgroups where that applies (vectors of at most
  * 2^22 entries -- beyond that the three kernels are faster --, x private to the library and no operand
  * aliasing another; ABFT_HIP_TAIL=0 keeps the three kernels).  p is the
- * caller's view of vec's slot (the vector the SpMV read).  Enqueue-only: capturable. */
+ * caller's view of vec's slot (the vector the SpMV read).  Enqueue-only: capturable.
+ * The order in which r.r is summed: see abft_hip_calc_xr_ratio_dev above.
+ * abft_hip_tail_stats tells which form a call took. */
 int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec, int vec_offset,
                               int part, abft_hip_vector *x, abft_hip_vector *r, abft_hip_vector *p,
                               abft_hip_vector *w, const double *dev_rr, double *dev_pw, double *dev_rr_new);
+/* What the last abft_hip_cg_iteration_dev on the context ran behind its SpMV (tests; host counters, nothing
+ * on the device): *path = 0 the three kernels, 1 the one launch in its form for operands that are not all
+ * 16-byte aligned (cg_tail_kernel<1, false>), 2 the aligned form that walks the vector in rounds (<2, false>),
+ * 3 the register-resident form (<2, true>); *grid = the workgroups launched and *want = the number the
+ * vector's length asks for before the resident cap (both 0 on path 0); counts[k] = calls that took path k
+ * since the context was created.  Any pointer may be null. */
+int abft_hip_tail_stats(abft_hip_ctx *ctx, int *path, int *grid, int *want, long counts[4]);
 
 /* ---- graph replay ------------------------------------------------------ */
 

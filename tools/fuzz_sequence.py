@@ -9,7 +9,11 @@ bit-identical to the model whenever they are read, scalars within the reductions
 
 ABFT_FUZZ_SEQ_INJECT=1 adds an operation (its own meaning of the seeds): in mode none, `inject` flips
 bits of an element in the library's matrix and in the oracle's -- in a packed block that re-plans the
-block -- and everything after it must hold as before.  The summary then counts the injects made."""
+block -- and everything after it must hold as before.  The summary then counts the injects made.
+
+The summary also says which form every `devstep` took behind its SpMV (abft_hip_tail_stats: host counters, nothing
+drawn from the seeds), and a campaign whose devsteps never reached the one launch fails (unless ABFT_HIP_TAIL=0
+asked for the three kernels)."""
 import os
 import sys
 import time
@@ -33,6 +37,7 @@ def bits_equal(a, b):
 
 
 INJECTS = [0]
+TAIL_PATHS = [0, 0, 0, 0]  # devsteps that ran the three kernels, cg_tail_kernel<1, false>, <2, false>, <2, true>
 
 
 def one_case(seed):
@@ -135,6 +140,7 @@ def one_case(seed):
                 base = sc.device_ptr
                 capi.check(ctx.L.abft_hip_cg_iteration_dev(ctx.h, A.h, dev[p].h, 0, capi.PART_ALL, dev[x].h, dev[r].h, dev[p].h,
                                                            dev[w].h, base, base + 32, base + 16))
+                TAIL_PATHS[ctx.tail_stats()[0]] += 1
                 got = ctx.download(sc)
                 model[w] = o.spmv(model[p])
                 want_pw = float(np.dot(model[p], model[w]))
@@ -209,6 +215,10 @@ def main():
             print("... %d sequences, %d failures, %.0f s" % (done, bad, time.time() - t0), flush=True)
     if os.environ.get("ABFT_FUZZ_SEQ_INJECT") == "1":
         print("injects: %d" % INJECTS[0], flush=True)
+    print("reached: devstep three_kernels=%d tail_1=%d tail_2=%d tail_2_fast=%d" % tuple(TAIL_PATHS), flush=True)
+    if sum(TAIL_PATHS) and not sum(TAIL_PATHS[1:]) and os.environ.get("ABFT_HIP_TAIL") != "0":
+        bad += 1
+        print("FAIL no devstep of %d reached the one-launch tail" % sum(TAIL_PATHS), flush=True)
     print("fuzz_sequence: %d sequences, %d failures" % (done, bad), flush=True)
     return 1 if bad else 0
 
