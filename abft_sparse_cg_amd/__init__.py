@@ -11,4 +11,5 @@ from .capi import MODES, AbftError  # noqa: F401
 
 capi.load()
 
-from .context import FatalEvent, HIPContext, ResidualCheckFailed, cg_solve, cg_solve_block, vecc_strip  # noqa: E402,F401
+from .context import (DEFAULT_STRIDE, FatalEvent, HIPContext, ResidualCheckFailed, cg_solve, cg_solve_block,  # noqa: E402,F401
+                      cg_solve_device, vecc_strip)

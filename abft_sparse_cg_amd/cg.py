@@ -67,6 +67,11 @@ Additional options of this build:
       --vector-ecc      E     Protect the CG vectors: none (default) or secded, a (64, 57)
                               code in each double's low 7 mantissa bits (CSR, one
                               right-hand side, no --precond / --check-every)
+      --device-loop     S     Keep alpha, beta and the stop test on the device and look
+                              at the residuals every S iterations (S >= 1) instead of
+                              twice per iteration: same iterations, residuals and x; the
+                              lines of a batch are printed after it.  Not with --rhs,
+                              --precond, --check-every, --vector-ecc or --flip-vector
 
 """
 
@@ -83,7 +88,7 @@ def parse(argv):
     o = dict(num_blocks=25, max_itrs=1000, conv=0.001, matrix_file=DEFAULT_MTX, synthetic=None, target="cpu",
              mode="none", flips=0, kind="ANY", seed=None, quiet=False, flip_at=None, fmt="csr", list=False,
              rhs=1, check_every=0, check_tol=1e-7, max_rollbacks=3, flip_vector=[], precond="none",
-             vector_ecc="none", block_fused=False)
+             vector_ecc="none", block_fused=False, device_loop=0)
 
     def num(s, conv):
         try:
@@ -185,6 +190,10 @@ def parse(argv):
                 fail("Invalid vector protection (want none or secded)")
         elif a == "--block-fused":
             o["block_fused"] = True
+        elif a == "--device-loop":
+            o["device_loop"] = num(arg("Invalid --device-loop stride (want a whole number >= 1)"), int)
+            if o["device_loop"] < 1:
+                fail("Invalid --device-loop stride (want a whole number >= 1)")
         elif a in ("--quiet", "-q"):
             o["quiet"] = True
         elif a in ("--help", "-h"):
@@ -195,6 +204,12 @@ def parse(argv):
         i += 1
     if o["block_fused"] and o["rhs"] < 2:
         fail("--block-fused needs --rhs K with K of 2 to 8: it selects the block loop's fused iteration")
+    if o["device_loop"]:
+        for flag, on in (("--rhs", o["rhs"] > 1), ("--precond", o["precond"] != "none"),
+                         ("--check-every", o["check_every"] > 0), ("--vector-ecc", o["vector_ecc"] != "none"),
+                         ("--flip-vector", bool(o["flip_vector"]))):
+            if on:
+                fail("--device-loop cannot be combined with %s" % flag)
     if o["vector_ecc"] == "none":
         if any(f[1] in ("w", "b") for f in o["flip_vector"]):
             fail(FLIP_VECTOR_MSG)  # (known only here: --vector-ecc may follow --flip-vector)
@@ -324,7 +339,7 @@ def load_matrix(o, row0=0, row1=None):
 
 def run_single(o):
     from . import HIPContext, generators
-    from .context import ResidualCheckFailed, cg_solve
+    from .context import ResidualCheckFailed, cg_solve, cg_solve_device
     cols, rows, vals, n, block = load_matrix(o)
     nnz = len(vals)
     ctx = HIPContext(o["mode"], o["fmt"])
@@ -352,12 +367,19 @@ def run_single(o):
             print("iteration %5u :  rr = %12.4f" % (itr, rr))
         apply_vector_flips(ctx, vecs, itr)
 
+    if o["device_loop"]:
+        print("iteration loop: device scalars, stride %d" % o["device_loop"])
     t0 = time.perf_counter()
     try:
-        itr, rr = cg_solve(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
-                           check_every=o["check_every"], check_tol=o["check_tol"], max_rollbacks=o["max_rollbacks"],
-                           on_check=lambda i, gap, ok, back: report_check(checks, "", i, gap, ok, back, bound),
-                           precond=dinv, **({"vector_ecc": True} if ecc else {}))
+        if o["device_loop"]:
+            itr, rr = cg_solve_device(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
+                                      stride=o["device_loop"])
+        else:
+            itr, rr = cg_solve(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
+                               check_every=o["check_every"], check_tol=o["check_tol"],
+                               max_rollbacks=o["max_rollbacks"],
+                               on_check=lambda i, gap, ok, back: report_check(checks, "", i, gap, ok, back, bound),
+                               precond=dinv, **({"vector_ecc": True} if ecc else {}))
     except ResidualCheckFailed as e:
         print("[ABFT] %s" % e)
         ctx.close()

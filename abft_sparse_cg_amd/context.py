@@ -542,6 +542,33 @@ class HIPContext:
         check(self.L.abft_hip_tail_stats(self.h, C.byref(path), C.byref(grid), C.byref(want), counts))
         return path.value, grid.value, want.value, list(counts)
 
+    # ---- the device-scalar loop (include/abft_hip.h): cg_solve_device ----
+    def cg_iteration_until_dev(self, mat, vec, x, r, p, w, scalars, rr_at, pw_at, rr_new_at, threshold, vec_offset=0,
+                               part=capi.PART_ALL):
+        """one guarded CG iteration, enqueue-only (abft_hip_cg_iteration_until_dev): live when scalars[rr_at] >
+        threshold on the device, else frozen.  scalars: a vector of device doubles; rr_at, pw_at, rr_new_at: where the
+        pairs {r.r, events} read, {p.w, events} and {r.r, events} written start in it"""
+        base = scalars.device_ptr
+        check(self.L.abft_hip_cg_iteration_until_dev(self.h, mat.h, vec.h, vec_offset, part, x.h, r.h, p.h, w.h,
+                                                     base + 8 * rr_at, base + 8 * pw_at, base + 8 * rr_new_at,
+                                                     threshold))
+
+    def graph_begin(self):
+        """start capturing the asynchronous calls on the context's stream (include/abft_hip.h, graph replay)"""
+        check(self.L.abft_hip_graph_begin(self.h))
+
+    def graph_end(self):
+        """-> the captured graph (graph_launch, graph_destroy)"""
+        g = C.c_void_p()
+        check(self.L.abft_hip_graph_end(self.h, C.byref(g)))
+        return g
+
+    def graph_launch(self, graph):
+        check(self.L.abft_hip_graph_launch(graph))
+
+    def graph_destroy(self, graph):
+        check(self.L.abft_hip_graph_destroy(graph))
+
     @property
     def stream(self):
         return self.L.abft_hip_get_stream(self.h)
@@ -724,6 +751,87 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
         if check_every and own_ckpt:
             ctx.destroy_vector(x_ckpt)
     return itr, rr
+
+
+# iterations per look at the scalars in cg_solve_device.  Not measured: the smallest stride within 2 % of the best
+# time on the 1 M-row matrix is to replace it (tools/device_loop_bench.py).
+DEFAULT_STRIDE = 16
+
+
+def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
+                    stride=DEFAULT_STRIDE, graph=True):
+    """cg_solve's loop (cg.cpp:87-118) with alpha, beta and the stop test on the device:
+    the host looks at the scalars once per batch of `stride` iterations instead of twice per iteration.
+
+    copy r <- b, copy p <- r and rr0 = dot(r, r) as cg_solve; with max_itrs == 0 or not rr0 > conv_threshold
+    that is all: (0, rr0).  Otherwise batches of m = min(stride, max_itrs - done) guarded iterations
+    (ctx.cg_iteration_until_dev) over a trail of stride + 1 pairs {r.r, events}: iteration k of a batch reads
+    pair k and writes pair k + 1, and is frozen -- x, r, p untouched, the pair handed on -- once its pair is not
+    above conv_threshold.  Every batch starts by copying pair `stride` to pair 0.  A full batch is one graph,
+    captured once and replayed (graph=True); a short last batch, and everything with graph=False, is enqueued
+    call by call.  After a batch the trail is downloaded -- the one synchronisation --, events are drained
+    (FatalEvent is raised there, before any callback of the batch), and the pairs are read in order: iteration
+    `done` was live with result pair k + 1 while pair k is above the threshold.
+
+    on_iteration(itr, rr) is called for every live iteration in order, but AFTER its batch: the vectors it sees
+    are the batch's end state, not that iteration's.  -> (itr, rr) as cg_solve: the count of live iterations and
+    the last live r.r (a frozen tail costs at most stride - 1 SpMVs per solve, plus one batch when the loop
+    stops on a batch's last iteration before max_itrs)."""
+    if int(stride) != stride or stride < 1:
+        raise ValueError("stride must be a whole number >= 1, not %r" % (stride,))
+    stride = int(stride)
+    ctx.copy_vector(r, b)
+    ctx.copy_vector(p, r)
+    rr = ctx.dot(r, r)
+    noted = {}
+    note_threshold(rr, conv_threshold, noted)
+    if max_itrs == 0 or not (rr > conv_threshold):
+        return 0, rr
+    pw_at = 2 * (stride + 1)
+    trail = ctx.create_vector(pw_at + 2)
+    first, last = ctx.view_vector(trail, 0, 2), ctx.view_vector(trail, 2 * stride, 2)
+    start = np.zeros(pw_at + 2)
+    start[2 * stride] = rr  # where the first batch's copy finds it
+    ctx.upload(trail, start)
+
+    def batch(m):
+        ctx.copy_vector(first, last)
+        for k in range(m):
+            ctx.cg_iteration_until_dev(A, p, x, r, p, w, trail, 2 * k, pw_at, 2 * k + 2, conv_threshold)
+
+    done, g = 0, None
+    try:
+        while True:
+            m = min(stride, max_itrs - done)
+            if graph and m == stride:
+                if g is None:
+                    ctx.graph_begin()
+                    try:
+                        batch(m)
+                    finally:
+                        g = ctx.graph_end()
+                ctx.graph_launch(g)
+            else:
+                batch(m)
+            t = ctx.download(trail)  # synchronises, then drains the events
+            stopped = False
+            for k in range(m):
+                if not (t[2 * k] > conv_threshold):
+                    stopped = True
+                    break
+                rr = float(t[2 * k + 2])
+                note_threshold(rr, conv_threshold, noted)
+                if on_iteration is not None:
+                    on_iteration(done, rr)
+                done += 1
+            if stopped or done >= max_itrs:
+                break
+    finally:
+        if g is not None:
+            ctx.graph_destroy(g)
+        for v in (first, last, trail):
+            ctx.destroy_vector(v)
+    return done, rr
 
 
 def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration):

@@ -3675,6 +3675,63 @@ extern "C" int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat
   return ABFT_OK;
 }
 
+// ---- the same iteration behind the stop test of cg.cpp:94, evaluated on the device ----------------
+// Always the three-kernel route (fold, r half, x / p half), the two halves in their guarded forms
+// (kernels.hip, calc_r_until_kernel): cg_tail_kernel's hand-off words must grow by every launch's
+// amounts, and a launch that returned early would break the bases the next one starts from.
+extern "C" int abft_hip_cg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                               int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                               abft_hip_vector *p, abft_hip_vector *w, const double *dev_rr,
+                                               double *dev_pw, double *dev_rr_new, double threshold) {
+  const char *what = "cg_iteration_until";
+  if (int rc = bind(ctx)) return rc;  // a pending x update applied, a speculation voided
+  if (!mat || !vec || !x || !r || !p || !w) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
+  if (!dev_rr || !dev_pw || !dev_rr_new) return set_err(ABFT_ERR_INVALID, "%s: null device scalar", what);
+  if (part != ABFT_PART_ALL && part != ABFT_PART_BOUNDARY)
+    return set_err(ABFT_ERR_INVALID, "%s: part %d (the interior part goes through abft_hip_spmv_dot_part_dev)", what, part);
+  // one rank only: a frozen rank would leave its peers waiting at the board
+  if (ctx->peers.attached)
+    return set_err(ABFT_ERR_INVALID, "%s: a peer board is attached; the guarded iteration runs on one rank", what);
+  auto apart = [](const double *a, const double *b) { return a + 2 <= b || b + 2 <= a; };
+  if (!apart(dev_rr, dev_pw) || !apart(dev_rr, dev_rr_new) || !apart(dev_pw, dev_rr_new))
+    return set_err(ABFT_ERR_INVALID, "%s: the scalar pairs overlap", what);
+  if (int rc = check_same(x, r, what)) return rc;
+  if (int rc = check_same(x, p, what)) return rc;
+  if (int rc = check_same(x, w, what)) return rc;
+  const int n = x->n;
+  const uint32_t n_out = mat->fmt == ABFT_FMT_CSR ? mat->csr.n_out : mat->coo.n_out;
+  if ((uint32_t)n != n_out)
+    return set_err(ABFT_ERR_INVALID, "%s: vectors of %d entries for a matrix of %u rows", what, n, n_out);
+  if (vec_offset < 0 || (uint64_t)vec_offset + n_out > (uint64_t)vec->n)
+    return set_err(ABFT_ERR_INVALID, "%s: window [%d,%llu) outside the input vector of %d", what, vec_offset,
+                   (unsigned long long)vec_offset + n_out, vec->n);
+  if (n > 0) {
+    if (!disjoint(x, r) || !disjoint(x, p) || !disjoint(x, w) || !disjoint(r, p) || !disjoint(r, w) || !disjoint(p, w))
+      return set_err(ABFT_ERR_INVALID, "%s: x, r, p and w overlap", what);
+    if (!disjoint(vec, x) || !disjoint(vec, r) || !disjoint(vec, w))
+      return set_err(ABFT_ERR_INVALID, "%s: the input vector overlaps x, r or w", what);
+    if (!disjoint(vec, p) && p->d != vec->d + vec_offset)  // (the vector the SpMV read, or a vector apart from it)
+      return set_err(ABFT_ERR_INVALID, "%s: p overlaps the input vector without being its window", what);
+  }
+  HeldFold hold;
+  if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold)) return rc;
+  if (hold.held) {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    ReduceOut big{};
+    big.partials = ctx->partials; big.ticket = ctx->ticket; big.dev_out = hold.fuse.dev_out; big.host = hold.fuse.host;
+    big.ev_count = hold.fuse.ev_count; big.seq = hold.fuse.seq; big.peers = hold.fuse.peers;
+    HIPCHK(launch_fuse_finalize(hold.fuse, hold.nparts, big, hold.fix.on ? &hold.fix : nullptr, ctx->stream));
+  }
+  const ReduceOut o = reduce_out(ctx, dev_rr_new, false);
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_r_until(r->d, w->d, dev_rr, dev_pw, threshold, ctx->alpha_dev, n, o, ctx->stream, x->d, p->d));
+  }
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_px_until(p->d, r->d, x->d, dev_rr, dev_rr_new, threshold, ctx->alpha_dev, n, ctx->stream));
+  return ABFT_OK;
+}
+
 // ------------------------------------------------------------- graph replay --
 
 // A captured sequence of asynchronous calls on the context's stream (and of whatever else

@@ -412,6 +412,14 @@ hipError_t launch_calc_px(double *p, const double *r, double *x, double beta, co
                           double alpha, const double *alpha_ptr, int n, hipStream_t s, double *p_out = nullptr,
                           double *x_out = nullptr);
 hipError_t launch_axpy(double *x, const double *p, double alpha, const double *alpha_ptr, int n, hipStream_t s);
+// the two halves of a guarded iteration (abft_hip_cg_iteration_until_dev): live when *rr > threshold -- then what
+// launch_calc_r (alpha = *rr / *pw, left in alpha_out) and launch_calc_px (beta = *rr_new / *rr) do --, else nothing
+// but the new pair out.dev_out = {the bits of *rr, queued events}
+hipError_t launch_calc_r_until(double *r, const double *w, const double *rr, const double *pw, double threshold,
+                               double *alpha_out, int n, const ReduceOut &out, hipStream_t s, const double *x,
+                               const double *p);
+hipError_t launch_calc_px_until(double *p, const double *r, double *x, const double *rr, const double *rr_new,
+                                double threshold, const double *alpha_ptr, int n, hipStream_t s);
 
 // ---- block right-hand sides (abft_hip_spmm and the *_block vector calls; 1 <= K <= 8) ----
 #define ABFT_MAX_RHS 8

@@ -3665,6 +3665,129 @@ hipError_t launch_axpy(double *x, const double *p, double alpha, const double *a
   return hipGetLastError();
 }
 
+// ---- the guarded iteration (abft_hip_cg_iteration_until_dev) ----
+// calc_r_kernel and calc_px_kernel with the stop test of cg.cpp:94 in front: the launch is LIVE when
+// *rr > threshold (false for NaN, as `while (rr > conv)` is) and then walks, computes and reduces exactly as
+// the unguarded kernel does on the same grid -- same bits everywhere.  Otherwise it is FROZEN: every thread
+// returns before it touches a vector, a partial or the ticket, and one thread of the r half writes the new
+// pair {the bits of *rr, queued events}.  Every thread of both launches reads the same word, which neither
+// writes, so the decision is uniform over the grid and the same in both; no workgroup waits for another.
+// (Kernels of their own and not a template flag on the two above: those keep their symbols and their code.)
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_until_kernel(double *r, const double *__restrict__ w,
+                                                                  const double *rr, const double *pw,
+                                                                  double threshold, double *alpha_out, int n,
+                                                                  ReduceOut out) {
+  __shared__ double s_w[4];
+  if (!(*rr > threshold)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      // the bits, whatever they are (a NaN's payload included): moved as an integer
+      *reinterpret_cast<unsigned long long *>(out.dev_out) = *reinterpret_cast<const unsigned long long *>(rr);
+      out.dev_out[1] = (double)__hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return;
+  }
+  const double alpha = *rr / *pw;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;  // for the x half
+  double acc = 0.0;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      double2 rv = *reinterpret_cast<const double2 *>(r + i);
+#if ABFT_CFG_DEAD_NT & 1
+      typedef double v2d __attribute__((ext_vector_type(2)));
+      const v2d wl = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(w + i));
+      const double2 wv = make_double2(wl.x, wl.y);
+#else
+      const double2 wv = *reinterpret_cast<const double2 *>(w + i);
+#endif
+      rv.x -= alpha * wv.x; rv.y -= alpha * wv.y;
+      *reinterpret_cast<double2 *>(r + i) = rv;
+      acc += rv.x * rv.x;
+      acc += rv.y * rv.y;
+    } else {
+      const double rs = r[i] - alpha * w[i];
+      r[i] = rs;
+      acc += rs * rs;
+    }
+  }
+  acc = block_sum(acc, s_w);
+  reduce_finish(acc, out, s_w);
+}
+
+// (rr: the pair the iteration started from -- the guard, and beta's denominator; rr_new: what the r half left)
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_until_kernel(double *p, const double *__restrict__ r, double *x,
+                                                                   const double *rr, const double *rr_new,
+                                                                   double threshold, const double *alpha_ptr, int n) {
+  const double rr0 = *rr;
+  if (!(rr0 > threshold)) return;
+  const double beta = *rr_new / rr0;
+  const double alpha = *alpha_ptr;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+#if ABFT_CFG_X_NT || (ABFT_CFG_DEAD_NT & 6)
+      typedef double v2d __attribute__((ext_vector_type(2)));
+#endif
+#if ABFT_CFG_DEAD_NT & 4
+      const v2d pl = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(p + i));
+      double2 pv = make_double2(pl.x, pl.y);
+#else
+      double2 pv = *reinterpret_cast<const double2 *>(p + i);
+#endif
+#if ABFT_CFG_X_NT
+      const v2d xl = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(x + i));
+      double2 xv = make_double2(xl.x, xl.y);
+#else
+      double2 xv = *reinterpret_cast<const double2 *>(x + i);
+#endif
+#if ABFT_CFG_DEAD_NT & 2
+      const v2d rl = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(r + i));
+      const double2 rv = make_double2(rl.x, rl.y);
+#else
+      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+#endif
+      xv.x += alpha * pv.x; xv.y += alpha * pv.y;
+      pv.x = rv.x + beta * pv.x;
+      pv.y = rv.y + beta * pv.y;
+#if ABFT_CFG_X_NT
+      __builtin_nontemporal_store(v2d{xv.x, xv.y}, reinterpret_cast<v2d *>(x + i));
+#else
+      *reinterpret_cast<double2 *>(x + i) = xv;
+#endif
+      *reinterpret_cast<double2 *>(p + i) = pv;
+    } else {
+      const double pv = p[i];
+      x[i] = x[i] + alpha * pv;
+      p[i] = r[i] + beta * pv;
+    }
+  }
+}
+
+// (the walk is chosen over all four operands in both launches, as launch_calc_r's is: r.r is summed in the same order)
+hipError_t launch_calc_r_until(double *r, const double *w, const double *rr, const double *pw, double threshold,
+                               double *alpha_out, int n, const ReduceOut &out, hipStream_t s, const double *x,
+                               const double *p) {
+  const int nb = reduce_blocks(n);
+  if (aligned16(r, w, x, p))
+    hipLaunchKernelGGL(calc_r_until_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, rr, pw, threshold, alpha_out, n, out);
+  else
+    hipLaunchKernelGGL(calc_r_until_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, rr, pw, threshold, alpha_out, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_px_until(double *p, const double *r, double *x, const double *rr, const double *rr_new,
+                                double threshold, const double *alpha_ptr, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+  if (aligned16(p, r, x))
+    hipLaunchKernelGGL(calc_px_until_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, x, rr, rr_new, threshold, alpha_ptr, n);
+  else
+    hipLaunchKernelGGL(calc_px_until_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, x, rr, rr_new, threshold, alpha_ptr, n);
+  return hipGetLastError();
+}
+
 // ---- block vectors (K right-hand sides, row-major: entry (i, j) at i*K + j) ----
 // One thread per row i walks rows exactly as the single kernels' threads walk elements (grid
 // reduce_blocks(n rows)); per column the same operations with the same roundings, so an active

@@ -617,6 +617,35 @@ int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abf
  * since the context was created.  Any pointer may be null. */
 int abft_hip_tail_stats(abft_hip_ctx *ctx, int *path, int *grid, int *want, long counts[4]);
 
+/* The guarded iteration: abft_hip_cg_iteration_dev behind the stop test of the reference loop (cg.cpp:94,
+ * `while (rr > conv)`), evaluated ON THE DEVICE, so that a loop with a convergence threshold can enqueue
+ * (or replay from a graph) several iterations and look at the scalars once per batch: iterations enqueued
+ * past convergence do nothing.
+ *   LIVE   when dev_rr[0] > threshold (false for NaN, as the reference's test is): bit for bit what
+ *          abft_hip_cg_iteration_dev leaves for the same arguments -- x, r, p, w, both pairs, the events words.
+ *   FROZEN otherwise: x, r and p keep every bit; dev_rr_new[0] gets the bits of dev_rr[0] (so the next guarded
+ *          iteration, reading that pair, is frozen too) and dev_rr_new[1] the queued-event count, as a live
+ *          iteration writes it; w and dev_pw are unspecified -- the SpMV still runs, with its ECC checks, its
+ *          repairs and its events (the guard is in the vector kernels alone).  Replaying a frozen iteration any
+ *          number of times changes nothing.
+ * `threshold` is a kernel argument: a captured graph keeps the threshold it was captured with.
+ * Enqueue-only and capturable; starts like every other entry (a pending x update applied, a speculation
+ * voided) and leaves nothing pending: the x half runs inside the call.  abft_hip_tail_stats is left as it was.
+ * What follows the SpMV is ALWAYS three kernels -- the fold of the fused product, the guarded r half, the
+ * guarded x / p half -- never abft_hip_cg_iteration_dev's one launch: that kernel's hand-off counters must grow by
+ * every launch's amounts, and a launch that returned early would break the bases its successor starts from.
+ * The guarded kernels decide by one word that neither writes, uniformly over the grid; a frozen launch returns
+ * before the reduction's ticket; no workgroup waits for another.
+ * Before anything is enqueued the call checks that x, r, p and w have the matrix's row count, that no two of
+ * them overlap, that vec overlaps none of x, r, w, and that p is vec's window [vec_offset, vec_offset + n) or
+ * apart from vec; that the three scalar pairs are non-null and apart; it refuses ABFT_PART_INTERIOR and a context
+ * with a peer board attached (one rank only: a frozen rank must never be the subject of a cross-rank wait).
+ * Every matrix abft_hip_cg_iteration_dev takes is accepted. */
+int abft_hip_cg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                    int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                    abft_hip_vector *p, abft_hip_vector *w, const double *dev_rr,
+                                    double *dev_pw, double *dev_rr_new, double threshold);
+
 /* ---- graph replay ------------------------------------------------------ */
 
 /* Capture everything enqueued on the context's stream between begin and end -- the
