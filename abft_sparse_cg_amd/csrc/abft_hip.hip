@@ -207,6 +207,8 @@ struct abft_hip_vector {
 };
 
 static constexpr uint32_t EVENT_CAP = 1u << 16;
+static constexpr size_t VECC_SEEN_BYTES = ABFT_VECC_SEEN_SLOTS * sizeof(unsigned long long);
+static_assert(sizeof(abft_event) % sizeof(unsigned long long) == 0, "the table behind the events is 8-byte aligned");
 static constexpr uint32_t MOVED_CAP = 4096;
 
 static int flush_deferred(abft_hip_ctx *ctx) {
@@ -397,9 +399,11 @@ extern "C" int abft_hip_init(int device, abft_hip_ctx **out) {
   HIPCHK(hipMemset(ctx->spec.scal, 0, 8 * sizeof(double)));
   if (const char *e = getenv("ABFT_HIP_SPECULATE")) ctx->spec.enabled = strcmp(e, "0") != 0;
   HIPCHK(hipHostGetDevicePointer((void **)&ctx->host_slot_dev, ctx->host_slot, 0));
-  HIPCHK(hipMalloc((void **)&ctx->ring.buf, EVENT_CAP * sizeof(abft_event)));
+  // the queue, and behind it the table of vector events already queued (abft_internal.h)
+  HIPCHK(hipMalloc((void **)&ctx->ring.buf, EVENT_CAP * sizeof(abft_event) + VECC_SEEN_BYTES));
   HIPCHK(hipMalloc((void **)&ctx->ring.count, sizeof(uint32_t)));
   HIPCHK(hipMemset(ctx->ring.count, 0, sizeof(uint32_t)));
+  HIPCHK(hipMemset(ctx->ring.buf + EVENT_CAP, 0, VECC_SEEN_BYTES));
   ctx->ring.cap = EVENT_CAP;
   HIPCHK(hipMalloc((void **)&ctx->moved.buf, 2 * (size_t)MOVED_CAP * sizeof(MovedEntry)));
   HIPCHK(hipMalloc((void **)&ctx->moved.count, sizeof(uint32_t)));
@@ -3865,6 +3869,7 @@ extern "C" int abft_hip_drain_events(abft_hip_ctx *ctx, abft_event *buf, int cap
   std::vector<abft_event> ev(n);
   HIPCHK(hipMemcpyAsync(ev.data(), ctx->ring.buf, (size_t)n * sizeof(abft_event), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->ring.count, 0, sizeof(uint32_t), ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->ring.buf + ctx->ring.cap, 0, VECC_SEEN_BYTES, ctx->stream));  // a key is only ever set together with an event
   HIPCHK(hipStreamSynchronize(ctx->stream));
   clear_pending_events(ctx);
   // The order a single-threaded reference run meets them in.  ECC events and the COO
@@ -3882,7 +3887,8 @@ extern "C" int abft_hip_drain_events(abft_hip_ctx *ctx, abft_event *buf, int cap
   });
   for (abft_event &e : ev)
     if (csr_check(e)) e.bit = 0;
-  // vector events equal in all four fields are one flip seen by several gatherers: reported once per drain
+  // vector events equal in all four fields are one flip seen by several gatherers: reported once per drain.
+  // vecc_cold already queues such a flip once; this pass remains for what its table could not hold
   // (the sort keeps equal index and kind together; between them the bits may interleave, hence the look back)
   {
     uint32_t kept = 0;

@@ -13,6 +13,12 @@ struct EventRing {
   uint32_t cap;
 };
 
+// Behind the `cap` events of EventRing::buf, in the same allocation: the table of vector events already
+// queued since the last drain (kernels.hip vecc_cold), ABFT_VECC_SEEN_SLOTS 64-bit keys, 0 = free.  It is
+// cleared wherever EventRing::count is reset.
+#define ABFT_VECC_SEEN_SLOTS 4096u
+#define ABFT_VECC_SEEN_PROBES 8u
+
 // CSR matrix as the kernels see it.  cols/vals keep the reference's SoA layout
 // (CSR/CPUContext.h:11-18) so element i is {vals[i], cols[i]}; both arrays are
 // over-allocated by 2 elements so the paired loads never leave the buffer.

@@ -149,19 +149,41 @@ __device__ __forceinline__ uint32_t ecc_suspect(const uint32_t *w) {
 // entry's argument list, `index` the element inside it.
 struct VeccWord { uint64_t w; int rc; };
 
+// A vector entry may be read by any number of threads -- every row of a dense column gathers the same
+// x[col] -- and each of them comes here with the same damaged word.  All repair it in their registers, but
+// only the first queues the event: a flipped word costs one slot of the queue however many threads see
+// it (65536 gatherers of one flipped bit would otherwise overflow the queue and end the solve, with y
+// correct).  The "already queued" table lies behind the ring's `cap` events (abft_internal.h): open
+// addressing over 64-bit keys {kind, index, bit | operand << 8} -- never 0, kind >= 10 --, cleared by the
+// drain.  A thread that meets only foreign keys queues its event anyway; the drain drops what still
+// repeats.
+__device__ __forceinline__ void push_vector_event(const EventRing &ev, uint32_t kind, uint32_t index, uint32_t bit) {
+  const unsigned long long key = ((unsigned long long)kind << 48) | ((unsigned long long)index << 16) |
+                                 (unsigned long long)(bit & 0xffffu);
+  unsigned long long *seen = reinterpret_cast<unsigned long long *>(ev.buf + ev.cap);
+  uint32_t h = ((index + (bit << 12)) * 0x9E3779B1u) >> 20;  // (32-bit: the callers' registers are this function's)
+#pragma unroll 1
+  for (uint32_t k = 0; k < ABFT_VECC_SEEN_PROBES; k++, h++) {
+    const unsigned long long was = atomicCAS(seen + (h & (ABFT_VECC_SEEN_SLOTS - 1u)), 0ull, key);
+    if (was == key) return;  // queued by another thread
+    if (was == 0ull) break;  // ours now
+  }
+  push_event(ev, kind, index, bit, ABFT_FMT_VECTOR);
+}
+
 __device__ __noinline__ VeccWord vecc_cold(uint64_t word, uint32_t index, uint32_t operand, EventRing ev) {
   VeccWord o;
   o.w = word; o.rc = 0;
   const uint32_t s = vecc_syndrome(word);
+  uint32_t bit = 0u;
   if (popc((uint32_t)word ^ (uint32_t)(word >> 32)) & 1u) {
-    const uint32_t bit = s ? vecc_position_to_bit(s) : 0u;
+    bit = s ? vecc_position_to_bit(s) : 0u;
     o.w = word ^ (1ull << bit);
     o.rc = 1;
-    push_event(ev, ABFT_EV_VEC_CORRECTED, index, bit | (operand << 8), ABFT_FMT_VECTOR);
   } else if (s) {
     o.rc = -1;
-    push_event(ev, ABFT_EV_VEC_DOUBLE, index, operand << 8, ABFT_FMT_VECTOR);
   }
+  if (o.rc) push_vector_event(ev, o.rc > 0 ? ABFT_EV_VEC_CORRECTED : ABFT_EV_VEC_DOUBLE, index, bit | (operand << 8));
   return o;
 }
 

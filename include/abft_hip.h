@@ -669,7 +669,11 @@ int abft_hip_graph_destroy(abft_hip_graph *graph);
  * single-threaded reference run prints them in.  *count = events returned,
  * *fatal = 1 if the last one is fatal (the reference would have exit(1)ed).
  * Vector events (ABFT_FMT_VECTOR) equal in all four fields are reported once per
- * drain: every gatherer of one vector entry sees the same flip. */
+ * drain: every gatherer of one vector entry sees the same flip.  The duplicates
+ * are already suppressed on the device -- the first thread to meet a flipped word
+ * queues it, the others find its key in a table that this call clears --, so a
+ * flipped entry of a dense column costs one slot of the queue, not one per row
+ * that gathers it, and cannot overflow it. */
 int abft_hip_drain_events(abft_hip_ctx *ctx, abft_event *buf, int cap, int *count, int *fatal);
 /* Capacity of the device event queue = the `cap` with which drain never truncates.
  * drain returns ABFT_ERR_RANGE (after filling buf / count / fatal) if the device queued
