@@ -542,6 +542,13 @@ class HIPContext:
         check(self.L.abft_hip_tail_stats(self.h, C.byref(path), C.byref(grid), C.byref(want), counts))
         return path.value, grid.value, want.value, list(counts)
 
+    def x_in_spmv_stats(self):
+        """x updates left pending on the old p by calc_p -> (absorbed, flushed): applied by the SpMV that followed, or
+        on their own because something else came first (abft_hip_x_in_spmv_stats, include/abft_hip.h)"""
+        absorbed, flushed = C.c_long(0), C.c_long(0)
+        check(self.L.abft_hip_x_in_spmv_stats(self.h, C.byref(absorbed), C.byref(flushed)))
+        return absorbed.value, flushed.value
+
     # ---- the device-scalar loop (include/abft_hip.h; DESIGN.md section 5f): cg_solve_device ----
     def cg_iteration_until_dev(self, mat, vec, x, r, p, w, scalars, rr_at, pw_at, rr_new_at, threshold, vec_offset=0,
                                part=capi.PART_ALL):

@@ -117,6 +117,31 @@ struct abft_hip_ctx {
     double alpha = 0.0;
   } defer;
   double *alpha_dev = nullptr;  // alpha of the deferred update when it was formed on the device
+  // cross-call fusion no. 4: in the host-scalar loop spmv(A, p, w), [dot], calc_xr, calc_p the deferred x += alpha p is
+  // the one piece of work nothing waits for, so once the library has seen spmv(A, p, w) directly follow a calc_p that
+  // took a deferred update along (`armed`), that calc_p writes the new p into `shadow`, swaps it with p's buffer and
+  // leaves the update pending on the OLD p (`active`); the predicted spmv(A, p, w) -- streaming CSR, fused product --
+  // applies it row by row under its own memory latency (spmv_csr_kernel<..., XUPD>).  Anything else that comes first
+  // applies it with axpy_kernel (bind) and disarms.  Same bits either way; only when each x[i] is written changes.
+  // ABFT_HIP_X_IN_SPMV=0 / =1; by default on the modes of ABFT_X_IN_SPMV_MODES; off without the deferred update or the fused product, with the
+  // speculation, and from the first graph capture on (a captured launch holds p's buffer by address).
+  bool xin_enabled = true;
+  unsigned xin_modes = ABFT_X_IN_SPMV_MODES;  // bit m: armed on matrices of ECC mode m (ABFT_HIP_X_IN_SPMV=1: every mode)
+  struct {
+    bool armed = false, active = false;
+    const abft_hip_vector *last_p = nullptr;  // set by the calc_p that consumed a deferred update on this p ...
+    const abft_hip_vector *prev_p = nullptr;  // ... and handed to the entry point that follows it directly (bind)
+    double *x = nullptr;                      // the pending update: x += alpha p_old over n elements
+    const double *p_old = nullptr;
+    double alpha = 0.0;
+    int n = 0;
+    const abft_hip_vector *ph = nullptr;      // the handle whose buffer was swapped
+    // context-owned: where the next calc_p writes (the old p while pending).  Two slots by length, so that a caller who
+    // alternates solves of two sizes does not free and allocate (both synchronise the device) at every switch
+    struct { double *buf = nullptr; int n = 0; } shadow[2];
+    int shadow_at = 0;                        // the slot used last
+    long absorbed = 0, flushed = 0;
+  } xpend;
   // block right-hand sides (abft_hip_dot_block, abft_hip_calc_xr_block): allocated by the first such call
   double *bpartials = nullptr;          // 2 * ABFT_MAX_RHS * ABFT_MAX_PARTIALS doubles (the 2K sums of a block check)
   HostSlotK *bslot = nullptr, *bslot_dev = nullptr;  // pinned K-wide result slot, its device alias
@@ -211,6 +236,17 @@ static constexpr size_t VECC_SEEN_BYTES = ABFT_VECC_SEEN_SLOTS * sizeof(unsigned
 static_assert(sizeof(abft_event) % sizeof(unsigned long long) == 0, "the table behind the events is 8-byte aligned");
 static constexpr uint32_t MOVED_CAP = 4096;
 
+// the pending x += alpha p_old on its own: something other than the predicted SpMV came first
+static int flush_xpend(abft_hip_ctx *ctx) {
+  auto &X = ctx->xpend;
+  if (!X.active) return ABFT_OK;
+  X.active = false;
+  X.armed = false;
+  X.flushed++;
+  HIPCHK(launch_axpy(X.x, X.p_old, X.alpha, nullptr, X.n, ctx->stream));
+  return ABFT_OK;
+}
+
 static int flush_deferred(abft_hip_ctx *ctx) {
   if (!ctx->defer.active) return ABFT_OK;
   ctx->defer.active = false;
@@ -244,10 +280,16 @@ static void spec_forget(abft_hip_ctx *ctx) {
 
 // (keep_spec: the caller is one of the continuations a speculation waits for -- dot(p, w), calc_xr, calc_p -- and
 // decides itself; every other entry point voids it)
-static int bind(abft_hip_ctx *ctx, bool keep_deferred = false, bool keep_spec = false) {
+// (keep_xpend: the caller is the SpMV that may absorb the update pending on the old p; calls that touch no vector keep
+// it as they keep the deferred one)
+static int bind(abft_hip_ctx *ctx, bool keep_deferred = false, bool keep_spec = false, bool keep_xpend = false) {
   if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");
   HIPCHK(hipSetDevice(ctx->device));
+  ctx->xpend.prev_p = ctx->xpend.last_p;
+  ctx->xpend.last_p = nullptr;
   if (!keep_spec) spec_drop(ctx);
+  if (!keep_deferred && !keep_xpend)
+    if (int rc = flush_xpend(ctx)) return rc;
   if (!keep_deferred) return flush_deferred(ctx);
   return ABFT_OK;
 }
@@ -398,6 +440,11 @@ extern "C" int abft_hip_init(int device, abft_hip_ctx **out) {
   HIPCHK(hipMalloc((void **)&ctx->spec.scal, 8 * sizeof(double)));
   HIPCHK(hipMemset(ctx->spec.scal, 0, 8 * sizeof(double)));
   if (const char *e = getenv("ABFT_HIP_SPECULATE")) ctx->spec.enabled = strcmp(e, "0") != 0;
+  if (const char *e = getenv("ABFT_HIP_X_IN_SPMV")) {  // 0: never; 1: on every mode; unset: on the modes it was measured to pay on
+    ctx->xin_enabled = strcmp(e, "0") != 0;
+    if (ctx->xin_enabled) ctx->xin_modes = ~0u;
+  }
+  ctx->xin_enabled = ctx->xin_enabled && ctx->defer_enabled && ctx->fuse_enabled && !ctx->spec.enabled;
   HIPCHK(hipHostGetDevicePointer((void **)&ctx->host_slot_dev, ctx->host_slot, 0));
   // the queue, and behind it the table of vector events already queued (abft_internal.h)
   HIPCHK(hipMalloc((void **)&ctx->ring.buf, EVENT_CAP * sizeof(abft_event) + VECC_SEEN_BYTES));
@@ -432,6 +479,7 @@ extern "C" int abft_hip_init(int device, abft_hip_ctx **out) {
 extern "C" int abft_hip_shutdown(abft_hip_ctx *ctx) {
   if (!ctx) return ABFT_OK;
   (void)hipSetDevice(ctx->device);
+  (void)flush_xpend(ctx);
   (void)flush_deferred(ctx);
   (void)hipStreamSynchronize(ctx->stream);
   if (debug_leak('d')) (void)hipDeviceSynchronize();
@@ -456,6 +504,7 @@ extern "C" int abft_hip_shutdown(abft_hip_ctx *ctx) {
   if (getenv("ABFT_HIP_VERBOSE") && (ctx->spec.commits || ctx->spec.drops))
     fprintf(stderr, "hip: speculated iterations: %ld taken over, %ld dropped\n", ctx->spec.commits, ctx->spec.drops);
   for (double *b : ctx->spec.shadow) (void)hipFree(b);
+  for (auto &b : ctx->xpend.shadow) (void)hipFree(b.buf);
   (void)hipFree(ctx->spec.scal);
   if (!debug_leak('h')) (void)hipHostFree(ctx->host_slot);
   (void)hipFree(ctx->ring.buf);
@@ -1983,9 +2032,49 @@ static int calc_xr_launch(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector
   return ABFT_OK;
 }
 
+static bool spec_plain(const abft_hip_vector *v, int n);
+
+// The new p into the context's buffer, the buffers swapped, the deferred x += alpha p left pending on the old one
+// (see abft_hip_ctx::xpend).  False: not now -- the caller runs calc_px as before.
+static bool xpend_take(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, double beta, int *rc) {
+  auto &X = ctx->xpend;
+  *rc = ABFT_OK;
+  if (!ctx->xin_enabled || !X.armed || X.active || ctx->defer.on_dev || ctx->capturing) return false;
+  // p's handle is the only way to its buffer (a whole root vector, never exposed, no views): the swap goes unseen
+  if (!spec_plain(p, p->n) || !disjoint(p, r)) return false;
+  int at = X.shadow[0].buf && X.shadow[0].n == p->n ? 0 : X.shadow[1].buf && X.shadow[1].n == p->n ? 1 : -1;
+  if (at < 0) {  // a length seen for the first time (or a third one): the slot not used last makes room
+    at = X.shadow[X.shadow_at].buf ? 1 - X.shadow_at : X.shadow_at;
+    (void)hipFree(X.shadow[at].buf);
+    X.shadow[at].buf = nullptr;
+    X.shadow[at].n = 0;
+    if (hipMalloc((void **)&X.shadow[at].buf, ((size_t)p->n + 2) * sizeof(double)) != hipSuccess) {  // no room: as before
+      (void)hipGetLastError();
+      X.shadow[at].buf = nullptr;
+      ctx->xin_enabled = false;
+      return false;
+    }
+    X.shadow[at].n = p->n;
+  }
+  X.shadow_at = at;
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_P);
+    const hipError_t e = launch_calc_p(p->d, r->d, beta, nullptr, nullptr, p->n, ctx->stream, X.shadow[at].buf);
+    if (e != hipSuccess) {
+      *rc = set_err(ABFT_ERR_HIP, "calc_p: %s", hipGetErrorString(e));
+      return true;
+    }
+  }
+  std::swap(p->d, X.shadow[at].buf);
+  X.active = true;
+  X.x = ctx->defer.x; X.p_old = X.shadow[at].buf; X.alpha = ctx->defer.alpha; X.n = p->n; X.ph = p;
+  return true;
+}
+
 // calc_p, or calc_p plus the x update the preceding calc_xr left behind
 static int calc_p_launch(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, double beta,
                          const double *num, const double *den) {
+  if (int rc = flush_xpend(ctx)) return rc;  // (calc_p twice in a row: the first one's old p is about to go)
   if (int rc = check_same(p, r, "calc_p")) return rc;
   ctx->fused.valid = false;
   if (ctx->defer.active) {
@@ -1993,6 +2082,13 @@ static int calc_p_launch(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_v
     xv.d = ctx->defer.x; xv.n = ctx->defer.n;
     if (ctx->defer.p == p->d && ctx->defer.n == p->n && disjoint(&xv, r)) {
       ctx->defer.active = false;
+      if (!num) {
+        int rc = ABFT_OK;
+        const bool taken = xpend_take(ctx, p, r, beta, &rc);
+        if (rc) return rc;
+        ctx->xpend.last_p = p;  // an SpMV of this p as the very next call arms (or keeps) the prediction
+        if (taken) return ABFT_OK;
+      }
       KernelTimer t(ctx, ABFT_K_CALC_P);
       HIPCHK(launch_calc_px(p->d, r->d, ctx->defer.x, beta, num, den, ctx->defer.alpha,
                             ctx->defer.on_dev ? ctx->alpha_dev : nullptr, p->n, ctx->stream));
@@ -2663,10 +2759,42 @@ struct HeldFold {
   FixArgs fix{};
 };
 
+// Is this call the SpMV the pending x update waits for -- abft_hip_spmv(A, p, w) on the streaming CSR layout, whole,
+// with the fused product, p the handle whose buffer was swapped, w apart from x, p and the old p?  (Then every check
+// spmv_common makes below holds, and the launch covers every row block.)  Also where the prediction is armed: such a
+// call on a plain p directly after the calc_p that took a deferred update on that p along.
+static bool xpend_predicted(abft_hip_ctx *ctx, const abft_hip_matrix *mat, const abft_hip_vector *vec,
+                            const abft_hip_vector *result, const double *dev_pair, int part, int c1, bool held,
+                            bool vecc) {
+  auto &X = ctx->xpend;
+  const abft_hip_vector *after_calc_p = X.prev_p;
+  X.prev_p = nullptr;
+  if (!ctx->xin_enabled || !mat || !vec || !result) return false;
+  if (mat->fmt != ABFT_FMT_CSR || mat->use_slice || mat->use_sweep || mat->use_panels) return false;
+  if (!(ctx->xin_modes >> (unsigned)mat->mode & 1u)) return false;  // not a mode it pays on (a pending update, left by a matrix of another mode, is applied first)
+  if (part != ABFT_PART_ALL || c1 >= 0 || dev_pair || held || vecc || ctx->capturing) return false;
+  const uint32_t n = mat->csr.n_out;
+  if (!mat->fuse_partials || !ctx->fuse_enabled || n == 0 || mat->csr.n_in != n || mat->csr.nblk == 0 ||
+      (uint32_t)vec->n != n || (uint32_t)result->n != n || !disjoint(vec, result))
+    return false;
+  if (!X.active) {
+    if (after_calc_p == vec && spec_plain(vec, vec->n)) X.armed = true;
+    return false;
+  }
+  abft_hip_vector xv, pv;  // just the ranges, for the overlap tests
+  xv.d = X.x; xv.n = X.n;
+  pv.d = const_cast<double *>(X.p_old); pv.n = X.n;
+  return X.ph == vec && (uint32_t)X.n == n && disjoint(&xv, result) && disjoint(&pv, result);
+}
+
 static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
                        abft_hip_vector *result, int vec_offset, double *dev_pair, int part = ABFT_PART_ALL,
                        int c0 = 0, int c1 = -1, HeldFold *hold = nullptr, bool vecc = false) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = bind(ctx, false, false, true)) return rc;
+  // the update pending on the old p (abft_hip_ctx::xpend): this launch applies it, or it is applied first
+  const bool absorb = xpend_predicted(ctx, mat, vec, result, dev_pair, part, c1, hold != nullptr, vecc);
+  if (!absorb)
+    if (int rc = flush_xpend(ctx)) return rc;
   if (!mat || !vec || !result) return set_err(ABFT_ERR_INVALID, "spmv: null argument");
   if (vecc) {  // protected vectors: the streaming CSR kernel only; the iteration they are part of is not speculated
     spec_forget(ctx);
@@ -2749,10 +2877,15 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
       else
         HIPCHK(launch_spmv_coo_panels(mat->mode, mat->coo, mat->panels, vec->d, result->d, ctx->ring,
                                       do_fuse ? &fuse : nullptr, mat->panel_grid, mat->panel_chunk, ctx->stream));
-    } else if (mat->fmt == ABFT_FMT_CSR)
+    } else if (mat->fmt == ABFT_FMT_CSR) {
+      const XUpd xu{ctx->xpend.x, ctx->xpend.p_old, ctx->xpend.alpha};
       HIPCHK(launch_spmv_csr(mat->mode, mat->csr, mat->compact, mat->packed, span, vec->d, result->d, ctx->ring,
-                             do_fuse ? &fuse : nullptr, ctx->stream, vecc));
-    else
+                             do_fuse ? &fuse : nullptr, ctx->stream, vecc, absorb ? &xu : nullptr));
+      if (absorb) {  // applied exactly once, whatever the launch reports about the matrix
+        ctx->xpend.active = false;
+        ctx->xpend.absorbed++;
+      }
+    } else
       HIPCHK(launch_spmv_coo(mat->mode, mat->coo, vec->d, result->d, ctx->ring, do_fuse ? &fuse : nullptr, ctx->stream));
     // COO: products whose stored column was silently corrupted go where the reference puts them --
     // inside the fold of the fused product below when there is one, else as a launch of its own
@@ -3312,6 +3445,7 @@ extern "C" int abft_hip_calc_p_precond(abft_hip_ctx *ctx, abft_hip_vector *p, co
                                        const abft_hip_vector *dinv, double beta) {
   if (int rc = check_precond("calc_p_precond", {r}, {p}, dinv)) return rc;
   if (int rc = bind_precond(ctx, true)) return rc;
+  if (int rc = flush_xpend(ctx)) return rc;
   if (ctx->defer.active) {
     abft_hip_vector xv;  // just the range, for the overlap tests
     xv.d = ctx->defer.x; xv.n = ctx->defer.n;
@@ -3736,6 +3870,14 @@ extern "C" int abft_hip_cg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matri
   return ABFT_OK;
 }
 
+// what became of the x updates left pending on the old p: applied by the predicted SpMV, or on their own
+extern "C" int abft_hip_x_in_spmv_stats(abft_hip_ctx *ctx, long *absorbed, long *flushed) {
+  if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");
+  if (absorbed) *absorbed = ctx->xpend.absorbed;
+  if (flushed) *flushed = ctx->xpend.flushed;
+  return ABFT_OK;
+}
+
 // ------------------------------------------------------------- graph replay --
 
 // A captured sequence of asynchronous calls on the context's stream (and of whatever else
@@ -3751,6 +3893,7 @@ struct abft_hip_graph {
 extern "C" int abft_hip_graph_begin(abft_hip_ctx *ctx) {
   if (int rc = bind(ctx)) return rc;
   if (ctx->prof) return set_err(ABFT_ERR_INVALID, "graph capture with kernel brackets enabled (abft_hip_profile_enable)");
+  ctx->xin_enabled = false;  // a captured launch holds p's buffer by address: no swap of it from here on
   HIPCHK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
   ctx->capturing = true;
   return ABFT_OK;

@@ -206,6 +206,15 @@ struct CooDev {
 #ifndef ABFT_CFG_PX_OUT_NT
 #define ABFT_CFG_PX_OUT_NT 0  // calc_px writing into shadow buffers (speculation): non-temporal stores, bit 0 x, bit 1 p
 #endif
+#ifndef ABFT_X_IN_SPMV_MODES
+#define ABFT_X_IN_SPMV_MODES 0x01u  // the x update inside the next SpMV (abft_hip.hip, xpend): bit m = armed by default on matrices of ECC mode m -- `none` only: in the five other modes the alternated series showed no gain, in sed a loss (profiles/r11/mode_*)
+#endif
+#ifndef ABFT_CFG_XUPD_NT
+#define ABFT_CFG_XUPD_NT 7  // spmv_csr_kernel<..., XUPD>: non-temporal access to the update's streams, bit 0 the p_old load, 1 the x load, 2 the x store (0: 2-3 % slower than without the update; 7 with P_OUT_NT: 5 % faster, profiles/r11)
+#endif
+#ifndef ABFT_CFG_P_OUT_NT
+#define ABFT_CFG_P_OUT_NT 1  // calc_p writing the new p into the buffer its handle swaps to (xpend): non-temporal stores
+#endif
 #ifndef ABFT_CFG_X_NT
 #define ABFT_CFG_X_NT 0  // calc_px: x (touched once per iteration) by non-temporal loads and stores
 #endif
@@ -330,6 +339,13 @@ struct TileSpan {
   uint32_t first, cut, skip, count;
 };
 
+// spmv_csr_kernel<..., XUPD>: the pending x += alpha p_old the launch applies, row by row (abft_hip.hip "xpend")
+struct XUpd {
+  double *xs;
+  const double *p_old;
+  double alpha;
+};
+
 // sweep-layout SpMV (modes other than constraints): panels [c0, c1) in one persistent launch of
 // `grid` workgroups (all resident); c0 > 0 resumes from the sums a previous launch left in y
 hipError_t launch_spmv_sweep(int mode, int rpt, const CsrDev &A, const SweepLayout &L, const double *x, double *y,
@@ -355,7 +371,7 @@ hipError_t launch_fuse_finalize(const FuseOut &f, uint32_t nblk, const ReduceOut
 // vecc: x and y hold protected elements (abft_hip_spmv_vecc)
 hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
                            const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s,
-                           bool vecc = false);
+                           bool vecc = false, const XUpd *xu = nullptr);
 hipError_t launch_spmv_coo(int mode, const CooDev &A, const double *x, double *y, EventRing ev,
                            const FuseOut *fuse, hipStream_t s);
 // behind every COO SpMV: see MovedList.  With a fused product the fix-up runs inside the fold
@@ -410,7 +426,7 @@ hipError_t launch_dot(const double *a, const double *b, int n, const ReduceOut &
 hipError_t launch_calc_xr(double *x, double *r, const double *p, const double *w, double alpha,
                           const double *num, const double *den, int n, const ReduceOut &out, hipStream_t s);
 hipError_t launch_calc_p(double *p, const double *r, double beta, const double *num, const double *den, int n,
-                         hipStream_t s);
+                         hipStream_t s, double *p_out = nullptr);
 hipError_t launch_calc_r(double *r, const double *w, double alpha, const double *num, const double *den,
                          double *alpha_out, int n, const ReduceOut &out, hipStream_t s, double *r_out = nullptr,
                          const double *x = nullptr, const double *p = nullptr);

@@ -833,11 +833,27 @@ __device__ __forceinline__ bool csr_row_sum(const CsrDev &A, const EventRing &ev
 // VECC (abft_hip_spmv_vecc): x and y hold protected elements.  Every gathered x and
 // the fused product's x[row] get the full check (repaired in registers, reported, x itself not written
 // back); y[row] is stored encoded and the fused product uses the decoded x[row] and the truncated sum.
-template <int MODE, int EPT, bool FUSE, bool VECC = false>
+// XUPD (cross-call fusion no. 4, abft_hip.hip "xpend"): the launch also applies the x += alpha p that the
+// preceding calc_p left pending on the OLD p -- xu.xs[row] = xu.xs[row] + xu.alpha * xu.p_old[row] for every
+// row of the workgroup's row block, exactly once, whatever becomes of the row (no elements, bad row
+// pointers, a fatal element): two row-indexed, coalesced streams that hang off the block descriptor only
+// and travel under the latency of the codes and the gathers.  Separate multiply and add
+// (-ffp-contract=off): the bits axpy_kernel / calc_px_kernel give.  The row blocks partition
+// [0, n_out) (cut_blocks), and the launch covers every block.
+#if ABFT_CFG_XUPD_NT  // the update's streams are touched once per launch: keep them out of the caches the gathers live in
+#define XUPD_LOAD_P(p) ((ABFT_CFG_XUPD_NT & 1) ? __builtin_nontemporal_load(p) : *(p))
+#define XUPD_LOAD_X(p) ((ABFT_CFG_XUPD_NT & 2) ? __builtin_nontemporal_load(p) : *(p))
+#define XUPD_STORE_X(p, v) do { if (ABFT_CFG_XUPD_NT & 4) __builtin_nontemporal_store((v), (p)); else *(p) = (v); } while (0)
+#else
+#define XUPD_LOAD_P(p) (*(p))
+#define XUPD_LOAD_X(p) (*(p))
+#define XUPD_STORE_X(p, v) (*(p) = (v))
+#endif
+template <int MODE, int EPT, bool FUSE, bool VECC = false, bool XUPD = false>
 __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const double *__restrict__ x,
                                                               double *__restrict__ y, EventRing ev,
                                                               FuseOut fuse, TileSpan span, CsrCompact cc,
-                                                              CsrPacked cp) {
+                                                              CsrPacked cp, XUpd xu) {
   constexpr uint32_t TILE = ABFT_BLOCK * EPT;
   __shared__ __attribute__((aligned(16))) double s_prod[TILE];
   __shared__ __attribute__((aligned(16))) uint32_t s_col[MODE == MODE_CONSTRAINTS ? TILE : 2];
@@ -869,6 +885,8 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
       }
       if (FUSE) xr = x[fuse.x_off + r];
     }
+    double xs = 0.0, po = 0.0;  // XUPD: the first row's operands, in flight beside the codes and the gathers
+    if (XUPD && r < row1) { xs = XUPD_LOAD_X(xu.xs + r); po = XUPD_LOAD_P(xu.p_old + r); }
     if (MODE == MODE_NONE && pd.y != 0u)
       csr_stage_packed<EPT, VECC>(A, cp, pd, x, ev, base, e0, e1, s_prod);
     else if (MODE == MODE_NONE)
@@ -880,7 +898,9 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
       if (row != r) {
         rs = A.rowptr[row]; re = A.rowptr[row + 1];
         if (FUSE) xr = x[fuse.x_off + row];
+        if (XUPD) { xs = XUPD_LOAD_X(xu.xs + row); po = XUPD_LOAD_P(xu.p_old + row); }
       }
+      if (XUPD) XUPD_STORE_X(xu.xs + row, xs + xu.alpha * po);  // in front of every `continue`: the update does not depend on the row
       if (MODE == MODE_CONSTRAINTS) {  // reference CSR/CPUContext.cpp:173-182
         if (re > A.nnz) { push_event(ev, ABFT_EV_ROW_SIZE, row, row, FMT_CSR); continue; }
         if (re < rs) { push_event(ev, ABFT_EV_ROW_ORDER, row, row, FMT_CSR); continue; }
@@ -904,6 +924,8 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
     }
   } else {
     // long row (or inconsistent pointers): rows of this block one at a time, tile by tile
+    if (XUPD)
+      for (uint32_t row = row0 + threadIdx.x; row < row1; row += ABFT_BLOCK) XUPD_STORE_X(xu.xs + row, XUPD_LOAD_X(xu.xs + row) + xu.alpha * XUPD_LOAD_P(xu.p_old + row));
     for (uint32_t row = row0; row < row1; row++) {
       const uint32_t rs = A.rowptr[row], re = A.rowptr[row + 1];
       if (MODE == MODE_CONSTRAINTS) {
@@ -1069,24 +1091,31 @@ int spmv_csr_panels_blocks_per_cu(int mode, bool fuse) {
 template <int MODE>
 static hipError_t launch_spmv_csr_mode(const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
                                        const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s,
-                                       bool vecc) {
-  if (vecc && fuse)
+                                       bool vecc, const XUpd *xu) {
+  if (xu)
+    hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true, false, true>), dim3(span.count), dim3(ABFT_BLOCK), 0,
+                       s, A, x, y, ev, *fuse, span, cc, cp, *xu);
+  else if (vecc && fuse)
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true, true>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
-                       x, y, ev, *fuse, span, cc, cp);
+                       x, y, ev, *fuse, span, cc, cp, XUpd{});
   else if (vecc)
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, false, true>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
-                       x, y, ev, FuseOut{}, span, cc, cp);
+                       x, y, ev, FuseOut{}, span, cc, cp, XUpd{});
   else if (fuse) {
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
-                       x, y, ev, *fuse, span, cc, cp);
+                       x, y, ev, *fuse, span, cc, cp, XUpd{});
   } else
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, false>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
-                       x, y, ev, FuseOut{}, span, cc, cp);
+                       x, y, ev, FuseOut{}, span, cc, cp, XUpd{});
   return hipGetLastError();
 }
 
 hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
-                           const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s, bool vecc) {
+                           const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s, bool vecc,
+                           const XUpd *xu) {
+  // the x update rides on a launch of every row block with the fused product, plain vectors (abft_hip.hip decides)
+  if (xu && (!fuse || vecc || span.first || span.skip || span.count != A.nblk || !span.count || !xu->xs || !xu->p_old))
+    return hipErrorInvalidValue;
   // every tile the span maps to must exist: checked here, on the host
   if (span.count == 0) return hipSuccess;
   if ((uint64_t)span.first + span.count + span.skip > A.nblk || span.cut > span.count) return hipErrorInvalidValue;
@@ -1096,12 +1125,12 @@ hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, cons
   if ((cp.code16 || cp.pdesc || cp.pal) && (mode != MODE_NONE || !cp.code16 || !cp.pdesc || !cp.pal))
     return hipErrorInvalidValue;
   switch (mode) {
-    case MODE_NONE: return launch_spmv_csr_mode<MODE_NONE>(A, cc, cp, span, x, y, ev, fuse, s, vecc);
-    case MODE_CONSTRAINTS: return launch_spmv_csr_mode<MODE_CONSTRAINTS>(A, cc, cp, span, x, y, ev, fuse, s, vecc);
-    case MODE_SED: return launch_spmv_csr_mode<MODE_SED>(A, cc, cp, span, x, y, ev, fuse, s, vecc);
-    case MODE_SEC7: return launch_spmv_csr_mode<MODE_SEC7>(A, cc, cp, span, x, y, ev, fuse, s, vecc);
-    case MODE_SEC8: return launch_spmv_csr_mode<MODE_SEC8>(A, cc, cp, span, x, y, ev, fuse, s, vecc);
-    case MODE_SECDED: return launch_spmv_csr_mode<MODE_SECDED>(A, cc, cp, span, x, y, ev, fuse, s, vecc);
+    case MODE_NONE: return launch_spmv_csr_mode<MODE_NONE>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu);
+    case MODE_CONSTRAINTS: return launch_spmv_csr_mode<MODE_CONSTRAINTS>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu);
+    case MODE_SED: return launch_spmv_csr_mode<MODE_SED>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu);
+    case MODE_SEC7: return launch_spmv_csr_mode<MODE_SEC7>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu);
+    case MODE_SEC8: return launch_spmv_csr_mode<MODE_SEC8>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu);
+    case MODE_SECDED: return launch_spmv_csr_mode<MODE_SECDED>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu);
     default: return hipErrorInvalidValue;
   }
 }
@@ -3479,21 +3508,29 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_xr_kernel(double *__restrict_
 }
 
 // calc_p (reference CSR/CPUContext.cpp:107-113): p = r + beta p
+// (p_out: where the new p goes -- p itself, or the buffer p's handle is about to swap to while the old p waits
+// for the SpMV that applies x += alpha p_old, abft_hip.hip "xpend")
 template <int VEC>
-__global__ __launch_bounds__(ABFT_BLOCK) void calc_p_kernel(double *__restrict__ p, const double *__restrict__ r,
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_p_kernel(const double *p, const double *__restrict__ r,
                                                             double beta, const double *num, const double *den,
-                                                            int n) {
+                                                            int n, double *p_out) {
   if (num) beta = *num / *den;  // beta = rr_new / rr formed on the device (cg.cpp:109)
   const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
   for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
     if (VEC == 2 && i + 1 < n) {
-      double2 pv = *reinterpret_cast<double2 *>(p + i);
+      double2 pv = *reinterpret_cast<const double2 *>(p + i);
       const double2 rv = *reinterpret_cast<const double2 *>(r + i);
       pv.x = rv.x + beta * pv.x;
       pv.y = rv.y + beta * pv.y;
-      *reinterpret_cast<double2 *>(p + i) = pv;
+#if ABFT_CFG_P_OUT_NT
+      typedef double v2d __attribute__((ext_vector_type(2)));
+      if (p_out != p) __builtin_nontemporal_store(v2d{pv.x, pv.y}, reinterpret_cast<v2d *>(p_out + i));
+      else *reinterpret_cast<double2 *>(p_out + i) = pv;
+#else
+      *reinterpret_cast<double2 *>(p_out + i) = pv;
+#endif
     } else {
-      p[i] = r[i] + beta * p[i];
+      p_out[i] = r[i] + beta * p[i];
     }
   }
 }
@@ -3523,13 +3560,14 @@ hipError_t launch_calc_xr(double *x, double *r, const double *p, const double *w
 }
 
 hipError_t launch_calc_p(double *p, const double *r, double beta, const double *num, const double *den, int n,
-                         hipStream_t s) {
+                         hipStream_t s, double *p_out) {
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
-  if (aligned16(p, r))
-    hipLaunchKernelGGL(calc_p_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, num, den, n);
+  if (!p_out) p_out = p;
+  if (aligned16(p, r, p_out))
+    hipLaunchKernelGGL(calc_p_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, num, den, n, p_out);
   else
-    hipLaunchKernelGGL(calc_p_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, num, den, n);
+    hipLaunchKernelGGL(calc_p_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, num, den, n, p_out);
   return hipGetLastError();
 }
 

@@ -617,6 +617,20 @@ int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abf
  * since the context was created.  Any pointer may be null. */
 int abft_hip_tail_stats(abft_hip_ctx *ctx, int *path, int *grid, int *want, long counts[4]);
 
+/* The x update inside the next SpMV (host-scalar loop; DESIGN.md section 4, "Fourth cross-call fusion").  Once
+ * abft_hip_spmv(A, p, w) has been seen directly behind an abft_hip_calc_p(p, r, beta) that took the x += alpha p of
+ * the preceding abft_hip_calc_xr along, the following abft_hip_calc_p writes the new p into a buffer of the
+ * context's, swaps it with p's and leaves x += alpha p_old pending; the abft_hip_spmv(A, p, w) that follows -- a
+ * CSR matrix in the streaming layout, with the fused product -- applies it row by row, and any other call applies
+ * it first, as a kernel of its own.  Every x, r, p, w, scalar and event keeps its bits; only when x[i] is written
+ * changes.  p must be a whole vector whose device pointer was never handed out and that has no views.
+ * By default the prediction is armed on matrices of mode ABFT_MODE_NONE only (the one mode it was measured to pay on);
+ * ABFT_HIP_X_IN_SPMV=1 (read when the context is created) arms it in every mode, =0 in none; it is also off with
+ * ABFT_HIP_FUSE_X=0, ABFT_HIP_FUSE_DOT=0 or ABFT_HIP_SPECULATE=1, and from the context's first
+ * abft_hip_graph_begin on.  *absorbed = pending updates applied by an SpMV, *flushed = applied on their own, since
+ * the context was created (host counters; either pointer may be null). */
+int abft_hip_x_in_spmv_stats(abft_hip_ctx *ctx, long *absorbed, long *flushed);
+
 /* The guarded iteration: abft_hip_cg_iteration_dev behind the stop test of the reference loop (cg.cpp:94,
  * `while (rr > conv)`), evaluated ON THE DEVICE, so that a loop with a convergence threshold can enqueue
  * (or replay from a graph) several iterations and look at the scalars once per batch: iterations enqueued
