@@ -549,6 +549,13 @@ class HIPContext:
         check(self.L.abft_hip_x_in_spmv_stats(self.h, C.byref(absorbed), C.byref(flushed)))
         return absorbed.value, flushed.value
 
+    def ahead_stats(self):
+        """kernels of the host-scalar loop run ahead of the scalars -> (committed_p, committed_r, dropped): calc_p / calc_xr
+        calls that took one over, and run-aheads thrown away (abft_hip_ahead_stats, include/abft_hip.h)"""
+        cp, cr, d = C.c_long(0), C.c_long(0), C.c_long(0)
+        check(self.L.abft_hip_ahead_stats(self.h, C.byref(cp), C.byref(cr), C.byref(d)))
+        return cp.value, cr.value, d.value
+
     # ---- the device-scalar loop (include/abft_hip.h; DESIGN.md section 5f): cg_solve_device ----
     def cg_iteration_until_dev(self, mat, vec, x, r, p, w, scalars, rr_at, pw_at, rr_new_at, threshold, vec_offset=0,
                                part=capi.PART_ALL):

@@ -92,6 +92,21 @@ struct abft_hip_ctx {
     int shadow_n = 0;
     double *scal = nullptr;               // device doubles: [0], [1] r.r (alternating), [2] p.w (+ their event counts behind: 6 doubles)
     long commits = 0, drops = 0;
+    // Run-ahead (cross-call fusion no. 5; ABFT_HIP_AHEAD=0|1|2, DESIGN.md section 4 "Fifth cross-call fusion"): the same
+    // idea with what x-in-SpMV left to do.  calc_p already writes out of place into xpend's buffer, so level 1 launches
+    // it right behind calc_r, BEFORE the host waits for r.r, with beta = rr_new / rr formed on the device (stage 3);
+    // level 2 also launches calc_r behind the SpMV's fold with alpha = rr / p.w formed on the device, into shadow[0],
+    // and the calc_p behind it (stage 4).  The caller's calc_xr / calc_p commit -- swap the buffers, launch nothing --
+    // when they name the same vectors and alpha / beta are bit for bit the host's quotients of the scalars handed
+    // back (and no NaN: its payload is not the same on both sides); every other entry point drops through bind().
+    // Armed by one complete iteration, run as written, whose alpha and beta were those quotients; a drop or an
+    // iteration with other scalars disarms.  Off with the speculation above and wherever x-in-SpMV is off.
+    int ahead = ABFT_AHEAD_DEFAULT;       // level; stage 3: calc_p in flight, 4: calc_r and calc_p in flight
+    bool a_armed = false;
+    bool a_alpha_ok = false;              // the calc_xr just run was handed rr / p.w on plain vectors (cleared by any entry point but calc_p)
+    double rr_prev = 0.0;                 // the scalar handed back before rr_host: beta's denominator
+    int a_slot = 0;                       // xpend.shadow[a_slot]: where the calc_p in flight writes
+    long a_commit_p = 0, a_commit_r = 0, a_drops = 0;
   } spec;
   EventRing ring{};                   // device memory
   MovedList moved{};                  // COO elements with a silently corrupted column (device memory)
@@ -264,6 +279,13 @@ static bool same_bits(double a, double b) { return memcmp(&a, &b, sizeof(a)) == 
 // already updated in place stay -- calc_xr is done; what the caller holds as r.r is the speculated one)
 static void spec_drop(abft_hip_ctx *ctx) {
   auto &S = ctx->spec;
+  S.a_alpha_ok = false;
+  if (S.stage >= 3) {  // a run-ahead: r (stage 4) and p are untouched, the scalars as the caller holds them
+    S.a_drops++;
+    S.a_armed = false;
+    S.stage = 0;
+    return;
+  }
   if (S.stage) S.drops++;
   if (S.stage == 2) {
     S.rr_at = 1 - S.rr_at;
@@ -274,6 +296,7 @@ static void spec_drop(abft_hip_ctx *ctx) {
 static void spec_forget(abft_hip_ctx *ctx) {
   spec_drop(ctx);
   ctx->spec.learned = false;
+  ctx->spec.a_armed = false;
   ctx->spec.have_rr = false;
   ctx->spec.x = ctx->spec.r = ctx->spec.p = ctx->spec.w = nullptr;
 }
@@ -445,6 +468,8 @@ extern "C" int abft_hip_init(int device, abft_hip_ctx **out) {
     if (ctx->xin_enabled) ctx->xin_modes = ~0u;
   }
   ctx->xin_enabled = ctx->xin_enabled && ctx->defer_enabled && ctx->fuse_enabled && !ctx->spec.enabled;
+  if (const char *e = getenv("ABFT_HIP_AHEAD")) ctx->spec.ahead = e[0] == '2' ? 2 : e[0] == '1' ? 1 : 0;
+  if (!ctx->xin_enabled) ctx->spec.ahead = 0;  // (it writes where xpend's calc_p writes, and commits by xpend's swap)
   HIPCHK(hipHostGetDevicePointer((void **)&ctx->host_slot_dev, ctx->host_slot, 0));
   // the queue, and behind it the table of vector events already queued (abft_internal.h)
   HIPCHK(hipMalloc((void **)&ctx->ring.buf, EVENT_CAP * sizeof(abft_event) + VECC_SEEN_BYTES));
@@ -2034,6 +2059,27 @@ static int calc_xr_launch(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector
 
 static bool spec_plain(const abft_hip_vector *v, int n);
 
+// the context's buffer for a new p of n entries -> its slot in xpend.shadow, or -1 (no memory: the path is off for good)
+static int xpend_buffer(abft_hip_ctx *ctx, int n) {
+  auto &X = ctx->xpend;
+  int at = X.shadow[0].buf && X.shadow[0].n == n ? 0 : X.shadow[1].buf && X.shadow[1].n == n ? 1 : -1;
+  if (at < 0) {  // a length seen for the first time (or a third one): the slot not used last makes room
+    at = X.shadow[X.shadow_at].buf ? 1 - X.shadow_at : X.shadow_at;
+    (void)hipFree(X.shadow[at].buf);
+    X.shadow[at].buf = nullptr;
+    X.shadow[at].n = 0;
+    if (hipMalloc((void **)&X.shadow[at].buf, ((size_t)n + 2) * sizeof(double)) != hipSuccess) {  // no room: as before
+      (void)hipGetLastError();
+      X.shadow[at].buf = nullptr;
+      ctx->xin_enabled = false;
+      return -1;
+    }
+    X.shadow[at].n = n;
+  }
+  X.shadow_at = at;
+  return at;
+}
+
 // The new p into the context's buffer, the buffers swapped, the deferred x += alpha p left pending on the old one
 // (see abft_hip_ctx::xpend).  False: not now -- the caller runs calc_px as before.
 static bool xpend_take(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, double beta, int *rc) {
@@ -2042,21 +2088,8 @@ static bool xpend_take(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vec
   if (!ctx->xin_enabled || !X.armed || X.active || ctx->defer.on_dev || ctx->capturing) return false;
   // p's handle is the only way to its buffer (a whole root vector, never exposed, no views): the swap goes unseen
   if (!spec_plain(p, p->n) || !disjoint(p, r)) return false;
-  int at = X.shadow[0].buf && X.shadow[0].n == p->n ? 0 : X.shadow[1].buf && X.shadow[1].n == p->n ? 1 : -1;
-  if (at < 0) {  // a length seen for the first time (or a third one): the slot not used last makes room
-    at = X.shadow[X.shadow_at].buf ? 1 - X.shadow_at : X.shadow_at;
-    (void)hipFree(X.shadow[at].buf);
-    X.shadow[at].buf = nullptr;
-    X.shadow[at].n = 0;
-    if (hipMalloc((void **)&X.shadow[at].buf, ((size_t)p->n + 2) * sizeof(double)) != hipSuccess) {  // no room: as before
-      (void)hipGetLastError();
-      X.shadow[at].buf = nullptr;
-      ctx->xin_enabled = false;
-      return false;
-    }
-    X.shadow[at].n = p->n;
-  }
-  X.shadow_at = at;
+  const int at = xpend_buffer(ctx, p->n);
+  if (at < 0) return false;
   {
     KernelTimer t(ctx, ABFT_K_CALC_P);
     const hipError_t e = launch_calc_p(p->d, r->d, beta, nullptr, nullptr, p->n, ctx->stream, X.shadow[at].buf);
@@ -2101,12 +2134,93 @@ static int calc_p_launch(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_v
   return ABFT_OK;
 }
 
+// ---- run-ahead (see abft_hip_ctx::spec) ----
+// the loop's four vectors: whole allocations only the library can see into, of one length, none of them twice
+static bool ahead_plain(const abft_hip_vector *x, const abft_hip_vector *r, const abft_hip_vector *p,
+                        const abft_hip_vector *w) {
+  if (!p || p->n <= 0) return false;
+  const int n = p->n;
+  return spec_plain(x, n) && spec_plain(r, n) && spec_plain(p, n) && spec_plain(w, n) && x != r && x != p && x != w &&
+         r != p && r != w && p != w;
+}
+
+// calc_p(p, r_d, beta = *num / *den) into xpend's buffer: the preconditions of xpend_take (the caller has checked the vectors)
+static bool ahead_p_launch(abft_hip_ctx *ctx, const abft_hip_vector *p, const double *r_d, const double *num,
+                           const double *den) {
+  auto &X = ctx->xpend;
+  if (!ctx->xin_enabled || !X.armed || X.active || ctx->capturing) return false;
+  const int at = xpend_buffer(ctx, p->n);
+  if (at < 0) return false;
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  if (launch_calc_p(p->d, r_d, 0.0, num, den, p->n, ctx->stream, X.shadow[at].buf) != hipSuccess) return false;
+  ctx->spec.a_slot = at;
+  return true;
+}
+
+// behind spmv(A, p, w) + fold (level 2): calc_r into the shadow with alpha = rr / p.w, calc_p from that shadow
+static void ahead_launch(abft_hip_ctx *ctx, const abft_hip_vector *vec, const abft_hip_vector *result) {
+  auto &S = ctx->spec;
+  if (S.ahead < 2 || !S.a_armed || S.stage || !S.have_rr || ctx->defer.active || ctx->capturing) return;
+  if (vec != S.p || result != S.w || !ahead_plain(S.x, S.r, S.p, S.w)) return;
+  if (!ctx->xin_enabled || !ctx->xpend.armed || ctx->xpend.active) return;
+  const int n = vec->n;
+  if (S.shadow_n != n || !S.shadow[0]) {  // r's shadow, allocated on first use
+    (void)hipFree(S.shadow[0]);
+    S.shadow[0] = nullptr;
+    S.shadow_n = 0;
+    if (hipMalloc((void **)&S.shadow[0], ((size_t)n + 2) * sizeof(double)) != hipSuccess) {  // no room: level 1
+      (void)hipGetLastError();
+      S.shadow[0] = nullptr;
+      S.ahead = 1;
+      return;
+    }
+    S.shadow_n = n;
+  }
+  if (xpend_buffer(ctx, n) < 0) return;
+  double *rr = S.scal + 2 * S.rr_at, *rr_new = S.scal + 2 * (1 - S.rr_at), *pw = S.scal + 4;
+  const ReduceOut o = reduce_out(ctx, rr_new, true);  // {r.r, events} to the host ring AND to the device
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    if (launch_calc_r(S.r->d, S.w->d, 0.0, rr, pw, nullptr, n, o, ctx->stream, S.shadow[0], S.x->d, S.p->d) != hipSuccess) return;
+  }
+  S.seq_rr = o.seq;
+  S.stage = 4;
+  if (!ahead_p_launch(ctx, S.p, S.shadow[0], rr_new, rr)) spec_drop(ctx);
+}
+
 extern "C" int abft_hip_calc_xr(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r, const abft_hip_vector *p,
                                 const abft_hip_vector *w, double alpha, double *result) {
   if (int rc = bind(ctx, false, true)) return rc;
   if (!result) { spec_drop(ctx); return set_err(ABFT_ERR_INVALID, "null result"); }
   auto &S = ctx->spec;
-  if (S.stage == 1) {
+  // was alpha the quotient of the two scalars the caller was handed -- r.r and the fused p.w of spmv(A, p, w)?
+  const bool had_rr = S.have_rr;
+  const double rr_old = S.rr_host;
+  const bool alpha_ok = S.ahead && had_rr && ctx->fused.valid && ctx->fused.have_value && !ctx->fused.vecc && p && w &&
+                        ctx->fused.x == p->d && ctx->fused.y == w->d && alpha == alpha &&
+                        same_bits(alpha, rr_old / ctx->fused.value) && ahead_plain(x, r, p, w);
+  if (S.stage == 4) {
+    // the calc_r that ran ahead is this very call: r's buffer and the shadow change places, x += alpha p is left to
+    // the calc_p as calc_xr_launch leaves it, and the calc_p behind it stays in flight
+    if (alpha_ok && x == S.x && r == S.r && p == S.p && w == S.w) {
+      double rr_new = 0.0;
+      if (int rc = scalar_from_host_slot(ctx, S.seq_rr, &rr_new)) { spec_drop(ctx); return rc; }
+      std::swap(r->d, S.shadow[0]);
+      ctx->fused.valid = false;
+      ctx->defer.active = true;
+      ctx->defer.on_dev = false;
+      ctx->defer.x = x->d; ctx->defer.p = p->d; ctx->defer.n = x->n; ctx->defer.alpha = alpha;
+      S.rr_prev = rr_old;
+      S.rr_at = 1 - S.rr_at;
+      S.rr_host = rr_new;
+      S.stage = 3;
+      S.a_alpha_ok = true;
+      S.a_commit_r++;
+      *result = rr_new;
+      return ABFT_OK;
+    }
+    spec_drop(ctx);
+  } else if (S.stage == 1) {
     // the speculated r half is this very call if it names the same vectors and alpha is, bit for bit, the quotient of
     // the two scalars the caller was (or could have been) handed: r.r and the fused p.w
     bool take = x == S.x && r == S.r && p == S.p && w == S.w && ctx->fused.valid;
@@ -2139,7 +2253,14 @@ extern "C" int abft_hip_calc_xr(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_
   const int at = S.have_rr ? 1 - S.rr_at : 0;
   const ReduceOut o = reduce_out(ctx, S.scal + 2 * at, true);
   if (int rc = calc_xr_launch(ctx, x, r, p, w, alpha, o)) { S.have_rr = false; return rc; }
+  // level 1: the calc_p that will follow, behind calc_r and before the host waits for r.r
+  if (!alpha_ok) S.a_armed = false;
+  const bool p_ahead = alpha_ok && S.a_armed && ctx->defer.active && !ctx->defer.on_dev && ctx->defer.p == p->d &&
+                       ahead_p_launch(ctx, p, r->d, S.scal + 2 * at, S.scal + 2 * S.rr_at);
   if (int rc = scalar_from_host_slot(ctx, o.seq, result)) { S.have_rr = false; return rc; }
+  if (p_ahead) S.stage = 3;
+  S.a_alpha_ok = alpha_ok;
+  S.rr_prev = rr_old;
   // what a speculation would need to know about this iteration
   S.have_rr = true; S.rr_at = at; S.rr_host = *result;
   S.x = x; S.r = r; S.p = const_cast<abft_hip_vector *>(p); S.w = const_cast<abft_hip_vector *>(w);
@@ -2158,7 +2279,26 @@ extern "C" int abft_hip_calc_xr_dev(abft_hip_ctx *ctx, abft_hip_vector *x, abft_
 extern "C" int abft_hip_calc_p(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, double beta) {
   if (int rc = bind(ctx, true, true)) return rc;
   auto &S = ctx->spec;
-  if (S.stage == 2) {
+  // was beta the quotient of the last two residuals handed back, behind a calc_xr whose alpha was its quotient?
+  const bool beta_ok = S.a_alpha_ok && p == S.p && r == S.r && beta == beta && same_bits(beta, S.rr_host / S.rr_prev) &&
+                       ahead_plain(S.x, S.r, S.p, S.w);
+  if (S.stage == 3) {
+    // the calc_p that ran ahead is this very call: what xpend_take does behind its launch, and no launch
+    auto &X = ctx->xpend;
+    if (beta_ok && ctx->defer.active && !ctx->defer.on_dev && ctx->defer.p == p->d && ctx->defer.n == p->n && !X.active) {
+      const int at = S.a_slot;
+      ctx->defer.active = false;
+      std::swap(p->d, X.shadow[at].buf);
+      X.active = true;
+      X.x = ctx->defer.x; X.p_old = X.shadow[at].buf; X.alpha = ctx->defer.alpha; X.n = p->n; X.ph = p;
+      X.last_p = p;
+      ctx->fused.valid = false;
+      S.stage = 0;
+      S.a_commit_p++;
+      return ABFT_OK;
+    }
+    spec_drop(ctx);
+  } else if (S.stage == 2) {
     // the speculated x / p half is this very call if it names p and r and beta is the quotient of the two residuals
     const bool take = p == S.p && r == S.r && same_bits(beta, S.rr_new_host / S.rr_host) && !ctx->defer.active;
     if (take) {
@@ -2176,6 +2316,7 @@ extern "C" int abft_hip_calc_p(abft_hip_ctx *ctx, abft_hip_vector *p, const abft
   // (learning: calc_p(p, r) right behind calc_xr(x, r, p, w) completes an iteration of the CG loop)
   const bool completes = S.have_rr && !S.learned && S.p == p && S.r == r && S.x && S.w;
   if (int rc = calc_p_launch(ctx, p, r, beta, nullptr, nullptr)) return rc;
+  S.a_armed = S.ahead && beta_ok;  // one complete iteration on the two quotients arms the run-ahead, any other disarms
   S.learned = completes || (S.learned && S.p == p && S.r == r);
   return ABFT_OK;
 }
@@ -2765,7 +2906,7 @@ struct HeldFold {
 // call on a plain p directly after the calc_p that took a deferred update on that p along.
 static bool xpend_predicted(abft_hip_ctx *ctx, const abft_hip_matrix *mat, const abft_hip_vector *vec,
                             const abft_hip_vector *result, const double *dev_pair, int part, int c1, bool held,
-                            bool vecc) {
+                            bool vecc, bool *eligible) {
   auto &X = ctx->xpend;
   const abft_hip_vector *after_calc_p = X.prev_p;
   X.prev_p = nullptr;
@@ -2777,6 +2918,7 @@ static bool xpend_predicted(abft_hip_ctx *ctx, const abft_hip_matrix *mat, const
   if (!mat->fuse_partials || !ctx->fuse_enabled || n == 0 || mat->csr.n_in != n || mat->csr.nblk == 0 ||
       (uint32_t)vec->n != n || (uint32_t)result->n != n || !disjoint(vec, result))
     return false;
+  *eligible = true;
   if (!X.active) {
     if (after_calc_p == vec && spec_plain(vec, vec->n)) X.armed = true;
     return false;
@@ -2792,7 +2934,8 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
                        int c0 = 0, int c1 = -1, HeldFold *hold = nullptr, bool vecc = false) {
   if (int rc = bind(ctx, false, false, true)) return rc;
   // the update pending on the old p (abft_hip_ctx::xpend): this launch applies it, or it is applied first
-  const bool absorb = xpend_predicted(ctx, mat, vec, result, dev_pair, part, c1, hold != nullptr, vecc);
+  bool absorb_ok = false;  // ... and whether this is a call that could apply one (then a run-ahead may follow it)
+  const bool absorb = xpend_predicted(ctx, mat, vec, result, dev_pair, part, c1, hold != nullptr, vecc, &absorb_ok);
   if (!absorb)
     if (int rc = flush_xpend(ctx)) return rc;
   if (!mat || !vec || !result) return set_err(ABFT_ERR_INVALID, "spmv: null argument");
@@ -2919,6 +3062,7 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
     ctx->fused.n = vec->n;
     ctx->fused.seq = fuse.seq;
     if (whole && part == ABFT_PART_ALL && !vecc) (void)spec_launch(ctx, vec, result);
+    if (absorb_ok) ahead_launch(ctx, vec, result);
   }
   return ABFT_OK;
 }
@@ -3871,6 +4015,14 @@ extern "C" int abft_hip_cg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matri
 }
 
 // what became of the x updates left pending on the old p: applied by the predicted SpMV, or on their own
+extern "C" int abft_hip_ahead_stats(abft_hip_ctx *ctx, long *committed_p, long *committed_r, long *dropped) {
+  if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");
+  if (committed_p) *committed_p = ctx->spec.a_commit_p;
+  if (committed_r) *committed_r = ctx->spec.a_commit_r;
+  if (dropped) *dropped = ctx->spec.a_drops;
+  return ABFT_OK;
+}
+
 extern "C" int abft_hip_x_in_spmv_stats(abft_hip_ctx *ctx, long *absorbed, long *flushed) {
   if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");
   if (absorbed) *absorbed = ctx->xpend.absorbed;

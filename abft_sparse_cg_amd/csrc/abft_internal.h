@@ -215,6 +215,15 @@ struct CooDev {
 #ifndef ABFT_CFG_P_OUT_NT
 #define ABFT_CFG_P_OUT_NT 1  // calc_p writing the new p into the buffer its handle swaps to (xpend): non-temporal stores
 #endif
+#ifndef ABFT_CFG_R_NT
+#define ABFT_CFG_R_NT 0  // calc_r_kernel's r store, non-temporal: bit 0 into the shadow of a run-ahead (r_out != r), bit 1 in place (profiles/r12/variants_ab.md)
+#endif
+#ifndef ABFT_CFG_Y_NT
+#define ABFT_CFG_Y_NT 0  // spmv_csr_kernel<MODE_NONE, ..., XUPD>: the y[row] store non-temporal (profiles/r12/variants_ab.md)
+#endif
+#ifndef ABFT_AHEAD_DEFAULT
+#define ABFT_AHEAD_DEFAULT 1  // run-ahead of the host-scalar loop (abft_hip.hip, spec.ahead) without ABFT_HIP_AHEAD: 0 off, 1 calc_p, 2 calc_r and calc_p -- 1: level 1 passed the rule against level 0 and the parent, level 2 did not pass it against level 1 (profiles/r12/variants_ab.md)
+#endif
 #ifndef ABFT_CFG_X_NT
 #define ABFT_CFG_X_NT 0  // calc_px: x (touched once per iteration) by non-temporal loads and stores
 #endif

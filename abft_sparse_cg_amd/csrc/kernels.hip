@@ -917,7 +917,8 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
             dsum += vecc_value(xw) * vecc_value(yw);
           }
         } else {
-          y[row] = acc;
+          if (ABFT_CFG_Y_NT && XUPD && MODE == MODE_NONE) __builtin_nontemporal_store(acc, y + row);  // w ends at the boundary calc_r waits behind
+          else y[row] = acc;
           if (FUSE) dsum += xr * acc;
         }
       }
@@ -3599,7 +3600,14 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_kernel(const double *r, con
       const double2 wv = *reinterpret_cast<const double2 *>(w + i);
 #endif
       rv.x -= alpha * wv.x; rv.y -= alpha * wv.y;
+#if ABFT_CFG_R_NT  // bit 0: the store into the shadow of a run-ahead (r_out != r), bit 1: the store in place
+      typedef double v2r __attribute__((ext_vector_type(2)));
+      if ((ABFT_CFG_R_NT & 1) && r_out != r) __builtin_nontemporal_store(v2r{rv.x, rv.y}, reinterpret_cast<v2r *>(r_out + i));
+      else if ((ABFT_CFG_R_NT & 2) && r_out == r) __builtin_nontemporal_store(v2r{rv.x, rv.y}, reinterpret_cast<v2r *>(r_out + i));
+      else *reinterpret_cast<double2 *>(r_out + i) = rv;
+#else
       *reinterpret_cast<double2 *>(r_out + i) = rv;
+#endif
       acc += rv.x * rv.x;
       acc += rv.y * rv.y;
     } else {

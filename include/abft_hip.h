@@ -631,6 +631,24 @@ int abft_hip_tail_stats(abft_hip_ctx *ctx, int *path, int *grid, int *want, long
  * the context was created (host counters; either pointer may be null). */
 int abft_hip_x_in_spmv_stats(abft_hip_ctx *ctx, long *absorbed, long *flushed);
 
+/* Run-ahead of the host-scalar loop ("Fifth cross-call fusion"; ABFT_HIP_AHEAD=0|1|2, read when
+ * the context is created).  The loop hands two scalars to the host per iteration, and the GPU runs nothing while the
+ * host forms alpha and beta from them.  Level 1: abft_hip_calc_xr launches, behind its own kernel and before it waits
+ * for r.r, the p = r + beta p of the abft_hip_calc_p that will follow, with beta = r.r_new / r.r formed on the device,
+ * into the buffer the x-in-SpMV path swaps p's with.  Level 2: abft_hip_spmv also launches, behind its fold, the
+ * r -= alpha w of the coming abft_hip_calc_xr with alpha = r.r / p.w formed on the device, into a buffer of the
+ * context's, and the level-1 kernel behind that.  The call that arrives with the same vectors and an alpha (beta) that
+ * is bit for bit the quotient of the scalars handed back -- and no NaN -- commits: the buffers change places and no
+ * kernel is launched.  Any other call drops what was launched, unread, and runs as written; the results are the same
+ * bits either way.  Armed by one complete iteration (abft_hip_spmv, abft_hip_dot(p, w), abft_hip_calc_xr,
+ * abft_hip_calc_p, nothing in between) on whole vectors that were never exposed and have no views, run as written,
+ * whose alpha and beta were the two quotients; a drop, or an iteration with other scalars, disarms until the next such
+ * iteration.  Only where the x-in-SpMV path is armed (above), and off with ABFT_HIP_SPECULATE=1.
+ * Default: level 1 (the level that was measured to pay; level 2 did not beat it: DESIGN.md section 4); ABFT_HIP_AHEAD=0 turns it off.
+ * *committed_p / *committed_r = calls of abft_hip_calc_p / abft_hip_calc_xr that took over a kernel run ahead,
+ * *dropped = run-aheads thrown away, since the context was created (host counters; any pointer may be null). */
+int abft_hip_ahead_stats(abft_hip_ctx *ctx, long *committed_p, long *committed_r, long *dropped);
+
 /* The guarded iteration: abft_hip_cg_iteration_dev behind the stop test of the reference loop (cg.cpp:94,
  * `while (rr > conv)`), evaluated ON THE DEVICE, so that a loop with a convergence threshold can enqueue
  * (or replay from a graph) several iterations and look at the scalars once per batch: iterations enqueued

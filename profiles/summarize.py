@@ -3,10 +3,13 @@
 
     python profiles/summarize.py trace  <dir> <out.md>      # --kernel-trace --stats run
     python profiles/summarize.py pmc    <dir> <out.json>    # one --pmc run (any counters)
+    python profiles/summarize.py gaps   <dir> <out.md>      # --kernel-trace run: idle time between kernels
 
 trace: per kernel name, launches / total / average / min / max duration (ns from
 the kernel-trace CSV's Start_Timestamp / End_Timestamp).
 pmc:   per kernel name and counter, the average value per launch.
+gaps:  the dispatches in start order; per pair (kernel, the kernel that starts next), the mean and median
+       of start(next) - end(previous), and what the pairs add up to per launch of the most frequent kernel.
 """
 import csv
 import glob
@@ -38,6 +41,29 @@ def trace(d, out):
         for k, v in sorted(rows.items(), key=lambda kv: -sum(kv[1])):
             o.write("| `%s` | %d | %.3f | %.2f | %.2f | %.2f | %.1f |\n" % (
                 k, len(v), sum(v) / 1e6, sum(v) / len(v) / 1e3, min(v) / 1e3, max(v) / 1e3, 100.0 * sum(v) / tot))
+    print(open(out).read())
+
+
+def gaps(d, out, min_share=0.02):
+    """pairs seen less often than min_share of all dispatches (set-up, the drain at the end) are left out"""
+    rows = []
+    for f in find(d, "*kernel_trace.csv"):
+        for r in csv.DictReader(open(f)):
+            rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"])))
+    rows.sort()
+    pairs = defaultdict(list)
+    for (s0, e0, k0), (s1, e1, k1) in zip(rows, rows[1:]):
+        pairs[(k0, k1)].append(s1 - e0)
+    keep = {k: sorted(v) for k, v in pairs.items() if len(v) >= min_share * len(rows)}
+    per_iter = max((len(v) for v in keep.values()), default=1)
+    with open(out, "w") as o:
+        o.write("| kernel | next kernel | pairs | mean gap us | median us | us per iteration |\n|---|---|---|---|---|---|\n")
+        total = 0.0
+        for (k0, k1), v in sorted(keep.items(), key=lambda kv: -sum(kv[1])):
+            total += sum(v) / per_iter / 1e3
+            o.write("| `%s` | `%s` | %d | %.2f | %.2f | %.2f |\n" % (
+                k0, k1, len(v), sum(v) / len(v) / 1e3, v[len(v) // 2] / 1e3, sum(v) / per_iter / 1e3))
+        o.write("\nidle between kernels: %.2f us per iteration (%d iterations)\n" % (total, per_iter))
     print(open(out).read())
 
 
@@ -82,4 +108,4 @@ if __name__ == "__main__":
     if sys.argv[1] == "pmc_phases":
         pmc_phases(*sys.argv[2:6])
     else:
-        {"trace": trace, "pmc": pmc}[sys.argv[1]](sys.argv[2], sys.argv[3])
+        {"trace": trace, "pmc": pmc, "gaps": gaps}[sys.argv[1]](sys.argv[2], sys.argv[3])
