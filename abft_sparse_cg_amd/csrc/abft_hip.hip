@@ -2223,7 +2223,8 @@ extern "C" int abft_hip_calc_xr(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_
   } else if (S.stage == 1) {
     // the speculated r half is this very call if it names the same vectors and alpha is, bit for bit, the quotient of
     // the two scalars the caller was (or could have been) handed: r.r and the fused p.w
-    bool take = x == S.x && r == S.r && p == S.p && w == S.w && ctx->fused.valid;
+    // (a view made since the launch -- abft_hip_vector_view drops nothing -- looks into r's buffer: no swap behind it)
+    bool take = x == S.x && r == S.r && p == S.p && w == S.w && ctx->fused.valid && spec_plain(r, r->n);
     if (take && !ctx->fused.have_value) {
       take = scalar_from_host_slot(ctx, ctx->fused.seq, &ctx->fused.value) == ABFT_OK;
       ctx->fused.have_value = take;
@@ -2300,7 +2301,9 @@ extern "C" int abft_hip_calc_p(abft_hip_ctx *ctx, abft_hip_vector *p, const abft
     spec_drop(ctx);
   } else if (S.stage == 2) {
     // the speculated x / p half is this very call if it names p and r and beta is the quotient of the two residuals
-    const bool take = p == S.p && r == S.r && same_bits(beta, S.rr_new_host / S.rr_host) && !ctx->defer.active;
+    // (p must still be a vector only the library sees into: a view of it may have been made since calc_xr)
+    const bool take = p == S.p && r == S.r && same_bits(beta, S.rr_new_host / S.rr_host) && !ctx->defer.active &&
+                      spec_plain(p, p->n);
     if (take) {
       std::swap(p->d, S.shadow[1]);
       ctx->fused.valid = false;

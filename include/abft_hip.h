@@ -582,8 +582,10 @@ int abft_hip_spmv_dot_range_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const a
  * that arrives with the same vectors and a bit-identical alpha takes it over (r's buffer and the shadow are swapped, no
  * launch, the GPU did not wait for the scalar's round trip) and at once enqueues the x / p half (x in place -- it is
  * due --, p with beta = r.r_new / r.r into a shadow), which calc_p takes over likewise; anything else drops the
- * shadows and runs the call as written.  The results are the same bits either way.  This reports how often a
- * speculated iteration was taken over / dropped. */
+ * shadows and runs the call as written.  A view made of r or p while a half is in flight (abft_hip_vector_view drops
+ * nothing itself) makes the call that would have swapped that vector's buffer drop the half instead: no buffer changes
+ * places behind a view.  The results are the same bits either way.  This reports how often a speculated iteration was
+ * taken over / dropped. */
 int abft_hip_speculation_stats(abft_hip_ctx *ctx, long *taken, long *dropped);
 
 /* `processes` processes drive this library on the context's device at the same time (ranks sharing one GPU:

@@ -3,7 +3,11 @@ classified with the generator's own model -- every class the campaign's summary 
 reached by at least one eligible case in ten, so that a 20-second run on the GPU cannot miss one --
 its "every block packs" / "no block packs" marks against a plain evaluation of the two one-sided
 rules, and the oracle on every mode-none case (no case of that mode is left out of the comparison).
-The library is not imported."""
+The library is not imported.
+
+The CG-loop family (fuzz_gen.loop_case, played by tools/fuzz_loop.py): same seed same case, well-formed scripts, and --
+over exactly the seeds tests/test_gpu_fuzz.py plays -- the coverage conditions on its structural tags, and its injects
+against the oracle alone."""
 import os
 import sys
 
@@ -175,3 +179,99 @@ def test_other_modes_are_not_mostly_skipped(cases):
                 break
         o.close()
     assert fatal <= 0.35 * len(other), (fatal, len(other))
+
+
+# ---------------------------------------------------------------- the CG-loop family --
+
+@pytest.fixture(scope="module")
+def loops():
+    return [fuzz_gen.loop_case(s) for s in fuzz_gen.LOOP_SEEDS]
+
+
+def test_loop_blocks_cover_the_seed_range():
+    assert len(fuzz_gen.LOOP_SEEDS) % fuzz_gen.LOOP_BLOCK == 0
+
+
+def test_loop_same_seed_same_case():
+    a, b = fuzz_gen.loop_case(23), fuzz_gen.loop_case(23)
+    assert (a.mode, a.solves, a.script, a.iterations, a.tags) == (b.mode, b.solves, b.script, b.iterations, b.tags)
+    assert fuzz_gen.loop_case(24).script != a.script
+
+
+def test_loop_cases_are_well_formed(loops):
+    for c in loops:
+        assert c.mode in fuzz_gen.MODES and 1 <= len(c.solves) <= 3
+        lengths = [v["n"] for v in c.solves]
+        assert len(set(lengths)) == len(lengths) or (len(lengths) == 2 and lengths[0] == lengths[1]), c.seed
+        for v in c.solves:
+            cols, rows, vals, n = fuzz_gen.loop_matrix(v["spec"])
+            assert (n, len(vals)) == (v["n"], v["nnz"]) and 1 <= n <= 3001
+            assert v["scale"] in [0] + fuzz_gen.LOOP_SCALES
+        # every solve's calls come in the loop's order, whatever lies between them
+        at = {s: 0 for s in range(len(c.solves))}
+        done = 0
+        for item in c.script:
+            s = item[1]
+            assert 0 <= s < len(c.solves)
+            if item[0] == "extra":
+                assert item[2] in fuzz_gen.LOOP_EXTRAS and item[4] == at[s], (c.seed, item)
+                if item[2] == "inject":
+                    assert c.mode in fuzz_gen.INJECT_MODES
+                    i, bits = item[3]
+                    assert 0 <= i < c.solves[s]["nnz"] and bits and all(0 <= b < 96 for b in bits)
+                    assert c.mode == "none" or len(bits) == 1
+                continue
+            name = "dot" if item[0] == "dot_copies" else item[0]
+            assert fuzz_gen.LOOP_MAIN[at[s]] == name, (c.seed, item)
+            if name in ("calc_xr", "calc_p"):
+                assert (item[2] == "q" and item[3] in (-1, 0, 1)) or (item[2] == "c" and np.isfinite(item[3]))
+            at[s] = (at[s] + 1) % 4
+            done += name == "calc_p"
+        assert all(v == 0 for v in at.values()), c.seed  # no iteration left open
+        assert done == c.iterations and 10 <= c.iterations <= 40, (c.seed, c.iterations)
+
+
+def test_loop_coverage_over_the_seeds_the_gpu_test_plays(loops):
+    n = len(loops)
+    assert 3 * sum(c.tags["must_commit"] for c in loops) >= n
+    for kind in fuzz_gen.LOOP_EXTRAS:
+        for gap in range(4):
+            have = sum((kind, gap) in c.tags["in_flight"] for c in loops)
+            assert have >= 3, (kind, gap, have)
+    for tag in ("three_lengths", "same_length_pair", "switch_inside", "event_every_spmv", "plain_loop"):
+        assert sum(bool(c.tags[tag]) for c in loops) >= 3, tag
+    for e in fuzz_gen.LOOP_SCALES:
+        assert sum(e in c.tags["scaled"] for c in loops) >= 3, e
+    assert {c.mode for c in loops} == set(fuzz_gen.MODES)
+    # stretches of three and more undisturbed iterations are common, and so are disturbed ones
+    assert sum(len(c.tags["in_flight"]) for c in loops) >= 2 * n
+
+
+def test_loop_injects_against_the_oracle(loops):
+    """the oracle alone: a single-bit flip in an ECC mode is corrected (one event, not fatal, gone at the next SpMV),
+    a flip in mode none is silent, and the order violation of a constraints case is reported at every SpMV"""
+    seen = {m: 0 for m in fuzz_gen.INJECT_MODES}
+    for c in loops:
+        flips = [(i[1], i[3]) for i in c.script if i[0] == "extra" and i[2] == "inject"]
+        assert bool(c.tags["event_every_spmv"]) == (c.mode == "constraints" and bool(flips))
+        for s, v in enumerate(c.solves):
+            mine = [f for t, f in flips if t == s]
+            if not mine:
+                continue
+            cols, rows, vals, n = fuzz_gen.loop_matrix(v["spec"])
+            o = OracleMatrix(CSR, c.mode, cols, rows, vals, n)
+            x = np.ones(n)
+            for i, bits in mine:
+                o.inject(i, list(bits))
+                seen[c.mode] += 1
+            for stage in range(2):
+                o.spmv(x)
+                ev, fatal = o.events()
+                if c.mode == "none":
+                    assert (ev, fatal) == ([], False)
+                elif c.mode == "constraints":
+                    assert len(mine) == 1 and fatal and [e[:2] for e in ev] == [(8, mine[0][0])], (c.seed, ev)
+                else:
+                    assert not fatal and len(ev) == (len(mine) if stage == 0 else 0), (c.seed, c.mode, stage, ev)
+            o.close()
+    assert all(v >= 3 for v in seen.values()), seen

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import _ahead as H
 from _oracle import laplace5, random_spd
 
 pytestmark = pytest.mark.gpu
@@ -106,3 +107,39 @@ def test_speculation_keeps_out_of_the_way(monkeypatch):
     it, rr = amd.cg_solve(ctx, A, b, x, r, p, w, max_itrs=12, conv_threshold=0.0)
     assert it == 12 and stats(ctx) == (0, 0)
     ctx.close()
+
+
+# what tests/test_gpu_ahead.py puts between calc_xr and calc_p, here with the speculated x / p half in flight
+EXTRAS = {
+    "upload r": [("upload", "r")],
+    "copy r <- q": [("copy", "r", "q")],
+    "view of p": [("view", "p")],
+    "pointer of r": [("ptr", "r")],
+    "graph_begin": [("graph",)],
+    "calc_xr again": [("calc_xr",)],
+    "destroy p": [("destroy", "p")],
+}
+
+
+@pytest.mark.parametrize("what", sorted(EXTRAS))
+def test_extra_call_between_calc_xr_and_calc_p(what, monkeypatch):
+    """iteration 4 of 9 on lap40: calc_xr has taken the speculated r half over and the x / p half is in flight when
+    the extra call arrives.  Same bits as without the switch -- also through a view made there, which a swap of p's
+    buffer behind it would leave looking at the old p -- and the speculation counted as dropped"""
+    import abft_sparse_cg_amd as amd
+    for name in ("ABFT_HIP_X_IN_SPMV", "ABFT_HIP_AHEAD"):
+        monkeypatch.delenv(name, raising=False)
+    script = H.predicted(9)
+    script[3] = {"before_p": EXTRAS[what]}
+    res = {}
+    for switch in "01":
+        monkeypatch.setenv("ABFT_HIP_SPECULATE", switch)
+        res[switch] = H.run(amd, "none", H.matrix("lap40"), script)
+    assert res["0"]["spec"] == (0, 0)
+    H.same(res["1"], res["0"])
+    assert len(res["1"].get("views", [])) == len(res["0"].get("views", [])) == (1 if what == "view of p" else 0)
+    for a, b in zip(res["1"].get("views", []), res["0"].get("views", [])):
+        assert np.array_equal(bits(a), bits(b))
+        assert np.array_equal(bits(a), bits(res["1"]["vectors"]["p"]))
+    taken, dropped = res["1"]["spec"]
+    assert taken >= 2 and dropped >= 1, (taken, dropped)  # iterations 2 and 3 were taken over, 4 was not

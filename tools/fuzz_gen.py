@@ -515,3 +515,324 @@ def packed_case(seed):
             c.spmm_k = int(rng.integers(2, 9))
             c.classes.add("spmm")
     return c
+
+
+# ------------------------------------------------- third family: CG-shaped call sequences --
+# tools/fuzz_loop.py plays these.  A case is one context: one to three solves (a matrix, the loop's x r p w, the
+# spares q s t u, the right-hand side b), a mode, and a flat script of calls.  The script's items:
+#     ("spmv", s)  ("dot", s) | ("dot_copies", s)  ("calc_xr", s, how, v)  ("calc_p", s, how, v)
+#         the four calls of an iteration of solve s.  how "q": the quotient of the scalars handed back, moved by v
+#         ulps; how "c": the constant v.  dot_copies: p.w from dot(q, s) of copies q <- p, s <- w, no dot(p, w).
+#     ("extra", s, kind, args, gap)
+#         one more call on solve s's vectors in front of call number `gap` of its iteration (gap 0: between two
+#         iterations).  LOOP_EXTRAS names the kinds; what each does, and to the model, is fuzz_loop.Player.extra.
+# `tags` are computed from the script alone (loop_tags): what the script must reach whatever the library does.
+
+LOOP_EXTRAS = ["download", "upload", "copy_in", "copy_out", "map_unmap", "view", "ptr", "dot", "dot_rr", "dot_pw",
+               "spmv_other", "spmv_second", "calc_xr_again", "calc_p_other", "drain", "synchronize", "residual_gap",
+               "block", "precond", "profile", "graph", "respare", "inject"]
+LOOP_SCALES = [480, -480, -530]  # powers of two: r.r near 2^960 and 2^-960 (normal), r.r and p.w subnormal
+LOOP_NAMED = ["one", "lap3", "diag23", "diag1", "arrow", "holes"]
+LOOP_MAIN = ["spmv", "dot", "calc_xr", "calc_p"]
+INJECT_MODES = ["none", "constraints", "sec7", "sec8", "secded"]  # (sed only detects: fatal)
+# the seeds tests/test_gpu_fuzz.py plays, in blocks of LOOP_BLOCK per child process; tests/test_fuzz_generator.py holds the
+# coverage conditions over exactly these
+LOOP_SEEDS = range(1, 193)
+LOOP_BLOCK = 48
+
+
+class LoopCase:
+    """seed, mode, solves [dict(spec, n, nnz, scale, rhs_seed)], script, iterations, tags (loop_tags)"""
+
+
+def loop_matrix(spec):
+    """-> (cols, rows, vals, n) of a solve's matrix spec"""
+    from _matrices import matrix
+    from _oracle import laplace5, random_spd
+    if spec[0] == "laplace5":
+        return laplace5(spec[1], spec[2])
+    if spec[0] == "random_spd":
+        return random_spd(spec[1], spec[2], seed=spec[3])
+    return matrix(spec[1])
+
+
+def _loop_spec(rng):
+    what = rng.random()
+    if what < 0.4:
+        return ("laplace5", int(rng.integers(3, 41)), int(rng.integers(3, 41)))
+    if what < 0.7:
+        return ("random_spd", int(rng.choice([50, 300, 2000, 3001])), int(rng.integers(2, 12)), int(rng.integers(0, 1000)))
+    return ("named", str(rng.choice(LOOP_NAMED)))
+
+
+def _slow(spec):
+    """CG on it neither converges to an exact zero nor leaves the normal range within 40 iterations from a right-hand
+    side of scale 1 (Laplacians of 8 x 8 and more, the diagonally dominant random matrices, arrow, holes)"""
+    if spec[0] == "laplace5":
+        return min(spec[1], spec[2]) >= 8
+    return spec[0] == "random_spd" or spec[1] in ("arrow", "holes")
+
+
+def _order_flip(rng, cols, rowptr, n):
+    """constraints mode: (element, [bit]) -- one column bit that lifts a column to or past its row successor's, inside
+    the vector (the order check fails at that element at every SpMV from then on) -- or None"""
+    nnz = len(cols)
+    for _ in range(200):
+        i = int(rng.integers(0, max(1, nnz - 1)))
+        r = int(np.searchsorted(rowptr, i, side="right")) - 1
+        if i + 1 >= int(rowptr[r + 1]):
+            continue
+        for b in rng.permutation(max(1, int(n).bit_length())):
+            new = int(cols[i]) ^ (1 << int(b))
+            if int(cols[i + 1]) <= new < n:
+                return i, [64 + int(b)]
+    return None
+
+
+def loop_tags(c):
+    """The structural tags of a case, from its script alone.
+    clean iteration: the four calls of one solve as written -- quotients, no extra call, no call of another solve
+    since the solve's previous iteration began -- on vectors only the library sees into (no pointer read so far, no
+    capture so far), with no event due at its SpMV.  in_flight: (kind, gap) of every extra call that is the first
+    disturbance behind two clean iterations of its solve.  must_commit: three clean iterations of one solve in a row
+    whose scalars are sure to be normal numbers (`steady`: a matrix CG neither finishes nor overflows on within 40
+    iterations; at 2^+-480 only the first six iterations of an undisturbed solve; never at 2^-530).  plain_loop: one
+    solve, scale 1, no extra call -- the counters are those of the arming rule (tests/_ahead.py: expected)."""
+    mode, S = c.mode, range(len(c.solves))
+    run_s, run_len, run_steady = None, 0, 0
+    open_it, pre_dirty = {}, {s: False for s in S}
+    exposed, pristine = {s: False for s in S}, {s: True for s in S}
+    pending, standing, count = {s: False for s in S}, {s: False for s in S}, {s: 0 for s in S}
+    graph_seen = False
+    tags = dict(must_commit=False, in_flight=[], switch_inside=False, event_every_spmv=False)
+
+    def calm(s):
+        return not (exposed[s] or graph_seen or standing[s])
+
+    def steady(s):
+        v = c.solves[s]
+        if not _slow(v["spec"]):
+            return False
+        return v["scale"] == 0 or (abs(v["scale"]) == 480 and pristine[s] and count[s] < 6)
+
+    for item in c.script:
+        s = item[1]
+        others = [t for t in open_it if t != s]
+        if others:
+            tags["switch_inside"] = True
+            for t in open_it:
+                open_it[t] = True
+            run_len = run_steady = 0
+        if item[0] == "extra":
+            kind, args, gap = item[2], item[3], item[4]
+            dirty = open_it[s] if s in open_it else pre_dirty[s]
+            if run_s == s and run_len >= 2 and not others and not dirty and calm(s):
+                tags["in_flight"].append((kind, gap))
+            if s in open_it:
+                open_it[s] = True
+            else:
+                pre_dirty[s] = True
+            pristine[s] = False
+            if kind == "ptr" and args[0] in "xrpw":
+                exposed[s] = True
+            if kind == "graph":
+                graph_seen = True
+            if kind == "inject" and mode != "none":
+                pending[s] = True
+                if mode == "constraints":
+                    standing[s] = True
+                    tags["event_every_spmv"] = True
+            continue
+        op = LOOP_MAIN.index("dot" if item[0] == "dot_copies" else item[0])
+        if op == 0:
+            if run_s != s:
+                run_s, run_len, run_steady = s, 0, 0
+            open_it[s] = bool(others) or pre_dirty[s] or not calm(s) or pending[s]
+            if not steady(s):
+                run_steady = 0
+            pre_dirty[s] = False
+            pending[s] = standing[s]
+        if item[0] == "dot_copies" or (op >= 2 and (item[2], item[3]) != ("q", 0)):
+            open_it[s] = True
+        if op == 3:
+            if open_it.pop(s):
+                run_len = run_steady = 0
+                pristine[s] = False
+            else:
+                run_len += 1
+                run_steady += 1
+                if run_steady >= 3:
+                    tags["must_commit"] = True
+            count[s] += 1
+    lengths = [v["n"] for v in c.solves]
+    tags["three_lengths"] = len(set(lengths)) == 3
+    tags["same_length_pair"] = len(lengths) == 2 and lengths[0] == lengths[1]
+    tags["scaled"] = sorted(set(v["scale"] for v in c.solves if v["scale"]))
+    tags["plain_loop"] = len(c.solves) == 1 and not tags["scaled"] and not any(i[0] == "extra" for i in c.script)
+    tags["in_flight"] = sorted(set(tags["in_flight"]))
+    return tags
+
+
+def loop_case(seed):
+    """case `seed` of the CG-loop family (its own seed space)"""
+    rng = np.random.default_rng([0xC6100, int(seed)])
+    c = LoopCase()
+    c.seed = int(seed)
+    c.mode = str(rng.choice(MODES))
+    # three extra calls the case is built around: the (kind, gap) pairs come round with the seeds
+    npairs = 4 * len(LOOP_EXTRAS)
+    focus = [divmod((3 * int(seed) + 31 * j) % npairs, 4) for j in range(3)]  # (31: three kinds far apart)
+    focus = [(LOOP_EXTRAS[k], g) for k, g in focus]
+    plain = int(seed) % 12 == 0  # one solve, scale 1, scalars perturbed, no extra call
+    if plain:
+        focus = []
+    if c.mode == "sed" and any(k == "inject" for k, _ in focus):
+        c.mode = "secded"
+    # the solves: one; two of equal length; two of different lengths; three of different lengths
+    pattern = "one" if plain else str(rng.choice(["one"] * 9 + ["equal"] * 3 + ["two"] * 4 + ["three"] * 4))
+    specs = [_loop_spec(rng)]
+    if pattern == "equal":
+        a = specs[0]
+        twin = {"diag1": "diag23", "diag23": "diag1"}
+        specs.append(("laplace5", a[2], a[1]) if a[0] == "laplace5" and rng.random() < 0.5 else
+                     ("named", twin[a[1]]) if a[0] == "named" and a[1] in twin else a)
+    while len(specs) < {"one": 1, "equal": 2, "two": 2, "three": 3}[pattern]:
+        b = _loop_spec(rng)
+        if all(loop_matrix(b)[3] != loop_matrix(a)[3] for a in specs):
+            specs.append(b)
+    scale = 0 if rng.random() < 0.7 or plain else int(rng.choice(LOOP_SCALES))
+    c.solves, mats = [], []
+    for spec in specs:
+        cols, rows, vals, n = loop_matrix(spec)
+        mats.append(dict(cols=cols.astype(np.int64), vb=vals.view(np.uint64).copy(), n=n, done=[], used=set(),
+                         rowptr=np.searchsorted(rows, np.arange(n + 1)), standing=False))
+        c.solves.append(dict(spec=spec, n=int(n), nnz=int(len(vals)), scale=scale if rng.random() < 0.8 else 0,
+                             rhs_seed=int(rng.integers(0, 1 << 30))))
+    ns = len(c.solves)
+
+    def extra(s, kind, gap):
+        """-> the script item (an inject that cannot be made becomes a drain)"""
+        m, pick = mats[s], lambda names: str(rng.choice(list(names)))
+        args = ()
+        if kind in ("download", "map_unmap", "view"):
+            args = (pick("xrpwqs"),)
+        elif kind == "upload":
+            args = (pick("xrpwq"), int(rng.integers(0, 1 << 30)))
+        elif kind == "copy_in":
+            args = (pick("xrpw"), pick("qs"))
+        elif kind == "copy_out":
+            args = (pick("qs"), pick("xrpw"))
+        elif kind == "ptr":
+            args = (pick("qstub") if rng.random() < 0.7 else pick("xrpw"),)
+        elif kind == "dot":
+            args = (pick("xrpwqs"), pick("xrpwqs"))
+        elif kind == "spmv_other":
+            args = [("q", "s"), ("r", "s"), ("p", "s"), ("x", "u"), ("q", "w"), ("w", "t")][int(rng.integers(0, 6))]
+        elif kind == "spmv_second":
+            args = (pick(["coo", "sweep", "panels"]), pick("pq"), "s")
+        elif kind == "calc_p_other":
+            args = (("q", "r") if rng.random() < 0.5 else ("p", "q")) + (float(rng.choice([0.5, -0.25, 0.0, 1.0])),)
+        elif kind == "block":
+            args = (int(rng.integers(2, 5)), int(rng.integers(0, 1 << 30)))
+        elif kind == "precond":
+            args = (float(rng.choice([0.37, -0.5, 0.0])), float(rng.choice([0.61, 1.0, 0.0])))
+        elif kind == "respare":
+            args = (int(rng.integers(0, 1 << 30)),)
+        elif kind == "inject":
+            flip = None
+            if c.mode == "none":
+                i = int(rng.integers(0, len(m["vb"])))
+                i, bits = sequence_flip(rng, m["cols"], m["vb"], i, m["n"], m["done"])
+                for b in bits:
+                    if b < 64:
+                        m["vb"][i] ^= np.uint64(1) << np.uint64(b)
+                    else:
+                        m["cols"][i] ^= 1 << (b - 64)
+                m["done"].append((i, bits))
+                flip = (int(i), [int(b) for b in bits])
+            elif c.mode == "constraints":
+                if not m["standing"]:  # one violation per matrix: it stays
+                    flip = _order_flip(rng, m["cols"], m["rowptr"], m["n"])
+                    m["standing"] = flip is not None
+            elif c.mode in INJECT_MODES:
+                i = int(rng.integers(0, len(m["vb"])))
+                if i not in m["used"]:  # a second flip in one codeword would be a double-bit error
+                    m["used"].add(i)
+                    flip = (i, [int(rng.integers(0, NBITS[CSR]))])
+            if flip is None:
+                kind = "drain"
+            else:
+                args = (flip[0], tuple(flip[1]))
+        return ("extra", s, kind, tuple(args), gap)
+
+    def iteration(s, what=None, plant=None):
+        """the items of one iteration of solve s -> [[items before and with call 0], ..., [... call 3]]"""
+        what = what if what is not None else str(rng.choice(["clean"] * 12 + ["alpha_ulp", "beta_ulp", "alpha_const",
+                                                                              "beta_const", "nodot"] + ([] if plain else ["extras"] * 3)))
+        calls = [[("spmv", s)], [("dot", s)], [("calc_xr", s, "q", 0)], [("calc_p", s, "q", 0)]]
+        if what == "alpha_ulp":
+            calls[2] = [("calc_xr", s, "q", int(rng.choice([-1, 1])))]
+        elif what == "beta_ulp":
+            calls[3] = [("calc_p", s, "q", int(rng.choice([-1, 1])))]
+        elif what == "alpha_const":
+            calls[2] = [("calc_xr", s, "c", float(rng.choice([0.0, 0.37, -0.5])))]
+        elif what == "beta_const":
+            calls[3] = [("calc_p", s, "c", float(rng.choice([0.0, 0.61, 1.0])))]
+        elif what == "nodot":
+            calls[1] = [("dot_copies", s)]
+        elif what == "extras":
+            for _ in range(int(rng.integers(1, 4))):
+                g = int(rng.integers(0, 4))
+                kind = str(rng.choice(LOOP_EXTRAS))
+                if kind == "graph" and rng.random() < 0.7:  # (the first capture ends x-in-SpMV for the context)
+                    kind = "synchronize"
+                calls[g].insert(len(calls[g]) - 1, extra(s, kind, g))
+        if plant:
+            calls[plant[1]].insert(0, extra(s, plant[0], plant[1]))
+        return calls
+
+    # stretches of whole iterations of one solve, the solves taking turns; two of them end in a planted extra call
+    # behind two clean iterations, some are three clean iterations, some interleave two solves inside an iteration
+    kinds = ["plant%d" % j for j in range(len(focus))] + (["commit"] if rng.random() < 0.6 else []) + \
+            ["free"] * int(rng.integers(1 if plain else 0, 5))
+    if ns > 1:
+        kinds += ["inside"] * int(rng.integers(0, 3))
+    kinds = [kinds[i] for i in rng.permutation(len(kinds))]
+    last = [k for k in kinds if k.startswith("plant") and focus[int(k[-1])][0] == "graph"]  # (nothing is in flight behind it)
+    kinds = [k for k in kinds if k not in last] + last
+    c.script, total, s = [], 0, int(rng.integers(0, ns))
+    if c.mode == "constraints" and not plain and rng.random() < 0.5:  # a violation that stands from the start
+        c.script.append(extra(s, "inject", 0))
+    for kind in kinds:
+        s = (s + int(rng.integers(1, ns))) % ns if ns > 1 else 0
+        if kind.startswith("plant"):
+            its = [iteration(s, "clean"), iteration(s, "clean"), iteration(s, "clean", focus[int(kind[-1])])]
+        elif kind == "commit":
+            its = [iteration(s, "clean") for _ in range(3)]
+        elif kind == "inside":
+            # solve s up to call g, then solve t: whole iterations, or up to its call h, s's rest, t's rest
+            t, g = (s + int(rng.integers(1, ns))) % ns, int(rng.integers(1, 4))
+            a = iteration(s)
+            if rng.random() < 0.5:
+                inner = [x for _ in range(int(rng.integers(1, 3))) for call in iteration(t) for x in call]
+                flat = [x for call in a[:g] for x in call] + inner + [x for call in a[g:] for x in call]
+                total += 1 + sum(1 for x in inner if x[0] == "spmv")
+            else:
+                b, h = iteration(t), int(rng.integers(1, 4))
+                flat = [x for call in a[:g] for x in call] + [x for call in b[:h] for x in call] + \
+                       [x for call in a[g:] for x in call] + [x for call in b[h:] for x in call]
+                total += 2
+            c.script += flat
+            continue
+        else:
+            its = [iteration(s) for _ in range(int(rng.integers(1, 7)))]
+        if total + len(its) > 40:
+            continue
+        total += len(its)
+        c.script += [x for it in its for call in it for x in call]
+    while total < 10:
+        c.script += [x for call in iteration(s) for x in call]
+        total += 1
+    c.iterations = total
+    c.tags = loop_tags(c)
+    return c
