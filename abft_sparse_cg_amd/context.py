@@ -567,6 +567,18 @@ class HIPContext:
                                                      base + 8 * rr_at, base + 8 * pw_at, base + 8 * rr_new_at,
                                                      threshold))
 
+    def pcg_iteration_until_dev(self, mat, vec, x, r, p, w, dinv, scalars, in_at, pw_at, out_at, threshold,
+                                vec_offset=0, part=capi.PART_ALL):
+        """one guarded Jacobi-preconditioned CG iteration, enqueue-only (abft_hip_pcg_iteration_until_dev; DESIGN.md
+        section 5g): live when scalars[in_at] > threshold on the device, else frozen.  scalars: a vector of device
+        doubles; in_at, out_at: where the records {r.r, events, r.z, 0.0} read and written start in it, pw_at: where
+        the pair {p.w, events} goes.  Under graph capture the context must have made a preconditioned call before
+        (precond_start): see the header"""
+        base = scalars.device_ptr
+        check(self.L.abft_hip_pcg_iteration_until_dev(self.h, mat.h, vec.h, vec_offset, part, x.h, r.h, p.h, w.h,
+                                                      dinv.h, base + 8 * in_at, base + 8 * pw_at, base + 8 * out_at,
+                                                      threshold))
+
     def graph_begin(self):
         """start capturing the asynchronous calls on the context's stream (include/abft_hip.h, graph replay)"""
         check(self.L.abft_hip_graph_begin(self.h))
@@ -773,7 +785,7 @@ DEFAULT_STRIDE = 16
 
 
 def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
-                    stride=DEFAULT_STRIDE, graph=True):
+                    stride=DEFAULT_STRIDE, graph=True, precond=None):
     """cg_solve's loop (cg.cpp:87-118) with alpha, beta and the stop test on the device:
     the host looks at the scalars once per batch of `stride` iterations instead of twice per iteration.
 
@@ -790,28 +802,45 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
     on_iteration(itr, rr) is called for every live iteration in order, but AFTER its batch: the vectors it sees
     are the batch's end state, not that iteration's.  -> (itr, rr) as cg_solve: the count of live iterations and
     the last live r.r (a frozen tail costs at most stride - 1 SpMVs per solve, plus one batch when the loop
-    stops on a batch's last iteration before max_itrs)."""
+    stops on a batch's last iteration before max_itrs).
+
+    precond: a vector dinv (ctx.jacobi(A)) makes it cg_solve(precond=dinv)'s loop: r <- b and
+    rz, rr0 = precond_start(r, dinv, p) as there, then batches of ctx.pcg_iteration_until_dev over a trail of
+    stride + 1 records of four doubles {r.r, events, r.z, 0.0} -- record k at 4 k, the pair p.w behind them at
+    4 (stride + 1), record `stride` seeded with {rr0, 0, rz, 0}.  Batches, the graph, the download, events, callbacks
+    and the return value are as above; the stop test stays on r.r.  With precond=None the calls and the trail are
+    exactly those made without the argument."""
     if int(stride) != stride or stride < 1:
         raise ValueError("stride must be a whole number >= 1, not %r" % (stride,))
     stride = int(stride)
     ctx.copy_vector(r, b)
-    ctx.copy_vector(p, r)
-    rr = ctx.dot(r, r)
+    if precond is None:
+        ctx.copy_vector(p, r)
+        rr = ctx.dot(r, r)
+        rec = 2  # doubles per record of the trail: the pair {r.r, events}
+    else:
+        rz, rr = ctx.precond_start(r, precond, p)
+        rec = 4  # {r.r, events, r.z, 0.0}
     noted = {}
     note_threshold(rr, conv_threshold, noted)
     if max_itrs == 0 or not (rr > conv_threshold):
         return 0, rr
-    pw_at = 2 * (stride + 1)
+    pw_at = rec * (stride + 1)
     trail = ctx.create_vector(pw_at + 2)
-    first, last = ctx.view_vector(trail, 0, 2), ctx.view_vector(trail, 2 * stride, 2)
+    first, last = ctx.view_vector(trail, 0, rec), ctx.view_vector(trail, rec * stride, rec)
     start = np.zeros(pw_at + 2)
-    start[2 * stride] = rr  # where the first batch's copy finds it
+    start[rec * stride] = rr  # where the first batch's copy finds it
+    if precond is not None:
+        start[rec * stride + 2] = rz
     ctx.upload(trail, start)
 
     def batch(m):
         ctx.copy_vector(first, last)
         for k in range(m):
-            ctx.cg_iteration_until_dev(A, p, x, r, p, w, trail, 2 * k, pw_at, 2 * k + 2, conv_threshold)
+            if precond is None:
+                ctx.cg_iteration_until_dev(A, p, x, r, p, w, trail, 2 * k, pw_at, 2 * k + 2, conv_threshold)
+            else:
+                ctx.pcg_iteration_until_dev(A, p, x, r, p, w, precond, trail, 4 * k, pw_at, 4 * k + 4, conv_threshold)
 
     done, g = 0, None
     try:
@@ -830,10 +859,10 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
             t = ctx.download(trail)  # synchronises, then drains the events
             stopped = False
             for k in range(m):
-                if not (t[2 * k] > conv_threshold):
+                if not (t[rec * k] > conv_threshold):
                     stopped = True
                     break
-                rr = float(t[2 * k + 2])
+                rr = float(t[rec * k + rec])
                 note_threshold(rr, conv_threshold, noted)
                 if on_iteration is not None:
                     on_iteration(done, rr)

@@ -4017,6 +4017,81 @@ extern "C" int abft_hip_cg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matri
   return ABFT_OK;
 }
 
+// ---- the guarded iteration with Jacobi preconditioning ----------------
+// spmv(A, vec, w) + p.w, then r -= alpha w, {r.z, r.r}, x += alpha p, p = dinv r + beta p with alpha = r.z / p.w and
+// beta = r.z' / r.z formed on the device, behind the same stop test on r.r.  The scalars travel as records of four
+// doubles {r.r, queued events, r.z, 0.0}.  Always three kernels (fold, guarded r half, guarded x / p half; kernels.hip,
+// calc_r_precond_until_kernel): live, the bits abft_hip_spmv_dot_dev + abft_hip_calc_xr_precond +
+// abft_hip_calc_p_precond leave.  Nothing is left pending and abft_hip_tail_stats is not touched.
+extern "C" int abft_hip_pcg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                                int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                                abft_hip_vector *p, abft_hip_vector *w, const abft_hip_vector *dinv,
+                                                const double *dev_in, double *dev_pw, double *dev_out,
+                                                double threshold) {
+  const char *what = "pcg_iteration_until";
+  if (int rc = bind(ctx)) return rc;  // a pending x update applied, a speculation voided
+  if (!mat || !vec || !x || !r || !p || !w || !dinv) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
+  if (!dev_in || !dev_pw || !dev_out) return set_err(ABFT_ERR_INVALID, "%s: null device scalar", what);
+  if (part != ABFT_PART_ALL && part != ABFT_PART_BOUNDARY)
+    return set_err(ABFT_ERR_INVALID, "%s: part %d (the interior part goes through abft_hip_spmv_dot_part_dev)", what, part);
+  // one rank only: a frozen rank would leave its peers waiting at the board
+  if (ctx->peers.attached)
+    return set_err(ABFT_ERR_INVALID, "%s: a peer board is attached; the guarded iteration runs on one rank", what);
+  // two records of four doubles and the pair of the SpMV
+  auto apart = [](const double *a, int na, const double *b, int nb) { return a + na <= b || b + nb <= a; };
+  if (!apart(dev_in, 4, dev_pw, 2) || !apart(dev_in, 4, dev_out, 4) || !apart(dev_pw, 2, dev_out, 4))
+    return set_err(ABFT_ERR_INVALID, "%s: the scalar records overlap", what);
+  if (int rc = check_same(x, r, what)) return rc;
+  if (int rc = check_same(x, p, what)) return rc;
+  if (int rc = check_same(x, w, what)) return rc;
+  const int n = x->n;
+  const uint32_t n_out = mat->fmt == ABFT_FMT_CSR ? mat->csr.n_out : mat->coo.n_out;
+  if ((uint32_t)n != n_out)
+    return set_err(ABFT_ERR_INVALID, "%s: vectors of %d entries for a matrix of %u rows", what, n, n_out);
+  if (dinv->n != n)
+    return set_err(ABFT_ERR_INVALID, "%s: dinv of %d entries for vectors of %d", what, dinv->n, n);
+  if (vec_offset < 0 || (uint64_t)vec_offset + n_out > (uint64_t)vec->n)
+    return set_err(ABFT_ERR_INVALID, "%s: window [%d,%llu) outside the input vector of %d", what, vec_offset,
+                   (unsigned long long)vec_offset + n_out, vec->n);
+  if (n > 0) {
+    if (!disjoint(x, r) || !disjoint(x, p) || !disjoint(x, w) || !disjoint(r, p) || !disjoint(r, w) || !disjoint(p, w))
+      return set_err(ABFT_ERR_INVALID, "%s: x, r, p and w overlap", what);
+    if (!disjoint(vec, x) || !disjoint(vec, r) || !disjoint(vec, w))
+      return set_err(ABFT_ERR_INVALID, "%s: the input vector overlaps x, r or w", what);
+    if (!disjoint(vec, p) && p->d != vec->d + vec_offset)  // (the vector the SpMV read, or a vector apart from it)
+      return set_err(ABFT_ERR_INVALID, "%s: p overlaps the input vector without being its window", what);
+    if (!disjoint(dinv, x) || !disjoint(dinv, r) || !disjoint(dinv, p) || !disjoint(dinv, w) || !disjoint(dinv, vec))
+      return set_err(ABFT_ERR_INVALID, "%s: dinv overlaps x, r, p, w or the input vector", what);
+  }
+  // the reduction's partials are allocated on first use, which a capturing stream does not allow
+  if (ctx->capturing && !ctx->bslot)
+    return set_err(ABFT_ERR_INVALID, "%s: called under graph capture before the context's block partials exist; make "
+                   "one eager preconditioned call first (abft_hip_precond_start, for example)", what);
+  if (int rc = block_slot(ctx)) return rc;
+  spec_forget(ctx);  // (as every preconditioned entry: the learned iteration names these vectors by handle)
+  HeldFold hold;
+  if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold)) return rc;
+  if (hold.held) {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    ReduceOut big{};
+    big.partials = ctx->partials; big.ticket = ctx->ticket; big.dev_out = hold.fuse.dev_out; big.host = hold.fuse.host;
+    big.ev_count = hold.fuse.ev_count; big.seq = hold.fuse.seq; big.peers = hold.fuse.peers;
+    HIPCHK(launch_fuse_finalize(hold.fuse, hold.nparts, big, hold.fix.on ? &hold.fix : nullptr, ctx->stream));
+  }
+  ReduceOutD o{};
+  o.partials = ctx->bpartials;
+  o.ticket = ctx->ticket;
+  o.dev_out = dev_out;
+  o.ev_count = ctx->ring.count;
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_r_precond_until(r->d, w->d, dinv->d, dev_in, dev_pw, threshold, ctx->alpha_dev, n, o, ctx->stream));
+  }
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_px_precond_until(p->d, r->d, dinv->d, x->d, dev_in, dev_out, threshold, ctx->alpha_dev, n, ctx->stream));
+  return ABFT_OK;
+}
+
 // what became of the x updates left pending on the old p: applied by the predicted SpMV, or on their own
 extern "C" int abft_hip_ahead_stats(abft_hip_ctx *ctx, long *committed_p, long *committed_r, long *dropped) {
   if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");

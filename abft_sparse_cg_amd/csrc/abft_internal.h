@@ -533,6 +533,22 @@ hipError_t launch_calc_xr_precond(double *x, double *r, const double *p, const d
 // p = z + beta p; x != nullptr: and x += alpha p with p as it was
 hipError_t launch_calc_p_precond(double *p, const double *r, const double *dinv, double *x, double beta, double alpha,
                                  int n, hipStream_t s);
+// the two halves of a guarded preconditioned iteration (abft_hip_pcg_iteration_until_dev).  Scalars travel as device
+// records of four doubles {r.r, queued events, r.z, 0.0}; live when in[0] > threshold -- then what
+// launch_calc_xr_precond(x == nullptr) (alpha = in[2] / *pw, left in alpha_out) and launch_calc_p_precond(x != nullptr)
+// (beta = out[2] / in[2]) do --, else nothing but the record handed on: out = {bits of in[0], events, bits of in[2], 0.0}
+struct ReduceOutD {
+  double *partials;          // 2 * ABFT_MAX_PARTIALS doubles at least: r.z's block partials at 0, r.r's at ABFT_MAX_PARTIALS
+  uint32_t *ticket;          // as ReduceOut::ticket
+  double *dev_out;           // the record (device memory)
+  const uint32_t *ev_count;
+};
+hipError_t launch_calc_r_precond_until(double *r, const double *w, const double *dinv, const double *in,
+                                       const double *pw, double threshold, double *alpha_out, int n,
+                                       const ReduceOutD &out, hipStream_t s);
+hipError_t launch_calc_px_precond_until(double *p, const double *r, const double *dinv, double *x, const double *in,
+                                        const double *out, double threshold, const double *alpha_ptr, int n,
+                                        hipStream_t s);
 hipError_t launch_precond_start_block(const double *r, const double *dinv, double *p, int n, int k, uint32_t mask,
                                       const ReduceOutW &out, hipStream_t s);
 hipError_t launch_calc_xr_precond_block(double *x, double *r, const double *p, const double *w, const double *dinv,

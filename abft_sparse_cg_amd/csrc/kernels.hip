@@ -4429,6 +4429,163 @@ hipError_t launch_calc_p_precond(double *p, const double *r, const double *dinv,
 }
 #undef ABFT_PRECOND_DISPATCH
 
+// ---- the guarded preconditioned iteration (abft_hip_pcg_iteration_until_dev) ----
+// calc_xr_precond_kernel<VEC, PAIRS, false> and calc_p_precond_kernel<VEC, PAIRS, true> behind the stop test of
+// calc_r_until_kernel / calc_px_until_kernel above, their scalars formed from device records of four doubles
+// {r.r, queued events, r.z, 0.0}: LIVE when in[0] > threshold (false for NaN) -- then alpha = in[2] / *pw and
+// beta = out[2] / in[2], and the walk, the per-thread sums and the fold are those kernels', bit for bit --, else
+// FROZEN: every thread returns before it touches a vector, a partial or the ticket, and one thread of the r half
+// hands the record on.  Both launches read the same word in[0], which neither writes: the decision is uniform
+// over the grid and the same in both; no workgroup waits for another.
+// (Kernels of their own, as the plain guarded pair: the unguarded ones keep their symbols and their code.)
+
+// reduce_finish_k<2> that leaves its two totals on the device: value[0] = r.z, value[1] = r.r
+__device__ __forceinline__ void reduce_finish_d(const double *value, const ReduceOutD &o, double *s_w) {
+  __shared__ uint32_t s_last;
+  double bv[2];
+#pragma unroll
+  for (int j = 0; j < 2; j++) bv[j] = block_sum(value[j], s_w + 4 * j);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+      __hip_atomic_store(o.partials + (size_t)j * ABFT_MAX_PARTIALS + blockIdx.x, bv[j], __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    s_last = reduce_take_ticket(o.ticket);
+  }
+  __syncthreads();
+  if (!s_last) return;
+  double tot[2];
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    double acc = 0.0;
+    for (uint32_t i = threadIdx.x; i < gridDim.x; i += ABFT_BLOCK)  // fixed order
+      acc += __hip_atomic_load(o.partials + (size_t)j * ABFT_MAX_PARTIALS + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tot[j] = block_sum(acc, s_w + 4 * (2 + j));
+  }
+  if (threadIdx.x == 0) {
+    const uint32_t nev = __hip_atomic_load(o.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(o.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+    o.dev_out[0] = tot[1];
+    o.dev_out[1] = (double)nev;
+    o.dev_out[2] = tot[0];
+    o.dev_out[3] = 0.0;
+  }
+}
+
+template <int VEC, bool PAIRS>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_precond_until_kernel(double *r, const double *w,
+                                                                          const double *__restrict__ dinv,
+                                                                          const double *in, const double *pw,
+                                                                          double threshold, double *alpha_out, int n,
+                                                                          ReduceOutD out) {
+  __shared__ double s_w[16];
+  if (!(in[0] > threshold)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      // the bits, whatever they are (a NaN's payload included): moved as integers
+      const unsigned long long *src = reinterpret_cast<const unsigned long long *>(in);
+      unsigned long long *dst = reinterpret_cast<unsigned long long *>(out.dev_out);
+      const unsigned long long rr_bits = src[0], rz_bits = src[2];
+      dst[0] = rr_bits;
+      out.dev_out[1] = (double)__hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      dst[2] = rz_bits;
+      out.dev_out[3] = 0.0;
+    }
+    return;
+  }
+  const double alpha = in[2] / *pw;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;  // for the x / p half
+  double acc[2] = {0.0, 0.0};
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const double2 wv = *reinterpret_cast<const double2 *>(w + i);
+      const double2 dv = pair_load<PAIRS>(dinv, i);
+      rv.x -= alpha * wv.x; rv.y -= alpha * wv.y;
+      *reinterpret_cast<double2 *>(r + i) = rv;
+      const double zx = dv.x * rv.x, zy = dv.y * rv.y;
+      acc[0] += rv.x * zx;
+      acc[0] += rv.y * zy;
+      acc[1] += rv.x * rv.x;
+      acc[1] += rv.y * rv.y;
+    } else {
+      const double d = dinv[i];
+      const double rs = r[i] - alpha * w[i];
+      r[i] = rs;
+      const double z = d * rs;
+      acc[0] += rs * z;
+      acc[1] += rs * rs;
+    }
+  }
+  reduce_finish_d(acc, out, s_w);
+}
+
+// (in: the record the iteration started from -- the guard, and beta's denominator; out: what the r half left)
+template <int VEC, bool PAIRS>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_precond_until_kernel(double *__restrict__ p,
+                                                                           const double *__restrict__ r,
+                                                                           const double *__restrict__ dinv,
+                                                                           double *__restrict__ x, const double *in,
+                                                                           const double *out, double threshold,
+                                                                           const double *alpha_ptr, int n) {
+  if (!(in[0] > threshold)) return;
+  const double beta = out[2] / in[2];
+  const double alpha = *alpha_ptr;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      double2 pv = *reinterpret_cast<const double2 *>(p + i);
+      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const double2 dv = pair_load<PAIRS>(dinv, i);
+      double2 xv = *reinterpret_cast<const double2 *>(x + i);
+      xv.x += alpha * pv.x; xv.y += alpha * pv.y;
+      *reinterpret_cast<double2 *>(x + i) = xv;
+      const double zx = dv.x * rv.x, zy = dv.y * rv.y;
+      pv.x = zx + beta * pv.x;
+      pv.y = zy + beta * pv.y;
+      *reinterpret_cast<double2 *>(p + i) = pv;
+    } else {
+      const double ps = p[i];
+      const double z = dinv[i] * r[i];
+      x[i] = x[i] + alpha * ps;
+      p[i] = z + beta * ps;
+    }
+  }
+}
+
+// VEC and PAIRS as launch_calc_xr_precond(x == nullptr) and launch_calc_p_precond(x != nullptr) choose them:
+// the sums are added in the same order
+#define ABFT_PCG_UNTIL_DISPATCH(KERNEL, ...)                                                           \
+  do {                                                                                                 \
+    if (!vec2)                                                                                         \
+      hipLaunchKernelGGL((KERNEL<1, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);           \
+    else if (pairs)                                                                                    \
+      hipLaunchKernelGGL((KERNEL<2, true>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);            \
+    else                                                                                               \
+      hipLaunchKernelGGL((KERNEL<2, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);           \
+  } while (0)
+
+hipError_t launch_calc_r_precond_until(double *r, const double *w, const double *dinv, const double *in,
+                                       const double *pw, double threshold, double *alpha_out, int n,
+                                       const ReduceOutD &out, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  const bool vec2 = aligned16(r, w), pairs = aligned16(dinv);
+  ABFT_PCG_UNTIL_DISPATCH(calc_r_precond_until_kernel, r, w, dinv, in, pw, threshold, alpha_out, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_px_precond_until(double *p, const double *r, const double *dinv, double *x, const double *in,
+                                        const double *out, double threshold, const double *alpha_ptr, int n,
+                                        hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+  const bool vec2 = aligned16(p, r, x), pairs = aligned16(dinv);
+  ABFT_PCG_UNTIL_DISPATCH(calc_px_precond_until_kernel, p, r, dinv, x, in, out, threshold, alpha_ptr, n);
+  return hipGetLastError();
+}
+#undef ABFT_PCG_UNTIL_DISPATCH
+
 // Block forms: one thread per row over the K columns, as the block kernels above; dinv[i] is loaded
 // once per row (one operator for all columns).  A column whose bit is clear keeps its bits (a
 // select).  Sums in dot_block_kernel<K>'s shape, value 2j = column j's r.z, 2j + 1 its r.r, for every

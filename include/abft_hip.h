@@ -680,6 +680,36 @@ int abft_hip_cg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, con
                                     abft_hip_vector *p, abft_hip_vector *w, const double *dev_rr,
                                     double *dev_pw, double *dev_rr_new, double threshold);
 
+/* The guarded iteration with Jacobi preconditioning (dinv: abft_hip_jacobi): one iteration of the preconditioned
+ * loop -- spmv(A, vec, w) with p.w, r -= alpha w, z = dinv r, x += alpha p, p = z + beta p -- behind the same stop
+ * test on r.r, alpha = r.z / p.w and beta = r.z' / r.z formed on the device.
+ * The scalars travel as device RECORDS of four doubles {r.r, queued events, r.z, 0.0}; the first two doubles of a
+ * record are an ordinary pair (abft_hip_read_pair reads it).  dev_in: the record the iteration starts from (read
+ * only), dev_out: the record it leaves, dev_pw: the pair {p.w, events} of the SpMV.
+ *   LIVE   when dev_in[0] > threshold (false for NaN): bit for bit what abft_hip_spmv_dot_dev(A, vec, w, vec_offset,
+ *          dev_pw), abft_hip_calc_xr_precond(x, r, p, w, dinv, dev_in[2] / dev_pw[0]) and
+ *          abft_hip_calc_p_precond(p, r, dinv, r.z' / dev_in[2]) leave in x, r, p and w, with
+ *          dev_out = {r.r', queued events, r.z', 0.0} the two sums abft_hip_calc_xr_precond returns.
+ *   FROZEN otherwise: x, r and p keep every bit; dev_out[0] and dev_out[2] get the bits of dev_in[0] and dev_in[2]
+ *          (moved as integers: a NaN keeps its payload), dev_out[1] the queued-event count, dev_out[3] 0.0; w and
+ *          dev_pw are unspecified -- the SpMV still runs, with its ECC checks and events.  Replaying a frozen
+ *          iteration changes nothing.
+ * Always three kernels behind the SpMV (the fold of the fused product, the guarded r half, the guarded x / p half),
+ * never abft_hip_cg_iteration_dev's one launch; abft_hip_tail_stats is left as it was.  Enqueue-only and capturable;
+ * starts like every other entry (a pending x update applied, a speculation voided) and leaves nothing pending.
+ * Refused before anything is enqueued: everything abft_hip_cg_iteration_until_dev refuses -- with the two records
+ * of four doubles and the pair dev_pw apart from each other --, a null dinv, a dinv that does not have the vectors' length,
+ * and a dinv that overlaps x, r, p, w or vec.
+ * Under graph capture (abft_hip_graph_begin) the call needs the context's block partials, which the first
+ * preconditioned (or block) call allocates and a capturing stream cannot: on a context that has made no such call
+ * it returns ABFT_ERR_INVALID.  Make one eager preconditioned call first -- abft_hip_precond_start, which the loop
+ * needs for its first record anyway.
+ * Every matrix abft_hip_cg_iteration_until_dev takes is accepted. */
+int abft_hip_pcg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                     int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                     abft_hip_vector *p, abft_hip_vector *w, const abft_hip_vector *dinv,
+                                     const double *dev_in, double *dev_pw, double *dev_out, double threshold);
+
 /* ---- graph replay ------------------------------------------------------ */
 
 /* Capture everything enqueued on the context's stream between begin and end -- the
