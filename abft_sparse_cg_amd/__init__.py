@@ -12,4 +12,4 @@ from .capi import MODES, AbftError  # noqa: F401
 capi.load()
 
 from .context import (DEFAULT_STRIDE, FatalEvent, HIPContext, ResidualCheckFailed, cg_solve, cg_solve_block,  # noqa: E402,F401
-                      cg_solve_device, vecc_strip)
+                      cg_solve_block_device, cg_solve_device, vecc_strip)

@@ -579,6 +579,22 @@ class HIPContext:
                                                       dinv.h, base + 8 * in_at, base + 8 * pw_at, base + 8 * out_at,
                                                       threshold))
 
+    def cg_block_iteration_until_dev(self, mat, X, R, P, W, k, scalars, in_at, pw_at, out_at, threshold, dinv=None):
+        """one guarded iteration of the fused block loop, enqueue-only (abft_hip_cg_block_iteration_until_dev; DESIGN.md
+        section 5h): column j is live when scalars[in_at + j] > threshold on the device, else frozen.  scalars: a vector
+        of device doubles; in_at, out_at: where the records of 2k + 2 doubles {r.r[k], r.z[k], events, 0.0} read and
+        written start in it, pw_at: where the k + 1 doubles {P.W[k], events} go.  dinv: the Jacobi vector, or None for
+        the plain form.  Under graph capture the context must hold the loop's buffers: block_loop_reserve"""
+        base = scalars.device_ptr
+        check(self.L.abft_hip_cg_block_iteration_until_dev(self.h, mat.h, X.h, R.h, P.h, W.h,
+                                                           None if dinv is None else dinv.h, k, base + 8 * in_at,
+                                                           base + 8 * pw_at, base + 8 * out_at, threshold))
+
+    def block_loop_reserve(self, mat, k):
+        """allocate what cg_block_iteration_until_dev needs for this matrix, so that it can be captured on a context
+        that has not run it yet (abft_hip_block_loop_reserve); not under capture"""
+        check(self.L.abft_hip_block_loop_reserve(self.h, mat.h, k))
+
     def graph_begin(self):
         """start capturing the asynchronous calls on the context's stream (include/abft_hip.h, graph replay)"""
         check(self.L.abft_hip_graph_begin(self.h))
@@ -780,7 +796,8 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
 
 
 # iterations per look at the scalars in cg_solve_device.  Not measured: the smallest stride within 2 % of the best
-# time on the 1 M-row matrix is to replace it (tools/device_loop_bench.py).
+# time on the 1 M-row matrix is to replace it (tools/device_loop_bench.py).  The block form
+# (cg_solve_block_device) has been swept over 4, 16 and 64: 16 is that stride on the 1 M-row matrix.
 DEFAULT_STRIDE = 16
 
 
@@ -875,6 +892,102 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
         for v in (first, last, trail):
             ctx.destroy_vector(v)
     return done, rr
+
+
+def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
+                          stride=DEFAULT_STRIDE, graph=True, precond=None):
+    """cg_solve_block(fused=True)'s loop with the K alphas, the K betas and the column mask on the device (DESIGN.md
+    section 5h): the host looks at the scalars once per batch of `stride` iterations instead of twice per iteration.
+
+    The start is cg_solve_block's: copy R <- B, then copy P <- R and dot_block, or with precond (ctx.jacobi(A))
+    precond_start_block.  With max_itrs == 0 or no column above conv_threshold that is all.  Otherwise batches of
+    m = min(stride, max_itrs - done) guarded iterations (ctx.cg_block_iteration_until_dev) over a trail of stride + 1
+    records of 2K + 2 doubles {r.r[K], r.z[K] (plain: r.r again), events, 0.0} -- record i at (2K + 2) i, the K + 1
+    doubles {P.W[K], events} behind them, record `stride` seeded with the start's sums.  Iteration i of a batch reads
+    record i and writes record i + 1; column j is live in it while record i's r.r[j] is above conv_threshold, frozen
+    -- its X, R, P untouched, its words handed on -- from then on.  Every batch starts by copying record `stride` to
+    record 0.  A full batch is one graph, captured once (behind ctx.block_loop_reserve) and replayed (graph=True); a
+    short last batch, and everything with graph=False, is enqueued call by call.  After a batch the trail is
+    downloaded -- the one synchronisation --, events are drained (FatalEvent is raised there, before any callback of
+    the batch), and the records are read in order: `active` of iteration i is the set of columns whose record-i r.r is
+    above the threshold, and the loop stops at the first i without one.
+
+    on_iteration(itr, rr, active) as cg_solve_block calls it -- rr of all K columns from record i + 1 -- but AFTER the
+    batch: the vectors it sees are the batch's end state.  -> (itrs[K], rr[K]) as cg_solve_block.
+    No check_every, no vector_ecc, one GPU."""
+    if int(stride) != stride or stride < 1:
+        raise ValueError("stride must be a whole number >= 1, not %r" % (stride,))
+    stride = int(stride)
+    k = B.K
+    if not k:
+        raise ValueError("cg_solve_block_device wants block vectors (create_block)")
+    ctx.copy_vector(R, B)
+    if precond is None:
+        ctx.copy_vector(P, R)
+        rr = np.array(ctx.dot_block(R, R, k), dtype=np.float64)
+        rz = rr
+    else:
+        rz, rr = ctx.precond_start_block(R, precond, P, k, (1 << k) - 1)
+        rz, rr = np.array(rz, dtype=np.float64), np.array(rr, dtype=np.float64)
+    itrs = [0] * k
+    noted = {}
+    for j in range(k):
+        note_threshold(rr[j], conv_threshold, noted)
+    if max_itrs == 0 or not any(rr[j] > conv_threshold for j in range(k)):
+        return itrs, rr
+    rec = 2 * k + 2  # doubles per record of the trail
+    pw_at = rec * (stride + 1)
+    trail = ctx.create_vector(pw_at + k + 1)
+    first, last = ctx.view_vector(trail, 0, rec), ctx.view_vector(trail, rec * stride, rec)
+    start = np.zeros(pw_at + k + 1)
+    start[rec * stride:rec * stride + k] = rr  # where the first batch's copy finds them
+    start[rec * stride + k:rec * stride + 2 * k] = rz
+    ctx.upload(trail, start)
+
+    def batch(m):
+        ctx.copy_vector(first, last)
+        for i in range(m):
+            ctx.cg_block_iteration_until_dev(A, X, R, P, W, k, trail, rec * i, pw_at, rec * (i + 1), conv_threshold,
+                                             dinv=precond)
+
+    done, g = 0, None
+    try:
+        while True:
+            m = min(stride, max_itrs - done)
+            if graph and m == stride:
+                if g is None:
+                    ctx.block_loop_reserve(A, k)
+                    ctx.graph_begin()
+                    try:
+                        batch(m)
+                    finally:
+                        g = ctx.graph_end()
+                ctx.graph_launch(g)
+            else:
+                batch(m)
+            t = ctx.download(trail)  # synchronises, then drains the events
+            stopped = False
+            for i in range(m):
+                active = sum(1 << j for j in range(k) if t[rec * i + j] > conv_threshold)
+                if not active:
+                    stopped = True
+                    break
+                rr = np.array(t[rec * (i + 1):rec * (i + 1) + k], dtype=np.float64)
+                for j in range(k):
+                    if (active >> j) & 1:
+                        itrs[j] += 1
+                        note_threshold(rr[j], conv_threshold, noted)
+                if on_iteration is not None:
+                    on_iteration(done, rr.copy(), active)
+                done += 1
+            if stopped or done >= max_itrs:
+                break
+    finally:
+        if g is not None:
+            ctx.graph_destroy(g)
+        for v in (first, last, trail):
+            ctx.destroy_vector(v)
+    return itrs, rr
 
 
 def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration):

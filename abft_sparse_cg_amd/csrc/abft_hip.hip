@@ -164,6 +164,7 @@ struct abft_hip_ctx {
   uint32_t bseq = 0;                    // last sequence number handed to a block reduction
   double *dotparts = nullptr;           // abft_hip_spmm_dot: k * nblk row-block partials, grown on demand
   size_t dotparts_cap = 0;
+  double *balpha_dev = nullptr;         // abft_hip_cg_block_iteration_until_dev: the r half's alphas for the x / p half
   unsigned prof = 0;  // bit k: bracket launches of kernel k with HIP events
   unsigned prof_stride = 1, prof_seen[ABFT_K_COUNT] = {};  // ... every prof_stride-th launch of it
   ProfSlot prof_k[ABFT_K_COUNT];
@@ -382,7 +383,11 @@ static std::vector<std::pair<int, hipStream_t>> g_stream_pool;  // (device, idle
 static hipStream_t pooled_stream_take(int device) {
   {
     std::lock_guard<std::mutex> lock(g_stream_mutex);
-    for (size_t i = 0; i < g_stream_pool.size(); i++)
+    // the stream given back last goes out first: contexts that live one at a time then keep reusing one stream and leave
+    // the rest of the pool as it was, so which streams a GROUP of contexts gets -- kernels of a peer board wait for
+    // each other and must sit on different hardware queues, which streams created one after the other do -- does not
+    // depend on how many contexts came and went before it (oldest first, every context rotated the pool by one)
+    for (size_t i = g_stream_pool.size(); i-- > 0;)
       if (g_stream_pool[i].first == device) {
         hipStream_t s = g_stream_pool[i].second;
         g_stream_pool.erase(g_stream_pool.begin() + (long)i);
@@ -524,6 +529,7 @@ extern "C" int abft_hip_shutdown(abft_hip_ctx *ctx) {
   (void)hipFree(ctx->tail_sync);
   (void)hipFree(ctx->bpartials);
   (void)hipFree(ctx->dotparts);
+  (void)hipFree(ctx->balpha_dev);
   if (ctx->bslot) (void)hipHostFree(ctx->bslot);
   if (ctx->wslot) (void)hipHostFree(ctx->wslot);
   if (getenv("ABFT_HIP_VERBOSE") && (ctx->spec.commits || ctx->spec.drops))
@@ -3689,34 +3695,45 @@ extern "C" int abft_hip_calc_p_precond_block(abft_hip_ctx *ctx, abft_hip_vector 
 // ---- the fused block iteration: P.W out of the SpMM, r and its sums, then x and p in one pass ----
 // Nothing is carried from one call to the next: every sum comes back through the call that forms it.
 
+// what abft_hip_spmm_dot takes: a whole square CSR matrix in the streaming layout, P and W blocks of its rows
+static int check_spmm_dot(const char *what, const abft_hip_matrix *mat, const abft_hip_vector *P,
+                          const abft_hip_vector *W, int k) {
+  if (mat->fmt != ABFT_FMT_CSR)
+    return set_err(ABFT_ERR_INVALID, "%s: COO matrices have no block SpMV; create the matrix as CSR with "
+                   "abft_hip_matrix_create_csr_stream", what);
+  if (mat->use_panels || mat->use_sweep || mat->use_slice)
+    return set_err(ABFT_ERR_INVALID, "%s: the matrix is stored in the %s layout; the block SpMV runs on the "
+                   "streaming row-block layout: create the matrix with abft_hip_matrix_create_csr_stream", what,
+                   mat->use_slice ? "slice" : mat->use_sweep ? "sweep" : "panel");
+  if (mat->csr.index_base != 0 || mat->csr.gidx)
+    return set_err(ABFT_ERR_INVALID, "%s: the matrix is a shard; the block SpMV takes a whole square matrix", what);
+  if (mat->csr.n_in != mat->csr.n_out)
+    return set_err(ABFT_ERR_INVALID, "%s: the matrix is not square (%u x %u): P . (A P) needs as many rows "
+                   "as columns", what, mat->csr.n_out, mat->csr.n_in);
+  if (int rc = check_block(what, k, (int)mat->csr.n_out, {P, W})) return rc;
+  if (!disjoint(P, W)) return set_err(ABFT_ERR_INVALID, "%s: input and output overlap", what);
+  return ABFT_OK;
+}
+
+// the SpMM's row-block partials: room for ABFT_MAX_RHS columns of this matrix
+static int dotparts_reserve(abft_hip_ctx *ctx, const abft_hip_matrix *mat, int k) {
+  const size_t need = (size_t)k * mat->csr.nblk;
+  if (need <= ctx->dotparts_cap) return ABFT_OK;
+  (void)hipFree(ctx->dotparts);
+  ctx->dotparts = nullptr;
+  ctx->dotparts_cap = 0;
+  HIPCHK(hipMalloc((void **)&ctx->dotparts, (size_t)ABFT_MAX_RHS * mat->csr.nblk * sizeof(double)));
+  ctx->dotparts_cap = (size_t)ABFT_MAX_RHS * mat->csr.nblk;
+  return ABFT_OK;
+}
+
 extern "C" int abft_hip_spmm_dot(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *P,
                                  abft_hip_vector *W, int k, double *out) {
   if (int rc = bind_block(ctx)) return rc;
   if (!mat || !P || !W || !out) return set_err(ABFT_ERR_INVALID, "spmm_dot: null argument");
-  if (mat->fmt != ABFT_FMT_CSR)
-    return set_err(ABFT_ERR_INVALID, "spmm_dot: COO matrices have no block SpMV; create the matrix as CSR with "
-                   "abft_hip_matrix_create_csr_stream");
-  if (mat->use_panels || mat->use_sweep || mat->use_slice)
-    return set_err(ABFT_ERR_INVALID, "spmm_dot: the matrix is stored in the %s layout; the block SpMV runs on the "
-                   "streaming row-block layout: create the matrix with abft_hip_matrix_create_csr_stream",
-                   mat->use_slice ? "slice" : mat->use_sweep ? "sweep" : "panel");
-  if (mat->csr.index_base != 0 || mat->csr.gidx)
-    return set_err(ABFT_ERR_INVALID, "spmm_dot: the matrix is a shard; the block SpMV takes a whole square matrix");
-  if (mat->csr.n_in != mat->csr.n_out)
-    return set_err(ABFT_ERR_INVALID, "spmm_dot: the matrix is not square (%u x %u): P . (A P) needs as many rows "
-                   "as columns", mat->csr.n_out, mat->csr.n_in);
-  const int N = (int)mat->csr.n_out;
-  if (int rc = check_block("spmm_dot", k, N, {P, W})) return rc;
-  if (!disjoint(P, W)) return set_err(ABFT_ERR_INVALID, "spmm_dot: input and output overlap");
+  if (int rc = check_spmm_dot("spmm_dot", mat, P, W, k)) return rc;
   if (int rc = block_slot(ctx)) return rc;
-  const size_t need = (size_t)k * mat->csr.nblk;
-  if (need > ctx->dotparts_cap) {
-    (void)hipFree(ctx->dotparts);
-    ctx->dotparts = nullptr;
-    ctx->dotparts_cap = 0;
-    HIPCHK(hipMalloc((void **)&ctx->dotparts, (size_t)ABFT_MAX_RHS * mat->csr.nblk * sizeof(double)));
-    ctx->dotparts_cap = (size_t)ABFT_MAX_RHS * mat->csr.nblk;
-  }
+  if (int rc = dotparts_reserve(ctx, mat, k)) return rc;
   {
     KernelTimer t(ctx, ABFT_K_SPMV);
     HIPCHK(launch_spmm_dot_csr(mat->mode, k, mat->csr, P->d, W->d, ctx->ring, ctx->dotparts, ctx->stream));
@@ -4089,6 +4106,89 @@ extern "C" int abft_hip_pcg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matr
   }
   KernelTimer t(ctx, ABFT_K_CALC_P);
   HIPCHK(launch_calc_px_precond_until(p->d, r->d, dinv->d, x->d, dev_in, dev_out, threshold, ctx->alpha_dev, n, ctx->stream));
+  return ABFT_OK;
+}
+
+// ---- the guarded block iteration: K right-hand sides, the column mask decided on the device ----------------
+// spmm(A, P, W) + P.W, then per column r -= alpha w, {r.r, r.z}, x += alpha p, p = [dinv] r + beta p behind the stop
+// test on that column's r.r.  Records of 2k + 2 doubles {r.r[k], r.z[k] (plain: the bits of r.r), queued events, 0.0};
+// dev_pw = {P.W[k], queued events}.  Four kernels in a line: the SpMM with its row-block partials, their fold into
+// dev_pw, the guarded r half, the guarded x / p half (kernels.hip, calc_r_block_until_kernel).  The SpMM always runs
+// (W = A P for every column, the matrix checked, its events queued).  A live column gets the bits abft_hip_spmm_dot +
+// abft_hip_calc_r[_precond]_block + abft_hip_calc_px[_precond]_block leave with the device's mask and the IEEE
+// quotients; a frozen one keeps every bit of its column of X, R, P and its record words.  Nothing is left pending.
+
+// what a capturing stream cannot allocate: the block slot and partials, the SpMM's partials, the alpha scratch
+static bool block_loop_ready(const abft_hip_ctx *ctx, const abft_hip_matrix *mat, int k) {
+  return ctx->bslot && ctx->balpha_dev && (size_t)k * mat->csr.nblk <= ctx->dotparts_cap;
+}
+
+static int block_loop_alloc(abft_hip_ctx *ctx, const abft_hip_matrix *mat, int k) {
+  if (int rc = block_slot(ctx)) return rc;
+  if (int rc = dotparts_reserve(ctx, mat, k)) return rc;
+  if (!ctx->balpha_dev) HIPCHK(hipMalloc((void **)&ctx->balpha_dev, ABFT_MAX_RHS * sizeof(double)));
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_block_loop_reserve(abft_hip_ctx *ctx, abft_hip_matrix *mat, int k) {
+  const char *what = "block_loop_reserve";
+  if (int rc = bind(ctx)) return rc;
+  if (!mat) return set_err(ABFT_ERR_INVALID, "%s: null matrix", what);
+  if (ctx->capturing) return set_err(ABFT_ERR_INVALID, "%s: called under graph capture (it allocates)", what);
+  if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "%s: k = %d outside [1, %d]", what, k, ABFT_MAX_RHS);
+  if (mat->fmt != ABFT_FMT_CSR || mat->use_panels || mat->use_sweep || mat->use_slice)
+    return set_err(ABFT_ERR_INVALID, "%s: the block loop runs on CSR matrices in the streaming row-block layout "
+                   "(abft_hip_matrix_create_csr_stream)", what);
+  return block_loop_alloc(ctx, mat, k);
+}
+
+extern "C" int abft_hip_cg_block_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, abft_hip_vector *X,
+                                                     abft_hip_vector *R, abft_hip_vector *P, abft_hip_vector *W,
+                                                     const abft_hip_vector *dinv, int k, const double *dev_in,
+                                                     double *dev_pw, double *dev_out, double threshold) {
+  const char *what = "cg_block_iteration_until";
+  if (int rc = bind_block(ctx)) return rc;  // a pending x update applied, the fused product and the learned iteration forgotten
+  if (!mat || !X || !R || !P || !W) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
+  if (!dev_in || !dev_pw || !dev_out) return set_err(ABFT_ERR_INVALID, "%s: null device scalar", what);
+  // one rank only, as the single guarded iterations
+  if (ctx->peers.attached)
+    return set_err(ABFT_ERR_INVALID, "%s: a peer board is attached; the guarded iteration runs on one rank", what);
+  if (int rc = check_fused_block(what, k, {}, {X, R, P, W}, dinv, dinv != nullptr)) return rc;
+  if (int rc = check_spmm_dot(what, mat, P, W, k)) return rc;
+  const abft_hip_vector *four[4] = {X, R, P, W};  // (one handle passed twice: check_fused_block compares handles)
+  for (int a = 0; a < 4 && X->n; a++)
+    for (int b = a + 1; b < 4; b++)
+      if (!disjoint(four[a], four[b])) return set_err(ABFT_ERR_INVALID, "%s: X, R, P and W overlap", what);
+  auto apart = [](const double *a, int na, const double *b, int nb) { return a + na <= b || b + nb <= a; };
+  const int rec = 2 * k + 2;
+  if (!apart(dev_in, rec, dev_pw, k + 1) || !apart(dev_in, rec, dev_out, rec) || !apart(dev_pw, k + 1, dev_out, rec))
+    return set_err(ABFT_ERR_INVALID, "%s: the scalar records overlap", what);
+  if (ctx->capturing && !block_loop_ready(ctx, mat, k))
+    return set_err(ABFT_ERR_INVALID, "%s: called under graph capture before the context holds the partials of this "
+                   "matrix and k; call abft_hip_block_loop_reserve first", what);
+  if (int rc = block_loop_alloc(ctx, mat, k)) return rc;
+  const int N = (int)mat->csr.n_out;
+  {
+    KernelTimer t(ctx, ABFT_K_SPMV);
+    HIPCHK(launch_spmm_dot_csr(mat->mode, k, mat->csr, P->d, W->d, ctx->ring, ctx->dotparts, ctx->stream));
+  }
+  ReduceOutB o{};
+  o.partials = ctx->bpartials;
+  o.ticket = ctx->ticket;
+  o.ev_count = ctx->ring.count;
+  o.dev_out = dev_pw;
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_spmm_fold_dev(ctx->dotparts, mat->csr.nblk, k, o, ctx->stream));
+  }
+  o.dev_out = dev_out;
+  const double *dv = dinv ? dinv->d : nullptr;
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_r_block_until(R->d, W->d, dv, dev_in, dev_pw, threshold, ctx->balpha_dev, N, k, o, ctx->stream));
+  }
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_px_block_until(X->d, P->d, R->d, dv, dev_in, dev_out, threshold, ctx->balpha_dev, N, k, ctx->stream));
   return ABFT_OK;
 }
 

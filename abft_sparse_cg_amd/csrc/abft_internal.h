@@ -549,6 +549,27 @@ hipError_t launch_calc_r_precond_until(double *r, const double *w, const double 
 hipError_t launch_calc_px_precond_until(double *p, const double *r, const double *dinv, double *x, const double *in,
                                         const double *out, double threshold, const double *alpha_ptr, int n,
                                         hipStream_t s);
+// the guarded block iteration (abft_hip_cg_block_iteration_until_dev).  Scalars travel as device records of 2k + 2
+// doubles {r.r of the k columns, their r.z (plain: the bits of r.r), queued events, 0.0}, the SpMM's products as
+// k + 1 doubles {P.W of the k columns, queued events}.  Column j is live when in[j] > threshold, decided by every
+// thread of both halves from the same words; a live column gets what launch_calc_r_block / launch_calc_r_precond_block
+// (alpha[j] = in[k + j] / pw[j], left in alpha_out[0..k)) and launch_calc_px_block (beta[j] = out[k + j] / in[k + j])
+// do with that mask, a frozen one keeps its bits and its record words; no column live: nothing but the record handed on
+struct ReduceOutB {
+  double *partials;          // 2 * ABFT_MAX_RHS * ABFT_MAX_PARTIALS doubles, value j's at j * ABFT_MAX_PARTIALS
+  uint32_t *ticket;          // as ReduceOut::ticket
+  double *dev_out;           // the record, or {P.W, events} (device memory)
+  const uint32_t *ev_count;
+};
+// launch_spmm_fold with the k totals and the events word left in out.dev_out[0..k]
+hipError_t launch_spmm_fold_dev(const double *parts, uint32_t nblk, int k, const ReduceOutB &out, hipStream_t s);
+// dinv == nullptr: the plain forms
+hipError_t launch_calc_r_block_until(double *r, const double *w, const double *dinv, const double *in,
+                                     const double *pw, double threshold, double *alpha_out, int n, int k,
+                                     const ReduceOutB &out, hipStream_t s);
+hipError_t launch_calc_px_block_until(double *x, double *p, const double *r, const double *dinv, const double *in,
+                                      const double *out, double threshold, const double *alpha_ptr, int n, int k,
+                                      hipStream_t s);
 hipError_t launch_precond_start_block(const double *r, const double *dinv, double *p, int n, int k, uint32_t mask,
                                       const ReduceOutW &out, hipStream_t s);
 hipError_t launch_calc_xr_precond_block(double *x, double *r, const double *p, const double *w, const double *dinv,

@@ -4852,6 +4852,252 @@ hipError_t launch_calc_px_block(double *x, double *p, const double *r, const dou
   return hipGetLastError();
 }
 
+// ---- the guarded block iteration (abft_hip_cg_block_iteration_until_dev) ----
+// spmm_fold_kernel<K>, calc_r_block_kernel<K, PRECOND> and calc_px_block_kernel<K, PRECOND> with their scalars on the
+// device and the column mask decided there.  Records of 2K + 2 doubles: [j] = r.r of column j, [K + j] = its r.z (the
+// plain form: the bits of [j]), [2K] = queued events, [2K + 1] = 0.0; the SpMM's products as K doubles and the events
+// word.  Column j is LIVE when in[j] > threshold (false for NaN): then alpha[j] = in[K + j] / pw[j], beta[j] =
+// out[K + j] / in[K + j], and the walk, the selects, the per-thread sums and the folds are those kernels', bit for
+// bit.  A FROZEN column keeps its bits through the same selects and its record words are handed on as integers.
+// With no column live every thread returns before it touches a vector, a partial or the ticket, and one thread of
+// the r half hands the record on.  Both halves form the mask from the same words of `in`, which neither writes: the
+// decision is uniform over the grid and the same in both launches; no workgroup waits for another.
+// (Kernels of their own, as the single guarded pairs: the unguarded ones keep their symbols and their code.)
+
+// reduce_finish_k<S> up to the S totals, which stay with the last-arriving block: -> 1 there (tot valid in every
+// thread's copy as block_sum leaves it), 0 elsewhere.  The same partials, ticket and fixed-order folds.
+template <int S>
+__device__ __forceinline__ uint32_t reduce_totals_dev(const double *value, double *partials, uint32_t *ticket,
+                                                      double *s_w, double *tot) {
+  __shared__ uint32_t s_last;
+  double bv[S];
+#pragma unroll
+  for (int j = 0; j < S; j++) bv[j] = block_sum(value[j], s_w + 4 * j);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < S; j++)
+      __hip_atomic_store(partials + (size_t)j * ABFT_MAX_PARTIALS + blockIdx.x, bv[j], __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    s_last = reduce_take_ticket(ticket);
+  }
+  __syncthreads();
+  if (!s_last) return 0u;
+#pragma unroll
+  for (int j = 0; j < S; j++) {
+    double acc = 0.0;
+    for (uint32_t i = threadIdx.x; i < gridDim.x; i += ABFT_BLOCK)  // fixed order
+      acc += __hip_atomic_load(partials + (size_t)j * ABFT_MAX_PARTIALS + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tot[j] = block_sum(acc, s_w + 4 * (S + j));
+  }
+  return 1u;
+}
+
+// spmm_fold_kernel<K> leaving {K totals, queued events} in dev_pw instead of the pinned slot
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void spmm_fold_dev_kernel(const double *__restrict__ parts, uint32_t n,
+                                                                   uint32_t chunk, ReduceOutB out) {
+  __shared__ double s_w[8 * K];
+  const uint32_t lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
+  double acc[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    const double *pj = parts + (size_t)j * n;
+    double a = 0.0;
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += 4u * ABFT_BLOCK) {
+      double v[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const uint32_t q = i + (uint32_t)u * ABFT_BLOCK;
+        v[u] = q < hi ? pj[q] : 0.0;
+      }
+      a += (v[0] + v[1]) + (v[2] + v[3]);
+    }
+    acc[j] = a;
+  }
+  double tot[K];
+  if (!reduce_totals_dev<K>(acc, out.partials, out.ticket, s_w, tot)) return;
+  if (threadIdx.x == 0) {
+    const uint32_t nev = __hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(out.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+#pragma unroll
+    for (int j = 0; j < K; j++) out.dev_out[j] = tot[j];
+    out.dev_out[K] = (double)nev;
+  }
+}
+
+hipError_t launch_spmm_fold_dev(const double *parts, uint32_t nblk, int k, const ReduceOutB &out, hipStream_t s) {
+  uint32_t nb = (nblk + 2047u) / 2048u;  // launch_spmm_fold's grid and chunks
+  if (nb < 1u) nb = 1u;
+  if (nb > 64u) nb = 64u;
+  const uint32_t chunk = (nblk + nb - 1u) / nb;
+#define ABFT_OP(K) hipLaunchKernelGGL(spmm_fold_dev_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, parts, nblk, chunk, out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+// a wave-uniform double moved into scalar registers (the same bits): a scalar formed by vector arithmetic from device
+// words then costs the streaming loops no vector registers, as a kernel argument costs none
+__device__ __forceinline__ double uniform_f64(double v) {
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
+  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
+template <int K>
+__device__ __forceinline__ uint32_t block_live_mask(const double *in, double threshold) {
+  uint32_t active = 0u;
+#pragma unroll
+  for (int j = 0; j < K; j++) active |= in[j] > threshold ? 1u << j : 0u;
+  return active;
+}
+
+template <int K, bool PRECOND>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_until_kernel(double *__restrict__ r,
+                                                                        const double *__restrict__ w,
+                                                                        const double *__restrict__ dinv,
+                                                                        const double *in, const double *pw,
+                                                                        double threshold, double *alpha_out, int n,
+                                                                        ReduceOutB out) {
+  constexpr int S = PRECOND ? 2 * K : K;
+  __shared__ double s_w[8 * S];
+  const uint32_t active = block_live_mask<K>(in, threshold);
+  const unsigned long long *src = reinterpret_cast<const unsigned long long *>(in);
+  unsigned long long *dst = reinterpret_cast<unsigned long long *>(out.dev_out);
+  if (!active) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      // the bits, whatever they are (a NaN's payload included): moved as integers
+      unsigned long long b[2 * K];
+#pragma unroll
+      for (int j = 0; j < 2 * K; j++) b[j] = src[j];
+#pragma unroll
+      for (int j = 0; j < 2 * K; j++) dst[j] = b[j];
+      out.dev_out[2 * K] = (double)__hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      out.dev_out[2 * K + 1] = 0.0;
+    }
+    return;
+  }
+  double alpha[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) alpha[j] = uniform_f64(in[K + j] / pw[j]);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {  // for the x / p half
+#pragma unroll
+    for (int j = 0; j < K; j++) alpha_out[j] = alpha[j];
+  }
+  double acc[S];
+#pragma unroll
+  for (int j = 0; j < S; j++) acc[j] = 0.0;
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double rv[K], wv[K];
+    const double d = PRECOND ? dinv[i] : 0.0;
+    block_load<K>(r + i * K, rv);
+    block_load<K>(w + i * K, wv);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const double rs = rv[j] - alpha[j] * wv[j];  // calc_r_block_kernel's two roundings
+      rv[j] = ((active >> j) & 1u) ? rs : rv[j];
+      if (PRECOND) {
+        const double z = d * rv[j];
+        acc[2 * j] += rv[j] * z;
+        acc[2 * j + 1] += rv[j] * rv[j];
+      } else {
+        acc[j] += rv[j] * rv[j];
+      }
+    }
+    block_store<K>(r + i * K, rv);
+  }
+  double tot[S];
+  if (!reduce_totals_dev<S>(acc, out.partials, out.ticket, s_w, tot)) return;
+  if (threadIdx.x == 0) {
+    const uint32_t nev = __hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(out.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      // a live column's new sums; a frozen one's words as they were read, not the recomputed sums
+      const unsigned long long rr_new = __double_as_longlong(PRECOND ? tot[2 * j + 1] : tot[j]);
+      const unsigned long long rz_new = PRECOND ? (unsigned long long)__double_as_longlong(tot[2 * j]) : rr_new;
+      const bool on = (active >> j) & 1u;
+      const unsigned long long rr_old = src[j], rz_old = src[K + j];
+      dst[j] = on ? rr_new : rr_old;
+      dst[K + j] = on ? rz_new : rz_old;
+    }
+    out.dev_out[2 * K] = (double)nev;
+    out.dev_out[2 * K + 1] = 0.0;
+  }
+}
+
+// (in: the record the iteration started from -- the mask, and beta's denominators; out: what the r half left)
+template <int K, bool PRECOND>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_until_kernel(double *__restrict__ x, double *__restrict__ p,
+                                                                         const double *__restrict__ r,
+                                                                         const double *__restrict__ dinv,
+                                                                         const double *in, const double *out,
+                                                                         double threshold, const double *alpha_ptr,
+                                                                         int n) {
+  const uint32_t active = block_live_mask<K>(in, threshold);
+  if (!active) return;
+  double alpha[K], beta[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    alpha[j] = alpha_ptr[j];
+    beta[j] = uniform_f64(out[K + j] / in[K + j]);
+  }
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    double xv[K], pv[K], rv[K];
+    const double d = PRECOND ? dinv[i] : 0.0;
+    block_load<K>(x + i * K, xv);
+    block_load<K>(p + i * K, pv);
+    block_load<K>(r + i * K, rv);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const bool on = (active >> j) & 1u;
+      const double xs = xv[j] + alpha[j] * pv[j];
+      const double z = PRECOND ? d * rv[j] : rv[j];
+      const double ps = z + beta[j] * pv[j];
+      xv[j] = on ? xs : xv[j];
+      pv[j] = on ? ps : pv[j];
+    }
+    block_store<K>(x + i * K, xv);
+    block_store<K>(p + i * K, pv);
+  }
+}
+
+hipError_t launch_calc_r_block_until(double *r, const double *w, const double *dinv, const double *in,
+                                     const double *pw, double threshold, double *alpha_out, int n, int k,
+                                     const ReduceOutB &out, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K)                                                                                                    \
+  if (dinv)                                                                                                           \
+    hipLaunchKernelGGL((calc_r_block_until_kernel<K, true>), dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, dinv, in, pw,    \
+                       threshold, alpha_out, n, out);                                                                 \
+  else                                                                                                                \
+    hipLaunchKernelGGL((calc_r_block_until_kernel<K, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, dinv, in, pw,   \
+                       threshold, alpha_out, n, out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_px_block_until(double *x, double *p, const double *r, const double *dinv, const double *in,
+                                      const double *out, double threshold, const double *alpha_ptr, int n, int k,
+                                      hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K)                                                                                                    \
+  if (dinv)                                                                                                           \
+    hipLaunchKernelGGL((calc_px_block_until_kernel<K, true>), dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, dinv, in,    \
+                       out, threshold, alpha_ptr, n);                                                                 \
+  else                                                                                                                \
+    hipLaunchKernelGGL((calc_px_block_until_kernel<K, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, dinv, in,   \
+                       out, threshold, alpha_ptr, n)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
 // ---- the inverse diagonal (abft_hip_matrix_diag_inverse) over the stored arrays ----
 // d = the sum, in storage order, of the values of a row's (COO: an output group's) elements that sit on
 // the diagonal; in these two layouts storage order inside a row / group is the caller's.  The column is

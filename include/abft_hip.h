@@ -710,6 +710,41 @@ int abft_hip_pcg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, co
                                      abft_hip_vector *p, abft_hip_vector *w, const abft_hip_vector *dinv,
                                      const double *dev_in, double *dev_pw, double *dev_out, double threshold);
 
+/* The guarded iteration for k right-hand sides (block vectors, 1 <= k <= ABFT_MAX_RHS): one iteration of the fused
+ * block loop -- W = A P with the k products P . W, then per column r -= alpha w, x += alpha p, p = r + beta p (with
+ * dinv: p = dinv r + beta p) -- with the k alphas, the k betas and the COLUMN MASK formed on the device: column j runs
+ * while ITS r.r is above the threshold.  dinv == NULL: the plain form.
+ * The scalars travel as device RECORDS of 2k + 2 doubles: [j] = r.r of column j, [k + j] = its r.z (the plain form:
+ * the bits of [j]), [2k] = the queued-event count, [2k + 1] = 0.0.  dev_in: the record the iteration starts from
+ * (read only), dev_out: the record it leaves, dev_pw: k + 1 doubles, the k products and the queued-event count.
+ *   Column j is LIVE when dev_in[j] > threshold (false for NaN): its column of X, R and P, dev_pw[j], dev_out[j] and
+ *          dev_out[k + j] are bit for bit what abft_hip_spmm_dot, abft_hip_calc_r_block (abft_hip_calc_r_precond_block)
+ *          and abft_hip_calc_px_block (abft_hip_calc_px_precond_block) leave when called with the mask of the live
+ *          columns, alpha[j] = dev_in[k + j] / P.W[j] and beta[j] = r.z'[j] / dev_in[k + j] as IEEE quotients.
+ *   FROZEN otherwise: its column of X, R and P keeps every bit; dev_out[j] and dev_out[k + j] get the bits of
+ *          dev_in[j] and dev_in[k + j] (moved as integers: a NaN keeps its payload).
+ * The SpMM always runs, with its ECC checks and events: W = A P in every column, as abft_hip_spmm_dot leaves it.
+ * With no column live nothing else is touched but dev_pw and dev_out; replaying such an iteration changes nothing.
+ * Four kernels in a line: the SpMM with its row-block partials, their fold, the guarded r half, the guarded x / p
+ * half.  Every thread of both halves forms the mask from the same words of dev_in, which neither writes; no workgroup
+ * waits for another.  Enqueue-only and capturable; starts like every other entry (a pending x update applied, a
+ * speculation voided) and leaves nothing pending.
+ * Refused before anything is enqueued, every operand left as it was: whatever abft_hip_spmm_dot refuses for (mat, P,
+ * W, k); X, R, P, W that are not blocks of the matrix's rows, or overlap each other; a dinv that does not have the
+ * matrix's row count or overlaps one of the four; null records or records that overlap each other (2k + 2, k + 1
+ * and 2k + 2 doubles); a context with a peer board attached.
+ * Under graph capture the call needs what a capturing stream cannot allocate -- the block partials, the SpMM's
+ * partials for this matrix, the alpha scratch: on a context that does not hold them it returns ABFT_ERR_INVALID.
+ * Call abft_hip_block_loop_reserve first; an eager call allocates them itself. */
+int abft_hip_cg_block_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, abft_hip_vector *X,
+                                          abft_hip_vector *R, abft_hip_vector *P, abft_hip_vector *W,
+                                          const abft_hip_vector *dinv, int k, const double *dev_in, double *dev_pw,
+                                          double *dev_out, double threshold);
+
+/* Allocate what abft_hip_cg_block_iteration_until_dev needs for this matrix and k (any k up to ABFT_MAX_RHS is then
+ * covered), so that the iteration can be captured on a fresh context.  Eager only: refused under graph capture. */
+int abft_hip_block_loop_reserve(abft_hip_ctx *ctx, abft_hip_matrix *mat, int k);
+
 /* ---- graph replay ------------------------------------------------------ */
 
 /* Capture everything enqueued on the context's stream between begin and end -- the

@@ -8,11 +8,18 @@ laplace5:3162,3162 (config 2, 10 M rows), laplace5:1000,1000 and laplace5:316,31
 
     python tools/device_loop_bench.py --out profiles/device_loop_bench.json [--iters 200] [--blocks 5]
                                       [--specs laplace5:1000,1000,...] [--strides 4,8,16,32]
-                                      [--precond jacobi]
+                                      [--precond jacobi] [--rhs 4,8 [--modes none,secded]]
 
 --precond jacobi alternates cg_solve(precond=dinv) and cg_solve_device(precond=dinv) instead,
 dinv = ctx.jacobi(A); the JSON says so under `precond`, in the file and in every row.  The yardstick is then
 cg_solve(precond=) of the same build.
+
+--rhs K[,K...] measures the block loops instead: cg_solve_block(fused=True) and
+cg_solve_block_device alternating on the same matrix (streaming layout) and the same K seeded right-hand sides, in
+every mode of --modes (default none,secded), over the strides 4, 16 and 64 unless --strides says otherwise; the
+per-column counts of the two loops are asserted equal.  Matrices by default laplace5:3162,3162 and
+laplace5:1000,1000; times are per iteration of all K columns.  --out defaults to
+profiles/device_loop_bench_block.json there.  Without --rhs nothing changes.
 
 Also reported per matrix: `best_stride`, the smallest stride within 2 % of the best device-loop time (what
 DEFAULT_STRIDE is to be on the 1 M-row matrix), and `frozen_spmv_worst`, stride - 1: the SpMVs a solve can waste
@@ -55,20 +62,92 @@ def timed_solve(ctx, A, vecs, n, its, stride, dinv=None):
     return (time.perf_counter() - t0) * 1e3, itr
 
 
+BLOCK_SPECS = ("laplace5:3162,3162", "laplace5:1000,1000")
+BLOCK_STRIDES = (4, 16, 64)
+
+
+def timed_block_solve(ctx, A, vecs, n, k, its, stride, dinv=None):
+    """stride 0: cg_solve_block(fused=True); else cg_solve_block_device -> (ms, per-column counts)"""
+    ctx.upload(vecs[1], np.zeros((n, k)))
+    ctx.synchronize()
+    t0 = time.perf_counter()
+    if stride:
+        itrs, _ = amd.cg_solve_block_device(ctx, A, *vecs, max_itrs=its, conv_threshold=THRESHOLD, stride=stride,
+                                            precond=dinv)
+    else:
+        itrs, _ = amd.cg_solve_block(ctx, A, *vecs, max_itrs=its, conv_threshold=THRESHOLD, precond=dinv, fused=True)
+    ctx.synchronize()
+    return (time.perf_counter() - t0) * 1e3, list(itrs)
+
+
+def block_main(a, res):
+    """--rhs: the block loops, one row per (matrix, mode, K)"""
+    strides = [int(s) for s in (a.strides or ",".join(str(s) for s in BLOCK_STRIDES)).split(",")]
+    res["rhs"] = [int(k) for k in a.rhs.split(",")]
+    res["modes"] = a.modes.split(",")
+    for spec in (a.specs or ";".join(BLOCK_SPECS)).split(";"):
+        cols, rows, vals, n = generators.generate(spec)
+        nnz = len(vals)
+        for mode in res["modes"]:
+            ctx = amd.HIPContext(mode, "csr", on_event=lambda ev, fatal: None)
+            A = ctx.create_matrix(cols, rows, vals, n, nnz, layout="stream")
+            dinv = ctx.jacobi(A) if a.precond == "jacobi" else None
+            for k in res["rhs"]:
+                vecs = [ctx.create_block(n, k) for _ in range(5)]
+                ctx.upload(vecs[0], np.random.default_rng(7).random((n, k)) + 0.5)
+                kinds = [0] + strides
+                for st in kinds:  # warm-up: first launches, the graph's instantiation path
+                    timed_block_solve(ctx, A, vecs, n, k, max(st, 5), st, dinv)
+                per = {st: [] for st in kinds}
+                for _ in range(a.blocks):
+                    counts = None
+                    for st in kinds:
+                        ms, itrs = timed_block_solve(ctx, A, vecs, n, k, a.iters, st, dinv)
+                        counts = counts or itrs
+                        assert itrs == counts == [a.iters] * k, (spec, mode, k, st, itrs, counts)  # equal counts, all live
+                        per[st].append(ms / a.iters)
+                host = statistics.median(per[0])
+                dev = {st: statistics.median(per[st]) for st in strides}
+                best = min(dev.values())
+                row = dict(spec=spec, fmt="csr", mode=mode, layout=ctx.matrix_info(A)[0], precond=a.precond, rhs=k, n=n,
+                           nnz=nnz, ms_per_iter_host_fused=host,
+                           ms_per_iter_device={str(st): v for st, v in dev.items()},
+                           ratio_device_over_host={str(st): v / host for st, v in dev.items()},
+                           best_stride=min(st for st in strides if dev[st] <= 1.02 * best),
+                           frozen_spmm_worst={str(st): st - 1 for st in strides},
+                           blocks={str(st): v for st, v in per.items()})
+                res["rows"].append(row)
+                print(json.dumps(row), flush=True)
+                for v in vecs:
+                    ctx.destroy_vector(v)
+            ctx.close()
+        del cols, rows, vals
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="device_loop_bench.json")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--specs", default=";".join(SPECS), help="matrices, separated by ';'")
-    ap.add_argument("--strides", default=",".join(str(s) for s in STRIDES))
+    ap.add_argument("--specs", default=None, help="matrices, separated by ';'")
+    ap.add_argument("--strides", default=None)
     ap.add_argument("--precond", choices=("none", "jacobi"), default="none")
+    ap.add_argument("--rhs", default=None, help="K[,K...]: the block loops with K right-hand sides")
+    ap.add_argument("--modes", default="none,secded", help="with --rhs: the ECC modes")
     a = ap.parse_args()
-    strides = [int(s) for s in a.strides.split(",")]
     argv = [v for i, v in enumerate(sys.argv) if v != "--out" and (i == 0 or sys.argv[i - 1] != "--out")]
     res = {"cmd": " ".join(argv), "iters": a.iters, "blocks": a.blocks, "threshold": THRESHOLD,
            "precond": a.precond, "rows": []}
-    for spec in a.specs.split(";"):
+    if a.rhs:
+        a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_block.json")
+        block_main(a, res)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        return 0
+    a.out = a.out or "device_loop_bench.json"
+    strides = [int(s) for s in (a.strides or ",".join(str(s) for s in STRIDES)).split(",")]
+    for spec in (a.specs or ";".join(SPECS)).split(";"):
         cols, rows, vals, n = generators.generate(spec)
         ctx = amd.HIPContext("none", "csr", on_event=lambda ev, fatal: None)
         A = ctx.create_matrix(cols, rows, vals, n, len(vals))
