@@ -801,6 +801,65 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
 DEFAULT_STRIDE = 16
 
 
+def _whole_stride(stride):
+    if int(stride) != stride or stride < 1:
+        raise ValueError("stride must be a whole number >= 1, not %r" % (stride,))
+    return int(stride)
+
+
+def _device_batches(ctx, max_itrs, stride, graph, rec, tail, seed, enqueue, record, before_capture=None):
+    """The batch loop of cg_solve_device and cg_solve_block_device: a trail of stride + 1 records of `rec` doubles
+    with `tail` doubles behind them (at pw_at = rec * (stride + 1): the SpMV's product), record `stride` starting
+    with `seed`.  A batch copies record `stride` to record 0 and calls enqueue(trail, i, pw_at) for its iterations
+    i = 0 .. m - 1; a full batch is captured once (behind before_capture()) and replayed when `graph`, else, and a
+    short last one, enqueued call by call.  Then the trail is downloaded -- the one synchronisation, which drains
+    the events -- and record(t, i, done) is called for i in order: true when iteration `done` was live (its
+    bookkeeping done), false at the first frozen one, which ends the loop.  -> the count of live iterations."""
+    pw_at = rec * (stride + 1)
+    trail = ctx.create_vector(pw_at + tail)
+    first, last = ctx.view_vector(trail, 0, rec), ctx.view_vector(trail, rec * stride, rec)
+    start = np.zeros(pw_at + tail)
+    start[rec * stride:rec * stride + len(seed)] = seed  # where the first batch's copy finds it
+    ctx.upload(trail, start)
+
+    def batch(m):
+        ctx.copy_vector(first, last)
+        for i in range(m):
+            enqueue(trail, i, pw_at)
+
+    done, g = 0, None
+    try:
+        while True:
+            m = min(stride, max_itrs - done)
+            if graph and m == stride:
+                if g is None:
+                    if before_capture is not None:
+                        before_capture()
+                    ctx.graph_begin()
+                    try:
+                        batch(m)
+                    finally:
+                        g = ctx.graph_end()
+                ctx.graph_launch(g)
+            else:
+                batch(m)
+            t = ctx.download(trail)  # synchronises, then drains the events
+            stopped = False
+            for i in range(m):
+                if not record(t, i, done):
+                    stopped = True
+                    break
+                done += 1
+            if stopped or done >= max_itrs:
+                break
+    finally:
+        if g is not None:
+            ctx.graph_destroy(g)
+        for v in (first, last, trail):
+            ctx.destroy_vector(v)
+    return done
+
+
 def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
                     stride=DEFAULT_STRIDE, graph=True, precond=None):
     """cg_solve's loop (cg.cpp:87-118) with alpha, beta and the stop test on the device:
@@ -827,71 +886,38 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
     4 (stride + 1), record `stride` seeded with {rr0, 0, rz, 0}.  Batches, the graph, the download, events, callbacks
     and the return value are as above; the stop test stays on r.r.  With precond=None the calls and the trail are
     exactly those made without the argument."""
-    if int(stride) != stride or stride < 1:
-        raise ValueError("stride must be a whole number >= 1, not %r" % (stride,))
-    stride = int(stride)
+    stride = _whole_stride(stride)
     ctx.copy_vector(r, b)
     if precond is None:
         ctx.copy_vector(p, r)
         rr = ctx.dot(r, r)
-        rec = 2  # doubles per record of the trail: the pair {r.r, events}
+        rec, seed = 2, [rr]  # doubles per record of the trail: the pair {r.r, events}
     else:
         rz, rr = ctx.precond_start(r, precond, p)
-        rec = 4  # {r.r, events, r.z, 0.0}
+        rec, seed = 4, [rr, 0.0, rz]  # {r.r, events, r.z, 0.0}
     noted = {}
     note_threshold(rr, conv_threshold, noted)
     if max_itrs == 0 or not (rr > conv_threshold):
         return 0, rr
-    pw_at = rec * (stride + 1)
-    trail = ctx.create_vector(pw_at + 2)
-    first, last = ctx.view_vector(trail, 0, rec), ctx.view_vector(trail, rec * stride, rec)
-    start = np.zeros(pw_at + 2)
-    start[rec * stride] = rr  # where the first batch's copy finds it
-    if precond is not None:
-        start[rec * stride + 2] = rz
-    ctx.upload(trail, start)
+    last_rr = [rr]
 
-    def batch(m):
-        ctx.copy_vector(first, last)
-        for k in range(m):
-            if precond is None:
-                ctx.cg_iteration_until_dev(A, p, x, r, p, w, trail, 2 * k, pw_at, 2 * k + 2, conv_threshold)
-            else:
-                ctx.pcg_iteration_until_dev(A, p, x, r, p, w, precond, trail, 4 * k, pw_at, 4 * k + 4, conv_threshold)
+    def enqueue(trail, k, pw_at):
+        if precond is None:
+            ctx.cg_iteration_until_dev(A, p, x, r, p, w, trail, 2 * k, pw_at, 2 * k + 2, conv_threshold)
+        else:
+            ctx.pcg_iteration_until_dev(A, p, x, r, p, w, precond, trail, 4 * k, pw_at, 4 * k + 4, conv_threshold)
 
-    done, g = 0, None
-    try:
-        while True:
-            m = min(stride, max_itrs - done)
-            if graph and m == stride:
-                if g is None:
-                    ctx.graph_begin()
-                    try:
-                        batch(m)
-                    finally:
-                        g = ctx.graph_end()
-                ctx.graph_launch(g)
-            else:
-                batch(m)
-            t = ctx.download(trail)  # synchronises, then drains the events
-            stopped = False
-            for k in range(m):
-                if not (t[rec * k] > conv_threshold):
-                    stopped = True
-                    break
-                rr = float(t[rec * k + rec])
-                note_threshold(rr, conv_threshold, noted)
-                if on_iteration is not None:
-                    on_iteration(done, rr)
-                done += 1
-            if stopped or done >= max_itrs:
-                break
-    finally:
-        if g is not None:
-            ctx.graph_destroy(g)
-        for v in (first, last, trail):
-            ctx.destroy_vector(v)
-    return done, rr
+    def record(t, k, done):
+        if not (t[rec * k] > conv_threshold):
+            return False
+        last_rr[0] = float(t[rec * k + rec])
+        note_threshold(last_rr[0], conv_threshold, noted)
+        if on_iteration is not None:
+            on_iteration(done, last_rr[0])
+        return True
+
+    done = _device_batches(ctx, max_itrs, stride, graph, rec, 2, seed, enqueue, record)
+    return done, last_rr[0]
 
 
 def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
@@ -915,9 +941,7 @@ def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1
     on_iteration(itr, rr, active) as cg_solve_block calls it -- rr of all K columns from record i + 1 -- but AFTER the
     batch: the vectors it sees are the batch's end state.  -> (itrs[K], rr[K]) as cg_solve_block.
     No check_every, no vector_ecc, one GPU."""
-    if int(stride) != stride or stride < 1:
-        raise ValueError("stride must be a whole number >= 1, not %r" % (stride,))
-    stride = int(stride)
+    stride = _whole_stride(stride)
     k = B.K
     if not k:
         raise ValueError("cg_solve_block_device wants block vectors (create_block)")
@@ -936,58 +960,28 @@ def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1
     if max_itrs == 0 or not any(rr[j] > conv_threshold for j in range(k)):
         return itrs, rr
     rec = 2 * k + 2  # doubles per record of the trail
-    pw_at = rec * (stride + 1)
-    trail = ctx.create_vector(pw_at + k + 1)
-    first, last = ctx.view_vector(trail, 0, rec), ctx.view_vector(trail, rec * stride, rec)
-    start = np.zeros(pw_at + k + 1)
-    start[rec * stride:rec * stride + k] = rr  # where the first batch's copy finds them
-    start[rec * stride + k:rec * stride + 2 * k] = rz
-    ctx.upload(trail, start)
+    last_rr = [rr]
 
-    def batch(m):
-        ctx.copy_vector(first, last)
-        for i in range(m):
-            ctx.cg_block_iteration_until_dev(A, X, R, P, W, k, trail, rec * i, pw_at, rec * (i + 1), conv_threshold,
-                                             dinv=precond)
+    def enqueue(trail, i, pw_at):
+        ctx.cg_block_iteration_until_dev(A, X, R, P, W, k, trail, rec * i, pw_at, rec * (i + 1), conv_threshold,
+                                         dinv=precond)
 
-    done, g = 0, None
-    try:
-        while True:
-            m = min(stride, max_itrs - done)
-            if graph and m == stride:
-                if g is None:
-                    ctx.block_loop_reserve(A, k)
-                    ctx.graph_begin()
-                    try:
-                        batch(m)
-                    finally:
-                        g = ctx.graph_end()
-                ctx.graph_launch(g)
-            else:
-                batch(m)
-            t = ctx.download(trail)  # synchronises, then drains the events
-            stopped = False
-            for i in range(m):
-                active = sum(1 << j for j in range(k) if t[rec * i + j] > conv_threshold)
-                if not active:
-                    stopped = True
-                    break
-                rr = np.array(t[rec * (i + 1):rec * (i + 1) + k], dtype=np.float64)
-                for j in range(k):
-                    if (active >> j) & 1:
-                        itrs[j] += 1
-                        note_threshold(rr[j], conv_threshold, noted)
-                if on_iteration is not None:
-                    on_iteration(done, rr.copy(), active)
-                done += 1
-            if stopped or done >= max_itrs:
-                break
-    finally:
-        if g is not None:
-            ctx.graph_destroy(g)
-        for v in (first, last, trail):
-            ctx.destroy_vector(v)
-    return itrs, rr
+    def record(t, i, done):
+        active = sum(1 << j for j in range(k) if t[rec * i + j] > conv_threshold)
+        if not active:
+            return False
+        rr = last_rr[0] = np.array(t[rec * (i + 1):rec * (i + 1) + k], dtype=np.float64)
+        for j in range(k):
+            if (active >> j) & 1:
+                itrs[j] += 1
+                note_threshold(rr[j], conv_threshold, noted)
+        if on_iteration is not None:
+            on_iteration(done, rr.copy(), active)
+        return True
+
+    _device_batches(ctx, max_itrs, stride, graph, rec, k + 1, np.concatenate([rr, rz]), enqueue, record,
+                    before_capture=lambda: ctx.block_loop_reserve(A, k))
+    return itrs, last_rr[0]
 
 
 def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration):

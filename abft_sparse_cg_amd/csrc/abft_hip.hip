@@ -3883,6 +3883,69 @@ extern "C" int abft_hip_set_sharers(abft_hip_ctx *ctx, int processes) {
   return ABFT_OK;
 }
 
+// the four vectors of a CG iteration: all there, of one length.  Every iteration entry checks this before it launches
+static int check_cg_vectors(const abft_hip_vector *x, const abft_hip_vector *r, const abft_hip_vector *p,
+                            const abft_hip_vector *w, const char *what) {
+  if (int rc = check_same(x, r, what)) return rc;
+  if (int rc = check_same(x, p, what)) return rc;
+  return check_same(x, w, what);
+}
+
+// the fold of its fused product that an SpMV held back (spmv_common's `hold`), launched now
+static int finish_held_fold(abft_hip_ctx *ctx, const HeldFold &hold) {
+  if (!hold.held) return ABFT_OK;
+  KernelTimer t(ctx, ABFT_K_DOT);
+  ReduceOut big{};
+  big.partials = ctx->partials; big.ticket = ctx->ticket; big.dev_out = hold.fuse.dev_out; big.host = hold.fuse.host;
+  big.ev_count = hold.fuse.ev_count; big.seq = hold.fuse.seq; big.peers = hold.fuse.peers;
+  HIPCHK(launch_fuse_finalize(hold.fuse, hold.nparts, big, hold.fix.on ? &hold.fix : nullptr, ctx->stream));
+  return ABFT_OK;
+}
+
+// What the single guarded entries (abft_hip_cg_iteration_until_dev, abft_hip_pcg_iteration_until_dev) require before
+// they launch: one rank, scalars apart, four disjoint vectors of the matrix' length, the SpMV's window.  dinv: the
+// preconditioned entry's (then the scalars are records of four doubles, else pairs), nullptr for the plain one.
+static int check_guarded_iteration(abft_hip_ctx *ctx, const char *what, const abft_hip_matrix *mat,
+                                   const abft_hip_vector *vec, int vec_offset, int part, const abft_hip_vector *x,
+                                   const abft_hip_vector *r, const abft_hip_vector *p, const abft_hip_vector *w,
+                                   bool precond, const abft_hip_vector *dinv, const double *dev_in,
+                                   const double *dev_pw, const double *dev_out) {
+  if (!mat || !vec || !x || !r || !p || !w || (precond && !dinv)) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
+  if (!dev_in || !dev_pw || !dev_out) return set_err(ABFT_ERR_INVALID, "%s: null device scalar", what);
+  if (part != ABFT_PART_ALL && part != ABFT_PART_BOUNDARY)
+    return set_err(ABFT_ERR_INVALID, "%s: part %d (the interior part goes through abft_hip_spmv_dot_part_dev)", what, part);
+  // one rank only: a frozen rank would leave its peers waiting at the board
+  if (ctx->peers.attached)
+    return set_err(ABFT_ERR_INVALID, "%s: a peer board is attached; the guarded iteration runs on one rank", what);
+  // two pairs (preconditioned: records of four doubles) and the pair of the SpMV
+  auto apart = [](const double *a, int na, const double *b, int nb) { return a + na <= b || b + nb <= a; };
+  const int rec = precond ? 4 : 2;
+  if (!apart(dev_in, rec, dev_pw, 2) || !apart(dev_in, rec, dev_out, rec) || !apart(dev_pw, 2, dev_out, rec))
+    return set_err(ABFT_ERR_INVALID, "%s: the scalar %s overlap", what, precond ? "records" : "pairs");
+  if (int rc = check_cg_vectors(x, r, p, w, what)) return rc;
+  const int n = x->n;
+  const uint32_t n_out = mat->fmt == ABFT_FMT_CSR ? mat->csr.n_out : mat->coo.n_out;
+  if ((uint32_t)n != n_out)
+    return set_err(ABFT_ERR_INVALID, "%s: vectors of %d entries for a matrix of %u rows", what, n, n_out);
+  if (precond && dinv->n != n)
+    return set_err(ABFT_ERR_INVALID, "%s: dinv of %d entries for vectors of %d", what, dinv->n, n);
+  if (vec_offset < 0 || (uint64_t)vec_offset + n_out > (uint64_t)vec->n)
+    return set_err(ABFT_ERR_INVALID, "%s: window [%d,%llu) outside the input vector of %d", what, vec_offset,
+                   (unsigned long long)vec_offset + n_out, vec->n);
+  if (n > 0) {
+    if (!disjoint(x, r) || !disjoint(x, p) || !disjoint(x, w) || !disjoint(r, p) || !disjoint(r, w) || !disjoint(p, w))
+      return set_err(ABFT_ERR_INVALID, "%s: x, r, p and w overlap", what);
+    if (!disjoint(vec, x) || !disjoint(vec, r) || !disjoint(vec, w))
+      return set_err(ABFT_ERR_INVALID, "%s: the input vector overlaps x, r or w", what);
+    if (!disjoint(vec, p) && p->d != vec->d + vec_offset)  // (the vector the SpMV read, or a vector apart from it)
+      return set_err(ABFT_ERR_INVALID, "%s: p overlaps the input vector without being its window", what);
+    if (precond &&
+        (!disjoint(dinv, x) || !disjoint(dinv, r) || !disjoint(dinv, p) || !disjoint(dinv, w) || !disjoint(dinv, vec)))
+      return set_err(ABFT_ERR_INVALID, "%s: dinv overlaps x, r, p, w or the input vector", what);
+  }
+  return ABFT_OK;
+}
+
 // ---- one CG iteration behind its exchange (cg.cpp:97-112), scalars on the device ----------------
 // spmv(A, vec, w) [a part of it] + p.w, then r -= alpha w, r.r, x += alpha p, p = r + beta p with
 // alpha = rr / p.w and beta = rr_new / rr formed on the device.  The same results, bit for bit, as
@@ -3897,11 +3960,12 @@ extern "C" int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat
                                          double *dev_rr_new) {
   if (!dev_rr || !dev_pw || !dev_rr_new) return set_err(ABFT_ERR_INVALID, "null device scalar");
   if (part == ABFT_PART_INTERIOR) return set_err(ABFT_ERR_INVALID, "cg_iteration: the interior part goes through abft_hip_spmv_dot_part_dev");
+  // before the SpMV, which overwrites w and holds its fold back: a call refused here has launched nothing
+  // (aliased operands and an attached board stay allowed: those rules are the guarded entries')
+  if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");
+  if (int rc = check_cg_vectors(x, r, p, w, "cg_iteration")) return rc;
   HeldFold hold;
   if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold)) return rc;
-  if (int rc = check_same(x, r, "cg_iteration")) return rc;
-  if (int rc = check_same(x, p, "cg_iteration")) return rc;
-  if (int rc = check_same(x, w, "cg_iteration")) return rc;
   const ReduceOut o = reduce_out(ctx, dev_rr_new, false);
   const int n = x->n;
   const bool vec2 = (((uintptr_t)x->d | (uintptr_t)r->d | (uintptr_t)p->d | (uintptr_t)w->d) & 15u) == 0;  // (as the three kernels decide)
@@ -3944,13 +4008,7 @@ extern "C" int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat
   ctx->tail_stats.want = merged ? want_wg : 0u;
   ctx->tail_stats.counts[ctx->tail_stats.path]++;
   if (!merged) {
-    if (hold.held) {
-      KernelTimer t(ctx, ABFT_K_DOT);
-      ReduceOut big{};
-      big.partials = ctx->partials; big.ticket = ctx->ticket; big.dev_out = hold.fuse.dev_out; big.host = hold.fuse.host;
-      big.ev_count = hold.fuse.ev_count; big.seq = hold.fuse.seq; big.peers = hold.fuse.peers;
-      HIPCHK(launch_fuse_finalize(hold.fuse, hold.nparts, big, hold.fix.on ? &hold.fix : nullptr, ctx->stream));
-    }
+    if (int rc = finish_held_fold(ctx, hold)) return rc;
     if (int rc = calc_xr_launch(ctx, x, r, p, w, 0.0, o, dev_rr, dev_pw)) return rc;
     return calc_p_launch(ctx, p, r, 0.0, dev_rr_new, dev_rr);
   }
@@ -3958,12 +4016,7 @@ extern "C" int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat
   TailArgs a{};
   a.f = hold.fuse;
   a.nparts = hold.nparts;
-  if (hold.nparts > 8192u) {  // launch_fuse_finalize's rule for many partials
-    uint32_t nb = (hold.nparts + 2047u) / 2048u;
-    if (nb > 64u) nb = 64u;
-    a.fold_nb = nb;
-    a.fold_chunk = (hold.nparts + nb - 1u) / nb;
-  }
+  if (hold.nparts > 8192u) a.fold_nb = fold_grid(hold.nparts, &a.fold_chunk);  // launch_fuse_finalize's rule for many partials
   a.fx = hold.fix;
   a.o = o;
   a.rr = dev_rr;
@@ -3987,43 +4040,13 @@ extern "C" int abft_hip_cg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matri
                                                double *dev_pw, double *dev_rr_new, double threshold) {
   const char *what = "cg_iteration_until";
   if (int rc = bind(ctx)) return rc;  // a pending x update applied, a speculation voided
-  if (!mat || !vec || !x || !r || !p || !w) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
-  if (!dev_rr || !dev_pw || !dev_rr_new) return set_err(ABFT_ERR_INVALID, "%s: null device scalar", what);
-  if (part != ABFT_PART_ALL && part != ABFT_PART_BOUNDARY)
-    return set_err(ABFT_ERR_INVALID, "%s: part %d (the interior part goes through abft_hip_spmv_dot_part_dev)", what, part);
-  // one rank only: a frozen rank would leave its peers waiting at the board
-  if (ctx->peers.attached)
-    return set_err(ABFT_ERR_INVALID, "%s: a peer board is attached; the guarded iteration runs on one rank", what);
-  auto apart = [](const double *a, const double *b) { return a + 2 <= b || b + 2 <= a; };
-  if (!apart(dev_rr, dev_pw) || !apart(dev_rr, dev_rr_new) || !apart(dev_pw, dev_rr_new))
-    return set_err(ABFT_ERR_INVALID, "%s: the scalar pairs overlap", what);
-  if (int rc = check_same(x, r, what)) return rc;
-  if (int rc = check_same(x, p, what)) return rc;
-  if (int rc = check_same(x, w, what)) return rc;
+  if (int rc = check_guarded_iteration(ctx, what, mat, vec, vec_offset, part, x, r, p, w, false, nullptr, dev_rr, dev_pw,
+                                       dev_rr_new))
+    return rc;
   const int n = x->n;
-  const uint32_t n_out = mat->fmt == ABFT_FMT_CSR ? mat->csr.n_out : mat->coo.n_out;
-  if ((uint32_t)n != n_out)
-    return set_err(ABFT_ERR_INVALID, "%s: vectors of %d entries for a matrix of %u rows", what, n, n_out);
-  if (vec_offset < 0 || (uint64_t)vec_offset + n_out > (uint64_t)vec->n)
-    return set_err(ABFT_ERR_INVALID, "%s: window [%d,%llu) outside the input vector of %d", what, vec_offset,
-                   (unsigned long long)vec_offset + n_out, vec->n);
-  if (n > 0) {
-    if (!disjoint(x, r) || !disjoint(x, p) || !disjoint(x, w) || !disjoint(r, p) || !disjoint(r, w) || !disjoint(p, w))
-      return set_err(ABFT_ERR_INVALID, "%s: x, r, p and w overlap", what);
-    if (!disjoint(vec, x) || !disjoint(vec, r) || !disjoint(vec, w))
-      return set_err(ABFT_ERR_INVALID, "%s: the input vector overlaps x, r or w", what);
-    if (!disjoint(vec, p) && p->d != vec->d + vec_offset)  // (the vector the SpMV read, or a vector apart from it)
-      return set_err(ABFT_ERR_INVALID, "%s: p overlaps the input vector without being its window", what);
-  }
   HeldFold hold;
   if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold)) return rc;
-  if (hold.held) {
-    KernelTimer t(ctx, ABFT_K_DOT);
-    ReduceOut big{};
-    big.partials = ctx->partials; big.ticket = ctx->ticket; big.dev_out = hold.fuse.dev_out; big.host = hold.fuse.host;
-    big.ev_count = hold.fuse.ev_count; big.seq = hold.fuse.seq; big.peers = hold.fuse.peers;
-    HIPCHK(launch_fuse_finalize(hold.fuse, hold.nparts, big, hold.fix.on ? &hold.fix : nullptr, ctx->stream));
-  }
+  if (int rc = finish_held_fold(ctx, hold)) return rc;
   const ReduceOut o = reduce_out(ctx, dev_rr_new, false);
   {
     KernelTimer t(ctx, ABFT_K_CALC_XR);
@@ -4047,39 +4070,10 @@ extern "C" int abft_hip_pcg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matr
                                                 double threshold) {
   const char *what = "pcg_iteration_until";
   if (int rc = bind(ctx)) return rc;  // a pending x update applied, a speculation voided
-  if (!mat || !vec || !x || !r || !p || !w || !dinv) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
-  if (!dev_in || !dev_pw || !dev_out) return set_err(ABFT_ERR_INVALID, "%s: null device scalar", what);
-  if (part != ABFT_PART_ALL && part != ABFT_PART_BOUNDARY)
-    return set_err(ABFT_ERR_INVALID, "%s: part %d (the interior part goes through abft_hip_spmv_dot_part_dev)", what, part);
-  // one rank only: a frozen rank would leave its peers waiting at the board
-  if (ctx->peers.attached)
-    return set_err(ABFT_ERR_INVALID, "%s: a peer board is attached; the guarded iteration runs on one rank", what);
-  // two records of four doubles and the pair of the SpMV
-  auto apart = [](const double *a, int na, const double *b, int nb) { return a + na <= b || b + nb <= a; };
-  if (!apart(dev_in, 4, dev_pw, 2) || !apart(dev_in, 4, dev_out, 4) || !apart(dev_pw, 2, dev_out, 4))
-    return set_err(ABFT_ERR_INVALID, "%s: the scalar records overlap", what);
-  if (int rc = check_same(x, r, what)) return rc;
-  if (int rc = check_same(x, p, what)) return rc;
-  if (int rc = check_same(x, w, what)) return rc;
+  if (int rc = check_guarded_iteration(ctx, what, mat, vec, vec_offset, part, x, r, p, w, true, dinv, dev_in, dev_pw,
+                                       dev_out))
+    return rc;
   const int n = x->n;
-  const uint32_t n_out = mat->fmt == ABFT_FMT_CSR ? mat->csr.n_out : mat->coo.n_out;
-  if ((uint32_t)n != n_out)
-    return set_err(ABFT_ERR_INVALID, "%s: vectors of %d entries for a matrix of %u rows", what, n, n_out);
-  if (dinv->n != n)
-    return set_err(ABFT_ERR_INVALID, "%s: dinv of %d entries for vectors of %d", what, dinv->n, n);
-  if (vec_offset < 0 || (uint64_t)vec_offset + n_out > (uint64_t)vec->n)
-    return set_err(ABFT_ERR_INVALID, "%s: window [%d,%llu) outside the input vector of %d", what, vec_offset,
-                   (unsigned long long)vec_offset + n_out, vec->n);
-  if (n > 0) {
-    if (!disjoint(x, r) || !disjoint(x, p) || !disjoint(x, w) || !disjoint(r, p) || !disjoint(r, w) || !disjoint(p, w))
-      return set_err(ABFT_ERR_INVALID, "%s: x, r, p and w overlap", what);
-    if (!disjoint(vec, x) || !disjoint(vec, r) || !disjoint(vec, w))
-      return set_err(ABFT_ERR_INVALID, "%s: the input vector overlaps x, r or w", what);
-    if (!disjoint(vec, p) && p->d != vec->d + vec_offset)  // (the vector the SpMV read, or a vector apart from it)
-      return set_err(ABFT_ERR_INVALID, "%s: p overlaps the input vector without being its window", what);
-    if (!disjoint(dinv, x) || !disjoint(dinv, r) || !disjoint(dinv, p) || !disjoint(dinv, w) || !disjoint(dinv, vec))
-      return set_err(ABFT_ERR_INVALID, "%s: dinv overlaps x, r, p, w or the input vector", what);
-  }
   // the reduction's partials are allocated on first use, which a capturing stream does not allow
   if (ctx->capturing && !ctx->bslot)
     return set_err(ABFT_ERR_INVALID, "%s: called under graph capture before the context's block partials exist; make "
@@ -4088,13 +4082,7 @@ extern "C" int abft_hip_pcg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matr
   spec_forget(ctx);  // (as every preconditioned entry: the learned iteration names these vectors by handle)
   HeldFold hold;
   if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold)) return rc;
-  if (hold.held) {
-    KernelTimer t(ctx, ABFT_K_DOT);
-    ReduceOut big{};
-    big.partials = ctx->partials; big.ticket = ctx->ticket; big.dev_out = hold.fuse.dev_out; big.host = hold.fuse.host;
-    big.ev_count = hold.fuse.ev_count; big.seq = hold.fuse.seq; big.peers = hold.fuse.peers;
-    HIPCHK(launch_fuse_finalize(hold.fuse, hold.nparts, big, hold.fix.on ? &hold.fix : nullptr, ctx->stream));
-  }
+  if (int rc = finish_held_fold(ctx, hold)) return rc;
   ReduceOutD o{};
   o.partials = ctx->bpartials;
   o.ticket = ctx->ticket;

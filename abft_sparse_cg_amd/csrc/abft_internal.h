@@ -377,6 +377,9 @@ hipError_t launch_spmv_coo_panels(int mode, const CooDev &A, const CsrPanels &P,
 // (`big`: where a multi-workgroup fold of many partials meets; see fold_partials_kernel)
 struct FixArgs;
 hipError_t launch_fuse_finalize(const FuseOut &f, uint32_t nblk, const ReduceOut &big, const FixArgs *fix, hipStream_t s);
+// the grid of a multi-workgroup fold of nblk partials (-> workgroups, *chunk partials each): launch_fuse_finalize's
+// many-partials path, launch_spmm_fold and launch_spmm_fold_dev all use it
+uint32_t fold_grid(uint32_t nblk, uint32_t *chunk);
 // vecc: x and y hold protected elements (abft_hip_spmv_vecc)
 hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
                            const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s,

@@ -3416,21 +3416,40 @@ __device__ __forceinline__ void reduce_finish(double block_value, const ReduceOu
 // workgroups: one workgroup reads at one CU's bandwidth and took 8-10 us.  Each
 // workgroup adds a contiguous chunk in a fixed order, then the chunks' sums meet
 // through the same last-arriver protocol as every other reduction.
+
+// One column's sum over this workgroup's chunk [lo, hi) of the partials at pj, in a fixed order.  The one body of
+// fold_partials_kernel, spmm_fold_kernel and spmm_fold_dev_kernel.
+__device__ __forceinline__ double fold_chunk_sum(const double *__restrict__ pj, uint32_t lo, uint32_t hi) {
+  double a = 0.0;
+  for (uint32_t i = lo + threadIdx.x; i < hi; i += 4u * ABFT_BLOCK) {
+    double v[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const uint32_t q = i + (uint32_t)u * ABFT_BLOCK;
+      v[u] = q < hi ? pj[q] : 0.0;
+    }
+    a += (v[0] + v[1]) + (v[2] + v[3]);
+  }
+  return a;
+}
+
+// The grid of a multi-workgroup fold of nblk partials: one workgroup per 2048 partials, 64 at most, each with a
+// contiguous chunk.  The one rule of fold_partials_kernel, spmm_fold_kernel, spmm_fold_dev_kernel and the fold that
+// abft_hip_cg_iteration_dev releases after its SpMV.
+uint32_t fold_grid(uint32_t nblk, uint32_t *chunk) {
+  uint32_t nb = (nblk + 2047u) / 2048u;
+  if (nb < 1u) nb = 1u;
+  if (nb > 64u) nb = 64u;
+  *chunk = (nblk + nb - 1u) / nb;
+  return nb;
+}
+
 __global__ __launch_bounds__(ABFT_BLOCK) void fold_partials_kernel(const double *__restrict__ parts, uint32_t n,
                                                                    uint32_t chunk, ReduceOut out, FixArgs fx) {
   __shared__ double s_w[4];
   if (fx.on && blockIdx.x == 0) coo_fixup_body(fx);  // workgroup 0 owns partial 0, which the fix-up corrects
   const uint32_t lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
-  double acc = 0.0;
-  for (uint32_t i = lo + threadIdx.x; i < hi; i += 4u * ABFT_BLOCK) {
-    double v[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const uint32_t j = i + (uint32_t)k * ABFT_BLOCK;
-      v[k] = j < hi ? parts[j] : 0.0;
-    }
-    acc += (v[0] + v[1]) + (v[2] + v[3]);
-  }
+  double acc = fold_chunk_sum(parts, lo, hi);
   acc = block_sum(acc, s_w);
   reduce_finish(acc, out, s_w);
 }
@@ -3443,9 +3462,8 @@ hipError_t launch_fuse_finalize(const FuseOut &f, uint32_t nblk, const ReduceOut
     hipLaunchKernelGGL(fuse_finalize_kernel, dim3(1), dim3(1024), 0, s, f, nblk, fx);
     return hipGetLastError();
   }
-  uint32_t nb = (nblk + 2047u) / 2048u;
-  if (nb > 64u) nb = 64u;
-  const uint32_t chunk = (nblk + nb - 1u) / nb;
+  uint32_t chunk;
+  const uint32_t nb = fold_grid(nblk, &chunk);
   hipLaunchKernelGGL(fold_partials_kernel, dim3(nb), dim3(ABFT_BLOCK), 0, s, f.partials, nblk, chunk, big, fx);
   return hipGetLastError();
 }
@@ -3579,14 +3597,12 @@ hipError_t launch_calc_p(double *p, const double *r, double beta, const double *
 // (calc_px_kernel: 40 N instead of 24 N) -- p is read once per iteration, 8 N bytes
 // less traffic, every x[i] and p[i] the same bits (same operands, same two roundings).
 
+// The walk of calc_r_kernel and calc_r_until_kernel: r_out = r - alpha w over the grid, -> this thread's serial sum of
+// the new r's squares.  ONE body, so that the guarded kernel cannot drift from the one it must match bit for bit.
 // (r_out: where the updated r goes -- r itself, or the shadow buffer of a speculated iteration, abft_hip.hip "speculation")
 template <int VEC>
-__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_kernel(const double *r, const double *__restrict__ w,
-                                                            double alpha, const double *num, const double *den,
-                                                            double *alpha_out, int n, ReduceOut out, double *r_out) {
-  __shared__ double s_w[4];
-  if (num) alpha = *num / *den;
-  if (alpha_out && blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;  // for the deferred x += alpha p
+__device__ __forceinline__ double calc_r_walk(const double *r, const double *__restrict__ w, double alpha, int n,
+                                              double *r_out) {
   double acc = 0.0;
   const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
   for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
@@ -3616,18 +3632,26 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_kernel(const double *r, con
       acc += rs * rs;
     }
   }
+  return acc;
+}
+
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_kernel(const double *r, const double *__restrict__ w,
+                                                            double alpha, const double *num, const double *den,
+                                                            double *alpha_out, int n, ReduceOut out, double *r_out) {
+  __shared__ double s_w[4];
+  if (num) alpha = *num / *den;
+  if (alpha_out && blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;  // for the deferred x += alpha p
+  double acc = calc_r_walk<VEC>(r, w, alpha, n, r_out);
   acc = block_sum(acc, s_w);
   reduce_finish(acc, out, s_w);
 }
 
+// The walk of calc_px_kernel and calc_px_until_kernel: x_out = x + alpha p, p_out = r + beta p, p read once.
 // (p_out, x_out: where the new p and x go -- p and x themselves, or the shadow buffers of a speculated iteration)
 template <int VEC>
-__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_kernel(const double *p, const double *__restrict__ r,
-                                                             const double *x, double beta,
-                                                             const double *num, const double *den, double alpha,
-                                                             const double *alpha_ptr, int n, double *p_out, double *x_out) {
-  if (num) beta = *num / *den;
-  if (alpha_ptr) alpha = *alpha_ptr;
+__device__ __forceinline__ void calc_px_walk(const double *p, const double *__restrict__ r, const double *x,
+                                             double beta, double alpha, int n, double *p_out, double *x_out) {
   const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
   for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
     if (VEC == 2 && i + 1 < n) {
@@ -3675,6 +3699,16 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_kernel(const double *p, co
       p_out[i] = r[i] + beta * pv;
     }
   }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_kernel(const double *p, const double *__restrict__ r,
+                                                             const double *x, double beta,
+                                                             const double *num, const double *den, double alpha,
+                                                             const double *alpha_ptr, int n, double *p_out, double *x_out) {
+  if (num) beta = *num / *den;
+  if (alpha_ptr) alpha = *alpha_ptr;
+  calc_px_walk<VEC>(p, r, x, beta, alpha, n, p_out, x_out);
 }
 
 // the deferred x += alpha p on its own, when something other than calc_p comes next
@@ -3740,7 +3774,8 @@ hipError_t launch_axpy(double *x, const double *p, double alpha, const double *a
 // returns before it touches a vector, a partial or the ticket, and one thread of the r half writes the new
 // pair {the bits of *rr, queued events}.  Every thread of both launches reads the same word, which neither
 // writes, so the decision is uniform over the grid and the same in both; no workgroup waits for another.
-// (Kernels of their own and not a template flag on the two above: those keep their symbols and their code.)
+// (Kernels with symbols of their own and not a template flag on the two above; the streaming loop is the one body
+// calc_r_walk / calc_px_walk, called with r_out = r, p_out = p, x_out = x.)
 template <int VEC>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_until_kernel(double *r, const double *__restrict__ w,
                                                                   const double *rr, const double *pw,
@@ -3757,28 +3792,7 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_until_kernel(double *r, con
   }
   const double alpha = *rr / *pw;
   if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;  // for the x half
-  double acc = 0.0;
-  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
-  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
-    if (VEC == 2 && i + 1 < n) {
-      double2 rv = *reinterpret_cast<const double2 *>(r + i);
-#if ABFT_CFG_DEAD_NT & 1
-      typedef double v2d __attribute__((ext_vector_type(2)));
-      const v2d wl = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(w + i));
-      const double2 wv = make_double2(wl.x, wl.y);
-#else
-      const double2 wv = *reinterpret_cast<const double2 *>(w + i);
-#endif
-      rv.x -= alpha * wv.x; rv.y -= alpha * wv.y;
-      *reinterpret_cast<double2 *>(r + i) = rv;
-      acc += rv.x * rv.x;
-      acc += rv.y * rv.y;
-    } else {
-      const double rs = r[i] - alpha * w[i];
-      r[i] = rs;
-      acc += rs * rs;
-    }
-  }
+  double acc = calc_r_walk<VEC>(r, w, alpha, n, r);
   acc = block_sum(acc, s_w);
   reduce_finish(acc, out, s_w);
 }
@@ -3792,45 +3806,7 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_until_kernel(double *p, co
   if (!(rr0 > threshold)) return;
   const double beta = *rr_new / rr0;
   const double alpha = *alpha_ptr;
-  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
-  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
-    if (VEC == 2 && i + 1 < n) {
-#if ABFT_CFG_X_NT || (ABFT_CFG_DEAD_NT & 6)
-      typedef double v2d __attribute__((ext_vector_type(2)));
-#endif
-#if ABFT_CFG_DEAD_NT & 4
-      const v2d pl = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(p + i));
-      double2 pv = make_double2(pl.x, pl.y);
-#else
-      double2 pv = *reinterpret_cast<const double2 *>(p + i);
-#endif
-#if ABFT_CFG_X_NT
-      const v2d xl = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(x + i));
-      double2 xv = make_double2(xl.x, xl.y);
-#else
-      double2 xv = *reinterpret_cast<const double2 *>(x + i);
-#endif
-#if ABFT_CFG_DEAD_NT & 2
-      const v2d rl = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(r + i));
-      const double2 rv = make_double2(rl.x, rl.y);
-#else
-      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
-#endif
-      xv.x += alpha * pv.x; xv.y += alpha * pv.y;
-      pv.x = rv.x + beta * pv.x;
-      pv.y = rv.y + beta * pv.y;
-#if ABFT_CFG_X_NT
-      __builtin_nontemporal_store(v2d{xv.x, xv.y}, reinterpret_cast<v2d *>(x + i));
-#else
-      *reinterpret_cast<double2 *>(x + i) = xv;
-#endif
-      *reinterpret_cast<double2 *>(p + i) = pv;
-    } else {
-      const double pv = p[i];
-      x[i] = x[i] + alpha * pv;
-      p[i] = r[i] + beta * pv;
-    }
-  }
+  calc_px_walk<VEC>(p, r, x, beta, alpha, n, p, x);
 }
 
 // (the walk is chosen over all four operands in both launches, as launch_calc_r's is: r.r is summed in the same order)
@@ -3890,10 +3866,17 @@ __device__ __forceinline__ void block_store(double *p, const double *v) {
   }
 }
 
-// reduce_finish for K values: K partials per block, one ticket, K fixed-order folds
-// (Out: ReduceOutK, or ReduceOutW for the 2K sums of a block residual check)
-template <int K, class Out = ReduceOutK>
-__device__ __forceinline__ void reduce_finish_k(const double *value, const Out &o, double *s_w) {
+// reduce_finish for K values: K partials per block, one ticket, K fixed-order folds.  The ONE routine every K-wide
+// reduction goes through: block sums, partial stores, the drained ticket, the last-arriving block's fixed-order folds.
+// -> true in the last-arriving block with the K totals (valid in every thread's copy, as block_sum leaves them),
+// false elsewhere.  Thread 0 of that block then publishes: reduce_rearm, and one of the publishers below, which
+// differ only in where the totals go.  (Out: ReduceOutK, ReduceOutW, ReduceOutD or ReduceOutB)
+// (Last: the type the answer comes back in, bool or uint32_t -- the same answer.  It is here for the register
+// allocator alone: with uint32_t the kernels that publish a ReduceOutB record get the branch on s_last as a scalar
+// one and 2-6 fewer VGPRs, as they had with a routine of their own; with bool every pinned-slot kernel keeps the
+// instructions it had.  DESIGN 5i has the table.)
+template <int K, class Out, class Last = bool>
+__device__ __forceinline__ Last reduce_totals_k(const double *value, const Out &o, double *s_w, double *tot) {
   __shared__ uint32_t s_last;
   double bv[K];
 #pragma unroll
@@ -3907,8 +3890,7 @@ __device__ __forceinline__ void reduce_finish_k(const double *value, const Out &
     s_last = reduce_take_ticket(o.ticket);
   }
   __syncthreads();
-  if (!s_last) return;
-  double tot[K];
+  if (!s_last) return Last(0);
 #pragma unroll
   for (int j = 0; j < K; j++) {
     double acc = 0.0;
@@ -3916,15 +3898,53 @@ __device__ __forceinline__ void reduce_finish_k(const double *value, const Out &
       acc += __hip_atomic_load(o.partials + (size_t)j * ABFT_MAX_PARTIALS + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     tot[j] = block_sum(acc, s_w + 4 * (K + j));
   }
-  if (threadIdx.x == 0) {
-    const uint32_t nev = __hip_atomic_load(o.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(o.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+  return Last(1);
+}
+
+// the publishing thread's first two steps: -> the queued-event count, the ticket ready for the next launch
+template <class Out>
+__device__ __forceinline__ uint32_t reduce_rearm(const Out &o) {
+  const uint32_t nev = __hip_atomic_load(o.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(o.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return nev;
+}
+
+// publisher: the K totals and the event count into the K-wide pinned slot
+// (Out: ReduceOutK, or ReduceOutW for the 2K sums of a block residual check)
+template <int K, class Out = ReduceOutK>
+__device__ __forceinline__ void reduce_finish_k(const double *value, const Out &o, double *s_w) {
+  double tot[K];
+  if (!reduce_totals_k<K>(value, o, s_w, tot) || threadIdx.x != 0) return;
+  const uint32_t nev = reduce_rearm(o);
 #pragma unroll
-    for (int j = 0; j < K; j++)
-      __hip_atomic_store(&o.host->value[j], tot[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(&o.host->evcount, nev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_store(&o.host->seq, o.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  for (int j = 0; j < K; j++)
+    __hip_atomic_store(&o.host->value[j], tot[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&o.host->evcount, nev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __hip_atomic_store(&o.host->seq, o.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// publisher: two totals, value[0] = r.z and value[1] = r.r, into the device record of four doubles
+__device__ __forceinline__ void reduce_finish_d(const double *value, const ReduceOutD &o, double *s_w) {
+  double tot[2];
+  if (!reduce_totals_k<2>(value, o, s_w, tot) || threadIdx.x != 0) return;
+  const uint32_t nev = reduce_rearm(o);
+  o.dev_out[0] = tot[1];
+  o.dev_out[1] = (double)nev;
+  o.dev_out[2] = tot[0];
+  o.dev_out[3] = 0.0;
+}
+
+// publisher: the K totals and the event count into the block record {K totals, queued events}
+template <int K>
+__device__ __forceinline__ void reduce_finish_b(const double *value, const ReduceOutB &o, double *s_w) {
+  double tot[K];
+  if (!reduce_totals_k<K, ReduceOutB, uint32_t>(value, o, s_w, tot)) return;
+  if (threadIdx.x == 0) {
+    const uint32_t nev = reduce_rearm(o);
+#pragma unroll
+    for (int j = 0; j < K; j++) o.dev_out[j] = tot[j];
+    o.dev_out[K] = (double)nev;
   }
 }
 
@@ -4299,16 +4319,14 @@ __global__ __launch_bounds__(ABFT_BLOCK) void precond_start_kernel(const double 
   reduce_finish_k<2>(acc, out, s_w);
 }
 
-// r -= alpha w; {r.z, r.r} of the new r.  XHALF = false walks as calc_r_kernel<VEC> does (x += alpha p
-// is left to the calc_p_precond that follows), XHALF = true as calc_xr_kernel<VEC> with x += alpha p.
+// r -= alpha w; {r.z, r.r} of the new r added to acc.  XHALF = false walks as calc_r_kernel<VEC> does (x += alpha p
+// is left to the calc_p_precond that follows), XHALF = true as calc_xr_kernel<VEC> with x += alpha p.  The one body
+// of calc_xr_precond_kernel and, as its XHALF = false instance, of calc_r_precond_until_kernel.
 // (x, r: no __restrict__ -- operands that alias each other take the XHALF form)
 template <int VEC, bool PAIRS, bool XHALF>
-__global__ __launch_bounds__(ABFT_BLOCK) void calc_xr_precond_kernel(double *x, double *r, const double *p,
-                                                                     const double *w,
-                                                                     const double *__restrict__ dinv, double alpha,
-                                                                     int n, ReduceOutK out) {
-  __shared__ double s_w[16];
-  double acc[2] = {0.0, 0.0};
+__device__ __forceinline__ void calc_xr_precond_walk(double *x, double *r, const double *p, const double *w,
+                                                     const double *__restrict__ dinv, double alpha, int n,
+                                                     double *acc) {
   const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
   for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
     if (VEC == 2 && i + 1 < n) {
@@ -4338,18 +4356,27 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_xr_precond_kernel(double *x, 
       acc[1] += rs * rs;
     }
   }
+}
+
+template <int VEC, bool PAIRS, bool XHALF>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_xr_precond_kernel(double *x, double *r, const double *p,
+                                                                     const double *w,
+                                                                     const double *__restrict__ dinv, double alpha,
+                                                                     int n, ReduceOutK out) {
+  __shared__ double s_w[16];
+  double acc[2] = {0.0, 0.0};
+  calc_xr_precond_walk<VEC, PAIRS, XHALF>(x, r, p, w, dinv, alpha, n, acc);
   reduce_finish_k<2>(acc, out, s_w);
 }
 
 // p = z + beta p, z recomputed from the operands calc_xr_precond multiplied (the same bits).  XHALF:
 // with the x += alpha p the preceding calc_xr_precond left behind, walking as calc_px_kernel<VEC> does
-// (p as calc_xr saw it); else as calc_p_kernel<VEC>.
+// (p as calc_xr saw it); else as calc_p_kernel<VEC>.  The one body of calc_p_precond_kernel and, as its
+// XHALF = true instance, of calc_px_precond_until_kernel.
 template <int VEC, bool PAIRS, bool XHALF>
-__global__ __launch_bounds__(ABFT_BLOCK) void calc_p_precond_kernel(double *__restrict__ p,
-                                                                    const double *__restrict__ r,
-                                                                    const double *__restrict__ dinv,
-                                                                    double *__restrict__ x, double beta, double alpha,
-                                                                    int n) {
+__device__ __forceinline__ void calc_p_precond_walk(double *__restrict__ p, const double *__restrict__ r,
+                                                    const double *__restrict__ dinv, double *__restrict__ x,
+                                                    double beta, double alpha, int n) {
   const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
   for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
     if (VEC == 2 && i + 1 < n) {
@@ -4374,15 +4401,27 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_p_precond_kernel(double *__re
   }
 }
 
+template <int VEC, bool PAIRS, bool XHALF>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_p_precond_kernel(double *__restrict__ p,
+                                                                    const double *__restrict__ r,
+                                                                    const double *__restrict__ dinv,
+                                                                    double *__restrict__ x, double beta, double alpha,
+                                                                    int n) {
+  calc_p_precond_walk<VEC, PAIRS, XHALF>(p, r, dinv, x, beta, alpha, n);
+}
+
 // VEC and PAIRS of one launch: `vec2` the alignment test of the plain kernel's operands, `pairs` that of the rest
-#define ABFT_PRECOND_DISPATCH(KERNEL, XH, ...)                                                              \
+// (MORE: the kernel's template arguments after VEC and PAIRS, in parentheses: `(, true)` / `(, false)` for XHALF, `()`
+// for the guarded kernels, which have none)
+#define ABFT_UNPAREN(...) __VA_ARGS__
+#define ABFT_PRECOND_DISPATCH(KERNEL, MORE, ...)                                                            \
   do {                                                                                                      \
     if (!vec2)                                                                                              \
-      hipLaunchKernelGGL((KERNEL<1, false, XH>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);            \
+      hipLaunchKernelGGL((KERNEL<1, false ABFT_UNPAREN MORE>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);            \
     else if (pairs)                                                                                         \
-      hipLaunchKernelGGL((KERNEL<2, true, XH>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);             \
+      hipLaunchKernelGGL((KERNEL<2, true ABFT_UNPAREN MORE>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);             \
     else                                                                                                    \
-      hipLaunchKernelGGL((KERNEL<2, false, XH>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);            \
+      hipLaunchKernelGGL((KERNEL<2, false ABFT_UNPAREN MORE>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);            \
   } while (0)
 
 hipError_t launch_precond_start(const double *r, const double *dinv, double *p, int n, const ReduceOutK &out,
@@ -4404,10 +4443,10 @@ hipError_t launch_calc_xr_precond(double *x, double *r, const double *p, const d
   const bool pairs = aligned16(dinv);
   if (x) {
     const bool vec2 = aligned16(x, r, p, w);
-    ABFT_PRECOND_DISPATCH(calc_xr_precond_kernel, true, x, r, p, w, dinv, alpha, n, out);
+    ABFT_PRECOND_DISPATCH(calc_xr_precond_kernel, (, true), x, r, p, w, dinv, alpha, n, out);
   } else {
     const bool vec2 = aligned16(r, w);
-    ABFT_PRECOND_DISPATCH(calc_xr_precond_kernel, false, x, r, p, w, dinv, alpha, n, out);
+    ABFT_PRECOND_DISPATCH(calc_xr_precond_kernel, (, false), x, r, p, w, dinv, alpha, n, out);
   }
   return hipGetLastError();
 }
@@ -4420,14 +4459,13 @@ hipError_t launch_calc_p_precond(double *p, const double *r, const double *dinv,
   const bool pairs = aligned16(dinv);
   if (x) {
     const bool vec2 = aligned16(p, r, x);
-    ABFT_PRECOND_DISPATCH(calc_p_precond_kernel, true, p, r, dinv, x, beta, alpha, n);
+    ABFT_PRECOND_DISPATCH(calc_p_precond_kernel, (, true), p, r, dinv, x, beta, alpha, n);
   } else {
     const bool vec2 = aligned16(p, r);
-    ABFT_PRECOND_DISPATCH(calc_p_precond_kernel, false, p, r, dinv, x, beta, alpha, n);
+    ABFT_PRECOND_DISPATCH(calc_p_precond_kernel, (, false), p, r, dinv, x, beta, alpha, n);
   }
   return hipGetLastError();
 }
-#undef ABFT_PRECOND_DISPATCH
 
 // ---- the guarded preconditioned iteration (abft_hip_pcg_iteration_until_dev) ----
 // calc_xr_precond_kernel<VEC, PAIRS, false> and calc_p_precond_kernel<VEC, PAIRS, true> behind the stop test of
@@ -4437,42 +4475,8 @@ hipError_t launch_calc_p_precond(double *p, const double *r, const double *dinv,
 // FROZEN: every thread returns before it touches a vector, a partial or the ticket, and one thread of the r half
 // hands the record on.  Both launches read the same word in[0], which neither writes: the decision is uniform
 // over the grid and the same in both; no workgroup waits for another.
-// (Kernels of their own, as the plain guarded pair: the unguarded ones keep their symbols and their code.)
-
-// reduce_finish_k<2> that leaves its two totals on the device: value[0] = r.z, value[1] = r.r
-__device__ __forceinline__ void reduce_finish_d(const double *value, const ReduceOutD &o, double *s_w) {
-  __shared__ uint32_t s_last;
-  double bv[2];
-#pragma unroll
-  for (int j = 0; j < 2; j++) bv[j] = block_sum(value[j], s_w + 4 * j);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-      __hip_atomic_store(o.partials + (size_t)j * ABFT_MAX_PARTIALS + blockIdx.x, bv[j], __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    s_last = reduce_take_ticket(o.ticket);
-  }
-  __syncthreads();
-  if (!s_last) return;
-  double tot[2];
-#pragma unroll
-  for (int j = 0; j < 2; j++) {
-    double acc = 0.0;
-    for (uint32_t i = threadIdx.x; i < gridDim.x; i += ABFT_BLOCK)  // fixed order
-      acc += __hip_atomic_load(o.partials + (size_t)j * ABFT_MAX_PARTIALS + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    tot[j] = block_sum(acc, s_w + 4 * (2 + j));
-  }
-  if (threadIdx.x == 0) {
-    const uint32_t nev = __hip_atomic_load(o.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(o.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
-    o.dev_out[0] = tot[1];
-    o.dev_out[1] = (double)nev;
-    o.dev_out[2] = tot[0];
-    o.dev_out[3] = 0.0;
-  }
-}
-
+// (Symbols of their own, as the plain guarded pair; the streaming loops are calc_xr_precond_walk<.., false> and
+// calc_p_precond_walk<.., true>, and the sums meet through reduce_totals_k as the unguarded kernel's do.)
 template <int VEC, bool PAIRS>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_precond_until_kernel(double *r, const double *w,
                                                                           const double *__restrict__ dinv,
@@ -4496,28 +4500,7 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_precond_until_kernel(double
   const double alpha = in[2] / *pw;
   if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;  // for the x / p half
   double acc[2] = {0.0, 0.0};
-  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
-  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
-    if (VEC == 2 && i + 1 < n) {
-      double2 rv = *reinterpret_cast<const double2 *>(r + i);
-      const double2 wv = *reinterpret_cast<const double2 *>(w + i);
-      const double2 dv = pair_load<PAIRS>(dinv, i);
-      rv.x -= alpha * wv.x; rv.y -= alpha * wv.y;
-      *reinterpret_cast<double2 *>(r + i) = rv;
-      const double zx = dv.x * rv.x, zy = dv.y * rv.y;
-      acc[0] += rv.x * zx;
-      acc[0] += rv.y * zy;
-      acc[1] += rv.x * rv.x;
-      acc[1] += rv.y * rv.y;
-    } else {
-      const double d = dinv[i];
-      const double rs = r[i] - alpha * w[i];
-      r[i] = rs;
-      const double z = d * rs;
-      acc[0] += rs * z;
-      acc[1] += rs * rs;
-    }
-  }
+  calc_xr_precond_walk<VEC, PAIRS, false>(nullptr, r, nullptr, w, dinv, alpha, n, acc);
   reduce_finish_d(acc, out, s_w);
 }
 
@@ -4532,46 +4515,17 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_precond_until_kernel(doubl
   if (!(in[0] > threshold)) return;
   const double beta = out[2] / in[2];
   const double alpha = *alpha_ptr;
-  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
-  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
-    if (VEC == 2 && i + 1 < n) {
-      double2 pv = *reinterpret_cast<const double2 *>(p + i);
-      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
-      const double2 dv = pair_load<PAIRS>(dinv, i);
-      double2 xv = *reinterpret_cast<const double2 *>(x + i);
-      xv.x += alpha * pv.x; xv.y += alpha * pv.y;
-      *reinterpret_cast<double2 *>(x + i) = xv;
-      const double zx = dv.x * rv.x, zy = dv.y * rv.y;
-      pv.x = zx + beta * pv.x;
-      pv.y = zy + beta * pv.y;
-      *reinterpret_cast<double2 *>(p + i) = pv;
-    } else {
-      const double ps = p[i];
-      const double z = dinv[i] * r[i];
-      x[i] = x[i] + alpha * ps;
-      p[i] = z + beta * ps;
-    }
-  }
+  calc_p_precond_walk<VEC, PAIRS, true>(p, r, dinv, x, beta, alpha, n);
 }
 
 // VEC and PAIRS as launch_calc_xr_precond(x == nullptr) and launch_calc_p_precond(x != nullptr) choose them:
 // the sums are added in the same order
-#define ABFT_PCG_UNTIL_DISPATCH(KERNEL, ...)                                                           \
-  do {                                                                                                 \
-    if (!vec2)                                                                                         \
-      hipLaunchKernelGGL((KERNEL<1, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);           \
-    else if (pairs)                                                                                    \
-      hipLaunchKernelGGL((KERNEL<2, true>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);            \
-    else                                                                                               \
-      hipLaunchKernelGGL((KERNEL<2, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);           \
-  } while (0)
-
 hipError_t launch_calc_r_precond_until(double *r, const double *w, const double *dinv, const double *in,
                                        const double *pw, double threshold, double *alpha_out, int n,
                                        const ReduceOutD &out, hipStream_t s) {
   const int nb = reduce_blocks(n);
   const bool vec2 = aligned16(r, w), pairs = aligned16(dinv);
-  ABFT_PCG_UNTIL_DISPATCH(calc_r_precond_until_kernel, r, w, dinv, in, pw, threshold, alpha_out, n, out);
+  ABFT_PRECOND_DISPATCH(calc_r_precond_until_kernel, (), r, w, dinv, in, pw, threshold, alpha_out, n, out);
   return hipGetLastError();
 }
 
@@ -4581,10 +4535,11 @@ hipError_t launch_calc_px_precond_until(double *p, const double *r, const double
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
   const bool vec2 = aligned16(p, r, x), pairs = aligned16(dinv);
-  ABFT_PCG_UNTIL_DISPATCH(calc_px_precond_until_kernel, p, r, dinv, x, in, out, threshold, alpha_ptr, n);
+  ABFT_PRECOND_DISPATCH(calc_px_precond_until_kernel, (), p, r, dinv, x, in, out, threshold, alpha_ptr, n);
   return hipGetLastError();
 }
-#undef ABFT_PCG_UNTIL_DISPATCH
+#undef ABFT_PRECOND_DISPATCH
+#undef ABFT_UNPAREN
 
 // Block forms: one thread per row over the K columns, as the block kernels above; dinv[i] is loaded
 // once per row (one operator for all columns).  A column whose bit is clear keeps its bits (a
@@ -4712,6 +4667,7 @@ hipError_t launch_calc_p_precond_block(double *p, const double *r, const double 
 // Fold of the K * nblk partials spmm_csr_kernel<.., DOT> left (column j's at parts + j * n): fold_partials_kernel's
 // shape per column -- every workgroup adds a contiguous chunk in a fixed order -- and the chunk sums meet through
 // reduce_finish_k, which publishes the K totals in the K-wide pinned slot.
+// (fold_chunk_sum: the chunk sums, written once for spmm_fold_kernel, spmm_fold_dev_kernel and fold_partials_kernel)
 template <int K>
 __global__ __launch_bounds__(ABFT_BLOCK) void spmm_fold_kernel(const double *__restrict__ parts, uint32_t n,
                                                                uint32_t chunk, ReduceOutK out) {
@@ -4719,28 +4675,13 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmm_fold_kernel(const double *__r
   const uint32_t lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
   double acc[K];
 #pragma unroll
-  for (int j = 0; j < K; j++) {
-    const double *pj = parts + (size_t)j * n;
-    double a = 0.0;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += 4u * ABFT_BLOCK) {
-      double v[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const uint32_t q = i + (uint32_t)u * ABFT_BLOCK;
-        v[u] = q < hi ? pj[q] : 0.0;
-      }
-      a += (v[0] + v[1]) + (v[2] + v[3]);
-    }
-    acc[j] = a;
-  }
+  for (int j = 0; j < K; j++) acc[j] = fold_chunk_sum(parts + (size_t)j * n, lo, hi);
   reduce_finish_k<K>(acc, out, s_w);
 }
 
 hipError_t launch_spmm_fold(const double *parts, uint32_t nblk, int k, const ReduceOutK &out, hipStream_t s) {
-  uint32_t nb = (nblk + 2047u) / 2048u;
-  if (nb < 1u) nb = 1u;
-  if (nb > 64u) nb = 64u;
-  const uint32_t chunk = (nblk + nb - 1u) / nb;
+  uint32_t chunk;
+  const uint32_t nb = fold_grid(nblk, &chunk);
 #define ABFT_OP(K) hipLaunchKernelGGL(spmm_fold_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, parts, nblk, chunk, out)
   ABFT_BLOCK_K_DISPATCH(ABFT_OP)
 #undef ABFT_OP
@@ -4753,16 +4694,12 @@ hipError_t launch_spmm_fold(const double *parts, uint32_t nblk, int k, const Red
 template <bool PRECOND> struct BlockSumsOut { typedef ReduceOutK type; };
 template <> struct BlockSumsOut<true> { typedef ReduceOutW type; };
 
+// (calc_r_block_walk: the one body of calc_r_block_kernel and calc_r_block_until_kernel.  alpha: K scalars, the
+// kernel argument's array or the guarded kernel's own)
 template <int K, bool PRECOND>
-__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_kernel(double *__restrict__ r, const double *__restrict__ w,
-                                                                  const double *__restrict__ dinv, BlockScalars alpha,
-                                                                  uint32_t active, int n,
-                                                                  typename BlockSumsOut<PRECOND>::type out) {
-  constexpr int S = PRECOND ? 2 * K : K;
-  __shared__ double s_w[8 * S];
-  double acc[S];
-#pragma unroll
-  for (int j = 0; j < S; j++) acc[j] = 0.0;
+__device__ __forceinline__ void calc_r_block_walk(double *__restrict__ r, const double *__restrict__ w,
+                                                  const double *__restrict__ dinv, const double *alpha,
+                                                  uint32_t active, int n, double *acc) {
   const long stride = (long)gridDim.x * ABFT_BLOCK;
   for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
     double rv[K], wv[K];
@@ -4771,7 +4708,7 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_kernel(double *__rest
     block_load<K>(w + i * K, wv);
 #pragma unroll
     for (int j = 0; j < K; j++) {
-      const double rs = rv[j] - alpha.v[j] * wv[j];  // calc_xr_block_kernel's two roundings
+      const double rs = rv[j] - alpha[j] * wv[j];  // calc_xr_block_kernel's two roundings
       rv[j] = ((active >> j) & 1u) ? rs : rv[j];
       if (PRECOND) {
         const double z = d * rv[j];
@@ -4783,16 +4720,29 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_kernel(double *__rest
     }
     block_store<K>(r + i * K, rv);
   }
+}
+
+template <int K, bool PRECOND>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_kernel(double *__restrict__ r, const double *__restrict__ w,
+                                                                  const double *__restrict__ dinv, BlockScalars alpha,
+                                                                  uint32_t active, int n,
+                                                                  typename BlockSumsOut<PRECOND>::type out) {
+  constexpr int S = PRECOND ? 2 * K : K;
+  __shared__ double s_w[8 * S];
+  double acc[S];
+#pragma unroll
+  for (int j = 0; j < S; j++) acc[j] = 0.0;
+  calc_r_block_walk<K, PRECOND>(r, w, dinv, alpha.v, active, n, acc);
   reduce_finish_k<S>(acc, out, s_w);
 }
 
 // x += alpha p and p = r + beta p (PRECOND: p = dinv * r + beta p) in one pass, p read once: the x half of
 // calc_xr_block_kernel and calc_p_block_kernel (or their precond forms), the same operands and roundings.
+// (calc_px_block_walk: the one body of calc_px_block_kernel and calc_px_block_until_kernel)
 template <int K, bool PRECOND>
-__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_kernel(double *__restrict__ x, double *__restrict__ p,
-                                                                   const double *__restrict__ r,
-                                                                   const double *__restrict__ dinv, BlockScalars alpha,
-                                                                   BlockScalars beta, uint32_t active, int n) {
+__device__ __forceinline__ void calc_px_block_walk(double *__restrict__ x, double *__restrict__ p,
+                                                   const double *__restrict__ r, const double *__restrict__ dinv,
+                                                   const double *alpha, const double *beta, uint32_t active, int n) {
   const long stride = (long)gridDim.x * ABFT_BLOCK;
   for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
     double xv[K], pv[K], rv[K];
@@ -4803,15 +4753,23 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_kernel(double *__res
 #pragma unroll
     for (int j = 0; j < K; j++) {
       const bool on = (active >> j) & 1u;
-      const double xs = xv[j] + alpha.v[j] * pv[j];
+      const double xs = xv[j] + alpha[j] * pv[j];
       const double z = PRECOND ? d * rv[j] : rv[j];
-      const double ps = z + beta.v[j] * pv[j];
+      const double ps = z + beta[j] * pv[j];
       xv[j] = on ? xs : xv[j];
       pv[j] = on ? ps : pv[j];
     }
     block_store<K>(x + i * K, xv);
     block_store<K>(p + i * K, pv);
   }
+}
+
+template <int K, bool PRECOND>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_kernel(double *__restrict__ x, double *__restrict__ p,
+                                                                   const double *__restrict__ r,
+                                                                   const double *__restrict__ dinv, BlockScalars alpha,
+                                                                   BlockScalars beta, uint32_t active, int n) {
+  calc_px_block_walk<K, PRECOND>(x, p, r, dinv, alpha.v, beta.v, active, n);
 }
 
 hipError_t launch_calc_r_block(double *r, const double *w, int n, int k, const BlockScalars &alpha, uint32_t active,
@@ -4862,36 +4820,8 @@ hipError_t launch_calc_px_block(double *x, double *p, const double *r, const dou
 // With no column live every thread returns before it touches a vector, a partial or the ticket, and one thread of
 // the r half hands the record on.  Both halves form the mask from the same words of `in`, which neither writes: the
 // decision is uniform over the grid and the same in both launches; no workgroup waits for another.
-// (Kernels of their own, as the single guarded pairs: the unguarded ones keep their symbols and their code.)
-
-// reduce_finish_k<S> up to the S totals, which stay with the last-arriving block: -> 1 there (tot valid in every
-// thread's copy as block_sum leaves it), 0 elsewhere.  The same partials, ticket and fixed-order folds.
-template <int S>
-__device__ __forceinline__ uint32_t reduce_totals_dev(const double *value, double *partials, uint32_t *ticket,
-                                                      double *s_w, double *tot) {
-  __shared__ uint32_t s_last;
-  double bv[S];
-#pragma unroll
-  for (int j = 0; j < S; j++) bv[j] = block_sum(value[j], s_w + 4 * j);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int j = 0; j < S; j++)
-      __hip_atomic_store(partials + (size_t)j * ABFT_MAX_PARTIALS + blockIdx.x, bv[j], __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    s_last = reduce_take_ticket(ticket);
-  }
-  __syncthreads();
-  if (!s_last) return 0u;
-#pragma unroll
-  for (int j = 0; j < S; j++) {
-    double acc = 0.0;
-    for (uint32_t i = threadIdx.x; i < gridDim.x; i += ABFT_BLOCK)  // fixed order
-      acc += __hip_atomic_load(partials + (size_t)j * ABFT_MAX_PARTIALS + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    tot[j] = block_sum(acc, s_w + 4 * (S + j));
-  }
-  return 1u;
-}
+// (Symbols of their own, as the single guarded pairs; the chunk sums are fold_chunk_sum, the streaming loops
+// calc_r_block_walk / calc_px_block_walk, and the sums meet through reduce_totals_k as the unguarded kernels' do.)
 
 // spmm_fold_kernel<K> leaving {K totals, queued events} in dev_pw instead of the pinned slot
 template <int K>
@@ -4901,36 +4831,13 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmm_fold_dev_kernel(const double 
   const uint32_t lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
   double acc[K];
 #pragma unroll
-  for (int j = 0; j < K; j++) {
-    const double *pj = parts + (size_t)j * n;
-    double a = 0.0;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += 4u * ABFT_BLOCK) {
-      double v[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const uint32_t q = i + (uint32_t)u * ABFT_BLOCK;
-        v[u] = q < hi ? pj[q] : 0.0;
-      }
-      a += (v[0] + v[1]) + (v[2] + v[3]);
-    }
-    acc[j] = a;
-  }
-  double tot[K];
-  if (!reduce_totals_dev<K>(acc, out.partials, out.ticket, s_w, tot)) return;
-  if (threadIdx.x == 0) {
-    const uint32_t nev = __hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(out.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
-#pragma unroll
-    for (int j = 0; j < K; j++) out.dev_out[j] = tot[j];
-    out.dev_out[K] = (double)nev;
-  }
+  for (int j = 0; j < K; j++) acc[j] = fold_chunk_sum(parts + (size_t)j * n, lo, hi);
+  reduce_finish_b<K>(acc, out, s_w);
 }
 
 hipError_t launch_spmm_fold_dev(const double *parts, uint32_t nblk, int k, const ReduceOutB &out, hipStream_t s) {
-  uint32_t nb = (nblk + 2047u) / 2048u;  // launch_spmm_fold's grid and chunks
-  if (nb < 1u) nb = 1u;
-  if (nb > 64u) nb = 64u;
-  const uint32_t chunk = (nblk + nb - 1u) / nb;
+  uint32_t chunk;
+  const uint32_t nb = fold_grid(nblk, &chunk);  // launch_spmm_fold's grid and chunks
 #define ABFT_OP(K) hipLaunchKernelGGL(spmm_fold_dev_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, parts, nblk, chunk, out)
   ABFT_BLOCK_K_DISPATCH(ABFT_OP)
 #undef ABFT_OP
@@ -4988,44 +4895,23 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_until_kernel(double *
   double acc[S];
 #pragma unroll
   for (int j = 0; j < S; j++) acc[j] = 0.0;
-  const long stride = (long)gridDim.x * ABFT_BLOCK;
-  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
-    double rv[K], wv[K];
-    const double d = PRECOND ? dinv[i] : 0.0;
-    block_load<K>(r + i * K, rv);
-    block_load<K>(w + i * K, wv);
-#pragma unroll
-    for (int j = 0; j < K; j++) {
-      const double rs = rv[j] - alpha[j] * wv[j];  // calc_r_block_kernel's two roundings
-      rv[j] = ((active >> j) & 1u) ? rs : rv[j];
-      if (PRECOND) {
-        const double z = d * rv[j];
-        acc[2 * j] += rv[j] * z;
-        acc[2 * j + 1] += rv[j] * rv[j];
-      } else {
-        acc[j] += rv[j] * rv[j];
-      }
-    }
-    block_store<K>(r + i * K, rv);
-  }
+  calc_r_block_walk<K, PRECOND>(r, w, dinv, alpha, active, n, acc);
+  // the hand-off: the record of 2K + 2 words, which mixes new sums and old words by the mask, is this kernel's own
   double tot[S];
-  if (!reduce_totals_dev<S>(acc, out.partials, out.ticket, s_w, tot)) return;
-  if (threadIdx.x == 0) {
-    const uint32_t nev = __hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(out.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+  if (!reduce_totals_k<S, ReduceOutB, uint32_t>(acc, out, s_w, tot) || threadIdx.x != 0) return;
+  const uint32_t nev = reduce_rearm(out);
 #pragma unroll
-    for (int j = 0; j < K; j++) {
-      // a live column's new sums; a frozen one's words as they were read, not the recomputed sums
-      const unsigned long long rr_new = __double_as_longlong(PRECOND ? tot[2 * j + 1] : tot[j]);
-      const unsigned long long rz_new = PRECOND ? (unsigned long long)__double_as_longlong(tot[2 * j]) : rr_new;
-      const bool on = (active >> j) & 1u;
-      const unsigned long long rr_old = src[j], rz_old = src[K + j];
-      dst[j] = on ? rr_new : rr_old;
-      dst[K + j] = on ? rz_new : rz_old;
-    }
-    out.dev_out[2 * K] = (double)nev;
-    out.dev_out[2 * K + 1] = 0.0;
+  for (int j = 0; j < K; j++) {
+    // a live column's new sums; a frozen one's words as they were read, not the recomputed sums
+    const unsigned long long rr_new = __double_as_longlong(PRECOND ? tot[2 * j + 1] : tot[j]);
+    const unsigned long long rz_new = PRECOND ? (unsigned long long)__double_as_longlong(tot[2 * j]) : rr_new;
+    const bool on = (active >> j) & 1u;
+    const unsigned long long rr_old = src[j], rz_old = src[K + j];
+    dst[j] = on ? rr_new : rr_old;
+    dst[K + j] = on ? rz_new : rz_old;
   }
+  out.dev_out[2 * K] = (double)nev;
+  out.dev_out[2 * K + 1] = 0.0;
 }
 
 // (in: the record the iteration started from -- the mask, and beta's denominators; out: what the r half left)
@@ -5044,25 +4930,7 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_until_kernel(double 
     alpha[j] = alpha_ptr[j];
     beta[j] = uniform_f64(out[K + j] / in[K + j]);
   }
-  const long stride = (long)gridDim.x * ABFT_BLOCK;
-  for (long i = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
-    double xv[K], pv[K], rv[K];
-    const double d = PRECOND ? dinv[i] : 0.0;
-    block_load<K>(x + i * K, xv);
-    block_load<K>(p + i * K, pv);
-    block_load<K>(r + i * K, rv);
-#pragma unroll
-    for (int j = 0; j < K; j++) {
-      const bool on = (active >> j) & 1u;
-      const double xs = xv[j] + alpha[j] * pv[j];
-      const double z = PRECOND ? d * rv[j] : rv[j];
-      const double ps = z + beta[j] * pv[j];
-      xv[j] = on ? xs : xv[j];
-      pv[j] = on ? ps : pv[j];
-    }
-    block_store<K>(x + i * K, xv);
-    block_store<K>(p + i * K, pv);
-  }
+  calc_px_block_walk<K, PRECOND>(x, p, r, dinv, alpha, beta, active, n);
 }
 
 hipError_t launch_calc_r_block_until(double *r, const double *w, const double *dinv, const double *in,

@@ -607,7 +607,8 @@ int abft_hip_set_sharers(abft_hip_ctx *ctx, int processes);
  * aliasing another; ABFT_HIP_TAIL=0 keeps the three kernels).  p is the
  * caller's view of vec's slot (the vector the SpMV read).  Enqueue-only: capturable.
  * The order in which r.r is summed: see abft_hip_calc_xr_ratio_dev above.
- * abft_hip_tail_stats tells which form a call took. */
+ * abft_hip_tail_stats tells which form a call took.  x, r, p or w missing or of different lengths:
+ * ABFT_ERR_INVALID before anything is launched (w and dev_pw keep what they held). */
 int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec, int vec_offset,
                               int part, abft_hip_vector *x, abft_hip_vector *r, abft_hip_vector *p,
                               abft_hip_vector *w, const double *dev_rr, double *dev_pw, double *dev_rr_new);

@@ -647,3 +647,32 @@ def test_scalars_in_edge_states(n, align, sharers, path, monkeypatch):
             assert all(np.isfinite(post[key]).all() for key in ("x", "r", "pfull", "w", "sc"))
     finally:
         dev.close()
+
+
+def test_a_refused_call_has_launched_nothing():
+    """abft_hip_cg_iteration_dev with an r of 63 entries for a matrix of 64 rows: ABFT_ERR_INVALID, decided on the
+    host before the SpMV -- which would overwrite w and hold the fold of p.w back -- so every word of w, x, r, p and of
+    the pair dev_pw keeps the bits it had"""
+    import abft_sparse_cg_amd as amd
+    from abft_sparse_cg_amd import capi
+    n = 64
+    cols, rows, vals, _ = tri(n)
+    ctx = amd.HIPContext("none", "csr")
+    try:
+        A = ctx.create_matrix(cols, rows, vals, n, len(vals))
+        vecs = {"x": ctx.create_vector(n), "r": ctx.create_vector(n - 1), "p": ctx.create_vector(n),
+                "w": ctx.create_vector(n), "sc": ctx.create_vector(6)}
+        for v in vecs.values():
+            ctx.upload(v, np.full(v.N, SENTINEL))
+        base = vecs["sc"].device_ptr
+        rc = ctx.L.abft_hip_cg_iteration_dev(ctx.h, A.h, vecs["p"].h, 0, capi.PART_ALL, vecs["x"].h, vecs["r"].h,
+                                             vecs["p"].h, vecs["w"].h, base, base + 32, base + 16)
+        assert rc == -1, rc  # ABFT_ERR_INVALID
+        assert b"lengths differ" in ctx.L.abft_hip_last_error()
+        ctx.synchronize()
+        want = bits(np.array([SENTINEL]))[0]
+        for name, v in vecs.items():
+            got = bits(ctx.download(v))
+            assert got.shape == (v.N,) and (got == want).all(), (name, got)
+    finally:
+        ctx.close()
