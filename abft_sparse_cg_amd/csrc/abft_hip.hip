@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "abft_internal.h"
+#include "loop_state.h"
 
 // ------------------------------------------------------------------ errors --
 
@@ -51,14 +52,19 @@ struct ProfSlot {
 
 static constexpr uint32_t ABFT_HOST_SLOTS = 4;  // result slots in the pinned ring
 
-struct abft_hip_ctx {
+// (LoopState, loop_state.h: what the context keeps between the calls of the host-scalar CG loop -- the fused product,
+// the deferred and the pending x update, the caller's iteration, the speculation, the run-ahead -- and the switches)
+struct abft_hip_ctx : LoopState {
+  abft_hip_ctx() {
+    xin_modes = ABFT_X_IN_SPMV_MODES;
+    ahead.level = ABFT_AHEAD_DEFAULT;
+  }
   int device = 0;
   int num_cus = 256;
   hipStream_t own_stream = nullptr, stream = nullptr;
   double *partials = nullptr;  // ABFT_MAX_PARTIALS doubles
   uint32_t *ticket = nullptr;  // reduction arrival counter (device)
   unsigned long long *tail_sync = nullptr;  // cg_tail_kernel's hand-off words (device; they only ever grow)
-  bool capturing = false;         // between abft_hip_graph_begin and _end
   bool tail_enabled = true;       // ABFT_HIP_TAIL=0: the iteration's tail as its three kernels
   int tail_cap[3][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}};  // [q: 1, 2, 4 blocks per workgroup][<1>, <2>, <2, fast>]: resident workgroups (asked once)
   int sharers = 1;                // processes that run this library on this device at the same time (abft_hip_set_sharers)
@@ -71,92 +77,10 @@ struct abft_hip_ctx {
   // reductions can be in flight since round 4: the fold of p.w and the speculated r.r behind it)
   HostSlot *host_slot = nullptr;
   HostSlot *host_slot_dev = nullptr;  // its device alias
-  // Speculation (cross-call fusion no. 3, round 4; the host-scalar loop of cg.cpp:97-112): once the library has
-  // seen one iteration -- spmv(A,p,w), [dot(p,w)], calc_xr(x,r,p,w,alpha), calc_p(p,r,beta) -- it enqueues, right
-  // behind the NEXT spmv(A,p,w) and its fold, the r half of that iteration with alpha = rr / p.w formed on the device,
-  // writing into a SHADOW buffer, and -- once calc_xr has been taken over -- the x / p half (x in place, p into a shadow).  When the caller's calc_xr / calc_p
-  // then arrive with the same vectors and bit-identical alpha / beta (the same IEEE quotients of the scalars it was
-  // handed), the shadows are swapped in -- no kernel is launched, the GPU never waited for the host; anything else
-  // drops the shadows and runs the call as written.  Same bits either way.  Opt-in: ABFT_HIP_SPECULATE=1.
-  struct {
-    bool enabled = false;                 // opt-in (ABFT_HIP_SPECULATE=1): see DESIGN.md section 4 for what it measured
-    bool learned = false;                 // x, r, p, w below are the vectors of the last complete iteration
-    abft_hip_vector *x = nullptr, *r = nullptr, *p = nullptr, *w = nullptr;
-    bool have_rr = false;                 // scal[rr_at] holds the scalar last handed to the caller (r.r), whose value is rr_host
-    int rr_at = 0;
-    double rr_host = 0.0;
-    int stage = 0;                        // 0: nothing in flight; 1: both halves enqueued; 2: r committed, x / p pending
-    uint32_t seq_rr = 0;                  // sequence number of the speculated r.r
-    double rr_new_host = 0.0;
-    double *shadow[2] = {nullptr, nullptr};  // r, p
-    int shadow_n = 0;
-    double *scal = nullptr;               // device doubles: [0], [1] r.r (alternating), [2] p.w (+ their event counts behind: 6 doubles)
-    long commits = 0, drops = 0;
-    // Run-ahead (cross-call fusion no. 5; ABFT_HIP_AHEAD=0|1|2, DESIGN.md section 4 "Fifth cross-call fusion"): the same
-    // idea with what x-in-SpMV left to do.  calc_p already writes out of place into xpend's buffer, so level 1 launches
-    // it right behind calc_r, BEFORE the host waits for r.r, with beta = rr_new / rr formed on the device (stage 3);
-    // level 2 also launches calc_r behind the SpMV's fold with alpha = rr / p.w formed on the device, into shadow[0],
-    // and the calc_p behind it (stage 4).  The caller's calc_xr / calc_p commit -- swap the buffers, launch nothing --
-    // when they name the same vectors and alpha / beta are bit for bit the host's quotients of the scalars handed
-    // back (and no NaN: its payload is not the same on both sides); every other entry point drops through bind().
-    // Armed by one complete iteration, run as written, whose alpha and beta were those quotients; a drop or an
-    // iteration with other scalars disarms.  Off with the speculation above and wherever x-in-SpMV is off.
-    int ahead = ABFT_AHEAD_DEFAULT;       // level; stage 3: calc_p in flight, 4: calc_r and calc_p in flight
-    bool a_armed = false;
-    bool a_alpha_ok = false;              // the calc_xr just run was handed rr / p.w on plain vectors (cleared by any entry point but calc_p)
-    double rr_prev = 0.0;                 // the scalar handed back before rr_host: beta's denominator
-    int a_slot = 0;                       // xpend.shadow[a_slot]: where the calc_p in flight writes
-    long a_commit_p = 0, a_commit_r = 0, a_drops = 0;
-  } spec;
   EventRing ring{};                   // device memory
   MovedList moved{};                  // COO elements with a silently corrupted column (device memory)
   int *bits_dev = nullptr;            // scratch for inject (32 ints)
-  // cross-call fusion: the last spmv also produced vec.result (see FuseOut)
-  bool fuse_enabled = true;
-  struct {
-    bool valid = false, have_value = false;
-    bool vecc = false;  // made by abft_hip_spmv_vecc: serves abft_hip_dot_vecc only (and a plain product a plain dot only)
-    const double *x = nullptr, *y = nullptr;
-    int n = 0;
-    uint32_t seq = 0;
-    double value = 0.0;
-  } fused;
-  // cross-call fusion no. 2: calc_xr leaves x += alpha p to the calc_p that follows
-  // it (see kernels.hip, calc_r_kernel); anything else that comes first flushes it
-  bool defer_enabled = true;
-  struct {
-    bool active = false, on_dev = false;
-    double *x = nullptr;
-    const double *p = nullptr;
-    int n = 0;
-    double alpha = 0.0;
-  } defer;
   double *alpha_dev = nullptr;  // alpha of the deferred update when it was formed on the device
-  // cross-call fusion no. 4: in the host-scalar loop spmv(A, p, w), [dot], calc_xr, calc_p the deferred x += alpha p is
-  // the one piece of work nothing waits for, so once the library has seen spmv(A, p, w) directly follow a calc_p that
-  // took a deferred update along (`armed`), that calc_p writes the new p into `shadow`, swaps it with p's buffer and
-  // leaves the update pending on the OLD p (`active`); the predicted spmv(A, p, w) -- streaming CSR, fused product --
-  // applies it row by row under its own memory latency (spmv_csr_kernel<..., XUPD>).  Anything else that comes first
-  // applies it with axpy_kernel (bind) and disarms.  Same bits either way; only when each x[i] is written changes.
-  // ABFT_HIP_X_IN_SPMV=0 / =1; by default on the modes of ABFT_X_IN_SPMV_MODES; off without the deferred update or the fused product, with the
-  // speculation, and from the first graph capture on (a captured launch holds p's buffer by address).
-  bool xin_enabled = true;
-  unsigned xin_modes = ABFT_X_IN_SPMV_MODES;  // bit m: armed on matrices of ECC mode m (ABFT_HIP_X_IN_SPMV=1: every mode)
-  struct {
-    bool armed = false, active = false;
-    const abft_hip_vector *last_p = nullptr;  // set by the calc_p that consumed a deferred update on this p ...
-    const abft_hip_vector *prev_p = nullptr;  // ... and handed to the entry point that follows it directly (bind)
-    double *x = nullptr;                      // the pending update: x += alpha p_old over n elements
-    const double *p_old = nullptr;
-    double alpha = 0.0;
-    int n = 0;
-    const abft_hip_vector *ph = nullptr;      // the handle whose buffer was swapped
-    // context-owned: where the next calc_p writes (the old p while pending).  Two slots by length, so that a caller who
-    // alternates solves of two sizes does not free and allocate (both synchronise the device) at every switch
-    struct { double *buf = nullptr; int n = 0; } shadow[2];
-    int shadow_at = 0;                        // the slot used last
-    long absorbed = 0, flushed = 0;
-  } xpend;
   // block right-hand sides (abft_hip_dot_block, abft_hip_calc_xr_block): allocated by the first such call
   double *bpartials = nullptr;          // 2 * ABFT_MAX_RHS * ABFT_MAX_PARTIALS doubles (the 2K sums of a block check)
   HostSlotK *bslot = nullptr, *bslot_dev = nullptr;  // pinned K-wide result slot, its device alias
@@ -236,17 +160,6 @@ struct abft_hip_matrix {
   std::vector<void *> allocs;
 };
 
-struct abft_hip_vector {
-  abft_hip_ctx *ctx = nullptr;
-  double *d = nullptr;
-  int n = 0;
-  bool owns = true;
-  double *host = nullptr;  // pinned staging for map/unmap
-  abft_hip_vector *root = nullptr;  // the allocation a view looks into (itself for an owner)
-  bool exposed = false;             // root only: the raw device pointer was handed out
-  int views = 0;                    // root only: live views into this allocation
-};
-
 static constexpr uint32_t EVENT_CAP = 1u << 16;
 static constexpr size_t VECC_SEEN_BYTES = ABFT_VECC_SEEN_SLOTS * sizeof(unsigned long long);
 static_assert(sizeof(abft_event) % sizeof(unsigned long long) == 0, "the table behind the events is 8-byte aligned");
@@ -254,67 +167,62 @@ static constexpr uint32_t MOVED_CAP = 4096;
 
 // the pending x += alpha p_old on its own: something other than the predicted SpMV came first
 static int flush_xpend(abft_hip_ctx *ctx) {
-  auto &X = ctx->xpend;
-  if (!X.active) return ABFT_OK;
-  X.active = false;
-  X.armed = false;
-  X.flushed++;
+  if (!pending_flush_due(*ctx)) return ABFT_OK;
+  const auto &X = ctx->xpend;
   HIPCHK(launch_axpy(X.x, X.p_old, X.alpha, nullptr, X.n, ctx->stream));
   return ABFT_OK;
 }
 
 static int flush_deferred(abft_hip_ctx *ctx) {
-  if (!ctx->defer.active) return ABFT_OK;
-  ctx->defer.active = false;
-  HIPCHK(launch_axpy(ctx->defer.x, ctx->defer.p, ctx->defer.alpha, ctx->defer.on_dev ? ctx->alpha_dev : nullptr,
-                     ctx->defer.n, ctx->stream));
+  if (!deferred_flush_due(*ctx)) return ABFT_OK;
+  const auto &D = ctx->defer;
+  HIPCHK(launch_axpy(D.x, D.p, D.alpha, D.on_dev ? ctx->alpha_dev : nullptr, D.n, ctx->stream));
   return ABFT_OK;
 }
 
-// Every entry point starts here.  Unless the caller is the calc_p that can absorb
-// it (keep_deferred), a pending x += alpha p is enqueued first, so no call ever
-// sees x or p in any state the unfused sequence would not have produced.
-static bool same_bits(double a, double b) { return memcmp(&a, &b, sizeof(a)) == 0; }
+// Every entry point starts here.  Unless the caller is the calc_p that can absorb it (KEEP_DEFERRED) or the SpMV that
+// can (KEEP_PENDING), a pending x += alpha p is enqueued first, so no call ever sees x or p in any state the unfused
+// sequence would not have produced; unless it is one of the calls what is in flight waits for (KEEP_FLIGHT), that is
+// dropped.  The flags are loop_state.h's; which entry passes which:
+//
+//   0 (drop, apply both updates)   set_stream, synchronize, synchronize_timeout, matrix_create_* (matrix_create),
+//                                  matrix_compact_stats, matrix_packed_stats, matrix_destroy, matrix_read_csr, _read_coo,
+//                                  _read_element, inject, inject_rowptr, vector_create, vector_map, vector_device_ptr,
+//                                  dot_dev, calc_xr_dev, calc_xr_ratio_dev, peer_exchange_begin, cg_iteration_until_dev,
+//                                  pcg_iteration_until_dev, block_loop_reserve, graph_begin, drain_events, profile_*,
+//                                  stream_probe
+//   FORGET_FUSED                   vector_unmap, vector_copy, graph_launch
+//   FORGET_ITER                    dot_vecc
+//   OTHER_VECTORS                  vector_destroy, matrix_diag_inverse, vector_flip, vector_encode, vector_scrub,
+//    (= FORGET_FUSED | FORGET_ITER)  calc_xr_vecc, calc_p_vecc, spmm, dot_block, calc_xr_block, calc_p_block, copy_block,
+//                                  residual_gap, residual_restart, residual_gap_block, residual_restart_block,
+//                                  spmm_dot, calc_r[_precond]_block, calc_px[_precond]_block, precond_start[_block],
+//                                  calc_xr_precond[_block], calc_p_precond_block, cg_block_iteration_until_dev
+//   KEEP_DEFERRED                  read_pair, write_pair, allreduce_pair_peers, calc_p_ratio_dev, peer_board_attach,
+//                                  _device_alloc, _device_free, _attach_device, _ipc_export, _ipc_attach, _fuse,
+//                                  peer_exchange_attach, _device_alloc, _device_free, _attach_device, _ipc_export,
+//                                  _ipc_attach, _finish
+//   KEEP_DEFERRED | OTHER_VECTORS  calc_p_precond
+//   KEEP_FLIGHT                    dot, calc_xr
+//   KEEP_FLIGHT | KEEP_DEFERRED    calc_p
+//   KEEP_PENDING                   every SpMV (spmv_common): spmv, spmv_dot_dev, spmv_vecc, spmv_part,
+//                                  spmv_dot_part_dev, spmv_dot_range_dev, cg_iteration_dev
+//   no prologue                    init, shutdown, the getters and counters, vector_view, matrix_set_interior,
+//                                  matrix_info, matrix_panels, graph_end, graph_destroy, the detach and *_failed calls
+//
+// An entry that forgets only once its arguments have passed (a refused call leaves the state alone) does so by hand,
+// with forget_fused / forget_iteration behind its checks.
+static constexpr unsigned OTHER_VECTORS = FORGET_FUSED | FORGET_ITER;
 
-// an in-flight speculation is void: its shadow buffers are never looked at again (stage 2: the committed r and the x
-// already updated in place stay -- calc_xr is done; what the caller holds as r.r is the speculated one)
-static void spec_drop(abft_hip_ctx *ctx) {
-  auto &S = ctx->spec;
-  S.a_alpha_ok = false;
-  if (S.stage >= 3) {  // a run-ahead: r (stage 4) and p are untouched, the scalars as the caller holds them
-    S.a_drops++;
-    S.a_armed = false;
-    S.stage = 0;
-    return;
-  }
-  if (S.stage) S.drops++;
-  if (S.stage == 2) {
-    S.rr_at = 1 - S.rr_at;
-    S.rr_host = S.rr_new_host;
-  }
-  S.stage = 0;
-}
-static void spec_forget(abft_hip_ctx *ctx) {
-  spec_drop(ctx);
-  ctx->spec.learned = false;
-  ctx->spec.a_armed = false;
-  ctx->spec.have_rr = false;
-  ctx->spec.x = ctx->spec.r = ctx->spec.p = ctx->spec.w = nullptr;
-}
-
-// (keep_spec: the caller is one of the continuations a speculation waits for -- dot(p, w), calc_xr, calc_p -- and
-// decides itself; every other entry point voids it)
-// (keep_xpend: the caller is the SpMV that may absorb the update pending on the old p; calls that touch no vector keep
-// it as they keep the deferred one)
-static int bind(abft_hip_ctx *ctx, bool keep_deferred = false, bool keep_spec = false, bool keep_xpend = false) {
+static int enter(abft_hip_ctx *ctx, unsigned keep) {
   if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");
   HIPCHK(hipSetDevice(ctx->device));
-  ctx->xpend.prev_p = ctx->xpend.last_p;
-  ctx->xpend.last_p = nullptr;
-  if (!keep_spec) spec_drop(ctx);
-  if (!keep_deferred && !keep_xpend)
+  prologue_begin(*ctx, keep);
+  if (prologue_flushes_pending(keep))
     if (int rc = flush_xpend(ctx)) return rc;
-  if (!keep_deferred) return flush_deferred(ctx);
+  if (prologue_flushes_deferred(keep))
+    if (int rc = flush_deferred(ctx)) return rc;
+  prologue_end(*ctx, keep);
   return ABFT_OK;
 }
 
@@ -465,16 +373,15 @@ extern "C" int abft_hip_init(int device, abft_hip_ctx **out) {
   HIPCHK(hipMalloc((void **)&ctx->alpha_dev, sizeof(double)));
   HIPCHK(hipHostMalloc((void **)&ctx->host_slot, ABFT_HOST_SLOTS * sizeof(HostSlot), hipHostMallocMapped | hipHostMallocCoherent));
   memset(ctx->host_slot, 0, ABFT_HOST_SLOTS * sizeof(HostSlot));
-  HIPCHK(hipMalloc((void **)&ctx->spec.scal, 8 * sizeof(double)));
-  HIPCHK(hipMemset(ctx->spec.scal, 0, 8 * sizeof(double)));
+  HIPCHK(hipMalloc((void **)&ctx->iter.scal, 8 * sizeof(double)));
+  HIPCHK(hipMemset(ctx->iter.scal, 0, 8 * sizeof(double)));
   if (const char *e = getenv("ABFT_HIP_SPECULATE")) ctx->spec.enabled = strcmp(e, "0") != 0;
   if (const char *e = getenv("ABFT_HIP_X_IN_SPMV")) {  // 0: never; 1: on every mode; unset: on the modes it was measured to pay on
     ctx->xin_enabled = strcmp(e, "0") != 0;
     if (ctx->xin_enabled) ctx->xin_modes = ~0u;
   }
-  ctx->xin_enabled = ctx->xin_enabled && ctx->defer_enabled && ctx->fuse_enabled && !ctx->spec.enabled;
-  if (const char *e = getenv("ABFT_HIP_AHEAD")) ctx->spec.ahead = e[0] == '2' ? 2 : e[0] == '1' ? 1 : 0;
-  if (!ctx->xin_enabled) ctx->spec.ahead = 0;  // (it writes where xpend's calc_p writes, and commits by xpend's swap)
+  if (const char *e = getenv("ABFT_HIP_AHEAD")) ctx->ahead.level = e[0] == '2' ? 2 : e[0] == '1' ? 1 : 0;
+  loop_settle_switches(*ctx);  // (speculation on: no x-in-SpMV; no x-in-SpMV: no run-ahead)
   HIPCHK(hipHostGetDevicePointer((void **)&ctx->host_slot_dev, ctx->host_slot, 0));
   // the queue, and behind it the table of vector events already queued (abft_internal.h)
   HIPCHK(hipMalloc((void **)&ctx->ring.buf, EVENT_CAP * sizeof(abft_event) + VECC_SEEN_BYTES));
@@ -534,9 +441,10 @@ extern "C" int abft_hip_shutdown(abft_hip_ctx *ctx) {
   if (ctx->wslot) (void)hipHostFree(ctx->wslot);
   if (getenv("ABFT_HIP_VERBOSE") && (ctx->spec.commits || ctx->spec.drops))
     fprintf(stderr, "hip: speculated iterations: %ld taken over, %ld dropped\n", ctx->spec.commits, ctx->spec.drops);
-  for (double *b : ctx->spec.shadow) (void)hipFree(b);
+  (void)hipFree(ctx->iter.r_shadow.buf);
+  (void)hipFree(ctx->spec.p_shadow.buf);
   for (auto &b : ctx->xpend.shadow) (void)hipFree(b.buf);
-  (void)hipFree(ctx->spec.scal);
+  (void)hipFree(ctx->iter.scal);
   if (!debug_leak('h')) (void)hipHostFree(ctx->host_slot);
   (void)hipFree(ctx->ring.buf);
   (void)hipFree(ctx->ring.count);
@@ -552,7 +460,7 @@ extern "C" int abft_hip_shutdown(abft_hip_ctx *ctx) {
 }
 
 extern "C" int abft_hip_set_stream(abft_hip_ctx *ctx, void *hip_stream) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
   return ABFT_OK;
@@ -561,7 +469,7 @@ extern "C" int abft_hip_set_stream(abft_hip_ctx *ctx, void *hip_stream) {
 extern "C" void *abft_hip_get_stream(abft_hip_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
 
 extern "C" int abft_hip_synchronize(abft_hip_ctx *ctx) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return ABFT_OK;
 }
@@ -569,7 +477,7 @@ extern "C" int abft_hip_synchronize(abft_hip_ctx *ctx) {
 // wait for the stream, but not for ever: ABFT_ERR_HIP with "timed out" if `seconds` pass first
 // (a first replay of a freshly captured graph that holds collectives is waited for this way)
 extern "C" int abft_hip_synchronize_timeout(abft_hip_ctx *ctx, double seconds) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   const auto t0 = std::chrono::steady_clock::now();
   for (;;) {
     const hipError_t q = hipStreamQuery(ctx->stream);
@@ -1518,7 +1426,7 @@ static int create_coo(abft_hip_ctx *ctx, int mode, const uint32_t *columns, cons
 static int create_any(abft_hip_ctx *ctx, int format, int mode, const uint32_t *columns,
                       const uint32_t *rows, const double *values, int n_out, int n_in, int nnz,
                       uint32_t index_base, abft_hip_matrix **out, bool force_stream = false) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   if (!out) return set_err(ABFT_ERR_INVALID, "null out");
   *out = nullptr;
   if (mode < ABFT_MODE_NONE || mode > ABFT_MODE_SECDED) return set_err(ABFT_ERR_INVALID, "unknown mode %d", mode);
@@ -1662,7 +1570,7 @@ extern "C" int abft_hip_matrix_info(abft_hip_matrix *mat, int *layout, int *laun
 extern "C" int abft_hip_matrix_compact_stats(abft_hip_matrix *mat, uint32_t *compact_tiles, uint32_t *tiles,
                                              uint32_t *mismatches) {
   if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
-  if (int rc = bind(mat->ctx)) return rc;
+  if (int rc = enter(mat->ctx, 0)) return rc;
   const bool stream = mat->fmt == ABFT_FMT_CSR && !mat->use_panels && !mat->use_sweep && !mat->use_slice;
   uint32_t nc = 0, bad = 0;
   const std::vector<uint4> &blk = mat->blk_host;
@@ -1693,7 +1601,7 @@ extern "C" int abft_hip_matrix_compact_stats(abft_hip_matrix *mat, uint32_t *com
 extern "C" int abft_hip_matrix_packed_stats(abft_hip_matrix *mat, uint32_t *packed_tiles, uint32_t *tiles,
                                             uint32_t *mismatches) {
   if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
-  if (int rc = bind(mat->ctx)) return rc;
+  if (int rc = enter(mat->ctx, 0)) return rc;
   const bool stream = mat->fmt == ABFT_FMT_CSR && !mat->use_panels && !mat->use_sweep && !mat->use_slice;
   uint32_t np = 0, bad = 0;
   const std::vector<uint4> &blk = mat->blk_host;
@@ -1734,7 +1642,7 @@ extern "C" int abft_hip_matrix_packed_stats(abft_hip_matrix *mat, uint32_t *pack
 
 extern "C" int abft_hip_matrix_destroy(abft_hip_matrix *mat) {
   if (!mat) return ABFT_OK;
-  if (int rc = bind(mat->ctx)) return rc;
+  if (int rc = enter(mat->ctx, 0)) return rc;
   HIPCHK(hipStreamSynchronize(mat->ctx->stream));
   matrix_free(mat);
   return ABFT_OK;
@@ -1743,7 +1651,7 @@ extern "C" int abft_hip_matrix_destroy(abft_hip_matrix *mat) {
 extern "C" int abft_hip_matrix_read_csr(abft_hip_matrix *mat, uint32_t *cols, uint32_t *rowptr,
                                         double *values) {
   if (!mat || mat->fmt != ABFT_FMT_CSR) return set_err(ABFT_ERR_INVALID, "not a CSR matrix");
-  if (int rc = bind(mat->ctx)) return rc;
+  if (int rc = enter(mat->ctx, 0)) return rc;
   hipStream_t s = mat->ctx->stream;
   const CsrDev &A = mat->csr;
   if (rowptr) HIPCHK(hipMemcpyAsync(rowptr, A.rowptr, ((size_t)A.n_out + 1) * 4, hipMemcpyDeviceToHost, s));
@@ -1769,7 +1677,7 @@ extern "C" int abft_hip_matrix_read_csr(abft_hip_matrix *mat, uint32_t *cols, ui
 
 extern "C" int abft_hip_matrix_read_coo(abft_hip_matrix *mat, void *elements) {
   if (!mat || mat->fmt != ABFT_FMT_COO) return set_err(ABFT_ERR_INVALID, "not a COO matrix");
-  if (int rc = bind(mat->ctx)) return rc;
+  if (int rc = enter(mat->ctx, 0)) return rc;
   const CooDev &A = mat->coo;
   if (!elements || !A.nnz) return ABFT_OK;
   std::vector<uint4> stored(A.nnz);
@@ -1786,7 +1694,7 @@ extern "C" int abft_hip_matrix_read_coo(abft_hip_matrix *mat, void *elements) {
 // the stored words of ONE element (the caller's index): 3 for CSR {value lo, value hi, column word}, 4 for COO
 extern "C" int abft_hip_matrix_read_element(abft_hip_matrix *mat, uint32_t index, uint32_t *words) {
   if (!mat || !words) return set_err(ABFT_ERR_INVALID, "null argument");
-  if (int rc = bind(mat->ctx)) return rc;
+  if (int rc = enter(mat->ctx, 0)) return rc;
   const uint32_t nnz = mat->fmt == ABFT_FMT_CSR ? mat->csr.nnz : mat->coo.nnz;
   if (index >= nnz) return set_err(ABFT_ERR_INVALID, "element index %u outside [0,%u)", index, nnz);
   hipStream_t s = mat->ctx->stream;
@@ -1808,7 +1716,7 @@ extern "C" int abft_hip_matrix_read_element(abft_hip_matrix *mat, uint32_t index
 
 extern "C" int abft_hip_inject(abft_hip_matrix *mat, uint32_t index, const int *bits, int nbits) {
   if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
-  if (int rc = bind(mat->ctx)) return rc;
+  if (int rc = enter(mat->ctx, 0)) return rc;
   const uint32_t nnz = mat->fmt == ABFT_FMT_CSR ? mat->csr.nnz : mat->coo.nnz;
   const int width = mat->fmt == ABFT_FMT_CSR ? 96 : 128;
   if (index >= nnz) return set_err(ABFT_ERR_INVALID, "element index %u outside [0,%u)", index, nnz);
@@ -1838,7 +1746,7 @@ extern "C" int abft_hip_inject(abft_hip_matrix *mat, uint32_t index, const int *
 // additive entry XORs `mask` into rowptr[row] so that those two checks can be exercised.
 extern "C" int abft_hip_inject_rowptr(abft_hip_matrix *mat, uint32_t row, uint32_t mask) {
   if (!mat || mat->fmt != ABFT_FMT_CSR) return set_err(ABFT_ERR_INVALID, "not a CSR matrix");
-  if (int rc = bind(mat->ctx)) return rc;
+  if (int rc = enter(mat->ctx, 0)) return rc;
   if (row > mat->csr.n_out) return set_err(ABFT_ERR_INVALID, "row pointer %u outside [0,%u]", row, mat->csr.n_out);
   hipStream_t s = mat->ctx->stream;
   uint32_t v = 0;
@@ -1854,7 +1762,7 @@ extern "C" int abft_hip_inject_rowptr(abft_hip_matrix *mat, uint32_t row, uint32
 // ------------------------------------------------------------------ vectors --
 
 extern "C" int abft_hip_vector_create(abft_hip_ctx *ctx, int N, abft_hip_vector **vec) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   if (!vec || N < 0) return set_err(ABFT_ERR_INVALID, "bad vector arguments");
   abft_hip_vector *v = new (std::nothrow) abft_hip_vector();
   if (!v) return set_err(ABFT_ERR_NOMEM, "vector allocation failed");
@@ -1882,9 +1790,7 @@ extern "C" int abft_hip_vector_view(abft_hip_vector *parent, int offset, int N, 
 
 extern "C" int abft_hip_vector_destroy(abft_hip_vector *vec) {
   if (!vec) return ABFT_OK;
-  if (int rc = bind(vec->ctx)) return rc;
-  vec->ctx->fused.valid = false;
-  spec_forget(vec->ctx);  // (the learned iteration names vectors by handle)
+  if (int rc = enter(vec->ctx, OTHER_VECTORS)) return rc;  // (the learned iteration names vectors by handle)
   HIPCHK(hipStreamSynchronize(vec->ctx->stream));
   if (!vec->owns && vec->root) vec->root->views--;
   if (vec->host && !debug_leak('v')) (void)hipHostFree(vec->host);
@@ -1895,7 +1801,7 @@ extern "C" int abft_hip_vector_destroy(abft_hip_vector *vec) {
 
 extern "C" int abft_hip_vector_map(abft_hip_vector *vec, double **host) {
   if (!vec || !host) return set_err(ABFT_ERR_INVALID, "null argument");
-  if (int rc = bind(vec->ctx)) return rc;
+  if (int rc = enter(vec->ctx, 0)) return rc;
   if (!vec->host) HIPCHK(hipHostMalloc((void **)&vec->host, ((size_t)vec->n + 1) * sizeof(double), hipHostMallocDefault));
   if (vec->n) HIPCHK(hipMemcpyAsync(vec->host, vec->d, (size_t)vec->n * sizeof(double), hipMemcpyDeviceToHost, vec->ctx->stream));
   HIPCHK(hipStreamSynchronize(vec->ctx->stream));
@@ -1905,8 +1811,7 @@ extern "C" int abft_hip_vector_map(abft_hip_vector *vec, double **host) {
 
 extern "C" int abft_hip_vector_unmap(abft_hip_vector *vec, double *host) {
   if (!vec || !host) return set_err(ABFT_ERR_INVALID, "null argument");
-  if (int rc = bind(vec->ctx)) return rc;
-  vec->ctx->fused.valid = false;
+  if (int rc = enter(vec->ctx, FORGET_FUSED)) return rc;
   if (vec->n) HIPCHK(hipMemcpyAsync(vec->d, host, (size_t)vec->n * sizeof(double), hipMemcpyHostToDevice, vec->ctx->stream));
   if (host != vec->host) HIPCHK(hipStreamSynchronize(vec->ctx->stream));  // caller's buffer: done with it on return
   return ABFT_OK;
@@ -1915,8 +1820,7 @@ extern "C" int abft_hip_vector_unmap(abft_hip_vector *vec, double *host) {
 extern "C" int abft_hip_vector_copy(abft_hip_vector *dst, const abft_hip_vector *src) {
   if (!dst || !src) return set_err(ABFT_ERR_INVALID, "null vector");
   if (src->n < dst->n) return set_err(ABFT_ERR_INVALID, "copy of %d elements from a vector of %d", dst->n, src->n);
-  if (int rc = bind(dst->ctx)) return rc;
-  dst->ctx->fused.valid = false;
+  if (int rc = enter(dst->ctx, FORGET_FUSED)) return rc;
   if (dst->d != src->d) HIPCHK(launch_copy(dst->d, src->d, dst->n, dst->ctx->stream));
   return ABFT_OK;
 }
@@ -1925,7 +1829,7 @@ extern "C" int abft_hip_vector_copy(abft_hip_vector *dst, const abft_hip_vector 
 // library's back, so a pending update is applied now and none is deferred on it again.
 extern "C" void *abft_hip_vector_device_ptr(abft_hip_vector *vec) {
   if (!vec) return nullptr;
-  if (vec->ctx) (void)bind(vec->ctx);  // (a pending x update is applied, a speculation dropped: the caller is about to look)
+  if (vec->ctx) (void)enter(vec->ctx, 0);  // (a pending x update is applied, a speculation dropped: the caller is about to look)
   (vec->root ? vec->root : vec)->exposed = true;
   return vec->d;
 }
@@ -1997,37 +1901,42 @@ static int check_same(const abft_hip_vector *a, const abft_hip_vector *b, const 
   return ABFT_OK;
 }
 
+// the fused product's value, read from its pinned slot once
+static int fused_value(abft_hip_ctx *ctx) {
+  if (ctx->fused.have_value) return ABFT_OK;
+  double v = 0.0;
+  if (int rc = scalar_from_host_slot(ctx, ctx->fused.seq, &v)) return rc;
+  fused_value_read(*ctx, v);
+  return ABFT_OK;
+}
+
 extern "C" int abft_hip_dot(abft_hip_ctx *ctx, const abft_hip_vector *a, const abft_hip_vector *b, double *result) {
-  if (int rc = bind(ctx, false, true)) return rc;  // (a dot served from the fused product leaves a speculation alone)
-  if (int rc = check_same(a, b, "dot")) { spec_drop(ctx); return rc; }
-  if (!result) { spec_drop(ctx); return set_err(ABFT_ERR_INVALID, "null result"); }
+  if (int rc = enter(ctx, KEEP_FLIGHT)) return rc;  // (a dot served from the fused product leaves what is in flight alone)
+  if (int rc = check_same(a, b, "dot")) { drop_in_flight(*ctx); return rc; }
+  if (!result) { drop_in_flight(*ctx); return set_err(ABFT_ERR_INVALID, "null result"); }
   // dot(p, w) right after spmv(A, p, w): the SpMV already formed it
-  if (ctx->fused.valid && !ctx->fused.vecc && a->n == ctx->fused.n &&
-      ((a->d == ctx->fused.x && b->d == ctx->fused.y) || (a->d == ctx->fused.y && b->d == ctx->fused.x))) {
-    if (!ctx->fused.have_value) {
-      if (int rc = scalar_from_host_slot(ctx, ctx->fused.seq, &ctx->fused.value)) return rc;
-      ctx->fused.have_value = true;
-    }
+  if (fused_serves_dot(*ctx, a, b, false)) {
+    if (int rc = fused_value(ctx)) return rc;
     *result = ctx->fused.value;
     return ABFT_OK;
   }
-  spec_drop(ctx);
-  if (!ctx->fused.have_value) ctx->fused.valid = false;  // the slot is about to be reused
+  drop_in_flight(*ctx);
+  fused_slot_reused(*ctx);
   // (the result also stays on the device: if this is the r.r a CG loop starts from, a speculated alpha divides it)
-  auto &S = ctx->spec;
-  const int at = S.have_rr ? 1 - S.rr_at : 0;
-  const ReduceOut o = reduce_out(ctx, S.scal + 2 * at, true);
+  auto &I = ctx->iter;
+  const int at = rr_next_at(I);
+  const ReduceOut o = reduce_out(ctx, I.scal + 2 * at, true);
   {
     KernelTimer t(ctx, ABFT_K_DOT);
     HIPCHK(launch_dot(a->d, b->d, a->n, o, ctx->stream));
   }
-  if (int rc = scalar_from_host_slot(ctx, o.seq, result)) { S.have_rr = false; return rc; }
-  S.have_rr = true; S.rr_at = at; S.rr_host = *result;
+  if (int rc = scalar_from_host_slot(ctx, o.seq, result)) { I.have_rr = false; return rc; }
+  rr_handed(I, at, *result);
   return ABFT_OK;
 }
 
 extern "C" int abft_hip_dot_dev(abft_hip_ctx *ctx, const abft_hip_vector *a, const abft_hip_vector *b, double *dev_result) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   if (int rc = check_same(a, b, "dot")) return rc;
   if (!dev_result) return set_err(ABFT_ERR_INVALID, "null result");
   KernelTimer t(ctx, ABFT_K_DOT);
@@ -2035,9 +1944,7 @@ extern "C" int abft_hip_dot_dev(abft_hip_ctx *ctx, const abft_hip_vector *a, con
   return ABFT_OK;
 }
 
-static bool disjoint(const abft_hip_vector *a, const abft_hip_vector *b) {
-  return a->d + a->n <= b->d || b->d + b->n <= a->d;
-}
+// ---- the host-scalar loop: the GPU work between loop_state.h's decisions and transitions ----
 
 static int calc_xr_launch(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r, const abft_hip_vector *p,
                           const abft_hip_vector *w, double alpha, const ReduceOut &o,
@@ -2045,68 +1952,64 @@ static int calc_xr_launch(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector
   if (int rc = check_same(x, r, "calc_xr")) return rc;
   if (int rc = check_same(x, p, "calc_xr")) return rc;
   if (int rc = check_same(x, w, "calc_xr")) return rc;
-  ctx->fused.valid = false;
-  // x += alpha p can wait for the calc_p that reads the same p next (one pass over p
-  // less per iteration) when nobody can look at x in between: x is not aliased by
-  // any other operand and its raw pointer has never been handed out
-  const bool defer = ctx->defer_enabled && x->n > 0 && !(x->root ? x->root : x)->exposed && disjoint(x, r) &&
-                     disjoint(x, p) && disjoint(x, w) && disjoint(r, p);
+  forget_fused(*ctx);
   KernelTimer t(ctx, ABFT_K_CALC_XR);
-  if (defer) {
+  if (can_defer_x(*ctx, x, r, p, w)) {
     HIPCHK(launch_calc_r(r->d, w->d, alpha, num, den, num ? ctx->alpha_dev : nullptr, x->n, o, ctx->stream, nullptr, x->d, p->d));
-    ctx->defer.active = true;
-    ctx->defer.on_dev = num != nullptr;
-    ctx->defer.x = x->d; ctx->defer.p = p->d; ctx->defer.n = x->n; ctx->defer.alpha = alpha;
+    arm_deferred(*ctx, x, p, alpha, num != nullptr);
     return ABFT_OK;
   }
   HIPCHK(launch_calc_xr(x->d, r->d, p->d, w->d, alpha, num, den, x->n, o, ctx->stream));
   return ABFT_OK;
 }
 
-static bool spec_plain(const abft_hip_vector *v, int n);
+// A context-owned buffer of n (+ 2) doubles, allocated on first use and again when the length changes (both
+// synchronise the device).  False: no room, and no buffer -- the caller switches its own path off for good.
+static void shadow_release(Shadow &s) {
+  (void)hipFree(s.buf);
+  s.buf = nullptr;
+  s.n = 0;
+}
+static bool shadow_ensure(Shadow &s, int n) {
+  if (s.buf && s.n == n) return true;
+  shadow_release(s);
+  if (hipMalloc((void **)&s.buf, ((size_t)n + 2) * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    s.buf = nullptr;
+    return false;
+  }
+  s.n = n;
+  return true;
+}
 
 // the context's buffer for a new p of n entries -> its slot in xpend.shadow, or -1 (no memory: the path is off for good)
 static int xpend_buffer(abft_hip_ctx *ctx, int n) {
   auto &X = ctx->xpend;
-  int at = X.shadow[0].buf && X.shadow[0].n == n ? 0 : X.shadow[1].buf && X.shadow[1].n == n ? 1 : -1;
-  if (at < 0) {  // a length seen for the first time (or a third one): the slot not used last makes room
-    at = X.shadow[X.shadow_at].buf ? 1 - X.shadow_at : X.shadow_at;
-    (void)hipFree(X.shadow[at].buf);
-    X.shadow[at].buf = nullptr;
-    X.shadow[at].n = 0;
-    if (hipMalloc((void **)&X.shadow[at].buf, ((size_t)n + 2) * sizeof(double)) != hipSuccess) {  // no room: as before
-      (void)hipGetLastError();
-      X.shadow[at].buf = nullptr;
-      ctx->xin_enabled = false;
-      return -1;
-    }
-    X.shadow[at].n = n;
+  const int at = pending_shadow_slot(X, n);
+  if (!shadow_ensure(X.shadow[at], n)) {
+    ctx->xin_enabled = false;
+    return -1;
   }
   X.shadow_at = at;
   return at;
 }
 
 // The new p into the context's buffer, the buffers swapped, the deferred x += alpha p left pending on the old one
-// (see abft_hip_ctx::xpend).  False: not now -- the caller runs calc_px as before.
+// (see PendingUpdate).  False: not now -- the caller runs calc_px as before.
 static bool xpend_take(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, double beta, int *rc) {
-  auto &X = ctx->xpend;
   *rc = ABFT_OK;
-  if (!ctx->xin_enabled || !X.armed || X.active || ctx->defer.on_dev || ctx->capturing) return false;
-  // p's handle is the only way to its buffer (a whole root vector, never exposed, no views): the swap goes unseen
-  if (!spec_plain(p, p->n) || !disjoint(p, r)) return false;
+  if (!pending_can_take(*ctx, p, r)) return false;
   const int at = xpend_buffer(ctx, p->n);
   if (at < 0) return false;
   {
     KernelTimer t(ctx, ABFT_K_CALC_P);
-    const hipError_t e = launch_calc_p(p->d, r->d, beta, nullptr, nullptr, p->n, ctx->stream, X.shadow[at].buf);
+    const hipError_t e = launch_calc_p(p->d, r->d, beta, nullptr, nullptr, p->n, ctx->stream, ctx->xpend.shadow[at].buf);
     if (e != hipSuccess) {
       *rc = set_err(ABFT_ERR_HIP, "calc_p: %s", hipGetErrorString(e));
       return true;
     }
   }
-  std::swap(p->d, X.shadow[at].buf);
-  X.active = true;
-  X.x = ctx->defer.x; X.p_old = X.shadow[at].buf; X.alpha = ctx->defer.alpha; X.n = p->n; X.ph = p;
+  adopt_p_leave_pending(*ctx, p, at);
   return true;
 }
 
@@ -2115,11 +2018,9 @@ static int calc_p_launch(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_v
                          const double *num, const double *den) {
   if (int rc = flush_xpend(ctx)) return rc;  // (calc_p twice in a row: the first one's old p is about to go)
   if (int rc = check_same(p, r, "calc_p")) return rc;
-  ctx->fused.valid = false;
+  forget_fused(*ctx);
   if (ctx->defer.active) {
-    abft_hip_vector xv;  // just the range, for the overlap test
-    xv.d = ctx->defer.x; xv.n = ctx->defer.n;
-    if (ctx->defer.p == p->d && ctx->defer.n == p->n && disjoint(&xv, r)) {
+    if (deferred_rides_with(*ctx, p, r)) {
       ctx->defer.active = false;
       if (!num) {
         int rc = ABFT_OK;
@@ -2140,202 +2041,146 @@ static int calc_p_launch(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_v
   return ABFT_OK;
 }
 
-// ---- run-ahead (see abft_hip_ctx::spec) ----
-// the loop's four vectors: whole allocations only the library can see into, of one length, none of them twice
-static bool ahead_plain(const abft_hip_vector *x, const abft_hip_vector *r, const abft_hip_vector *p,
-                        const abft_hip_vector *w) {
-  if (!p || p->n <= 0) return false;
-  const int n = p->n;
-  return spec_plain(x, n) && spec_plain(r, n) && spec_plain(p, n) && spec_plain(w, n) && x != r && x != p && x != w &&
-         r != p && r != w && p != w;
-}
-
-// calc_p(p, r_d, beta = *num / *den) into xpend's buffer: the preconditions of xpend_take (the caller has checked the vectors)
+// run-ahead: calc_p(p, r_d, beta = *num / *den) into xpend's buffer (the caller has asked ahead_wants_p / ahead_wants_rp)
 static bool ahead_p_launch(abft_hip_ctx *ctx, const abft_hip_vector *p, const double *r_d, const double *num,
                            const double *den) {
-  auto &X = ctx->xpend;
-  if (!ctx->xin_enabled || !X.armed || X.active || ctx->capturing) return false;
   const int at = xpend_buffer(ctx, p->n);
   if (at < 0) return false;
   KernelTimer t(ctx, ABFT_K_CALC_P);
-  if (launch_calc_p(p->d, r_d, 0.0, num, den, p->n, ctx->stream, X.shadow[at].buf) != hipSuccess) return false;
-  ctx->spec.a_slot = at;
+  if (launch_calc_p(p->d, r_d, 0.0, num, den, p->n, ctx->stream, ctx->xpend.shadow[at].buf) != hipSuccess) return false;
+  ctx->ahead.slot = at;
   return true;
 }
 
-// behind spmv(A, p, w) + fold (level 2): calc_r into the shadow with alpha = rr / p.w, calc_p from that shadow
-static void ahead_launch(abft_hip_ctx *ctx, const abft_hip_vector *vec, const abft_hip_vector *result) {
-  auto &S = ctx->spec;
-  if (S.ahead < 2 || !S.a_armed || S.stage || !S.have_rr || ctx->defer.active || ctx->capturing) return;
-  if (vec != S.p || result != S.w || !ahead_plain(S.x, S.r, S.p, S.w)) return;
-  if (!ctx->xin_enabled || !ctx->xpend.armed || ctx->xpend.active) return;
+// run-ahead, behind spmv(A, p, w) + fold (level 2): calc_r into the shadow with alpha = rr / p.w, calc_p from that shadow
+static void ahead_launch(abft_hip_ctx *ctx, bool eligible, const abft_hip_vector *vec, const abft_hip_vector *result) {
+  if (!ahead_wants_rp(*ctx, eligible, vec, result)) return;
+  auto &I = ctx->iter;
   const int n = vec->n;
-  if (S.shadow_n != n || !S.shadow[0]) {  // r's shadow, allocated on first use
-    (void)hipFree(S.shadow[0]);
-    S.shadow[0] = nullptr;
-    S.shadow_n = 0;
-    if (hipMalloc((void **)&S.shadow[0], ((size_t)n + 2) * sizeof(double)) != hipSuccess) {  // no room: level 1
-      (void)hipGetLastError();
-      S.shadow[0] = nullptr;
-      S.ahead = 1;
-      return;
-    }
-    S.shadow_n = n;
+  if (!shadow_ensure(I.r_shadow, n)) {  // no room: level 1
+    ctx->ahead.level = 1;
+    return;
   }
   if (xpend_buffer(ctx, n) < 0) return;
-  double *rr = S.scal + 2 * S.rr_at, *rr_new = S.scal + 2 * (1 - S.rr_at), *pw = S.scal + 4;
-  const ReduceOut o = reduce_out(ctx, rr_new, true);  // {r.r, events} to the host ring AND to the device
+  const ScalTriple s = scal_triple(I);
+  const ReduceOut o = reduce_out(ctx, s.rr_new, true);  // {r.r, events} to the host ring AND to the device
   {
     KernelTimer t(ctx, ABFT_K_CALC_XR);
-    if (launch_calc_r(S.r->d, S.w->d, 0.0, rr, pw, nullptr, n, o, ctx->stream, S.shadow[0], S.x->d, S.p->d) != hipSuccess) return;
+    if (launch_calc_r(I.r->d, I.w->d, 0.0, s.rr, s.pw, nullptr, n, o, ctx->stream, I.r_shadow.buf, I.x->d, I.p->d) != hipSuccess) return;
   }
-  S.seq_rr = o.seq;
-  S.stage = 4;
-  if (!ahead_p_launch(ctx, S.p, S.shadow[0], rr_new, rr)) spec_drop(ctx);
+  r_half_launched(*ctx, InFlight::AheadRP, o.seq);
+  if (!ahead_p_launch(ctx, I.p, I.r_shadow.buf, s.rr_new, s.rr)) drop_in_flight(*ctx);
+}
+
+// speculation, behind spmv(A, p, w) + fold: the learned iteration's r half into the shadow
+static int spec_launch(abft_hip_ctx *ctx, const abft_hip_vector *vec, const abft_hip_vector *result) {
+  if (!spec_wants_r(*ctx, vec, result)) return ABFT_OK;
+  auto &I = ctx->iter;
+  auto &S = ctx->spec;
+  const int n = vec->n;
+  if (I.r_shadow.n != n || S.p_shadow.n != n) {
+    shadow_release(I.r_shadow);
+    shadow_release(S.p_shadow);
+    if (!shadow_ensure(I.r_shadow, n) || !shadow_ensure(S.p_shadow, n)) {  // no room: no speculation
+      shadow_release(I.r_shadow);
+      S.enabled = false;
+      return ABFT_OK;
+    }
+  }
+  const ScalTriple s = scal_triple(I);
+  const ReduceOut o = reduce_out(ctx, s.rr_new, true);  // {r.r, events} to the host ring AND to the device
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_r(I.r->d, I.w->d, 0.0, s.rr, s.pw, ctx->alpha_dev, n, o, ctx->stream, I.r_shadow.buf, I.x->d, I.p->d));
+  }
+  // (the x / p half follows when calc_xr has been taken over: from then on x += alpha p is DUE, so x is updated in
+  // place and only p -- whose beta the caller has yet to name -- goes to a shadow.  Both halves out of place from
+  // here cost calc_px 8-10 us: five address streams instead of three)
+  r_half_launched(*ctx, InFlight::SpecR, o.seq);
+  return ABFT_OK;
+}
+
+// ---- abft_hip_calc_xr: one function per outcome of classify_calc_xr ----
+
+static int xr_commit_ahead(abft_hip_ctx *ctx, const XrCall &c, abft_hip_vector *x, abft_hip_vector *r,
+                           const abft_hip_vector *p, double alpha, double *result) {
+  if (int rc = scalar_from_host_slot(ctx, ctx->iter.seq_rr, result)) { drop_in_flight(*ctx); return rc; }
+  commit_ahead_r(*ctx, c, x, r, p, alpha, *result);
+  return ABFT_OK;
+}
+
+// *taken false: alpha was not, bit for bit, the quotient of the two scalars the caller was (or could have been)
+// handed -- r.r and the fused p.w; dropped, the call runs as written
+static int xr_try_spec(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r, const abft_hip_vector *p, double alpha,
+                       double *result, bool *taken) {
+  *taken = fused_value(ctx) == ABFT_OK && alpha_was_rr_over_pw(*ctx, alpha, false);
+  if (!*taken) { drop_in_flight(*ctx); return ABFT_OK; }
+  // enqueue the x / p half BEFORE waiting for r.r: x += alpha p in place (it is due now), p = r + beta p with
+  // beta = r.r_new / r.r formed on the device into the shadow (the caller has yet to name its beta)
+  {
+    const ScalTriple s = scal_triple(ctx->iter);
+    KernelTimer t(ctx, ABFT_K_CALC_P);
+    HIPCHK(launch_calc_px(p->d, ctx->iter.r_shadow.buf, x->d, 0.0, s.rr_new, s.rr, 0.0, ctx->alpha_dev, x->n, ctx->stream,
+                          ctx->spec.p_shadow.buf, nullptr));
+  }
+  if (int rc = scalar_from_host_slot(ctx, ctx->iter.seq_rr, result)) { drop_in_flight(*ctx); return rc; }
+  commit_spec_r(*ctx, r, *result);
+  return ABFT_OK;
+}
+
+static int xr_as_written(abft_hip_ctx *ctx, const XrCall &c, abft_hip_vector *x, abft_hip_vector *r,
+                         const abft_hip_vector *p, const abft_hip_vector *w, double alpha, double *result) {
+  auto &I = ctx->iter;
+  const int at = rr_next_at(I);
+  const ReduceOut o = reduce_out(ctx, I.scal + 2 * at, true);
+  if (int rc = calc_xr_launch(ctx, x, r, p, w, alpha, o)) { I.have_rr = false; return rc; }
+  // level 1: the calc_p that will follow, behind calc_r and before the host waits for r.r
+  const ScalTriple s = scal_triple(I);
+  const bool p_ahead = ahead_wants_p(*ctx, c, p) && ahead_p_launch(ctx, p, r->d, s.rr_new, s.rr);
+  if (int rc = scalar_from_host_slot(ctx, o.seq, result)) { I.have_rr = false; return rc; }
+  calc_xr_ran(*ctx, c, p_ahead, at, *result, x, r, p, w);
+  return ABFT_OK;
 }
 
 extern "C" int abft_hip_calc_xr(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r, const abft_hip_vector *p,
                                 const abft_hip_vector *w, double alpha, double *result) {
-  if (int rc = bind(ctx, false, true)) return rc;
-  if (!result) { spec_drop(ctx); return set_err(ABFT_ERR_INVALID, "null result"); }
-  auto &S = ctx->spec;
-  // was alpha the quotient of the two scalars the caller was handed -- r.r and the fused p.w of spmv(A, p, w)?
-  const bool had_rr = S.have_rr;
-  const double rr_old = S.rr_host;
-  const bool alpha_ok = S.ahead && had_rr && ctx->fused.valid && ctx->fused.have_value && !ctx->fused.vecc && p && w &&
-                        ctx->fused.x == p->d && ctx->fused.y == w->d && alpha == alpha &&
-                        same_bits(alpha, rr_old / ctx->fused.value) && ahead_plain(x, r, p, w);
-  if (S.stage == 4) {
-    // the calc_r that ran ahead is this very call: r's buffer and the shadow change places, x += alpha p is left to
-    // the calc_p as calc_xr_launch leaves it, and the calc_p behind it stays in flight
-    if (alpha_ok && x == S.x && r == S.r && p == S.p && w == S.w) {
-      double rr_new = 0.0;
-      if (int rc = scalar_from_host_slot(ctx, S.seq_rr, &rr_new)) { spec_drop(ctx); return rc; }
-      std::swap(r->d, S.shadow[0]);
-      ctx->fused.valid = false;
-      ctx->defer.active = true;
-      ctx->defer.on_dev = false;
-      ctx->defer.x = x->d; ctx->defer.p = p->d; ctx->defer.n = x->n; ctx->defer.alpha = alpha;
-      S.rr_prev = rr_old;
-      S.rr_at = 1 - S.rr_at;
-      S.rr_host = rr_new;
-      S.stage = 3;
-      S.a_alpha_ok = true;
-      S.a_commit_r++;
-      *result = rr_new;
-      return ABFT_OK;
-    }
-    spec_drop(ctx);
-  } else if (S.stage == 1) {
-    // the speculated r half is this very call if it names the same vectors and alpha is, bit for bit, the quotient of
-    // the two scalars the caller was (or could have been) handed: r.r and the fused p.w
-    // (a view made since the launch -- abft_hip_vector_view drops nothing -- looks into r's buffer: no swap behind it)
-    bool take = x == S.x && r == S.r && p == S.p && w == S.w && ctx->fused.valid && spec_plain(r, r->n);
-    if (take && !ctx->fused.have_value) {
-      take = scalar_from_host_slot(ctx, ctx->fused.seq, &ctx->fused.value) == ABFT_OK;
-      ctx->fused.have_value = take;
-    }
-    take = take && same_bits(alpha, S.rr_host / ctx->fused.value);
-    if (take) {
-      // enqueue the x / p half BEFORE waiting for r.r: x += alpha p in place (it is due now), p = r + beta p with
-      // beta = r.r_new / r.r formed on the device into the shadow (the caller has yet to name its beta)
-      {
-        double *rr = S.scal + 2 * S.rr_at, *rr_dev_new = S.scal + 2 * (1 - S.rr_at);
-        KernelTimer t(ctx, ABFT_K_CALC_P);
-        HIPCHK(launch_calc_px(p->d, S.shadow[0], x->d, 0.0, rr_dev_new, rr, 0.0, ctx->alpha_dev, x->n, ctx->stream, S.shadow[1],
-                              nullptr));
-      }
-      double rr_new = 0.0;
-      if (int rc = scalar_from_host_slot(ctx, S.seq_rr, &rr_new)) { spec_drop(ctx); return rc; }
-      std::swap(r->d, S.shadow[0]);  // r is now what calc_r left in the shadow; its old buffer is the next shadow
-      ctx->fused.valid = false;
-      S.stage = 2;
-      S.rr_new_host = rr_new;
-      *result = rr_new;
-      return ABFT_OK;
-    }
-    spec_drop(ctx);
-  } else
-    spec_drop(ctx);
-  const int at = S.have_rr ? 1 - S.rr_at : 0;
-  const ReduceOut o = reduce_out(ctx, S.scal + 2 * at, true);
-  if (int rc = calc_xr_launch(ctx, x, r, p, w, alpha, o)) { S.have_rr = false; return rc; }
-  // level 1: the calc_p that will follow, behind calc_r and before the host waits for r.r
-  if (!alpha_ok) S.a_armed = false;
-  const bool p_ahead = alpha_ok && S.a_armed && ctx->defer.active && !ctx->defer.on_dev && ctx->defer.p == p->d &&
-                       ahead_p_launch(ctx, p, r->d, S.scal + 2 * at, S.scal + 2 * S.rr_at);
-  if (int rc = scalar_from_host_slot(ctx, o.seq, result)) { S.have_rr = false; return rc; }
-  if (p_ahead) S.stage = 3;
-  S.a_alpha_ok = alpha_ok;
-  S.rr_prev = rr_old;
-  // what a speculation would need to know about this iteration
-  S.have_rr = true; S.rr_at = at; S.rr_host = *result;
-  S.x = x; S.r = r; S.p = const_cast<abft_hip_vector *>(p); S.w = const_cast<abft_hip_vector *>(w);
-  S.learned = false;  // ... until the calc_p that completes it
-  return ABFT_OK;
+  if (int rc = enter(ctx, KEEP_FLIGHT)) return rc;
+  if (!result) { drop_in_flight(*ctx); return set_err(ABFT_ERR_INVALID, "null result"); }
+  const XrCall c = classify_calc_xr(*ctx, x, r, p, w, alpha);
+  if (c.outcome == XrOutcome::CommitAhead) return xr_commit_ahead(ctx, c, x, r, p, alpha, result);
+  if (c.outcome == XrOutcome::TrySpec) {
+    bool taken = false;
+    const int rc = xr_try_spec(ctx, x, r, p, alpha, result, &taken);
+    if (rc || taken) return rc;
+  }
+  return xr_as_written(ctx, c, x, r, p, w, alpha, result);
 }
 
 extern "C" int abft_hip_calc_xr_dev(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r,
                                     const abft_hip_vector *p, const abft_hip_vector *w, double alpha,
                                     double *dev_result) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   if (!dev_result) return set_err(ABFT_ERR_INVALID, "null result");
   return calc_xr_launch(ctx, x, r, p, w, alpha, reduce_out(ctx, dev_result, false));
 }
 
 extern "C" int abft_hip_calc_p(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, double beta) {
-  if (int rc = bind(ctx, true, true)) return rc;
-  auto &S = ctx->spec;
-  // was beta the quotient of the last two residuals handed back, behind a calc_xr whose alpha was its quotient?
-  const bool beta_ok = S.a_alpha_ok && p == S.p && r == S.r && beta == beta && same_bits(beta, S.rr_host / S.rr_prev) &&
-                       ahead_plain(S.x, S.r, S.p, S.w);
-  if (S.stage == 3) {
-    // the calc_p that ran ahead is this very call: what xpend_take does behind its launch, and no launch
-    auto &X = ctx->xpend;
-    if (beta_ok && ctx->defer.active && !ctx->defer.on_dev && ctx->defer.p == p->d && ctx->defer.n == p->n && !X.active) {
-      const int at = S.a_slot;
-      ctx->defer.active = false;
-      std::swap(p->d, X.shadow[at].buf);
-      X.active = true;
-      X.x = ctx->defer.x; X.p_old = X.shadow[at].buf; X.alpha = ctx->defer.alpha; X.n = p->n; X.ph = p;
-      X.last_p = p;
-      ctx->fused.valid = false;
-      S.stage = 0;
-      S.a_commit_p++;
-      return ABFT_OK;
-    }
-    spec_drop(ctx);
-  } else if (S.stage == 2) {
-    // the speculated x / p half is this very call if it names p and r and beta is the quotient of the two residuals
-    // (p must still be a vector only the library sees into: a view of it may have been made since calc_xr)
-    const bool take = p == S.p && r == S.r && same_bits(beta, S.rr_new_host / S.rr_host) && !ctx->defer.active &&
-                      spec_plain(p, p->n);
-    if (take) {
-      std::swap(p->d, S.shadow[1]);
-      ctx->fused.valid = false;
-      S.stage = 0;
-      S.rr_at = 1 - S.rr_at;  // the speculated r.r is the residual the caller now holds
-      S.rr_host = S.rr_new_host;
-      S.commits++;
-      return ABFT_OK;
-    }
-    spec_drop(ctx);
-  } else
-    spec_drop(ctx);
-  // (learning: calc_p(p, r) right behind calc_xr(x, r, p, w) completes an iteration of the CG loop)
-  const bool completes = S.have_rr && !S.learned && S.p == p && S.r == r && S.x && S.w;
+  if (int rc = enter(ctx, KEEP_FLIGHT | KEEP_DEFERRED)) return rc;
+  const PCall c = classify_calc_p(*ctx, p, r, beta);
+  if (c.outcome == POutcome::CommitAhead) { commit_ahead_p(*ctx, p); return ABFT_OK; }
+  if (c.outcome == POutcome::CommitSpec) { commit_spec_p(*ctx, p); return ABFT_OK; }
+  const bool completes = completes_iteration(*ctx, p, r);
   if (int rc = calc_p_launch(ctx, p, r, beta, nullptr, nullptr)) return rc;
-  S.a_armed = S.ahead && beta_ok;  // one complete iteration on the two quotients arms the run-ahead, any other disarms
-  S.learned = completes || (S.learned && S.p == p && S.r == r);
+  calc_p_ran(*ctx, c, completes, p, r);
   return ABFT_OK;
 }
 
 // {sum, events} that a collective left in device memory -> the host, through the pinned
 // slot the host polls (cheaper than a copy plus a stream synchronise)
 extern "C" int abft_hip_read_pair(abft_hip_ctx *ctx, const double *dev_pair, double *value, double *events) {
-  if (int rc = bind(ctx, true)) return rc;  // touches no vector: a deferred x update may stay pending
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;  // touches no vector: a deferred x update may stay pending
   if (!dev_pair || !value) return set_err(ABFT_ERR_INVALID, "null argument");
-  if (!ctx->fused.have_value) ctx->fused.valid = false;  // the slot is about to be reused
+  fused_slot_reused(*ctx);
   const uint32_t seq = ++ctx->seq;
   HIPCHK(launch_publish_pair(dev_pair, ctx->host_slot_dev + (seq % ABFT_HOST_SLOTS), seq, ctx->stream));
   if (int rc = scalar_from_host_slot(ctx, seq, value)) return rc;
@@ -2345,7 +2190,7 @@ extern "C" int abft_hip_read_pair(abft_hip_ctx *ctx, const double *dev_pair, dou
 
 // the way back (host-staged collectives: several ranks on one GPU in the tests)
 extern "C" int abft_hip_write_pair(abft_hip_ctx *ctx, double *dev_pair, double value, double events) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (!dev_pair) return set_err(ABFT_ERR_INVALID, "null argument");
   const double v[2] = {value, events};
   HIPCHK(hipMemcpyAsync(dev_pair, v, sizeof(v), hipMemcpyHostToDevice, ctx->stream));
@@ -2359,7 +2204,7 @@ extern "C" size_t abft_hip_peer_board_bytes(void) { return (ABFT_PEER_BOARD_BYTE
 
 extern "C" int abft_hip_peer_board_attach(abft_hip_ctx *ctx, void *shared, size_t bytes, int rank, int size,
                                           double timeout_seconds) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (!shared || bytes < abft_hip_peer_board_bytes() || ((uintptr_t)shared & 4095u))
     return set_err(ABFT_ERR_INVALID, "peer board: a page-aligned mapping of at least %zu bytes is needed",
                    abft_hip_peer_board_bytes());
@@ -2415,7 +2260,7 @@ static int board_alloc(abft_hip_ctx *ctx, PeerSlot **out) {
 }
 
 extern "C" int abft_hip_peer_board_device_alloc(abft_hip_ctx *ctx, void **board) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (!board) return set_err(ABFT_ERR_INVALID, "null argument");
   PeerSlot *p = nullptr;
   if (int rc = board_alloc(ctx, &p)) return rc;
@@ -2424,7 +2269,7 @@ extern "C" int abft_hip_peer_board_device_alloc(abft_hip_ctx *ctx, void **board)
 }
 
 extern "C" int abft_hip_peer_board_device_free(abft_hip_ctx *ctx, void *board) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (board) HIPCHK(hipFree(board));
   return ABFT_OK;
 }
@@ -2460,7 +2305,7 @@ static int attach_table(abft_hip_ctx *ctx, void *const *boards, int rank, int si
 
 extern "C" int abft_hip_peer_board_attach_device(abft_hip_ctx *ctx, void *const *boards, int rank, int size,
                                                  double timeout_seconds) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (size < 1 || size > ABFT_PEER_MAX_RANKS || rank < 0 || rank >= size)
     return set_err(ABFT_ERR_RANGE, "peer board: rank %d of %d (at most %d ranks)", rank, size, ABFT_PEER_MAX_RANKS);
   if (!boards) return set_err(ABFT_ERR_INVALID, "null argument");
@@ -2474,7 +2319,7 @@ extern "C" size_t abft_hip_peer_board_ipc_handle_bytes(void) { return sizeof(hip
 
 // this rank's copy, allocated here, as an IPC handle for the other processes of the node
 extern "C" int abft_hip_peer_board_ipc_export(abft_hip_ctx *ctx, void *handle) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (!handle) return set_err(ABFT_ERR_INVALID, "null argument");
   if (ctx->peers.attached || ctx->peers.own_local) return set_err(ABFT_ERR_INVALID, "peer board: already attached or exported");
   PeerSlot *p = nullptr;
@@ -2494,7 +2339,7 @@ extern "C" int abft_hip_peer_board_ipc_export(abft_hip_ctx *ctx, void *handle) {
 // `handles`: size x abft_hip_peer_board_ipc_handle_bytes(), by rank (this rank's own entry is not opened)
 extern "C" int abft_hip_peer_board_ipc_attach(abft_hip_ctx *ctx, const void *handles, int rank, int size,
                                               double timeout_seconds) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (size < 1 || size > ABFT_PEER_MAX_RANKS || rank < 0 || rank >= size)
     return set_err(ABFT_ERR_RANGE, "peer board: rank %d of %d (at most %d ranks)", rank, size, ABFT_PEER_MAX_RANKS);
   if (!handles || !ctx->peers.own_local || ctx->peers.attached)
@@ -2534,7 +2379,7 @@ extern "C" int abft_hip_peer_board_detach(abft_hip_ctx *ctx) {
 
 // dev_pair[0..2) += over the ranks of the board, in place, enqueued on the context's stream
 extern "C" int abft_hip_allreduce_pair_peers(abft_hip_ctx *ctx, double *dev_pair) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (!dev_pair) return set_err(ABFT_ERR_INVALID, "null argument");
   if (!ctx->peers.attached) return set_err(ABFT_ERR_INVALID, "peer board: not attached");
   HIPCHK(launch_peer_allreduce(dev_pair, peer_args(ctx), ctx->stream));
@@ -2546,7 +2391,7 @@ extern "C" int abft_hip_allreduce_pair_peers(abft_hip_ctx *ctx, double *dev_pair
 // over the ranks of the board -- the block that finishes the shard's sum does the all-reduce in its tail,
 // no kernel of its own.  Every rank must switch at the same point of its call sequence.
 extern "C" int abft_hip_peer_board_fuse(abft_hip_ctx *ctx, int on) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (on && !ctx->peers.attached) return set_err(ABFT_ERR_INVALID, "peer board: not attached");
   ctx->peers.fuse = on != 0;
   return ABFT_OK;
@@ -2649,7 +2494,7 @@ static int exchange_attach_common(abft_hip_ctx *ctx, unsigned char *alias, void 
 extern "C" int abft_hip_peer_exchange_attach(abft_hip_ctx *ctx, void *shared, size_t bytes, int rank, int size,
                                              size_t outbox_bytes, const abft_peer_piece *out, int nout,
                                              const abft_peer_piece *in, int nin, double timeout_seconds) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (!shared || ((uintptr_t)shared & 4095u) || bytes < abft_hip_peer_exchange_bytes(size, outbox_bytes))
     return set_err(ABFT_ERR_INVALID, "peer exchange: a page-aligned mapping of at least %zu bytes is needed",
                    abft_hip_peer_exchange_bytes(size, outbox_bytes));
@@ -2690,7 +2535,7 @@ static int region_alloc(abft_hip_ctx *ctx, size_t bytes, unsigned char **out) {
 }
 
 extern "C" int abft_hip_peer_exchange_device_alloc(abft_hip_ctx *ctx, int size, size_t outbox_bytes, void **region) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (!region) return set_err(ABFT_ERR_INVALID, "null argument");
   unsigned char *p = nullptr;
   if (int rc = region_alloc(ctx, abft_hip_peer_exchange_bytes(size, outbox_bytes), &p)) return rc;
@@ -2699,7 +2544,7 @@ extern "C" int abft_hip_peer_exchange_device_alloc(abft_hip_ctx *ctx, int size, 
 }
 
 extern "C" int abft_hip_peer_exchange_device_free(abft_hip_ctx *ctx, void *region) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (region) HIPCHK(hipFree(region));
   return ABFT_OK;
 }
@@ -2707,7 +2552,7 @@ extern "C" int abft_hip_peer_exchange_device_free(abft_hip_ctx *ctx, void *regio
 extern "C" int abft_hip_peer_exchange_attach_device(abft_hip_ctx *ctx, void *const *regions, int rank, int size,
                                                     size_t outbox_bytes, const abft_peer_piece *out, int nout,
                                                     const abft_peer_piece *in, int nin, double timeout_seconds) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (!regions || size < 1 || size > ABFT_PEER_MAX_RANKS || rank < 0 || rank >= size)
     return set_err(ABFT_ERR_INVALID, "peer exchange: bad arguments");
   for (int r = 0; r < size; r++)
@@ -2720,7 +2565,7 @@ extern "C" int abft_hip_peer_exchange_attach_device(abft_hip_ctx *ctx, void *con
 }
 
 extern "C" int abft_hip_peer_exchange_ipc_export(abft_hip_ctx *ctx, int size, size_t outbox_bytes, void *handle) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (!handle) return set_err(ABFT_ERR_INVALID, "null argument");
   if (ctx->xchg.attached || ctx->xchg.own_local) return set_err(ABFT_ERR_INVALID, "peer exchange: already attached or exported");
   unsigned char *p = nullptr;
@@ -2740,7 +2585,7 @@ extern "C" int abft_hip_peer_exchange_ipc_export(abft_hip_ctx *ctx, int size, si
 extern "C" int abft_hip_peer_exchange_ipc_attach(abft_hip_ctx *ctx, const void *handles, int rank, int size,
                                                  size_t outbox_bytes, const abft_peer_piece *out, int nout,
                                                  const abft_peer_piece *in, int nin, double timeout_seconds) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (size < 1 || size > ABFT_PEER_MAX_RANKS || rank < 0 || rank >= size)
     return set_err(ABFT_ERR_RANGE, "peer exchange: rank %d of %d (at most %d ranks)", rank, size, ABFT_PEER_MAX_RANKS);
   if (!handles || !ctx->xchg.own_local || ctx->xchg.attached)
@@ -2793,7 +2638,7 @@ extern "C" int abft_hip_peer_exchange_detach(abft_hip_ctx *ctx) {
 // far; what the caller enqueues until abft_hip_peer_exchange_finish runs next to the exchange (the
 // rows of an SpMV that read no window).  Captured into a graph the two event hand-offs are edges.
 extern "C" int abft_hip_peer_exchange_begin(abft_hip_ctx *ctx, abft_hip_vector *full, int beside) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   if (!full) return set_err(ABFT_ERR_INVALID, "null argument");
   if (!ctx->xchg.attached) return set_err(ABFT_ERR_INVALID, "peer exchange: not attached");
   if (ctx->xchg.pending) return set_err(ABFT_ERR_INVALID, "peer exchange: the previous one was not finished");
@@ -2813,7 +2658,7 @@ extern "C" int abft_hip_peer_exchange_begin(abft_hip_ctx *ctx, abft_hip_vector *
 }
 
 extern "C" int abft_hip_peer_exchange_finish(abft_hip_ctx *ctx) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (!ctx->xchg.pending) return ABFT_OK;
   ctx->xchg.pending = false;
   HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->xchg.join, 0));
@@ -2846,59 +2691,19 @@ extern "C" int abft_hip_peer_exchange_failed(abft_hip_ctx *ctx) {
 extern "C" int abft_hip_calc_xr_ratio_dev(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r,
                                           const abft_hip_vector *p, const abft_hip_vector *w,
                                           const double *dev_num, const double *dev_den, double *dev_result) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   if (!dev_num || !dev_den || !dev_result) return set_err(ABFT_ERR_INVALID, "null device scalar");
   return calc_xr_launch(ctx, x, r, p, w, 0.0, reduce_out(ctx, dev_result, false), dev_num, dev_den);
 }
 
 extern "C" int abft_hip_calc_p_ratio_dev(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r,
                                          const double *dev_num, const double *dev_den) {
-  if (int rc = bind(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED)) return rc;
   if (!dev_num || !dev_den) {
     (void)flush_deferred(ctx);
     return set_err(ABFT_ERR_INVALID, "null device scalar");
   }
   return calc_p_launch(ctx, p, r, 0.0, dev_num, dev_den);
-}
-
-// Shared by abft_hip_spmv (dev_pair == nullptr: the fused product, if any, goes to
-// the pinned slot for a following dot) and abft_hip_spmv_dot_dev.
-// ---- speculation (see abft_hip_ctx::spec) ----------------------------------------------------------
-static bool spec_plain(const abft_hip_vector *v, int n) {  // a whole allocation nobody else can see into
-  return v && v->owns && v->root == v && !v->exposed && v->views == 0 && v->n == n && v->d;
-}
-
-// behind spmv(A, p, w) + fold: the learned iteration's r half and x / p half into the shadow buffers
-static int spec_launch(abft_hip_ctx *ctx, const abft_hip_vector *vec, const abft_hip_vector *result) {
-  auto &S = ctx->spec;
-  if (!S.enabled || !S.learned || !S.have_rr || S.stage || ctx->defer.active || ctx->capturing) return ABFT_OK;
-  if (vec != S.p || result != S.w) return ABFT_OK;
-  const int n = vec->n;
-  if (n <= 0 || !spec_plain(S.x, n) || !spec_plain(S.r, n) || !spec_plain(S.p, n) || !spec_plain(S.w, n)) return ABFT_OK;
-  if (S.shadow_n != n) {
-    for (double *&b : S.shadow) { (void)hipFree(b); b = nullptr; }
-    S.shadow_n = 0;
-    for (double *&b : S.shadow)
-      if (hipMalloc((void **)&b, ((size_t)n + 2) * sizeof(double)) != hipSuccess) {  // no room: no speculation
-        (void)hipGetLastError();
-        for (double *&c : S.shadow) { (void)hipFree(c); c = nullptr; }
-        S.enabled = false;
-        return ABFT_OK;
-      }
-    S.shadow_n = n;
-  }
-  double *rr = S.scal + 2 * S.rr_at, *rr_new = S.scal + 2 * (1 - S.rr_at), *pw = S.scal + 4;
-  const ReduceOut o = reduce_out(ctx, rr_new, true);  // {r.r, events} to the host ring AND to the device
-  {
-    KernelTimer t(ctx, ABFT_K_CALC_XR);
-    HIPCHK(launch_calc_r(S.r->d, S.w->d, 0.0, rr, pw, ctx->alpha_dev, n, o, ctx->stream, S.shadow[0], S.x->d, S.p->d));
-  }
-  // (the x / p half follows when calc_xr has been taken over: from then on x += alpha p is DUE, so x is updated in
-  // place and only p -- whose beta the caller has yet to name -- goes to a shadow.  Both halves out of place from
-  // here cost calc_px 8-10 us: five address streams instead of three)
-  S.stage = 1;
-  S.seq_rr = o.seq;
-  return ABFT_OK;
 }
 
 // `hold` (abft_hip_cg_iteration_dev): the fold of the fused product is not launched; what it needs is left there
@@ -2909,47 +2714,36 @@ struct HeldFold {
   FixArgs fix{};
 };
 
-// Is this call the SpMV the pending x update waits for -- abft_hip_spmv(A, p, w) on the streaming CSR layout, whole,
-// with the fused product, p the handle whose buffer was swapped, w apart from x, p and the old p?  (Then every check
-// spmv_common makes below holds, and the launch covers every row block.)  Also where the prediction is armed: such a
-// call on a plain p directly after the calc_p that took a deferred update on that p along.
-static bool xpend_predicted(abft_hip_ctx *ctx, const abft_hip_matrix *mat, const abft_hip_vector *vec,
+// Could this call be the SpMV a pending x update waits for -- abft_hip_spmv(A, p, w) on the streaming CSR layout, whole,
+// with the fused product, on a mode the path is on for?  (Then every check spmv_common makes below holds, and the
+// launch covers every row block.)  loop_state.h decides the rest (pending_absorbed_by): p the handle whose buffer was
+// swapped, w apart from x and the old p.
+static bool spmv_can_absorb(const abft_hip_ctx *ctx, const abft_hip_matrix *mat, const abft_hip_vector *vec,
                             const abft_hip_vector *result, const double *dev_pair, int part, int c1, bool held,
-                            bool vecc, bool *eligible) {
-  auto &X = ctx->xpend;
-  const abft_hip_vector *after_calc_p = X.prev_p;
-  X.prev_p = nullptr;
-  if (!ctx->xin_enabled || !mat || !vec || !result) return false;
+                            bool vecc) {
+  if (!mat || !vec || !result) return false;
+  if (!pending_path_on(*ctx, (unsigned)mat->mode)) return false;  // (not a mode it pays on: a pending update, left by a matrix of another mode, is applied first)
   if (mat->fmt != ABFT_FMT_CSR || mat->use_slice || mat->use_sweep || mat->use_panels) return false;
-  if (!(ctx->xin_modes >> (unsigned)mat->mode & 1u)) return false;  // not a mode it pays on (a pending update, left by a matrix of another mode, is applied first)
-  if (part != ABFT_PART_ALL || c1 >= 0 || dev_pair || held || vecc || ctx->capturing) return false;
+  if (part != ABFT_PART_ALL || c1 >= 0 || dev_pair || held || vecc) return false;
   const uint32_t n = mat->csr.n_out;
-  if (!mat->fuse_partials || !ctx->fuse_enabled || n == 0 || mat->csr.n_in != n || mat->csr.nblk == 0 ||
-      (uint32_t)vec->n != n || (uint32_t)result->n != n || !disjoint(vec, result))
-    return false;
-  *eligible = true;
-  if (!X.active) {
-    if (after_calc_p == vec && spec_plain(vec, vec->n)) X.armed = true;
-    return false;
-  }
-  abft_hip_vector xv, pv;  // just the ranges, for the overlap tests
-  xv.d = X.x; xv.n = X.n;
-  pv.d = const_cast<double *>(X.p_old); pv.n = X.n;
-  return X.ph == vec && (uint32_t)X.n == n && disjoint(&xv, result) && disjoint(&pv, result);
+  return mat->fuse_partials && n != 0 && mat->csr.n_in == n && mat->csr.nblk != 0 &&
+         (uint32_t)vec->n == n && (uint32_t)result->n == n && disjoint(vec, result);
 }
 
+// Shared by abft_hip_spmv (dev_pair == nullptr: the fused product, if any, goes to
+// the pinned slot for a following dot) and abft_hip_spmv_dot_dev.
 static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
                        abft_hip_vector *result, int vec_offset, double *dev_pair, int part = ABFT_PART_ALL,
                        int c0 = 0, int c1 = -1, HeldFold *hold = nullptr, bool vecc = false) {
-  if (int rc = bind(ctx, false, false, true)) return rc;
-  // the update pending on the old p (abft_hip_ctx::xpend): this launch applies it, or it is applied first
-  bool absorb_ok = false;  // ... and whether this is a call that could apply one (then a run-ahead may follow it)
-  const bool absorb = xpend_predicted(ctx, mat, vec, result, dev_pair, part, c1, hold != nullptr, vecc, &absorb_ok);
+  if (int rc = enter(ctx, KEEP_PENDING)) return rc;
+  // the update pending on the old p (PendingUpdate): this launch applies it, or it is applied first
+  const bool absorb_ok = spmv_can_absorb(ctx, mat, vec, result, dev_pair, part, c1, hold != nullptr, vecc);  // (then a run-ahead may follow it)
+  const bool absorb = pending_absorbed_by(*ctx, absorb_ok, vec, result);
   if (!absorb)
     if (int rc = flush_xpend(ctx)) return rc;
   if (!mat || !vec || !result) return set_err(ABFT_ERR_INVALID, "spmv: null argument");
   if (vecc) {  // protected vectors: the streaming CSR kernel only; the iteration they are part of is not speculated
-    spec_forget(ctx);
+    forget_iteration(*ctx);
     const char *layout = mat->fmt != ABFT_FMT_CSR ? "COO" : mat->use_slice ? "slice" : mat->use_sweep ? "sweep"
                          : mat->use_panels ? "panel" : nullptr;
     if (layout)
@@ -2968,7 +2762,7 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
   if (dev_pair && (vec_offset < 0 || (uint64_t)vec_offset + n_out > (uint64_t)vec->n))
     return set_err(ABFT_ERR_INVALID, "spmv_dot: window [%d,%llu) outside the input vector of %d", vec_offset,
                    (unsigned long long)vec_offset + n_out, vec->n);
-  ctx->fused.valid = false;
+  forget_fused(*ctx);
   FuseOut fuse{};
   const bool to_host = !dev_pair && ctx->fuse_enabled && n_in == n_out && (uint32_t)vec->n == n_in &&
                        (uint32_t)result->n == n_out;
@@ -2998,7 +2792,7 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
     fuse.ev_count = ctx->ring.count;
     fuse.seq = dev_pair ? 0 : ++ctx->seq;
     fuse.host = dev_pair ? nullptr : ctx->host_slot_dev + (fuse.seq % ABFT_HOST_SLOTS);
-    fuse.dev_out = dev_pair ? dev_pair : ctx->spec.scal + 4;  // (host form: p.w stays on the device too, for a speculated alpha)
+    fuse.dev_out = dev_pair ? dev_pair : ctx->iter.scal + 4;  // (host form: p.w stays on the device too, for a speculated alpha)
     fuse.x_off = dev_pair ? (uint32_t)vec_offset : 0u;
     if (dev_pair && ctx->peers.fuse) fuse.peers = peer_args(ctx);
   }
@@ -3033,10 +2827,7 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
       const XUpd xu{ctx->xpend.x, ctx->xpend.p_old, ctx->xpend.alpha};
       HIPCHK(launch_spmv_csr(mat->mode, mat->csr, mat->compact, mat->packed, span, vec->d, result->d, ctx->ring,
                              do_fuse ? &fuse : nullptr, ctx->stream, vecc, absorb ? &xu : nullptr));
-      if (absorb) {  // applied exactly once, whatever the launch reports about the matrix
-        ctx->xpend.active = false;
-        ctx->xpend.absorbed++;
-      }
+      if (absorb) pending_absorbed(*ctx);
     } else
       HIPCHK(launch_spmv_coo(mat->mode, mat->coo, vec->d, result->d, ctx->ring, do_fuse ? &fuse : nullptr, ctx->stream));
     // COO: products whose stored column was silently corrupted go where the reference puts them --
@@ -3063,15 +2854,9 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
     HIPCHK(launch_fuse_finalize(fuse, nparts, big, fix.on ? &fix : nullptr, ctx->stream));
   }
   if (to_host && do_fuse) {
-    ctx->fused.valid = true;
-    ctx->fused.have_value = false;
-    ctx->fused.vecc = vecc;
-    ctx->fused.x = vec->d;
-    ctx->fused.y = result->d;
-    ctx->fused.n = vec->n;
-    ctx->fused.seq = fuse.seq;
+    fused_made(*ctx, vecc, vec, result, fuse.seq);
     if (whole && part == ABFT_PART_ALL && !vecc) (void)spec_launch(ctx, vec, result);
-    if (absorb_ok) ahead_launch(ctx, vec, result);
+    ahead_launch(ctx, absorb_ok, vec, result);
   }
   return ABFT_OK;
 }
@@ -3107,16 +2892,8 @@ static int check_block(const char *what, int k, int N, std::initializer_list<con
   return ABFT_OK;
 }
 
-// the prologue of every block call: what abft_hip_spmv / abft_hip_dot start with (a pending x update
-// applied, a speculation voided), and -- since block calls write vectors the single calls' caches
-// may name -- the fused product and the learned iteration forgotten
-static int bind_block(abft_hip_ctx *ctx) {
-  if (int rc = bind(ctx)) return rc;
-  ctx->fused.valid = false;
-  spec_forget(ctx);
-  return ABFT_OK;
-}
-
+// (every block call enters with OTHER_VECTORS: block calls write vectors the single calls' caches may name, so the
+// fused product and the learned iteration are forgotten)
 static int block_slot(abft_hip_ctx *ctx) {
   if (ctx->bslot) return ABFT_OK;
   HIPCHK(hipMalloc((void **)&ctx->bpartials, (size_t)2 * ABFT_MAX_RHS * ABFT_MAX_PARTIALS * sizeof(double)));
@@ -3148,7 +2925,7 @@ static int results_from_block_slot(abft_hip_ctx *ctx, uint32_t seq, int k, doubl
 
 extern "C" int abft_hip_spmm(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *X, abft_hip_vector *Y,
                              int k) {
-  if (int rc = bind_block(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!mat || !X || !Y) return set_err(ABFT_ERR_INVALID, "spmm: null argument");
   if (mat->fmt != ABFT_FMT_CSR)
     return set_err(ABFT_ERR_INVALID, "spmm: COO matrices have no block SpMV; create the matrix as CSR with "
@@ -3170,7 +2947,7 @@ extern "C" int abft_hip_spmm(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft
 
 extern "C" int abft_hip_dot_block(abft_hip_ctx *ctx, const abft_hip_vector *a, const abft_hip_vector *b, int k,
                                   double *out) {
-  if (int rc = bind_block(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!a || !b || !out) return set_err(ABFT_ERR_INVALID, "dot_block: null argument");
   if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "dot_block: k = %d outside [1, %d]", k, ABFT_MAX_RHS);
   const int N = a->n / k;
@@ -3187,7 +2964,7 @@ extern "C" int abft_hip_dot_block(abft_hip_ctx *ctx, const abft_hip_vector *a, c
 extern "C" int abft_hip_calc_xr_block(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r,
                                       const abft_hip_vector *p, const abft_hip_vector *w, int k, const double *alpha,
                                       uint32_t active, double *rr_out) {
-  if (int rc = bind_block(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!x || !r || !p || !w || !alpha || !rr_out) return set_err(ABFT_ERR_INVALID, "calc_xr_block: null argument");
   if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "calc_xr_block: k = %d outside [1, %d]", k, ABFT_MAX_RHS);
   const int N = x->n / k;
@@ -3207,7 +2984,7 @@ extern "C" int abft_hip_calc_xr_block(abft_hip_ctx *ctx, abft_hip_vector *x, abf
 
 extern "C" int abft_hip_calc_p_block(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, int k,
                                      const double *beta, uint32_t active) {
-  if (int rc = bind_block(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!p || !r || !beta) return set_err(ABFT_ERR_INVALID, "calc_p_block: null argument");
   if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "calc_p_block: k = %d outside [1, %d]", k, ABFT_MAX_RHS);
   const int N = p->n / k;
@@ -3221,13 +2998,13 @@ extern "C" int abft_hip_calc_p_block(abft_hip_ctx *ctx, abft_hip_vector *p, cons
 }
 
 // ---- residual checks (include/abft_hip.h): vector fault injection, b - A x against r, restart ----
-// Every entry starts with bind_block: a deferred x += alpha p is applied (a flip or a check sees the
+// Every entry starts with the prologue (OTHER_VECTORS): a deferred x += alpha p is applied (a flip or a check sees the
 // real x), a speculation is voided, and the fused product is forgotten; the check's SpMV writes the
 // scratch vector, so the fused product is forgotten again behind it.
 
 extern "C" int abft_hip_vector_flip(abft_hip_vector *v, int index, const int *bits, int nbits) {
   if (!v) return set_err(ABFT_ERR_INVALID, "vector_flip: null vector");
-  if (int rc = bind_block(v->ctx)) return rc;
+  if (int rc = enter(v->ctx, OTHER_VECTORS)) return rc;
   if (index < 0 || index >= v->n) return set_err(ABFT_ERR_INVALID, "vector_flip: index %d outside [0,%d)", index, v->n);
   if (nbits < 0 || nbits > 64 || (nbits && !bits)) return set_err(ABFT_ERR_INVALID, "vector_flip: bad bit list");
   unsigned long long mask = 0;
@@ -3241,26 +3018,19 @@ extern "C" int abft_hip_vector_flip(abft_hip_vector *v, int index, const int *bi
 }
 
 // ---- protected vectors (include/abft_hip.h): encode, scrub and the four CG calls on codewords ----
-// Every entry starts with bind (a deferred x += alpha p applied, a speculation voided) and forgets the
+// Every entry starts with the prologue (a deferred x += alpha p applied, a speculation voided) and forgets the
 // learned iteration: a protected loop is never speculated.  An entry that writes a vector also forgets
 // the fused product.  Lengths and overlaps are checked before anything of the call is enqueued.
 
-static int bind_vecc(abft_hip_ctx *ctx, bool writes) {
-  if (int rc = bind(ctx)) return rc;
-  spec_forget(ctx);
-  if (writes) ctx->fused.valid = false;
-  return ABFT_OK;
-}
-
 extern "C" int abft_hip_vector_encode(abft_hip_ctx *ctx, abft_hip_vector *v) {
-  if (int rc = bind_vecc(ctx, true)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!v) return set_err(ABFT_ERR_INVALID, "vector_encode: null vector");
   HIPCHK(launch_vector_encode(v->d, v->n, ctx->stream));
   return ABFT_OK;
 }
 
 extern "C" int abft_hip_vector_scrub(abft_hip_ctx *ctx, abft_hip_vector *v, int *corrected, int *uncorrectable) {
-  if (int rc = bind_vecc(ctx, true)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!v) return set_err(ABFT_ERR_INVALID, "vector_scrub: null vector");
   uint32_t counts[2] = {0u, 0u};
   uint32_t *dev = reinterpret_cast<uint32_t *>(ctx->bits_dev);  // (the injection scratch: idle between calls)
@@ -3279,20 +3049,16 @@ extern "C" int abft_hip_spmv_vecc(abft_hip_ctx *ctx, abft_hip_matrix *mat, const
 }
 
 extern "C" int abft_hip_dot_vecc(abft_hip_ctx *ctx, const abft_hip_vector *a, const abft_hip_vector *b, double *out) {
-  if (int rc = bind_vecc(ctx, false)) return rc;
+  if (int rc = enter(ctx, FORGET_ITER)) return rc;
   if (int rc = check_same(a, b, "dot_vecc")) return rc;
   if (!out) return set_err(ABFT_ERR_INVALID, "dot_vecc: null result");
   // dot_vecc(p, w) right after spmv_vecc(A, p, w): the SpMV already formed it (never a plain product)
-  if (ctx->fused.valid && ctx->fused.vecc && a->n == ctx->fused.n &&
-      ((a->d == ctx->fused.x && b->d == ctx->fused.y) || (a->d == ctx->fused.y && b->d == ctx->fused.x))) {
-    if (!ctx->fused.have_value) {
-      if (int rc = scalar_from_host_slot(ctx, ctx->fused.seq, &ctx->fused.value)) return rc;
-      ctx->fused.have_value = true;
-    }
+  if (fused_serves_dot(*ctx, a, b, true)) {
+    if (int rc = fused_value(ctx)) return rc;
     *out = ctx->fused.value;
     return ABFT_OK;
   }
-  if (!ctx->fused.have_value) ctx->fused.valid = false;  // the slot is about to be reused
+  fused_slot_reused(*ctx);
   const ReduceOut o = reduce_out(ctx, nullptr, true);
   {
     KernelTimer t(ctx, ABFT_K_DOT);
@@ -3303,7 +3069,7 @@ extern "C" int abft_hip_dot_vecc(abft_hip_ctx *ctx, const abft_hip_vector *a, co
 
 extern "C" int abft_hip_calc_xr_vecc(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r,
                                      const abft_hip_vector *p, const abft_hip_vector *w, double alpha, double *rr) {
-  if (int rc = bind_vecc(ctx, true)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!rr) return set_err(ABFT_ERR_INVALID, "calc_xr_vecc: null result");
   if (int rc = check_same(x, r, "calc_xr_vecc")) return rc;
   if (int rc = check_same(x, p, "calc_xr_vecc")) return rc;
@@ -3319,7 +3085,7 @@ extern "C" int abft_hip_calc_xr_vecc(abft_hip_ctx *ctx, abft_hip_vector *x, abft
 }
 
 extern "C" int abft_hip_calc_p_vecc(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, double beta) {
-  if (int rc = bind_vecc(ctx, true)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (int rc = check_same(p, r, "calc_p_vecc")) return rc;
   if (!disjoint(p, r)) return set_err(ABFT_ERR_INVALID, "calc_p_vecc: p and r overlap");
   KernelTimer t(ctx, ABFT_K_CALC_P);
@@ -3348,12 +3114,12 @@ static int check_residual_args(const char *what, abft_hip_matrix *A, const abft_
 extern "C" int abft_hip_residual_gap(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *b,
                                      const abft_hip_vector *x, const abft_hip_vector *r, abft_hip_vector *scratch,
                                      double out[2]) {
-  if (int rc = bind_block(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!out) return set_err(ABFT_ERR_INVALID, "residual_gap: null result");
   if (int rc = check_residual_args("residual_gap", A, b, x, r, scratch, nullptr)) return rc;
   if (int rc = block_slot(ctx)) return rc;
   if (int rc = spmv_common(ctx, A, x, scratch, 0, nullptr)) return rc;
-  ctx->fused.valid = false;
+  forget_fused(*ctx);
   const ReduceOutK o = reduce_out_k(ctx);
   {
     KernelTimer t(ctx, ABFT_K_DOT);
@@ -3365,11 +3131,11 @@ extern "C" int abft_hip_residual_gap(abft_hip_ctx *ctx, abft_hip_matrix *A, cons
 extern "C" int abft_hip_residual_restart(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *b,
                                          const abft_hip_vector *x, abft_hip_vector *r, abft_hip_vector *p,
                                          abft_hip_vector *scratch, double *rr) {
-  if (int rc = bind_block(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!rr) return set_err(ABFT_ERR_INVALID, "residual_restart: null result");
   if (int rc = check_residual_args("residual_restart", A, b, x, r, scratch, p)) return rc;
   if (int rc = spmv_common(ctx, A, x, scratch, 0, nullptr)) return rc;
-  ctx->fused.valid = false;
+  forget_fused(*ctx);
   const ReduceOut o = reduce_out(ctx, nullptr, true);
   {
     KernelTimer t(ctx, ABFT_K_DOT);
@@ -3394,12 +3160,12 @@ static int check_residual_block_args(const char *what, abft_hip_matrix *A, int k
 extern "C" int abft_hip_residual_gap_block(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *B,
                                            const abft_hip_vector *X, const abft_hip_vector *R,
                                            abft_hip_vector *scratch, int k, uint32_t active, double *out) {
-  if (int rc = bind_block(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!out) return set_err(ABFT_ERR_INVALID, "residual_gap_block: null result");
   if (int rc = check_residual_block_args("residual_gap_block", A, k, {B, X, R}, scratch)) return rc;
   if (int rc = block_slot(ctx)) return rc;
   if (int rc = abft_hip_spmm(ctx, A, X, scratch, k)) return rc;
-  ctx->fused.valid = false;
+  forget_fused(*ctx);
   ReduceOutW o{};
   o.partials = ctx->bpartials;
   o.ticket = ctx->ticket;
@@ -3419,14 +3185,14 @@ extern "C" int abft_hip_residual_gap_block(abft_hip_ctx *ctx, abft_hip_matrix *A
 extern "C" int abft_hip_residual_restart_block(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *B,
                                                const abft_hip_vector *X, abft_hip_vector *R, abft_hip_vector *P,
                                                abft_hip_vector *scratch, int k, uint32_t mask, double *rr) {
-  if (int rc = bind_block(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!rr) return set_err(ABFT_ERR_INVALID, "residual_restart_block: null result");
   if (int rc = check_residual_block_args("residual_restart_block", A, k, {B, X, R, P}, scratch)) return rc;
   if (!disjoint(R, B) || !disjoint(R, X) || !disjoint(R, P) || !disjoint(P, B) || !disjoint(P, X))
     return set_err(ABFT_ERR_INVALID, "residual_restart_block: R and P must not overlap each other, B or X");
   if (int rc = block_slot(ctx)) return rc;
   if (int rc = abft_hip_spmm(ctx, A, X, scratch, k)) return rc;
-  ctx->fused.valid = false;
+  forget_fused(*ctx);
   const ReduceOutK o = reduce_out_k(ctx);
   {
     KernelTimer t(ctx, ABFT_K_DOT);
@@ -3437,7 +3203,7 @@ extern "C" int abft_hip_residual_restart_block(abft_hip_ctx *ctx, abft_hip_matri
 
 extern "C" int abft_hip_copy_block(abft_hip_ctx *ctx, abft_hip_vector *dst, const abft_hip_vector *src, int k,
                                    uint32_t mask) {
-  if (int rc = bind_block(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!dst || !src) return set_err(ABFT_ERR_INVALID, "copy_block: null vector");
   if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "copy_block: k = %d outside [1, %d]", k, ABFT_MAX_RHS);
   const int N = dst->n / k;
@@ -3497,9 +3263,7 @@ extern "C" int abft_hip_matrix_diag_inverse(abft_hip_ctx *ctx, abft_hip_matrix *
   const uint32_t N = mat->fmt == ABFT_FMT_CSR ? mat->csr.n_out : mat->coo.n_out;
   if ((uint32_t)dinv->n != N)
     return set_err(ABFT_ERR_INVALID, "diag_inverse: a vector of %d entries for %u rows", dinv->n, N);
-  if (int rc = bind(ctx)) return rc;
-  ctx->fused.valid = false;
-  spec_forget(ctx);
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   *bad = 0;
   if (!N) return ABFT_OK;
   hipStream_t s = ctx->stream;
@@ -3530,14 +3294,6 @@ extern "C" int abft_hip_matrix_diag_inverse(abft_hip_ctx *ctx, abft_hip_matrix *
   return ABFT_OK;
 }
 
-// the prologue of the preconditioned vector entries (see above)
-static int bind_precond(abft_hip_ctx *ctx, bool keep_deferred = false) {
-  if (int rc = bind(ctx, keep_deferred)) return rc;
-  ctx->fused.valid = false;
-  spec_forget(ctx);
-  return ABFT_OK;
-}
-
 static int check_precond(const char *what, std::initializer_list<const abft_hip_vector *> reads,
                          std::initializer_list<const abft_hip_vector *> writes, const abft_hip_vector *dinv) {
   if (!dinv) return set_err(ABFT_ERR_INVALID, "%s: null vector", what);
@@ -3560,7 +3316,7 @@ extern "C" int abft_hip_precond_start(abft_hip_ctx *ctx, const abft_hip_vector *
   if (!out) return set_err(ABFT_ERR_INVALID, "precond_start: null result");
   if (int rc = check_precond("precond_start", {r}, {p}, dinv)) return rc;
   if (r->n && !disjoint(r, p)) return set_err(ABFT_ERR_INVALID, "precond_start: r and p overlap");
-  if (int rc = bind_precond(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (int rc = block_slot(ctx)) return rc;
   const ReduceOutK o = reduce_out_k(ctx);
   {
@@ -3575,7 +3331,7 @@ extern "C" int abft_hip_calc_xr_precond(abft_hip_ctx *ctx, abft_hip_vector *x, a
                                         const abft_hip_vector *dinv, double alpha, double out[2]) {
   if (!out) return set_err(ABFT_ERR_INVALID, "calc_xr_precond: null result");
   if (int rc = check_precond("calc_xr_precond", {p, w}, {x, r}, dinv)) return rc;
-  if (int rc = bind_precond(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (int rc = block_slot(ctx)) return rc;
   // the x half waits for the calc_p_precond that reads the same p next, under calc_xr's own rule
   // (calc_xr_launch): x aliased by no other operand, its raw pointer never handed out
@@ -3597,7 +3353,7 @@ extern "C" int abft_hip_calc_xr_precond(abft_hip_ctx *ctx, abft_hip_vector *x, a
 extern "C" int abft_hip_calc_p_precond(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r,
                                        const abft_hip_vector *dinv, double beta) {
   if (int rc = check_precond("calc_p_precond", {r}, {p}, dinv)) return rc;
-  if (int rc = bind_precond(ctx, true)) return rc;
+  if (int rc = enter(ctx, KEEP_DEFERRED | OTHER_VECTORS)) return rc;
   if (int rc = flush_xpend(ctx)) return rc;
   if (ctx->defer.active) {
     abft_hip_vector xv;  // just the range, for the overlap tests
@@ -3649,7 +3405,7 @@ extern "C" int abft_hip_precond_start_block(abft_hip_ctx *ctx, const abft_hip_ve
   if (!out) return set_err(ABFT_ERR_INVALID, "precond_start_block: null result");
   if (int rc = check_precond_block("precond_start_block", k, {R}, {P}, dinv)) return rc;
   if (R->n && !disjoint(R, P)) return set_err(ABFT_ERR_INVALID, "precond_start_block: R and P overlap");
-  if (int rc = bind_precond(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (int rc = block_slot(ctx)) return rc;
   const ReduceOutW o = reduce_out_w(ctx);
   {
@@ -3667,7 +3423,7 @@ extern "C" int abft_hip_calc_xr_precond_block(abft_hip_ctx *ctx, abft_hip_vector
   if (int rc = check_precond_block("calc_xr_precond_block", k, {P, W}, {X, R}, dinv)) return rc;
   if (X->n && (!disjoint(X, R) || !disjoint(X, P) || !disjoint(X, W) || !disjoint(R, P) || !disjoint(R, W)))
     return set_err(ABFT_ERR_INVALID, "calc_xr_precond_block: x and r must not overlap each other or p, w");
-  if (int rc = bind_precond(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (int rc = block_slot(ctx)) return rc;
   BlockScalars a{};
   for (int j = 0; j < k; j++) a.v[j] = alpha[j];
@@ -3684,7 +3440,7 @@ extern "C" int abft_hip_calc_p_precond_block(abft_hip_ctx *ctx, abft_hip_vector 
   if (!beta) return set_err(ABFT_ERR_INVALID, "calc_p_precond_block: null argument");
   if (int rc = check_precond_block("calc_p_precond_block", k, {R}, {P}, dinv)) return rc;
   if (P->n && !disjoint(P, R)) return set_err(ABFT_ERR_INVALID, "calc_p_precond_block: p and r overlap");
-  if (int rc = bind_precond(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   BlockScalars b{};
   for (int j = 0; j < k; j++) b.v[j] = beta[j];
   KernelTimer t(ctx, ABFT_K_CALC_P);
@@ -3729,7 +3485,7 @@ static int dotparts_reserve(abft_hip_ctx *ctx, const abft_hip_matrix *mat, int k
 
 extern "C" int abft_hip_spmm_dot(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *P,
                                  abft_hip_vector *W, int k, double *out) {
-  if (int rc = bind_block(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!mat || !P || !W || !out) return set_err(ABFT_ERR_INVALID, "spmm_dot: null argument");
   if (int rc = check_spmm_dot("spmm_dot", mat, P, W, k)) return rc;
   if (int rc = block_slot(ctx)) return rc;
@@ -3776,7 +3532,7 @@ static int check_fused_block(const char *what, int k, std::initializer_list<cons
 static int calc_r_block_common(abft_hip_ctx *ctx, const char *what, abft_hip_vector *R, const abft_hip_vector *W,
                                const abft_hip_vector *dinv, bool precond, int k, const double *alpha, uint32_t active,
                                double *out) {
-  if (int rc = bind_block(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!alpha || !out) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
   if (int rc = check_fused_block(what, k, {W}, {R}, dinv, precond)) return rc;
   if (int rc = block_slot(ctx)) return rc;
@@ -3802,7 +3558,7 @@ static int calc_r_block_common(abft_hip_ctx *ctx, const char *what, abft_hip_vec
 static int calc_px_block_common(abft_hip_ctx *ctx, const char *what, abft_hip_vector *X, abft_hip_vector *P,
                                 const abft_hip_vector *R, const abft_hip_vector *dinv, bool precond, int k,
                                 const double *alpha, const double *beta, uint32_t active) {
-  if (int rc = bind_block(ctx)) return rc;
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!alpha || !beta) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
   if (int rc = check_fused_block(what, k, {R}, {X, P}, dinv, precond)) return rc;
   BlockScalars a{}, b{};
@@ -4012,7 +3768,7 @@ extern "C" int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat
     if (int rc = calc_xr_launch(ctx, x, r, p, w, 0.0, o, dev_rr, dev_pw)) return rc;
     return calc_p_launch(ctx, p, r, 0.0, dev_rr_new, dev_rr);
   }
-  ctx->fused.valid = false;
+  forget_fused(*ctx);
   TailArgs a{};
   a.f = hold.fuse;
   a.nparts = hold.nparts;
@@ -4039,7 +3795,7 @@ extern "C" int abft_hip_cg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matri
                                                abft_hip_vector *p, abft_hip_vector *w, const double *dev_rr,
                                                double *dev_pw, double *dev_rr_new, double threshold) {
   const char *what = "cg_iteration_until";
-  if (int rc = bind(ctx)) return rc;  // a pending x update applied, a speculation voided
+  if (int rc = enter(ctx, 0)) return rc;  // a pending x update applied, a speculation voided
   if (int rc = check_guarded_iteration(ctx, what, mat, vec, vec_offset, part, x, r, p, w, false, nullptr, dev_rr, dev_pw,
                                        dev_rr_new))
     return rc;
@@ -4069,7 +3825,7 @@ extern "C" int abft_hip_pcg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matr
                                                 const double *dev_in, double *dev_pw, double *dev_out,
                                                 double threshold) {
   const char *what = "pcg_iteration_until";
-  if (int rc = bind(ctx)) return rc;  // a pending x update applied, a speculation voided
+  if (int rc = enter(ctx, 0)) return rc;  // a pending x update applied, a speculation voided
   if (int rc = check_guarded_iteration(ctx, what, mat, vec, vec_offset, part, x, r, p, w, true, dinv, dev_in, dev_pw,
                                        dev_out))
     return rc;
@@ -4079,7 +3835,7 @@ extern "C" int abft_hip_pcg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matr
     return set_err(ABFT_ERR_INVALID, "%s: called under graph capture before the context's block partials exist; make "
                    "one eager preconditioned call first (abft_hip_precond_start, for example)", what);
   if (int rc = block_slot(ctx)) return rc;
-  spec_forget(ctx);  // (as every preconditioned entry: the learned iteration names these vectors by handle)
+  forget_iteration(*ctx);  // (as every preconditioned entry: the learned iteration names these vectors by handle)
   HeldFold hold;
   if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold)) return rc;
   if (int rc = finish_held_fold(ctx, hold)) return rc;
@@ -4120,7 +3876,7 @@ static int block_loop_alloc(abft_hip_ctx *ctx, const abft_hip_matrix *mat, int k
 
 extern "C" int abft_hip_block_loop_reserve(abft_hip_ctx *ctx, abft_hip_matrix *mat, int k) {
   const char *what = "block_loop_reserve";
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   if (!mat) return set_err(ABFT_ERR_INVALID, "%s: null matrix", what);
   if (ctx->capturing) return set_err(ABFT_ERR_INVALID, "%s: called under graph capture (it allocates)", what);
   if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "%s: k = %d outside [1, %d]", what, k, ABFT_MAX_RHS);
@@ -4135,7 +3891,7 @@ extern "C" int abft_hip_cg_block_iteration_until_dev(abft_hip_ctx *ctx, abft_hip
                                                      const abft_hip_vector *dinv, int k, const double *dev_in,
                                                      double *dev_pw, double *dev_out, double threshold) {
   const char *what = "cg_block_iteration_until";
-  if (int rc = bind_block(ctx)) return rc;  // a pending x update applied, the fused product and the learned iteration forgotten
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;  // a pending x update applied, the fused product and the learned iteration forgotten
   if (!mat || !X || !R || !P || !W) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
   if (!dev_in || !dev_pw || !dev_out) return set_err(ABFT_ERR_INVALID, "%s: null device scalar", what);
   // one rank only, as the single guarded iterations
@@ -4180,15 +3936,16 @@ extern "C" int abft_hip_cg_block_iteration_until_dev(abft_hip_ctx *ctx, abft_hip
   return ABFT_OK;
 }
 
-// what became of the x updates left pending on the old p: applied by the predicted SpMV, or on their own
+// what became of the calc_p and calc_r launched ahead: taken over by the caller's calls, or dropped
 extern "C" int abft_hip_ahead_stats(abft_hip_ctx *ctx, long *committed_p, long *committed_r, long *dropped) {
   if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");
-  if (committed_p) *committed_p = ctx->spec.a_commit_p;
-  if (committed_r) *committed_r = ctx->spec.a_commit_r;
-  if (dropped) *dropped = ctx->spec.a_drops;
+  if (committed_p) *committed_p = ctx->ahead.commit_p;
+  if (committed_r) *committed_r = ctx->ahead.commit_r;
+  if (dropped) *dropped = ctx->ahead.drops;
   return ABFT_OK;
 }
 
+// what became of the x updates left pending on the old p: applied by the predicted SpMV, or on their own
 extern "C" int abft_hip_x_in_spmv_stats(abft_hip_ctx *ctx, long *absorbed, long *flushed) {
   if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");
   if (absorbed) *absorbed = ctx->xpend.absorbed;
@@ -4209,7 +3966,7 @@ struct abft_hip_graph {
 };
 
 extern "C" int abft_hip_graph_begin(abft_hip_ctx *ctx) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   if (ctx->prof) return set_err(ABFT_ERR_INVALID, "graph capture with kernel brackets enabled (abft_hip_profile_enable)");
   ctx->xin_enabled = false;  // a captured launch holds p's buffer by address: no swap of it from here on
   HIPCHK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
@@ -4245,8 +4002,7 @@ extern "C" int abft_hip_graph_end(abft_hip_ctx *ctx, abft_hip_graph **out) {
 
 extern "C" int abft_hip_graph_launch(abft_hip_graph *g) {
   if (!g) return set_err(ABFT_ERR_INVALID, "null graph");
-  if (int rc = bind(g->ctx)) return rc;
-  g->ctx->fused.valid = false;
+  if (int rc = enter(g->ctx, FORGET_FUSED)) return rc;
   HIPCHK(hipGraphLaunch(g->exec, g->ctx->stream));
   return ABFT_OK;
 }
@@ -4317,7 +4073,7 @@ static void clear_pending_events(abft_hip_ctx *ctx) {
 }
 
 extern "C" int abft_hip_drain_events(abft_hip_ctx *ctx, abft_event *buf, int cap, int *count, int *fatal) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   if (!count || cap < 0 || (cap && !buf)) return set_err(ABFT_ERR_INVALID, "bad drain arguments");
   *count = 0;
   if (fatal) *fatal = 0;
@@ -4386,13 +4142,13 @@ extern "C" int abft_hip_event_capacity(void) { return (int)EVENT_CAP; }
 // -------------------------------------------------------------- measurement --
 
 extern "C" int abft_hip_profile_enable(abft_hip_ctx *ctx, int on) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   ctx->prof = on < 0 ? 0u : (unsigned)on & ((1u << ABFT_K_COUNT) - 1u);
   return ABFT_OK;
 }
 
 extern "C" int abft_hip_profile_stride(abft_hip_ctx *ctx, int stride) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   if (stride < 1) return set_err(ABFT_ERR_INVALID, "profile stride %d", stride);
   ctx->prof_stride = (unsigned)stride;
   for (unsigned &n : ctx->prof_seen) n = 0;
@@ -4400,7 +4156,7 @@ extern "C" int abft_hip_profile_stride(abft_hip_ctx *ctx, int stride) {
 }
 
 extern "C" int abft_hip_profile_reset(abft_hip_ctx *ctx) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (int k = 0; k < ABFT_K_COUNT; k++) {
     KernelTimer::fold(ctx, k);
@@ -4411,7 +4167,7 @@ extern "C" int abft_hip_profile_reset(abft_hip_ctx *ctx) {
 }
 
 extern "C" int abft_hip_profile_read(abft_hip_ctx *ctx, int kernel, double *total_ms, long *launches) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   if (kernel < 0 || kernel >= ABFT_K_COUNT) return set_err(ABFT_ERR_INVALID, "unknown kernel id %d", kernel);
   HIPCHK(hipStreamSynchronize(ctx->stream));
   KernelTimer::fold(ctx, kernel);
@@ -4421,7 +4177,7 @@ extern "C" int abft_hip_profile_read(abft_hip_ctx *ctx, int kernel, double *tota
 }
 
 extern "C" int abft_hip_stream_probe(abft_hip_ctx *ctx, size_t bytes, int reps, double *gbps_copy, double *gbps_read) {
-  if (int rc = bind(ctx)) return rc;
+  if (int rc = enter(ctx, 0)) return rc;
   if (bytes < 1024 || reps < 1) return set_err(ABFT_ERR_INVALID, "bad probe arguments");
   bytes &= ~(size_t)15;
   double *a = nullptr, *b = nullptr;

@@ -18,53 +18,12 @@ calls of that solve next); `model_holds` holds what `run` or `run_turns` read ag
 views made on the way show), the drained events -- and the counters of abft_hip_ahead_stats, abft_hip_x_in_spmv_stats
 and abft_hip_speculation_stats."""
 import ctypes as C
-import math
 
 import numpy as np
 
+from _loop_scripts import expected, predicted, ulps  # noqa: F401  (they live where a test without a GPU can import them)
 from _x_in_spmv import bits, matrix, same  # noqa: F401  (same: re-exported for the tests)
 from abft_sparse_cg_amd.context import fdiv
-
-
-def predicted(k):
-    return [{} for _ in range(k)]
-
-
-def ulps(v, k):
-    for _ in range(abs(k)):
-        v = float(np.nextafter(v, np.inf if k > 0 else -np.inf))
-    return v
-
-
-def expected(script, scalars, level):
-    """(committed_p, committed_r, dropped) of a script without extra steps, from the arming rule and the alpha and beta
-    the run handed in (scalars: rr0, then pw, alpha, rr_new, beta per iteration)"""
-    armed, cp, cr, dropped = False, 0, 0, 0
-    for j, it in enumerate(script):
-        alpha, beta = scalars[1 + 4 * j + 1], scalars[1 + 4 * j + 3]
-        ok_a = not it.get("alpha_ulps") and not math.isnan(alpha)
-        ok_b = ok_a and not it.get("beta_ulps") and not math.isnan(beta)
-        p_ahead = False
-        if level == 2 and armed:  # calc_r and calc_p behind the SpMV
-            if ok_a:
-                cr += 1
-                p_ahead = True
-            else:
-                dropped += 1
-                armed = False
-        elif level >= 1 and armed and ok_a:  # calc_p behind calc_r
-            p_ahead = True
-        elif not ok_a:
-            armed = False
-        if p_ahead:
-            if ok_b:
-                cp += 1
-            else:
-                dropped += 1
-                armed = False
-        else:
-            armed = ok_b
-    return cp, cr, dropped
 
 
 class _Stop(Exception):
