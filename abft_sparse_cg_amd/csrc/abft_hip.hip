@@ -18,6 +18,9 @@
 #include <vector>
 
 #include "abft_internal.h"
+// palettes the pool of a matrix holds beyond those of create (one per re-planned block at most)
+#define ABFT_PAL_SPARE 1024u
+#include "layout_plan.h"
 #include "loop_state.h"
 
 // ------------------------------------------------------------------ errors --
@@ -130,35 +133,38 @@ struct abft_hip_matrix {
   CsrDev csr{};
   CooDev coo{};
   double *fuse_partials = nullptr;  // FuseOut buffer (square matrices)
-  bool use_panels = false;          // panel layout chosen at create time
-  bool coo_pc = false;              // COO panel layout run by spmv_coo_pc_kernel (producer / consumer waves)
-  bool coo_lean = false;            // ... or by spmv_coo_lean_kernel (cold paths out of the hot loop)
+  // chosen at create time (layout_plan.h): Stream (COO: grouped by output), Panels, Sweep (one persistent launch; see
+  // SweepLayout) or Slice (wave-private row sums in LDS; see SliceLayout)
+  Layout layout = Layout::Stream;
+  CooPanelKernel coo_kernel = CooPanelKernel::Panels;  // COO panel layout: spmv_coo_panels_kernel, _pc_ (producer / consumer waves) or _lean_ (cold paths out of the hot loop)
   CsrPanels panels{};
   uint32_t panel_grid = 0;          // workgroups of the panel kernel
   uint32_t panel_chunk = 0;         // panels per launch (0 = all)
-  bool use_sweep = false;           // sweep layout (one persistent launch; see SweepLayout)
   SweepLayout sweep{};
   int sweep_rpt = 8;
   uint32_t sweep_grid = 0, sweep_width = 0;
-  bool use_slice = false;           // slice layout (wave-private row sums in LDS; see SliceLayout)
   SliceLayout slice{};
   uint32_t slice_grid = 0, slice_width = 0;
   // streaming CSR: host copy of the row-block descriptors, and the tiles [t_lo, t_hi)
   // made of interior rows only (abft_hip_matrix_set_interior; empty by default)
-  std::vector<uint4> blk_host;
+  std::vector<Blk> blk_host;
   uint32_t t_lo = 0, t_hi = 0;
   // mode none on that layout: the compact column offsets (see CsrCompact) and a host copy of the bases
   CsrCompact compact{};
   std::vector<uint32_t> cbase_host;
-  // ... and the packed codes (see CsrPacked): host copies of the descriptors and the palette pool,
-  // each palette's place in the pool by its 16 entries, and the pool's device capacity (entries)
+  // ... and the packed codes (see CsrPacked): host copies of the descriptors and the palette pool
   CsrPacked packed{};
-  std::vector<uint2> pdesc_host;
-  std::vector<uint64_t> pal_host;
-  std::map<std::array<uint64_t, ABFT_PAL_ENTRIES>, uint32_t> pal_index;
-  size_t pal_cap = 0;
+  std::vector<Pair> pdesc_host;
+  PalettePool pool;
   std::vector<void *> allocs;
+  bool streams() const { return layout == Layout::Stream; }
 };
+
+// what the kernels read as uint4 / uint2 is uploaded from layout_plan.h's Blk / Pair
+static_assert(sizeof(Blk) == sizeof(uint4) && offsetof(Blk, x) == offsetof(uint4, x) && offsetof(Blk, y) == offsetof(uint4, y) &&
+              offsetof(Blk, z) == offsetof(uint4, z) && offsetof(Blk, w) == offsetof(uint4, w), "Blk is uploaded as uint4");
+static_assert(sizeof(Pair) == sizeof(uint2) && offsetof(Pair, x) == offsetof(uint2, x) && offsetof(Pair, y) == offsetof(uint2, y),
+              "Pair is uploaded as uint2");
 
 static constexpr uint32_t EVENT_CAP = 1u << 16;
 static constexpr size_t VECC_SEEN_BYTES = ABFT_VECC_SEEN_SLOTS * sizeof(unsigned long long);
@@ -506,9 +512,10 @@ static int dev_upload(abft_hip_matrix *m, T **dst, const T *src, size_t count, s
   return ABFT_OK;
 }
 
-static void matrix_free(abft_hip_matrix *m) {
-  if (!m) return;
-  if (m->use_sweep && m->sweep.debug) {
+// ABFT_HIP_SWEEP_DEBUG / ABFT_HIP_PANEL_DEBUG: what the kernels counted into the debug buffers, printed when the
+// matrix is destroyed (the phase clocks need a -DABFT_DBG_STAMPS build)
+static void print_debug_stats(const abft_hip_matrix *m) {
+  if (m->layout == Layout::Sweep && m->sweep.debug) {
     uint32_t d[16] = {0};
     if (hipMemcpy(d, m->sweep.debug, sizeof(d), hipMemcpyDeviceToHost) == hipSuccess) {
       fprintf(stderr, "sweep pacing: %u workgroup exits, %u waits, %u unsuccessful polls (lag %u, %u panels, grid %u)\n",
@@ -579,7 +586,7 @@ static void matrix_free(abft_hip_matrix *m) {
       }
     }
   }
-  if (m->use_panels && m->panels.debug) {
+  if (m->layout == Layout::Panels && m->panels.debug) {
     unsigned long long t[16] = {0};
     if (hipMemcpy(t, m->panels.debug, sizeof(t), hipMemcpyDeviceToHost) == hipSuccess)
       for (int h = 0; h < 2; h++) {
@@ -594,80 +601,171 @@ static void matrix_free(abft_hip_matrix *m) {
                 100.0 * (double)(q[7] - known) / q[7]);
       }
   }
+}
+
+static void matrix_free(abft_hip_matrix *m) {
+  if (!m) return;
+  print_debug_stats(m);
   for (void *p : m->allocs) (void)hipFree(p);
   delete m;
 }
 
-// Cut [0, n) into blocks of whole segments whose elements fit one LDS tile.
-// `align2`: the tile starts at the even element at or below the block's first
-// element (CSR pair loads), so that one counts against the capacity too.
-static void cut_blocks(const uint32_t *ptr, uint32_t n, uint32_t tile, bool align2,
-                       std::vector<uint4> &blk) {
-  const uint32_t max_segments = 4 * ABFT_BLOCK;
-  blk.clear();
-  uint32_t s = 0;
-  while (s < n) {
-    const uint32_t base = align2 ? (ptr[s] & ~1u) : ptr[s];
-    uint32_t e = s;
-    while (e < n && e - s < max_segments && ptr[e + 1] >= ptr[e] && ptr[e + 1] - base <= tile) e++;
-    if (e == s) e = s + 1;  // a single segment longer than a tile: walked tile by tile
-    blk.push_back(make_uint4(s, e, ptr[s], ptr[e]));
-    s = e;
+// the matrix under construction: freed, with everything uploaded so far, on every way out but release()
+struct MatrixGuard {
+  abft_hip_matrix *m;
+  explicit MatrixGuard(abft_hip_matrix *m_) : m(m_) {}
+  MatrixGuard(const MatrixGuard &) = delete;
+  MatrixGuard &operator=(const MatrixGuard &) = delete;
+  ~MatrixGuard() { matrix_free(m); }
+  abft_hip_matrix *release() {
+    abft_hip_matrix *r = m;
+    m = nullptr;
+    return r;
   }
+};
+
+// ---- layout planning: layout_plan.h decides, this file reads the knobs, uploads and attaches ----
+
+static const PlanGeometry g_geometry = {(uint32_t)ABFT_BLOCK,      (uint32_t)ABFT_CSR_TILE,      (uint32_t)ABFT_COO_TILE,
+                                        (uint32_t)ABFT_PANEL_ROWS, (uint32_t)ABFT_CFG_SWEEP_EPT, 4u * (uint32_t)ABFT_BLOCK};
+
+// the layout knobs, read once per create (a caller may change the environment between two creates)
+static LayoutKnobs from_env() {
+  return read_knobs([](const char *name) -> const char * { return getenv(name); });
 }
 
-// Flag the CSR row blocks whose rows all have the same length -- bit 31 of the end row:
-// the kernel then derives each row's range from the block descriptor alone and never reads
-// the row pointers (banded matrices: nearly every block; measured 151 -> 138 us on config
-// 2's SpMV, 143 -> 134 us in secded; the same shortcut in the COO kernel was 4 % slower).
-static void flag_uniform_blocks(const uint32_t *ptr, uint32_t tile, std::vector<uint4> &blk) {
-  for (uint4 &b : blk) {
-    const uint32_t nseg = b.y - b.x;
-    if (nseg < 2 || b.w - b.z > tile || nseg > (uint32_t)ABFT_BLOCK) continue;
-    const uint32_t len = ptr[b.x + 1] - ptr[b.x];
-    bool same = len > 0 && (b.w - b.z) == len * nseg;
-    for (uint32_t r = b.x; same && r < b.y; r++) same = ptr[r + 1] - ptr[r] == len;
-    if (same) b.y |= 0x80000000u;
-  }
+template <typename T>
+static int upload_all(abft_hip_matrix *m, T **dst, const std::vector<T> &v) {
+  return dev_upload(m, dst, v.data(), v.size(), v.size());
 }
 
-// Mode none, streaming layout: the compact column offsets (see CsrCompact).  A block the SpMV
-// stages as one tile whose columns span at most 65536 values gets its smallest column as base
-// and every column as a 16-bit offset from it; every other block stays wide.  Config 2: a block
-// of ~204 rows of the 3162-wide band spans ~6 530 columns.  ABFT_HIP_COMPACT_COLS=0: all wide,
-// nothing allocated (A/B runs in one build).
-static int build_compact_cols(abft_hip_matrix *m, const uint32_t *columns, const std::vector<uint4> &blk,
-                              size_t padded) {
-  if (const char *e = getenv("ABFT_HIP_COMPACT_COLS"))
-    if (!strcmp(e, "0")) return ABFT_OK;
-  std::vector<uint32_t> cbase(blk.size(), ABFT_CBASE_WIDE);
-  std::vector<uint16_t> c16(padded + 2, 0);  // the kernel's 8-byte load at the last even index reads 2 past cols' padding
-  bool any = false;
-  for (size_t b = 0; b < blk.size(); b++) {
-    const uint32_t e0 = blk[b].z, e1 = blk[b].w;
-    if (e1 < e0 || e1 - (e0 & ~1u) > (uint32_t)ABFT_CSR_TILE) continue;  // walked tile by tile: reads cols
-    uint32_t lo = 0, hi = 0;
-    if (e1 > e0) lo = hi = columns[e0];
-    for (uint32_t i = e0; i < e1; i++) {
-      lo = std::min(lo, columns[i]);
-      hi = std::max(hi, columns[i]);
-    }
-    if (hi - lo > 0xFFFFu) continue;
-    cbase[b] = lo;
-    for (uint32_t i = e0; i < e1; i++) c16[i] = (uint16_t)(columns[i] - lo);
-    any = true;
+// a progress board per XCD: 8 boards of PACE_SLOTS "nobody here" (kernels.hip: PACE_*)
+static int pace_board(abft_hip_matrix *m, uint32_t **board) {
+  const std::vector<uint32_t> init(8 * 256, 0xffffffffu);
+  if (int rc = upload_all(m, board, init)) return rc;
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // `init` goes out of scope
+  return ABFT_OK;
+}
+
+// `count` zeroed words a kernel counts into for print_debug_stats
+template <typename T>
+static int debug_buffer(abft_hip_matrix *m, T **buf, size_t count) {
+  const std::vector<T> zero(count, 0);
+  if (int rc = upload_all(m, buf, zero)) return rc;
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));
+  return ABFT_OK;
+}
+
+// CSR, every layout but the streaming one: cols / vals in storage order, and the two index maps
+static int upload_permuted(abft_hip_matrix *m, const std::vector<uint32_t> &pos, const std::vector<uint32_t> &orig,
+                           const uint32_t *columns, const double *values, size_t padded) {
+  CsrDev &A = m->csr;
+  const size_t nnz = A.nnz;
+  std::vector<uint32_t> pcols(nnz);
+  std::vector<double> pvals(nnz);
+  for (size_t i = 0; i < nnz; i++) {
+    pcols[pos[i]] = columns[i];
+    pvals[pos[i]] = values[i];
   }
-  if (!any) return ABFT_OK;
+  uint32_t *d_orig = nullptr, *d_pos = nullptr;
+  int rc;
+  if ((rc = dev_upload(m, &A.cols, pcols.data(), nnz, padded)) || (rc = dev_upload(m, &A.vals, pvals.data(), nnz, padded)) ||
+      (rc = dev_upload(m, &d_orig, orig.data(), nnz, nnz)) || (rc = dev_upload(m, &d_pos, pos.data(), nnz, nnz)))
+    return rc;
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // pcols/pvals go out of scope
+  A.orig_index = d_orig;
+  A.pos_of_orig = d_pos;
+  return ABFT_OK;
+}
+
+// CSR and COO: the segment tables of the panel layout (`pb` outlives the create's last synchronize)
+static int attach_panels(abft_hip_matrix *m, const PanelBuild &pb, const LayoutKnobs &knobs) {
+  uint32_t *d_segbase = nullptr;
+  uint16_t *d_segptr = nullptr;
+  int rc;
+  if ((rc = upload_all(m, &d_segbase, pb.seg_base)) || (rc = upload_all(m, &d_segptr, pb.seg_ptr))) return rc;
+  m->layout = Layout::Panels;
+  m->panels.seg_base = d_segbase;
+  m->panels.seg_ptr = d_segptr;
+  m->panels.ngroups = pb.ngroups;
+  m->panels.npanels = pb.npanels;
+  m->panels.width = pb.width;
+  m->panels.xpf = (uint32_t)std::max(0L, knobs.xpf);
+  m->panels.debug = nullptr;
+  if (knobs.panel_debug) return debug_buffer(m, &m->panels.debug, 16);  // phase clocks of a -DABFT_DBG_STAMPS build
+  return ABFT_OK;
+}
+
+static int attach_sweep(abft_hip_matrix *m, const SweepBuild &sb, uint32_t capacity, const LayoutKnobs &knobs) {
+  int rc;
+  uint32_t *d_wbase = nullptr;
+  uint8_t *d_counts = nullptr;
+  if ((rc = upload_all(m, &d_wbase, sb.wbase)) || (rc = upload_all(m, &d_counts, sb.counts)) || (rc = pace_board(m, &m->sweep.pace)))
+    return rc;
+  m->layout = Layout::Sweep;
+  m->sweep_grid = sweep_grid(sb.ngroups, capacity);
+  m->sweep_rpt = sb.rpt;
+  m->sweep_width = sb.width;
+  m->sweep.wbase = d_wbase;
+  m->sweep.counts = d_counts;
+  m->sweep.ngroups = sb.ngroups;
+  m->sweep.npanels = sb.npanels;
+  m->sweep.lag = knob_u32(knobs.sweep_lag, 0L, 2u);  // workgroups of an XCD spread over at most two consecutive panels
+  if (knobs.sweep_debug)  // pacing statistics, and per workgroup clocks
+    if ((rc = debug_buffer(m, &m->sweep.debug, 16)) ||
+        (rc = debug_buffer(m, &m->sweep.debug_wg, 4u * (size_t)std::max<uint32_t>(sb.ngroups, 1u))))
+      return rc;
+  return ABFT_OK;
+}
+
+static int attach_slice(abft_hip_matrix *m, const SliceBuild &sb, uint32_t waves, const LayoutKnobs &knobs) {
+  int rc;
+  uint32_t *d_sub = nullptr;
+  uint16_t *d_rid = nullptr;
+  if ((rc = upload_all(m, &d_sub, sb.sub)) || (rc = upload_all(m, &d_rid, sb.rid)) || (rc = pace_board(m, &m->slice.pace))) return rc;
+  m->layout = Layout::Slice;
+  m->slice_grid = slice_grid(sb.nslices, waves);
+  m->slice_width = sb.width;
+  m->slice.sub = d_sub;
+  m->slice.rid = d_rid;
+  m->slice.nslices = sb.nslices;
+  m->slice.npanels = sb.npanels;
+  m->slice.rows_log2 = sb.rows_log2;
+  m->slice.lag = knob_u32(knobs.slice_lag, 0L, 2u);
+  return ABFT_OK;
+}
+
+// Mode none, streaming layout: the compact column offsets (see CsrCompact) of the blocks that have them.
+// ABFT_HIP_COMPACT_COLS=0, or no such block: all wide, nothing allocated (A/B runs in one build).
+static int attach_compact(abft_hip_matrix *m, CompactBuild &cb) {
+  if (!cb.any) return ABFT_OK;
   uint16_t *d16 = nullptr;
   uint32_t *dbase = nullptr;
   int rc;
-  if ((rc = dev_upload(m, &d16, c16.data(), c16.size(), c16.size())) ||
-      (rc = dev_upload(m, &dbase, cbase.data(), cbase.size(), cbase.size())))
-    return rc;
-  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // c16 / cbase go out of scope
+  if ((rc = upload_all(m, &d16, cb.c16)) || (rc = upload_all(m, &dbase, cb.cbase))) return rc;
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // cbase moves
   m->compact.cols16 = d16;
   m->compact.cbase = dbase;
-  m->cbase_host = std::move(cbase);
+  m->cbase_host = std::move(cb.cbase);
+  return ABFT_OK;
+}
+
+// ... and the packed codes (see CsrPacked); the pool has room for the palettes injects add.
+// ABFT_HIP_PACKED=0, or no block packs: nothing allocated.
+static int attach_packed(abft_hip_matrix *m, PackedBuild &pk) {
+  if (!pk.any) return ABFT_OK;
+  uint16_t *dcode = nullptr;
+  Pair *ddesc = nullptr;
+  uint64_t *dpal = nullptr;
+  int rc;
+  if ((rc = upload_all(m, &dcode, pk.codes)) || (rc = upload_all(m, &ddesc, pk.pdesc)) ||
+      (rc = dev_upload(m, &dpal, m->pool.host.data(), m->pool.host.size(), m->pool.cap)))
+    return rc;
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // pdesc moves
+  m->packed.code16 = dcode;
+  m->packed.pdesc = reinterpret_cast<const uint2 *>(ddesc);
+  m->packed.pal = reinterpret_cast<const double *>(dpal);
+  m->pdesc_host = std::move(pk.pdesc);
   return ABFT_OK;
 }
 
@@ -675,20 +773,14 @@ static int build_compact_cols(abft_hip_matrix *m, const uint32_t *columns, const
 // invariant -- rewrite the offset if the new column is still in [base, base + 65535], else
 // mark the block wide (its SpMV then reads cols, as for any wide block, columns >= N included).
 static int compact_after_inject(abft_hip_matrix *m, uint32_t pos) {
-  const std::vector<uint4> &blk = m->blk_host;
-  // the block holding pos: the last one starting at or before it (an empty block that starts at
-  // pos comes before the one holding pos)
-  auto it = std::upper_bound(blk.begin(), blk.end(), pos, [](uint32_t p, const uint4 &d) { return p < d.z; });
-  if (it == blk.begin()) return ABFT_OK;
-  const size_t b = (size_t)(it - blk.begin()) - 1;
-  if (pos >= blk[b].w || m->cbase_host[b] == ABFT_CBASE_WIDE) return ABFT_OK;
+  const ptrdiff_t b = block_holding(m->blk_host, pos);
+  if (b < 0 || m->cbase_host[b] == ABFT_CBASE_WIDE) return ABFT_OK;
   hipStream_t s = m->ctx->stream;
   uint32_t col = 0;
   HIPCHK(hipMemcpyAsync(&col, m->csr.cols + pos, sizeof(col), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  const uint32_t off = col - m->cbase_host[b];  // (a column below the base wraps to a large offset)
-  if (off <= 0xFFFFu) {
-    const uint16_t o = (uint16_t)off;
+  uint16_t o;
+  if (compact_offset(m->cbase_host[b], col, o)) {
     HIPCHK(hipMemcpyAsync(const_cast<uint16_t *>(m->compact.cols16) + pos, &o, sizeof(o), hipMemcpyHostToDevice, s));
   } else {
     m->cbase_host[b] = ABFT_CBASE_WIDE;
@@ -699,113 +791,13 @@ static int compact_after_inject(abft_hip_matrix *m, uint32_t pos) {
   return ABFT_OK;
 }
 
-// Mode none, streaming layout: the one planner of a packed block (see CsrPacked), at create and
-// after an inject.  Elements [e0, e1) with columns c[] and value bits v[] (indexed from e0): true
-// if the block packs, with its base, shift, padded palette (value patterns ascending, zeros behind)
-// and codes[0, e1 - e0).  A block that packs is one the SpMV stages as one tile (as for compact
-// columns) with at most 16 distinct value patterns whose column span fits the bits left over.
-static bool plan_packed_block(uint32_t e0, uint32_t e1, const uint32_t *c, const uint64_t *v, uint32_t &cbase,
-                              uint32_t &shift, std::array<uint64_t, ABFT_PAL_ENTRIES> &pal, uint16_t *codes) {
-  if (e1 < e0 || e1 - (e0 & ~1u) > (uint32_t)ABFT_CSR_TILE) return false;  // walked tile by tile
-  const uint32_t n = e1 - e0;
-  uint32_t nv = 0, lo = n ? c[0] : 0u, hi = lo;
-  pal.fill(0);
-  for (uint32_t i = 0; i < n; i++) {
-    lo = std::min(lo, c[i]);
-    hi = std::max(hi, c[i]);
-    if (std::find(pal.begin(), pal.begin() + nv, v[i]) == pal.begin() + nv) {
-      if (nv == ABFT_PAL_ENTRIES) return false;
-      pal[nv++] = v[i];
-    }
-  }
-  uint32_t k = 0;
-  while ((1u << k) < nv) k++;
-  shift = 16u - k;
-  if (hi - lo >= (1u << shift)) return false;
-  std::sort(pal.begin(), pal.begin() + nv);
-  cbase = lo;
-  for (uint32_t i = 0; i < n; i++) {
-    const uint32_t idx = (uint32_t)(std::lower_bound(pal.begin(), pal.begin() + nv, v[i]) - pal.begin());
-    codes[i] = (uint16_t)((idx << shift) | (c[i] - lo));
-  }
-  return true;
-}
-
-// palettes the pool holds beyond those of create (one per re-planned block at most)
-#define ABFT_PAL_SPARE 1024u
-
-// the descriptor of a packed block whose palette is `pal`: the palette's place in the pool, appended
-// to the host pool if it is new (the caller uploads the pool)
-static uint2 packed_desc(abft_hip_matrix *m, uint32_t cbase, uint32_t shift,
-                         const std::array<uint64_t, ABFT_PAL_ENTRIES> &pal) {
-  auto it = m->pal_index.find(pal);
-  uint32_t no;
-  if (it != m->pal_index.end()) {
-    no = it->second;
-  } else {
-    no = (uint32_t)(m->pal_host.size() / ABFT_PAL_ENTRIES);
-    m->pal_index.emplace(pal, no);
-    m->pal_host.insert(m->pal_host.end(), pal.begin(), pal.end());
-  }
-  return make_uint2(cbase, no << 5 | shift);
-}
-
-// Mode none, streaming layout, at create: packed codes for every block that packs.
-// ABFT_HIP_PACKED=0: none packed, nothing allocated (A/B runs in one build).
-static int build_packed(abft_hip_matrix *m, const uint32_t *columns, const double *values,
-                        const std::vector<uint4> &blk, size_t padded) {
-  if (const char *e = getenv("ABFT_HIP_PACKED"))
-    if (!strcmp(e, "0")) return ABFT_OK;
-  std::vector<uint2> pdesc(blk.size(), make_uint2(0u, 0u));
-  std::vector<uint16_t> codes(padded + 2, 0);  // as cols16: the kernel's loads at even indices stay inside
-  std::array<uint64_t, ABFT_PAL_ENTRIES> pal;
-  std::vector<uint64_t> vb;
-  bool any = false;
-  for (size_t b = 0; b < blk.size(); b++) {
-    const uint32_t e0 = blk[b].z, e1 = blk[b].w;
-    if (e1 < e0 || e1 - (e0 & ~1u) > (uint32_t)ABFT_CSR_TILE) continue;
-    vb.resize(e1 - e0);
-    if (e1 > e0) memcpy(vb.data(), values + e0, (size_t)(e1 - e0) * 8);
-    uint32_t cbase, shift;
-    if (!plan_packed_block(e0, e1, columns + e0, vb.data(), cbase, shift, pal, codes.data() + e0)) continue;
-    pdesc[b] = packed_desc(m, cbase, shift, pal);
-    any = true;
-  }
-  if (!any) {
-    m->pal_host.clear();
-    m->pal_index.clear();
-    return ABFT_OK;
-  }
-  uint16_t *dcode = nullptr;
-  uint2 *ddesc = nullptr;
-  uint64_t *dpal = nullptr;
-  // room for the palettes injects add: sized once, so the pointer every SpMV (and any captured graph)
-  // holds never changes; an inject that would need more demotes its block instead
-  const size_t cap = m->pal_host.size() + ABFT_PAL_SPARE * ABFT_PAL_ENTRIES;
-  int rc;
-  if ((rc = dev_upload(m, &dcode, codes.data(), codes.size(), codes.size())) ||
-      (rc = dev_upload(m, &ddesc, pdesc.data(), pdesc.size(), pdesc.size())) ||
-      (rc = dev_upload(m, &dpal, m->pal_host.data(), m->pal_host.size(), cap)))
-    return rc;
-  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // codes / pdesc go out of scope
-  m->packed.code16 = dcode;
-  m->packed.pdesc = ddesc;
-  m->packed.pal = reinterpret_cast<const double *>(dpal);
-  m->pal_cap = cap;
-  m->pdesc_host = std::move(pdesc);
-  return ABFT_OK;
-}
-
 // After an inject into element `pos` of a packed block: re-plan the block from the device's
 // vals / cols (the words the SpMV would otherwise read) -- packed anew, with its codes and
 // palette rewritten, or left to the compact / wide path, which compact_after_inject keeps right.
 static int packed_after_inject(abft_hip_matrix *m, uint32_t pos) {
-  const std::vector<uint4> &blk = m->blk_host;
-  auto it = std::upper_bound(blk.begin(), blk.end(), pos, [](uint32_t p, const uint4 &d) { return p < d.z; });
-  if (it == blk.begin()) return ABFT_OK;
-  const size_t b = (size_t)(it - blk.begin()) - 1;
-  if (pos >= blk[b].w || m->pdesc_host[b].y == 0u) return ABFT_OK;
-  const uint32_t e0 = blk[b].z, e1 = blk[b].w, n = e1 - e0;
+  const ptrdiff_t b = block_holding(m->blk_host, pos);
+  if (b < 0 || m->pdesc_host[b].y == 0u) return ABFT_OK;
+  const uint32_t e0 = m->blk_host[b].z, e1 = m->blk_host[b].w, n = e1 - e0;
   hipStream_t s = m->ctx->stream;
   std::vector<uint32_t> c(n);
   std::vector<uint64_t> v(n);
@@ -813,365 +805,27 @@ static int packed_after_inject(abft_hip_matrix *m, uint32_t pos) {
   HIPCHK(hipMemcpyAsync(c.data(), m->csr.cols + e0, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(v.data(), m->csr.vals + e0, (size_t)n * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  uint32_t cbase, shift;
-  std::array<uint64_t, ABFT_PAL_ENTRIES> pal;
-  uint2 d = make_uint2(0u, 0u);  // demoted unless it packs and its palette fits the pool
-  if (plan_packed_block(e0, e1, c.data(), v.data(), cbase, shift, pal, codes.data()) &&
-      (m->pal_index.count(pal) || m->pal_host.size() + ABFT_PAL_ENTRIES <= m->pal_cap)) {
-    const size_t had = m->pal_host.size();
-    d = packed_desc(m, cbase, shift, pal);
-    if (m->pal_host.size() > had)
-      HIPCHK(hipMemcpyAsync(const_cast<double *>(m->packed.pal) + had, m->pal_host.data() + had,
-                            (m->pal_host.size() - had) * 8, hipMemcpyHostToDevice, s));
+  const size_t had = m->pool.host.size();
+  const Pair d = replan_packed_block(g_geometry, m->pool, e0, e1, c.data(), v.data(), codes.data());
+  if (d.y != 0u) {
+    if (m->pool.host.size() > had)
+      HIPCHK(hipMemcpyAsync(const_cast<double *>(m->packed.pal) + had, m->pool.host.data() + had,
+                            (m->pool.host.size() - had) * 8, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(const_cast<uint16_t *>(m->packed.code16) + e0, codes.data(), (size_t)n * 2,
                           hipMemcpyHostToDevice, s));
   }
-  HIPCHK(hipMemcpyAsync(const_cast<uint2 *>(m->packed.pdesc) + b, &d, sizeof(uint2), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(const_cast<uint2 *>(m->packed.pdesc) + b, &d, sizeof(d), hipMemcpyHostToDevice, s));
   HIPCHK(hipStreamSynchronize(s));  // `codes` and `d` are local
   m->pdesc_host[b] = d;  // only once the device holds it
   return ABFT_OK;
 }
 
-// ---- panel layout planning (host) ----------------------------------------------
-
-struct PanelBuild {
-  uint32_t ngroups = 0, npanels = 0, width = 0;
-  std::vector<uint32_t> seg_base;  // nseg + 1
-  std::vector<uint16_t> seg_ptr;   // nseg * (ABFT_PANEL_ROWS + 1)
-  std::vector<uint32_t> pos, orig; // caller's index -> storage position and back
-};
-
-// Decide whether the panel layout pays for this matrix and, if so, build it.
-// `out_idx` / `in_idx` are the element's output index and gather index (CSR: row /
-// column; COO: column / row).  It pays when the input vector is much larger than
-// an XCD's L2 and an output group reaches into several panels (scattered gather
-// indices); banded matrices keep the streaming layout, whose x window already
-// lives in L2.  Needs the gather indices of one output to be non-decreasing in
-// the caller's order (as the reference loader delivers them): panels are swept
-// in ascending order, so an output's additions then happen in the caller's order.
-// ABFT_HIP_LAYOUT=stream|panels|auto and ABFT_HIP_PANEL_WIDTH (entries) override.
-static bool plan_panels(int mode, const uint32_t *in_idx, const uint32_t *out_idx, int n_out, int n_in, int nnz,
-                        PanelBuild &pb, bool constraints_ok = false) {
-  const char *env = getenv("ABFT_HIP_LAYOUT");
-  const bool force = env && (!strcmp(env, "panels") || !strcmp(env, "sweep"));  // (sweep: CSR only, 1-byte counts)
-  // constraints mode: COO only (its checks compare an element with its caller-order successor through a table
-  // of stored positions, whatever the layout; the CSR panel kernel has no check across a panel boundary --
-  // CSR matrices take the sweep layout in that mode)
-  if ((env && !strcmp(env, "stream")) || (mode == ABFT_MODE_CONSTRAINTS && !constraints_ok) || nnz <= 0 || n_out <= 0)
-    return false;
-  uint32_t width = 1u << 18;  // 2 MB of x per panel; two panels per launch (ABFT_HIP_PANEL_CHUNK)
-  if (const char *w = getenv("ABFT_HIP_PANEL_WIDTH")) width = (uint32_t)std::max(1L, atol(w));
-  if (!force && (size_t)n_in * sizeof(double) <= (size_t)8 << 20) return false;
-  const uint64_t ngroups = ((uint64_t)n_out + ABFT_PANEL_ROWS - 1) / ABFT_PANEL_ROWS;
-  const uint64_t npanels = ((uint64_t)n_in + width - 1) / width;
-  const uint64_t nseg = ngroups * npanels;
-  if (nseg == 0 || nseg > ((uint64_t)1 << 27)) return false;
-  // the per-segment offset tables (2 bytes per output and segment) must stay small next to the matrix itself
-  if (!force && nseg * (ABFT_PANEL_ROWS + 1) * sizeof(uint16_t) > (uint64_t)nnz * 3u) return false;
-  {
-    std::vector<uint32_t> last((size_t)n_out, 0);
-    for (int i = 0; i < nnz; i++) {
-      if (in_idx[i] < last[out_idx[i]]) return false;  // would reorder an output's additions
-      last[out_idx[i]] = in_idx[i];
-    }
-  }
-  auto segment = [&](int i) {
-    return (uint64_t)(out_idx[i] / ABFT_PANEL_ROWS) * npanels + std::min<uint64_t>(in_idx[i] / width, npanels - 1);
-  };
-  pb.ngroups = (uint32_t)ngroups; pb.npanels = (uint32_t)npanels; pb.width = width;
-  pb.seg_base.assign(nseg + 1, 0);
-  for (int i = 0; i < nnz; i++) pb.seg_base[segment(i) + 1]++;
-  uint64_t nonempty = 0;
-  for (uint64_t sgm = 0; sgm < nseg; sgm++) {
-    if (pb.seg_base[sgm + 1] > 65535u) return false;  // 16-bit offsets inside a segment
-    nonempty += pb.seg_base[sgm + 1] != 0;
-  }
-  if (!force && nonempty < 3 * ngroups) return false;  // an output group stays within a panel or two: banded
-  for (uint64_t sgm = 0; sgm < nseg; sgm++) pb.seg_base[sgm + 1] += pb.seg_base[sgm];
-  // per segment: offsets of each of its ABFT_PANEL_ROWS outputs (elements of one output contiguous)
-  pb.seg_ptr.assign(nseg * (ABFT_PANEL_ROWS + 1), 0);
-  for (int i = 0; i < nnz; i++) pb.seg_ptr[segment(i) * (ABFT_PANEL_ROWS + 1) + out_idx[i] % ABFT_PANEL_ROWS + 1]++;
-  for (uint64_t sgm = 0; sgm < nseg; sgm++) {
-    uint16_t *p = pb.seg_ptr.data() + sgm * (ABFT_PANEL_ROWS + 1);
-    for (int r = 0; r < ABFT_PANEL_ROWS; r++) p[r + 1] = (uint16_t)(p[r + 1] + p[r]);
-  }
-  // place: segment base + output's offset + arrival order within (segment, output)
-  pb.pos.resize((size_t)nnz);
-  pb.orig.resize((size_t)nnz);
-  std::vector<uint16_t> cursor(nseg * ABFT_PANEL_ROWS, 0);
-  for (int i = 0; i < nnz; i++) {
-    const uint64_t sgm = segment(i);
-    const uint32_t lo = out_idx[i] % ABFT_PANEL_ROWS;
-    const uint32_t p = pb.seg_base[sgm] + pb.seg_ptr[sgm * (ABFT_PANEL_ROWS + 1) + lo] + cursor[sgm * ABFT_PANEL_ROWS + lo]++;
-    pb.pos[i] = p;
-    pb.orig[p] = (uint32_t)i;
-  }
-  return true;
-}
-
-// ---- sweep layout planning (host) ------------------------------------------------
-struct SweepBuild {
-  uint32_t ngroups = 0, npanels = 0, width = 0;
-  int rpt = 8;
-  std::vector<uint32_t> wbase;     // nseg * 4 + 1
-  std::vector<uint8_t> counts;     // [segment][thread][j]
-  std::vector<uint32_t> pos, orig; // caller's index -> storage position and back
-};
-
-// Same decision as plan_panels (scattered columns over a vector much larger than an XCD's
-// L2; a row's columns non-decreasing in the caller's order), then the sweep layout's arrays
-// (CSR: the caller's order is row-major).  `capacity(rpt)`: workgroups of the kernel variant
-// with `rpt` rows per thread that can be resident at once.  ABFT_HIP_LAYOUT=sweep forces it,
-// ABFT_HIP_PANEL_WIDTH / ABFT_HIP_SWEEP_RPT override the geometry.
-template <typename Cap>
-static bool plan_sweep(int mode, const uint32_t *cols, const uint32_t *rows, int n_out, int n_in, int nnz, Cap capacity,
-                       SweepBuild &sb) {
-  const char *env = getenv("ABFT_HIP_LAYOUT");
-  const bool force = env && !strcmp(env, "sweep");
-  // (constraints mode too, round 3: the kernel stages the columns and runs the reference's checks in the
-  // summing phase; round 2 sent that mode to the streaming layout, 2.5 x every other mode on config 4)
-  if ((env && strcmp(env, "sweep") && strcmp(env, "auto")) || nnz <= 0 || n_out <= 0) return false;
-  if (!force && (size_t)n_in * sizeof(double) <= (size_t)8 << 20) return false;
-  // rows per thread: the group size that keeps the most workgroups per CU busy (up to 4: more did
-  // not help), then the fewest rounds, then the smallest groups
-  {
-    double best = -1.0;
-    uint64_t best_rounds = 0;
-    for (int rpt : {2, 4, 8, 16}) {  // (1 row per thread, 8 workgroups per CU: 169 vs 128 us on config 4's 1/8 shard)
-      if (rpt == 16 && mode == ABFT_MODE_CONSTRAINTS) continue;  // (its per-row check state does not fit 128 registers there)
-      const uint64_t groups = ((uint64_t)n_out + 256u * rpt - 1) / (256u * rpt), cap = std::max<uint64_t>(capacity(rpt), 1);
-      const uint64_t rounds = (groups + cap - 1) / cap;
-      const double per_cu = std::min(4.0, (double)((groups + rounds - 1) / rounds) / 256.0);
-      if (per_cu > best + 1e-9 || (per_cu > best - 1e-9 && rounds < best_rounds)) {
-        best = per_cu; best_rounds = rounds; sb.rpt = rpt;
-      }
-    }
-  }
-  if (const char *r = getenv("ABFT_HIP_SWEEP_RPT")) {
-    const int v = atoi(r);
-    if (v == 2 || v == 4 || v == 8 || (v == 16 && mode != ABFT_MODE_CONSTRAINTS)) sb.rpt = v;
-  }
-  // entries of the gathered vector per panel: about 1 MB of it (2 MB: 757 vs 743 us on config 4) unless that
-  // leaves a segment well under two tiles on average -- the 1/8 row shard of config 4 that one rank
-  // of an 8-GPU job multiplies: 161 us with 1 MB panels, 134 us with 2 MB ones
-  // Inside that range the width is set so that the average segment just fills a whole number of
-  // tiles: every tile costs its full load phase, so a segment of 1.6 tiles pays for 2 (config 4,
-  // 16 rows per thread: 3 277 elements per segment at 2^17 entries, 724 us; 4 000 at 164 000 entries
-  // -- two tiles less 1.5 standard deviations -- 681 us; 4 300, where most segments spill into a third
-  // tile, 737 us; `gpurun_out/r2/width_ab2.log`)
-  uint32_t width = 1u << 17;
-  {
-    const uint64_t groups = ((uint64_t)n_out + 256u * sb.rpt - 1) / (256u * sb.rpt);
-    const double tile = 256.0 * (sb.rpt <= 4 ? 4.0 : (double)ABFT_CFG_SWEEP_EPT);
-    const double per_entry = (double)nnz / ((double)groups * (double)n_in);  // elements of a segment per entry of x
-    if ((double)width * per_entry * 2.0 < 3.0 * tile) width = 1u << 18;
-    for (int k = 1; k <= 8; k++) {
-      const double w = (k * tile - 1.5 * std::sqrt(k * tile)) / per_entry;
-      if (w < 0.92 * (double)(1u << 17)) continue;
-      if (w <= 1.25 * (double)(1u << 18)) width = (uint32_t)w & ~15u;
-      break;
-    }
-  }
-  if (const char *w = getenv("ABFT_HIP_PANEL_WIDTH")) width = (uint32_t)std::max(1L, atol(w));
-  const uint64_t npanels = ((uint64_t)n_in + width - 1) / width;
-  if (npanels == 0 || (uint64_t)n_out * npanels > ((uint64_t)1 << 31)) return false;
-  // one count per (row, panel) must stay small next to the matrix itself
-  if (!force && (uint64_t)n_out * npanels > (uint64_t)nnz * 3u) return false;
-  auto panel_of = [&](int i) { return std::min<uint64_t>(cols[i] / width, npanels - 1); };
-  for (int i = 1; i < nnz; i++)
-    if (rows[i] == rows[i - 1] && cols[i] < cols[i - 1]) return false;  // would reorder a row's additions
-  std::vector<uint8_t> rc((size_t)n_out * npanels, 0);  // elements per (row, panel)
-  for (int i = 0; i < nnz; i++) {
-    uint8_t &c = rc[(size_t)rows[i] * npanels + panel_of(i)];
-    if (c == 255u) return false;  // one-byte counts: such a matrix keeps the panel layout
-    c++;
-  }
-  if (!force) {  // a row group that stays within a panel or two is banded: streaming layout
-    const uint64_t g2k = ((uint64_t)n_out + 2047) / 2048;
-    uint64_t nonempty = 0;
-    std::vector<char> seen(npanels);
-    for (uint64_t g = 0; g < g2k; g++) {
-      std::fill(seen.begin(), seen.end(), 0);
-      const uint64_t r1 = std::min<uint64_t>((g + 1) * 2048, (uint64_t)n_out);
-      for (uint64_t r = g * 2048; r < r1; r++)
-        for (uint64_t c = 0; c < npanels; c++) seen[c] |= rc[r * npanels + c] != 0;
-      for (uint64_t c = 0; c < npanels; c++) nonempty += seen[c];
-    }
-    if (nonempty < 3 * g2k) return false;
-  }
-  const uint32_t G = 256u * (uint32_t)sb.rpt, WR = 64u * (uint32_t)sb.rpt;
-  const uint64_t ngroups = ((uint64_t)n_out + G - 1) / G, nseg = ngroups * npanels;
-  if (nseg > ((uint64_t)1 << 26)) return false;
-  sb.ngroups = (uint32_t)ngroups; sb.npanels = (uint32_t)npanels; sb.width = width;
-  // element ranges: per (segment, wave) base, per (segment, thread, j) count
-  sb.wbase.assign(nseg * 4 + 1, 0);
-  sb.counts.assign((size_t)nseg * 256u * sb.rpt + 16, 0);
-  uint64_t run = 0;
-  for (uint64_t g = 0; g < ngroups; g++)
-    for (uint64_t c = 0; c < npanels; c++) {
-      const uint64_t seg = g * npanels + c;
-      for (uint32_t w = 0; w < 4; w++) {
-        sb.wbase[seg * 4 + w] = (uint32_t)run;
-        for (uint32_t j = 0; j < (uint32_t)sb.rpt; j++)
-          for (uint32_t l = 0; l < 64; l++) {
-            const uint64_t row = g * G + w * WR + j * 64 + l;
-            const uint32_t k = row < (uint64_t)n_out ? rc[row * npanels + c] : 0u;
-            sb.counts[(seg * 256u + w * 64u + l) * sb.rpt + j] = (uint8_t)k;
-            run += k;
-          }
-      }
-    }
-  sb.wbase[nseg * 4] = (uint32_t)run;
-  // placement: rows ascending, a row's elements in the caller's order.  Inside a segment the
-  // rows follow the ownership order (wave, j, lane) = ascending local index, so filling the
-  // segments in row order lands every element at its place.
-  sb.pos.resize((size_t)nnz);
-  sb.orig.resize((size_t)nnz);
-  std::vector<uint32_t> fill(nseg, 0);
-  for (int i = 0; i < nnz; i++) {
-    const uint64_t seg = (uint64_t)(rows[i] / G) * npanels + panel_of(i);
-    const uint32_t p = sb.wbase[seg * 4] + fill[seg]++;
-    sb.pos[i] = p;
-    sb.orig[p] = (uint32_t)i;
-  }
-  return true;
-}
-
-static int finish_sweep(abft_hip_matrix *m, const SweepBuild &sb, uint32_t capacity) {
-  int rc;
-  uint32_t *d_wbase = nullptr, *d_pace = nullptr;
-  uint8_t *d_counts = nullptr;
-  if ((rc = dev_upload(m, &d_wbase, sb.wbase.data(), sb.wbase.size(), sb.wbase.size())) ||
-      (rc = dev_upload(m, &d_counts, sb.counts.data(), sb.counts.size(), sb.counts.size())))
-    return rc;
-  // all groups resident if they fit; else equal rounds
-  const uint32_t rounds = (sb.ngroups + capacity - 1) / capacity;
-  m->sweep_grid = (sb.ngroups + rounds - 1) / rounds;
-  std::vector<uint32_t> init(8 * 256, 0xffffffffu);  // 8 boards of PACE_SLOTS "nobody here"
-  if ((rc = dev_upload(m, &d_pace, init.data(), init.size(), init.size()))) return rc;
-  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // `init` goes out of scope
-  m->use_sweep = true;
-  m->sweep_rpt = sb.rpt;
-  m->sweep_width = sb.width;
-  m->sweep.wbase = d_wbase;
-  m->sweep.counts = d_counts;
-  m->sweep.ngroups = sb.ngroups;
-  m->sweep.npanels = sb.npanels;
-  m->sweep.pace = d_pace;
-  m->sweep.lag = 2;  // workgroups of an XCD spread over at most two consecutive panels
-  if (const char *e = getenv("ABFT_HIP_SWEEP_LAG")) m->sweep.lag = (uint32_t)std::max(0L, atol(e));
-  if (getenv("ABFT_HIP_SWEEP_DEBUG")) {  // pacing statistics, printed when the matrix is destroyed
-    uint32_t *d_dbg = nullptr;
-    const uint32_t z[16] = {0};
-    if ((rc = dev_upload(m, &d_dbg, z, 16, 16))) return rc;
-    HIPCHK(hipStreamSynchronize(m->ctx->stream));
-    m->sweep.debug = d_dbg;
-    unsigned long long *d_wg = nullptr;
-    std::vector<unsigned long long> zw(4u * (size_t)std::max<uint32_t>(sb.ngroups, 1u), 0ull);
-    if ((rc = dev_upload(m, &d_wg, zw.data(), zw.size(), zw.size()))) return rc;
-    HIPCHK(hipStreamSynchronize(m->ctx->stream));
-    m->sweep.debug_wg = d_wg;
-  }
-  return ABFT_OK;
-}
-
-// ---- slice layout planning (host) ------------------------------------------------
-struct SliceBuild {
-  uint32_t nslices = 0, npanels = 0, width = 0, rows_log2 = 0;
-  std::vector<uint32_t> sub;       // nslices * (npanels + 1)
-  std::vector<uint16_t> rid;       // per stored element
-  std::vector<uint32_t> pos, orig; // caller's index -> storage position and back
-};
-
-// The slice layout's arrays (see SliceLayout).  Opt-in only (ABFT_HIP_LAYOUT=slice): measured slower than
-// the sweep layout on config 4 and on its 1/8 shard, kept for A/B runs and because it
-// has no limit on the elements of one row in one panel.  Needs a row's columns non-decreasing in the
-// caller's order (panels ascend).  `waves(rows_log2)`: waves of the kernel resident at once with slices
-// of that many rows.  ABFT_HIP_PANEL_WIDTH / ABFT_HIP_SLICE_ROWS / ABFT_HIP_SLICE_LAG override the geometry.
-template <typename Cap>
-static bool plan_slice(int mode, const uint32_t *cols, const uint32_t *rows, int n_out, int n_in, int nnz, Cap waves,
-                       SliceBuild &sb) {
-  const char *env = getenv("ABFT_HIP_LAYOUT");
-  if (!env || strcmp(env, "slice") || mode == ABFT_MODE_CONSTRAINTS || nnz <= 0 || n_out <= 0) return false;
-  const bool force = true;
-  for (int i = 1; i < nnz; i++)
-    if (rows[i] == rows[i - 1] && cols[i] < cols[i - 1]) return false;  // would reorder a row's additions
-  // rows per slice: the smallest power of two (64..1024) with which every slice has a wave of its
-  // own at once; beyond that, 512 and several rounds
-  uint32_t lg = 6;
-  while (lg < 10 && ((uint64_t)n_out + (1u << lg) - 1) >> lg > waves(lg)) lg++;
-  if (((uint64_t)n_out + (1u << lg) - 1) >> lg > waves(lg)) lg = 9;
-  if (const char *r = getenv("ABFT_HIP_SLICE_ROWS")) {
-    const long v = atol(r);
-    for (uint32_t k = 4; k <= 11; k++)
-      if (v == (1L << k)) lg = k;
-  }
-  uint32_t width = 1u << 17;  // entries of the gathered vector per panel (1 MB of it)
-  if (const char *w = getenv("ABFT_HIP_PANEL_WIDTH")) width = (uint32_t)std::max(1L, atol(w));
-  const uint64_t npanels = ((uint64_t)n_in + width - 1) / width;
-  const uint64_t nslices = ((uint64_t)n_out + (1u << lg) - 1) >> lg;
-  if (npanels == 0 || nslices * (npanels + 1) > ((uint64_t)1 << 28)) return false;
-  if (!force && nslices * (npanels + 1) * 4u > (uint64_t)nnz * 3u) return false;  // the table must stay small next to the matrix
-  sb.nslices = (uint32_t)nslices; sb.npanels = (uint32_t)npanels; sb.width = width; sb.rows_log2 = lg;
-  auto panel_of = [&](int i) { return std::min<uint64_t>(cols[i] / width, npanels - 1); };
-  sb.sub.assign(nslices * (npanels + 1), 0);
-  // counts per (slice, panel) into sub[s][c + 1] ... then running bases
-  std::vector<uint32_t> cnt(nslices * npanels, 0);
-  for (int i = 0; i < nnz; i++) cnt[(uint64_t)(rows[i] >> lg) * npanels + panel_of(i)]++;
-  uint32_t run = 0;
-  for (uint64_t s = 0; s < nslices; s++) {
-    for (uint64_t c = 0; c < npanels; c++) {
-      sb.sub[s * (npanels + 1) + c] = run;
-      run += cnt[s * npanels + c];
-    }
-    sb.sub[s * (npanels + 1) + npanels] = run;
-  }
-  // placement in the caller's order: inside a (slice, panel) run rows ascend and a row's elements keep their order
-  sb.pos.resize((size_t)nnz);
-  sb.orig.resize((size_t)nnz);
-  sb.rid.assign((size_t)nnz + 2, 0);
-  std::fill(cnt.begin(), cnt.end(), 0);
-  for (int i = 0; i < nnz; i++) {
-    const uint64_t s = rows[i] >> lg, c = panel_of(i);
-    const uint32_t p = sb.sub[s * (npanels + 1) + c] + cnt[s * npanels + c]++;
-    sb.pos[i] = p;
-    sb.orig[p] = (uint32_t)i;
-    sb.rid[p] = (uint16_t)(rows[i] - (uint32_t)(s << lg) + 1u);  // 0 = no element (what a load past the end returns)
-  }
-  return true;
-}
-
-static int finish_slice(abft_hip_matrix *m, const SliceBuild &sb, uint32_t waves) {
-  int rc;
-  uint32_t *d_sub = nullptr, *d_pace = nullptr;
-  uint16_t *d_rid = nullptr;
-  if ((rc = dev_upload(m, &d_sub, sb.sub.data(), sb.sub.size(), sb.sub.size())) ||
-      (rc = dev_upload(m, &d_rid, sb.rid.data(), sb.rid.size(), sb.rid.size())))
-    return rc;
-  std::vector<uint32_t> init(8 * 256, 0xffffffffu);
-  if ((rc = dev_upload(m, &d_pace, init.data(), init.size(), init.size()))) return rc;
-  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // `init` goes out of scope
-  // all slices resident if they fit; else equal rounds
-  const uint32_t groups = (sb.nslices + 3u) / 4u, cap = std::max(waves / 4u, 1u);
-  const uint32_t rounds = (groups + cap - 1) / cap;
-  m->slice_grid = (groups + rounds - 1) / rounds;
-  m->use_slice = true;
-  m->slice_width = sb.width;
-  m->slice.sub = d_sub;
-  m->slice.rid = d_rid;
-  m->slice.nslices = sb.nslices;
-  m->slice.npanels = sb.npanels;
-  m->slice.rows_log2 = sb.rows_log2;
-  m->slice.pace = d_pace;
-  m->slice.lag = 2;
-  if (const char *e = getenv("ABFT_HIP_SLICE_LAG")) m->slice.lag = (uint32_t)std::max(0L, atol(e));
-  return ABFT_OK;
-}
-
-static int create_csr(abft_hip_ctx *ctx, int mode, const uint32_t *columns, const uint32_t *rows,
-                      const double *values, int n_out, int n_in, int nnz, uint32_t index_base,
-                      abft_hip_matrix **out, bool force_stream) {
-  // validate: a bad index must fail here, loudly, not fault a kernel later
+// validate, plan (layout_plan.h), upload, attach, encode
+static int create_csr(abft_hip_matrix *m, const LayoutKnobs &knobs, const uint32_t *columns, const uint32_t *rows,
+                      const double *values, int n_out, int n_in, int nnz, uint32_t index_base, bool force_stream) {
+  abft_hip_ctx *ctx = m->ctx;
+  const int mode = m->mode;
+  // a bad index must fail here, loudly, not fault a kernel later
   for (int i = 0; i < nnz; i++) {
     if (rows[i] >= (uint32_t)n_out)
       return set_err(ABFT_ERR_INVALID, "row index %u at element %d is outside [0,%d)", rows[i], i, n_out);
@@ -1181,245 +835,87 @@ static int create_csr(abft_hip_ctx *ctx, int mode, const uint32_t *columns, cons
       return set_err(ABFT_ERR_RANGE, "column %u at element %d needs more than 24 bits: ECC modes keep "
                      "their check bits in the column's top byte", columns[i], i);
   }
-  abft_hip_matrix *m = new (std::nothrow) abft_hip_matrix();
-  if (!m) return set_err(ABFT_ERR_NOMEM, "matrix allocation failed");
-  m->ctx = ctx; m->fmt = ABFT_FMT_CSR; m->mode = mode;
-  // row pointers exactly as the reference builds them (CSR/CPUContext.cpp:24-41);
-  // trailing empty rows get nnz (the reference leaves them uninitialised)
-  std::vector<uint32_t> rowptr((size_t)n_out + 1);
-  uint32_t next = 0;
-  for (int i = 0; i < nnz; i++)
-    while (next <= rows[i]) rowptr[next++] = (uint32_t)i;
-  while (next <= (uint32_t)n_out) rowptr[next++] = (uint32_t)nnz;
-  std::vector<uint4> blk;
-  cut_blocks(rowptr.data(), (uint32_t)n_out, ABFT_CSR_TILE, true, blk);
-  flag_uniform_blocks(rowptr.data(), ABFT_CSR_TILE, blk);
+  // streaming row blocks (default), or for scattered x the sweep layout (ABFT_HIP_LAYOUT=panels: its chunked-launch
+  // predecessor; =slice: kept for A/B runs)
+  auto slice_waves = [&](uint32_t lg) { return (uint64_t)spmv_slice_blocks_per_cu(mode, lg) * 4u * (uint64_t)ctx->num_cus; };
+  auto sweep_cap = [&](int rpt) { return (uint64_t)spmv_sweep_blocks_per_cu(mode, rpt) * (uint64_t)ctx->num_cus; };
+  CsrPlan plan;
+  plan_csr(g_geometry, knobs, mode == ABFT_MODE_NONE, mode == ABFT_MODE_CONSTRAINTS, force_stream, columns, rows, values, n_out,
+           n_in, nnz, slice_waves, sweep_cap, m->pool, plan);
 
   CsrDev &A = m->csr;
   A.n_out = (uint32_t)n_out; A.n_in = (uint32_t)n_in; A.nnz = (uint32_t)nnz; A.index_base = index_base;
-  A.nblk = (uint32_t)blk.size();
+  A.nblk = (uint32_t)plan.blk.size();
   A.orig_index = nullptr;
   A.pos_of_orig = nullptr;
-  const size_t padded = ((size_t)nnz + 3) & ~(size_t)1;  // even, >= nnz + 2
   int rc;
+  if (plan.layout == Layout::Stream) {
+    if ((rc = dev_upload(m, &A.cols, columns, (size_t)nnz, plan.padded)) || (rc = dev_upload(m, &A.vals, values, (size_t)nnz, plan.padded)))
+      return rc;
+  } else {
+    if ((rc = upload_permuted(m, plan.pos(), plan.orig(), columns, values, plan.padded))) return rc;
+    if (plan.layout == Layout::Slice) rc = attach_slice(m, plan.slice, (uint32_t)slice_waves(plan.slice.rows_log2), knobs);
+    else if (plan.layout == Layout::Sweep) rc = attach_sweep(m, plan.sweep, (uint32_t)sweep_cap(plan.sweep.rpt), knobs);
+    else rc = attach_panels(m, plan.panels, knobs);
+    if (rc) return rc;
+  }
   uint32_t *d_rowptr = nullptr;
-  uint4 *d_blk = nullptr;
-
-  // ---- layout: streaming row blocks (default), or for scattered x the sweep layout
-  // ---- (ABFT_HIP_LAYOUT=panels: its chunked-launch predecessor, kept for A/B runs) ----
-  SliceBuild lb;
-  auto slice_waves = [&](uint32_t lg) { return (uint64_t)spmv_slice_blocks_per_cu(mode, lg) * 4u * (uint64_t)ctx->num_cus; };
-  const bool slice = !force_stream && plan_slice(mode, columns, rows, n_out, n_in, nnz, slice_waves, lb);
-  SweepBuild sb;
-  auto cap = [&](int rpt) { return (uint64_t)spmv_sweep_blocks_per_cu(mode, rpt) * (uint64_t)ctx->num_cus; };
-  const bool sweep = !force_stream && !slice && plan_sweep(mode, columns, rows, n_out, n_in, nnz, cap, sb);
-  PanelBuild pb;
-  const bool panels = !force_stream && !slice && !sweep && plan_panels(mode, columns, rows, n_out, n_in, nnz, pb);
-  if (slice) {
-    std::vector<uint32_t> pcols((size_t)nnz);
-    std::vector<double> pvals((size_t)nnz);
-    for (int i = 0; i < nnz; i++) {
-      pcols[lb.pos[i]] = columns[i];
-      pvals[lb.pos[i]] = values[i];
-    }
-    uint32_t *d_orig = nullptr, *d_pos = nullptr;
-    if ((rc = dev_upload(m, &A.cols, pcols.data(), (size_t)nnz, padded)) ||
-        (rc = dev_upload(m, &A.vals, pvals.data(), (size_t)nnz, padded)) ||
-        (rc = dev_upload(m, &d_orig, lb.orig.data(), (size_t)nnz, (size_t)nnz)) ||
-        (rc = dev_upload(m, &d_pos, lb.pos.data(), (size_t)nnz, (size_t)nnz)) ||
-        (rc = finish_slice(m, lb, (uint32_t)slice_waves(lb.rows_log2)))) {
-      matrix_free(m);
-      return rc;
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));  // pcols/pvals go out of scope
-    A.orig_index = d_orig;
-    A.pos_of_orig = d_pos;
-  } else if (sweep) {
-    std::vector<uint32_t> pcols((size_t)nnz);
-    std::vector<double> pvals((size_t)nnz);
-    for (int i = 0; i < nnz; i++) {
-      pcols[sb.pos[i]] = columns[i];
-      pvals[sb.pos[i]] = values[i];
-    }
-    uint32_t *d_orig = nullptr, *d_pos = nullptr;
-    if ((rc = dev_upload(m, &A.cols, pcols.data(), (size_t)nnz, padded)) ||
-        (rc = dev_upload(m, &A.vals, pvals.data(), (size_t)nnz, padded)) ||
-        (rc = dev_upload(m, &d_orig, sb.orig.data(), (size_t)nnz, (size_t)nnz)) ||
-        (rc = dev_upload(m, &d_pos, sb.pos.data(), (size_t)nnz, (size_t)nnz)) ||
-        (rc = finish_sweep(m, sb, (uint32_t)cap(sb.rpt)))) {
-      matrix_free(m);
-      return rc;
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));  // pcols/pvals go out of scope
-    A.orig_index = d_orig;
-    A.pos_of_orig = d_pos;
-  } else if (panels) {
-    std::vector<uint32_t> pcols((size_t)nnz);
-    std::vector<double> pvals((size_t)nnz);
-    for (int i = 0; i < nnz; i++) {
-      pcols[pb.pos[i]] = columns[i];
-      pvals[pb.pos[i]] = values[i];
-    }
-    uint32_t *d_segbase = nullptr, *d_orig = nullptr, *d_pos = nullptr;
-    uint16_t *d_segptr = nullptr;
-    if ((rc = dev_upload(m, &A.cols, pcols.data(), (size_t)nnz, padded)) ||
-        (rc = dev_upload(m, &A.vals, pvals.data(), (size_t)nnz, padded)) ||
-        (rc = dev_upload(m, &d_segbase, pb.seg_base.data(), pb.seg_base.size(), pb.seg_base.size())) ||
-        (rc = dev_upload(m, &d_segptr, pb.seg_ptr.data(), pb.seg_ptr.size(), pb.seg_ptr.size())) ||
-        (rc = dev_upload(m, &d_orig, pb.orig.data(), (size_t)nnz, (size_t)nnz)) ||
-        (rc = dev_upload(m, &d_pos, pb.pos.data(), (size_t)nnz, (size_t)nnz))) {
-      matrix_free(m);
-      return rc;
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));  // pcols/pvals go out of scope
-    A.orig_index = d_orig;
-    A.pos_of_orig = d_pos;
-    m->use_panels = true;
-    m->panels.seg_base = d_segbase;
-    m->panels.seg_ptr = d_segptr;
-    m->panels.ngroups = pb.ngroups;
-    m->panels.npanels = pb.npanels;
-    m->panels.width = pb.width;
-    m->panels.xpf = 0;
-    if (const char *e = getenv("ABFT_HIP_PANEL_XPF")) m->panels.xpf = (uint32_t)std::max(0L, atol(e));
-    m->panels.debug = nullptr;
-    if (getenv("ABFT_HIP_PANEL_DEBUG")) {  // phase clocks of a -DABFT_DBG_STAMPS build, printed when the matrix is destroyed
-      unsigned long long *d_dbg = nullptr;
-      const unsigned long long z[16] = {0};
-      if ((rc = dev_upload(m, &d_dbg, z, 16, 16))) return rc;
-      HIPCHK(hipStreamSynchronize(m->ctx->stream));
-      m->panels.debug = d_dbg;
-    }
-  } else if ((rc = dev_upload(m, &A.cols, columns, (size_t)nnz, padded)) ||
-             (rc = dev_upload(m, &A.vals, values, (size_t)nnz, padded))) {
-    matrix_free(m);
-    return rc;
-  }
-  if ((rc = dev_upload(m, &d_rowptr, rowptr.data(), rowptr.size(), rowptr.size())) ||
-      (rc = dev_upload(m, &d_blk, blk.data(), blk.size(), blk.size()))) {
-    matrix_free(m);
-    return rc;
-  }
+  Blk *d_blk = nullptr;
+  if ((rc = upload_all(m, &d_rowptr, plan.rowptr)) || (rc = upload_all(m, &d_blk, plan.blk))) return rc;
   A.rowptr = d_rowptr;
-  A.blk = d_blk;
-  if (!panels && !sweep && !slice) m->blk_host = blk;
-  if (!panels && !sweep && !slice && mode == ABFT_MODE_NONE &&
-      ((rc = build_compact_cols(m, columns, blk, padded)) || (rc = build_packed(m, columns, values, blk, padded)))) {
-    matrix_free(m);
-    return rc;
+  A.blk = reinterpret_cast<const uint4 *>(d_blk);
+  if (plan.layout == Layout::Stream) {
+    m->blk_host = plan.blk;
+    if ((rc = attach_compact(m, plan.compact)) || (rc = attach_packed(m, plan.packed))) return rc;
   }
   hipError_t e = launch_encode_csr(mode, A.cols, A.vals, A.nnz, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // host arrays may be freed on return
-  if (e != hipSuccess) {
-    matrix_free(m);
-    return set_err(ABFT_ERR_HIP, "CSR upload/encode failed: %s", hipGetErrorString(e));
-  }
-  *out = m;
+  if (e != hipSuccess) return set_err(ABFT_ERR_HIP, "CSR upload/encode failed: %s", hipGetErrorString(e));
   return ABFT_OK;
 }
 
-static int create_coo(abft_hip_ctx *ctx, int mode, const uint32_t *columns, const uint32_t *rows,
-                      const double *values, int n_out, int n_in, int nnz, uint32_t index_base,
-                      abft_hip_matrix **out) {
+static int create_coo(abft_hip_matrix *m, const LayoutKnobs &knobs, const uint32_t *columns, const uint32_t *rows,
+                      const double *values, int n_out, int n_in, int nnz, uint32_t index_base) {
+  abft_hip_ctx *ctx = m->ctx;
+  const int mode = m->mode;
   for (int i = 0; i < nnz; i++) {
     if (columns[i] >= (uint32_t)n_out)
       return set_err(ABFT_ERR_INVALID, "column index %u at element %d is outside [0,%d)", columns[i], i, n_out);
     if (mode >= ABFT_MODE_SED && columns[i] > ABFT_COLMASK_HOST)
       return set_err(ABFT_ERR_RANGE, "column %u at element %d needs more than 24 bits", columns[i], i);
   }
-  abft_hip_matrix *m = new (std::nothrow) abft_hip_matrix();
-  if (!m) return set_err(ABFT_ERR_NOMEM, "matrix allocation failed");
-  m->ctx = ctx; m->fmt = ABFT_FMT_COO; m->mode = mode;
-  // Group by output index (col), stable in the caller's order: result[col] is
-  // then summed in the order the reference's serial scatter adds into it
-  // (COO/CPUContext.cpp:111-120).
-  std::vector<uint32_t> grp((size_t)n_out + 1, 0);
-  for (int i = 0; i < nnz; i++) grp[columns[i] + 1]++;
-  for (int c = 0; c < n_out; c++) grp[c + 1] += grp[c];
-  std::vector<uint32_t> fill(grp.begin(), grp.end() - 1);
-  std::vector<uint32_t> orig((size_t)std::max(nnz, 1)), pos((size_t)std::max(nnz, 1));
+  // grouped by output (default), or (output group, row panel) segments
+  CooPlan plan;
+  plan_coo(g_geometry, knobs, mode == ABFT_MODE_CONSTRAINTS, columns, rows, n_out, n_in, nnz, plan);
   struct El { uint32_t col, row; double value; };
   std::vector<El> elems((size_t)std::max(nnz, 1));
-  // layout: grouped by output (default), or (output group, row panel) segments when
-  // the gathered vector is far larger than L2 and the row indices are scattered
-  PanelBuild pb;
-  const bool panels = plan_panels(mode, rows, columns, n_out, n_in, nnz, pb, true);  // gather index = row, output = column
-  for (int i = 0; i < nnz; i++) {
-    const uint32_t p = panels ? pb.pos[i] : fill[columns[i]]++;
-    elems[p] = El{columns[i], rows[i], values[i]};
-    orig[p] = (uint32_t)i;
-    pos[i] = p;
-  }
-  std::vector<uint4> blk;
-  cut_blocks(grp.data(), (uint32_t)n_out, ABFT_COO_TILE, false, blk);
+  for (int i = 0; i < nnz; i++) elems[plan.pos[i]] = El{columns[i], rows[i], values[i]};
 
   CooDev &A = m->coo;
   A.n_out = (uint32_t)n_out; A.n_in = (uint32_t)n_in; A.nnz = (uint32_t)nnz; A.index_base = index_base;
-  A.nblk = (uint32_t)blk.size();
+  A.nblk = (uint32_t)plan.blk.size();
   A.moved = ctx->moved;
   int rc;
   uint32_t *d_grp = nullptr, *d_orig = nullptr, *d_pos = nullptr;
-  uint4 *d_el = nullptr, *d_blk = nullptr;
+  uint4 *d_el = nullptr;
+  Blk *d_blk = nullptr;
   if ((rc = dev_upload(m, &d_el, reinterpret_cast<const uint4 *>(elems.data()), (size_t)nnz, (size_t)nnz + 1)) ||
-      (rc = dev_upload(m, &d_grp, grp.data(), grp.size(), grp.size())) ||
-      (rc = dev_upload(m, &d_blk, blk.data(), blk.size(), blk.size())) ||
-      (rc = dev_upload(m, &d_orig, orig.data(), (size_t)nnz, (size_t)nnz)) ||
-      (rc = dev_upload(m, &d_pos, pos.data(), (size_t)nnz, (size_t)nnz))) {
-    matrix_free(m);
+      (rc = upload_all(m, &d_grp, plan.grp)) || (rc = upload_all(m, &d_blk, plan.blk)) ||
+      (rc = dev_upload(m, &d_orig, plan.orig.data(), (size_t)nnz, (size_t)nnz)) ||
+      (rc = dev_upload(m, &d_pos, plan.pos.data(), (size_t)nnz, (size_t)nnz)))
     return rc;
-  }
-  A.elems = d_el; A.grp_ptr = d_grp; A.blk = d_blk; A.orig_index = d_orig; A.pos_of_orig = d_pos;
+  A.elems = d_el; A.grp_ptr = d_grp; A.blk = reinterpret_cast<const uint4 *>(d_blk); A.orig_index = d_orig; A.pos_of_orig = d_pos;
   if (mode == ABFT_MODE_CONSTRAINTS) {
-    // {col,row} of every stored element as it is now (kernels.hip, coo_constraints_cold); the complement for an
-    // element that fails the reference's checks already (COO/CPUContext.cpp:155-188), which is then checked on
-    // every pass.  (One entry more than elements: lanes past a tile's end read the entry of its first position,
-    // which for an empty tile at the end of the matrix is position nnz.)
-    std::vector<uint2> made((size_t)nnz + 1, make_uint2(0u, 0u));
-    for (int i = 0; i < nnz; i++) {
-      bool fails = rows[i] >= (uint32_t)n_in || columns[i] >= (uint32_t)n_out;
-      if (!fails && i + 1 < nnz) fails = rows[i] > rows[i + 1] || (rows[i] == rows[i + 1] && columns[i] >= columns[i + 1]);
-      made[pos[i]] = fails ? make_uint2(~columns[i], ~rows[i]) : make_uint2(columns[i], rows[i]);
-    }
-    uint2 *d_made = nullptr;
-    if ((rc = dev_upload(m, &d_made, made.data(), made.size(), made.size()))) {
-      matrix_free(m);
-      return rc;
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));  // `made` goes out of scope
-    A.as_created = d_made;
+    Pair *d_made = nullptr;
+    if ((rc = upload_all(m, &d_made, plan.as_created))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    A.as_created = reinterpret_cast<const uint2 *>(d_made);
   }
-  if (panels) {
-    uint32_t *d_segbase = nullptr;
-    uint16_t *d_segptr = nullptr;
-    if ((rc = dev_upload(m, &d_segbase, pb.seg_base.data(), pb.seg_base.size(), pb.seg_base.size())) ||
-        (rc = dev_upload(m, &d_segptr, pb.seg_ptr.data(), pb.seg_ptr.size(), pb.seg_ptr.size()))) {
-      matrix_free(m);
-      return rc;
-    }
-    m->use_panels = true;
-    m->panels.seg_base = d_segbase;
-    m->panels.seg_ptr = d_segptr;
-    m->panels.ngroups = pb.ngroups;
-    m->panels.npanels = pb.npanels;
-    m->panels.width = pb.width;
-    m->panels.xpf = 0;
-    if (const char *e = getenv("ABFT_HIP_PANEL_XPF")) m->panels.xpf = (uint32_t)std::max(0L, atol(e));
-    m->panels.debug = nullptr;
-    if (getenv("ABFT_HIP_PANEL_DEBUG")) {  // phase clocks of a -DABFT_DBG_STAMPS build, printed when the matrix is destroyed
-      unsigned long long *d_dbg = nullptr;
-      const unsigned long long z[16] = {0};
-      if ((rc = dev_upload(m, &d_dbg, z, 16, 16))) return rc;
-      HIPCHK(hipStreamSynchronize(m->ctx->stream));
-      m->panels.debug = d_dbg;
-    }
-  }
+  if (plan.layout == Layout::Panels)
+    if ((rc = attach_panels(m, plan.panels, knobs))) return rc;
   hipError_t e = launch_encode_coo(mode, A.elems, A.nnz, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    matrix_free(m);
-    return set_err(ABFT_ERR_HIP, "COO upload/encode failed: %s", hipGetErrorString(e));
-  }
-  *out = m;
+  if (e != hipSuccess) return set_err(ABFT_ERR_HIP, "COO upload/encode failed: %s", hipGetErrorString(e));
   return ABFT_OK;
 }
 
@@ -1432,65 +928,43 @@ static int create_any(abft_hip_ctx *ctx, int format, int mode, const uint32_t *c
   if (mode < ABFT_MODE_NONE || mode > ABFT_MODE_SECDED) return set_err(ABFT_ERR_INVALID, "unknown mode %d", mode);
   if (n_out < 0 || n_in < 0 || nnz < 0) return set_err(ABFT_ERR_INVALID, "negative size");
   if (nnz && (!columns || !rows || !values)) return set_err(ABFT_ERR_INVALID, "null input array");
-  int rc;
-  if (format == ABFT_FMT_CSR) rc = create_csr(ctx, mode, columns, rows, values, n_out, n_in, nnz, index_base, out, force_stream);
-  else if (format == ABFT_FMT_COO) rc = create_coo(ctx, mode, columns, rows, values, n_out, n_in, nnz, index_base, out);
-  else return set_err(ABFT_ERR_INVALID, "unknown format %d", format);
-  if (rc != ABFT_OK) return rc;
-  abft_hip_matrix *m = *out;
-  const uint32_t nblk = format == ABFT_FMT_CSR ? m->csr.nblk : m->coo.nblk;
-  if (m->use_panels) {
-    const int per_cu = format == ABFT_FMT_CSR ? spmv_csr_panels_blocks_per_cu(mode, true) : 8;
-    m->panel_grid = std::min<uint32_t>(m->panels.ngroups, (uint32_t)(per_cu * ctx->num_cus));
-    // panels per launch: the kernel boundary keeps the chip in one window of x -- 4 MB (config 4's
-    // 33 MB vector: 2 panels per launch were best), 8 MB where the whole vector is only a few L2s
-    // large and its misses come out of the Infinity Cache anyway (config 5, 16.8 MB: 223 us with 2
-    // panels per launch, 207 with 4, 210 with all 8 in one launch)
-    const uint32_t n_in_b = (format == ABFT_FMT_CSR ? m->csr.n_in : m->coo.n_in);
-    m->panel_chunk = (size_t)n_in_b * sizeof(double) <= ((size_t)24 << 20) ? 4 : 2;
-    if (const char *e = getenv("ABFT_HIP_PANEL_CHUNK")) m->panel_chunk = (uint32_t)std::max(0L, atol(e));
-    if (m->panel_chunk) m->panel_grid = m->panels.ngroups;  // one row group per workgroup between boundaries
-    // COO (round 4): ALL panels in one launch, the workgroups of an XCD held inside one window of x by a progress
-    // board per XCD instead of by kernel boundaries (ABFT_HIP_PANEL_LAG: panels a workgroup may be ahead of the
-    // slowest of its XCD; 0 = the chunked launches above)
-    // (config 5, sec7, same box, us per SpMV: two launches of 4 panels 201-202, one unpaced launch 201, paced with
-    // lag 1 / 2 / 3: 207 / 195-196 / 202; panels of 1.3 MB instead of 2 MB: 223 unpaced, 198 with lag 2 --
-    // gpurun_out/r4/c5_ab3.txt, c5_ab4.txt.  Default: lag 2 when every group has its own resident workgroup.)
-    if (format == ABFT_FMT_COO && mode != ABFT_MODE_CONSTRAINTS) {
-      const char *e = getenv("ABFT_HIP_COO_PC");
-      m->coo_pc = e && strcmp(e, "0") != 0;
-      e = getenv("ABFT_HIP_COO_LEAN");
-      m->coo_lean = !m->coo_pc && e && strcmp(e, "0") != 0;
+  if (format != ABFT_FMT_CSR && format != ABFT_FMT_COO) return set_err(ABFT_ERR_INVALID, "unknown format %d", format);
+  const LayoutKnobs knobs = from_env();
+  const bool coo = format == ABFT_FMT_COO;
+  MatrixGuard guard(new (std::nothrow) abft_hip_matrix());
+  abft_hip_matrix *m = guard.m;
+  if (!m) return set_err(ABFT_ERR_NOMEM, "matrix allocation failed");
+  m->ctx = ctx; m->fmt = format; m->mode = mode;
+  if (int rc = coo ? create_coo(m, knobs, columns, rows, values, n_out, n_in, nnz, index_base)
+                   : create_csr(m, knobs, columns, rows, values, n_out, n_in, nnz, index_base, force_stream))
+    return rc;
+  const uint32_t nblk = coo ? m->coo.nblk : m->csr.nblk;
+  if (m->layout == Layout::Panels) {
+    auto resident = [&](CooPanelKernel k) {
+      return (uint32_t)((k == CooPanelKernel::ProducerConsumer ? spmv_coo_pc_blocks_per_cu(mode)
+                         : k == CooPanelKernel::Lean           ? spmv_coo_lean_blocks_per_cu(mode)
+                                                               : spmv_coo_panels_blocks_per_cu(mode)) * ctx->num_cus);
+    };
+    const int per_cu = coo ? 8 : spmv_csr_panels_blocks_per_cu(mode, true);
+    const PanelLaunch L = panel_launch(knobs, coo, mode == ABFT_MODE_CONSTRAINTS, coo ? m->coo.n_in : m->csr.n_in, m->panels.ngroups,
+                                       (uint32_t)(per_cu * ctx->num_cus), resident);
+    m->panel_grid = L.grid;
+    m->panel_chunk = L.chunk;
+    m->coo_kernel = L.kernel;
+    if (L.lag > 0) {
+      if (int rc = pace_board(m, &m->panels.pace)) return rc;
+      m->panels.lag = L.lag;
     }
-    const uint32_t resident = (uint32_t)(format != ABFT_FMT_COO ? 0 : (m->coo_pc ? spmv_coo_pc_blocks_per_cu(mode)
-                                                                      : m->coo_lean ? spmv_coo_lean_blocks_per_cu(mode)
-                                                                                    : spmv_coo_panels_blocks_per_cu(mode)) * ctx->num_cus);
-    uint32_t lag = (format == ABFT_FMT_COO && m->panels.ngroups <= resident && !getenv("ABFT_HIP_PANEL_CHUNK")) ? 2u : 0u;
-    if (const char *e = getenv("ABFT_HIP_PANEL_LAG")) lag = (uint32_t)std::max(0L, atol(e));
-    if (format == ABFT_FMT_COO && lag > 0) {
-      uint32_t *d_pace = nullptr;
-      std::vector<uint32_t> init(8 * 256, 0xffffffffu);  // 8 boards of PACE_SLOTS "nobody here"
-      if ((rc = dev_upload(m, &d_pace, init.data(), init.size(), init.size()))) { matrix_free(m); *out = nullptr; return rc; }
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      m->panels.pace = d_pace;
-      m->panels.lag = lag;
-      m->panel_chunk = 0;
-      m->panel_grid = std::min<uint32_t>(m->panels.ngroups, std::max(resident, 1u));
-    }
-    // (tests: fewer workgroups than groups, i.e. several rounds of groups per workgroup, on small matrices)
-    if (const char *e = getenv("ABFT_HIP_PANEL_GRID")) m->panel_grid = std::max<uint32_t>(1u, std::min<uint32_t>(m->panel_grid, (uint32_t)std::max(1L, atol(e))));
   }
   if (nblk > 0) {  // spmv can also deliver vec[x_off + row].result[row]
     // one partial per SpMV workgroup: row blocks (streaming) or output groups (panels)
-    const uint32_t max_parts = std::max({nblk, m->use_panels ? std::max(m->panel_grid, m->panels.ngroups) : 0u,
-                                         m->use_sweep ? m->sweep_grid : 0u, m->use_slice ? m->slice_grid : 0u});
-    if (hipMalloc((void **)&m->fuse_partials, (size_t)std::max<uint32_t>(max_parts, 1) * sizeof(double)) != hipSuccess) {
-      matrix_free(m);
-      *out = nullptr;
+    const uint32_t max_parts = std::max({nblk, m->layout == Layout::Panels ? std::max(m->panel_grid, m->panels.ngroups) : 0u,
+                                         m->layout == Layout::Sweep ? m->sweep_grid : 0u, m->layout == Layout::Slice ? m->slice_grid : 0u});
+    if (hipMalloc((void **)&m->fuse_partials, (size_t)std::max<uint32_t>(max_parts, 1) * sizeof(double)) != hipSuccess)
       return set_err(ABFT_ERR_NOMEM, "fusion buffer for %u blocks does not fit", nblk);
-    }
     m->allocs.push_back(m->fuse_partials);
   }
+  *out = guard.release();
   return ABFT_OK;
 }
 
@@ -1545,7 +1019,7 @@ extern "C" int abft_hip_matrix_set_interior(abft_hip_matrix *mat, int row_lo, in
   mat->t_lo = mat->t_hi = 0;
   // only the streaming CSR layout launches by row block; elsewhere the interior
   // part stays empty and ABFT_PART_BOUNDARY does all the work
-  const std::vector<uint4> &b = mat->blk_host;
+  const std::vector<Blk> &b = mat->blk_host;
   uint32_t lo = 0;
   while (lo < b.size() && b[lo].x < (uint32_t)row_lo) lo++;  // first tile starting at or after row_lo
   uint32_t hi = lo;
@@ -1556,10 +1030,10 @@ extern "C" int abft_hip_matrix_set_interior(abft_hip_matrix *mat, int row_lo, in
 
 extern "C" int abft_hip_matrix_info(abft_hip_matrix *mat, int *layout, int *launches_per_spmv) {
   if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
-  if (layout) *layout = mat->use_slice ? 3 : mat->use_sweep ? 2 : mat->use_panels ? 1 : 0;
+  if (layout) *layout = layout_number(mat->layout);
   if (launches_per_spmv) {
     int n = 1;
-    if (mat->use_panels && mat->panel_chunk && mat->panels.npanels)
+    if (mat->layout == Layout::Panels && mat->panel_chunk && mat->panels.npanels)
       n = (int)((mat->panels.npanels + mat->panel_chunk - 1) / mat->panel_chunk);
     // (COO: the corrupted-column fix-up rides in the fold of the fused product; without one it is a launch of its own)
     *launches_per_spmv = n;
@@ -1571,9 +1045,9 @@ extern "C" int abft_hip_matrix_compact_stats(abft_hip_matrix *mat, uint32_t *com
                                              uint32_t *mismatches) {
   if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
   if (int rc = enter(mat->ctx, 0)) return rc;
-  const bool stream = mat->fmt == ABFT_FMT_CSR && !mat->use_panels && !mat->use_sweep && !mat->use_slice;
+  const bool stream = mat->fmt == ABFT_FMT_CSR && mat->streams();
   uint32_t nc = 0, bad = 0;
-  const std::vector<uint4> &blk = mat->blk_host;
+  const std::vector<Blk> &blk = mat->blk_host;
   if (stream && mat->compact.cbase) {
     // from the device copies, not the host's bookkeeping: what the SpMV reads
     const CsrDev &A = mat->csr;
@@ -1602,16 +1076,16 @@ extern "C" int abft_hip_matrix_packed_stats(abft_hip_matrix *mat, uint32_t *pack
                                             uint32_t *mismatches) {
   if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
   if (int rc = enter(mat->ctx, 0)) return rc;
-  const bool stream = mat->fmt == ABFT_FMT_CSR && !mat->use_panels && !mat->use_sweep && !mat->use_slice;
+  const bool stream = mat->fmt == ABFT_FMT_CSR && mat->streams();
   uint32_t np = 0, bad = 0;
-  const std::vector<uint4> &blk = mat->blk_host;
+  const std::vector<Blk> &blk = mat->blk_host;
   if (stream && mat->packed.pdesc) {
     // decoded from the device copies, not the host's bookkeeping: what the SpMV reads
     const CsrDev &A = mat->csr;
     hipStream_t s = mat->ctx->stream;
     std::vector<uint2> pdesc(blk.size());
     std::vector<uint32_t> cols(A.nnz);
-    std::vector<uint64_t> vals(A.nnz), pal(mat->pal_host.size());
+    std::vector<uint64_t> vals(A.nnz), pal(mat->pool.host.size());
     std::vector<uint16_t> code(A.nnz);
     HIPCHK(hipMemcpyAsync(pdesc.data(), mat->packed.pdesc, blk.size() * sizeof(uint2), hipMemcpyDeviceToHost, s));
     if (!pal.empty())
@@ -1655,7 +1129,7 @@ extern "C" int abft_hip_matrix_read_csr(abft_hip_matrix *mat, uint32_t *cols, ui
   hipStream_t s = mat->ctx->stream;
   const CsrDev &A = mat->csr;
   if (rowptr) HIPCHK(hipMemcpyAsync(rowptr, A.rowptr, ((size_t)A.n_out + 1) * 4, hipMemcpyDeviceToHost, s));
-  if (!mat->use_panels && !mat->use_sweep && !mat->use_slice) {
+  if (mat->streams()) {
     if (cols && A.nnz) HIPCHK(hipMemcpyAsync(cols, A.cols, (size_t)A.nnz * 4, hipMemcpyDeviceToHost, s));
     if (values && A.nnz) HIPCHK(hipMemcpyAsync(values, A.vals, (size_t)A.nnz * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -2723,7 +2197,7 @@ static bool spmv_can_absorb(const abft_hip_ctx *ctx, const abft_hip_matrix *mat,
                             bool vecc) {
   if (!mat || !vec || !result) return false;
   if (!pending_path_on(*ctx, (unsigned)mat->mode)) return false;  // (not a mode it pays on: a pending update, left by a matrix of another mode, is applied first)
-  if (mat->fmt != ABFT_FMT_CSR || mat->use_slice || mat->use_sweep || mat->use_panels) return false;
+  if (mat->fmt != ABFT_FMT_CSR || !mat->streams()) return false;
   if (part != ABFT_PART_ALL || c1 >= 0 || dev_pair || held || vecc) return false;
   const uint32_t n = mat->csr.n_out;
   return mat->fuse_partials && n != 0 && mat->csr.n_in == n && mat->csr.nblk != 0 &&
@@ -2744,8 +2218,7 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
   if (!mat || !vec || !result) return set_err(ABFT_ERR_INVALID, "spmv: null argument");
   if (vecc) {  // protected vectors: the streaming CSR kernel only; the iteration they are part of is not speculated
     forget_iteration(*ctx);
-    const char *layout = mat->fmt != ABFT_FMT_CSR ? "COO" : mat->use_slice ? "slice" : mat->use_sweep ? "sweep"
-                         : mat->use_panels ? "panel" : nullptr;
+    const char *layout = mat->fmt != ABFT_FMT_CSR ? "COO" : mat->streams() ? nullptr : layout_name(mat->layout);
     if (layout)
       return set_err(ABFT_ERR_INVALID, "spmv_vecc: a matrix in the %s layout (protected vectors run on CSR matrices "
                      "in the streaming layout only)", layout);
@@ -2773,7 +2246,7 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
   if (part == ABFT_PART_INTERIOR && n_int == 0) return ABFT_OK;  // nothing to run ahead of the exchange
   // a range of column panels (layouts that sweep panels): [c0, c1) of them, the sums of an
   // earlier range carried in `result`; the fused product belongs to the range that ends the sweep
-  const uint32_t npan = mat->use_sweep ? mat->sweep.npanels : mat->use_slice ? mat->slice.npanels : 1u;  // (the other layouts run whole)
+  const uint32_t npan = mat->layout == Layout::Sweep ? mat->sweep.npanels : mat->layout == Layout::Slice ? mat->slice.npanels : 1u;  // (the other layouts run whole)
   const bool whole = c1 < 0;
   if (whole) { c0 = 0; c1 = (int)npan; }
   if (c0 < 0 || c0 >= c1 || (uint32_t)c1 > npan) return set_err(ABFT_ERR_INVALID, "spmv: panels [%d,%d) outside [0,%u)", c0, c1, npan);
@@ -2800,24 +2273,24 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
   FixArgs fix{};
   {
     KernelTimer t(ctx, ABFT_K_SPMV);
-    if (mat->use_slice) {
+    if (mat->layout == Layout::Slice) {
       nparts = mat->slice_grid;
       HIPCHK(launch_spmv_slice(mat->mode, mat->csr, mat->slice, vec->d, result->d, ctx->ring, do_fuse ? &fuse : nullptr,
                                mat->slice_grid, (uint32_t)c0, (uint32_t)c1, ctx->stream));
-    } else if (mat->use_sweep) {
+    } else if (mat->layout == Layout::Sweep) {
       nparts = mat->sweep_grid;
       HIPCHK(launch_spmv_sweep(mat->mode, mat->sweep_rpt, mat->csr, mat->sweep, vec->d, result->d, ctx->ring,
                                do_fuse ? &fuse : nullptr, mat->sweep_grid, (uint32_t)c0, (uint32_t)c1, ctx->stream));
-    } else if (mat->fmt == ABFT_FMT_CSR && mat->use_panels) {
+    } else if (mat->fmt == ABFT_FMT_CSR && mat->layout == Layout::Panels) {
       nparts = mat->panel_grid;
       HIPCHK(launch_spmv_csr_panels(mat->mode, mat->csr, mat->panels, vec->d, result->d, ctx->ring,
                                     do_fuse ? &fuse : nullptr, mat->panel_grid, mat->panel_chunk, ctx->stream));
-    } else if (mat->fmt == ABFT_FMT_COO && mat->use_panels) {
+    } else if (mat->fmt == ABFT_FMT_COO && mat->layout == Layout::Panels) {
       nparts = mat->panel_grid;
-      if (mat->coo_pc)
+      if (mat->coo_kernel == CooPanelKernel::ProducerConsumer)
         HIPCHK(launch_spmv_coo_pc(mat->mode, mat->coo, mat->panels, vec->d, result->d, ctx->ring,
                                   do_fuse ? &fuse : nullptr, mat->panel_grid, mat->panel_chunk, ctx->stream));
-      else if (mat->coo_lean)
+      else if (mat->coo_kernel == CooPanelKernel::Lean)
         HIPCHK(launch_spmv_coo_lean(mat->mode, mat->coo, mat->panels, vec->d, result->d, ctx->ring,
                                     do_fuse ? &fuse : nullptr, mat->panel_grid, mat->panel_chunk, ctx->stream));
       else
@@ -2833,7 +2306,7 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
     // COO: products whose stored column was silently corrupted go where the reference puts them --
     // inside the fold of the fused product below when there is one, else as a launch of its own
     if (mat->fmt == ABFT_FMT_COO) {
-      fix = make_fix_args(mat->mode, mat->coo, mat->use_panels ? &mat->panels : nullptr, vec->d, result->d,
+      fix = make_fix_args(mat->mode, mat->coo, mat->layout == Layout::Panels ? &mat->panels : nullptr, vec->d, result->d,
                           do_fuse ? &fuse : nullptr);
       if (!do_fuse) HIPCHK(launch_coo_fixup(fix, ctx->stream));
     }
@@ -2930,10 +2403,10 @@ extern "C" int abft_hip_spmm(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft
   if (mat->fmt != ABFT_FMT_CSR)
     return set_err(ABFT_ERR_INVALID, "spmm: COO matrices have no block SpMV; create the matrix as CSR with "
                    "abft_hip_matrix_create_csr_stream");
-  if (mat->use_panels || mat->use_sweep || mat->use_slice)
+  if (!mat->streams())
     return set_err(ABFT_ERR_INVALID, "spmm: the matrix is stored in the %s layout; the block SpMV runs on the "
                    "streaming row-block layout: create the matrix with abft_hip_matrix_create_csr_stream",
-                   mat->use_slice ? "slice" : mat->use_sweep ? "sweep" : "panel");
+                   layout_name(mat->layout));
   if (mat->csr.n_in != mat->csr.n_out || mat->csr.index_base != 0 || mat->csr.gidx)
     return set_err(ABFT_ERR_INVALID, "spmm: the matrix is a shard; the block SpMV takes a whole square matrix");
   const int N = (int)mat->csr.n_out;
@@ -3268,7 +2741,7 @@ extern "C" int abft_hip_matrix_diag_inverse(abft_hip_ctx *ctx, abft_hip_matrix *
   if (!N) return ABFT_OK;
   hipStream_t s = ctx->stream;
   const uint32_t colmask = mat->mode >= ABFT_MODE_SED ? ABFT_COLMASK_HOST : 0xFFFFFFFFu;
-  if (mat->use_panels || mat->use_sweep || mat->use_slice) {
+  if (!mat->streams()) {
     std::vector<double> d(N, 0.0);
     if (int rc = diag_from_readback(mat, colmask, d)) return rc;
     uint32_t nbad = 0;
@@ -3457,10 +2930,10 @@ static int check_spmm_dot(const char *what, const abft_hip_matrix *mat, const ab
   if (mat->fmt != ABFT_FMT_CSR)
     return set_err(ABFT_ERR_INVALID, "%s: COO matrices have no block SpMV; create the matrix as CSR with "
                    "abft_hip_matrix_create_csr_stream", what);
-  if (mat->use_panels || mat->use_sweep || mat->use_slice)
+  if (!mat->streams())
     return set_err(ABFT_ERR_INVALID, "%s: the matrix is stored in the %s layout; the block SpMV runs on the "
                    "streaming row-block layout: create the matrix with abft_hip_matrix_create_csr_stream", what,
-                   mat->use_slice ? "slice" : mat->use_sweep ? "sweep" : "panel");
+                   layout_name(mat->layout));
   if (mat->csr.index_base != 0 || mat->csr.gidx)
     return set_err(ABFT_ERR_INVALID, "%s: the matrix is a shard; the block SpMV takes a whole square matrix", what);
   if (mat->csr.n_in != mat->csr.n_out)
@@ -3593,8 +3066,8 @@ extern "C" int abft_hip_calc_px_precond_block(abft_hip_ctx *ctx, abft_hip_vector
 
 extern "C" int abft_hip_matrix_panels(abft_hip_matrix *mat, int *npanels, int *width) {
   if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
-  if (npanels) *npanels = mat->use_sweep ? (int)mat->sweep.npanels : mat->use_slice ? (int)mat->slice.npanels : 1;
-  if (width) *width = mat->use_sweep ? (int)mat->sweep_width : mat->use_slice ? (int)mat->slice_width
+  if (npanels) *npanels = mat->layout == Layout::Sweep ? (int)mat->sweep.npanels : mat->layout == Layout::Slice ? (int)mat->slice.npanels : 1;
+  if (width) *width = mat->layout == Layout::Sweep ? (int)mat->sweep_width : mat->layout == Layout::Slice ? (int)mat->slice_width
                                      : (int)(mat->fmt == ABFT_FMT_CSR ? mat->csr.n_in : mat->coo.n_in);
   return ABFT_OK;
 }
@@ -3880,7 +3353,7 @@ extern "C" int abft_hip_block_loop_reserve(abft_hip_ctx *ctx, abft_hip_matrix *m
   if (!mat) return set_err(ABFT_ERR_INVALID, "%s: null matrix", what);
   if (ctx->capturing) return set_err(ABFT_ERR_INVALID, "%s: called under graph capture (it allocates)", what);
   if (k < 1 || k > ABFT_MAX_RHS) return set_err(ABFT_ERR_INVALID, "%s: k = %d outside [1, %d]", what, k, ABFT_MAX_RHS);
-  if (mat->fmt != ABFT_FMT_CSR || mat->use_panels || mat->use_sweep || mat->use_slice)
+  if (mat->fmt != ABFT_FMT_CSR || !mat->streams())
     return set_err(ABFT_ERR_INVALID, "%s: the block loop runs on CSR matrices in the streaming row-block layout "
                    "(abft_hip_matrix_create_csr_stream)", what);
   return block_loop_alloc(ctx, mat, k);
