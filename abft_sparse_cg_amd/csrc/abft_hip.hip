@@ -61,11 +61,18 @@ struct abft_hip_ctx : LoopState {
   abft_hip_ctx() {
     xin_modes = ABFT_X_IN_SPMV_MODES;
     ahead.level = ABFT_AHEAD_DEFAULT;
+    ahead.defer_finish = ABFT_DEFER_FINISH_DEFAULT != 0;
   }
   int device = 0;
   int num_cus = 256;
   hipStream_t own_stream = nullptr, stream = nullptr;
   double *partials = nullptr;  // ABFT_MAX_PARTIALS doubles
+  // The partials of the two reductions a later launch finishes (abft_internal.h, "finished by the launch behind"):
+  // the chunk sums of the fused p.w's fold (64 doubles) and calc_r's block partials (ABFT_MAX_PARTIALS doubles).
+  // RULE: a deferred reduction's partials stay untouched until its consumer kernel has ended.  calc_r stores its
+  // block partials while other blocks of the same launch may still be folding the p.w chunk sums at their head, so
+  // the two never share an area, and neither shares `partials`, which every ticket reduction writes.
+  double *partials_pw = nullptr, *partials_rr = nullptr;
   uint32_t *ticket = nullptr;  // reduction arrival counter (device)
   unsigned long long *tail_sync = nullptr;  // cg_tail_kernel's hand-off words (device; they only ever grow)
   bool tail_enabled = true;       // ABFT_HIP_TAIL=0: the iteration's tail as its three kernels
@@ -368,6 +375,8 @@ extern "C" int abft_hip_init(int device, abft_hip_ctx **out) {
   if (!ctx->own_stream) return set_err(ABFT_ERR_HIP, "hipStreamCreateWithFlags failed");
   ctx->stream = ctx->own_stream;
   HIPCHK(hipMalloc((void **)&ctx->partials, ABFT_MAX_PARTIALS * sizeof(double)));
+  HIPCHK(hipMalloc((void **)&ctx->partials_pw, 64 * sizeof(double)));
+  HIPCHK(hipMalloc((void **)&ctx->partials_rr, ABFT_MAX_PARTIALS * sizeof(double)));
   HIPCHK(hipMalloc((void **)&ctx->ticket, ABFT_TICKET_WORDS * sizeof(uint32_t)));
   HIPCHK(hipMemset(ctx->ticket, 0, ABFT_TICKET_WORDS * sizeof(uint32_t)));
   HIPCHK(hipMalloc((void **)&ctx->tail_sync, 64 * sizeof(unsigned long long)));
@@ -387,6 +396,7 @@ extern "C" int abft_hip_init(int device, abft_hip_ctx **out) {
     if (ctx->xin_enabled) ctx->xin_modes = ~0u;
   }
   if (const char *e = getenv("ABFT_HIP_AHEAD")) ctx->ahead.level = e[0] == '2' ? 2 : e[0] == '1' ? 1 : 0;
+  if (const char *e = getenv("ABFT_HIP_DEFER_FINISH")) ctx->ahead.defer_finish = strcmp(e, "0") != 0;
   loop_settle_switches(*ctx);  // (speculation on: no x-in-SpMV; no x-in-SpMV: no run-ahead)
   HIPCHK(hipHostGetDevicePointer((void **)&ctx->host_slot_dev, ctx->host_slot, 0));
   // the queue, and behind it the table of vector events already queued (abft_internal.h)
@@ -429,6 +439,8 @@ extern "C" int abft_hip_shutdown(abft_hip_ctx *ctx) {
   for (int k = 0; k < ABFT_K_COUNT; k++) KernelTimer::fold(ctx, k);
   for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
   (void)hipFree(ctx->partials);
+  (void)hipFree(ctx->partials_pw);
+  (void)hipFree(ctx->partials_rr);
   (void)hipFree(ctx->alpha_dev);
   (void)hipFree(ctx->ticket);
   if (getenv("ABFT_HIP_TAIL_DEBUG") && ctx->tail_sync) {  // -DABFT_DBG_STAMPS builds: workgroup 0's wall clock (10 ns) at the phase boundaries of the last launch
@@ -1516,34 +1528,66 @@ static int calc_p_launch(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_v
 }
 
 // run-ahead: calc_p(p, r_d, beta = *num / *den) into xpend's buffer (the caller has asked ahead_wants_p / ahead_wants_rp)
+// rr_head: the calc_r in front of it left the finish of its r.r (*num) to this launch -- rr_nb block partials
 static bool ahead_p_launch(abft_hip_ctx *ctx, const abft_hip_vector *p, const double *r_d, const double *num,
-                           const double *den) {
+                           const double *den, const ReduceOut *rr_head = nullptr, uint32_t rr_nb = 0) {
   const int at = xpend_buffer(ctx, p->n);
   if (at < 0) return false;
   KernelTimer t(ctx, ABFT_K_CALC_P);
-  if (launch_calc_p(p->d, r_d, 0.0, num, den, p->n, ctx->stream, ctx->xpend.shadow[at].buf) != hipSuccess) return false;
+  double *p_out = ctx->xpend.shadow[at].buf;
+  const hipError_t e = rr_head ? launch_calc_p_head(p->d, r_d, den, p->n, ctx->stream, p_out, *rr_head, rr_nb)
+                               : launch_calc_p(p->d, r_d, 0.0, num, den, p->n, ctx->stream, p_out);
+  if (e != hipSuccess) return false;
   ctx->ahead.slot = at;
   return true;
 }
 
-// run-ahead, behind spmv(A, p, w) + fold (level 2): calc_r into the shadow with alpha = rr / p.w, calc_p from that shadow
-static void ahead_launch(abft_hip_ctx *ctx, bool eligible, const abft_hip_vector *vec, const abft_hip_vector *result) {
-  if (!ahead_wants_rp(*ctx, eligible, vec, result)) return;
-  auto &I = ctx->iter;
-  const int n = vec->n;
-  if (!shadow_ensure(I.r_shadow, n)) {  // no room: level 1
+// The ReduceOut of a reduction whose finish the next launch does: as `o`, its partials in an area of their own
+// (ctx->partials_pw / partials_rr) and no ticket.
+static ReduceOut deferred_out(ReduceOut o, double *area) {
+  o.partials = area;
+  o.ticket = nullptr;
+  return o;
+}
+
+// run-ahead, behind spmv(A, p, w) (level 2): is it launched, and has it the buffers it writes?  Asked before the
+// fold of the fused p.w goes out, which may leave its finish to the run-ahead's calc_r.
+static bool ahead_prepare(abft_hip_ctx *ctx, bool eligible, const abft_hip_vector *vec, const abft_hip_vector *result) {
+  if (!ahead_wants_rp(*ctx, eligible, vec, result)) return false;
+  if (!shadow_ensure(ctx->iter.r_shadow, vec->n)) {  // no room: level 1
     ctx->ahead.level = 1;
-    return;
+    return false;
   }
-  if (xpend_buffer(ctx, n) < 0) return;
+  return xpend_buffer(ctx, vec->n) >= 0;
+}
+
+// ... and the launches, behind the fold: calc_r into the shadow with alpha = rr / p.w, calc_p from that shadow.
+// pw_head: the fold left the finish of p.w to this calc_r (pw_nb chunk sums).  With ahead.defer_finish calc_r in turn
+// leaves the finish of r.r to the calc_p.  A launch that fails behind a deferred producer: the finisher in its place.
+static void ahead_launch(abft_hip_ctx *ctx, const ReduceOut *pw_head, uint32_t pw_nb) {
+  auto &I = ctx->iter;
+  const int n = I.p->n;
   const ScalTriple s = scal_triple(I);
-  const ReduceOut o = reduce_out(ctx, s.rr_new, true);  // {r.r, events} to the host ring AND to the device
+  const bool defer_rr = ctx->ahead.defer_finish;
+  ReduceOut o = reduce_out(ctx, s.rr_new, true);  // {r.r, events} to the host ring AND to the device
+  if (defer_rr) o = deferred_out(o, ctx->partials_rr);
+  const uint32_t nb = (uint32_t)reduce_blocks(n);
   {
     KernelTimer t(ctx, ABFT_K_CALC_XR);
-    if (launch_calc_r(I.r->d, I.w->d, 0.0, s.rr, s.pw, nullptr, n, o, ctx->stream, I.r_shadow.buf, I.x->d, I.p->d) != hipSuccess) return;
+    const hipError_t e =
+        defer_rr ? launch_calc_r_defer(I.r->d, I.w->d, 0.0, s.rr, s.pw, nullptr, n, o.partials, ctx->stream, I.r_shadow.buf,
+                                       I.x->d, I.p->d, pw_head, pw_nb)
+                 : launch_calc_r(I.r->d, I.w->d, 0.0, s.rr, s.pw, nullptr, n, o, ctx->stream, I.r_shadow.buf, I.x->d, I.p->d);
+    if (e != hipSuccess) {
+      if (pw_head) (void)launch_deferred_finish(*pw_head, pw_nb, ctx->stream);
+      return;
+    }
   }
   r_half_launched(*ctx, InFlight::AheadRP, o.seq);
-  if (!ahead_p_launch(ctx, I.p, I.r_shadow.buf, s.rr_new, s.rr)) drop_in_flight(*ctx);
+  if (!ahead_p_launch(ctx, I.p, I.r_shadow.buf, s.rr_new, s.rr, defer_rr ? &o : nullptr, nb)) {
+    if (defer_rr) (void)launch_deferred_finish(o, nb, ctx->stream);
+    drop_in_flight(*ctx);
+  }
 }
 
 // speculation, behind spmv(A, p, w) + fold: the learned iteration's r half into the shadow
@@ -1606,11 +1650,32 @@ static int xr_as_written(abft_hip_ctx *ctx, const XrCall &c, abft_hip_vector *x,
                          const abft_hip_vector *p, const abft_hip_vector *w, double alpha, double *result) {
   auto &I = ctx->iter;
   const int at = rr_next_at(I);
-  const ReduceOut o = reduce_out(ctx, I.scal + 2 * at, true);
-  if (int rc = calc_xr_launch(ctx, x, r, p, w, alpha, o)) { I.have_rr = false; return rc; }
-  // level 1: the calc_p that will follow, behind calc_r and before the host waits for r.r
+  ReduceOut o = reduce_out(ctx, I.scal + 2 * at, true);
   const ScalTriple s = scal_triple(I);
-  const bool p_ahead = ahead_wants_p(*ctx, c, p) && ahead_p_launch(ctx, p, r->d, s.rr_new, s.rr);
+  bool p_ahead = false;
+  if (xr_can_defer_finish(*ctx, c, x, r, p, w) && xpend_buffer(ctx, p->n) >= 0) {
+    // level 1 with the calc_p known before calc_r goes out: calc_r leaves the finish of r.r to it.  (What
+    // calc_xr_launch does on its calc_r path, with the other launch; the vectors are plain_loop_vectors.)
+    o = deferred_out(o, ctx->partials_rr);
+    const uint32_t nb = (uint32_t)reduce_blocks(x->n);
+    forget_fused(*ctx);
+    {
+      KernelTimer t(ctx, ABFT_K_CALC_XR);
+      const hipError_t e = launch_calc_r_defer(r->d, w->d, alpha, nullptr, nullptr, nullptr, x->n, o.partials, ctx->stream,
+                                               nullptr, x->d, p->d, nullptr, 0u);
+      if (e != hipSuccess) { I.have_rr = false; return set_err(ABFT_ERR_HIP, "calc_xr: %s", hipGetErrorString(e)); }
+    }
+    arm_deferred(*ctx, x, p, alpha, false);
+    p_ahead = ahead_wants_p(*ctx, c, p) && ahead_p_launch(ctx, p, r->d, s.rr_new, s.rr, &o, nb);
+    if (!p_ahead) {
+      const hipError_t e = launch_deferred_finish(o, nb, ctx->stream);
+      if (e != hipSuccess) { I.have_rr = false; return set_err(ABFT_ERR_HIP, "calc_xr: %s", hipGetErrorString(e)); }
+    }
+  } else {
+    if (int rc = calc_xr_launch(ctx, x, r, p, w, alpha, o)) { I.have_rr = false; return rc; }
+    // level 1: the calc_p that will follow, behind calc_r and before the host waits for r.r
+    p_ahead = ahead_wants_p(*ctx, c, p) && ahead_p_launch(ctx, p, r->d, s.rr_new, s.rr);
+  }
   if (int rc = scalar_from_host_slot(ctx, o.seq, result)) { I.have_rr = false; return rc; }
   calc_xr_ran(*ctx, c, p_ahead, at, *result, x, r, p, w);
   return ABFT_OK;
@@ -2319,17 +2384,28 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
     hold->fix = fix;
     return ABFT_OK;
   }
+  // level 2 of the run-ahead: calc_r and calc_p go out behind the fold, and a multi-workgroup fold may leave its
+  // finish to that calc_r
+  const bool ahead = to_host && do_fuse && ahead_prepare(ctx, absorb_ok, vec, result);
+  const bool defer_pw = ahead && ctx->ahead.defer_finish && fuse_finalize_folds(nparts) && !fuse.peers.size;
+  ReduceOut pw_head{};
+  uint32_t pw_nb = 0;
   if (do_fuse) {
     KernelTimer t(ctx, ABFT_K_DOT);  // what is left of the dot: one block folding the partials
     ReduceOut big{};  // same outputs as the one-block fold, reached through the reduction protocol
     big.partials = ctx->partials; big.ticket = ctx->ticket; big.dev_out = fuse.dev_out; big.host = fuse.host;
     big.ev_count = fuse.ev_count; big.seq = fuse.seq; big.peers = fuse.peers;
-    HIPCHK(launch_fuse_finalize(fuse, nparts, big, fix.on ? &fix : nullptr, ctx->stream));
+    if (defer_pw) {
+      pw_head = deferred_out(big, ctx->partials_pw);
+      HIPCHK(launch_fuse_finalize_defer(fuse, nparts, pw_head.partials, fix.on ? &fix : nullptr, &pw_nb, ctx->stream));
+    } else {
+      HIPCHK(launch_fuse_finalize(fuse, nparts, big, fix.on ? &fix : nullptr, ctx->stream));
+    }
   }
   if (to_host && do_fuse) {
     fused_made(*ctx, vecc, vec, result, fuse.seq);
     if (whole && part == ABFT_PART_ALL && !vecc) (void)spec_launch(ctx, vec, result);
-    ahead_launch(ctx, absorb_ok, vec, result);
+    if (ahead) ahead_launch(ctx, defer_pw ? &pw_head : nullptr, pw_nb);
   }
   return ABFT_OK;
 }

@@ -222,10 +222,13 @@ struct CooDev {
 #define ABFT_CFG_Y_NT 0  // spmv_csr_kernel<MODE_NONE, ..., XUPD>: the y[row] store non-temporal (profiles/r12/variants_ab.md)
 #endif
 #ifndef ABFT_AHEAD_DEFAULT
-#define ABFT_AHEAD_DEFAULT 1  // run-ahead of the host-scalar loop (abft_hip.hip, spec.ahead) without ABFT_HIP_AHEAD: 0 off, 1 calc_p, 2 calc_r and calc_p -- 1: level 1 passed the rule against level 0 and the parent, level 2 did not pass it against level 1 (profiles/r12/variants_ab.md)
+#define ABFT_AHEAD_DEFAULT 1  // run-ahead of the host-scalar loop (abft_hip.hip, spec.ahead) without ABFT_HIP_AHEAD: 0 off, 1 calc_p, 2 calc_r and calc_p -- 1: level 1 passed the rule against level 0 and the parent, level 2 did not pass it against level 1 (profiles/r12/variants_ab.md), nor with the deferred finishes (profiles/r13/bench_ab.md)
+#endif
+#ifndef ABFT_DEFER_FINISH_DEFAULT
+#define ABFT_DEFER_FINISH_DEFAULT 1  // without ABFT_HIP_DEFER_FINISH: the reductions in front of a run-ahead kernel leave their finish to its head (loop_state.h, RunAhead::defer_finish) -- 1: at level 1 its slowest run lay above the parent's fastest (profiles/r13/bench_ab.md)
 #endif
 #ifndef ABFT_CFG_X_NT
-#define ABFT_CFG_X_NT 0  // calc_px: x (touched once per iteration) by non-temporal loads and stores
+#define ABFT_CFG_X_NT 0 // calc_px: x (touched once per iteration) by non-temporal loads and stores
 #endif
 #ifndef ABFT_CFG_COO_LEAN_WAVES
 #define ABFT_CFG_COO_LEAN_WAVES 8  // register budget of spmv_coo_lean_kernel, in waves per SIMD (8: 64 VGPRs)
@@ -445,6 +448,26 @@ hipError_t launch_calc_r(double *r, const double *w, double alpha, const double 
 hipError_t launch_calc_px(double *p, const double *r, double *x, double beta, const double *num, const double *den,
                           double alpha, const double *alpha_ptr, int n, hipStream_t s, double *p_out = nullptr,
                           double *x_out = nullptr);
+// ---- reductions finished by the launch behind them (kernels.hip, deferred_head) ----
+// The producer leaves its block partials and ends; every block of the consumer folds them at its head as the last
+// arriver of the ticket form would have (the same bits), and its block 0 publishes {sum, queued events} as `head`
+// says (partials: where the producer left them; dev_out, host, ev_count, seq as in the ticket form; no ticket, no peers).
+// Only for a pair enqueued back to back in one call; the partials' area is the reduction's until the consumer has ended.
+// launch_calc_r without its finish -> reduce_blocks(n) partials at block_partials.  head: it is also the consumer of
+// the deferred fold in front of it (head_nb chunk sums): alpha = *num / that p.w
+hipError_t launch_calc_r_defer(double *r, const double *w, double alpha, const double *num, const double *den,
+                               double *alpha_out, int n, double *block_partials, hipStream_t s, double *r_out,
+                               const double *x, const double *p, const ReduceOut *head, uint32_t head_nb);
+// launch_calc_p with beta = (the r.r of `head`, nb partials) / *den
+hipError_t launch_calc_p_head(const double *p, const double *r, const double *den, int n, hipStream_t s, double *p_out,
+                              const ReduceOut &head, uint32_t nb);
+// does launch_fuse_finalize take the multi-workgroup form (the one with a finish to defer) for nblk partials?
+bool fuse_finalize_folds(uint32_t nblk);
+// that form without its finish -> *nb_out chunk sums at chunk_sums
+hipError_t launch_fuse_finalize_defer(const FuseOut &f, uint32_t nblk, double *chunk_sums, const FixArgs *fix,
+                                      uint32_t *nb_out, hipStream_t s);
+// the head alone, in one block: behind a deferred producer whose consumer could not be launched
+hipError_t launch_deferred_finish(const ReduceOut &head, uint32_t nb, hipStream_t s);
 hipError_t launch_axpy(double *x, const double *p, double alpha, const double *alpha_ptr, int n, hipStream_t s);
 // the two halves of a guarded iteration (abft_hip_cg_iteration_until_dev): live when *rr > threshold -- then what
 // launch_calc_r (alpha = *rr / *pw, left in alpha_out) and launch_calc_px (beta = *rr_new / *rr) do --, else nothing

@@ -3374,6 +3374,29 @@ __device__ __forceinline__ uint32_t reduce_take_ticket(uint32_t *ticket) {
   return last;
 }
 
+// The fold of nb block partials by one whole block, in a fixed order: thread t adds partials t, t + 256, ... ascending,
+// then block_sum.  ONE body for the last arriver of reduce_finish and for the blocks of a consumer kernel that finish a
+// deferred reduction at their head (deferred_head): the same partials give the same bits wherever they are folded.
+// (AGENT: loads that pass the L1, for partials other blocks of this launch stored; a deferred reduction's partials
+// were stored by an earlier launch and are read plainly, so that the blocks of one CU share them in its L1)
+template <bool AGENT>
+__device__ __forceinline__ double fold_block_partials(const double *partials, uint32_t nb, double *s_w) {
+  double acc = 0.0;
+  for (uint32_t i = threadIdx.x; i < nb; i += ABFT_BLOCK)  // fixed order
+    acc += AGENT ? __hip_atomic_load(partials + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : partials[i];
+  return block_sum(acc, s_w);
+}
+
+// {value, queued events} into the pinned slot (one thread): write-through system-scope stores, drained, then the
+// sequence number: the host sees {value, evcount} before seq without a release fence (which would first write back
+// every dirty line calc_xr left in this XCD's L2)
+__device__ __forceinline__ void publish_host(HostSlot *host, double value, uint32_t nev, uint32_t seq) {
+  __hip_atomic_store(&host->value, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&host->evcount, nev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __hip_atomic_store(&host->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 __device__ __forceinline__ void reduce_finish(double block_value, const ReduceOut &o, double *s_w) {
   __shared__ uint32_t s_last;
   if (threadIdx.x == 0) {
@@ -3383,10 +3406,7 @@ __device__ __forceinline__ void reduce_finish(double block_value, const ReduceOu
   }
   __syncthreads();
   if (!s_last) return;
-  double acc = 0.0;
-  for (uint32_t i = threadIdx.x; i < gridDim.x; i += ABFT_BLOCK)  // fixed order
-    acc += __hip_atomic_load(o.partials + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  acc = block_sum(acc, s_w);
+  double acc = fold_block_partials<true>(o.partials, gridDim.x, s_w);
   uint32_t nev = 0u;
   double evs = 0.0;
   if (threadIdx.x == 0) {
@@ -3400,16 +3420,41 @@ __device__ __forceinline__ void reduce_finish(double block_value, const ReduceOu
       o.dev_out[1] = evs;
     }
     __hip_atomic_store(o.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
-    if (o.host) {
-      // write-through system-scope stores, drained, then the sequence number: the
-      // host sees {value, evcount} before seq without a release fence (which would
-      // first write back every dirty line calc_xr left in this XCD's L2)
-      __hip_atomic_store(&o.host->value, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(&o.host->evcount, nev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(&o.host->seq, o.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (o.host) publish_host(o.host, acc, nev, o.seq);
   }
+}
+
+// ---- a reduction finished by the kernel behind it ----
+// When the kernel that consumes a reduction's result is enqueued in the same call, the producer needs no last
+// arriver: its blocks leave their partials with plain stores and end (no drain, no ticket), and EVERY block of the
+// consumer folds them at its head, by fold_block_partials as the last arriver would have -- the same bits in every
+// block.  Block 0 of the consumer publishes what reduce_finish publishes: {sum, queued events} to o.dev_out and to the
+// pinned slot.  The kernel boundary is the hand-off: o.partials belongs to this reduction until the consumer has ended
+// (abft_hip.hip keeps one area per deferred reduction).  No peers: the single-process loop only.
+// (o: the producer's ReduceOut; ticket unused.  s_h: four doubles of LDS that nothing else in the kernel uses)
+__device__ __forceinline__ double deferred_head(const ReduceOut &o, uint32_t nb, double *s_h) {
+  const double acc = fold_block_partials<false>(o.partials, nb, s_h);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const uint32_t nev = __hip_atomic_load(o.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (o.dev_out) {
+      o.dev_out[0] = acc;
+      o.dev_out[1] = (double)nev;
+    }
+    if (o.host) publish_host(o.host, acc, nev, o.seq);
+  }
+  return acc;
+}
+
+// the head alone, in one block: behind a deferred producer whose consumer could not be launched, so that the host
+// never waits on a slot nobody writes
+__global__ __launch_bounds__(ABFT_BLOCK) void deferred_finish_kernel(ReduceOut o, uint32_t nb) {
+  __shared__ double s_h[4];
+  (void)deferred_head(o, nb, s_h);
+}
+
+hipError_t launch_deferred_finish(const ReduceOut &o, uint32_t nb, hipStream_t s) {
+  hipLaunchKernelGGL(deferred_finish_kernel, dim3(1), dim3(ABFT_BLOCK), 0, s, o, nb);
+  return hipGetLastError();
 }
 
 // Fold of many fused-dot partials (config 2: 48 806 of them, 390 KB) by several
@@ -3454,17 +3499,46 @@ __global__ __launch_bounds__(ABFT_BLOCK) void fold_partials_kernel(const double 
   reduce_finish(acc, out, s_w);
 }
 
+// fold_partials_kernel with its finish left to the kernel behind it (deferred_head): the chunk sums, and no more
+__global__ __launch_bounds__(ABFT_BLOCK) void fold_partials_defer_kernel(const double *__restrict__ parts, uint32_t n,
+                                                                         uint32_t chunk, double *chunk_sums,
+                                                                         FixArgs fx) {
+  __shared__ double s_w[4];
+  if (fx.on && blockIdx.x == 0) coo_fixup_body(fx);
+  const uint32_t lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
+  double acc = fold_chunk_sum(parts, lo, hi);
+  acc = block_sum(acc, s_w);
+  if (threadIdx.x == 0) chunk_sums[blockIdx.x] = acc;
+}
+
+bool fuse_finalize_folds(uint32_t nblk) { return nblk > 8192u; }
+
 hipError_t launch_fuse_finalize(const FuseOut &f, uint32_t nblk, const ReduceOut &big, const FixArgs *fix,
                                 hipStream_t s) {
   FixArgs fx{};
   if (fix) fx = *fix;
-  if (nblk <= 8192u || !big.partials) {
+  if (!fuse_finalize_folds(nblk) || !big.partials) {
     hipLaunchKernelGGL(fuse_finalize_kernel, dim3(1), dim3(1024), 0, s, f, nblk, fx);
     return hipGetLastError();
   }
   uint32_t chunk;
   const uint32_t nb = fold_grid(nblk, &chunk);
+#ifdef ABFT_DBG_DEFER_ALWAYS  // timing build: every multi-workgroup fold without its tail, a one-block finisher behind it
+  hipLaunchKernelGGL(fold_partials_defer_kernel, dim3(nb), dim3(ABFT_BLOCK), 0, s, f.partials, nblk, chunk, big.partials, fx);
+  return launch_deferred_finish(big, nb, s);
+#endif
   hipLaunchKernelGGL(fold_partials_kernel, dim3(nb), dim3(ABFT_BLOCK), 0, s, f.partials, nblk, chunk, big, fx);
+  return hipGetLastError();
+}
+
+hipError_t launch_fuse_finalize_defer(const FuseOut &f, uint32_t nblk, double *chunk_sums, const FixArgs *fix,
+                                      uint32_t *nb_out, hipStream_t s) {
+  FixArgs fx{};
+  if (fix) fx = *fix;
+  uint32_t chunk;
+  const uint32_t nb = fold_grid(nblk, &chunk);
+  *nb_out = nb;
+  hipLaunchKernelGGL(fold_partials_defer_kernel, dim3(nb), dim3(ABFT_BLOCK), 0, s, f.partials, nblk, chunk, chunk_sums, fx);
   return hipGetLastError();
 }
 
@@ -3529,16 +3603,18 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_xr_kernel(double *__restrict_
 // calc_p (reference CSR/CPUContext.cpp:107-113): p = r + beta p
 // (p_out: where the new p goes -- p itself, or the buffer p's handle is about to swap to while the old p waits
 // for the SpMV that applies x += alpha p_old, abft_hip.hip "xpend")
-template <int VEC>
-__global__ __launch_bounds__(ABFT_BLOCK) void calc_p_kernel(const double *p, const double *__restrict__ r,
-                                                            double beta, const double *num, const double *den,
-                                                            int n, double *p_out) {
-  if (num) beta = *num / *den;  // beta = rr_new / rr formed on the device (cg.cpp:109)
+// The walk of calc_p_kernel and calc_p_head_kernel: p_out = r + beta p over the grid.
+// (PRE: this thread's first pair of p and r was loaded by the caller -- before it knew beta -- into p0, r0)
+template <int VEC, bool PRE>
+__device__ __forceinline__ void calc_p_walk(const double *p, const double *__restrict__ r, double beta, int n,
+                                            double *p_out, double2 p0, double2 r0) {
   const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
-  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
+  const long start = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
+  for (long i = start; i < n; i += stride) {
     if (VEC == 2 && i + 1 < n) {
-      double2 pv = *reinterpret_cast<const double2 *>(p + i);
-      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const bool pre = PRE && i == start;
+      double2 pv = pre ? p0 : *reinterpret_cast<const double2 *>(p + i);
+      const double2 rv = pre ? r0 : *reinterpret_cast<const double2 *>(r + i);
       pv.x = rv.x + beta * pv.x;
       pv.y = rv.y + beta * pv.y;
 #if ABFT_CFG_P_OUT_NT
@@ -3552,6 +3628,33 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_p_kernel(const double *p, con
       p_out[i] = r[i] + beta * p[i];
     }
   }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_p_kernel(const double *p, const double *__restrict__ r,
+                                                            double beta, const double *num, const double *den,
+                                                            int n, double *p_out) {
+  if (num) beta = *num / *den;  // beta = rr_new / rr formed on the device (cg.cpp:109)
+  calc_p_walk<VEC, false>(p, r, beta, n, p_out, double2{}, double2{});
+}
+
+// calc_p behind a calc_r that left its r.r to this kernel (deferred_head): every block folds the nb block partials
+// behind its first loads of p and r, beta = r.r_new / *den -- the division calc_p_kernel does with *num --, block 0
+// publishes {r.r_new, queued events}; then calc_p_kernel's walk.
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_p_head_kernel(const double *p, const double *__restrict__ r,
+                                                                 const double *den, int n, double *p_out,
+                                                                 ReduceOut head, uint32_t nb) {
+  __shared__ double s_h[4];
+  const long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
+  double2 pv = make_double2(0.0, 0.0), rv = pv;
+  if (VEC == 2 && i + 1 < n) {
+    pv = *reinterpret_cast<const double2 *>(p + i);
+    rv = *reinterpret_cast<const double2 *>(r + i);
+  }
+  const double rr = *den;
+  const double beta = deferred_head(head, nb, s_h) / rr;
+  calc_p_walk<VEC, true>(p, r, beta, n, p_out, pv, rv);
 }
 
 static inline bool aligned16(const void *a, const void *b = nullptr, const void *c = nullptr,
@@ -3587,6 +3690,17 @@ hipError_t launch_calc_p(double *p, const double *r, double beta, const double *
     hipLaunchKernelGGL(calc_p_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, num, den, n, p_out);
   else
     hipLaunchKernelGGL(calc_p_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, num, den, n, p_out);
+  return hipGetLastError();
+}
+
+// (head, nb: the ReduceOut and the grid of the calc_r whose r.r this launch finishes, launch_calc_r_defer)
+hipError_t launch_calc_p_head(const double *p, const double *r, const double *den, int n, hipStream_t s, double *p_out,
+                              const ReduceOut &head, uint32_t nb) {
+  const int g = reduce_blocks(n);
+  if (aligned16(p, r, p_out))
+    hipLaunchKernelGGL(calc_p_head_kernel<2>, dim3(g), dim3(ABFT_BLOCK), 0, s, p, r, den, n, p_out, head, nb);
+  else
+    hipLaunchKernelGGL(calc_p_head_kernel<1>, dim3(g), dim3(ABFT_BLOCK), 0, s, p, r, den, n, p_out, head, nb);
   return hipGetLastError();
 }
 
@@ -3645,6 +3759,29 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_kernel(const double *r, con
   double acc = calc_r_walk<VEC>(r, w, alpha, n, r_out);
   acc = block_sum(acc, s_w);
   reduce_finish(acc, out, s_w);
+}
+
+// calc_r_kernel with its finish left to the kernel behind it (calc_p_head_kernel, or deferred_finish_kernel): the
+// same walk and block_sum, the block's partial stored plainly, and the kernel ends.
+// HEAD: it also finishes the deferred fold of the fused p.w in front of it (fold_partials_defer_kernel):
+// alpha = *num / p.w, the division calc_r_kernel does with *den; block 0 publishes {p.w, queued events}.
+template <int VEC, bool HEAD>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_defer_kernel(const double *r, const double *__restrict__ w,
+                                                                  double alpha, const double *num, const double *den,
+                                                                  double *alpha_out, int n, double *block_partials,
+                                                                  double *r_out, ReduceOut head, uint32_t nb) {
+  __shared__ double s_w[4];
+  if (HEAD) {
+    __shared__ double s_h[4];
+    const double rr = *num;
+    alpha = rr / deferred_head(head, nb, s_h);
+  } else if (num) {
+    alpha = *num / *den;
+  }
+  if (alpha_out && blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;
+  double acc = calc_r_walk<VEC>(r, w, alpha, n, r_out);
+  acc = block_sum(acc, s_w);
+  if (threadIdx.x == 0) block_partials[blockIdx.x] = acc;
 }
 
 // The walk of calc_px_kernel and calc_px_until_kernel: x_out = x + alpha p, p_out = r + beta p, p read once.
@@ -3737,10 +3874,39 @@ hipError_t launch_calc_r(double *r, const double *w, double alpha, const double 
                          const double *p) {
   const int nb = reduce_blocks(n);
   if (!r_out) r_out = r;
+#ifdef ABFT_DBG_DEFER_ALWAYS  // timing build: every calc_r without its tail, a one-block finisher behind it
+  if (!out.peers.size) {
+    if (hipError_t e = launch_calc_r_defer(r, w, alpha, num, den, alpha_out, n, out.partials, s, r_out, x, p, nullptr, 0u))
+      return e;
+    return launch_deferred_finish(out, (uint32_t)nb, s);
+  }
+#endif
   if (aligned16(r, w, r_out) && aligned16(x, p))
     hipLaunchKernelGGL(calc_r_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, alpha, num, den, alpha_out, n, out, r_out);
   else
     hipLaunchKernelGGL(calc_r_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, alpha, num, den, alpha_out, n, out, r_out);
+  return hipGetLastError();
+}
+
+// launch_calc_r with the finish of r.r left to the launch behind it: the block partials go to block_partials
+// (reduce_blocks(n) of them), which launch_calc_p_head or launch_deferred_finish folds.
+// head != nullptr: it finishes the deferred fold in front of it (launch_fuse_finalize_defer: head_nb chunk sums at
+// head->partials) and divides *num by that p.w; den is not read.
+hipError_t launch_calc_r_defer(double *r, const double *w, double alpha, const double *num, const double *den,
+                               double *alpha_out, int n, double *block_partials, hipStream_t s, double *r_out,
+                               const double *x, const double *p, const ReduceOut *head, uint32_t head_nb) {
+  const int nb = reduce_blocks(n);
+  if (!r_out) r_out = r;
+  const bool vec2 = aligned16(r, w, r_out) && aligned16(x, p);
+  const dim3 g(nb), b(ABFT_BLOCK);
+  if (head) {
+    if (vec2) hipLaunchKernelGGL((calc_r_defer_kernel<2, true>), g, b, 0, s, r, w, alpha, num, den, alpha_out, n, block_partials, r_out, *head, head_nb);
+    else hipLaunchKernelGGL((calc_r_defer_kernel<1, true>), g, b, 0, s, r, w, alpha, num, den, alpha_out, n, block_partials, r_out, *head, head_nb);
+  } else {
+    const ReduceOut none{};
+    if (vec2) hipLaunchKernelGGL((calc_r_defer_kernel<2, false>), g, b, 0, s, r, w, alpha, num, den, alpha_out, n, block_partials, r_out, none, 0u);
+    else hipLaunchKernelGGL((calc_r_defer_kernel<1, false>), g, b, 0, s, r, w, alpha, num, den, alpha_out, n, block_partials, r_out, none, 0u);
+  }
   return hipGetLastError();
 }
 

@@ -138,6 +138,11 @@ struct RunAhead {
   bool alpha_ok = false;  // the calc_xr just run was handed rr / p.w on plain vectors (cleared by any entry point but calc_p)
   int slot = 0;           // xpend.shadow[slot]: where the calc_p in flight writes
   long commit_p = 0, commit_r = 0, drops = 0;
+  // ABFT_HIP_DEFER_FINISH: a reduction whose consumer kernel is launched behind it in the same call -- calc_r before
+  // the calc_p run ahead, at level 2 also the fused p.w's fold before calc_r -- leaves its finish (the fold of the
+  // block partials, the published scalar) to the head of that consumer.  The same launches carrying the same bits:
+  // no state of its own, nothing to commit or drop.  Off wherever the run-ahead is (loop_settle_switches).
+  bool defer_finish = false;
 };
 
 // what has been launched ahead of the call that will ask for it
@@ -171,6 +176,7 @@ struct LoopState {
 static inline void loop_settle_switches(LoopState &L) {
   L.xin_enabled = L.xin_enabled && L.defer_enabled && L.fuse_enabled && !L.spec.enabled;
   if (!L.xin_enabled) L.ahead.level = 0;
+  if (L.ahead.level == 0) L.ahead.defer_finish = false;
 }
 static inline bool loop_invariant(const LoopState &L) {
   return (!L.spec.enabled || !L.xin_enabled) && (L.xin_enabled || L.ahead.level == 0);
@@ -467,6 +473,14 @@ static inline void commit_spec_r(LoopState &L, abft_hip_vector *r, double rr_new
 static inline bool ahead_wants_p(LoopState &L, const XrCall &c, const abft_hip_vector *p) {
   if (!c.alpha_ok) L.ahead.armed = false;
   return c.alpha_ok && L.ahead.armed && L.defer.active && !L.defer.on_dev && L.defer.p == p->d && pending_can_run_ahead(L);
+}
+// The same question asked BEFORE the launch, without the side effect: will ahead_wants_p say yes once this calc_xr has
+// gone out?  (can_defer_x: the launch then is calc_r and leaves x += alpha p deferred on this p, with alpha on the
+// host.)  Then calc_r may leave the finish of r.r to that calc_p -- the shadow for the new p permitting, which the
+// caller secures before it launches either.
+static inline bool xr_can_defer_finish(const LoopState &L, const XrCall &c, const abft_hip_vector *x,
+                                       const abft_hip_vector *r, const abft_hip_vector *p, const abft_hip_vector *w) {
+  return L.ahead.defer_finish && c.alpha_ok && L.ahead.armed && can_defer_x(L, x, r, p, w) && pending_can_run_ahead(L);
 }
 // ... and what it leaves behind once its r.r (slot `at` of scal) has been handed back: what the run-ahead and a
 // speculation need to know about this iteration

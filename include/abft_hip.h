@@ -648,6 +648,11 @@ int abft_hip_x_in_spmv_stats(abft_hip_ctx *ctx, long *absorbed, long *flushed);
  * whose alpha and beta were the two quotients; a drop, or an iteration with other scalars, disarms until the next such
  * iteration.  Only where the x-in-SpMV path is armed (above), and off with ABFT_HIP_SPECULATE=1.
  * Default: level 1 (the level that was measured to pay; level 2 did not beat it: DESIGN.md section 4); ABFT_HIP_AHEAD=0 turns it off.
+ * ABFT_HIP_DEFER_FINISH=0|1 (read when the context is created; default 1; no effect where the run-ahead is off): a
+ * reduction whose consumer kernel is launched behind it in the same call -- the r -= alpha w in front of the level-1
+ * kernel, at level 2 also the multi-workgroup fold of p.w in front of that -- ends with its block partials, and every
+ * workgroup of the consumer folds them at its head, in the order the reduction's own last workgroup would have; its
+ * first workgroup publishes the scalar.  The same bits, the same counters, one serial tail less per hand-off.
  * *committed_p / *committed_r = calls of abft_hip_calc_p / abft_hip_calc_xr that took over a kernel run ahead,
  * *dropped = run-aheads thrown away, since the context was created (host counters; any pointer may be null). */
 int abft_hip_ahead_stats(abft_hip_ctx *ctx, long *committed_p, long *committed_r, long *dropped);
