@@ -123,6 +123,7 @@ SIGNATURES = {
     "abft_hip_cg_iteration_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "abft_hip_tail_stats": (C.c_int, [vp, i32p, i32p, i32p, C.POINTER(C.c_long)]),
     "abft_hip_x_in_spmv_stats": (C.c_int, [vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "abft_hip_lazy_x_stats": (C.c_int, [vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "abft_hip_ahead_stats": (C.c_int, [vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "abft_hip_cg_iteration_until_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double]),
     "abft_hip_pcg_iteration_until_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,

@@ -549,6 +549,14 @@ class HIPContext:
         check(self.L.abft_hip_x_in_spmv_stats(self.h, C.byref(absorbed), C.byref(flushed)))
         return absorbed.value, flushed.value
 
+    def lazy_x_stats(self):
+        """the queue of x updates (ABFT_HIP_LAZY_X) -> (bursts, applied_in_bursts, applied_by_flush): SpMV launches that
+        applied a full queue, the updates they applied, and queued updates applied on their own because something other
+        than the loop's next call came first (abft_hip_lazy_x_stats, include/abft_hip.h)"""
+        b, a, f = C.c_long(0), C.c_long(0), C.c_long(0)
+        check(self.L.abft_hip_lazy_x_stats(self.h, C.byref(b), C.byref(a), C.byref(f)))
+        return b.value, a.value, f.value
+
     def ahead_stats(self):
         """kernels of the host-scalar loop run ahead of the scalars -> (committed_p, committed_r, dropped): calc_p / calc_xr
         calls that took one over, and run-aheads thrown away (abft_hip_ahead_stats, include/abft_hip.h)"""

@@ -62,6 +62,7 @@ struct abft_hip_ctx : LoopState {
     xin_modes = ABFT_X_IN_SPMV_MODES;
     ahead.level = ABFT_AHEAD_DEFAULT;
     ahead.defer_finish = ABFT_DEFER_FINISH_DEFAULT != 0;
+    lazy.depth = ABFT_LAZY_X_DEFAULT;
   }
   int device = 0;
   int num_cus = 256;
@@ -178,8 +179,27 @@ static constexpr size_t VECC_SEEN_BYTES = ABFT_VECC_SEEN_SLOTS * sizeof(unsigned
 static_assert(sizeof(abft_event) % sizeof(unsigned long long) == 0, "the table behind the events is 8-byte aligned");
 static constexpr uint32_t MOVED_CAP = 4096;
 
+static XUpd xupd_of(const LazyBatch &b) {
+  XUpd u{};
+  u.xs = b.x;
+  u.n = b.count;
+  for (int k = 0; k < b.count; k++) { u.u[k].p_old = b.e[k].p_old; u.u[k].alpha = b.e[k].alpha; }
+  return u;
+}
+
+// the queued x updates on their own, in arrival order, in one launch: something other than the four continuations
+// that keep the queue came (loop_state.h, LazyUpdates).  Always before a younger update is applied to the same x.
+static int flush_lazy(abft_hip_ctx *ctx) {
+  LazyBatch b;
+  if (!lazy_flush_due(*ctx, b)) return ABFT_OK;
+  HIPCHK(launch_axpy_chain(xupd_of(b), b.n, ctx->stream));
+  return ABFT_OK;
+}
+
 // the pending x += alpha p_old on its own: something other than the predicted SpMV came first
 static int flush_xpend(abft_hip_ctx *ctx) {
+  if (!ctx->xpend.active) return ABFT_OK;
+  if (int rc = flush_lazy(ctx)) return rc;
   if (!pending_flush_due(*ctx)) return ABFT_OK;
   const auto &X = ctx->xpend;
   HIPCHK(launch_axpy(X.x, X.p_old, X.alpha, nullptr, X.n, ctx->stream));
@@ -187,6 +207,8 @@ static int flush_xpend(abft_hip_ctx *ctx) {
 }
 
 static int flush_deferred(abft_hip_ctx *ctx) {
+  if (!ctx->defer.active) return ABFT_OK;
+  if (int rc = flush_lazy(ctx)) return rc;
   if (!deferred_flush_due(*ctx)) return ABFT_OK;
   const auto &D = ctx->defer;
   HIPCHK(launch_axpy(D.x, D.p, D.alpha, D.on_dev ? ctx->alpha_dev : nullptr, D.n, ctx->stream));
@@ -196,7 +218,8 @@ static int flush_deferred(abft_hip_ctx *ctx) {
 // Every entry point starts here.  Unless the caller is the calc_p that can absorb it (KEEP_DEFERRED) or the SpMV that
 // can (KEEP_PENDING), a pending x += alpha p is enqueued first, so no call ever sees x or p in any state the unfused
 // sequence would not have produced; unless it is one of the calls what is in flight waits for (KEEP_FLIGHT), that is
-// dropped.  The flags are loop_state.h's; which entry passes which:
+// dropped; unless it is one of the four continuations that keep them (KEEP_LAZY), the queued x updates are applied
+// before either.  The flags are loop_state.h's; which entry passes which:
 //
 //   0 (drop, apply both updates)   set_stream, synchronize, synchronize_timeout, matrix_create_* (matrix_create),
 //                                  matrix_compact_stats, matrix_packed_stats, matrix_destroy, matrix_read_csr, _read_coo,
@@ -216,10 +239,13 @@ static int flush_deferred(abft_hip_ctx *ctx) {
 //                                  peer_exchange_attach, _device_alloc, _device_free, _attach_device, _ipc_export,
 //                                  _ipc_attach, _finish
 //   KEEP_DEFERRED | OTHER_VECTORS  calc_p_precond
-//   KEEP_FLIGHT                    dot, calc_xr
+//   KEEP_FLIGHT | KEEP_LAZY        dot, calc_xr
 //   KEEP_FLIGHT | KEEP_DEFERRED    calc_p
-//   KEEP_PENDING                   every SpMV (spmv_common): spmv, spmv_dot_dev, spmv_vecc, spmv_part,
+//    | KEEP_LAZY
+//   KEEP_PENDING | KEEP_LAZY       every SpMV (spmv_common): spmv, spmv_dot_dev, spmv_vecc, spmv_part,
 //                                  spmv_dot_part_dev, spmv_dot_range_dev, cg_iteration_dev
+//   (KEEP_LAZY: the entry applies the queue itself unless it is the eligible spmv(A, p, w), the dot served from the
+//    fused product, the calc_xr that defers onto the queue's x, or the calc_p that takes that update along)
 //   no prologue                    init, shutdown, the getters and counters, vector_view, matrix_set_interior,
 //                                  matrix_info, matrix_panels, graph_end, graph_destroy, the detach and *_failed calls
 //
@@ -231,6 +257,8 @@ static int enter(abft_hip_ctx *ctx, unsigned keep) {
   if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");
   HIPCHK(hipSetDevice(ctx->device));
   prologue_begin(*ctx, keep);
+  if (prologue_flushes_lazy(keep))
+    if (int rc = flush_lazy(ctx)) return rc;
   if (prologue_flushes_pending(keep))
     if (int rc = flush_xpend(ctx)) return rc;
   if (prologue_flushes_deferred(keep))
@@ -397,6 +425,7 @@ extern "C" int abft_hip_init(int device, abft_hip_ctx **out) {
   }
   if (const char *e = getenv("ABFT_HIP_AHEAD")) ctx->ahead.level = e[0] == '2' ? 2 : e[0] == '1' ? 1 : 0;
   if (const char *e = getenv("ABFT_HIP_DEFER_FINISH")) ctx->ahead.defer_finish = strcmp(e, "0") != 0;
+  if (const char *e = getenv("ABFT_HIP_LAZY_X")) ctx->lazy.depth = e[0] == '4' ? 4 : e[0] == '2' ? 2 : 1;
   loop_settle_switches(*ctx);  // (speculation on: no x-in-SpMV; no x-in-SpMV: no run-ahead)
   HIPCHK(hipHostGetDevicePointer((void **)&ctx->host_slot_dev, ctx->host_slot, 0));
   // the queue, and behind it the table of vector events already queued (abft_internal.h)
@@ -432,6 +461,7 @@ extern "C" int abft_hip_init(int device, abft_hip_ctx **out) {
 extern "C" int abft_hip_shutdown(abft_hip_ctx *ctx) {
   if (!ctx) return ABFT_OK;
   (void)hipSetDevice(ctx->device);
+  (void)flush_lazy(ctx);
   (void)flush_xpend(ctx);
   (void)flush_deferred(ctx);
   (void)hipStreamSynchronize(ctx->stream);
@@ -462,6 +492,7 @@ extern "C" int abft_hip_shutdown(abft_hip_ctx *ctx) {
   (void)hipFree(ctx->iter.r_shadow.buf);
   (void)hipFree(ctx->spec.p_shadow.buf);
   for (auto &b : ctx->xpend.shadow) (void)hipFree(b.buf);
+  for (int k = 0; k < ctx->lazy.nspare; k++) (void)hipFree(ctx->lazy.spare[k]);
   (void)hipFree(ctx->iter.scal);
   if (!debug_leak('h')) (void)hipHostFree(ctx->host_slot);
   (void)hipFree(ctx->ring.buf);
@@ -1397,9 +1428,9 @@ static int fused_value(abft_hip_ctx *ctx) {
 }
 
 extern "C" int abft_hip_dot(abft_hip_ctx *ctx, const abft_hip_vector *a, const abft_hip_vector *b, double *result) {
-  if (int rc = enter(ctx, KEEP_FLIGHT)) return rc;  // (a dot served from the fused product leaves what is in flight alone)
-  if (int rc = check_same(a, b, "dot")) { drop_in_flight(*ctx); return rc; }
-  if (!result) { drop_in_flight(*ctx); return set_err(ABFT_ERR_INVALID, "null result"); }
+  if (int rc = enter(ctx, KEEP_FLIGHT | KEEP_LAZY)) return rc;  // (a dot served from the fused product leaves what is in flight and the queued x updates alone)
+  if (int rc = check_same(a, b, "dot")) { drop_in_flight(*ctx); (void)flush_lazy(ctx); return rc; }
+  if (!result) { drop_in_flight(*ctx); (void)flush_lazy(ctx); return set_err(ABFT_ERR_INVALID, "null result"); }
   // dot(p, w) right after spmv(A, p, w): the SpMV already formed it
   if (fused_serves_dot(*ctx, a, b, false)) {
     if (int rc = fused_value(ctx)) return rc;
@@ -1407,6 +1438,7 @@ extern "C" int abft_hip_dot(abft_hip_ctx *ctx, const abft_hip_vector *a, const a
     return ABFT_OK;
   }
   drop_in_flight(*ctx);
+  if (int rc = flush_lazy(ctx)) return rc;
   fused_slot_reused(*ctx);
   // (the result also stays on the device: if this is the r.r a CG loop starts from, a speculated alpha divides it)
   auto &I = ctx->iter;
@@ -1480,6 +1512,28 @@ static int xpend_buffer(abft_hip_ctx *ctx, int n) {
   return at;
 }
 
+// The spares of the queue of x updates for the pending update's length, asked with the queue empty: depth - 1 buffers.
+// No room for them: the largest depth that fits, for good (down to 1: today's single buffer, no queue).  Switching
+// length frees and allocates (both synchronise the device), as a third length does for xpend's buffers.
+static void lazy_ring_ensure(abft_hip_ctx *ctx) {
+  auto &Z = ctx->lazy;
+  if (lazy_ring_ready(*ctx)) return;
+  const int n = ctx->xpend.n;
+  for (int k = 0; k < Z.nspare; k++) (void)hipFree(Z.spare[k]);
+  Z.nspare = 0;
+  Z.spare_n = n;
+  while (Z.nspare < Z.depth - 1) {
+    double *buf = nullptr;
+    if (hipMalloc((void **)&buf, ((size_t)n + 2) * sizeof(double)) == hipSuccess) {
+      Z.spare[Z.nspare++] = buf;
+      continue;
+    }
+    (void)hipGetLastError();
+    Z.depth = Z.nspare >= 1 ? 2 : 1;  // 4 -> 2 with one spare in hand, else 1
+    while (Z.nspare > Z.depth - 1) (void)hipFree(Z.spare[--Z.nspare]);
+  }
+}
+
 // The new p into the context's buffer, the buffers swapped, the deferred x += alpha p left pending on the old one
 // (see PendingUpdate).  False: not now -- the caller runs calc_px as before.
 static bool xpend_take(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, double beta, int *rc) {
@@ -1513,8 +1567,9 @@ static int calc_p_launch(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_v
         const bool taken = xpend_take(ctx, p, r, beta, &rc);
         if (rc) return rc;
         ctx->xpend.last_p = p;  // an SpMV of this p as the very next call arms (or keeps) the prediction
-        if (taken) return ABFT_OK;
+        if (taken) return ABFT_OK;  // (and keeps the queued x updates: this one is pending behind them)
       }
+      if (int rc = flush_lazy(ctx)) return rc;  // x is updated in place: the queued updates first
       KernelTimer t(ctx, ABFT_K_CALC_P);
       HIPCHK(launch_calc_px(p->d, r->d, ctx->defer.x, beta, num, den, ctx->defer.alpha,
                             ctx->defer.on_dev ? ctx->alpha_dev : nullptr, p->n, ctx->stream));
@@ -1522,6 +1577,7 @@ static int calc_p_launch(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_v
     }
     if (int rc = flush_deferred(ctx)) return rc;
   }
+  if (int rc = flush_lazy(ctx)) return rc;  // (a calc_p that takes no update along is not one of the loop's)
   KernelTimer t(ctx, ABFT_K_CALC_P);
   HIPCHK(launch_calc_p(p->d, r->d, beta, num, den, p->n, ctx->stream));
   return ABFT_OK;
@@ -1683,7 +1739,9 @@ static int xr_as_written(abft_hip_ctx *ctx, const XrCall &c, abft_hip_vector *x,
 
 extern "C" int abft_hip_calc_xr(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *r, const abft_hip_vector *p,
                                 const abft_hip_vector *w, double alpha, double *result) {
-  if (int rc = enter(ctx, KEEP_FLIGHT)) return rc;
+  if (int rc = enter(ctx, KEEP_FLIGHT | KEEP_LAZY)) return rc;
+  if (!result || !lazy_kept_by_calc_xr(*ctx, x, r, p, w))  // (kept: this call defers its update onto the queue's x)
+    if (int rc = flush_lazy(ctx)) return rc;
   if (!result) { drop_in_flight(*ctx); return set_err(ABFT_ERR_INVALID, "null result"); }
   const XrCall c = classify_calc_xr(*ctx, x, r, p, w, alpha);
   if (c.outcome == XrOutcome::CommitAhead) return xr_commit_ahead(ctx, c, x, r, p, alpha, result);
@@ -1704,7 +1762,7 @@ extern "C" int abft_hip_calc_xr_dev(abft_hip_ctx *ctx, abft_hip_vector *x, abft_
 }
 
 extern "C" int abft_hip_calc_p(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, double beta) {
-  if (int rc = enter(ctx, KEEP_FLIGHT | KEEP_DEFERRED)) return rc;
+  if (int rc = enter(ctx, KEEP_FLIGHT | KEEP_DEFERRED | KEEP_LAZY)) return rc;  // (the queue: kept by a commit, else calc_p_launch decides)
   const PCall c = classify_calc_p(*ctx, p, r, beta);
   if (c.outcome == POutcome::CommitAhead) { commit_ahead_p(*ctx, p); return ABFT_OK; }
   if (c.outcome == POutcome::CommitSpec) { commit_spec_p(*ctx, p); return ABFT_OK; }
@@ -2274,12 +2332,14 @@ static bool spmv_can_absorb(const abft_hip_ctx *ctx, const abft_hip_matrix *mat,
 static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
                        abft_hip_vector *result, int vec_offset, double *dev_pair, int part = ABFT_PART_ALL,
                        int c0 = 0, int c1 = -1, HeldFold *hold = nullptr, bool vecc = false) {
-  if (int rc = enter(ctx, KEEP_PENDING)) return rc;
+  if (int rc = enter(ctx, KEEP_PENDING | KEEP_LAZY)) return rc;
   // the update pending on the old p (PendingUpdate): this launch applies it, or it is applied first
   const bool absorb_ok = spmv_can_absorb(ctx, mat, vec, result, dev_pair, part, c1, hold != nullptr, vecc);  // (then a run-ahead may follow it)
   const bool absorb = pending_absorbed_by(*ctx, absorb_ok, vec, result);
-  if (!absorb)
+  if (!absorb) {  // any other SpMV: the queued x updates first, then the pending one
+    if (int rc = flush_lazy(ctx)) return rc;
     if (int rc = flush_xpend(ctx)) return rc;
+  }
   if (!mat || !vec || !result) return set_err(ABFT_ERR_INVALID, "spmv: null argument");
   if (vecc) {  // protected vectors: the streaming CSR kernel only; the iteration they are part of is not speculated
     forget_iteration(*ctx);
@@ -2362,10 +2422,24 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
         HIPCHK(launch_spmv_coo_panels(mat->mode, mat->coo, mat->panels, vec->d, result->d, ctx->ring,
                                       do_fuse ? &fuse : nullptr, mat->panel_grid, mat->panel_chunk, ctx->stream));
     } else if (mat->fmt == ABFT_FMT_CSR) {
-      const XUpd xu{ctx->xpend.x, ctx->xpend.p_old, ctx->xpend.alpha};
+      // the update pending on the old p: this launch applies it (depth 1), queues it and applies nothing, or applies
+      // the whole queue and it (loop_state.h, LazyUpdates)
+      XUpd xu{};
+      if (absorb) {
+        if (lazy_queue_mismatch(*ctx))
+          if (int rc = flush_lazy(ctx)) return rc;
+        lazy_ring_ensure(ctx);
+        switch (lazy_step(*ctx)) {
+          case LazyStep::ApplyOne:
+            xu.xs = ctx->xpend.x; xu.u[0].p_old = ctx->xpend.p_old; xu.u[0].alpha = ctx->xpend.alpha; xu.n = 1;
+            pending_absorbed(*ctx);  // (applied exactly once, whatever the launch reports about the matrix)
+            break;
+          case LazyStep::Queue: lazy_queue_pending(*ctx); break;
+          case LazyStep::Burst: xu = xupd_of(lazy_burst(*ctx)); break;
+        }
+      }
       HIPCHK(launch_spmv_csr(mat->mode, mat->csr, mat->compact, mat->packed, span, vec->d, result->d, ctx->ring,
-                             do_fuse ? &fuse : nullptr, ctx->stream, vecc, absorb ? &xu : nullptr));
-      if (absorb) pending_absorbed(*ctx);
+                             do_fuse ? &fuse : nullptr, ctx->stream, vecc, xu.n ? &xu : nullptr));
     } else
       HIPCHK(launch_spmv_coo(mat->mode, mat->coo, vec->d, result->d, ctx->ring, do_fuse ? &fuse : nullptr, ctx->stream));
     // COO: products whose stored column was silently corrupted go where the reference puts them --
@@ -3499,6 +3573,14 @@ extern "C" int abft_hip_x_in_spmv_stats(abft_hip_ctx *ctx, long *absorbed, long 
   if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");
   if (absorbed) *absorbed = ctx->xpend.absorbed;
   if (flushed) *flushed = ctx->xpend.flushed;
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_lazy_x_stats(abft_hip_ctx *ctx, long *bursts, long *applied_in_bursts, long *applied_by_flush) {
+  if (!ctx) return set_err(ABFT_ERR_INVALID, "null context");
+  if (bursts) *bursts = ctx->lazy.bursts;
+  if (applied_in_bursts) *applied_in_bursts = ctx->lazy.applied_in_bursts;
+  if (applied_by_flush) *applied_by_flush = ctx->lazy.applied_by_flush;
   return ABFT_OK;
 }
 

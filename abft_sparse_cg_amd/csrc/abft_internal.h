@@ -210,7 +210,7 @@ struct CooDev {
 #define ABFT_X_IN_SPMV_MODES 0x01u  // the x update inside the next SpMV (abft_hip.hip, xpend): bit m = armed by default on matrices of ECC mode m -- `none` only: in the five other modes the alternated series showed no gain, in sed a loss (profiles/r11/mode_*)
 #endif
 #ifndef ABFT_CFG_XUPD_NT
-#define ABFT_CFG_XUPD_NT 7  // spmv_csr_kernel<..., XUPD>: non-temporal access to the update's streams, bit 0 the p_old load, 1 the x load, 2 the x store (0: 2-3 % slower than without the update; 7 with P_OUT_NT: 5 % faster, profiles/r11)
+#define ABFT_CFG_XUPD_NT 7  // spmv_csr_kernel<..., NUPD>: non-temporal access to the update's streams, bit 0 the p_old load, 1 the x load, 2 the x store (0: 2-3 % slower than without the update; 7 with P_OUT_NT: 5 % faster, profiles/r11)
 #endif
 #ifndef ABFT_CFG_P_OUT_NT
 #define ABFT_CFG_P_OUT_NT 1  // calc_p writing the new p into the buffer its handle swaps to (xpend): non-temporal stores
@@ -219,10 +219,13 @@ struct CooDev {
 #define ABFT_CFG_R_NT 0  // calc_r_kernel's r store, non-temporal: bit 0 into the shadow of a run-ahead (r_out != r), bit 1 in place (profiles/r12/variants_ab.md)
 #endif
 #ifndef ABFT_CFG_Y_NT
-#define ABFT_CFG_Y_NT 0  // spmv_csr_kernel<MODE_NONE, ..., XUPD>: the y[row] store non-temporal (profiles/r12/variants_ab.md)
+#define ABFT_CFG_Y_NT 0  // spmv_csr_kernel<MODE_NONE, ..., NUPD>: the y[row] store non-temporal (profiles/r12/variants_ab.md)
 #endif
 #ifndef ABFT_AHEAD_DEFAULT
 #define ABFT_AHEAD_DEFAULT 1  // run-ahead of the host-scalar loop (abft_hip.hip, spec.ahead) without ABFT_HIP_AHEAD: 0 off, 1 calc_p, 2 calc_r and calc_p -- 1: level 1 passed the rule against level 0 and the parent, level 2 did not pass it against level 1 (profiles/r12/variants_ab.md), nor with the deferred finishes (profiles/r13/bench_ab.md)
+#endif
+#ifndef ABFT_LAZY_X_DEFAULT
+#define ABFT_LAZY_X_DEFAULT 2  // queue depth of the x updates without ABFT_HIP_LAZY_X (loop_state.h, LazyUpdates): 1 no queue, 2 or 4: every 2nd / 4th predicted SpMV applies that many in one pass -- 2: its slowest run lay above the fastest of depth 1 and of the parent, depth 4's did not lie above depth 2's fastest (profiles/r14/bench_ab.md)
 #endif
 #ifndef ABFT_DEFER_FINISH_DEFAULT
 #define ABFT_DEFER_FINISH_DEFAULT 1  // without ABFT_HIP_DEFER_FINISH: the reductions in front of a run-ahead kernel leave their finish to its head (loop_state.h, RunAhead::defer_finish) -- 1: at level 1 its slowest run lay above the parent's fastest (profiles/r13/bench_ab.md)
@@ -351,11 +354,12 @@ struct TileSpan {
   uint32_t first, cut, skip, count;
 };
 
-// spmv_csr_kernel<..., XUPD>: the pending x += alpha p_old the launch applies, row by row (abft_hip.hip "xpend")
+// spmv_csr_kernel<..., NUPD>: the n (1, 2 or 4) updates x += u[k].alpha * u[k].p_old the launch applies row by row, k = 0 first
+// (abft_hip.hip "xpend", and the queue of loop_state.h's LazyUpdates); axpy_chain_kernel: 1 to 4 of them
 struct XUpd {
   double *xs;
-  const double *p_old;
-  double alpha;
+  struct { const double *p_old; double alpha; } u[4];  // (pairs: one update's arguments lie where they lay before there were four)
+  int n;
 };
 
 // sweep-layout SpMV (modes other than constraints): panels [c0, c1) in one persistent launch of
@@ -469,6 +473,8 @@ hipError_t launch_fuse_finalize_defer(const FuseOut &f, uint32_t nblk, double *c
 // the head alone, in one block: behind a deferred producer whose consumer could not be launched
 hipError_t launch_deferred_finish(const ReduceOut &head, uint32_t nb, hipStream_t s);
 hipError_t launch_axpy(double *x, const double *p, double alpha, const double *alpha_ptr, int n, hipStream_t s);
+// x += u.u[0].alpha * u.u[0].p_old, then u.u[1], ... u.u[u.n - 1] (1 <= u.n <= 4) over n elements: launch_axpy u.n times, x read and written once
+hipError_t launch_axpy_chain(const XUpd &u, int n, hipStream_t s);
 // the two halves of a guarded iteration (abft_hip_cg_iteration_until_dev): live when *rr > threshold -- then what
 // launch_calc_r (alpha = *rr / *pw, left in alpha_out) and launch_calc_px (beta = *rr_new / *rr) do --, else nothing
 // but the new pair out.dev_out = {the bits of *rr, queued events}

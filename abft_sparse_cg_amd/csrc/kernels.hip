@@ -833,13 +833,16 @@ __device__ __forceinline__ bool csr_row_sum(const CsrDev &A, const EventRing &ev
 // VECC (abft_hip_spmv_vecc): x and y hold protected elements.  Every gathered x and
 // the fused product's x[row] get the full check (repaired in registers, reported, x itself not written
 // back); y[row] is stored encoded and the fused product uses the decoded x[row] and the truncated sum.
-// XUPD (cross-call fusion no. 4, abft_hip.hip "xpend"): the launch also applies the x += alpha p that the
-// preceding calc_p left pending on the OLD p -- xu.xs[row] = xu.xs[row] + xu.alpha * xu.p_old[row] for every
+// NUPD = 1 (cross-call fusion no. 4, abft_hip.hip "xpend"): the launch also applies the x += alpha p that the
+// preceding calc_p left pending on the OLD p -- xu.xs[row] = xu.xs[row] + xu.u[0].alpha * xu.u[0].p_old[row] for every
 // row of the workgroup's row block, exactly once, whatever becomes of the row (no elements, bad row
 // pointers, a fatal element): two row-indexed, coalesced streams that hang off the block descriptor only
 // and travel under the latency of the codes and the gathers.  Separate multiply and add
 // (-ffp-contract=off): the bits axpy_kernel / calc_px_kernel give.  The row blocks partition
 // [0, n_out) (cut_blocks), and the launch covers every block.
+// NUPD = 2, 4 (no. 6, loop_state.h LazyUpdates): that many queued updates in one pass, oldest first -- x read once,
+// NUPD old p's read beside it, xs = xs + a0 * p0; xs = xs + a1 * p1; ... and one store.  Exactly NUPD
+// updates: a slot padded with alpha = 0 would turn -0.0 into +0.0 and 0 * inf into NaN.
 #if ABFT_CFG_XUPD_NT  // the update's streams are touched once per launch: keep them out of the caches the gathers live in
 #define XUPD_LOAD_P(p) ((ABFT_CFG_XUPD_NT & 1) ? __builtin_nontemporal_load(p) : *(p))
 #define XUPD_LOAD_X(p) ((ABFT_CFG_XUPD_NT & 2) ? __builtin_nontemporal_load(p) : *(p))
@@ -849,7 +852,24 @@ __device__ __forceinline__ bool csr_row_sum(const CsrDev &A, const EventRing &ev
 #define XUPD_LOAD_X(p) (*(p))
 #define XUPD_STORE_X(p, v) (*(p) = (v))
 #endif
-template <int MODE, int EPT, bool FUSE, bool VECC = false, bool XUPD = false>
+// the NUPD multiply-adds of one element, oldest first
+// (scalars, not an array: the NUPD = 1 instantiation is instruction for instruction what it was before there were four)
+template <int NUPD>
+__device__ __forceinline__ void xupd_load(const XUpd &xu, uint32_t row, double &xs, double &po, double &po1, double &po2,
+                                          double &po3) {
+  xs = XUPD_LOAD_X(xu.xs + row);
+  po = XUPD_LOAD_P(xu.u[0].p_old + row);
+  if (NUPD > 1) po1 = XUPD_LOAD_P(xu.u[1].p_old + row);
+  if (NUPD > 2) { po2 = XUPD_LOAD_P(xu.u[2].p_old + row); po3 = XUPD_LOAD_P(xu.u[3].p_old + row); }
+}
+template <int NUPD>
+__device__ __forceinline__ double xupd_chain(const XUpd &xu, double xs, double po, double po1, double po2, double po3) {
+  xs = xs + xu.u[0].alpha * po;
+  if (NUPD > 1) xs = xs + xu.u[1].alpha * po1;
+  if (NUPD > 2) { xs = xs + xu.u[2].alpha * po2; xs = xs + xu.u[3].alpha * po3; }
+  return xs;
+}
+template <int MODE, int EPT, bool FUSE, bool VECC = false, int NUPD = 0>
 __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const double *__restrict__ x,
                                                               double *__restrict__ y, EventRing ev,
                                                               FuseOut fuse, TileSpan span, CsrCompact cc,
@@ -885,8 +905,8 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
       }
       if (FUSE) xr = x[fuse.x_off + r];
     }
-    double xs = 0.0, po = 0.0;  // XUPD: the first row's operands, in flight beside the codes and the gathers
-    if (XUPD && r < row1) { xs = XUPD_LOAD_X(xu.xs + r); po = XUPD_LOAD_P(xu.p_old + r); }
+    double xs = 0.0, po = 0.0, po1 = 0.0, po2 = 0.0, po3 = 0.0;  // NUPD: the first row's operands, in flight beside the codes and the gathers
+    if (NUPD && r < row1) xupd_load<NUPD>(xu, r, xs, po, po1, po2, po3);
     if (MODE == MODE_NONE && pd.y != 0u)
       csr_stage_packed<EPT, VECC>(A, cp, pd, x, ev, base, e0, e1, s_prod);
     else if (MODE == MODE_NONE)
@@ -898,9 +918,9 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
       if (row != r) {
         rs = A.rowptr[row]; re = A.rowptr[row + 1];
         if (FUSE) xr = x[fuse.x_off + row];
-        if (XUPD) { xs = XUPD_LOAD_X(xu.xs + row); po = XUPD_LOAD_P(xu.p_old + row); }
+        if (NUPD) xupd_load<NUPD>(xu, row, xs, po, po1, po2, po3);
       }
-      if (XUPD) XUPD_STORE_X(xu.xs + row, xs + xu.alpha * po);  // in front of every `continue`: the update does not depend on the row
+      if (NUPD) XUPD_STORE_X(xu.xs + row, xupd_chain<NUPD>(xu, xs, po, po1, po2, po3));  // in front of every `continue`: the update does not depend on the row
       if (MODE == MODE_CONSTRAINTS) {  // reference CSR/CPUContext.cpp:173-182
         if (re > A.nnz) { push_event(ev, ABFT_EV_ROW_SIZE, row, row, FMT_CSR); continue; }
         if (re < rs) { push_event(ev, ABFT_EV_ROW_ORDER, row, row, FMT_CSR); continue; }
@@ -917,7 +937,7 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
             dsum += vecc_value(xw) * vecc_value(yw);
           }
         } else {
-          if (ABFT_CFG_Y_NT && XUPD && MODE == MODE_NONE) __builtin_nontemporal_store(acc, y + row);  // w ends at the boundary calc_r waits behind
+          if (ABFT_CFG_Y_NT && NUPD && MODE == MODE_NONE) __builtin_nontemporal_store(acc, y + row);  // w ends at the boundary calc_r waits behind
           else y[row] = acc;
           if (FUSE) dsum += xr * acc;
         }
@@ -925,8 +945,12 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
     }
   } else {
     // long row (or inconsistent pointers): rows of this block one at a time, tile by tile
-    if (XUPD)
-      for (uint32_t row = row0 + threadIdx.x; row < row1; row += ABFT_BLOCK) XUPD_STORE_X(xu.xs + row, XUPD_LOAD_X(xu.xs + row) + xu.alpha * XUPD_LOAD_P(xu.p_old + row));
+    if (NUPD)
+      for (uint32_t row = row0 + threadIdx.x; row < row1; row += ABFT_BLOCK) {
+        double xs = 0.0, po = 0.0, po1 = 0.0, po2 = 0.0, po3 = 0.0;
+        xupd_load<NUPD>(xu, row, xs, po, po1, po2, po3);
+        XUPD_STORE_X(xu.xs + row, xupd_chain<NUPD>(xu, xs, po, po1, po2, po3));
+      }
     for (uint32_t row = row0; row < row1; row++) {
       const uint32_t rs = A.rowptr[row], re = A.rowptr[row + 1];
       if (MODE == MODE_CONSTRAINTS) {
@@ -1093,8 +1117,14 @@ template <int MODE>
 static hipError_t launch_spmv_csr_mode(const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
                                        const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s,
                                        bool vecc, const XUpd *xu) {
-  if (xu)
-    hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true, false, true>), dim3(span.count), dim3(ABFT_BLOCK), 0,
+  if (xu && xu->n == 4)
+    hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true, false, 4>), dim3(span.count), dim3(ABFT_BLOCK), 0,
+                       s, A, x, y, ev, *fuse, span, cc, cp, *xu);
+  else if (xu && xu->n == 2)
+    hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true, false, 2>), dim3(span.count), dim3(ABFT_BLOCK), 0,
+                       s, A, x, y, ev, *fuse, span, cc, cp, *xu);
+  else if (xu)
+    hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true, false, 1>), dim3(span.count), dim3(ABFT_BLOCK), 0,
                        s, A, x, y, ev, *fuse, span, cc, cp, *xu);
   else if (vecc && fuse)
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true, true>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
@@ -1115,8 +1145,12 @@ hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, cons
                            const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s, bool vecc,
                            const XUpd *xu) {
   // the x update rides on a launch of every row block with the fused product, plain vectors (abft_hip.hip decides)
-  if (xu && (!fuse || vecc || span.first || span.skip || span.count != A.nblk || !span.count || !xu->xs || !xu->p_old))
-    return hipErrorInvalidValue;
+  if (xu) {
+    if (!fuse || vecc || span.first || span.skip || span.count != A.nblk || !span.count || !xu->xs) return hipErrorInvalidValue;
+    if (xu->n != 1 && xu->n != 2 && xu->n != 4) return hipErrorInvalidValue;
+    for (int k = 0; k < xu->n; k++)
+      if (!xu->u[k].p_old) return hipErrorInvalidValue;
+  }
   // every tile the span maps to must exist: checked here, on the host
   if (span.count == 0) return hipSuccess;
   if ((uint64_t)span.first + span.count + span.skip > A.nblk || span.cut > span.count) return hipErrorInvalidValue;
@@ -3866,6 +3900,29 @@ __global__ __launch_bounds__(ABFT_BLOCK) void axpy_kernel(double *__restrict__ x
   }
 }
 
+// the queued updates x += a0 p0; x += a1 p1; ... on their own (loop_state.h, LazyUpdates): axpy_kernel
+// u.n times -- per element the same multiplies and adds in the same order -- with x read once and written once
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void axpy_chain_kernel(XUpd u, int n) {
+  double *x = u.xs;
+  const int cnt = u.n;  // uniform
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      double2 xv = *reinterpret_cast<double2 *>(x + i);
+      for (int k = 0; k < cnt; k++) {
+        const double2 pv = *reinterpret_cast<const double2 *>(u.u[k].p_old + i);
+        xv.x += u.u[k].alpha * pv.x; xv.y += u.u[k].alpha * pv.y;
+      }
+      *reinterpret_cast<double2 *>(x + i) = xv;
+    } else {
+      double xv = x[i];
+      for (int k = 0; k < cnt; k++) xv = xv + u.u[k].alpha * u.u[k].p_old[i];
+      x[i] = xv;
+    }
+  }
+}
+
 // (x, p: the operands of the calc_xr this is the r half of.  The kernel does not touch them, but the order in which r.r
 // is summed follows the walk, and the walk is chosen over all four operands -- as calc_xr_kernel's and cg_tail_kernel's
 // is -- so that the sum has the same bits whichever of the three runs the call)
@@ -3930,6 +3987,22 @@ hipError_t launch_axpy(double *x, const double *p, double alpha, const double *a
     hipLaunchKernelGGL(axpy_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, alpha, alpha_ptr, n);
   else
     hipLaunchKernelGGL(axpy_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, alpha, alpha_ptr, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_axpy_chain(const XUpd &u, int n, hipStream_t s) {
+  if (u.n < 1 || u.n > 4 || !u.xs) return hipErrorInvalidValue;
+  if (n <= 0) return hipSuccess;
+  bool vec2 = aligned16(u.xs);
+  for (int k = 0; k < u.n; k++) {
+    if (!u.u[k].p_old) return hipErrorInvalidValue;
+    vec2 = vec2 && aligned16(u.u[k].p_old);
+  }
+  const int nb = reduce_blocks(n);
+  if (vec2)
+    hipLaunchKernelGGL(axpy_chain_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, u, n);
+  else
+    hipLaunchKernelGGL(axpy_chain_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, u, n);
   return hipGetLastError();
 }
 

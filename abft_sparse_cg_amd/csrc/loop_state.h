@@ -3,7 +3,7 @@
 // and every decision taken on it: which call is served from what is already in flight, what is dropped, what is armed.
 // Host code only, no HIP header: abft_hip.hip asks a decision here, does the GPU work (launches, allocations, waits
 // for a pinned slot) and reports back through a transition; tests/host/loop_state_play.cpp does the same with no GPU.
-// Nothing here launches, allocates or fails.  DESIGN.md section 4 describes the five fusions.
+// Nothing here launches, allocates or fails.  DESIGN.md section 4 describes the fusions.
 #pragma once
 #include <cassert>
 #include <cstdint>
@@ -75,7 +75,7 @@ struct DeferredUpdate {
 // for, so once the library has seen spmv(A, p, w) directly follow a calc_p that took a deferred update along
 // (`armed`), that calc_p writes the new p into `shadow`, swaps it with p's buffer and leaves the update pending on
 // the OLD p (`active`); the predicted spmv(A, p, w) -- streaming CSR, fused product -- applies it row by row under
-// its own memory latency (spmv_csr_kernel<..., XUPD>).  Anything else that comes first applies it with axpy_kernel
+// its own memory latency (spmv_csr_kernel<..., NUPD = 1>).  Anything else that comes first applies it with axpy_kernel
 // (the prologue) and disarms.  Same bits either way; only when each x[i] is written changes.
 struct PendingUpdate {
   bool armed = false, active = false;
@@ -91,6 +91,36 @@ struct PendingUpdate {
   Shadow shadow[2];
   int shadow_at = 0;                        // the slot used last
   long absorbed = 0, flushed = 0;
+};
+
+// cross-call fusion no. 6 (ABFT_HIP_LAZY_X=1|2|4): nobody reads x until the solve ends or a caller looks, yet the
+// pending update costs its SpMV a read and a write of x every iteration.  With depth d > 1 the predicted SpMV that
+// absorbs a pending update only QUEUES it -- the old p stays where it is, a spare buffer takes its place as the next
+// calc_p's target -- until the queue and the pending update together make d: that SpMV applies all d in one pass
+// (spmv_csr_kernel<..., NUPD = d>: x read once, written once, the d multiply-adds per element in arrival order).
+// Four continuations of the predicted loop keep the queue: the eligible spmv(A, p, w), the dot served from its fused
+// product, the calc_xr that defers its update onto the queue's x, and the calc_p that takes that update along.
+// Everything else applies it first, in order, with one axpy_chain_kernel (the prologue).  Same bits either way.
+// depth 1: no queue, nothing here is ever touched.
+struct LazyUpdates {
+  static constexpr int MAX_DEPTH = 4;
+  struct Entry { double *p_old; double alpha; };
+  int depth = 1;           // 1, 2 or 4; lowered for good when the spare buffers do not fit (abft_hip.hip: lazy_ring_ensure)
+  double *x = nullptr;     // the queue's target: x += q[0].alpha * q[0].p_old, then q[1], ... over n elements
+  int n = 0;
+  int count = 0;
+  Entry q[MAX_DEPTH] = {};
+  // context-owned buffers of spare_n (+ 2) doubles nobody reads or writes: with the queued old p's and the one in
+  // xpend.shadow they are the `depth` buffers that, with the one behind p's handle, make the ring of depth + 1
+  double *spare[MAX_DEPTH - 1] = {};
+  int nspare = 0, spare_n = 0;
+  long bursts = 0, applied_in_bursts = 0, applied_by_flush = 0;
+};
+// updates to apply to x in one pass, oldest first
+struct LazyBatch {
+  double *x = nullptr;
+  int n = 0, count = 0;
+  LazyUpdates::Entry e[LazyUpdates::MAX_DEPTH] = {};
 };
 
 // The caller's iteration, as the library knows it: what the SpMV's fold, the speculation and the run-ahead all read.
@@ -165,6 +195,7 @@ struct LoopState {
   FusedProduct fused;
   DeferredUpdate defer;
   PendingUpdate xpend;
+  LazyUpdates lazy;
   CallerIteration iter;
   Speculation spec;
   RunAhead ahead;
@@ -177,6 +208,8 @@ static inline void loop_settle_switches(LoopState &L) {
   L.xin_enabled = L.xin_enabled && L.defer_enabled && L.fuse_enabled && !L.spec.enabled;
   if (!L.xin_enabled) L.ahead.level = 0;
   if (L.ahead.level == 0) L.ahead.defer_finish = false;
+  // the queue hangs off x-in-SpMV's pending update: no such path, no queue
+  if (!L.xin_enabled || (L.lazy.depth != 2 && L.lazy.depth != 4)) L.lazy.depth = 1;
 }
 static inline bool loop_invariant(const LoopState &L) {
   return (!L.spec.enabled || !L.xin_enabled) && (L.xin_enabled || L.ahead.level == 0);
@@ -250,6 +283,7 @@ enum : unsigned {
   KEEP_PENDING = 4u,   // the SpMV that may absorb the update pending on the old p: decides itself
   FORGET_FUSED = 8u,   // writes a vector the fused product may name
   FORGET_ITER = 16u,   // works on vectors the learned iteration may name, in a way the loop's bookkeeping does not follow
+  KEEP_LAZY = 32u,     // one of the four continuations that keep the queue of x updates (LazyUpdates): decides itself
 };
 
 static inline void prologue_begin(LoopState &L, unsigned keep) {
@@ -259,6 +293,7 @@ static inline void prologue_begin(LoopState &L, unsigned keep) {
 }
 static inline bool prologue_flushes_pending(unsigned keep) { return !(keep & (KEEP_DEFERRED | KEEP_PENDING)); }
 static inline bool prologue_flushes_deferred(unsigned keep) { return !(keep & KEEP_DEFERRED); }
+static inline bool prologue_flushes_lazy(unsigned keep) { return !(keep & KEEP_LAZY); }
 static inline void prologue_end(LoopState &L, unsigned keep) {
   if (keep & FORGET_FUSED) forget_fused(L);
   if (keep & FORGET_ITER) forget_iteration(L);
@@ -376,6 +411,84 @@ static inline bool pending_absorbed_by(LoopState &L, bool eligible, const abft_h
 static inline void pending_absorbed(LoopState &L) {  // applied exactly once, whatever the launch reports about the matrix
   L.xpend.active = false;
   L.xpend.absorbed++;
+}
+
+// ---- fusion no. 6: the queue of x updates ----
+
+// Everything queued is due on its own (something other than the four keeping continuations came): true -> the caller
+// applies `out` with one launch.  The old p's go back to the spares behind that launch, in stream order.
+static inline bool lazy_flush_due(LoopState &L, LazyBatch &out) {
+  auto &Z = L.lazy;
+  if (Z.count == 0) return false;
+  out.x = Z.x; out.n = Z.n; out.count = Z.count;
+  for (int k = 0; k < Z.count; k++) {
+    out.e[k] = Z.q[k];
+    assert(Z.nspare < LazyUpdates::MAX_DEPTH - 1);
+    Z.spare[Z.nspare++] = Z.q[k].p_old;
+  }
+  Z.applied_by_flush += Z.count;
+  Z.count = 0;
+  return true;
+}
+// Take or apply, once pending_absorbed_by has said "absorb".  First: a pending update on another x or length than the
+// queue's does not join it -- the caller flushes the queue ...
+static inline bool lazy_queue_mismatch(const LoopState &L) {
+  const auto &Z = L.lazy;
+  return Z.count > 0 && (Z.x != L.xpend.x || Z.n != L.xpend.n);
+}
+// ... and, the queue empty, has the spares of this length ready before it asks (false: lazy_ring_ensure is due)
+static inline bool lazy_ring_ready(const LoopState &L) {
+  const auto &Z = L.lazy;
+  return Z.depth <= 1 || Z.count > 0 || (Z.spare_n == L.xpend.n && Z.nspare == Z.depth - 1);
+}
+enum class LazyStep {
+  ApplyOne,  // depth 1: this SpMV applies the pending update, as ever (pending_absorbed)
+  Queue,     // the pending update joins the queue, this SpMV applies nothing (lazy_queue_pending)
+  Burst,     // the queue and the pending update make `depth`: this SpMV applies them all (lazy_burst)
+};
+static inline LazyStep lazy_step(const LoopState &L) {
+  const auto &Z = L.lazy;
+  assert(L.xpend.active && !lazy_queue_mismatch(L) && lazy_ring_ready(L));
+  if (Z.depth <= 1) return LazyStep::ApplyOne;
+  if (Z.count + 1 >= Z.depth) return LazyStep::Burst;
+  assert(Z.nspare > 0);
+  return LazyStep::Queue;
+}
+// The pending update is the queue's youngest entry; its SpMV has taken it over (`absorbed`).  The old p stays put: a
+// spare takes its place in xpend.shadow, where the next calc_p -- as written or run ahead -- writes.
+static inline void lazy_queue_pending(LoopState &L) {
+  auto &Z = L.lazy;
+  auto &X = L.xpend;
+  double *old = const_cast<double *>(X.p_old);
+  Z.x = X.x; Z.n = X.n;
+  Z.q[Z.count++] = {old, X.alpha};
+  for (auto &s : X.shadow)
+    if (s.buf == old) s.buf = Z.spare[--Z.nspare];
+  pending_absorbed(L);
+}
+// The queue, then the pending update: what this SpMV applies.  The queued old p's are spares again behind it.
+static inline LazyBatch lazy_burst(LoopState &L) {
+  auto &Z = L.lazy;
+  const auto &X = L.xpend;
+  LazyBatch b;
+  b.x = X.x; b.n = X.n;
+  for (int k = 0; k < Z.count; k++) {
+    b.e[b.count++] = Z.q[k];
+    Z.spare[Z.nspare++] = Z.q[k].p_old;
+  }
+  b.e[b.count++] = {const_cast<double *>(X.p_old), X.alpha};
+  Z.count = 0;
+  Z.bursts++;
+  Z.applied_in_bursts += b.count;
+  pending_absorbed(L);
+  return b;
+}
+// calc_xr(x, r, p, w) keeps the queue when it defers its own update (can_defer_x) onto the queue's x
+static inline bool lazy_kept_by_calc_xr(const LoopState &L, const abft_hip_vector *x, const abft_hip_vector *r,
+                                        const abft_hip_vector *p, const abft_hip_vector *w) {
+  const auto &Z = L.lazy;
+  if (Z.count == 0) return true;
+  return x && r && p && w && x->d == Z.x && x->n == Z.n && can_defer_x(L, x, r, p, w);
 }
 
 // ---- the two quotients ----

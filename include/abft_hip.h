@@ -630,9 +630,22 @@ int abft_hip_tail_stats(abft_hip_ctx *ctx, int *path, int *grid, int *want, long
  * By default the prediction is armed on matrices of mode ABFT_MODE_NONE only (the one mode it was measured to pay on);
  * ABFT_HIP_X_IN_SPMV=1 (read when the context is created) arms it in every mode, =0 in none; it is also off with
  * ABFT_HIP_FUSE_X=0, ABFT_HIP_FUSE_DOT=0 or ABFT_HIP_SPECULATE=1, and from the context's first
- * abft_hip_graph_begin on.  *absorbed = pending updates applied by an SpMV, *flushed = applied on their own, since
- * the context was created (host counters; either pointer may be null). */
+ * abft_hip_graph_begin on.  *absorbed = pending updates taken over by the predicted SpMV -- applied by that launch
+ * or, with ABFT_HIP_LAZY_X above 1, queued by it for a later one -- *flushed = pending updates applied on their own
+ * before their SpMV came, since the context was created (host counters; either pointer may be null). */
 int abft_hip_x_in_spmv_stats(abft_hip_ctx *ctx, long *absorbed, long *flushed);
+
+/* The queue of x updates ("Sixth cross-call fusion"; ABFT_HIP_LAZY_X=1|2|4, read when the context
+ * is created; 1 wherever the x update inside the next SpMV is off).  Nobody reads x before the solve ends or the
+ * caller looks at it, so with depth d > 1 the predicted SpMV only queues the update it takes over, and every d-th one
+ * applies d of them in one pass: x read and written once, the d multiply-adds per element in arrival order -- the
+ * same bits.  The loop's own calls keep the queue (that abft_hip_spmv(A, p, w), the abft_hip_dot(p, w) served from its
+ * fused product, the abft_hip_calc_xr on the same x and the abft_hip_calc_p behind it); every other call applies it
+ * first, in order, with one kernel.  The context holds d buffers of p's length for it (d + 1 with the one behind p's
+ * handle); where they do not fit, the depth falls to 2 or 1.  *bursts = SpMV launches that applied d updates,
+ * *applied_in_bursts = updates those applied, *applied_by_flush = queued updates applied on their own, since the
+ * context was created (host counters; any pointer may be null). */
+int abft_hip_lazy_x_stats(abft_hip_ctx *ctx, long *bursts, long *applied_in_bursts, long *applied_by_flush);
 
 /* Run-ahead of the host-scalar loop ("Fifth cross-call fusion"; ABFT_HIP_AHEAD=0|1|2, read when
  * the context is created).  The loop hands two scalars to the host per iteration, and the GPU runs nothing while the
