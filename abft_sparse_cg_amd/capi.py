@@ -63,6 +63,7 @@ SIGNATURES = {
     "abft_hip_matrix_info": (C.c_int, [vp, i32p, i32p]),
     "abft_hip_matrix_compact_stats": (C.c_int, [vp, u32p, u32p, u32p]),
     "abft_hip_matrix_packed_stats": (C.c_int, [vp, u32p, u32p, u32p]),
+    "abft_hip_packed_stats": (C.c_int, [vp, u32p, u32p, u32p]),
     "abft_hip_matrix_read_element": (C.c_int, [vp, C.c_uint32, u32p]),
     "abft_hip_matrix_read_csr": (C.c_int, [vp, vp, vp, vp]),
     "abft_hip_matrix_read_coo": (C.c_int, [vp, vp]),

@@ -458,6 +458,13 @@ class HIPContext:
         check(self.L.abft_hip_matrix_info(mat.h, C.byref(lay), C.byref(n)))
         return ("stream", "panels", "sweep", "slice")[lay.value], n.value
 
+    def packed_stats(self, mat):
+        """-> (packed row blocks, those staged without per-element bound tests, those of them whose equal-length rows
+        are also summed without clamps) -- measurement and tests only (include/abft_hip.h, abft_hip_packed_stats)"""
+        p, s, r = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(self.L.abft_hip_packed_stats(mat.h, C.byref(p), C.byref(s), C.byref(r)))
+        return p.value, s.value, r.value
+
     def set_interior(self, mat, row_lo, row_hi):
         """rows [row_lo, row_hi) read nothing a peer still has to send (include/abft_hip.h)"""
         check(self.L.abft_hip_matrix_set_interior(mat.h, row_lo, row_hi))

@@ -164,6 +164,12 @@ struct abft_hip_matrix {
   CsrPacked packed{};
   std::vector<Pair> pdesc_host;
   PalettePool pool;
+  // ... and what the SpMV may skip on them (see CsrPackedFast): allocated once at create, never moved (captured graphs
+  // hold it by address); with a host copy of the words
+  CsrPackedFast packed_fast{};
+  std::vector<uint32_t> fast_host;
+  size_t codes_len = 0;  // codes allocated behind packed.code16 (packed_fast_word's window condition)
+  bool fast_on = false;  // ABFT_HIP_PACKED_FAST as create read it: off, every word is and stays 0
   std::vector<void *> allocs;
   bool streams() const { return layout == Layout::Stream; }
 };
@@ -674,7 +680,9 @@ static const PlanGeometry g_geometry = {(uint32_t)ABFT_BLOCK,      (uint32_t)ABF
 
 // the layout knobs, read once per create (a caller may change the environment between two creates)
 static LayoutKnobs from_env() {
-  return read_knobs([](const char *name) -> const char * { return getenv(name); });
+  LayoutKnobs k = read_knobs([](const char *name) -> const char * { return getenv(name); });
+  if (!k.packed_fast) k.packed_fast = ABFT_PACKED_FAST_DEFAULT != 0;
+  return k;
 }
 
 template <typename T>
@@ -795,16 +803,26 @@ static int attach_compact(abft_hip_matrix *m, CompactBuild &cb) {
 
 // ... and the packed codes (see CsrPacked); the pool has room for the palettes injects add.
 // ABFT_HIP_PACKED=0, or no block packs: nothing allocated.
-static int attach_packed(abft_hip_matrix *m, PackedBuild &pk) {
+static int attach_packed(abft_hip_matrix *m, PackedBuild &pk, bool fast) {
   if (!pk.any) return ABFT_OK;
   uint16_t *dcode = nullptr;
   Pair *ddesc = nullptr;
   uint64_t *dpal = nullptr;
+  Blk *dfast = nullptr;
   int rc;
   if ((rc = upload_all(m, &dcode, pk.codes)) || (rc = upload_all(m, &ddesc, pk.pdesc)) ||
       (rc = dev_upload(m, &dpal, m->pool.host.data(), m->pool.host.size(), m->pool.cap)))
     return rc;
-  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // pdesc moves
+  // one record per block, {descriptor, fast word, 0}: what the mode-none SpMV on plain vectors loads instead of the
+  // descriptor (ABFT_HIP_PACKED_FAST=0: the planner has left every word 0, and `fast_on` keeps a re-plan from setting one)
+  std::vector<Blk> rec(pk.pdesc.size());
+  for (size_t b = 0; b < rec.size(); b++) rec[b] = Blk{pk.pdesc[b].x, pk.pdesc[b].y, pk.fast[b], 0u};
+  if ((rc = upload_all(m, &dfast, rec))) return rc;
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // pdesc moves, rec goes out of scope
+  m->packed_fast.rec = reinterpret_cast<const uint4 *>(dfast);
+  m->fast_on = fast;
+  m->fast_host = std::move(pk.fast);
+  m->codes_len = pk.codes.size();
   m->packed.code16 = dcode;
   m->packed.pdesc = reinterpret_cast<const uint2 *>(ddesc);
   m->packed.pal = reinterpret_cast<const double *>(dpal);
@@ -858,8 +876,14 @@ static int packed_after_inject(abft_hip_matrix *m, uint32_t pos) {
                           hipMemcpyHostToDevice, s));
   }
   HIPCHK(hipMemcpyAsync(const_cast<uint2 *>(m->packed.pdesc) + b, &d, sizeof(d), hipMemcpyHostToDevice, s));
-  HIPCHK(hipStreamSynchronize(s));  // `codes` and `d` are local
+  // the block's record -- the descriptor again, with its fast word from the one function that decides it (0 for a
+  // demoted block) -- behind its descriptor and codes; every SpMV is ordered behind all three on this stream
+  const uint32_t fw = m->fast_on ? packed_fast_word(g_geometry, m->blk_host[b], d, m->csr.n_in, m->codes_len) : 0u;
+  const Blk rec{d.x, d.y, fw, 0u};
+  HIPCHK(hipMemcpyAsync(const_cast<uint4 *>(m->packed_fast.rec) + b, &rec, sizeof(rec), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));  // `codes`, `d` and `rec` are local
   m->pdesc_host[b] = d;  // only once the device holds it
+  m->fast_host[b] = fw;
   return ABFT_OK;
 }
 
@@ -909,7 +933,7 @@ static int create_csr(abft_hip_matrix *m, const LayoutKnobs &knobs, const uint32
   A.blk = reinterpret_cast<const uint4 *>(d_blk);
   if (plan.layout == Layout::Stream) {
     m->blk_host = plan.blk;
-    if ((rc = attach_compact(m, plan.compact)) || (rc = attach_packed(m, plan.packed))) return rc;
+    if ((rc = attach_compact(m, plan.compact)) || (rc = attach_packed(m, plan.packed, *knobs.packed_fast))) return rc;
   }
   hipError_t e = launch_encode_csr(mode, A.cols, A.vals, A.nnz, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // host arrays may be freed on return
@@ -1154,6 +1178,29 @@ extern "C" int abft_hip_matrix_packed_stats(abft_hip_matrix *mat, uint32_t *pack
   if (packed_tiles) *packed_tiles = np;
   if (tiles) *tiles = stream ? (uint32_t)blk.size() : 0u;
   if (mismatches) *mismatches = bad;
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_packed_stats(abft_hip_matrix *mat, uint32_t *packed, uint32_t *stage_fast, uint32_t *row_fast) {
+  if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
+  if (int rc = enter(mat->ctx, 0)) return rc;
+  uint32_t np = 0, ns = 0, nr = 0;
+  if (mat->fmt == ABFT_FMT_CSR && mat->streams() && mat->packed.pdesc) {
+    // the words from the device copy: what the SpMV reads
+    std::vector<Blk> rec(mat->blk_host.size(), Blk{0u, 0u, 0u, 0u});
+    if (mat->packed_fast.rec && !rec.empty()) {
+      HIPCHK(hipMemcpyAsync(rec.data(), mat->packed_fast.rec, rec.size() * sizeof(Blk), hipMemcpyDeviceToHost, mat->ctx->stream));
+      HIPCHK(hipStreamSynchronize(mat->ctx->stream));
+    }
+    for (size_t b = 0; b < rec.size(); b++) {
+      np += rec[b].y != 0u;
+      ns += (rec[b].z & ABFT_FAST_STAGE) != 0u;
+      nr += (rec[b].z >> ABFT_FAST_LEN_SHIFT) != 0u;
+    }
+  }
+  if (packed) *packed = np;
+  if (stage_fast) *stage_fast = ns;
+  if (row_fast) *row_fast = nr;
   return ABFT_OK;
 }
 
@@ -2439,7 +2486,7 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
         }
       }
       HIPCHK(launch_spmv_csr(mat->mode, mat->csr, mat->compact, mat->packed, span, vec->d, result->d, ctx->ring,
-                             do_fuse ? &fuse : nullptr, ctx->stream, vecc, xu.n ? &xu : nullptr));
+                             do_fuse ? &fuse : nullptr, ctx->stream, vecc, xu.n ? &xu : nullptr, mat->packed_fast));
     } else
       HIPCHK(launch_spmv_coo(mat->mode, mat->coo, vec->d, result->d, ctx->ring, do_fuse ? &fuse : nullptr, ctx->stream));
     // COO: products whose stored column was silently corrupted go where the reference puts them --

@@ -63,6 +63,20 @@ struct CsrPacked {
   const uint2 *pdesc;      // nblk: {cbase, (pbase / 16) << 5 | shift}; .y == 0: not packed (shift is 12..16)
   const double *pal;       // the palette pool, ABFT_PAL_ENTRIES per palette
 };
+// ... and what the SpMV may skip on a packed block (layout_plan.h, packed_fast_word, which proves it at plan time): one
+// word per row block, 0: the general path.  Bit 0: staged with unclamped code loads and unchecked gathers
+// (csr_stage_packed_fast); bits 8..11: besides, rows of that one length, summed without row pointers or clamps.
+// The word travels in a 16-byte record {cbase, descriptor's second word, fast word, 0} per block, an array of its own
+// beside pdesc (which keeps every bit): the kernels that read the word -- spmv_csr_kernel<MODE_NONE, ..., VECC = false,
+// ...> -- load the record INSTEAD of the descriptor, one scalar load as before.  A struct of its own, the LAST kernel
+// argument: a fourth pointer in CsrPacked would move XUpd's argument offsets in every instantiation.
+// (layout_plan.h, which a CPU build includes without this header, has the same three lines)
+#define ABFT_FAST_STAGE 1u
+#define ABFT_FAST_LEN_SHIFT 8u
+#define ABFT_FAST_LEN_MAX 8u
+struct CsrPackedFast {
+  const uint4 *rec;  // nblk records, or NULL: nothing packed
+};
 
 // Panel ("column-blocked") layout for matrices whose columns are scattered over
 // a vector much larger than an XCD's 4 MB L2 (random / unstructured).  Rows are
@@ -220,6 +234,9 @@ struct CooDev {
 #endif
 #ifndef ABFT_CFG_Y_NT
 #define ABFT_CFG_Y_NT 0  // spmv_csr_kernel<MODE_NONE, ..., NUPD>: the y[row] store non-temporal (profiles/r12/variants_ab.md)
+#endif
+#ifndef ABFT_PACKED_FAST_DEFAULT
+#define ABFT_PACKED_FAST_DEFAULT 1  // the predicate-free path on packed blocks proven safe (CsrPackedFast) without ABFT_HIP_PACKED_FAST: 0 off, 1 on (profiles/r15)
 #endif
 #ifndef ABFT_AHEAD_DEFAULT
 #define ABFT_AHEAD_DEFAULT 1  // run-ahead of the host-scalar loop (abft_hip.hip, spec.ahead) without ABFT_HIP_AHEAD: 0 off, 1 calc_p, 2 calc_r and calc_p -- 1: level 1 passed the rule against level 0 and the parent, level 2 did not pass it against level 1 (profiles/r12/variants_ab.md), nor with the deferred finishes (profiles/r13/bench_ab.md)
@@ -390,7 +407,7 @@ uint32_t fold_grid(uint32_t nblk, uint32_t *chunk);
 // vecc: x and y hold protected elements (abft_hip_spmv_vecc)
 hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
                            const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s,
-                           bool vecc = false, const XUpd *xu = nullptr);
+                           bool vecc = false, const XUpd *xu = nullptr, CsrPackedFast pf = CsrPackedFast{nullptr});
 hipError_t launch_spmv_coo(int mode, const CooDev &A, const double *x, double *y, EventRing ev,
                            const FuseOut *fuse, hipStream_t s);
 // behind every COO SpMV: see MovedList.  With a fused product the fix-up runs inside the fold

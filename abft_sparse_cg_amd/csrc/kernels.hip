@@ -757,6 +757,66 @@ __device__ __forceinline__ void csr_stage_packed(const CsrDev &A, const CsrPacke
   if (VECC && __builtin_expect(xbad != 0u, 0)) vecc_redo_gathers<EPT>(xbad, x, col, val, ev, s_prod);
 }
 
+// csr_stage_packed on a block whose fast word (CsrPackedFast) has the stage bit: the planner has proven that the
+// whole tile window of codes is allocated and that every 16-bit code decodes to a column inside x, so the code
+// loads are not clamped, the gathers not tested and nothing is zeroed -- no compare, no select.  The slots outside
+// [e0, e1) (the one before an odd e0, those behind e1) stage a product of whatever code lies there: finite
+// garbage or not, no row's range reads it.  Inside [e0, e1): the same v_mul_f64 of the same two operands.
+// ABFT_CFG_PACKED_PAL == 0 only (the caller falls back to csr_stage_packed otherwise).
+template <int EPT>
+__device__ __forceinline__ void csr_stage_packed_fast(const CsrPacked &cp, uint2 pd, const double *__restrict__ x,
+                                                      uint32_t base, double *s_prod) {
+  constexpr int STEPS = EPT / 2;
+  const uint32_t shift = pd.y & 31u, mask = (1u << shift) - 1u;  // uniform
+  const uint32_t pbase = (pd.y >> 5) * ABFT_PAL_ENTRIES;
+  const double pal = cp.pal[pbase + (threadIdx.x & (ABFT_PAL_ENTRIES - 1u))];
+  const int pal_lo = __double2loint(pal), pal_hi = __double2hiint(pal);
+  const double *xb = x + pd.x;  // uniform
+  uint32_t raw[STEPS];
+#pragma unroll
+  for (int s = 0; s < STEPS; s++)
+    raw[s] = STREAM_LOAD(reinterpret_cast<const uint32_t *>(cp.code16 + base + 2u * threadIdx.x + (uint32_t)s * (2u * ABFT_BLOCK)));
+  double xv[EPT], val[EPT];
+#pragma unroll
+  for (int j = 0; j < EPT; j++) {
+    const uint32_t code = (j & 1) ? raw[j >> 1] >> 16 : raw[j >> 1] & 0xFFFFu;
+    xv[j] = gather_load(xb + (code & mask));
+    const int src = (int)((code >> shift) << 2);  // byte address of the palette lane
+    val[j] = as_double((uint32_t)__builtin_amdgcn_ds_bpermute(src, pal_lo),
+                       (uint32_t)__builtin_amdgcn_ds_bpermute(src, pal_hi));
+  }
+#pragma unroll
+  for (int s = 0; s < STEPS; s++)
+    *reinterpret_cast<double2 *>(s_prod + 2u * threadIdx.x + (uint32_t)s * (2u * ABFT_BLOCK)) =
+        make_double2(val[2 * s] * xv[2 * s], val[2 * s + 1] * xv[2 * s + 1]);
+}
+
+// The row phase of a block whose fast word carries a row length: LEN products from p[0], added in ascending order
+// onto 0.0 -- the first add is kept (0.0 + a0: what turns a lone -0.0 product into +0.0 in csr_row_sum too).  All
+// reads are issued before the first add; the offsets are immediates.
+template <int LEN>
+__device__ __forceinline__ double csr_row_sum_fixed(const double *p) {
+  double a[LEN];
+#pragma unroll
+  for (int j = 0; j < LEN; j++) a[j] = p[j];
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < LEN; j++) acc += a[j];
+  return acc;
+}
+__device__ __forceinline__ double csr_row_sum_len(const double *p, uint32_t len) {  // len: uniform, 1 .. ABFT_FAST_LEN_MAX
+  switch (len) {
+    case 1: return csr_row_sum_fixed<1>(p);
+    case 2: return csr_row_sum_fixed<2>(p);
+    case 3: return csr_row_sum_fixed<3>(p);
+    case 4: return csr_row_sum_fixed<4>(p);
+    case 5: return csr_row_sum_fixed<5>(p);
+    case 6: return csr_row_sum_fixed<6>(p);
+    case 7: return csr_row_sum_fixed<7>(p);
+    default: return csr_row_sum_fixed<8>(p);
+  }
+}
+
 // Constraints mode: the reference's two checks of element i (CSR/CPUContext.cpp:186-200) on
 // the staged columns -- its column against the vector's size, then against its row successor's
 // (read from the matrix when element i is the last one staged).  Returns false if a fatal event
@@ -869,21 +929,36 @@ __device__ __forceinline__ double xupd_chain(const XUpd &xu, double xs, double p
   if (NUPD > 2) { xs = xs + xu.u[2].alpha * po2; xs = xs + xu.u[3].alpha * po3; }
   return xs;
 }
+// what a matrix without fast records reads (CsrPackedFast): not packed, nothing proven.  In global memory like the
+// records: picked against a __constant__ the address is a generic one, and the record comes through a flat load
+// into vector registers.
+__device__ uint4 k_no_record = {0u, 0u, 0u, 0u};
 template <int MODE, int EPT, bool FUSE, bool VECC = false, int NUPD = 0>
 __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const double *__restrict__ x,
                                                               double *__restrict__ y, EventRing ev,
                                                               FuseOut fuse, TileSpan span, CsrCompact cc,
-                                                              CsrPacked cp, XUpd xu) {
+                                                              CsrPacked cp, XUpd xu, CsrPackedFast pf) {
   constexpr uint32_t TILE = ABFT_BLOCK * EPT;
+  constexpr bool FASTABLE = MODE == MODE_NONE && !VECC && ABFT_CFG_PACKED_PAL == 0;  // the instantiations that read pf (and not cp.pdesc)
   __shared__ __attribute__((aligned(16))) double s_prod[TILE];
   __shared__ __attribute__((aligned(16))) uint32_t s_col[MODE == MODE_CONSTRAINTS ? TILE : 2];
   const uint32_t b = xcd_tile(blockIdx.x, span.count);
   const uint32_t t = span.first + b + (b >= span.cut ? span.skip : 0u);
+  // mode none on plain vectors: the tile's record {packed-code descriptor, fast word} (CsrPackedFast; all 0: not
+  // packed, nothing proven), uniform.  In front of the block descriptor on purpose: hipcc asks for a kernel argument
+  // where it is first used, and with this one asked for behind `desc` the record's load waited for the descriptor's --
+  // with the descriptor and the word loaded apart, as first built, three dependent round trips in front of every
+  // workgroup's codes instead of one, which ate the path's whole gain (profiles/r15).
+  // A matrix without records reads the one record of zeros below: the null test picks the address, not the value --
+  // with the value picked behind a branch, the loaded record meets the zeros at a join and hipcc waits for it there.
+  uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+  if (FASTABLE) rec = *(pf.rec ? pf.rec + t : &k_no_record);
   const uint4 desc = A.blk[t];  // one scalar load instead of two dependent pairs
   // mode none: this tile's column base (by tile, not workgroup: span cut / skip), uniform
   const uint32_t cb = (MODE == MODE_NONE && cc.cbase) ? cc.cbase[t] : ABFT_CBASE_WIDE;
   // ... and its packed-code descriptor (.y == 0: not packed), uniform as well
-  const uint2 pd = (MODE == MODE_NONE && cp.pdesc) ? cp.pdesc[t] : make_uint2(0u, 0u);
+  const uint2 pd = FASTABLE ? make_uint2(rec.x, rec.y) : (MODE == MODE_NONE && cp.pdesc) ? cp.pdesc[t] : make_uint2(0u, 0u);
+  const uint32_t fw = rec.z;
   // bit 31 of the second word: every row of this block has the same length (banded
   // matrices: nearly all blocks), so the row pointers need not be read at all
   const bool uniform = ABFT_CFG_UNIFORM_ROWS && MODE != MODE_CONSTRAINTS && (desc.y >> 31) != 0u;
@@ -891,7 +966,23 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
   const uint32_t base = e0 & ~1u;
   double dsum = 0.0;  // FUSE: this thread's share of sum x[row] * y[row]
 
-  if (e1 >= e0 && e1 - base <= TILE) {
+  if (FASTABLE && (fw >> ABFT_FAST_LEN_SHIFT) != 0u) {
+    // one packed tile of at most ABFT_BLOCK rows of `len` elements each: nothing is tested per element or per row
+    const uint32_t len = fw >> ABFT_FAST_LEN_SHIFT, row = row0 + threadIdx.x;
+    const bool mine = row < row1;
+    double xr = 0.0, xs = 0.0, po = 0.0, po1 = 0.0, po2 = 0.0, po3 = 0.0;
+    if (FUSE && mine) xr = x[fuse.x_off + row];
+    if (NUPD && mine) xupd_load<NUPD>(xu, row, xs, po, po1, po2, po3);
+    csr_stage_packed_fast<EPT>(cp, pd, x, base, s_prod);
+    __syncthreads();
+    if (mine) {
+      if (NUPD) XUPD_STORE_X(xu.xs + row, xupd_chain<NUPD>(xu, xs, po, po1, po2, po3));
+      const double acc = csr_row_sum_len(s_prod + (e0 - base) + len * threadIdx.x, len);
+      if (ABFT_CFG_Y_NT && NUPD) __builtin_nontemporal_store(acc, y + row);
+      else y[row] = acc;
+      if (FUSE) dsum += xr * acc;
+    }
+  } else if (e1 >= e0 && e1 - base <= TILE) {
     // row pointers for phase 2, requested before the tile so their latency overlaps
     const uint32_t r = row0 + threadIdx.x;
     uint32_t rs = 0, re = 0;
@@ -907,7 +998,9 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_kernel(CsrDev A, const do
     }
     double xs = 0.0, po = 0.0, po1 = 0.0, po2 = 0.0, po3 = 0.0;  // NUPD: the first row's operands, in flight beside the codes and the gathers
     if (NUPD && r < row1) xupd_load<NUPD>(xu, r, xs, po, po1, po2, po3);
-    if (MODE == MODE_NONE && pd.y != 0u)
+    if (FASTABLE && fw != 0u)  // the stage bit alone: rows of several lengths, long ones, or more rows than threads
+      csr_stage_packed_fast<EPT>(cp, pd, x, base, s_prod);
+    else if (MODE == MODE_NONE && pd.y != 0u)
       csr_stage_packed<EPT, VECC>(A, cp, pd, x, ev, base, e0, e1, s_prod);
     else if (MODE == MODE_NONE)
       csr_stage_none<EPT, VECC>(A, cc, cb, x, ev, base, e0, e1, s_prod, s_col);
@@ -1116,34 +1209,34 @@ int spmv_csr_panels_blocks_per_cu(int mode, bool fuse) {
 template <int MODE>
 static hipError_t launch_spmv_csr_mode(const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
                                        const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s,
-                                       bool vecc, const XUpd *xu) {
+                                       bool vecc, const XUpd *xu, CsrPackedFast pf) {
   if (xu && xu->n == 4)
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true, false, 4>), dim3(span.count), dim3(ABFT_BLOCK), 0,
-                       s, A, x, y, ev, *fuse, span, cc, cp, *xu);
+                       s, A, x, y, ev, *fuse, span, cc, cp, *xu, pf);
   else if (xu && xu->n == 2)
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true, false, 2>), dim3(span.count), dim3(ABFT_BLOCK), 0,
-                       s, A, x, y, ev, *fuse, span, cc, cp, *xu);
+                       s, A, x, y, ev, *fuse, span, cc, cp, *xu, pf);
   else if (xu)
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true, false, 1>), dim3(span.count), dim3(ABFT_BLOCK), 0,
-                       s, A, x, y, ev, *fuse, span, cc, cp, *xu);
+                       s, A, x, y, ev, *fuse, span, cc, cp, *xu, pf);
   else if (vecc && fuse)
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true, true>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
-                       x, y, ev, *fuse, span, cc, cp, XUpd{});
+                       x, y, ev, *fuse, span, cc, cp, XUpd{}, pf);
   else if (vecc)
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, false, true>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
-                       x, y, ev, FuseOut{}, span, cc, cp, XUpd{});
+                       x, y, ev, FuseOut{}, span, cc, cp, XUpd{}, pf);
   else if (fuse) {
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, true>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
-                       x, y, ev, *fuse, span, cc, cp, XUpd{});
+                       x, y, ev, *fuse, span, cc, cp, XUpd{}, pf);
   } else
     hipLaunchKernelGGL((spmv_csr_kernel<MODE, ABFT_CSR_EPT, false>), dim3(span.count), dim3(ABFT_BLOCK), 0, s, A,
-                       x, y, ev, FuseOut{}, span, cc, cp, XUpd{});
+                       x, y, ev, FuseOut{}, span, cc, cp, XUpd{}, pf);
   return hipGetLastError();
 }
 
 hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
                            const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s, bool vecc,
-                           const XUpd *xu) {
+                           const XUpd *xu, CsrPackedFast pf) {
   // the x update rides on a launch of every row block with the fused product, plain vectors (abft_hip.hip decides)
   if (xu) {
     if (!fuse || vecc || span.first || span.skip || span.count != A.nblk || !span.count || !xu->xs) return hipErrorInvalidValue;
@@ -1159,13 +1252,15 @@ hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, cons
   // packed codes likewise, and then all three arrays
   if ((cp.code16 || cp.pdesc || cp.pal) && (mode != MODE_NONE || !cp.code16 || !cp.pdesc || !cp.pal))
     return hipErrorInvalidValue;
+  // the records come with the packed blocks, always: on plain vectors the kernel reads them in the descriptors' stead
+  if ((pf.rec != nullptr) != (cp.pdesc != nullptr)) return hipErrorInvalidValue;
   switch (mode) {
-    case MODE_NONE: return launch_spmv_csr_mode<MODE_NONE>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu);
-    case MODE_CONSTRAINTS: return launch_spmv_csr_mode<MODE_CONSTRAINTS>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu);
-    case MODE_SED: return launch_spmv_csr_mode<MODE_SED>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu);
-    case MODE_SEC7: return launch_spmv_csr_mode<MODE_SEC7>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu);
-    case MODE_SEC8: return launch_spmv_csr_mode<MODE_SEC8>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu);
-    case MODE_SECDED: return launch_spmv_csr_mode<MODE_SECDED>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu);
+    case MODE_NONE: return launch_spmv_csr_mode<MODE_NONE>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu, pf);
+    case MODE_CONSTRAINTS: return launch_spmv_csr_mode<MODE_CONSTRAINTS>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu, pf);
+    case MODE_SED: return launch_spmv_csr_mode<MODE_SED>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu, pf);
+    case MODE_SEC7: return launch_spmv_csr_mode<MODE_SEC7>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu, pf);
+    case MODE_SEC8: return launch_spmv_csr_mode<MODE_SEC8>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu, pf);
+    case MODE_SECDED: return launch_spmv_csr_mode<MODE_SECDED>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu, pf);
     default: return hipErrorInvalidValue;
   }
 }

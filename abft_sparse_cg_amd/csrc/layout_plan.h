@@ -49,6 +49,7 @@ struct LayoutKnobs {
   std::optional<long> chunk, grid;                      // ABFT_HIP_PANEL_CHUNK / _PANEL_GRID
   long xpf = 0;                    // ABFT_HIP_PANEL_XPF
   bool compact = true, packed = true;       // ABFT_HIP_COMPACT_COLS=0 / ABFT_HIP_PACKED=0 turn them off
+  std::optional<bool> packed_fast;          // ABFT_HIP_PACKED_FAST=0|1 (unset: the caller's default, ABFT_PACKED_FAST_DEFAULT)
   bool coo_pc = false, coo_lean = false;    // ABFT_HIP_COO_PC / ABFT_HIP_COO_LEAN set and not "0"
   bool panel_debug = false, sweep_debug = false;  // ABFT_HIP_PANEL_DEBUG / ABFT_HIP_SWEEP_DEBUG set
 };
@@ -83,6 +84,7 @@ static inline LayoutKnobs read_knobs(Lookup get) {
   k.xpf = num("ABFT_HIP_PANEL_XPF").value_or(0L);
   k.compact = !off("ABFT_HIP_COMPACT_COLS");
   k.packed = !off("ABFT_HIP_PACKED");
+  if (get("ABFT_HIP_PACKED_FAST")) k.packed_fast = !off("ABFT_HIP_PACKED_FAST");
   k.coo_pc = on("ABFT_HIP_COO_PC");
   k.coo_lean = on("ABFT_HIP_COO_LEAN");
   k.panel_debug = get("ABFT_HIP_PANEL_DEBUG") != nullptr;
@@ -296,13 +298,43 @@ struct PackedBuild {
   bool any = false;
   std::vector<Pair> pdesc;      // per block {cbase, palette number << 5 | shift}; .y == 0: not packed
   std::vector<uint16_t> codes;  // padded + 2, as cols16: the kernel's loads at even indices stay inside
+  std::vector<uint32_t> fast;   // per block: packed_fast_word, or 0: the general path (all 0 with the switch off)
 };
 
+// What the SpMV may skip on a packed block, proven here so that the kernel need not test it per element
+// (0: nothing, the general path):
+//   bit 0 (stage-fast): the block is staged as one tile; cbase + 2^shift <= n_in, so EVERY 16-bit code -- valid, stale
+//     or corrupted -- decodes to a column inside the gathered vector; and the whole tile window of codes,
+//     [e0 & ~1, (e0 & ~1) + csr_tile), lies inside the `codes_len` codes allocated, so the loads need no clamp.
+//     The staged products of the slots outside [e0, e1) are then garbage, which no row's range reads.
+//   bits 8..11 (row-fast): besides, every row has the same length 1..8 (the uniform flag, at most one row per
+//     thread), kept here: thread t sums the `len` products from e0 + len * t.
+// The one place the word is computed: at create, and again for a block re-planned after an inject.
+#define ABFT_FAST_STAGE 1u
+#define ABFT_FAST_LEN_SHIFT 8u
+#define ABFT_FAST_LEN_MAX 8u
+static inline uint32_t packed_fast_word(const PlanGeometry &geo, const Blk &b, Pair pd, uint32_t n_in, size_t codes_len) {
+  const uint32_t e0 = b.z, e1 = b.w, shift = pd.y & 31u;
+  if (pd.y == 0u || !one_tile(geo, e0, e1) || shift > 16u) return 0u;
+  if ((uint64_t)pd.x + ((uint64_t)1 << shift) > (uint64_t)n_in) return 0u;
+  if ((uint64_t)(e0 & ~1u) + geo.csr_tile > (uint64_t)codes_len) return 0u;
+  uint32_t word = ABFT_FAST_STAGE;
+  const uint32_t rows = (b.y & 0x7fffffffu) - b.x;
+  if ((b.y >> 31) != 0u && rows > 0u && rows <= geo.block && (e1 - e0) % rows == 0u) {
+    const uint32_t len = (e1 - e0) / rows;
+    if (len >= 1u && len <= ABFT_FAST_LEN_MAX) word |= len << ABFT_FAST_LEN_SHIFT;
+  }
+  return word;
+}
+
 // at create: packed codes for every block that packs; the pool holds their palettes (empty if none packs)
+// (`fast`: the switch; `n_in`: entries of the gathered vector)
 static inline void plan_packed(const PlanGeometry &geo, const uint32_t *columns, const double *values,
-                               const std::vector<Blk> &blk, size_t padded, PalettePool &pool, PackedBuild &pk) {
+                               const std::vector<Blk> &blk, size_t padded, PalettePool &pool, PackedBuild &pk,
+                               bool fast = false, uint32_t n_in = 0) {
   pk.pdesc.assign(blk.size(), Pair{0u, 0u});
   pk.codes.assign(padded + 2, 0);
+  pk.fast.assign(blk.size(), 0u);
   pk.any = false;
   Palette pal;
   std::vector<uint64_t> vb;
@@ -314,6 +346,7 @@ static inline void plan_packed(const PlanGeometry &geo, const uint32_t *columns,
     uint32_t cbase, shift;
     if (!plan_packed_block(geo, e0, e1, columns + e0, vb.data(), cbase, shift, pal, pk.codes.data() + e0)) continue;
     pk.pdesc[b] = pool.desc(cbase, shift, pal);
+    if (fast) pk.fast[b] = packed_fast_word(geo, blk[b], pk.pdesc[b], n_in, pk.codes.size());
     pk.any = true;
   }
   if (pk.any) pool.seal(); else pool.clear();
@@ -628,7 +661,8 @@ static inline void plan_csr(const PlanGeometry &geo, const LayoutKnobs &knobs, b
     plan.layout = Layout::Panels;
   if (plan.layout != Layout::Stream || !mode_none) return;
   if (knobs.compact) plan_compact_cols(geo, columns, plan.blk, plan.padded, plan.compact);
-  if (knobs.packed) plan_packed(geo, columns, values, plan.blk, plan.padded, pool, plan.packed);
+  if (knobs.packed)  // (the fast words: only where the caller has set the switch; unset is off here)
+    plan_packed(geo, columns, values, plan.blk, plan.padded, pool, plan.packed, knobs.packed_fast.value_or(false), (uint32_t)n_in);
 }
 
 // ---- a whole COO matrix ------------------------------------------------------------------------------------------

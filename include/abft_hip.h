@@ -156,6 +156,11 @@ int abft_hip_matrix_compact_stats(abft_hip_matrix *mat, uint32_t *compact_tiles,
  * (cols, vals) (0 unless the copies have come apart).  Any pointer may be NULL. */
 int abft_hip_matrix_packed_stats(abft_hip_matrix *mat, uint32_t *packed_tiles, uint32_t *tiles,
                                  uint32_t *mismatches);
+/* The same layout (measurement and tests only): *packed = packed row blocks, *stage_fast = those the SpMV stages
+ * without per-element bound tests (the planner has proven every code's column inside the vector and the tile's
+ * window of codes inside the allocation), *row_fast = those of them whose equal-length rows (1..8 elements) it
+ * also sums without row pointers or clamps.  0, 0 with ABFT_HIP_PACKED_FAST=0.  Any pointer may be NULL. */
+int abft_hip_packed_stats(abft_hip_matrix *mat, uint32_t *packed, uint32_t *stage_fast, uint32_t *row_fast);
 
 /* Read back the stored (ECC-encoded) arrays in the caller's element order.
  * CSR: cols[nnz], rowptr[nrows+1], values[nnz].  Any pointer may be NULL. */
