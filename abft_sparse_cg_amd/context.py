@@ -385,6 +385,19 @@ class HIPContext:
     def calc_p_vecc(self, p, r, beta):
         check(self.L.abft_hip_calc_p_vecc(self.h, p.h, r.h, beta))
 
+    def calc_r_vecc(self, r, w, alpha):
+        """calc_xr_vecc's r half on its own: r -= alpha w on codewords -> r.r over the stored r (abft_hip_calc_r_vecc;
+        operands 0: r, 1: w).  With calc_px_vecc behind it: what calc_xr_vecc + calc_p_vecc leave, p read once"""
+        out = C.c_double()
+        check(self.L.abft_hip_calc_r_vecc(self.h, r.h, w.h, alpha, C.byref(out)))
+        self._drain_if_pending()
+        return out.value
+
+    def calc_px_vecc(self, x, p, r, alpha, beta):
+        """x += alpha p and p = r + beta p on codewords, in one pass over the old p (abft_hip_calc_px_vecc; operands
+        0: x, 1: p, 2: r)"""
+        check(self.L.abft_hip_calc_px_vecc(self.h, x.h, p.h, r.h, alpha, beta))
+
     def vecc_supported(self, mat):
         """spmv_vecc runs on CSR matrices in the streaming layout only"""
         return mat.fmt == FMT_CSR and self.matrix_info(mat)[0] == "stream"
@@ -581,6 +594,16 @@ class HIPContext:
         check(self.L.abft_hip_cg_iteration_until_dev(self.h, mat.h, vec.h, vec_offset, part, x.h, r.h, p.h, w.h,
                                                      base + 8 * rr_at, base + 8 * pw_at, base + 8 * rr_new_at,
                                                      threshold))
+
+    def cg_vecc_iteration_until_dev(self, mat, vec, x, r, p, w, scalars, rr_at, pw_at, rr_new_at, threshold,
+                                    vec_offset=0, part=capi.PART_ALL):
+        """one guarded CG iteration on protected vectors, enqueue-only (abft_hip_cg_vecc_iteration_until_dev; DESIGN.md
+        section 5k): cg_iteration_until_dev's arguments and pairs, the vectors codewords.  Vector events name their
+        operand among vec, x, r, p, w = 0 .. 4.  CSR matrices in the streaming layout only"""
+        base = scalars.device_ptr
+        check(self.L.abft_hip_cg_vecc_iteration_until_dev(self.h, mat.h, vec.h, vec_offset, part, x.h, r.h, p.h, w.h,
+                                                          base + 8 * rr_at, base + 8 * pw_at, base + 8 * rr_new_at,
+                                                          threshold))
 
     def pcg_iteration_until_dev(self, mat, vec, x, r, p, w, dinv, scalars, in_at, pw_at, out_at, threshold,
                                 vec_offset=0, part=capi.PART_ALL):
@@ -876,7 +899,7 @@ def _device_batches(ctx, max_itrs, stride, graph, rec, tail, seed, enqueue, reco
 
 
 def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
-                    stride=DEFAULT_STRIDE, graph=True, precond=None):
+                    stride=DEFAULT_STRIDE, graph=True, precond=None, vector_ecc=False):
     """cg_solve's loop (cg.cpp:87-118) with alpha, beta and the stop test on the device:
     the host looks at the scalars once per batch of `stride` iterations instead of twice per iteration.
 
@@ -900,10 +923,30 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
     stride + 1 records of four doubles {r.r, events, r.z, 0.0} -- record k at 4 k, the pair p.w behind them at
     4 (stride + 1), record `stride` seeded with {rr0, 0, rz, 0}.  Batches, the graph, the download, events, callbacks
     and the return value are as above; the stop test stays on r.r.  With precond=None the calls and the trail are
-    exactly those made without the argument."""
+    exactly those made without the argument.
+
+    vector_ecc=True makes it cg_solve(vector_ecc=True)'s loop on protected vectors: the start
+    is that loop's -- b and x encoded in place, r <- b scrubbed at once, p <- r, rr0 = dot_vecc(r, r) --, then batches
+    of ctx.cg_vecc_iteration_until_dev over the same trail of pairs as the plain loop, and x and b are scrubbed before
+    returning (x and b hold codewords then: vecc_strip what is downloaded).  The pairs are plain doubles in device
+    memory, outside any code.  Refused (ValueError, before anything runs) with precond and for a matrix
+    ctx.vecc_supported refuses.  With vector_ecc=False the calls are exactly those made without the argument."""
     stride = _whole_stride(stride)
+    if vector_ecc:
+        if precond is not None:
+            raise ValueError("vector_ecc with precond: the preconditioned kernels write unencoded vectors")
+        if not ctx.vecc_supported(A):
+            raise ValueError("vector_ecc needs a CSR matrix in the streaming layout (this one: %s)"
+                             % ("COO" if A.fmt != FMT_CSR else ctx.matrix_info(A)[0]))
+        ctx.encode_vector(b)
+        ctx.encode_vector(x)
     ctx.copy_vector(r, b)
-    if precond is None:
+    if vector_ecc:
+        ctx.scrub_vector(r)  # the one read of b: repaired in r, b itself stays as it is until the end
+        ctx.copy_vector(p, r)
+        rr = ctx.dot_vecc(r, r)
+        rec, seed = 2, [rr]
+    elif precond is None:
         ctx.copy_vector(p, r)
         rr = ctx.dot(r, r)
         rec, seed = 2, [rr]  # doubles per record of the trail: the pair {r.r, events}
@@ -912,12 +955,12 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
         rec, seed = 4, [rr, 0.0, rz]  # {r.r, events, r.z, 0.0}
     noted = {}
     note_threshold(rr, conv_threshold, noted)
-    if max_itrs == 0 or not (rr > conv_threshold):
-        return 0, rr
-    last_rr = [rr]
+    done, last_rr = 0, [rr]
 
     def enqueue(trail, k, pw_at):
-        if precond is None:
+        if vector_ecc:
+            ctx.cg_vecc_iteration_until_dev(A, p, x, r, p, w, trail, 2 * k, pw_at, 2 * k + 2, conv_threshold)
+        elif precond is None:
             ctx.cg_iteration_until_dev(A, p, x, r, p, w, trail, 2 * k, pw_at, 2 * k + 2, conv_threshold)
         else:
             ctx.pcg_iteration_until_dev(A, p, x, r, p, w, precond, trail, 4 * k, pw_at, 4 * k + 4, conv_threshold)
@@ -931,7 +974,11 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
             on_iteration(done, last_rr[0])
         return True
 
-    done = _device_batches(ctx, max_itrs, stride, graph, rec, 2, seed, enqueue, record)
+    if max_itrs != 0 and rr > conv_threshold:
+        done = _device_batches(ctx, max_itrs, stride, graph, rec, 2, seed, enqueue, record)
+    if vector_ecc:
+        ctx.scrub_vector(x)
+        ctx.scrub_vector(b)
     return done, last_rr[0]
 
 

@@ -231,12 +231,12 @@ static int flush_deferred(abft_hip_ctx *ctx) {
 //                                  matrix_compact_stats, matrix_packed_stats, matrix_destroy, matrix_read_csr, _read_coo,
 //                                  _read_element, inject, inject_rowptr, vector_create, vector_map, vector_device_ptr,
 //                                  dot_dev, calc_xr_dev, calc_xr_ratio_dev, peer_exchange_begin, cg_iteration_until_dev,
-//                                  pcg_iteration_until_dev, block_loop_reserve, graph_begin, drain_events, profile_*,
+//                                  pcg_iteration_until_dev, cg_vecc_iteration_until_dev, block_loop_reserve, graph_begin, drain_events, profile_*,
 //                                  stream_probe
 //   FORGET_FUSED                   vector_unmap, vector_copy, graph_launch
 //   FORGET_ITER                    dot_vecc
 //   OTHER_VECTORS                  vector_destroy, matrix_diag_inverse, vector_flip, vector_encode, vector_scrub,
-//    (= FORGET_FUSED | FORGET_ITER)  calc_xr_vecc, calc_p_vecc, spmm, dot_block, calc_xr_block, calc_p_block, copy_block,
+//    (= FORGET_FUSED | FORGET_ITER)  calc_xr_vecc, calc_p_vecc, calc_r_vecc, calc_px_vecc, spmm, dot_block, calc_xr_block, calc_p_block, copy_block,
 //                                  residual_gap, residual_restart, residual_gap_block, residual_restart_block,
 //                                  spmm_dot, calc_r[_precond]_block, calc_px[_precond]_block, precond_start[_block],
 //                                  calc_xr_precond[_block], calc_p_precond_block, cg_block_iteration_until_dev
@@ -2763,6 +2763,36 @@ extern "C" int abft_hip_calc_p_vecc(abft_hip_ctx *ctx, abft_hip_vector *p, const
   return ABFT_OK;
 }
 
+// calc_xr_vecc's r half on its own: r -= alpha w (operands 0: r, 1: w), *rr = r.r over the stored r.  With
+// abft_hip_calc_px_vecc behind it the pair leaves what calc_xr_vecc + calc_p_vecc leave, p read once (kernels.hip,
+// calc_r_vecc_walk).
+extern "C" int abft_hip_calc_r_vecc(abft_hip_ctx *ctx, abft_hip_vector *r, const abft_hip_vector *w, double alpha,
+                                    double *rr) {
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
+  if (!rr) return set_err(ABFT_ERR_INVALID, "calc_r_vecc: null result");
+  if (int rc = check_same(r, w, "calc_r_vecc")) return rc;
+  if (!disjoint(r, w)) return set_err(ABFT_ERR_INVALID, "calc_r_vecc: r and w overlap");
+  const ReduceOut o = reduce_out(ctx, nullptr, true);
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_r_vecc(r->d, w->d, alpha, r->n, o, ctx->ring, ctx->stream));
+  }
+  return scalar_from_host_slot(ctx, o.seq, rr);
+}
+
+// x += alpha p and p = r + beta p in one pass, both from the old p (operands 0: x, 1: p, 2: r; r is not written back)
+extern "C" int abft_hip_calc_px_vecc(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *p, const abft_hip_vector *r,
+                                     double alpha, double beta) {
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
+  if (int rc = check_same(x, p, "calc_px_vecc")) return rc;
+  if (int rc = check_same(x, r, "calc_px_vecc")) return rc;
+  if (!disjoint(x, p) || !disjoint(x, r) || !disjoint(p, r))
+    return set_err(ABFT_ERR_INVALID, "calc_px_vecc: x, p and r overlap");
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_px_vecc(x->d, p->d, r->d, alpha, beta, x->n, ctx->ring, ctx->stream));
+  return ABFT_OK;
+}
+
 // the vectors of a single check: x has the matrix's input length, the others its output length, the
 // scratch overlaps none of them; `out1` / `out2` (restart: r, p) overlap nothing else either
 static int check_residual_args(const char *what, abft_hip_matrix *A, const abft_hip_vector *b, const abft_hip_vector *x,
@@ -3520,6 +3550,43 @@ extern "C" int abft_hip_pcg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matr
   }
   KernelTimer t(ctx, ABFT_K_CALC_P);
   HIPCHK(launch_calc_px_precond_until(p->d, r->d, dinv->d, x->d, dev_in, dev_out, threshold, ctx->alpha_dev, n, ctx->stream));
+  return ABFT_OK;
+}
+
+// ---- the guarded iteration on protected vectors ----------------
+// spmv_vecc(A, vec, w) + p.w, then r -= alpha w, r.r, x += alpha p, p = r + beta p on codewords, behind the same stop
+// test, with the pairs {r.r, events} and {p.w, events} as abft_hip_cg_iteration_until_dev keeps them.  Always three
+// kernels behind the SpMV (fold, guarded r half, guarded x / p half; kernels.hip, calc_r_vecc_until_kernel): live, the
+// bits abft_hip_spmv_vecc + abft_hip_dot_vecc (served from the fused product) + abft_hip_calc_r_vecc +
+// abft_hip_calc_px_vecc leave.  Vector events count vec, x, r, p, w as operands 0..4.  Nothing is left pending,
+// abft_hip_tail_stats is not touched, and every buffer it uses exists from abft_hip_init on: it can be captured on
+// a fresh context.
+extern "C" int abft_hip_cg_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                                    int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                                    abft_hip_vector *p, abft_hip_vector *w, const double *dev_rr,
+                                                    double *dev_pw, double *dev_rr_new, double threshold) {
+  const char *what = "cg_vecc_iteration_until";
+  if (int rc = enter(ctx, 0)) return rc;  // a pending x update applied, a speculation voided
+  if (int rc = check_guarded_iteration(ctx, what, mat, vec, vec_offset, part, x, r, p, w, false, nullptr, dev_rr, dev_pw,
+                                       dev_rr_new))
+    return rc;
+  // what spmv_vecc refuses, refused here under this entry's name: spmv_common would forget the learned iteration first,
+  // and a refused call leaves the state alone
+  if (const char *layout = mat->fmt != ABFT_FMT_CSR ? "COO" : mat->streams() ? nullptr : layout_name(mat->layout))
+    return set_err(ABFT_ERR_INVALID, "%s: a matrix in the %s layout (protected vectors run on CSR matrices in the "
+                   "streaming layout only)", what, layout);
+  const int n = x->n;
+  HeldFold hold;
+  if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold, /*vecc=*/true)) return rc;
+  if (int rc = finish_held_fold(ctx, hold)) return rc;
+  const ReduceOut o = reduce_out(ctx, dev_rr_new, false);
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_r_vecc_until(r->d, w->d, dev_rr, dev_pw, threshold, ctx->alpha_dev, n, o, ctx->ring, ctx->stream));
+  }
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_px_vecc_until(x->d, p->d, r->d, dev_rr, dev_rr_new, threshold, ctx->alpha_dev, n, ctx->ring,
+                                   ctx->stream));
   return ABFT_OK;
 }
 

@@ -560,6 +560,17 @@ hipError_t launch_dot_vecc(const double *a, const double *b, int n, const Reduce
 hipError_t launch_calc_xr_vecc(double *x, double *r, const double *p, const double *w, double alpha, int n,
                                const ReduceOut &out, EventRing ev, hipStream_t s);
 hipError_t launch_calc_p_vecc(double *p, const double *r, double beta, int n, EventRing ev, hipStream_t s);
+// the two-kernel tail on protected vectors: calc_xr_vecc's r half, and its x half inside
+// calc_p_vecc's pass over p; each chooses its walk by the alignment of its own operands
+hipError_t launch_calc_r_vecc(double *r, const double *w, double alpha, int n, const ReduceOut &out, EventRing ev,
+                              hipStream_t s);
+hipError_t launch_calc_px_vecc(double *x, double *p, const double *r, double alpha, double beta, int n, EventRing ev,
+                               hipStream_t s);
+// their guarded forms (abft_hip_cg_vecc_iteration_until_dev): launch_calc_r_until's / launch_calc_px_until's protocol
+hipError_t launch_calc_r_vecc_until(double *r, const double *w, const double *rr, const double *pw, double threshold,
+                                    double *alpha_out, int n, const ReduceOut &out, EventRing ev, hipStream_t s);
+hipError_t launch_calc_px_vecc_until(double *x, double *p, const double *r, const double *rr, const double *rr_new,
+                                     double threshold, const double *alpha_ptr, int n, EventRing ev, hipStream_t s);
 // {gap2, tt2} = {sum ((b - y) - r)^2, sum (b - y)^2} through the K-wide slot (values 0, 1)
 hipError_t launch_residual_gap(const double *b, const double *y, const double *r, int n, const ReduceOutK &out,
                                hipStream_t s);

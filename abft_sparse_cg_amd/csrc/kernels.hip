@@ -6349,3 +6349,225 @@ hipError_t launch_calc_p_vecc(double *p, const double *r, double beta, int n, Ev
     hipLaunchKernelGGL(calc_p_vecc_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, n, ev);
   return hipGetLastError();
 }
+
+// ---- the two-kernel tail on protected vectors (abft_hip_calc_r_vecc, abft_hip_calc_px_vecc) and the guarded
+// iteration built on it (abft_hip_cg_vecc_iteration_until_dev) ----
+// calc_xr_vecc_kernel cut where calc_r_kernel / calc_px_kernel cut calc_xr_kernel: the r half alone, and the x half
+// moved into calc_p's pass over p, so that p is read once per iteration.  Same discipline as above -- no call in
+// the hot loops, a step with a suspect word only noted, the chain walked once more behind the loop -- and per element
+// the same operands and roundings, per thread the same order of adds: with the walk chosen alike (VEC, by the
+// alignment of the operands) x, r and r.r have calc_xr_vecc's bits and p has calc_p_vecc's.
+// ONE body per pair (section 5i): the host-scalar kernel and the guarded one call the same walk.  op_*: the ordinal
+// a repaired word of that vector is reported under -- the host-scalar entries count their own arguments, the guarded
+// entry counts vec, x, r, p, w as 0..4.
+
+// r <- enc(dec(r) - alpha dec(w)) over the grid -> this thread's serial sum of the stored r's squares; w is not written back
+template <int VEC>
+__device__ __forceinline__ double calc_r_vecc_walk(double *__restrict__ r, const double *__restrict__ w, double alpha,
+                                                   int n, uint32_t op_r, uint32_t op_w, EventRing ev) {
+  double acc = 0.0;
+  uint32_t bad = 0u;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
+  for (long i = first; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const double2 wv = *reinterpret_cast<const double2 *>(w + i);
+      const uint64_t r0 = vecc_bits(rv.x), r1 = vecc_bits(rv.y), w0 = vecc_bits(wv.x), w1 = vecc_bits(wv.y);
+      const uint32_t sus = (vecc_suspect(r0) | vecc_suspect(r1)) | (vecc_suspect(w0) | vecc_suspect(w1));
+      bad |= sus;
+      if (!sus) {
+        const uint64_t rs0 = vecc_encode(vecc_value(r0) - alpha * vecc_value(w0));
+        const uint64_t rs1 = vecc_encode(vecc_value(r1) - alpha * vecc_value(w1));
+        *reinterpret_cast<double2 *>(r + i) = make_double2(vecc_double(rs0), vecc_double(rs1));
+        acc += vecc_value(rs0) * vecc_value(rs0);
+        acc += vecc_value(rs1) * vecc_value(rs1);
+      }
+    } else {
+      const uint64_t r0 = vecc_bits(r[i]), w0 = vecc_bits(w[i]);
+      const uint32_t sus = vecc_suspect(r0) | vecc_suspect(w0);
+      bad |= sus;
+      if (!sus) {
+        const uint64_t rs = vecc_encode(vecc_value(r0) - alpha * vecc_value(w0));
+        r[i] = vecc_double(rs);
+        acc += vecc_value(rs) * vecc_value(rs);
+      }
+    }
+  }
+  if (__builtin_expect(bad != 0u, 0)) {
+    acc = 0.0;
+    for (long i = first; i < n; i += stride) {
+      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
+      uint32_t sus = 0u;
+      for (int k = 0; k < m; k++) sus |= vecc_suspect(vecc_bits(r[i + k])) | vecc_suspect(vecc_bits(w[i + k]));
+      for (int k = 0; k < m; k++) {
+        uint64_t rs = vecc_bits(r[i + k]);  // a step carried out above: what it stored
+        if (sus) {
+          const uint32_t j = (uint32_t)(i + k);
+          const double ro = vecc_decode_cold_ok(r + i + k, j, op_r, ev);
+          const double wo = vecc_decode_cold_ok(w + i + k, j, op_w, ev);
+          rs = vecc_encode(ro - alpha * wo);
+          r[i + k] = vecc_double(rs);
+        }
+        acc += vecc_value(rs) * vecc_value(rs);
+      }
+    }
+  }
+  return acc;
+}
+
+// x <- enc(dec(x) + alpha dec(p)) and p <- enc(dec(r) + beta dec(p)) in one pass over p, both from the old p;
+// r is not written back
+template <int VEC>
+__device__ __forceinline__ void calc_px_vecc_walk(double *__restrict__ x, double *__restrict__ p,
+                                                  const double *__restrict__ r, double alpha, double beta, int n,
+                                                  uint32_t op_x, uint32_t op_p, uint32_t op_r, EventRing ev) {
+  uint32_t bad = 0u;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
+  for (long i = first; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      const double2 pv = *reinterpret_cast<const double2 *>(p + i);
+      const double2 xv = *reinterpret_cast<const double2 *>(x + i);
+      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const uint64_t p0 = vecc_bits(pv.x), p1 = vecc_bits(pv.y), x0 = vecc_bits(xv.x), x1 = vecc_bits(xv.y);
+      const uint64_t r0 = vecc_bits(rv.x), r1 = vecc_bits(rv.y);
+      const uint32_t sus = (vecc_suspect(p0) | vecc_suspect(p1)) | (vecc_suspect(x0) | vecc_suspect(x1)) |
+                           (vecc_suspect(r0) | vecc_suspect(r1));
+      bad |= sus;
+      if (!sus) {
+        const uint64_t xs0 = vecc_encode(vecc_value(x0) + alpha * vecc_value(p0));
+        const uint64_t xs1 = vecc_encode(vecc_value(x1) + alpha * vecc_value(p1));
+        const uint64_t q0 = vecc_encode(vecc_value(r0) + beta * vecc_value(p0));
+        const uint64_t q1 = vecc_encode(vecc_value(r1) + beta * vecc_value(p1));
+        *reinterpret_cast<double2 *>(x + i) = make_double2(vecc_double(xs0), vecc_double(xs1));
+        *reinterpret_cast<double2 *>(p + i) = make_double2(vecc_double(q0), vecc_double(q1));
+      }
+    } else {
+      const uint64_t p0 = vecc_bits(p[i]), x0 = vecc_bits(x[i]), r0 = vecc_bits(r[i]);
+      const uint32_t sus = vecc_suspect(p0) | vecc_suspect(x0) | vecc_suspect(r0);
+      bad |= sus;
+      if (!sus) {
+        x[i] = vecc_double(vecc_encode(vecc_value(x0) + alpha * vecc_value(p0)));
+        p[i] = vecc_double(vecc_encode(vecc_value(r0) + beta * vecc_value(p0)));
+      }
+    }
+  }
+  if (__builtin_expect(bad != 0u, 0)) {
+    for (long i = first; i < n; i += stride) {
+      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
+      uint32_t sus = 0u;
+      for (int k = 0; k < m; k++)
+        sus |= vecc_suspect(vecc_bits(p[i + k])) | vecc_suspect(vecc_bits(x[i + k])) | vecc_suspect(vecc_bits(r[i + k]));
+      if (!sus) continue;  // carried out above
+      for (int k = 0; k < m; k++) {
+        const uint32_t j = (uint32_t)(i + k);
+        const double xo = vecc_decode_cold_ok(x + i + k, j, op_x, ev);
+        const double po = vecc_decode_cold_ok(p + i + k, j, op_p, ev);
+        const double ro = vecc_decode_cold_ok(r + i + k, j, op_r, ev);
+        x[i + k] = vecc_double(vecc_encode(xo + alpha * po));
+        p[i + k] = vecc_double(vecc_encode(ro + beta * po));
+      }
+    }
+  }
+}
+
+// calc_r on protected vectors: r -= alpha w (operands 0: r, 1: w); r.r over the r it stores
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_vecc_kernel(double *__restrict__ r, const double *__restrict__ w,
+                                                                 double alpha, int n, ReduceOut out, EventRing ev) {
+  __shared__ double s_w[4];
+  double acc = calc_r_vecc_walk<VEC>(r, w, alpha, n, 0u, 1u, ev);
+  acc = block_sum(acc, s_w);
+  reduce_finish(acc, out, s_w);
+}
+
+// calc_px on protected vectors: x += alpha p; p = r + beta p (operands 0: x, 1: p, 2: r)
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_vecc_kernel(double *__restrict__ x, double *__restrict__ p,
+                                                                  const double *__restrict__ r, double alpha,
+                                                                  double beta, int n, EventRing ev) {
+  calc_px_vecc_walk<VEC>(x, p, r, alpha, beta, n, 0u, 1u, 2u, ev);
+}
+
+// The guarded forms: calc_r_until_kernel's and calc_px_until_kernel's protocol, word for word, in front of the
+// protected walks.  Operands as the guarded entry counts them: x 1, r 2, p 3, w 4 (0 is the SpMV's gathered vector).
+// A frozen launch touches no vector: it repairs nothing and reports nothing.
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_vecc_until_kernel(double *__restrict__ r,
+                                                                       const double *__restrict__ w, const double *rr,
+                                                                       const double *pw, double threshold,
+                                                                       double *alpha_out, int n, ReduceOut out,
+                                                                       EventRing ev) {
+  __shared__ double s_w[4];
+  if (!(*rr > threshold)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      // the bits, whatever they are (a NaN's payload included): moved as an integer
+      *reinterpret_cast<unsigned long long *>(out.dev_out) = *reinterpret_cast<const unsigned long long *>(rr);
+      out.dev_out[1] = (double)__hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return;
+  }
+  const double alpha = *rr / *pw;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;  // for the x half
+  double acc = calc_r_vecc_walk<VEC>(r, w, alpha, n, 2u, 4u, ev);
+  acc = block_sum(acc, s_w);
+  reduce_finish(acc, out, s_w);
+}
+
+// (rr: the pair the iteration started from -- the guard, and beta's denominator; rr_new: what the r half left)
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_vecc_until_kernel(double *__restrict__ x, double *__restrict__ p,
+                                                                        const double *__restrict__ r, const double *rr,
+                                                                        const double *rr_new, double threshold,
+                                                                        const double *alpha_ptr, int n, EventRing ev) {
+  const double rr0 = *rr;
+  if (!(rr0 > threshold)) return;
+  const double beta = *rr_new / rr0;
+  const double alpha = *alpha_ptr;
+  calc_px_vecc_walk<VEC>(x, p, r, alpha, beta, n, 1u, 3u, 2u, ev);
+}
+
+// (each half chooses its walk over its own operands, in the host-scalar and in the guarded form alike: a live guarded
+// iteration has the bits of the two host-scalar calls whatever the alignment of the vectors it does not touch)
+hipError_t launch_calc_r_vecc(double *r, const double *w, double alpha, int n, const ReduceOut &out, EventRing ev,
+                              hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  if (aligned16(r, w))
+    hipLaunchKernelGGL(calc_r_vecc_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, alpha, n, out, ev);
+  else
+    hipLaunchKernelGGL(calc_r_vecc_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, alpha, n, out, ev);
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_px_vecc(double *x, double *p, const double *r, double alpha, double beta, int n, EventRing ev,
+                               hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+  if (aligned16(x, p, r))
+    hipLaunchKernelGGL(calc_px_vecc_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, alpha, beta, n, ev);
+  else
+    hipLaunchKernelGGL(calc_px_vecc_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, alpha, beta, n, ev);
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_r_vecc_until(double *r, const double *w, const double *rr, const double *pw, double threshold,
+                                    double *alpha_out, int n, const ReduceOut &out, EventRing ev, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  if (aligned16(r, w))
+    hipLaunchKernelGGL(calc_r_vecc_until_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, rr, pw, threshold, alpha_out, n, out, ev);
+  else
+    hipLaunchKernelGGL(calc_r_vecc_until_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, rr, pw, threshold, alpha_out, n, out, ev);
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_px_vecc_until(double *x, double *p, const double *r, const double *rr, const double *rr_new,
+                                     double threshold, const double *alpha_ptr, int n, EventRing ev, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+  if (aligned16(x, p, r))
+    hipLaunchKernelGGL(calc_px_vecc_until_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, rr, rr_new, threshold, alpha_ptr, n, ev);
+  else
+    hipLaunchKernelGGL(calc_px_vecc_until_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, rr, rr_new, threshold, alpha_ptr, n, ev);
+  return hipGetLastError();
+}

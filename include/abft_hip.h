@@ -343,6 +343,20 @@ int abft_hip_calc_xr_vecc(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector
                           const abft_hip_vector *w, double alpha, double *rr);
 /* p = r + beta p (operands 0, 1); p may not overlap r */
 int abft_hip_calc_p_vecc(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r, double beta);
+/* The same two updates as two kernels that read p once (the cut abft_hip_calc_xr / _calc_p's deferred x update
+ * makes on plain vectors, as calls of their own):
+ *   rr_new = calc_r_vecc(r, w, alpha);  calc_px_vecc(x, p, r, alpha, rr_new / rr)
+ * For the same alpha and beta x, r and *rr are bit for bit what abft_hip_calc_xr_vecc leaves and returns and p what
+ * abft_hip_calc_p_vecc leaves, where both walk alike: each call chooses its walk (pairs or single elements) by the
+ * 16-byte alignment of ITS operands, so vectors that are all whole, or all views at an odd offset, always agree.
+ * Both start like abft_hip_calc_xr_vecc (the prologue, the learned iteration and the fused product forgotten) and
+ * check every length and overlap before anything is enqueued.
+ * r -= alpha w (operands 0: r, 1: w; w is not written back); *rr = abft_hip_dot_vecc(r, r) of the r it leaves */
+int abft_hip_calc_r_vecc(abft_hip_ctx *ctx, abft_hip_vector *r, const abft_hip_vector *w, double alpha, double *rr);
+/* x += alpha p; p = r + beta p, both from the p the call finds (operands 0: x, 1: p, 2: r; r is not written back).
+ * No two of x, p, r may overlap. */
+int abft_hip_calc_px_vecc(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *p, const abft_hip_vector *r,
+                          double alpha, double beta);
 
 /* ---- Jacobi (diagonal) preconditioning ------------------------------------
  * M^-1 = diag(dinv) is one more N-vector; z = dinv * r is one rounded product formed
@@ -733,6 +747,29 @@ int abft_hip_pcg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, co
                                      int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
                                      abft_hip_vector *p, abft_hip_vector *w, const abft_hip_vector *dinv,
                                      const double *dev_in, double *dev_pw, double *dev_out, double threshold);
+
+/* The guarded iteration on PROTECTED vectors (the *_vecc entries above): x, r, p, w and vec hold codewords; the scalar
+ * pairs are plain doubles in device memory, outside any code, as abft_hip_cg_iteration_until_dev keeps them.
+ *   LIVE   when dev_rr[0] > threshold (false for NaN): bit for bit -- x, r, p, w, both pairs -- what
+ *          abft_hip_spmv_vecc(A, vec, w), abft_hip_dot_vecc(p, w) served from its fused product,
+ *          abft_hip_calc_r_vecc(r, w, rr / pw) and abft_hip_calc_px_vecc(x, p, r, rr / pw, rr_new / rr) leave, the
+ *          quotients formed on the device.
+ *   FROZEN otherwise: x, r and p keep every bit -- a word with a flipped bit included: a frozen launch of the two
+ *          vector kernels repairs nothing and reports nothing --; dev_rr_new[0] gets the bits of dev_rr[0] (moved as
+ *          an integer), dev_rr_new[1] the queued-event count; w and dev_pw are unspecified.  The SpMV still runs,
+ *          with its matrix checks, its gather checks on vec and their events.  Replaying changes nothing.
+ * Vector events (ABFT_EV_VEC_CORRECTED, ABFT_EV_VEC_DOUBLE) name their operand by its place among this entry's vector
+ * arguments vec, x, r, p, w = 0 .. 4: the SpMV reports the gathered vector as 0, the r half r as 2 and w as 4, the
+ * x / p half x as 1, r as 2 and p as 3.
+ * Always three kernels behind the SpMV (the fold of the fused product, the guarded r half, the guarded x / p half);
+ * enqueue-only and capturable -- every buffer it uses exists from abft_hip_init on, so also on a fresh context --;
+ * starts like abft_hip_cg_iteration_until_dev and leaves nothing pending; abft_hip_tail_stats is left as it was.
+ * Refused before anything is enqueued: everything abft_hip_cg_iteration_until_dev refuses, a COO matrix, and every
+ * CSR layout abft_hip_spmv_vecc refuses (the message names the layout). */
+int abft_hip_cg_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                         int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                         abft_hip_vector *p, abft_hip_vector *w, const double *dev_rr,
+                                         double *dev_pw, double *dev_rr_new, double threshold);
 
 /* The guarded iteration for k right-hand sides (block vectors, 1 <= k <= ABFT_MAX_RHS): one iteration of the fused
  * block loop -- W = A P with the k products P . W, then per column r -= alpha w, x += alpha p, p = r + beta p (with

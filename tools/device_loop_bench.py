@@ -21,6 +21,13 @@ per-column counts of the two loops are asserted equal.  Matrices by default lapl
 laplace5:1000,1000; times are per iteration of all K columns.  --out defaults to
 profiles/device_loop_bench_block.json there.  Without --rhs nothing changes.
 
+--vector-ecc measures the loops on protected vectors instead: cg_solve(vector_ecc=True) and
+cg_solve_device(vector_ecc=True) alternating on the same matrix (streaming layout), in every mode of --modes (default
+none,secded).  Matrices by default laplace5:3162,3162 and laplace5:1000,1000.  The yardstick is
+cg_solve(vector_ecc=True) of the same build; both loops pay the same start (two encodes, a scrub) and end (two
+scrubs) inside the timed window.  --out defaults to profiles/device_loop_bench_vecc.json there.  Without the flag
+nothing changes.
+
 Also reported per matrix: `best_stride`, the smallest stride within 2 % of the best device-loop time (what
 DEFAULT_STRIDE is to be on the 1 M-row matrix), and `frozen_spmv_worst`, stride - 1: the SpMVs a solve can waste
 behind convergence.
@@ -48,16 +55,18 @@ STRIDES = (4, 8, 16, 32)
 THRESHOLD = 1e-300
 
 
-def timed_solve(ctx, A, vecs, n, its, stride, dinv=None):
-    """stride 0: the host loop; dinv: the preconditioned loops -> (ms, iterations run)"""
+def timed_solve(ctx, A, vecs, n, its, stride, dinv=None, vecc=False):
+    """stride 0: the host loop; dinv: the preconditioned loops; vecc: the loops on protected vectors
+    -> (ms, iterations run)"""
+    kw = {"vector_ecc": True} if vecc else {}
     ctx.upload(vecs[1], np.zeros(n))
     ctx.synchronize()
     t0 = time.perf_counter()
     if stride:
         itr, _ = amd.cg_solve_device(ctx, A, *vecs, max_itrs=its, conv_threshold=THRESHOLD, stride=stride,
-                                     precond=dinv)
+                                     precond=dinv, **kw)
     else:
-        itr, _ = amd.cg_solve(ctx, A, *vecs, max_itrs=its, conv_threshold=THRESHOLD, precond=dinv)
+        itr, _ = amd.cg_solve(ctx, A, *vecs, max_itrs=its, conv_threshold=THRESHOLD, precond=dinv, **kw)
     ctx.synchronize()
     return (time.perf_counter() - t0) * 1e3, itr
 
@@ -124,6 +133,47 @@ def block_main(a, res):
         del cols, rows, vals
 
 
+VECC_SPECS = ("laplace5:3162,3162", "laplace5:1000,1000")
+
+
+def vecc_main(a, res):
+    """--vector-ecc: the loops on protected vectors, one row per (matrix, mode)"""
+    strides = [int(s) for s in (a.strides or ",".join(str(s) for s in STRIDES)).split(",")]
+    res["vector_ecc"] = True
+    res["modes"] = a.modes.split(",")
+    for spec in (a.specs or ";".join(VECC_SPECS)).split(";"):
+        cols, rows, vals, n = generators.generate(spec)
+        nnz = len(vals)
+        for mode in res["modes"]:
+            ctx = amd.HIPContext(mode, "csr", on_event=lambda ev, fatal: None)
+            A = ctx.create_matrix(cols, rows, vals, n, nnz, layout="stream")
+            vecs = [ctx.create_vector(n) for _ in range(5)]
+            ctx.upload(vecs[0], generators.reference_rhs(n))
+            kinds = [0] + strides
+            for k in kinds:  # warm-up: first launches, the graph's instantiation path
+                timed_solve(ctx, A, vecs, n, max(k, 5), k, vecc=True)
+            per = {k: [] for k in kinds}
+            for _ in range(a.blocks):
+                for k in kinds:
+                    ms, itr = timed_solve(ctx, A, vecs, n, a.iters, k, vecc=True)
+                    assert itr == a.iters, (spec, mode, k, itr)  # every iteration live in both loops
+                    per[k].append(ms / a.iters)
+            host = statistics.median(per[0])
+            dev = {k: statistics.median(per[k]) for k in strides}
+            best = min(dev.values())
+            row = dict(spec=spec, fmt="csr", mode=mode, layout=ctx.matrix_info(A)[0], vector_ecc=True, n=n, nnz=nnz,
+                       ms_per_iter_host_vecc=host,
+                       ms_per_iter_device_vecc={str(k): v for k, v in dev.items()},
+                       ratio_device_over_host={str(k): v / host for k, v in dev.items()},
+                       best_stride=min(k for k in strides if dev[k] <= 1.02 * best),
+                       frozen_spmv_worst={str(k): k - 1 for k in strides},
+                       blocks={str(k): v for k, v in per.items()})
+            res["rows"].append(row)
+            print(json.dumps(row), flush=True)
+            ctx.close()
+        del cols, rows, vals
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -133,14 +183,24 @@ def main():
     ap.add_argument("--strides", default=None)
     ap.add_argument("--precond", choices=("none", "jacobi"), default="none")
     ap.add_argument("--rhs", default=None, help="K[,K...]: the block loops with K right-hand sides")
-    ap.add_argument("--modes", default="none,secded", help="with --rhs: the ECC modes")
+    ap.add_argument("--modes", default="none,secded", help="with --rhs or --vector-ecc: the ECC modes")
+    ap.add_argument("--vector-ecc", action="store_true", help="the loops on protected vectors")
     a = ap.parse_args()
+    if a.vector_ecc and (a.rhs or a.precond != "none"):
+        ap.error("--vector-ecc goes with neither --rhs nor --precond")
     argv = [v for i, v in enumerate(sys.argv) if v != "--out" and (i == 0 or sys.argv[i - 1] != "--out")]
     res = {"cmd": " ".join(argv), "iters": a.iters, "blocks": a.blocks, "threshold": THRESHOLD,
            "precond": a.precond, "rows": []}
     if a.rhs:
         a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_block.json")
         block_main(a, res)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        return 0
+    if a.vector_ecc:
+        a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_vecc.json")
+        vecc_main(a, res)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
