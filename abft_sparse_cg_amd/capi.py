@@ -95,6 +95,9 @@ SIGNATURES = {
     "abft_hip_calc_p_vecc": (C.c_int, [vp, vp, vp, C.c_double]),
     "abft_hip_calc_r_vecc": (C.c_int, [vp, vp, vp, C.c_double, f64p]),
     "abft_hip_calc_px_vecc": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_double]),
+    "abft_hip_precond_start_vecc": (C.c_int, [vp, vp, vp, vp, f64p]),
+    "abft_hip_calc_r_precond_vecc": (C.c_int, [vp, vp, vp, vp, C.c_double, f64p]),
+    "abft_hip_calc_px_precond_vecc": (C.c_int, [vp, vp, vp, vp, vp, C.c_double, C.c_double]),
     "abft_hip_residual_gap": (C.c_int, [vp, vp, vp, vp, vp, vp, f64p]),
     "abft_hip_residual_restart": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, f64p]),
     "abft_hip_residual_gap_block": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, f64p]),
@@ -131,6 +134,8 @@ SIGNATURES = {
     "abft_hip_cg_iteration_until_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double]),
     "abft_hip_cg_vecc_iteration_until_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
                                                       C.c_double]),
+    "abft_hip_pcg_vecc_iteration_until_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                       C.c_double]),
     "abft_hip_pcg_iteration_until_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
                                                    C.c_double]),
     "abft_hip_cg_block_iteration_until_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_double]),

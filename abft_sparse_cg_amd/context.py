@@ -398,15 +398,39 @@ class HIPContext:
         0: x, 1: p, 2: r)"""
         check(self.L.abft_hip_calc_px_vecc(self.h, x.h, p.h, r.h, alpha, beta))
 
+    def precond_start_vecc(self, r, dinv, p):
+        """p = enc(z), z = val(dinv) * val(r), on codewords -- dinv's too: ctx.jacobi(A, protected=True) --
+        -> (r . z, r . r), the second the bits dot_vecc(r, r) gives (abft_hip_precond_start_vecc; operands 0: r,
+        1: dinv, 2: p).  A repaired dinv word is stored back: dinv outlives the iteration"""
+        out = np.zeros(2)
+        check(self.L.abft_hip_precond_start_vecc(self.h, r.h, dinv.h, p.h, out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return float(out[0]), float(out[1])
+
+    def calc_r_precond_vecc(self, r, w, dinv, alpha):
+        """r -= alpha w on codewords -> (r . z, r . r) over the stored r, z = val(dinv) * r
+        (abft_hip_calc_r_precond_vecc; operands 0: r, 1: w, 2: dinv)"""
+        out = np.zeros(2)
+        check(self.L.abft_hip_calc_r_precond_vecc(self.h, r.h, w.h, dinv.h, alpha, out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return float(out[0]), float(out[1])
+
+    def calc_px_precond_vecc(self, x, p, r, dinv, alpha, beta):
+        """x += alpha p and p = dinv r + beta p on codewords, in one pass over the old p
+        (abft_hip_calc_px_precond_vecc; operands 0: x, 1: p, 2: r, 3: dinv)"""
+        check(self.L.abft_hip_calc_px_precond_vecc(self.h, x.h, p.h, r.h, dinv.h, alpha, beta))
+
     def vecc_supported(self, mat):
         """spmv_vecc runs on CSR matrices in the streaming layout only"""
         return mat.fmt == FMT_CSR and self.matrix_info(mat)[0] == "stream"
 
     # ---- Jacobi preconditioning (include/abft_hip.h) ----
-    def jacobi(self, mat, strict=True):
+    def jacobi(self, mat, strict=True, protected=False):
         """-> a new Vector dinv, dinv[i] = 1 / (sum of the diagonal elements of row i), the Jacobi
         preconditioner of cg_solve(..., precond=dinv).  Rows without a positive finite diagonal get 1.0;
-        their number is dinv.bad, and with strict they raise ValueError (Jacobi wants a positive diagonal)."""
+        their number is dinv.bad, and with strict they raise ValueError (Jacobi wants a positive diagonal).
+        protected=True encodes dinv in place (encode_vector) and sets dinv.protected = True: the preconditioner
+        of cg_solve / cg_solve_device(..., vector_ecc=True, precond=dinv), and of those only."""
         dinv = self.create_vector(mat.n_out)
         bad = C.c_uint32(0)
         try:
@@ -419,6 +443,9 @@ class HIPContext:
             self.destroy_vector(dinv)
             raise ValueError("jacobi: %d of %d rows have no positive finite diagonal (strict=False sets their "
                              "entries to 1.0)" % (bad.value, mat.n_out))
+        if protected:
+            self.encode_vector(dinv)
+            dinv.protected = True
         return dinv
 
     def precond_start(self, r, dinv, p):
@@ -605,6 +632,17 @@ class HIPContext:
                                                           base + 8 * rr_at, base + 8 * pw_at, base + 8 * rr_new_at,
                                                           threshold))
 
+    def pcg_vecc_iteration_until_dev(self, mat, vec, x, r, p, w, dinv, scalars, in_at, pw_at, out_at, threshold,
+                                     vec_offset=0, part=capi.PART_ALL):
+        """one guarded Jacobi-preconditioned CG iteration on protected vectors, enqueue-only
+        (abft_hip_pcg_vecc_iteration_until_dev): pcg_iteration_until_dev's arguments and records,
+        the vectors -- dinv too -- codewords.  Vector events name their operand among vec, x, r, p, w, dinv = 0 .. 5.
+        Under graph capture it needs one eager precond_start_vecc on the context first"""
+        base = scalars.device_ptr
+        check(self.L.abft_hip_pcg_vecc_iteration_until_dev(self.h, mat.h, vec.h, vec_offset, part, x.h, r.h, p.h, w.h,
+                                                           dinv.h, base + 8 * in_at, base + 8 * pw_at,
+                                                           base + 8 * out_at, threshold))
+
     def pcg_iteration_until_dev(self, mat, vec, x, r, p, w, dinv, scalars, in_at, pw_at, out_at, threshold,
                                 vec_offset=0, part=capi.PART_ALL):
         """one guarded Jacobi-preconditioned CG iteration, enqueue-only (abft_hip_pcg_iteration_until_dev; DESIGN.md
@@ -705,6 +743,20 @@ def _ckpt_name(itr):
     return "the start" if itr < 0 else "iteration %d" % itr
 
 
+def _check_protected_precond(precond, vector_ecc):
+    """-> whether precond is a protected dinv (ctx.jacobi(A, protected=True)).  dinv's words must be what the loop's
+    kernels read them as: codewords with vector_ecc, plain doubles without -- anything else is refused here"""
+    protected = precond is not None and bool(getattr(precond, "protected", False))
+    if vector_ecc and precond is not None and not protected:
+        raise ValueError("vector_ecc with an unprotected precond: the protected kernels would misread its plain "
+                         "doubles as codewords; make it with ctx.jacobi(A, protected=True)")
+    if protected and not vector_ecc:
+        raise ValueError("a protected precond (ctx.jacobi(A, protected=True)) without vector_ecc: the plain "
+                         "preconditioned kernels would multiply with its code bits; pass vector_ecc=True, or make "
+                         "the precond with ctx.jacobi(A)")
+    return protected
+
+
 def _check_args(check_every, check_tol, max_rollbacks):
     if check_every < 0 or int(check_every) != check_every:
         raise ValueError("check_every must be a whole number >= 0, not %r" % (check_every,))
@@ -741,19 +793,26 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
     forms (spmv_vecc, dot_vecc, calc_xr_vecc, calc_p_vecc), each of which repairs a flipped bit of any
     operand in registers; x and b are scrubbed before returning, so what the caller downloads is repaired
     (vecc_strip gives the values).  Stop test, on_iteration and the return value are as without it; a word
-    with two flipped bits raises FatalEvent.  Refused (ValueError, before anything runs) with check_every > 0,
-    with precond, and for a matrix spmv_vecc does not run on: those kernels write unencoded vectors.
-    With vector_ecc=False the calls are exactly those made without the argument."""
+    with two flipped bits raises FatalEvent.  Refused (ValueError, before anything runs) with check_every > 0
+    and for a matrix spmv_vecc does not run on: those kernels write unencoded vectors.
+    With vector_ecc=False the calls are exactly those made without the argument.
+
+    vector_ecc=True with precond=ctx.jacobi(A, protected=True) is Jacobi-preconditioned CG on protected vectors
+    (DESIGN.md section 5l), dinv under the code like the rest: the same start up to the scrub of r, then
+    rz, rr = precond_start_vecc(r, dinv, p), and per iteration spmv_vecc, dot_vecc(p, w),
+    rz_new, rr = calc_r_precond_vecc(r, w, dinv, rz / pw) and calc_px_precond_vecc(x, p, r, dinv, alpha, rz_new / rz);
+    x, b and dinv are scrubbed before returning.  A precond that is not marked protected is refused with
+    vector_ecc (its plain doubles would be misread as codewords), a protected one without it (ValueError, before
+    anything runs)."""
     _check_args(check_every, check_tol, max_rollbacks)
+    if vector_ecc and check_every:
+        raise ValueError("vector_ecc with check_every > 0: the residual kernels write unencoded vectors")
+    _check_protected_precond(precond, vector_ecc)
     if vector_ecc:
-        if check_every:
-            raise ValueError("vector_ecc with check_every > 0: the residual kernels write unencoded vectors")
-        if precond is not None:
-            raise ValueError("vector_ecc with precond: the preconditioned kernels write unencoded vectors")
         if not ctx.vecc_supported(A):
             raise ValueError("vector_ecc needs a CSR matrix in the streaming layout (this one: %s)"
                              % ("COO" if A.fmt != FMT_CSR else ctx.matrix_info(A)[0]))
-        return _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration)
+        return _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, precond)
     ctx.copy_vector(r, b)
     rz = None
     if precond is None:
@@ -929,12 +988,17 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
     is that loop's -- b and x encoded in place, r <- b scrubbed at once, p <- r, rr0 = dot_vecc(r, r) --, then batches
     of ctx.cg_vecc_iteration_until_dev over the same trail of pairs as the plain loop, and x and b are scrubbed before
     returning (x and b hold codewords then: vecc_strip what is downloaded).  The pairs are plain doubles in device
-    memory, outside any code.  Refused (ValueError, before anything runs) with precond and for a matrix
-    ctx.vecc_supported refuses.  With vector_ecc=False the calls are exactly those made without the argument."""
+    memory, outside any code.  Refused (ValueError, before anything runs) for a matrix ctx.vecc_supported refuses.
+    With vector_ecc=False the calls are exactly those made without the argument.
+
+    vector_ecc=True with precond=ctx.jacobi(A, protected=True) makes it cg_solve's loop of the same arguments
+    (DESIGN.md section 5l): that start -- rz, rr0 = precond_start_vecc(r, dinv, p) behind the scrub of r --, then
+    batches of ctx.pcg_vecc_iteration_until_dev over the preconditioned trail of four-double records, and x, b and
+    dinv are scrubbed before returning.  A precond not marked protected is refused with vector_ecc, a protected one
+    without it (ValueError, before anything runs)."""
     stride = _whole_stride(stride)
+    protected = _check_protected_precond(precond, vector_ecc)
     if vector_ecc:
-        if precond is not None:
-            raise ValueError("vector_ecc with precond: the preconditioned kernels write unencoded vectors")
         if not ctx.vecc_supported(A):
             raise ValueError("vector_ecc needs a CSR matrix in the streaming layout (this one: %s)"
                              % ("COO" if A.fmt != FMT_CSR else ctx.matrix_info(A)[0]))
@@ -943,9 +1007,13 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
     ctx.copy_vector(r, b)
     if vector_ecc:
         ctx.scrub_vector(r)  # the one read of b: repaired in r, b itself stays as it is until the end
-        ctx.copy_vector(p, r)
-        rr = ctx.dot_vecc(r, r)
-        rec, seed = 2, [rr]
+        if protected:
+            rz, rr = ctx.precond_start_vecc(r, precond, p)
+            rec, seed = 4, [rr, 0.0, rz]
+        else:
+            ctx.copy_vector(p, r)
+            rr = ctx.dot_vecc(r, r)
+            rec, seed = 2, [rr]
     elif precond is None:
         ctx.copy_vector(p, r)
         rr = ctx.dot(r, r)
@@ -958,7 +1026,10 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
     done, last_rr = 0, [rr]
 
     def enqueue(trail, k, pw_at):
-        if vector_ecc:
+        if protected:
+            ctx.pcg_vecc_iteration_until_dev(A, p, x, r, p, w, precond, trail, 4 * k, pw_at, 4 * k + 4,
+                                             conv_threshold)
+        elif vector_ecc:
             ctx.cg_vecc_iteration_until_dev(A, p, x, r, p, w, trail, 2 * k, pw_at, 2 * k + 2, conv_threshold)
         elif precond is None:
             ctx.cg_iteration_until_dev(A, p, x, r, p, w, trail, 2 * k, pw_at, 2 * k + 2, conv_threshold)
@@ -979,6 +1050,8 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
     if vector_ecc:
         ctx.scrub_vector(x)
         ctx.scrub_vector(b)
+        if protected:
+            ctx.scrub_vector(precond)
     return done, last_rr[0]
 
 
@@ -1004,6 +1077,7 @@ def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1
     batch: the vectors it sees are the batch's end state.  -> (itrs[K], rr[K]) as cg_solve_block.
     No check_every, no vector_ecc, one GPU."""
     stride = _whole_stride(stride)
+    _check_protected_precond(precond, False)  # (the block loops have no protected form)
     k = B.K
     if not k:
         raise ValueError("cg_solve_block_device wants block vectors (create_block)")
@@ -1046,22 +1120,31 @@ def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1
     return itrs, last_rr[0]
 
 
-def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration):
-    """cg_solve(vector_ecc=True): the loop of cg_solve on protected vectors"""
+def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, precond=None):
+    """cg_solve(vector_ecc=True): the loop of cg_solve on protected vectors; precond: a protected dinv"""
     ctx.encode_vector(b)
     ctx.encode_vector(x)
     ctx.copy_vector(r, b)
     ctx.scrub_vector(r)  # the one read of b: repaired in r, b itself stays as it is until the end
-    ctx.copy_vector(p, r)
-    rr = ctx.dot_vecc(r, r)
+    if precond is None:
+        ctx.copy_vector(p, r)
+        rr = ctx.dot_vecc(r, r)
+    else:
+        rz, rr = ctx.precond_start_vecc(r, precond, p)
     itr = 0
     noted = {}
     note_threshold(rr, conv_threshold, noted)
     while itr < max_itrs and rr > conv_threshold:
         ctx.spmv_vecc(A, p, w)
         pw = ctx.dot_vecc(p, w)
-        rr_new = ctx.calc_xr_vecc(x, r, p, w, fdiv(rr, pw))
-        ctx.calc_p_vecc(p, r, fdiv(rr_new, rr))
+        if precond is None:
+            rr_new = ctx.calc_xr_vecc(x, r, p, w, fdiv(rr, pw))
+            ctx.calc_p_vecc(p, r, fdiv(rr_new, rr))
+        else:
+            alpha = fdiv(rz, pw)
+            rz_new, rr_new = ctx.calc_r_precond_vecc(r, w, precond, alpha)
+            ctx.calc_px_precond_vecc(x, p, r, precond, alpha, fdiv(rz_new, rz))
+            rz = rz_new
         rr = rr_new
         note_threshold(rr, conv_threshold, noted)
         if on_iteration is not None:
@@ -1069,6 +1152,8 @@ def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration
         itr += 1
     ctx.scrub_vector(x)
     ctx.scrub_vector(b)
+    if precond is not None:
+        ctx.scrub_vector(precond)
     return itr, rr
 
 
@@ -1095,6 +1180,7 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
     64 N K bytes of vectors behind the SpMM instead of 88 N K.  Control flow, masks and checks are the same;
     x, r and p get the same operations, and only P . W is summed in another order."""
     _check_args(check_every, check_tol, max_rollbacks)
+    _check_protected_precond(precond, False)  # (the block loops have no protected form)
     k = B.K
     if not k:
         raise ValueError("cg_solve_block wants block vectors (create_block)")

@@ -231,12 +231,12 @@ static int flush_deferred(abft_hip_ctx *ctx) {
 //                                  matrix_compact_stats, matrix_packed_stats, matrix_destroy, matrix_read_csr, _read_coo,
 //                                  _read_element, inject, inject_rowptr, vector_create, vector_map, vector_device_ptr,
 //                                  dot_dev, calc_xr_dev, calc_xr_ratio_dev, peer_exchange_begin, cg_iteration_until_dev,
-//                                  pcg_iteration_until_dev, cg_vecc_iteration_until_dev, block_loop_reserve, graph_begin, drain_events, profile_*,
+//                                  pcg_iteration_until_dev, cg_vecc_iteration_until_dev, pcg_vecc_iteration_until_dev, block_loop_reserve, graph_begin, drain_events, profile_*,
 //                                  stream_probe
 //   FORGET_FUSED                   vector_unmap, vector_copy, graph_launch
 //   FORGET_ITER                    dot_vecc
 //   OTHER_VECTORS                  vector_destroy, matrix_diag_inverse, vector_flip, vector_encode, vector_scrub,
-//    (= FORGET_FUSED | FORGET_ITER)  calc_xr_vecc, calc_p_vecc, calc_r_vecc, calc_px_vecc, spmm, dot_block, calc_xr_block, calc_p_block, copy_block,
+//    (= FORGET_FUSED | FORGET_ITER)  calc_xr_vecc, calc_p_vecc, calc_r_vecc, calc_px_vecc, precond_start_vecc, calc_r_precond_vecc, calc_px_precond_vecc, spmm, dot_block, calc_xr_block, calc_p_block, copy_block,
 //                                  residual_gap, residual_restart, residual_gap_block, residual_restart_block,
 //                                  spmm_dot, calc_r[_precond]_block, calc_px[_precond]_block, precond_start[_block],
 //                                  calc_xr_precond[_block], calc_p_precond_block, cg_block_iteration_until_dev
@@ -3071,6 +3071,65 @@ extern "C" int abft_hip_calc_p_precond(abft_hip_ctx *ctx, abft_hip_vector *p, co
   return ABFT_OK;
 }
 
+// ---- Jacobi preconditioning on protected vectors ----
+// The r / px cut of abft_hip_calc_r_vecc / abft_hip_calc_px_vecc with z = dec(dinv) * r formed in registers; dinv holds
+// codewords too, and is the one operand a call that only reads it may write: the cold path stores a repaired word back.
+// Each starts like abft_hip_calc_r_vecc and checks every pointer, length and overlap -- dinv's included -- before
+// anything is enqueued.  `v`: the call's vectors, dinv among them.
+static int check_precond_vecc(const char *what, std::initializer_list<const abft_hip_vector *> v) {
+  for (const abft_hip_vector *a : v)
+    if (!a) return set_err(ABFT_ERR_INVALID, "%s: null vector", what);
+  const abft_hip_vector *first = *v.begin();
+  for (const abft_hip_vector *a : v)
+    if (a->n != first->n) return set_err(ABFT_ERR_INVALID, "%s: lengths differ (%d vs %d)", what, first->n, a->n);
+  for (auto a = v.begin(); a != v.end(); ++a)
+    for (auto b = a + 1; b != v.end(); ++b)
+      if (first->n && !disjoint(*a, *b)) return set_err(ABFT_ERR_INVALID, "%s: two operands overlap", what);
+  return ABFT_OK;
+}
+
+// p = enc(dinv r) (operands 0: r, 1: dinv, 2: p; r is not written back); out = {r.z, r.r}
+extern "C" int abft_hip_precond_start_vecc(abft_hip_ctx *ctx, const abft_hip_vector *r, abft_hip_vector *dinv,
+                                           abft_hip_vector *p, double out[2]) {
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
+  if (!out) return set_err(ABFT_ERR_INVALID, "precond_start_vecc: null result");
+  if (int rc = check_precond_vecc("precond_start_vecc", {r, dinv, p})) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_precond_start_vecc(r->d, dinv->d, p->d, r->n, o, ctx->ring, ctx->stream));
+  }
+  return pair_from_block_slot(ctx, o.seq, out);
+}
+
+// r -= alpha w (operands 0: r, 1: w, 2: dinv; w is not written back); out = {r.z, r.r} over the r it stores
+extern "C" int abft_hip_calc_r_precond_vecc(abft_hip_ctx *ctx, abft_hip_vector *r, const abft_hip_vector *w,
+                                            abft_hip_vector *dinv, double alpha, double out[2]) {
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
+  if (!out) return set_err(ABFT_ERR_INVALID, "calc_r_precond_vecc: null result");
+  if (int rc = check_precond_vecc("calc_r_precond_vecc", {r, w, dinv})) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_r_precond_vecc(r->d, w->d, dinv->d, alpha, r->n, o, ctx->ring, ctx->stream));
+  }
+  return pair_from_block_slot(ctx, o.seq, out);
+}
+
+// x += alpha p; p = dinv r + beta p, both from the p the call finds (operands 0: x, 1: p, 2: r, 3: dinv; r is not
+// written back)
+extern "C" int abft_hip_calc_px_precond_vecc(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *p,
+                                             const abft_hip_vector *r, abft_hip_vector *dinv, double alpha,
+                                             double beta) {
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
+  if (int rc = check_precond_vecc("calc_px_precond_vecc", {x, p, r, dinv})) return rc;
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_px_precond_vecc(x->d, p->d, r->d, dinv->d, alpha, beta, x->n, ctx->ring, ctx->stream));
+  return ABFT_OK;
+}
+
 // the block vectors of a preconditioned block call and its N-entry dinv, which no written block may overlap
 static int check_precond_block(const char *what, int k, std::initializer_list<const abft_hip_vector *> reads,
                                std::initializer_list<const abft_hip_vector *> writes, const abft_hip_vector *dinv) {
@@ -3587,6 +3646,53 @@ extern "C" int abft_hip_cg_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_
   KernelTimer t(ctx, ABFT_K_CALC_P);
   HIPCHK(launch_calc_px_vecc_until(x->d, p->d, r->d, dev_rr, dev_rr_new, threshold, ctx->alpha_dev, n, ctx->ring,
                                    ctx->stream));
+  return ABFT_OK;
+}
+
+// ---- the guarded Jacobi iteration on protected vectors ----------------
+// abft_hip_pcg_iteration_until_dev's protocol -- records of four doubles {r.r, queued events, r.z, 0.0}, alpha =
+// r.z / p.w and beta = r.z' / r.z formed on the device -- on codewords, dinv's included.  Always three kernels behind
+// the SpMV (fold, guarded r half, guarded x / p half; kernels.hip, calc_r_precond_vecc_until_kernel): live, the bits
+// abft_hip_spmv_vecc with its fused product + abft_hip_calc_r_precond_vecc + abft_hip_calc_px_precond_vecc leave.
+// Vector events count vec, x, r, p, w, dinv as operands 0..5.  Nothing is left pending and abft_hip_tail_stats is not
+// touched.
+extern "C" int abft_hip_pcg_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                                     int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                                     abft_hip_vector *p, abft_hip_vector *w, abft_hip_vector *dinv,
+                                                     const double *dev_in, double *dev_pw, double *dev_out,
+                                                     double threshold) {
+  const char *what = "pcg_vecc_iteration_until";
+  if (int rc = enter(ctx, 0)) return rc;  // a pending x update applied, a speculation voided
+  if (int rc = check_guarded_iteration(ctx, what, mat, vec, vec_offset, part, x, r, p, w, true, dinv, dev_in, dev_pw,
+                                       dev_out))
+    return rc;
+  // what spmv_vecc refuses, refused here under this entry's name (as abft_hip_cg_vecc_iteration_until_dev)
+  if (const char *layout = mat->fmt != ABFT_FMT_CSR ? "COO" : mat->streams() ? nullptr : layout_name(mat->layout))
+    return set_err(ABFT_ERR_INVALID, "%s: a matrix in the %s layout (protected vectors run on CSR matrices in the "
+                   "streaming layout only)", what, layout);
+  const int n = x->n;
+  // the reduction's partials are allocated on first use, which a capturing stream does not allow
+  if (ctx->capturing && !ctx->bslot)
+    return set_err(ABFT_ERR_INVALID, "%s: called under graph capture before the context's block partials exist; make "
+                   "one eager abft_hip_precond_start_vecc first (the loop needs it for its first record anyway)", what);
+  if (int rc = block_slot(ctx)) return rc;
+  forget_iteration(*ctx);  // (as every preconditioned entry: the learned iteration names these vectors by handle)
+  HeldFold hold;
+  if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold, /*vecc=*/true)) return rc;
+  if (int rc = finish_held_fold(ctx, hold)) return rc;
+  ReduceOutD o{};
+  o.partials = ctx->bpartials;
+  o.ticket = ctx->ticket;
+  o.dev_out = dev_out;
+  o.ev_count = ctx->ring.count;
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_r_precond_vecc_until(r->d, w->d, dinv->d, dev_in, dev_pw, threshold, ctx->alpha_dev, n, o,
+                                            ctx->ring, ctx->stream));
+  }
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_px_precond_vecc_until(x->d, p->d, r->d, dinv->d, dev_in, dev_out, threshold, ctx->alpha_dev, n,
+                                           ctx->ring, ctx->stream));
   return ABFT_OK;
 }
 

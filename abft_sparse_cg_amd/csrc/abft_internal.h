@@ -609,6 +609,22 @@ hipError_t launch_calc_r_precond_until(double *r, const double *w, const double 
 hipError_t launch_calc_px_precond_until(double *p, const double *r, const double *dinv, double *x, const double *in,
                                         const double *out, double threshold, const double *alpha_ptr, int n,
                                         hipStream_t s);
+// Jacobi preconditioning on protected vectors: the r / px cut of launch_calc_r_vecc /
+// launch_calc_px_vecc with z = dec(dinv) * r formed in registers, {r.z, r.r} as launch_precond_start returns them; each
+// chooses its walk by the alignment of ALL its operands.  dinv is not const: the cold path stores a repaired word back.
+hipError_t launch_precond_start_vecc(const double *r, double *dinv, double *p, int n, const ReduceOutK &out,
+                                     EventRing ev, hipStream_t s);
+hipError_t launch_calc_r_precond_vecc(double *r, const double *w, double *dinv, double alpha, int n,
+                                      const ReduceOutK &out, EventRing ev, hipStream_t s);
+hipError_t launch_calc_px_precond_vecc(double *x, double *p, const double *r, double *dinv, double alpha, double beta,
+                                       int n, EventRing ev, hipStream_t s);
+// their guarded forms (abft_hip_pcg_vecc_iteration_until_dev): launch_calc_r_precond_until's / _px_precond_until's protocol
+hipError_t launch_calc_r_precond_vecc_until(double *r, const double *w, double *dinv, const double *in,
+                                            const double *pw, double threshold, double *alpha_out, int n,
+                                            const ReduceOutD &out, EventRing ev, hipStream_t s);
+hipError_t launch_calc_px_precond_vecc_until(double *x, double *p, const double *r, double *dinv, const double *in,
+                                             const double *out, double threshold, const double *alpha_ptr, int n,
+                                             EventRing ev, hipStream_t s);
 // the guarded block iteration (abft_hip_cg_block_iteration_until_dev).  Scalars travel as device records of 2k + 2
 // doubles {r.r of the k columns, their r.z (plain: the bits of r.r), queued events, 0.0}, the SpMM's products as
 // k + 1 doubles {P.W of the k columns, queued events}.  Column j is live when in[j] > threshold, decided by every

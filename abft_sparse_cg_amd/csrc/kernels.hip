@@ -6571,3 +6571,341 @@ hipError_t launch_calc_px_vecc_until(double *x, double *p, const double *r, cons
     hipLaunchKernelGGL(calc_px_vecc_until_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, rr, rr_new, threshold, alpha_ptr, n, ev);
   return hipGetLastError();
 }
+
+// ---- Jacobi preconditioning on protected vectors (abft_hip_precond_start_vecc, abft_hip_calc_r_precond_vecc,
+// abft_hip_calc_px_precond_vecc) and the guarded iteration built on them (abft_hip_pcg_vecc_iteration_until_dev;
+// DESIGN.md section 5l) ----
+// The r / px cut above with z = dec(dinv) * (value of r), one rounded product that is never stored and never
+// truncated, where the plain preconditioned kernels form it: p <- enc(z) at the start, {sum r z, sum r r} over the r
+// the r half stores, p <- enc(z + beta dec(p)) in the x / p half.  dinv holds codewords like every other operand.
+// Walks, grid, stride and per-thread sums are those of dot_vecc_kernel, calc_r_vecc_walk and calc_px_vecc_walk, VEC = 2
+// when ALL operands of the call, dinv included, are 16-byte aligned; the two sums meet as precond_start_kernel's do.
+// With dinv == enc(1.0) in every entry z is the value of r bit for bit, so r, x, p and r.r are the plain protected
+// kernels' and r.z has r.r's bits.  Same cold-path discipline: a step with a suspect word is only noted and the chain
+// walked once more behind the loop.  One exception to "a vector that is only read is not written back": dinv outlives
+// the iteration -- no kernel ever rewrites it --, so the cold path stores a repaired dinv word back (the one lane that
+// owns the element: a flip in dinv is reported once and gone afterwards; two flips stay, fatal).
+// ONE body per pair (section 5i), the operand ordinals passed in as above.
+
+// vecc_decode_cold_ok for a dinv word: the repaired word is stored back
+__device__ __forceinline__ double vecc_decode_cold_fix(double *p, uint32_t index, uint32_t operand, const EventRing &ev) {
+  uint64_t w = vecc_bits(*p);
+  if (__builtin_expect(vecc_suspect(w) != 0u, 0)) {
+    const VeccWord o = vecc_cold(w, index, operand, ev);
+    if (o.rc > 0) *p = vecc_double(o.w);
+    w = o.w;
+  }
+  return vecc_value(w);
+}
+
+// p <- enc(z), z = dec(dinv) * dec(r); acc += {sum dec(r) z, sum dec(r)^2}.  r is not written back, p only written.
+template <int VEC>
+__device__ __forceinline__ void precond_start_vecc_walk(const double *__restrict__ r, double *__restrict__ dinv,
+                                                        double *__restrict__ p, int n, uint32_t op_r, uint32_t op_d,
+                                                        EventRing ev, double *acc) {
+  uint32_t bad = 0u;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
+  for (long i = first; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const double2 dv = *reinterpret_cast<const double2 *>(dinv + i);
+      const uint64_t r0 = vecc_bits(rv.x), r1 = vecc_bits(rv.y), d0 = vecc_bits(dv.x), d1 = vecc_bits(dv.y);
+      const uint32_t sus = (vecc_suspect(r0) | vecc_suspect(r1)) | (vecc_suspect(d0) | vecc_suspect(d1));
+      bad |= sus;
+      if (!sus) {
+        const double z0 = vecc_value(d0) * vecc_value(r0), z1 = vecc_value(d1) * vecc_value(r1);
+        *reinterpret_cast<double2 *>(p + i) = make_double2(vecc_double(vecc_encode(z0)), vecc_double(vecc_encode(z1)));
+        acc[0] += vecc_value(r0) * z0;
+        acc[0] += vecc_value(r1) * z1;
+        acc[1] += vecc_value(r0) * vecc_value(r0);
+        acc[1] += vecc_value(r1) * vecc_value(r1);
+      }
+    } else {
+      const uint64_t r0 = vecc_bits(r[i]), d0 = vecc_bits(dinv[i]);
+      const uint32_t sus = vecc_suspect(r0) | vecc_suspect(d0);
+      bad |= sus;
+      if (!sus) {
+        const double z = vecc_value(d0) * vecc_value(r0);
+        p[i] = vecc_double(vecc_encode(z));
+        acc[0] += vecc_value(r0) * z;
+        acc[1] += vecc_value(r0) * vecc_value(r0);
+      }
+    }
+  }
+  if (__builtin_expect(bad != 0u, 0)) {  // r and dinv are as they were, p is only written: the whole chain again
+    acc[0] = 0.0; acc[1] = 0.0;
+    for (long i = first; i < n; i += stride) {
+      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
+      for (int k = 0; k < m; k++) {
+        const uint32_t j = (uint32_t)(i + k);
+        const double ro = vecc_decode_cold_ok(r + i + k, j, op_r, ev);
+        const double z = vecc_decode_cold_fix(dinv + i + k, j, op_d, ev) * ro;
+        p[i + k] = vecc_double(vecc_encode(z));
+        acc[0] += ro * z;
+        acc[1] += ro * ro;
+      }
+    }
+  }
+}
+
+// r <- enc(dec(r) - alpha dec(w)); acc += {sum r' z', sum r' r'}, r' the stored r without its code bits and
+// z' = dec(dinv) * r'.  w is not written back.
+template <int VEC>
+__device__ __forceinline__ void calc_r_precond_vecc_walk(double *__restrict__ r, const double *__restrict__ w,
+                                                         double *__restrict__ dinv, double alpha, int n, uint32_t op_r,
+                                                         uint32_t op_w, uint32_t op_d, EventRing ev, double *acc) {
+  uint32_t bad = 0u;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
+  for (long i = first; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const double2 wv = *reinterpret_cast<const double2 *>(w + i);
+      const double2 dv = *reinterpret_cast<const double2 *>(dinv + i);
+      const uint64_t r0 = vecc_bits(rv.x), r1 = vecc_bits(rv.y), w0 = vecc_bits(wv.x), w1 = vecc_bits(wv.y);
+      const uint64_t d0 = vecc_bits(dv.x), d1 = vecc_bits(dv.y);
+      const uint32_t sus = (vecc_suspect(r0) | vecc_suspect(r1)) | (vecc_suspect(w0) | vecc_suspect(w1)) |
+                           (vecc_suspect(d0) | vecc_suspect(d1));
+      bad |= sus;
+      if (!sus) {
+        const uint64_t rs0 = vecc_encode(vecc_value(r0) - alpha * vecc_value(w0));
+        const uint64_t rs1 = vecc_encode(vecc_value(r1) - alpha * vecc_value(w1));
+        *reinterpret_cast<double2 *>(r + i) = make_double2(vecc_double(rs0), vecc_double(rs1));
+        const double z0 = vecc_value(d0) * vecc_value(rs0), z1 = vecc_value(d1) * vecc_value(rs1);
+        acc[0] += vecc_value(rs0) * z0;
+        acc[0] += vecc_value(rs1) * z1;
+        acc[1] += vecc_value(rs0) * vecc_value(rs0);
+        acc[1] += vecc_value(rs1) * vecc_value(rs1);
+      }
+    } else {
+      const uint64_t r0 = vecc_bits(r[i]), w0 = vecc_bits(w[i]), d0 = vecc_bits(dinv[i]);
+      const uint32_t sus = vecc_suspect(r0) | vecc_suspect(w0) | vecc_suspect(d0);
+      bad |= sus;
+      if (!sus) {
+        const uint64_t rs = vecc_encode(vecc_value(r0) - alpha * vecc_value(w0));
+        r[i] = vecc_double(rs);
+        const double z = vecc_value(d0) * vecc_value(rs);
+        acc[0] += vecc_value(rs) * z;
+        acc[1] += vecc_value(rs) * vecc_value(rs);
+      }
+    }
+  }
+  if (__builtin_expect(bad != 0u, 0)) {
+    acc[0] = 0.0; acc[1] = 0.0;
+    for (long i = first; i < n; i += stride) {
+      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
+      uint32_t sus = 0u;
+      for (int k = 0; k < m; k++)
+        sus |= vecc_suspect(vecc_bits(r[i + k])) | vecc_suspect(vecc_bits(w[i + k])) | vecc_suspect(vecc_bits(dinv[i + k]));
+      for (int k = 0; k < m; k++) {
+        uint64_t rs = vecc_bits(r[i + k]);     // a step carried out above: what it stored ...
+        double d = vecc_value(vecc_bits(dinv[i + k]));  // ... and the clean word it multiplied with
+        if (sus) {
+          const uint32_t j = (uint32_t)(i + k);
+          const double ro = vecc_decode_cold_ok(r + i + k, j, op_r, ev);
+          const double wo = vecc_decode_cold_ok(w + i + k, j, op_w, ev);
+          d = vecc_decode_cold_fix(dinv + i + k, j, op_d, ev);
+          rs = vecc_encode(ro - alpha * wo);
+          r[i + k] = vecc_double(rs);
+        }
+        const double z = d * vecc_value(rs);
+        acc[0] += vecc_value(rs) * z;
+        acc[1] += vecc_value(rs) * vecc_value(rs);
+      }
+    }
+  }
+}
+
+// x <- enc(dec(x) + alpha dec(p)) and p <- enc(dec(dinv) dec(r) + beta dec(p)) in one pass over p, both from the
+// old p; r is not written back
+template <int VEC>
+__device__ __forceinline__ void calc_px_precond_vecc_walk(double *__restrict__ x, double *__restrict__ p,
+                                                          const double *__restrict__ r, double *__restrict__ dinv,
+                                                          double alpha, double beta, int n, uint32_t op_x,
+                                                          uint32_t op_p, uint32_t op_r, uint32_t op_d, EventRing ev) {
+  uint32_t bad = 0u;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
+  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
+  for (long i = first; i < n; i += stride) {
+    if (VEC == 2 && i + 1 < n) {
+      const double2 pv = *reinterpret_cast<const double2 *>(p + i);
+      const double2 xv = *reinterpret_cast<const double2 *>(x + i);
+      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
+      const double2 dv = *reinterpret_cast<const double2 *>(dinv + i);
+      const uint64_t p0 = vecc_bits(pv.x), p1 = vecc_bits(pv.y), x0 = vecc_bits(xv.x), x1 = vecc_bits(xv.y);
+      const uint64_t r0 = vecc_bits(rv.x), r1 = vecc_bits(rv.y), d0 = vecc_bits(dv.x), d1 = vecc_bits(dv.y);
+      const uint32_t sus = (vecc_suspect(p0) | vecc_suspect(p1)) | (vecc_suspect(x0) | vecc_suspect(x1)) |
+                           (vecc_suspect(r0) | vecc_suspect(r1)) | (vecc_suspect(d0) | vecc_suspect(d1));
+      bad |= sus;
+      if (!sus) {
+        const uint64_t xs0 = vecc_encode(vecc_value(x0) + alpha * vecc_value(p0));
+        const uint64_t xs1 = vecc_encode(vecc_value(x1) + alpha * vecc_value(p1));
+        const double z0 = vecc_value(d0) * vecc_value(r0), z1 = vecc_value(d1) * vecc_value(r1);
+        const uint64_t q0 = vecc_encode(z0 + beta * vecc_value(p0));
+        const uint64_t q1 = vecc_encode(z1 + beta * vecc_value(p1));
+        *reinterpret_cast<double2 *>(x + i) = make_double2(vecc_double(xs0), vecc_double(xs1));
+        *reinterpret_cast<double2 *>(p + i) = make_double2(vecc_double(q0), vecc_double(q1));
+      }
+    } else {
+      const uint64_t p0 = vecc_bits(p[i]), x0 = vecc_bits(x[i]), r0 = vecc_bits(r[i]), d0 = vecc_bits(dinv[i]);
+      const uint32_t sus = (vecc_suspect(p0) | vecc_suspect(x0)) | (vecc_suspect(r0) | vecc_suspect(d0));
+      bad |= sus;
+      if (!sus) {
+        const double z = vecc_value(d0) * vecc_value(r0);
+        x[i] = vecc_double(vecc_encode(vecc_value(x0) + alpha * vecc_value(p0)));
+        p[i] = vecc_double(vecc_encode(z + beta * vecc_value(p0)));
+      }
+    }
+  }
+  if (__builtin_expect(bad != 0u, 0)) {
+    for (long i = first; i < n; i += stride) {
+      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
+      uint32_t sus = 0u;
+      for (int k = 0; k < m; k++)
+        sus |= (vecc_suspect(vecc_bits(p[i + k])) | vecc_suspect(vecc_bits(x[i + k]))) |
+               (vecc_suspect(vecc_bits(r[i + k])) | vecc_suspect(vecc_bits(dinv[i + k])));
+      if (!sus) continue;  // carried out above
+      for (int k = 0; k < m; k++) {
+        const uint32_t j = (uint32_t)(i + k);
+        const double xo = vecc_decode_cold_ok(x + i + k, j, op_x, ev);
+        const double po = vecc_decode_cold_ok(p + i + k, j, op_p, ev);
+        const double ro = vecc_decode_cold_ok(r + i + k, j, op_r, ev);
+        const double z = vecc_decode_cold_fix(dinv + i + k, j, op_d, ev) * ro;
+        x[i + k] = vecc_double(vecc_encode(xo + alpha * po));
+        p[i + k] = vecc_double(vecc_encode(z + beta * po));
+      }
+    }
+  }
+}
+
+// p = enc(dinv r); {r.z, r.r} (operands 0: r, 1: dinv, 2: p)
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void precond_start_vecc_kernel(const double *__restrict__ r,
+                                                                        double *__restrict__ dinv,
+                                                                        double *__restrict__ p, int n, ReduceOutK out,
+                                                                        EventRing ev) {
+  __shared__ double s_w[16];
+  double acc[2] = {0.0, 0.0};
+  precond_start_vecc_walk<VEC>(r, dinv, p, n, 0u, 1u, ev, acc);
+  reduce_finish_k<2>(acc, out, s_w);
+}
+
+// r -= alpha w; {r.z, r.r} of the r it stores (operands 0: r, 1: w, 2: dinv)
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_precond_vecc_kernel(double *__restrict__ r,
+                                                                         const double *__restrict__ w,
+                                                                         double *__restrict__ dinv, double alpha, int n,
+                                                                         ReduceOutK out, EventRing ev) {
+  __shared__ double s_w[16];
+  double acc[2] = {0.0, 0.0};
+  calc_r_precond_vecc_walk<VEC>(r, w, dinv, alpha, n, 0u, 1u, 2u, ev, acc);
+  reduce_finish_k<2>(acc, out, s_w);
+}
+
+// x += alpha p; p = dinv r + beta p (operands 0: x, 1: p, 2: r, 3: dinv)
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_precond_vecc_kernel(double *__restrict__ x, double *__restrict__ p,
+                                                                          const double *__restrict__ r,
+                                                                          double *__restrict__ dinv, double alpha,
+                                                                          double beta, int n, EventRing ev) {
+  calc_px_precond_vecc_walk<VEC>(x, p, r, dinv, alpha, beta, n, 0u, 1u, 2u, 3u, ev);
+}
+
+// The guarded forms: calc_r_precond_until_kernel's and calc_px_precond_until_kernel's protocol, word for word, in
+// front of the protected walks.  Operands as the guarded entry counts them: x 1, r 2, p 3, w 4, dinv 5 (0 is the
+// SpMV's gathered vector).  A frozen launch touches no vector, dinv included: it repairs nothing and reports nothing.
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_precond_vecc_until_kernel(double *__restrict__ r,
+                                                                               const double *__restrict__ w,
+                                                                               double *__restrict__ dinv,
+                                                                               const double *in, const double *pw,
+                                                                               double threshold, double *alpha_out,
+                                                                               int n, ReduceOutD out, EventRing ev) {
+  __shared__ double s_w[16];
+  if (!(in[0] > threshold)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      // the bits, whatever they are (a NaN's payload included): moved as integers
+      const unsigned long long *src = reinterpret_cast<const unsigned long long *>(in);
+      unsigned long long *dst = reinterpret_cast<unsigned long long *>(out.dev_out);
+      const unsigned long long rr_bits = src[0], rz_bits = src[2];
+      dst[0] = rr_bits;
+      out.dev_out[1] = (double)__hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      dst[2] = rz_bits;
+      out.dev_out[3] = 0.0;
+    }
+    return;
+  }
+  const double alpha = in[2] / *pw;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;  // for the x / p half
+  double acc[2] = {0.0, 0.0};
+  calc_r_precond_vecc_walk<VEC>(r, w, dinv, alpha, n, 2u, 4u, 5u, ev, acc);
+  reduce_finish_d(acc, out, s_w);
+}
+
+// (in: the record the iteration started from -- the guard, and beta's denominator; out: what the r half left)
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_precond_vecc_until_kernel(double *__restrict__ x,
+                                                                                double *__restrict__ p,
+                                                                                const double *__restrict__ r,
+                                                                                double *__restrict__ dinv,
+                                                                                const double *in, const double *out,
+                                                                                double threshold,
+                                                                                const double *alpha_ptr, int n,
+                                                                                EventRing ev) {
+  if (!(in[0] > threshold)) return;
+  const double beta = out[2] / in[2];
+  const double alpha = *alpha_ptr;
+  calc_px_precond_vecc_walk<VEC>(x, p, r, dinv, alpha, beta, n, 1u, 3u, 2u, 5u, ev);
+}
+
+// (each chooses its walk over its own operands, in the host-scalar and in the guarded form alike)
+#define ABFT_VECC_DISPATCH(KERNEL, VEC2, ...)                                                   \
+  do {                                                                                          \
+    if (VEC2)                                                                                   \
+      hipLaunchKernelGGL(KERNEL<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);             \
+    else                                                                                        \
+      hipLaunchKernelGGL(KERNEL<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);             \
+  } while (0)
+
+hipError_t launch_precond_start_vecc(const double *r, double *dinv, double *p, int n, const ReduceOutK &out,
+                                     EventRing ev, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  ABFT_VECC_DISPATCH(precond_start_vecc_kernel, aligned16(r, dinv, p), r, dinv, p, n, out, ev);
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_r_precond_vecc(double *r, const double *w, double *dinv, double alpha, int n,
+                                      const ReduceOutK &out, EventRing ev, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  ABFT_VECC_DISPATCH(calc_r_precond_vecc_kernel, aligned16(r, w, dinv), r, w, dinv, alpha, n, out, ev);
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_px_precond_vecc(double *x, double *p, const double *r, double *dinv, double alpha, double beta,
+                                       int n, EventRing ev, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+  ABFT_VECC_DISPATCH(calc_px_precond_vecc_kernel, aligned16(x, p, r, dinv), x, p, r, dinv, alpha, beta, n, ev);
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_r_precond_vecc_until(double *r, const double *w, double *dinv, const double *in,
+                                            const double *pw, double threshold, double *alpha_out, int n,
+                                            const ReduceOutD &out, EventRing ev, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  ABFT_VECC_DISPATCH(calc_r_precond_vecc_until_kernel, aligned16(r, w, dinv), r, w, dinv, in, pw, threshold, alpha_out,
+                     n, out, ev);
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_px_precond_vecc_until(double *x, double *p, const double *r, double *dinv, const double *in,
+                                             const double *out, double threshold, const double *alpha_ptr, int n,
+                                             EventRing ev, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+  ABFT_VECC_DISPATCH(calc_px_precond_vecc_until_kernel, aligned16(x, p, r, dinv), x, p, r, dinv, in, out, threshold,
+                     alpha_ptr, n, ev);
+  return hipGetLastError();
+}
+#undef ABFT_VECC_DISPATCH

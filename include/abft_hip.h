@@ -369,9 +369,10 @@ int abft_hip_calc_px_vecc(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector
  * exactly as its plain counterpart (dot, calc_xr, calc_p and their block forms), so with
  * dinv == 1.0 everywhere it leaves and returns the plain call's bits.  Every length is
  * checked, and a dinv that overlaps a vector the call writes is refused
- * (ABFT_ERR_INVALID) before anything is enqueued.  dinv carries no ECC words: damage to
- * it changes M, hence the rate of convergence, never the consistency of r with b - A x
- * that the residual checks verify. */
+ * (ABFT_ERR_INVALID) before anything is enqueued.  In these entries dinv carries no ECC
+ * words: damage to it changes M, hence the rate of convergence, never the consistency of r
+ * with b - A x that the residual checks verify (the protected forms below keep dinv under
+ * the vectors' code). */
 
 /* dinv[i] = 1.0 / d[i], d[i] = the sum, in the caller's element order, of the values of the
  * elements whose row and column are both i (the column as that mode's SpMV decodes it: ECC
@@ -395,6 +396,39 @@ int abft_hip_calc_xr_precond(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vec
 /* p = z + beta p, z formed again from the same operands (the same bits) */
 int abft_hip_calc_p_precond(abft_hip_ctx *ctx, abft_hip_vector *p, const abft_hip_vector *r,
                             const abft_hip_vector *dinv, double beta);
+/* The same preconditioning on PROTECTED vectors (the *_vecc entries above): r, p, x, w AND dinv hold codewords
+ * (abft_hip_vector_encode dinv once).  val(w): the repaired word without its 7 code bits; enc(v): v truncated toward
+ * zero plus the code bits; z = val(dinv[i]) * (value of r[i]) is one rounded fp64 product, never stored and never
+ * truncated; every multiply and add is separate; sums are over the values as stored.  The loop:
+ *   copy r <- b;  {rz, rr} = precond_start_vecc(r, dinv, p)
+ *   while rr > threshold:  spmv_vecc(A, p, w);  alpha = rz / dot_vecc(p, w)
+ *                          {rz_new, rr} = calc_r_precond_vecc(r, w, dinv, alpha)
+ *                          calc_px_precond_vecc(x, p, r, dinv, alpha, rz_new / rz);  rz = rz_new
+ * -- the r / px cut of abft_hip_calc_r_vecc / _calc_px_vecc: one set of walks, 80 N bytes of vectors behind the SpMV.
+ * Each walks and sums as its plain protected counterpart (abft_hip_dot_vecc for the start), pairs only when ALL its
+ * operands, dinv included, are 16-byte aligned, the two sums through the K-wide slot as abft_hip_precond_start's.
+ * With dinv == enc(1.0) everywhere, on whole vectors: calc_r_precond_vecc leaves abft_hip_calc_r_vecc's r and returns
+ * its r.r in out[1], out[0] the same bits; calc_px_precond_vecc leaves abft_hip_calc_px_vecc's x and p;
+ * precond_start_vecc leaves a copy of r in p.
+ * A flipped bit in any operand is repaired in registers and reported (ABFT_EV_VEC_CORRECTED, the operand's ordinal
+ * as listed); a vector a call only reads is not written back -- EXCEPT dinv, which no call of the loop ever rewrites:
+ * the repaired dinv word is stored back, so a flip in dinv is reported once and gone afterwards.  Two flips in one
+ * word are ABFT_EV_VEC_DOUBLE, fatal, the word left as it is.  Hence dinv is not const here.
+ * Each starts like abft_hip_calc_r_vecc (the prologue, the learned iteration and the fused product forgotten) and
+ * refuses (ABFT_ERR_INVALID) a null pointer, differing lengths and ANY two operands that overlap, dinv included, before
+ * anything is enqueued, every operand untouched.
+ * p = enc(z), z from val(r) (operands 0: r, 1: dinv, 2: p; p is only written, r not written back);
+ * out = {sum val(r) z, sum val(r) val(r)}; out[1] is abft_hip_dot_vecc(r, r) bit for bit */
+int abft_hip_precond_start_vecc(abft_hip_ctx *ctx, const abft_hip_vector *r, abft_hip_vector *dinv,
+                                abft_hip_vector *p, double out[2]);
+/* r = enc(val(r) - alpha val(w)) (operands 0: r, 1: w, 2: dinv; w is not written back);
+ * out = {sum r' z', sum r' r'}, r' the stored r without its code bits, z' = val(dinv) r' */
+int abft_hip_calc_r_precond_vecc(abft_hip_ctx *ctx, abft_hip_vector *r, const abft_hip_vector *w,
+                                 abft_hip_vector *dinv, double alpha, double out[2]);
+/* x = enc(val(x) + alpha val(p)); p = enc(val(dinv) val(r) + beta val(p)), both from the p the call finds, read once
+ * (operands 0: x, 1: p, 2: r, 3: dinv; r is not written back) */
+int abft_hip_calc_px_precond_vecc(abft_hip_ctx *ctx, abft_hip_vector *x, abft_hip_vector *p,
+                                  const abft_hip_vector *r, abft_hip_vector *dinv, double alpha, double beta);
 /* Block forms (k <= 8 columns, row-major as above; ONE dinv of N entries for all columns: one
  * operator).  out[2j], out[2j + 1] = column j's two sums, for every column.  P is rewritten in
  * the columns set in `mask` only; `active` as in abft_hip_calc_xr_block / _calc_p_block: a
@@ -770,6 +804,30 @@ int abft_hip_cg_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat
                                          int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
                                          abft_hip_vector *p, abft_hip_vector *w, const double *dev_rr,
                                          double *dev_pw, double *dev_rr_new, double threshold);
+
+/* The guarded Jacobi iteration on PROTECTED vectors: abft_hip_pcg_iteration_until_dev's protocol on codewords, dinv's
+ * included.  Records of four plain doubles {r.r, queued events, r.z, 0.0}; dev_pw is the SpMV's pair.
+ *   LIVE   when dev_in[0] > threshold (false for NaN): bit for bit -- x, r, p, w, dev_pw, dev_out -- what
+ *          abft_hip_spmv_vecc(A, vec, w) with its fused product,
+ *          abft_hip_calc_r_precond_vecc(r, w, dinv, dev_in[2] / dev_pw[0]) and
+ *          abft_hip_calc_px_precond_vecc(x, p, r, dinv, that alpha, r.z' / dev_in[2]) leave, the quotients formed on
+ *          the device.
+ *   FROZEN otherwise: x, r, p and dinv keep every bit -- a word with a flipped bit included: a frozen launch of the two
+ *          vector kernels repairs nothing and reports nothing --; dev_out[0] and dev_out[2] get dev_in's bits (moved
+ *          as integers), dev_out[1] the queued-event count, dev_out[3] 0.0; w and dev_pw are unspecified.  The SpMV
+ *          still runs, with its checks.
+ * Vector events name their operand by its place among vec, x, r, p, w, dinv = 0 .. 5.
+ * Always three kernels behind the SpMV (the fold, the guarded r half, the guarded x / p half); both guards decide on
+ * dev_in[0], which neither kernel writes; a frozen launch returns before the reduction's ticket; no workgroup waits
+ * for another.  Enqueue-only and capturable once the context holds its block partials: under graph capture on a
+ * context that does not, ABFT_ERR_INVALID, and the message names the remedy -- one eager abft_hip_precond_start_vecc,
+ * which allocates them and which the loop needs for its first record anyway.
+ * Refused before anything is enqueued: everything abft_hip_cg_vecc_iteration_until_dev refuses, and everything
+ * abft_hip_pcg_iteration_until_dev refuses about dinv and the records. */
+int abft_hip_pcg_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                          int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                          abft_hip_vector *p, abft_hip_vector *w, abft_hip_vector *dinv,
+                                          const double *dev_in, double *dev_pw, double *dev_out, double threshold);
 
 /* The guarded iteration for k right-hand sides (block vectors, 1 <= k <= ABFT_MAX_RHS): one iteration of the fused
  * block loop -- W = A P with the k products P . W, then per column r -= alpha w, x += alpha p, p = r + beta p (with

@@ -9,6 +9,7 @@ laplace5:3162,3162 (config 2, 10 M rows), laplace5:1000,1000 and laplace5:316,31
     python tools/device_loop_bench.py --out profiles/device_loop_bench.json [--iters 200] [--blocks 5]
                                       [--specs laplace5:1000,1000,...] [--strides 4,8,16,32]
                                       [--precond jacobi] [--rhs 4,8 [--modes none,secded]]
+                                      [--vector-ecc [--precond jacobi] [--modes none,secded]]
 
 --precond jacobi alternates cg_solve(precond=dinv) and cg_solve_device(precond=dinv) instead,
 dinv = ctx.jacobi(A); the JSON says so under `precond`, in the file and in every row.  The yardstick is then
@@ -27,6 +28,12 @@ none,secded).  Matrices by default laplace5:3162,3162 and laplace5:1000,1000.  T
 cg_solve(vector_ecc=True) of the same build; both loops pay the same start (two encodes, a scrub) and end (two
 scrubs) inside the timed window.  --out defaults to profiles/device_loop_bench_vecc.json there.  Without the flag
 nothing changes.
+
+--vector-ecc --precond jacobi measures Jacobi-preconditioned CG on protected vectors:
+cg_solve(vector_ecc=True, precond=dinv) and cg_solve_device(vector_ecc=True, precond=dinv) alternating, dinv =
+ctx.jacobi(A, protected=True) made once per context.  The yardstick is the protected host PCG loop of the same build;
+both loops pay the same start and the same end (three scrubs now) inside the timed window.  --out defaults to
+profiles/device_loop_bench_vecc_precond.json there; the rows say precond: jacobi.
 
 Also reported per matrix: `best_stride`, the smallest stride within 2 % of the best device-loop time (what
 DEFAULT_STRIDE is to be on the 1 M-row matrix), and `frozen_spmv_worst`, stride - 1: the SpMVs a solve can waste
@@ -137,7 +144,8 @@ VECC_SPECS = ("laplace5:3162,3162", "laplace5:1000,1000")
 
 
 def vecc_main(a, res):
-    """--vector-ecc: the loops on protected vectors, one row per (matrix, mode)"""
+    """--vector-ecc: the loops on protected vectors (with --precond jacobi: the protected PCG loops), one row per
+    (matrix, mode)"""
     strides = [int(s) for s in (a.strides or ",".join(str(s) for s in STRIDES)).split(",")]
     res["vector_ecc"] = True
     res["modes"] = a.modes.split(",")
@@ -149,20 +157,21 @@ def vecc_main(a, res):
             A = ctx.create_matrix(cols, rows, vals, n, nnz, layout="stream")
             vecs = [ctx.create_vector(n) for _ in range(5)]
             ctx.upload(vecs[0], generators.reference_rhs(n))
+            dinv = ctx.jacobi(A, protected=True) if a.precond == "jacobi" else None
             kinds = [0] + strides
             for k in kinds:  # warm-up: first launches, the graph's instantiation path
-                timed_solve(ctx, A, vecs, n, max(k, 5), k, vecc=True)
+                timed_solve(ctx, A, vecs, n, max(k, 5), k, dinv, vecc=True)
             per = {k: [] for k in kinds}
             for _ in range(a.blocks):
                 for k in kinds:
-                    ms, itr = timed_solve(ctx, A, vecs, n, a.iters, k, vecc=True)
+                    ms, itr = timed_solve(ctx, A, vecs, n, a.iters, k, dinv, vecc=True)
                     assert itr == a.iters, (spec, mode, k, itr)  # every iteration live in both loops
                     per[k].append(ms / a.iters)
             host = statistics.median(per[0])
             dev = {k: statistics.median(per[k]) for k in strides}
             best = min(dev.values())
-            row = dict(spec=spec, fmt="csr", mode=mode, layout=ctx.matrix_info(A)[0], vector_ecc=True, n=n, nnz=nnz,
-                       ms_per_iter_host_vecc=host,
+            row = dict(spec=spec, fmt="csr", mode=mode, layout=ctx.matrix_info(A)[0], vector_ecc=True,
+                       precond=a.precond, n=n, nnz=nnz, ms_per_iter_host_vecc=host,
                        ms_per_iter_device_vecc={str(k): v for k, v in dev.items()},
                        ratio_device_over_host={str(k): v / host for k, v in dev.items()},
                        best_stride=min(k for k in strides if dev[k] <= 1.02 * best),
@@ -186,8 +195,8 @@ def main():
     ap.add_argument("--modes", default="none,secded", help="with --rhs or --vector-ecc: the ECC modes")
     ap.add_argument("--vector-ecc", action="store_true", help="the loops on protected vectors")
     a = ap.parse_args()
-    if a.vector_ecc and (a.rhs or a.precond != "none"):
-        ap.error("--vector-ecc goes with neither --rhs nor --precond")
+    if a.vector_ecc and a.rhs:
+        ap.error("--vector-ecc does not go with --rhs")
     argv = [v for i, v in enumerate(sys.argv) if v != "--out" and (i == 0 or sys.argv[i - 1] != "--out")]
     res = {"cmd": " ".join(argv), "iters": a.iters, "blocks": a.blocks, "threshold": THRESHOLD,
            "precond": a.precond, "rows": []}
@@ -199,7 +208,8 @@ def main():
             json.dump(res, f, indent=1)
         return 0
     if a.vector_ecc:
-        a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_vecc.json")
+        a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_vecc_precond.json" if a.precond == "jacobi"
+                                      else "device_loop_bench_vecc.json")
         vecc_main(a, res)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
