@@ -115,6 +115,10 @@ SIGNATURES = {
     "abft_hip_calc_px_block": (C.c_int, [vp, vp, vp, vp, C.c_int, f64p, f64p, C.c_uint32]),
     "abft_hip_calc_r_precond_block": (C.c_int, [vp, vp, vp, vp, C.c_int, f64p, C.c_uint32, f64p]),
     "abft_hip_calc_px_precond_block": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, f64p, f64p, C.c_uint32]),
+    "abft_hip_spmm_dot_vecc": (C.c_int, [vp, vp, vp, vp, C.c_int, f64p]),
+    "abft_hip_dot_block_vecc": (C.c_int, [vp, vp, vp, C.c_int, f64p]),
+    "abft_hip_calc_r_block_vecc": (C.c_int, [vp, vp, vp, C.c_int, f64p, C.c_uint32, f64p]),
+    "abft_hip_calc_px_block_vecc": (C.c_int, [vp, vp, vp, vp, C.c_int, f64p, f64p, C.c_uint32]),
     "abft_hip_dot_dev": (C.c_int, [vp, vp, vp, vp]),
     "abft_hip_calc_xr_dev": (C.c_int, [vp, vp, vp, vp, vp, C.c_double, vp]),
     "abft_hip_read_pair": (C.c_int, [vp, vp, f64p, f64p]),

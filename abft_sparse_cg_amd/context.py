@@ -420,6 +420,46 @@ class HIPContext:
         (abft_hip_calc_px_precond_vecc; operands 0: x, 1: p, 2: r, 3: dinv)"""
         check(self.L.abft_hip_calc_px_precond_vecc(self.h, x.h, p.h, r.h, dinv.h, alpha, beta))
 
+    # ---- protected block vectors (include/abft_hip.h; DESIGN.md section 5m): cg_solve_block(..., vector_ecc=True) ----
+    def spmm_dot_vecc(self, mat, P, W, k, drain=True):
+        """spmm_dot on codewords: W = enc(A val(P)) -> np.ndarray of the k products val(P[:, j]) . strip(W[:, j])
+        (abft_hip_spmm_dot_vecc; operand 0: P, not written back).  Events as after spmm_dot."""
+        out = np.zeros(k)
+        check(self.L.abft_hip_spmm_dot_vecc(self.h, mat.h, P.h, W.h, k, out.ctypes.data_as(capi.f64p)))
+        if drain:
+            self._drain()
+        else:
+            self._drain_if_pending()
+        return out
+
+    def dot_block_vecc(self, a, b, k):
+        """-> np.ndarray of k dots val(a[:, j]) . val(b[:, j]) (abft_hip_dot_block_vecc; operands 0: a, 1: b)"""
+        out = np.zeros(k)
+        check(self.L.abft_hip_dot_block_vecc(self.h, a.h, b.h, k, out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return out
+
+    def calc_r_block_vecc(self, R, W, k, alpha, active):
+        """calc_r_block on codewords: R[:, j] = enc(val(R) - alpha[j] val(W)) in the columns set in `active`
+        -> rr[k] over the stored R of every column (abft_hip_calc_r_block_vecc; operands 0: R, 1: W)"""
+        a = np.zeros(capi.MAX_RHS)
+        a[:k] = alpha
+        out = np.zeros(k)
+        check(self.L.abft_hip_calc_r_block_vecc(self.h, R.h, W.h, k, a.ctypes.data_as(capi.f64p), int(active),
+                                                out.ctypes.data_as(capi.f64p)))
+        self._drain_if_pending()
+        return out
+
+    def calc_px_block_vecc(self, X, P, R, k, alpha, beta, active):
+        """calc_px_block on codewords, in the columns set in `active`: X = enc(val(X) + alpha[j] val(P)) and
+        P = enc(val(R) + beta[j] val(P)), both from the old P (abft_hip_calc_px_block_vecc; operands 0: X, 1: P, 2: R)"""
+        a = np.zeros(capi.MAX_RHS)
+        a[:k] = alpha
+        b = np.zeros(capi.MAX_RHS)
+        b[:k] = beta
+        check(self.L.abft_hip_calc_px_block_vecc(self.h, X.h, P.h, R.h, k, a.ctypes.data_as(capi.f64p),
+                                                 b.ctypes.data_as(capi.f64p), int(active)))
+
     def vecc_supported(self, mat):
         """spmv_vecc runs on CSR matrices in the streaming layout only"""
         return mat.fmt == FMT_CSR and self.matrix_info(mat)[0] == "stream"
@@ -1157,8 +1197,45 @@ def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration
     return itr, rr
 
 
+def _cg_solve_block_vecc(ctx, A, B, X, R, P, W, k, max_itrs, conv_threshold, on_iteration):
+    """cg_solve_block(vector_ecc=True): the fused block loop on protected block vectors"""
+    ctx.encode_vector(B)
+    ctx.encode_vector(X)
+    ctx.copy_vector(R, B)
+    ctx.scrub_vector(R)  # the one read of B: repaired in R, B itself stays as it is until the end
+    ctx.copy_vector(P, R)
+    rr = np.array(ctx.dot_block_vecc(R, R, k), dtype=np.float64)
+    itrs = [0] * k
+    noted = {}
+    for j in range(k):
+        note_threshold(rr[j], conv_threshold, noted)
+    itr = 0
+    while True:
+        active = sum(1 << j for j in range(k) if itrs[j] < max_itrs and rr[j] > conv_threshold)
+        if not active:
+            break
+        on = [(active >> j) & 1 for j in range(k)]
+        pw = ctx.spmm_dot_vecc(A, P, W, k, drain=False)
+        alpha = [fdiv(rr[j], pw[j]) if on[j] else 0.0 for j in range(k)]
+        rr_new = ctx.calc_r_block_vecc(R, W, k, alpha, active)
+        beta = [fdiv(rr_new[j], rr[j]) if on[j] else 0.0 for j in range(k)]
+        ctx.calc_px_block_vecc(X, P, R, k, alpha, beta, active)
+        for j in range(k):
+            if on[j]:
+                rr[j] = rr_new[j]
+                itrs[j] += 1
+                note_threshold(rr[j], conv_threshold, noted)
+        if on_iteration is not None:
+            on_iteration(itr, rr.copy(), active)
+        itr += 1
+    ctx.scrub_vector(X)
+    ctx.scrub_vector(B)
+    return itrs, rr
+
+
 def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None, check_every=0,
-                   check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None, precond=None, fused=False):
+                   check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None, precond=None, fused=False,
+                   vector_ecc=False):
     """cg_solve for the K columns of block vectors (ctx.create_block) at once: per column j exactly
     cg_solve's control flow -- column j iterates while itrs[j] < max_itrs and rr[j] > conv_threshold --
     on one spmm / dot_block / calc_xr_block / calc_p_block per iteration.  A column that has stopped
@@ -1178,12 +1255,31 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
     fused: the iteration in three calls -- spmm_dot (P . W out of the SpMM), calc_r_block (r and its sums),
     calc_px_block (x and p in one pass over p) -- instead of spmm / dot_block / calc_xr_block / calc_p_block:
     64 N K bytes of vectors behind the SpMM instead of 88 N K.  Control flow, masks and checks are the same;
-    x, r and p get the same operations, and only P . W is summed in another order."""
+    x, r and p get the same operations, and only P . W is summed in another order.
+
+    vector_ecc=True runs the loop on protected block vectors, as cg_solve(vector_ecc=True) does
+    for one column: B and X are encoded in place, R <- B is a copy of codewords that is scrubbed at once, P <- R,
+    rr = dot_block_vecc(R, R); per iteration spmm_dot_vecc, calc_r_block_vecc and calc_px_block_vecc -- always the
+    three-call iteration: `fused` is ignored, there is no four-call protected form --; X and B are scrubbed before
+    returning.  Every word of every column is checked by every call, stopped columns included, and a stopped
+    column's words are stored back repaired.  Control flow, masks, on_iteration and the return value are as
+    without it.  Refused (ValueError, before anything runs) with check_every > 0, with any precond, and for a matrix
+    ctx.vecc_supported refuses.  With vector_ecc=False the calls are exactly those made without the argument."""
     _check_args(check_every, check_tol, max_rollbacks)
-    _check_protected_precond(precond, False)  # (the block loops have no protected form)
+    if vector_ecc:
+        if check_every:
+            raise ValueError("vector_ecc with check_every > 0: the residual kernels write unencoded vectors")
+        if precond is not None:
+            raise ValueError("vector_ecc with a precond: the protected block loop has no Jacobi form")
+        if not ctx.vecc_supported(A):
+            raise ValueError("vector_ecc needs a CSR matrix in the streaming layout (this one: %s)"
+                             % ("COO" if A.fmt != FMT_CSR else ctx.matrix_info(A)[0]))
+    _check_protected_precond(precond, False)  # (a protected dinv has no block loop to go to)
     k = B.K
     if not k:
         raise ValueError("cg_solve_block wants block vectors (create_block)")
+    if vector_ecc:
+        return _cg_solve_block_vecc(ctx, A, B, X, R, P, W, k, max_itrs, conv_threshold, on_iteration)
     ctx.copy_vector(R, B)
     rz = None
     if precond is None:

@@ -3350,6 +3350,75 @@ extern "C" int abft_hip_calc_px_precond_block(abft_hip_ctx *ctx, abft_hip_vector
   return calc_px_block_common(ctx, "calc_px_precond_block", X, P, R, dinv, true, k, alpha, beta, active);
 }
 
+// ---- the fused block iteration on protected block vectors ----
+// The plain twins' checks (check_spmm_dot, check_block, check_fused_block), all of them before anything of the call
+// is enqueued; the kernels get the event ring, for the repaired words.
+
+extern "C" int abft_hip_spmm_dot_vecc(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *P,
+                                      abft_hip_vector *W, int k, double *out) {
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
+  if (!mat || !P || !W || !out) return set_err(ABFT_ERR_INVALID, "spmm_dot_vecc: null argument");
+  if (int rc = check_spmm_dot("spmm_dot_vecc", mat, P, W, k)) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  if (int rc = dotparts_reserve(ctx, mat, k)) return rc;
+  {
+    KernelTimer t(ctx, ABFT_K_SPMV);
+    HIPCHK(launch_spmm_dot_vecc_csr(mat->mode, k, mat->csr, P->d, W->d, ctx->ring, ctx->dotparts, ctx->stream));
+  }
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_spmm_fold(ctx->dotparts, mat->csr.nblk, k, o, ctx->stream));
+  }
+  return results_from_block_slot(ctx, o.seq, k, out);
+}
+
+extern "C" int abft_hip_dot_block_vecc(abft_hip_ctx *ctx, const abft_hip_vector *a, const abft_hip_vector *b, int k,
+                                       double *out) {
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
+  if (!a || !b || !out) return set_err(ABFT_ERR_INVALID, "dot_block_vecc: null argument");
+  if (k < 1 || k > ABFT_MAX_RHS)
+    return set_err(ABFT_ERR_INVALID, "dot_block_vecc: k = %d outside [1, %d]", k, ABFT_MAX_RHS);
+  const int N = a->n / k;
+  if (int rc = check_block("dot_block_vecc", k, N, {a, b})) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_dot_block_vecc(a->d, b->d, N, k, o, ctx->ring, ctx->stream));
+  }
+  return results_from_block_slot(ctx, o.seq, k, out);
+}
+
+extern "C" int abft_hip_calc_r_block_vecc(abft_hip_ctx *ctx, abft_hip_vector *R, const abft_hip_vector *W, int k,
+                                          const double *alpha, uint32_t active, double *rr_out) {
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
+  if (!alpha || !rr_out) return set_err(ABFT_ERR_INVALID, "calc_r_block_vecc: null argument");
+  if (int rc = check_fused_block("calc_r_block_vecc", k, {W}, {R}, nullptr, false)) return rc;
+  if (int rc = block_slot(ctx)) return rc;
+  BlockScalars a{};
+  for (int j = 0; j < k; j++) a.v[j] = alpha[j];
+  const ReduceOutK o = reduce_out_k(ctx);
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    HIPCHK(launch_calc_r_block_vecc(R->d, W->d, R->n / k, k, a, active, o, ctx->ring, ctx->stream));
+  }
+  return results_from_block_slot(ctx, o.seq, k, rr_out);
+}
+
+extern "C" int abft_hip_calc_px_block_vecc(abft_hip_ctx *ctx, abft_hip_vector *X, abft_hip_vector *P,
+                                           const abft_hip_vector *R, int k, const double *alpha, const double *beta,
+                                           uint32_t active) {
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
+  if (!alpha || !beta) return set_err(ABFT_ERR_INVALID, "calc_px_block_vecc: null argument");
+  if (int rc = check_fused_block("calc_px_block_vecc", k, {R}, {X, P}, nullptr, false)) return rc;
+  BlockScalars a{}, b{};
+  for (int j = 0; j < k; j++) { a.v[j] = alpha[j]; b.v[j] = beta[j]; }
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  HIPCHK(launch_calc_px_block_vecc(X->d, P->d, R->d, X->n / k, k, a, b, active, ctx->ring, ctx->stream));
+  return ABFT_OK;
+}
+
 extern "C" int abft_hip_matrix_panels(abft_hip_matrix *mat, int *npanels, int *width) {
   if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
   if (npanels) *npanels = mat->layout == Layout::Sweep ? (int)mat->sweep.npanels : mat->layout == Layout::Slice ? (int)mat->slice.npanels : 1;

@@ -566,6 +566,16 @@ hipError_t launch_calc_r_vecc(double *r, const double *w, double alpha, int n, c
                               hipStream_t s);
 hipError_t launch_calc_px_vecc(double *x, double *p, const double *r, double alpha, double beta, int n, EventRing ev,
                                hipStream_t s);
+// the fused block iteration on protected block vectors: launch_spmm_dot_csr,
+// launch_dot_block, launch_calc_r_block and launch_calc_px_block on codewords
+hipError_t launch_spmm_dot_vecc_csr(int mode, int k, const CsrDev &A, const double *x, double *y, EventRing ev,
+                                    double *dotp, hipStream_t s);
+hipError_t launch_dot_block_vecc(const double *a, const double *b, int n, int k, const ReduceOutK &out, EventRing ev,
+                                 hipStream_t s);
+hipError_t launch_calc_r_block_vecc(double *r, const double *w, int n, int k, const BlockScalars &alpha,
+                                    uint32_t active, const ReduceOutK &out, EventRing ev, hipStream_t s);
+hipError_t launch_calc_px_block_vecc(double *x, double *p, const double *r, int n, int k, const BlockScalars &alpha,
+                                     const BlockScalars &beta, uint32_t active, EventRing ev, hipStream_t s);
 // their guarded forms (abft_hip_cg_vecc_iteration_until_dev): launch_calc_r_until's / launch_calc_px_until's protocol
 hipError_t launch_calc_r_vecc_until(double *r, const double *w, const double *rr, const double *pw, double threshold,
                                     double *alpha_out, int n, const ReduceOut &out, EventRing ev, hipStream_t s);

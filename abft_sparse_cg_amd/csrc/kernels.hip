@@ -1354,22 +1354,70 @@ __device__ __forceinline__ void spmm_gather(const double *__restrict__ x, uint32
   }
 }
 
+// VECC (abft_hip_spmm_dot_vecc): the gathered rows of x are codewords.  In the gather/add
+// loops a word is decoded to its value and one that fails vecc_suspect is only NOTED (no call where loads are in
+// flight) ...
+template <int K>
+__device__ __forceinline__ uint32_t spmm_decode(double *xv) {
+  uint32_t sus = 0u;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    const uint64_t w = vecc_bits(xv[j]);
+    sus |= vecc_suspect(w);
+    xv[j] = vecc_value(w);
+  }
+  return sus;
+}
+
+// ... and a row (in the long-row path: the current tile's share of it) whose gathers held a noted word is summed a
+// second time here, from the sums it started with, one element at a time: every word through the full decode
+// (repaired in registers, reported once; x is not written back -- many rows gather the same entry, and calc_px
+// rewrites it next).  Same elements, same order of adds: the sums have the undamaged call's bits.
+template <int K>
+__device__ __forceinline__ void spmm_row_redo(const double *__restrict__ x, uint32_t n_in, uint32_t k0, uint32_t k1,
+                                              const double *s_val, const uint32_t *s_col, EventRing ev, double *acc) {
+#pragma unroll 1
+  for (uint32_t k = k0; k < k1; k++) {
+    const uint32_t c = s_col[k];
+    const double v = s_val[k];
+    const bool in = c < n_in;
+    const uint32_t at = (in ? c : 0u) * (uint32_t)K;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const double xj = in ? vecc_decode_cold_ok(x + at + j, at + (uint32_t)j, 0u, ev) : 0.0;
+      acc[j] += v * xj;
+    }
+  }
+}
+
 // Row sums of elements [rs, re) from the staged elements, K columns, ascending element order.
 // Constraints mode runs csr_row_sum's checks (csr_check_element) in the same order, so the
 // same events are queued; returns false if a fatal one was.
-template <int MODE, int K>
+template <int MODE, int K, bool VECC = false>
 __device__ __forceinline__ bool spmm_row_sum(const CsrDev &A, const EventRing &ev, const double *__restrict__ x,
                                              uint32_t base, uint32_t rs, uint32_t re, uint32_t row_end,
                                              const double *s_val, const uint32_t *s_col, double *acc,
                                              uint32_t row) {
+  double start[K];  // VECC: the sums the row came in with, for the second summation
+  uint32_t sus = 0u;
+  if (VECC) {
+#pragma unroll
+    for (int j = 0; j < K; j++) start[j] = acc[j];
+  }
   if (MODE == MODE_CONSTRAINTS) {
     for (uint32_t i = rs; i < re; i++) {
       if (!csr_check_element(A, ev, base, i, re, row_end, s_col, row)) return false;
       double xv[K];
       spmm_gather<K>(x, s_col[i - base], A.n_in, xv);
+      if (VECC) sus |= spmm_decode<K>(xv);
       const double v = s_val[i - base];
 #pragma unroll
       for (int j = 0; j < K; j++) acc[j] += v * xv[j];
+    }
+    if (VECC && __builtin_expect(sus != 0u, 0)) {  // (every element passed its checks above: they are not run again)
+#pragma unroll
+      for (int j = 0; j < K; j++) acc[j] = start[j];
+      spmm_row_redo<K>(x, A.n_in, rs - base, re - base, s_val, s_col, ev, acc);
     }
     return true;
   }
@@ -1387,11 +1435,17 @@ __device__ __forceinline__ bool spmm_row_sum(const CsrDev &A, const EventRing &e
     }
 #pragma unroll
     for (int u = 0; u < U; u++) {
+      if (VECC) sus |= spmm_decode<K>(xv[u]);
       if (u == 0 || i + (uint32_t)u < re) {
 #pragma unroll
         for (int j = 0; j < K; j++) acc[j] += v[u] * xv[u][j];
       }
     }
+  }
+  if (VECC && __builtin_expect(sus != 0u, 0)) {
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] = start[j];
+    spmm_row_redo<K>(x, A.n_in, rs - base, re - base, s_val, s_col, ev, acc);
   }
   return true;
 }
@@ -1419,13 +1473,35 @@ __device__ __forceinline__ void spmm_dot_row(const double *__restrict__ x, uint3
   for (int j = 0; j < K; j++) dsum[j] += xr[j] * acc[j];
 }
 
+// VECC: row `row` of y stored encoded, and this thread's share of the K products from the decoded x[row, j] and
+// the stored word without its code bits (spmv_vecc's rule); x's row through the same two steps as the gathers:
+// checked, and only a row with a suspect word goes through the full decode
+template <int K>
+__device__ __forceinline__ void spmm_finish_row_vecc(const double *__restrict__ x, double *__restrict__ y, uint32_t row,
+                                                     uint32_t n_in, const EventRing &ev, double *acc, double *dsum) {
+#pragma unroll
+  for (int j = 0; j < K; j++) acc[j] = vecc_double(vecc_encode(acc[j]));
+  spmm_store_row<K>(y, row, acc);
+  double xr[K];
+  spmm_gather<K>(x, row, n_in, xr);
+  if (__builtin_expect(spmm_decode<K>(xr) != 0u, 0)) {
+    const uint32_t at = row * (uint32_t)K;
+#pragma unroll
+    for (int j = 0; j < K; j++) xr[j] = vecc_decode_cold_ok(x + at + j, at + (uint32_t)j, 0u, ev);
+  }
+#pragma unroll
+  for (int j = 0; j < K; j++) dsum[j] += xr[j] * vecc_value(vecc_bits(acc[j]));
+}
+
 // The block form of spmv_csr_kernel, whole matrix (reference lines as there).
 // DOT (abft_hip_spmm_dot): a square matrix; the thread that stores y[row, 0..K)
 // also adds x[row, j] * y[row, j] to its K running products -- a row of a long-row block once, when
 // thread 0's carried sums are complete.  The workgroup leaves K partials (block_sum's shape per column),
 // column j's at dotp[j * A.nblk + tile], with plain stores and exits, as fused_dot_finish does: no ticket
 // here.  spmm_fold_kernel, launched behind, folds them in a fixed order.
-template <int MODE, int EPT, int K, bool DOT = false>
+// VECC (with DOT only; abft_hip_spmm_dot_vecc): x and y hold protected elements -- spmm_row_sum and
+// spmm_finish_row_vecc above.
+template <int MODE, int EPT, int K, bool DOT = false, bool VECC = false>
 __global__ __launch_bounds__(ABFT_BLOCK) void spmm_csr_kernel(CsrDev A, const double *__restrict__ x,
                                                               double *__restrict__ y, EventRing ev,
                                                               double *__restrict__ dotp) {
@@ -1466,9 +1542,13 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmm_csr_kernel(CsrDev A, const do
       double acc[K];
 #pragma unroll
       for (int j = 0; j < K; j++) acc[j] = 0.0;
-      if (spmm_row_sum<MODE, K>(A, ev, x, base, rs, re, re, s_val, s_col, acc, row)) {
-        spmm_store_row<K>(y, row, acc);
-        if (DOT) spmm_dot_row<K>(x, row, A.n_in, acc, dsum);
+      if (spmm_row_sum<MODE, K, VECC>(A, ev, x, base, rs, re, re, s_val, s_col, acc, row)) {
+        if (VECC) {
+          spmm_finish_row_vecc<K>(x, y, row, A.n_in, ev, acc, dsum);
+        } else {
+          spmm_store_row<K>(y, row, acc);
+          if (DOT) spmm_dot_row<K>(x, row, A.n_in, acc, dsum);
+        }
       }
     }
   } else {
@@ -1491,12 +1571,16 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmm_csr_kernel(CsrDev A, const do
         __syncthreads();
         spmm_stage<MODE, EPT>(A, ev, b, lo, hi, s_val, s_col);
         __syncthreads();
-        if (threadIdx.x == 0 && ok) ok = spmm_row_sum<MODE, K>(A, ev, x, b, lo, hi, re, s_val, s_col, acc, row);
+        if (threadIdx.x == 0 && ok) ok = spmm_row_sum<MODE, K, VECC>(A, ev, x, b, lo, hi, re, s_val, s_col, acc, row);
         lo = hi;
       }
       if (threadIdx.x == 0 && ok) {
-        spmm_store_row<K>(y, row, acc);
-        if (DOT) spmm_dot_row<K>(x, row, A.n_in, acc, dsum);
+        if (VECC) {
+          spmm_finish_row_vecc<K>(x, y, row, A.n_in, ev, acc, dsum);
+        } else {
+          spmm_store_row<K>(y, row, acc);
+          if (DOT) spmm_dot_row<K>(x, row, A.n_in, acc, dsum);
+        }
       }
     }
   }
@@ -1510,11 +1594,11 @@ __global__ __launch_bounds__(ABFT_BLOCK) void spmm_csr_kernel(CsrDev A, const do
   }
 }
 
-template <int MODE, bool DOT>
+template <int MODE, bool DOT, bool VECC = false>
 static hipError_t launch_spmm_csr_mode(int k, const CsrDev &A, const double *x, double *y, EventRing ev,
                                        double *dotp, hipStream_t s) {
   const dim3 g(A.nblk), b(ABFT_BLOCK);
-#define ABFT_OP(K) hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, K, DOT>), g, b, 0, s, A, x, y, ev, dotp)
+#define ABFT_OP(K) hipLaunchKernelGGL((spmm_csr_kernel<MODE, ABFT_CSR_EPT, K, DOT, VECC>), g, b, 0, s, A, x, y, ev, dotp)
   switch (k) {
     case 1:  // without DOT, k = 1 is launch_spmv_csr
       if constexpr (DOT) { ABFT_OP(1); break; }
@@ -1532,17 +1616,17 @@ static hipError_t launch_spmm_csr_mode(int k, const CsrDev &A, const double *x, 
   return hipGetLastError();
 }
 
-template <bool DOT>
+template <bool DOT, bool VECC = false>
 static hipError_t launch_spmm_csr_any(int mode, int k, const CsrDev &A, const double *x, double *y, EventRing ev,
                                       double *dotp, hipStream_t s) {
   if (A.nblk == 0) return hipSuccess;
   switch (mode) {
-    case MODE_NONE: return launch_spmm_csr_mode<MODE_NONE, DOT>(k, A, x, y, ev, dotp, s);
-    case MODE_CONSTRAINTS: return launch_spmm_csr_mode<MODE_CONSTRAINTS, DOT>(k, A, x, y, ev, dotp, s);
-    case MODE_SED: return launch_spmm_csr_mode<MODE_SED, DOT>(k, A, x, y, ev, dotp, s);
-    case MODE_SEC7: return launch_spmm_csr_mode<MODE_SEC7, DOT>(k, A, x, y, ev, dotp, s);
-    case MODE_SEC8: return launch_spmm_csr_mode<MODE_SEC8, DOT>(k, A, x, y, ev, dotp, s);
-    case MODE_SECDED: return launch_spmm_csr_mode<MODE_SECDED, DOT>(k, A, x, y, ev, dotp, s);
+    case MODE_NONE: return launch_spmm_csr_mode<MODE_NONE, DOT, VECC>(k, A, x, y, ev, dotp, s);
+    case MODE_CONSTRAINTS: return launch_spmm_csr_mode<MODE_CONSTRAINTS, DOT, VECC>(k, A, x, y, ev, dotp, s);
+    case MODE_SED: return launch_spmm_csr_mode<MODE_SED, DOT, VECC>(k, A, x, y, ev, dotp, s);
+    case MODE_SEC7: return launch_spmm_csr_mode<MODE_SEC7, DOT, VECC>(k, A, x, y, ev, dotp, s);
+    case MODE_SEC8: return launch_spmm_csr_mode<MODE_SEC8, DOT, VECC>(k, A, x, y, ev, dotp, s);
+    case MODE_SECDED: return launch_spmm_csr_mode<MODE_SECDED, DOT, VECC>(k, A, x, y, ev, dotp, s);
     default: return hipErrorInvalidValue;
   }
 }
@@ -1555,6 +1639,11 @@ hipError_t launch_spmm_csr(int mode, int k, const CsrDev &A, const double *x, do
 hipError_t launch_spmm_dot_csr(int mode, int k, const CsrDev &A, const double *x, double *y, EventRing ev,
                                double *dotp, hipStream_t s) {
   return launch_spmm_csr_any<true>(mode, k, A, x, y, ev, dotp, s);
+}
+
+hipError_t launch_spmm_dot_vecc_csr(int mode, int k, const CsrDev &A, const double *x, double *y, EventRing ev,
+                                    double *dotp, hipStream_t s) {
+  return launch_spmm_csr_any<true, true>(mode, k, A, x, y, ev, dotp, s);
 }
 
 // ----------------------------------------------------------------- COO SpMV --
@@ -6569,6 +6658,225 @@ hipError_t launch_calc_px_vecc_until(double *x, double *p, const double *r, cons
     hipLaunchKernelGGL(calc_px_vecc_until_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, rr, rr_new, threshold, alpha_ptr, n, ev);
   else
     hipLaunchKernelGGL(calc_px_vecc_until_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, rr, rr_new, threshold, alpha_ptr, n, ev);
+  return hipGetLastError();
+}
+
+// ---- protected block vectors (abft_hip_dot_block_vecc, abft_hip_calc_r_block_vecc, abft_hip_calc_px_block_vecc;
+// DESIGN.md section 5m) ----
+// dot_block_kernel<K>, calc_r_block_kernel<K, false> and calc_px_block_kernel<K, false> on codewords: their grid, walk
+// (one row per thread step), block_load / block_store and reduce_finish_k, every multiply and add separate.  A STEP is
+// one row: all K columns of all operands, inactive columns included -- protection does not stop when a column
+// converges.  The discipline is that of the single kernels above: a step with a suspect word is only noted -- nothing
+// of it is stored or summed -- and behind the loop a thread with a noted step walks its chain once more.  There a
+// step that reads clean has been carried out and adds the stored values it left; a step that still fails has every
+// word decoded through vecc_cold (repair in registers, event with index row * K + column), is carried out and adds
+// what it stores.  An active column is computed; an inactive one is selected, never computed with, and in a written
+// operand its word is stored back as repaired: a clean word keeps every bit.  Per column the operations and roundings
+// of calc_r_vecc_walk / calc_px_vecc_walk: column j is, word for word, what they leave for column j alone.
+
+// bit 0: a word of the row fails its check
+template <int K>
+__device__ __forceinline__ uint32_t block_suspect(const double *v) {
+  uint32_t sus = 0u;
+#pragma unroll
+  for (int j = 0; j < K; j++) sus |= vecc_suspect(vecc_bits(v[j]));
+  return sus;
+}
+
+// the full decode of a word in a register -> the word as repaired (two flips: as it is)
+__device__ __forceinline__ uint64_t vecc_repaired(double v, uint32_t index, uint32_t operand, const EventRing &ev) {
+  uint64_t w = vecc_bits(v);
+  if (__builtin_expect(vecc_suspect(w) != 0u, 0)) w = vecc_cold(w, index, operand, ev).w;
+  return w;
+}
+
+// operands 0: a, 1: b; nothing is written
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void dot_block_vecc_kernel(const double *__restrict__ a,
+                                                                    const double *__restrict__ b, int n,
+                                                                    ReduceOutK out, EventRing ev) {
+  __shared__ double s_w[8 * K];
+  double acc[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) acc[j] = 0.0;
+  uint32_t bad = 0u;
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  const long first = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x;
+  for (long i = first; i < n; i += stride) {
+    double av[K], bv[K];
+    block_load<K>(a + i * K, av);
+    block_load<K>(b + i * K, bv);
+    const uint32_t sus = block_suspect<K>(av) | block_suspect<K>(bv);
+    bad |= sus;
+    if (!sus) {
+#pragma unroll
+      for (int j = 0; j < K; j++) acc[j] += vecc_value(vecc_bits(av[j])) * vecc_value(vecc_bits(bv[j]));
+    }
+  }
+  if (__builtin_expect(bad != 0u, 0)) {  // nothing was stored: the whole chain again, with the repairs
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] = 0.0;
+#pragma unroll 1
+    for (long i = first; i < n; i += stride) {
+      double av[K], bv[K];
+      block_load<K>(a + i * K, av);
+      block_load<K>(b + i * K, bv);
+#pragma unroll
+      for (int j = 0; j < K; j++) {
+        const uint32_t at = (uint32_t)(i * K + j);
+        const double x = vecc_value(vecc_repaired(av[j], at, 0u, ev));
+        acc[j] += x * vecc_value(vecc_repaired(bv[j], at, 1u, ev));
+      }
+    }
+  }
+  reduce_finish_k<K>(acc, out, s_w);
+}
+
+// R <- enc(val(R) - alpha_j val(W)) in the active columns; the K sums over the stored R of EVERY column, as
+// calc_r_block_kernel sums them: dot_block_vecc_kernel(R, R) of the R it leaves, bit for bit.  Operands 0: R, 1: W;
+// W is not written back.
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_vecc_kernel(double *__restrict__ r,
+                                                                       const double *__restrict__ w,
+                                                                       BlockScalars alpha, uint32_t active, int n,
+                                                                       ReduceOutK out, EventRing ev) {
+  __shared__ double s_w[8 * K];
+  double acc[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) acc[j] = 0.0;
+  uint32_t bad = 0u;
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  const long first = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x;
+  for (long i = first; i < n; i += stride) {
+    double rv[K], wv[K];
+    block_load<K>(r + i * K, rv);
+    block_load<K>(w + i * K, wv);
+    const uint32_t sus = block_suspect<K>(rv) | block_suspect<K>(wv);
+    bad |= sus;
+    if (!sus) {
+#pragma unroll
+      for (int j = 0; j < K; j++) {
+        const double rs = vecc_double(vecc_encode(vecc_value(vecc_bits(rv[j])) - alpha.v[j] * vecc_value(vecc_bits(wv[j]))));
+        rv[j] = ((active >> j) & 1u) ? rs : rv[j];
+        const double q = vecc_value(vecc_bits(rv[j]));
+        acc[j] += q * q;
+      }
+      block_store<K>(r + i * K, rv);
+    }
+  }
+  if (__builtin_expect(bad != 0u, 0)) {
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] = 0.0;
+#pragma unroll 1
+    for (long i = first; i < n; i += stride) {
+      double rv[K], wv[K];
+      block_load<K>(r + i * K, rv);  // a step carried out above: what it stored
+      block_load<K>(w + i * K, wv);
+      if (block_suspect<K>(rv) | block_suspect<K>(wv)) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+          const uint32_t at = (uint32_t)(i * K + j);
+          const uint64_t ro = vecc_repaired(rv[j], at, 0u, ev);
+          const uint64_t wo = vecc_repaired(wv[j], at, 1u, ev);
+          const uint64_t rs = vecc_encode(vecc_value(ro) - alpha.v[j] * vecc_value(wo));
+          rv[j] = vecc_double(((active >> j) & 1u) ? rs : ro);
+        }
+        block_store<K>(r + i * K, rv);
+      }
+#pragma unroll
+      for (int j = 0; j < K; j++) {
+        const double q = vecc_value(vecc_bits(rv[j]));
+        acc[j] += q * q;
+      }
+    }
+  }
+  reduce_finish_k<K>(acc, out, s_w);
+}
+
+// X <- enc(val(X) + alpha_j val(P)) and P <- enc(val(R) + beta_j val(P)), both from the old P, in the active columns.
+// Operands 0: X, 1: P, 2: R; R is not written back.
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_vecc_kernel(double *__restrict__ x, double *__restrict__ p,
+                                                                        const double *__restrict__ r,
+                                                                        BlockScalars alpha, BlockScalars beta,
+                                                                        uint32_t active, int n, EventRing ev) {
+  uint32_t bad = 0u;
+  const long stride = (long)gridDim.x * ABFT_BLOCK;
+  const long first = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x;
+  for (long i = first; i < n; i += stride) {
+    double xv[K], pv[K], rv[K];
+    block_load<K>(x + i * K, xv);
+    block_load<K>(p + i * K, pv);
+    block_load<K>(r + i * K, rv);
+    const uint32_t sus = block_suspect<K>(xv) | block_suspect<K>(pv) | block_suspect<K>(rv);
+    bad |= sus;
+    if (!sus) {
+#pragma unroll
+      for (int j = 0; j < K; j++) {
+        const bool on = (active >> j) & 1u;
+        const double po = vecc_value(vecc_bits(pv[j]));
+        const double xs = vecc_double(vecc_encode(vecc_value(vecc_bits(xv[j])) + alpha.v[j] * po));
+        const double ps = vecc_double(vecc_encode(vecc_value(vecc_bits(rv[j])) + beta.v[j] * po));
+        xv[j] = on ? xs : xv[j];
+        pv[j] = on ? ps : pv[j];
+      }
+      block_store<K>(x + i * K, xv);
+      block_store<K>(p + i * K, pv);
+    }
+  }
+  if (__builtin_expect(bad != 0u, 0)) {
+#pragma unroll 1
+    for (long i = first; i < n; i += stride) {
+      double xv[K], pv[K], rv[K];
+      block_load<K>(x + i * K, xv);
+      block_load<K>(p + i * K, pv);
+      block_load<K>(r + i * K, rv);
+      if (!(block_suspect<K>(xv) | block_suspect<K>(pv) | block_suspect<K>(rv))) continue;  // carried out above
+#pragma unroll
+      for (int j = 0; j < K; j++) {
+        const bool on = (active >> j) & 1u;
+        const uint32_t at = (uint32_t)(i * K + j);
+        const uint64_t xo = vecc_repaired(xv[j], at, 0u, ev);
+        const uint64_t po = vecc_repaired(pv[j], at, 1u, ev);
+        const uint64_t ro = vecc_repaired(rv[j], at, 2u, ev);
+        const uint64_t xs = vecc_encode(vecc_value(xo) + alpha.v[j] * vecc_value(po));
+        const uint64_t ps = vecc_encode(vecc_value(ro) + beta.v[j] * vecc_value(po));
+        xv[j] = vecc_double(on ? xs : xo);
+        pv[j] = vecc_double(on ? ps : po);
+      }
+      block_store<K>(x + i * K, xv);
+      block_store<K>(p + i * K, pv);
+    }
+  }
+}
+
+hipError_t launch_dot_block_vecc(const double *a, const double *b, int n, int k, const ReduceOutK &out, EventRing ev,
+                                 hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K) hipLaunchKernelGGL(dot_block_vecc_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, a, b, n, out, ev)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_r_block_vecc(double *r, const double *w, int n, int k, const BlockScalars &alpha,
+                                    uint32_t active, const ReduceOutK &out, EventRing ev, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K) \
+  hipLaunchKernelGGL(calc_r_block_vecc_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, alpha, active, n, out, ev)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_px_block_vecc(double *x, double *p, const double *r, int n, int k, const BlockScalars &alpha,
+                                     const BlockScalars &beta, uint32_t active, EventRing ev, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K) \
+  hipLaunchKernelGGL(calc_px_block_vecc_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, alpha, beta, active, n, ev)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
   return hipGetLastError();
 }
 

@@ -474,6 +474,36 @@ int abft_hip_calc_px_precond_block(abft_hip_ctx *ctx, abft_hip_vector *X, abft_h
                                    const abft_hip_vector *R, const abft_hip_vector *dinv, int k,
                                    const double *alpha, const double *beta, uint32_t active);
 
+/* The fused block iteration on PROTECTED block vectors: every double of the N x k
+ * blocks is a (64, 57) codeword, as in the abft_hip_*_vecc entries above; abft_hip_vector_encode, _scrub,
+ * _flip and _copy treat a block as N * k words (a scrub's event index is row * k + column).  Each entry is
+ * its plain twin on codewords -- same checks and refusals, same grid, walk and reductions -- that decodes
+ * every word it loads (inactive columns included), computes with the values in full fp64 and encodes every
+ * word it stores.  A word with one flipped bit is repaired in registers and reported once
+ * (ABFT_EV_VEC_CORRECTED, index row * k + column, bit | operand << 8); two flipped bits are
+ * ABFT_EV_VEC_DOUBLE (fatal).  With the same scalars and mask, column j of every vector is word for word
+ * what abft_hip_spmv_vecc, abft_hip_calc_r_vecc and abft_hip_calc_px_vecc leave for column j alone.
+ * A column whose bit is clear in `active` is never computed with; in a vector the call writes its words are
+ * stored back repaired (a clean word keeps every bit).
+ *
+ * W = enc(A val(P)), out[j] = sum over rows of val(P[row, j]) * strip(stored W[row, j]); P is operand 0 and is
+ * not written back.  Matrix elements are checked as in abft_hip_spmm_dot. */
+int abft_hip_spmm_dot_vecc(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *P,
+                           abft_hip_vector *W, int k, double *out);
+/* out[j] = sum val(a[:, j]) * val(b[:, j]) (operands 0: a, 1: b; nothing is written) */
+int abft_hip_dot_block_vecc(abft_hip_ctx *ctx, const abft_hip_vector *a, const abft_hip_vector *b, int k,
+                            double *out);
+/* R[:, j] = enc(val(R[:, j]) - alpha[j] val(W[:, j])) in the active columns; rr_out[j] = the sum of the squares
+ * of the stored R's values for EVERY column: the bits abft_hip_dot_block_vecc(R, R) then gives (operands 0: R,
+ * 1: W; W is not written back) */
+int abft_hip_calc_r_block_vecc(abft_hip_ctx *ctx, abft_hip_vector *R, const abft_hip_vector *W, int k,
+                               const double *alpha, uint32_t active, double *rr_out);
+/* in the active columns X[:, j] = enc(val(X) + alpha[j] val(P)) and P[:, j] = enc(val(R) + beta[j] val(P)), both
+ * from the P the call finds (operands 0: X, 1: P, 2: R; R is not written back) */
+int abft_hip_calc_px_block_vecc(abft_hip_ctx *ctx, abft_hip_vector *X, abft_hip_vector *P,
+                                const abft_hip_vector *R, int k, const double *alpha, const double *beta,
+                                uint32_t active);
+
 /* Shard-local forms for the row-partitioned solver: same kernels, but the
  * result stays on the device so a collective can sum it across ranks before
  * the host reads it.  `dev_result` is a device pointer to TWO doubles:
