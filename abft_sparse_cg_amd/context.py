@@ -706,6 +706,16 @@ class HIPContext:
                                                            None if dinv is None else dinv.h, k, base + 8 * in_at,
                                                            base + 8 * pw_at, base + 8 * out_at, threshold))
 
+    def cg_block_vecc_iteration_until_dev(self, mat, X, R, P, W, k, scalars, in_at, pw_at, out_at, threshold):
+        """one guarded iteration of the fused block loop on protected block vectors, enqueue-only
+        (abft_hip_cg_block_vecc_iteration_until_dev): cg_block_iteration_until_dev's arguments
+        and records without a dinv, the vectors codewords, the records plain doubles.  Vector events name their
+        operand as the single guarded entries do -- the gathered P, X, R, P, W = 0 .. 4 -- with index row * k + column.
+        CSR matrices in the streaming layout only.  Under graph capture: block_loop_reserve first"""
+        base = scalars.device_ptr
+        check(self.L.abft_hip_cg_block_vecc_iteration_until_dev(self.h, mat.h, X.h, R.h, P.h, W.h, k, base + 8 * in_at,
+                                                                base + 8 * pw_at, base + 8 * out_at, threshold))
+
     def block_loop_reserve(self, mat, k):
         """allocate what cg_block_iteration_until_dev needs for this matrix, so that it can be captured on a context
         that has not run it yet (abft_hip_block_loop_reserve); not under capture"""
@@ -1096,7 +1106,7 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
 
 
 def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
-                          stride=DEFAULT_STRIDE, graph=True, precond=None):
+                          stride=DEFAULT_STRIDE, graph=True, precond=None, vector_ecc=False):
     """cg_solve_block(fused=True)'s loop with the K alphas, the K betas and the column mask on the device (DESIGN.md
     section 5h): the host looks at the scalars once per batch of `stride` iterations instead of twice per iteration.
 
@@ -1115,14 +1125,36 @@ def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1
 
     on_iteration(itr, rr, active) as cg_solve_block calls it -- rr of all K columns from record i + 1 -- but AFTER the
     batch: the vectors it sees are the batch's end state.  -> (itrs[K], rr[K]) as cg_solve_block.
-    No check_every, no vector_ecc, one GPU."""
+
+    vector_ecc=True makes it cg_solve_block(vector_ecc=True)'s loop on protected block vectors:
+    the start is that loop's -- B and X encoded in place, R <- B scrubbed at once, P <- R, rr = dot_block_vecc(R, R)
+    --, then batches of ctx.cg_block_vecc_iteration_until_dev over the same trail of records, which are plain doubles
+    in device memory, outside any code; X and B are scrubbed before returning, on the early return as well (X and B
+    hold codewords then: vecc_strip what is downloaded).  Batches, the graph, the download, events, callbacks and the
+    return value are as above.  Refused (ValueError, before anything runs) with any precond and for a matrix
+    ctx.vecc_supported refuses.  With vector_ecc=False the calls are exactly those made without the argument.
+    No check_every, one GPU."""
     stride = _whole_stride(stride)
-    _check_protected_precond(precond, False)  # (the block loops have no protected form)
+    if vector_ecc:
+        if precond is not None:
+            raise ValueError("vector_ecc with a precond: the protected block loop has no Jacobi form")
+        if not ctx.vecc_supported(A):
+            raise ValueError("vector_ecc needs a CSR matrix in the streaming layout (this one: %s)"
+                             % ("COO" if A.fmt != FMT_CSR else ctx.matrix_info(A)[0]))
+    _check_protected_precond(precond, False)  # (a protected dinv has no block loop to go to)
     k = B.K
     if not k:
         raise ValueError("cg_solve_block_device wants block vectors (create_block)")
+    if vector_ecc:
+        ctx.encode_vector(B)
+        ctx.encode_vector(X)
     ctx.copy_vector(R, B)
-    if precond is None:
+    if vector_ecc:
+        ctx.scrub_vector(R)  # the one read of B: repaired in R, B itself stays as it is until the end
+        ctx.copy_vector(P, R)
+        rr = np.array(ctx.dot_block_vecc(R, R, k), dtype=np.float64)
+        rz = rr
+    elif precond is None:
         ctx.copy_vector(P, R)
         rr = np.array(ctx.dot_block(R, R, k), dtype=np.float64)
         rz = rr
@@ -1134,11 +1166,18 @@ def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1
     for j in range(k):
         note_threshold(rr[j], conv_threshold, noted)
     if max_itrs == 0 or not any(rr[j] > conv_threshold for j in range(k)):
+        if vector_ecc:
+            ctx.scrub_vector(X)
+            ctx.scrub_vector(B)
         return itrs, rr
     rec = 2 * k + 2  # doubles per record of the trail
     last_rr = [rr]
 
     def enqueue(trail, i, pw_at):
+        if vector_ecc:
+            ctx.cg_block_vecc_iteration_until_dev(A, X, R, P, W, k, trail, rec * i, pw_at, rec * (i + 1),
+                                                  conv_threshold)
+            return
         ctx.cg_block_iteration_until_dev(A, X, R, P, W, k, trail, rec * i, pw_at, rec * (i + 1), conv_threshold,
                                          dinv=precond)
 
@@ -1157,6 +1196,9 @@ def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1
 
     _device_batches(ctx, max_itrs, stride, graph, rec, k + 1, np.concatenate([rr, rz]), enqueue, record,
                     before_capture=lambda: ctx.block_loop_reserve(A, k))
+    if vector_ecc:
+        ctx.scrub_vector(X)
+        ctx.scrub_vector(B)
     return itrs, last_rr[0]
 
 

@@ -3798,11 +3798,12 @@ extern "C" int abft_hip_block_loop_reserve(abft_hip_ctx *ctx, abft_hip_matrix *m
   return block_loop_alloc(ctx, mat, k);
 }
 
-extern "C" int abft_hip_cg_block_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, abft_hip_vector *X,
-                                                     abft_hip_vector *R, abft_hip_vector *P, abft_hip_vector *W,
-                                                     const abft_hip_vector *dinv, int k, const double *dev_in,
-                                                     double *dev_pw, double *dev_out, double threshold) {
-  const char *what = "cg_block_iteration_until";
+// (vecc: the operands hold codewords -- abft_hip_cg_block_vecc_iteration_until_dev, dinv == nullptr.  Checks, records
+// and the line of four kernels are the same; the SpMM and the two guarded halves are the protected ones.)
+static int block_iteration_until(abft_hip_ctx *ctx, const char *what, bool vecc, abft_hip_matrix *mat,
+                                 abft_hip_vector *X, abft_hip_vector *R, abft_hip_vector *P, abft_hip_vector *W,
+                                 const abft_hip_vector *dinv, int k, const double *dev_in, double *dev_pw,
+                                 double *dev_out, double threshold) {
   if (int rc = enter(ctx, OTHER_VECTORS)) return rc;  // a pending x update applied, the fused product and the learned iteration forgotten
   if (!mat || !X || !R || !P || !W) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
   if (!dev_in || !dev_pw || !dev_out) return set_err(ABFT_ERR_INVALID, "%s: null device scalar", what);
@@ -3826,7 +3827,10 @@ extern "C" int abft_hip_cg_block_iteration_until_dev(abft_hip_ctx *ctx, abft_hip
   const int N = (int)mat->csr.n_out;
   {
     KernelTimer t(ctx, ABFT_K_SPMV);
-    HIPCHK(launch_spmm_dot_csr(mat->mode, k, mat->csr, P->d, W->d, ctx->ring, ctx->dotparts, ctx->stream));
+    if (vecc)
+      HIPCHK(launch_spmm_dot_vecc_csr(mat->mode, k, mat->csr, P->d, W->d, ctx->ring, ctx->dotparts, ctx->stream));
+    else
+      HIPCHK(launch_spmm_dot_csr(mat->mode, k, mat->csr, P->d, W->d, ctx->ring, ctx->dotparts, ctx->stream));
   }
   ReduceOutB o{};
   o.partials = ctx->bpartials;
@@ -3841,11 +3845,43 @@ extern "C" int abft_hip_cg_block_iteration_until_dev(abft_hip_ctx *ctx, abft_hip
   const double *dv = dinv ? dinv->d : nullptr;
   {
     KernelTimer t(ctx, ABFT_K_CALC_XR);
-    HIPCHK(launch_calc_r_block_until(R->d, W->d, dv, dev_in, dev_pw, threshold, ctx->balpha_dev, N, k, o, ctx->stream));
+    if (vecc)
+      HIPCHK(launch_calc_r_block_vecc_until(R->d, W->d, dev_in, dev_pw, threshold, ctx->balpha_dev, N, k, o, ctx->ring,
+                                            ctx->stream));
+    else
+      HIPCHK(launch_calc_r_block_until(R->d, W->d, dv, dev_in, dev_pw, threshold, ctx->balpha_dev, N, k, o, ctx->stream));
   }
   KernelTimer t(ctx, ABFT_K_CALC_P);
-  HIPCHK(launch_calc_px_block_until(X->d, P->d, R->d, dv, dev_in, dev_out, threshold, ctx->balpha_dev, N, k, ctx->stream));
+  if (vecc)
+    HIPCHK(launch_calc_px_block_vecc_until(X->d, P->d, R->d, dev_in, dev_out, threshold, ctx->balpha_dev, N, k, ctx->ring,
+                                           ctx->stream));
+  else
+    HIPCHK(launch_calc_px_block_until(X->d, P->d, R->d, dv, dev_in, dev_out, threshold, ctx->balpha_dev, N, k, ctx->stream));
   return ABFT_OK;
+}
+
+extern "C" int abft_hip_cg_block_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, abft_hip_vector *X,
+                                                     abft_hip_vector *R, abft_hip_vector *P, abft_hip_vector *W,
+                                                     const abft_hip_vector *dinv, int k, const double *dev_in,
+                                                     double *dev_pw, double *dev_out, double threshold) {
+  return block_iteration_until(ctx, "cg_block_iteration_until", false, mat, X, R, P, W, dinv, k, dev_in, dev_pw, dev_out,
+                               threshold);
+}
+
+// ---- the guarded block iteration on protected vectors ----------------
+// abft_hip_cg_block_iteration_until_dev with dinv == NULL, on codewords: the protected SpMM with its row-block
+// partials, their fold into dev_pw, the guarded protected r half, the guarded protected x / p half (kernels.hip,
+// calc_r_block_vecc_until_kernel).  Records and dev_pw are the plain entry's, plain doubles outside any code.  A live
+// column gets the bits abft_hip_spmm_dot_vecc + abft_hip_calc_r_block_vecc + abft_hip_calc_px_block_vecc leave with
+// the device's mask and the IEEE quotients; a frozen column of a live launch is checked and stored back repaired; a
+// launch with no live column touches no vector.  Vector events count the gathered P, X, R, P, W as operands 0..4, as
+// the single guarded entries do.  Every refusal comes before anything is enqueued.
+extern "C" int abft_hip_cg_block_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, abft_hip_vector *X,
+                                                          abft_hip_vector *R, abft_hip_vector *P, abft_hip_vector *W,
+                                                          int k, const double *dev_in, double *dev_pw, double *dev_out,
+                                                          double threshold) {
+  return block_iteration_until(ctx, "cg_block_vecc_iteration_until", true, mat, X, R, P, W, nullptr, k, dev_in, dev_pw,
+                               dev_out, threshold);
 }
 
 // what became of the calc_p and calc_r launched ahead: taken over by the caller's calls, or dropped

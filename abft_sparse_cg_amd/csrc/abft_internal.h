@@ -656,6 +656,14 @@ hipError_t launch_calc_r_block_until(double *r, const double *w, const double *d
 hipError_t launch_calc_px_block_until(double *x, double *p, const double *r, const double *dinv, const double *in,
                                       const double *out, double threshold, const double *alpha_ptr, int n, int k,
                                       hipStream_t s);
+// their protected twins (abft_hip_cg_block_vecc_iteration_until_dev): the plain forms' protocol in front of the walks
+// of launch_calc_r_block_vecc / launch_calc_px_block_vecc; vector events count X, R, P, W as operands 1..4
+hipError_t launch_calc_r_block_vecc_until(double *r, const double *w, const double *in, const double *pw,
+                                          double threshold, double *alpha_out, int n, int k, const ReduceOutB &out,
+                                          EventRing ev, hipStream_t s);
+hipError_t launch_calc_px_block_vecc_until(double *x, double *p, const double *r, const double *in, const double *out,
+                                           double threshold, const double *alpha_ptr, int n, int k, EventRing ev,
+                                           hipStream_t s);
 hipError_t launch_precond_start_block(const double *r, const double *dinv, double *p, int n, int k, uint32_t mask,
                                       const ReduceOutW &out, hipStream_t s);
 hipError_t launch_calc_xr_precond_block(double *x, double *r, const double *p, const double *w, const double *dinv,

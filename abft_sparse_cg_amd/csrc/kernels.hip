@@ -6733,17 +6733,14 @@ __global__ __launch_bounds__(ABFT_BLOCK) void dot_block_vecc_kernel(const double
 }
 
 // R <- enc(val(R) - alpha_j val(W)) in the active columns; the K sums over the stored R of EVERY column, as
-// calc_r_block_kernel sums them: dot_block_vecc_kernel(R, R) of the R it leaves, bit for bit.  Operands 0: R, 1: W;
-// W is not written back.
+// calc_r_block_kernel sums them: dot_block_vecc_kernel(R, R) of the R it leaves, bit for bit.  W is not written back.
+// (calc_r_block_vecc_walk: the one body of calc_r_block_vecc_kernel and calc_r_block_vecc_until_kernel.  alpha: K
+// scalars, the kernel argument's array or the guarded kernel's own; op_*: the ordinal a repaired word of that operand
+// is reported under, as in calc_r_vecc_walk; acc: the K sums, zero on entry)
 template <int K>
-__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_vecc_kernel(double *__restrict__ r,
-                                                                       const double *__restrict__ w,
-                                                                       BlockScalars alpha, uint32_t active, int n,
-                                                                       ReduceOutK out, EventRing ev) {
-  __shared__ double s_w[8 * K];
-  double acc[K];
-#pragma unroll
-  for (int j = 0; j < K; j++) acc[j] = 0.0;
+__device__ __forceinline__ void calc_r_block_vecc_walk(double *__restrict__ r, const double *__restrict__ w,
+                                                       const double *alpha, uint32_t active, int n, uint32_t op_r,
+                                                       uint32_t op_w, const EventRing &ev, double *acc) {
   uint32_t bad = 0u;
   const long stride = (long)gridDim.x * ABFT_BLOCK;
   const long first = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x;
@@ -6756,7 +6753,7 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_vecc_kernel(double *_
     if (!sus) {
 #pragma unroll
       for (int j = 0; j < K; j++) {
-        const double rs = vecc_double(vecc_encode(vecc_value(vecc_bits(rv[j])) - alpha.v[j] * vecc_value(vecc_bits(wv[j]))));
+        const double rs = vecc_double(vecc_encode(vecc_value(vecc_bits(rv[j])) - alpha[j] * vecc_value(vecc_bits(wv[j]))));
         rv[j] = ((active >> j) & 1u) ? rs : rv[j];
         const double q = vecc_value(vecc_bits(rv[j]));
         acc[j] += q * q;
@@ -6776,9 +6773,9 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_vecc_kernel(double *_
 #pragma unroll
         for (int j = 0; j < K; j++) {
           const uint32_t at = (uint32_t)(i * K + j);
-          const uint64_t ro = vecc_repaired(rv[j], at, 0u, ev);
-          const uint64_t wo = vecc_repaired(wv[j], at, 1u, ev);
-          const uint64_t rs = vecc_encode(vecc_value(ro) - alpha.v[j] * vecc_value(wo));
+          const uint64_t ro = vecc_repaired(rv[j], at, op_r, ev);
+          const uint64_t wo = vecc_repaired(wv[j], at, op_w, ev);
+          const uint64_t rs = vecc_encode(vecc_value(ro) - alpha[j] * vecc_value(wo));
           rv[j] = vecc_double(((active >> j) & 1u) ? rs : ro);
         }
         block_store<K>(r + i * K, rv);
@@ -6790,16 +6787,16 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_vecc_kernel(double *_
       }
     }
   }
-  reduce_finish_k<K>(acc, out, s_w);
 }
 
 // X <- enc(val(X) + alpha_j val(P)) and P <- enc(val(R) + beta_j val(P)), both from the old P, in the active columns.
-// Operands 0: X, 1: P, 2: R; R is not written back.
+// R is not written back.
+// (calc_px_block_vecc_walk: the one body of calc_px_block_vecc_kernel and calc_px_block_vecc_until_kernel)
 template <int K>
-__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_vecc_kernel(double *__restrict__ x, double *__restrict__ p,
-                                                                        const double *__restrict__ r,
-                                                                        BlockScalars alpha, BlockScalars beta,
-                                                                        uint32_t active, int n, EventRing ev) {
+__device__ __forceinline__ void calc_px_block_vecc_walk(double *__restrict__ x, double *__restrict__ p,
+                                                        const double *__restrict__ r, const double *alpha,
+                                                        const double *beta, uint32_t active, int n, uint32_t op_x,
+                                                        uint32_t op_p, uint32_t op_r, const EventRing &ev) {
   uint32_t bad = 0u;
   const long stride = (long)gridDim.x * ABFT_BLOCK;
   const long first = (long)blockIdx.x * ABFT_BLOCK + threadIdx.x;
@@ -6815,8 +6812,8 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_vecc_kernel(double *
       for (int j = 0; j < K; j++) {
         const bool on = (active >> j) & 1u;
         const double po = vecc_value(vecc_bits(pv[j]));
-        const double xs = vecc_double(vecc_encode(vecc_value(vecc_bits(xv[j])) + alpha.v[j] * po));
-        const double ps = vecc_double(vecc_encode(vecc_value(vecc_bits(rv[j])) + beta.v[j] * po));
+        const double xs = vecc_double(vecc_encode(vecc_value(vecc_bits(xv[j])) + alpha[j] * po));
+        const double ps = vecc_double(vecc_encode(vecc_value(vecc_bits(rv[j])) + beta[j] * po));
         xv[j] = on ? xs : xv[j];
         pv[j] = on ? ps : pv[j];
       }
@@ -6836,11 +6833,11 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_vecc_kernel(double *
       for (int j = 0; j < K; j++) {
         const bool on = (active >> j) & 1u;
         const uint32_t at = (uint32_t)(i * K + j);
-        const uint64_t xo = vecc_repaired(xv[j], at, 0u, ev);
-        const uint64_t po = vecc_repaired(pv[j], at, 1u, ev);
-        const uint64_t ro = vecc_repaired(rv[j], at, 2u, ev);
-        const uint64_t xs = vecc_encode(vecc_value(xo) + alpha.v[j] * vecc_value(po));
-        const uint64_t ps = vecc_encode(vecc_value(ro) + beta.v[j] * vecc_value(po));
+        const uint64_t xo = vecc_repaired(xv[j], at, op_x, ev);
+        const uint64_t po = vecc_repaired(pv[j], at, op_p, ev);
+        const uint64_t ro = vecc_repaired(rv[j], at, op_r, ev);
+        const uint64_t xs = vecc_encode(vecc_value(xo) + alpha[j] * vecc_value(po));
+        const uint64_t ps = vecc_encode(vecc_value(ro) + beta[j] * vecc_value(po));
         xv[j] = vecc_double(on ? xs : xo);
         pv[j] = vecc_double(on ? ps : po);
       }
@@ -6848,6 +6845,103 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_vecc_kernel(double *
       block_store<K>(p + i * K, pv);
     }
   }
+}
+
+// calc_r_block on protected vectors (operands 0: R, 1: W)
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_vecc_kernel(double *__restrict__ r,
+                                                                       const double *__restrict__ w,
+                                                                       BlockScalars alpha, uint32_t active, int n,
+                                                                       ReduceOutK out, EventRing ev) {
+  __shared__ double s_w[8 * K];
+  double acc[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) acc[j] = 0.0;
+  calc_r_block_vecc_walk<K>(r, w, alpha.v, active, n, 0u, 1u, ev, acc);
+  reduce_finish_k<K>(acc, out, s_w);
+}
+
+// calc_px_block on protected vectors (operands 0: X, 1: P, 2: R)
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_vecc_kernel(double *__restrict__ x, double *__restrict__ p,
+                                                                        const double *__restrict__ r,
+                                                                        BlockScalars alpha, BlockScalars beta,
+                                                                        uint32_t active, int n, EventRing ev) {
+  calc_px_block_vecc_walk<K>(x, p, r, alpha.v, beta.v, active, n, 0u, 1u, 2u, ev);
+}
+
+// The guarded forms (abft_hip_cg_block_vecc_iteration_until_dev): calc_r_block_until_kernel's
+// and calc_px_block_until_kernel's protocol, word for word, in front of the protected block walks.  Records, mask,
+// quotients and the hand-off are the plain guarded kernels' (PRECOND = false); records and dev_pw are plain doubles
+// outside any code.  Operands as the guarded entries count them: X 1, R 2, P 3, W 4 (0 is the SpMM's gathered P).
+// A launch with no live column touches no vector: it repairs nothing and reports nothing.
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_vecc_until_kernel(double *__restrict__ r,
+                                                                             const double *__restrict__ w,
+                                                                             const double *in, const double *pw,
+                                                                             double threshold, double *alpha_out,
+                                                                             int n, ReduceOutB out, EventRing ev) {
+  __shared__ double s_w[8 * K];
+  const uint32_t active = block_live_mask<K>(in, threshold);
+  const unsigned long long *src = reinterpret_cast<const unsigned long long *>(in);
+  unsigned long long *dst = reinterpret_cast<unsigned long long *>(out.dev_out);
+  if (!active) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      // the bits, whatever they are (a NaN's payload included): moved as integers
+      unsigned long long b[2 * K];
+#pragma unroll
+      for (int j = 0; j < 2 * K; j++) b[j] = src[j];
+#pragma unroll
+      for (int j = 0; j < 2 * K; j++) dst[j] = b[j];
+      out.dev_out[2 * K] = (double)__hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      out.dev_out[2 * K + 1] = 0.0;
+    }
+    return;
+  }
+  double alpha[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) alpha[j] = uniform_f64(in[K + j] / pw[j]);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {  // for the x / p half
+#pragma unroll
+    for (int j = 0; j < K; j++) alpha_out[j] = alpha[j];
+  }
+  double acc[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) acc[j] = 0.0;
+  calc_r_block_vecc_walk<K>(r, w, alpha, active, n, 2u, 4u, ev, acc);
+  double tot[K];
+  if (!reduce_totals_k<K, ReduceOutB, uint32_t>(acc, out, s_w, tot) || threadIdx.x != 0) return;
+  const uint32_t nev = reduce_rearm(out);
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    // a live column's new sum in both words; a frozen one's words as they were read, not the recomputed sum
+    const unsigned long long rr_new = __double_as_longlong(tot[j]);
+    const bool on = (active >> j) & 1u;
+    const unsigned long long rr_old = src[j], rz_old = src[K + j];
+    dst[j] = on ? rr_new : rr_old;
+    dst[K + j] = on ? rr_new : rz_old;
+  }
+  out.dev_out[2 * K] = (double)nev;
+  out.dev_out[2 * K + 1] = 0.0;
+}
+
+// (in: the record the iteration started from -- the mask, and beta's denominators; out: what the r half left)
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_vecc_until_kernel(double *__restrict__ x,
+                                                                              double *__restrict__ p,
+                                                                              const double *__restrict__ r,
+                                                                              const double *in, const double *out,
+                                                                              double threshold, const double *alpha_ptr,
+                                                                              int n, EventRing ev) {
+  const uint32_t active = block_live_mask<K>(in, threshold);
+  if (!active) return;
+  double alpha[K], beta[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    alpha[j] = alpha_ptr[j];
+    beta[j] = uniform_f64(out[K + j] / in[K + j]);
+  }
+  calc_px_block_vecc_walk<K>(x, p, r, alpha, beta, active, n, 1u, 3u, 2u, ev);
 }
 
 hipError_t launch_dot_block_vecc(const double *a, const double *b, int n, int k, const ReduceOutK &out, EventRing ev,
@@ -6875,6 +6969,31 @@ hipError_t launch_calc_px_block_vecc(double *x, double *p, const double *r, int 
   const int nb = reduce_blocks(n);
 #define ABFT_OP(K) \
   hipLaunchKernelGGL(calc_px_block_vecc_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, alpha, beta, active, n, ev)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_r_block_vecc_until(double *r, const double *w, const double *in, const double *pw,
+                                          double threshold, double *alpha_out, int n, int k, const ReduceOutB &out,
+                                          EventRing ev, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K)                                                                                                 \
+  hipLaunchKernelGGL(calc_r_block_vecc_until_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, in, pw, threshold, \
+                     alpha_out, n, out, ev)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_calc_px_block_vecc_until(double *x, double *p, const double *r, const double *in, const double *out,
+                                           double threshold, const double *alpha_ptr, int n, int k, EventRing ev,
+                                           hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K)                                                                                               \
+  hipLaunchKernelGGL(calc_px_block_vecc_until_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, in, out, \
+                     threshold, alpha_ptr, n, ev)
   ABFT_BLOCK_K_DISPATCH(ABFT_OP)
 #undef ABFT_OP
   return hipGetLastError();

@@ -890,6 +890,34 @@ int abft_hip_cg_block_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *ma
                                           const abft_hip_vector *dinv, int k, const double *dev_in, double *dev_pw,
                                           double *dev_out, double threshold);
 
+/* The guarded block iteration on PROTECTED vectors: abft_hip_cg_block_iteration_until_dev with dinv == NULL, on
+ * codewords.  X, R, P and W hold codewords; the records (2k + 2 doubles) and dev_pw (k + 1 doubles) are the plain
+ * entry's: plain doubles in device memory, outside any code.
+ *   Column j LIVE (dev_in[j] > threshold, false for NaN): its column of X, R and P, dev_pw[j], dev_out[j] and
+ *          dev_out[k + j] are bit for bit what abft_hip_spmm_dot_vecc, abft_hip_calc_r_block_vecc and
+ *          abft_hip_calc_px_block_vecc leave when called with the mask of the live columns, alpha[j] = dev_in[k + j] /
+ *          P.W[j] and beta[j] = r.r'[j] / dev_in[k + j] as IEEE quotients.
+ *   Column j FROZEN in a launch with a live column: dev_out[j] and dev_out[k + j] get the bits of dev_in[j] and
+ *          dev_in[k + j] (moved as integers: a NaN keeps its payload); its words of R, X and P are checked and stored
+ *          back repaired -- a clean word keeps every bit --, as those calls do with that mask.
+ *   NO column live: X, R and P keep every bit, a word with a flipped bit included: such a launch of the two vector
+ *          kernels repairs nothing and reports nothing; the record is handed on as integers with the queued-event
+ *          count and 0.0; replaying changes nothing.  The SpMM still runs, with its matrix checks, its gather checks
+ *          on P and their events.
+ * Vector events (ABFT_EV_VEC_CORRECTED, ABFT_EV_VEC_DOUBLE) use the single guarded entries' numbering: 0 the P that
+ * the SpMM gathers, 1 X, 2 R, 3 P, 4 W -- the r half reports R as 2 and W as 4, the x / p half X as 1, R as 2 and P
+ * as 3 --, with index row * k + column.
+ * Four kernels in a line: the protected SpMM with its row-block partials, their fold into dev_pw, the guarded r half,
+ * the guarded x / p half; no workgroup waits for another.  Enqueue-only and capturable; leaves nothing pending.
+ * Refused before anything is enqueued, every operand and record left as it was: everything
+ * abft_hip_cg_block_iteration_until_dev refuses (overlaps, records, a peer board, k), and everything
+ * abft_hip_spmm_dot_vecc refuses about the matrix (the message names the layout, or COO).
+ * Under graph capture the call needs what abft_hip_block_loop_reserve allocates and returns ABFT_ERR_INVALID naming
+ * it otherwise; an eager call allocates it itself. */
+int abft_hip_cg_block_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, abft_hip_vector *X,
+                                               abft_hip_vector *R, abft_hip_vector *P, abft_hip_vector *W, int k,
+                                               const double *dev_in, double *dev_pw, double *dev_out, double threshold);
+
 /* Allocate what abft_hip_cg_block_iteration_until_dev needs for this matrix and k (any k up to ABFT_MAX_RHS is then
  * covered), so that the iteration can be captured on a fresh context.  Eager only: refused under graph capture. */
 int abft_hip_block_loop_reserve(abft_hip_ctx *ctx, abft_hip_matrix *mat, int k);

@@ -10,6 +10,7 @@ laplace5:3162,3162 (config 2, 10 M rows), laplace5:1000,1000 and laplace5:316,31
                                       [--specs laplace5:1000,1000,...] [--strides 4,8,16,32]
                                       [--precond jacobi] [--rhs 4,8 [--modes none,secded]]
                                       [--vector-ecc [--precond jacobi] [--modes none,secded]]
+                                      [--vector-ecc --rhs 4,8 [--modes none,secded]]
 
 --precond jacobi alternates cg_solve(precond=dinv) and cg_solve_device(precond=dinv) instead,
 dinv = ctx.jacobi(A); the JSON says so under `precond`, in the file and in every row.  The yardstick is then
@@ -34,6 +35,14 @@ cg_solve(vector_ecc=True, precond=dinv) and cg_solve_device(vector_ecc=True, pre
 ctx.jacobi(A, protected=True) made once per context.  The yardstick is the protected host PCG loop of the same build;
 both loops pay the same start and the same end (three scrubs now) inside the timed window.  --out defaults to
 profiles/device_loop_bench_vecc_precond.json there; the rows say precond: jacobi.
+
+--vector-ecc --rhs K[,K...] measures the block loops on protected vectors: three loops over the
+same iterations -- cg_solve_block(vector_ecc=True), cg_solve_block_device(vector_ecc=True) and, for context, the plain
+cg_solve_block_device -- alternating on the same matrix (streaming layout) and the same K seeded right-hand sides, with
+the specs, strides and modes of --rhs; the per-column counts are asserted equal.  The yardstick is the protected host
+block loop of the same build; both protected loops pay the same start and end inside the timed window.  --out defaults
+to profiles/device_loop_bench_block_vecc.json there.  --precond jacobi is refused: the protected block loops have no
+Jacobi form.
 
 Also reported per matrix: `best_stride`, the smallest stride within 2 % of the best device-loop time (what
 DEFAULT_STRIDE is to be on the 1 M-row matrix), and `frozen_spmv_worst`, stride - 1: the SpMVs a solve can waste
@@ -82,14 +91,21 @@ BLOCK_SPECS = ("laplace5:3162,3162", "laplace5:1000,1000")
 BLOCK_STRIDES = (4, 16, 64)
 
 
-def timed_block_solve(ctx, A, vecs, n, k, its, stride, dinv=None):
-    """stride 0: cg_solve_block(fused=True); else cg_solve_block_device -> (ms, per-column counts)"""
+def timed_block_solve(ctx, A, vecs, n, k, its, stride, dinv=None, vecc=False, b=None):
+    """stride 0: cg_solve_block(fused=True); else cg_solve_block_device; vecc: the loops on protected block vectors (b:
+    the right-hand sides, uploaded again outside the timed window -- a protected solve leaves codewords in them)
+    -> (ms, per-column counts)"""
+    kw = {"vector_ecc": True} if vecc else {}
+    if b is not None:
+        ctx.upload(vecs[0], b)
     ctx.upload(vecs[1], np.zeros((n, k)))
     ctx.synchronize()
     t0 = time.perf_counter()
     if stride:
         itrs, _ = amd.cg_solve_block_device(ctx, A, *vecs, max_itrs=its, conv_threshold=THRESHOLD, stride=stride,
-                                            precond=dinv)
+                                            precond=dinv, **kw)
+    elif vecc:
+        itrs, _ = amd.cg_solve_block(ctx, A, *vecs, max_itrs=its, conv_threshold=THRESHOLD, vector_ecc=True)
     else:
         itrs, _ = amd.cg_solve_block(ctx, A, *vecs, max_itrs=its, conv_threshold=THRESHOLD, precond=dinv, fused=True)
     ctx.synchronize()
@@ -132,6 +148,54 @@ def block_main(a, res):
                            best_stride=min(st for st in strides if dev[st] <= 1.02 * best),
                            frozen_spmm_worst={str(st): st - 1 for st in strides},
                            blocks={str(st): v for st, v in per.items()})
+                res["rows"].append(row)
+                print(json.dumps(row), flush=True)
+                for v in vecs:
+                    ctx.destroy_vector(v)
+            ctx.close()
+        del cols, rows, vals
+
+
+def block_vecc_main(a, res):
+    """--vector-ecc --rhs: the block loops on protected vectors, one row per (matrix, mode, K).  Kinds: ("host", 0) the
+    protected host loop, ("vecc", stride) the protected device loop, ("plain", stride) the plain device loop"""
+    strides = [int(s) for s in (a.strides or ",".join(str(s) for s in BLOCK_STRIDES)).split(",")]
+    res["rhs"] = [int(k) for k in a.rhs.split(",")]
+    res["vector_ecc"] = True
+    res["modes"] = a.modes.split(",")
+    for spec in (a.specs or ";".join(BLOCK_SPECS)).split(";"):
+        cols, rows, vals, n = generators.generate(spec)
+        nnz = len(vals)
+        for mode in res["modes"]:
+            ctx = amd.HIPContext(mode, "csr", on_event=lambda ev, fatal: None)
+            A = ctx.create_matrix(cols, rows, vals, n, nnz, layout="stream")
+            for k in res["rhs"]:
+                vecs = [ctx.create_block(n, k) for _ in range(5)]
+                b = np.random.default_rng(7).random((n, k)) + 0.5
+                kinds = [("host", 0)] + [("vecc", st) for st in strides] + [("plain", st) for st in strides]
+
+                def run(kind, its):
+                    return timed_block_solve(ctx, A, vecs, n, k, its, kind[1], vecc=kind[0] != "plain", b=b)
+                for kind in kinds:  # warm-up: first launches, the graph's instantiation path
+                    run(kind, max(kind[1], 5))
+                per = {kind: [] for kind in kinds}
+                for _ in range(a.blocks):
+                    for kind in kinds:
+                        ms, itrs = run(kind, a.iters)
+                        assert itrs == [a.iters] * k, (spec, mode, k, kind, itrs)  # equal counts, all live
+                        per[kind].append(ms / a.iters)
+                host = statistics.median(per[("host", 0)])
+                dev = {st: statistics.median(per[("vecc", st)]) for st in strides}
+                plain = {st: statistics.median(per[("plain", st)]) for st in strides}
+                best = min(dev.values())
+                row = dict(spec=spec, fmt="csr", mode=mode, layout=ctx.matrix_info(A)[0], vector_ecc=True, precond="none",
+                           rhs=k, n=n, nnz=nnz, ms_per_iter_host_vecc=host,
+                           ms_per_iter_device_vecc={str(st): v for st, v in dev.items()},
+                           ms_per_iter_device_plain={str(st): v for st, v in plain.items()},
+                           ratio_device_over_host={str(st): v / host for st, v in dev.items()},
+                           best_stride=min(st for st in strides if dev[st] <= 1.02 * best),
+                           frozen_spmm_worst={str(st): st - 1 for st in strides},
+                           blocks={"%s:%d" % kind: v for kind, v in per.items()})
                 res["rows"].append(row)
                 print(json.dumps(row), flush=True)
                 for v in vecs:
@@ -195,11 +259,18 @@ def main():
     ap.add_argument("--modes", default="none,secded", help="with --rhs or --vector-ecc: the ECC modes")
     ap.add_argument("--vector-ecc", action="store_true", help="the loops on protected vectors")
     a = ap.parse_args()
-    if a.vector_ecc and a.rhs:
-        ap.error("--vector-ecc does not go with --rhs")
+    if a.vector_ecc and a.rhs and a.precond == "jacobi":
+        ap.error("--vector-ecc --rhs does not go with --precond jacobi: the protected block loops have no Jacobi form")
     argv = [v for i, v in enumerate(sys.argv) if v != "--out" and (i == 0 or sys.argv[i - 1] != "--out")]
     res = {"cmd": " ".join(argv), "iters": a.iters, "blocks": a.blocks, "threshold": THRESHOLD,
            "precond": a.precond, "rows": []}
+    if a.rhs and a.vector_ecc:
+        a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_block_vecc.json")
+        block_vecc_main(a, res)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        return 0
     if a.rhs:
         a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_block.json")
         block_main(a, res)
