@@ -721,6 +721,20 @@ class HIPContext:
         that has not run it yet (abft_hip_block_loop_reserve); not under capture"""
         check(self.L.abft_hip_block_loop_reserve(self.h, mat.h, k))
 
+    def residual_check_dev(self, mat, b, x, r, scratch, x_ckpt, trail, chk_at, limit):
+        """a whole residual check, enqueue-only, its verdict formed and acted on on the device
+        (abft_hip_residual_check_dev): scratch = A x, then trail[chk_at .. chk_at + 3] =
+        {sum ((b - Ax) - r)^2, sum (b - Ax)^2, verdict, queued events} -- the sums residual_gap returns, verdict 1.0
+        when the first is <= limit and both are finite, else 2.0 --, then x_ckpt <- x when it passed, x <- x_ckpt
+        when not.  trail: a vector of device doubles.  Under graph capture: residual_check_reserve first"""
+        check(self.L.abft_hip_residual_check_dev(self.h, mat.h, b.h, x.h, r.h, scratch.h, x_ckpt.h,
+                                                 trail.device_ptr + 8 * chk_at, limit))
+
+    def residual_check_reserve(self):
+        """allocate what residual_check_dev needs, so that it can be captured on a context that has made no
+        K-wide reduction yet (abft_hip_residual_check_reserve); not under capture"""
+        check(self.L.abft_hip_residual_check_reserve(self.h))
+
     def graph_begin(self):
         """start capturing the asynchronous calls on the context's stream (include/abft_hip.h, graph replay)"""
         check(self.L.abft_hip_graph_begin(self.h))
@@ -1007,8 +1021,117 @@ def _device_batches(ctx, max_itrs, stride, graph, rec, tail, seed, enqueue, reco
     return done
 
 
+def _check_batch(done, max_itrs, stride, check_every):
+    """The batch schedule of cg_solve_device(check_every > 0): -> (m, check), the length of the batch that starts
+    at iteration count done < max_itrs and whether a residual check is enqueued behind its last iteration.  A batch
+    never crosses a check position (the counts that are multiples of check_every), so the check follows exactly the
+    iterations i with (i + 1) % check_every == 0.  From a multiple of check_every on -- the start, and the count
+    after every periodic check, rollbacks included -- two shapes recur: (stride, False), and
+    ((check_every - 1) % stride + 1, True)."""
+    next_check = (done // check_every + 1) * check_every
+    m = min(stride, max_itrs - done, next_check - done)
+    return m, done + m == next_check
+
+
+def _device_batches_checked(ctx, A, b, x, r, w, x_ckpt, max_itrs, stride, graph, rec, seed, enqueue, record, goes_on,
+                            restart, check_every, check_tol, max_rollbacks, bb, on_check):
+    """_device_batches with residual checks.  The trail has four more doubles behind the p.w
+    pair (at chk_at = pw_at + 2) for ctx.residual_check_dev.  A batch of m iterations uses records stride - m ..
+    stride, so that record `stride` holds the latest scalars after every batch, whatever its length: it copies
+    record `stride` to record stride - m, calls enqueue(trail, i, pw_at) for i = stride - m .. stride - 1 and, when
+    _check_batch says so, enqueues the check behind them.  The two recurring shapes are captured once each (behind
+    ctx.residual_check_reserve) and replayed when `graph`; every other batch is enqueued call by call.  The download
+    of the trail stays the one synchronisation; record(t, i, done) as in _device_batches, then the check's slot.
+    goes_on(): cg_solve's `rr > conv_threshold` on the last live r.r.  restart() -> the seed of a recurrence
+    restarted from the restored x.  -> the count of live iterations."""
+    pw_at = rec * (stride + 1)
+    chk_at = pw_at + 2
+    trail = ctx.create_vector(chk_at + 4)
+    last, chk = ctx.view_vector(trail, rec * stride, rec), ctx.view_vector(trail, chk_at, 4)
+    firsts, graphs = {}, {}
+    start = np.zeros(chk_at + 4)
+    start[rec * stride:rec * stride + len(seed)] = seed
+    ctx.upload(trail, start)
+    limit = check_tol * check_tol * bb  # as _check_passes forms it
+    recurring = ((stride, False), ((check_every - 1) % stride + 1, True))
+    st = dict(checked=False, ckpt=-1, fails=0, records=[])
+    done = 0
+
+    def batch(m, check):
+        ctx.copy_vector(firsts[m], last)
+        for i in range(stride - m, stride):
+            enqueue(trail, i, pw_at)
+        if check:
+            ctx.residual_check_dev(A, b, x, r, w, x_ckpt, trail, chk_at, limit)
+
+    def verdict(c):
+        """the slot of a check that followed iteration done - 1: the device has copied x to the checkpoint (passed)
+        or the checkpoint back into x (anything else)"""
+        gap2, ok = float(c[0]), c[2] == 1.0
+        gap = math.sqrt(gap2) if gap2 >= 0 else gap2
+        back = None
+        if ok:
+            st["ckpt"] = done - 1
+        else:
+            st["fails"] += 1
+            back = st["ckpt"]
+            again = np.zeros(rec)
+            new = restart()
+            again[:len(new)] = new
+            ctx.upload(last, again)
+        st["checked"] = True
+        st["records"].append((done - 1, gap, ok, back))
+        if on_check is not None:
+            on_check(done - 1, gap, ok, back)
+        if not ok and (st["fails"] > max_rollbacks or done >= max_itrs):
+            raise ResidualCheckFailed(
+                "residual check failed at iteration %d (gap %.3e > %.3e) %s; x holds the checkpoint of %s"
+                % (done - 1, gap, check_tol * math.sqrt(bb),
+                   "after %d rollbacks" % (st["fails"] - 1) if done < max_itrs else "at max_itrs",
+                   _ckpt_name(back)), st["records"])
+
+    try:
+        while True:
+            if not (done < max_itrs and goes_on()):
+                if st["checked"]:
+                    break
+                # the final state, which no check has seen: the one extra synchronisation of a solve
+                ctx.residual_check_dev(A, b, x, r, w, x_ckpt, trail, chk_at, limit)
+                verdict(ctx.download(chk))
+                continue
+            m, check = _check_batch(done, max_itrs, stride, check_every)
+            if m not in firsts:
+                firsts[m] = ctx.view_vector(trail, rec * (stride - m), rec)
+            if graph and (m, check) in recurring:
+                if (m, check) not in graphs:
+                    ctx.residual_check_reserve()
+                    ctx.graph_begin()
+                    try:
+                        batch(m, check)
+                    finally:
+                        graphs[(m, check)] = ctx.graph_end()
+                ctx.graph_launch(graphs[(m, check)])
+            else:
+                batch(m, check)
+            t = ctx.download(trail)  # synchronises, then drains the events
+            for i in range(stride - m, stride):
+                if not record(t, i, done):
+                    break  # frozen: a check behind this batch has seen the final state
+                done += 1
+                st["checked"] = False
+            if check:
+                verdict(t[chk_at:chk_at + 4])
+    finally:
+        for g in graphs.values():
+            ctx.graph_destroy(g)
+        for v in list(firsts.values()) + [last, chk, trail]:
+            ctx.destroy_vector(v)
+    return done
+
+
 def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
-                    stride=DEFAULT_STRIDE, graph=True, precond=None, vector_ecc=False):
+                    stride=DEFAULT_STRIDE, graph=True, precond=None, vector_ecc=False, check_every=0,
+                    check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None):
     """cg_solve's loop (cg.cpp:87-118) with alpha, beta and the stop test on the device:
     the host looks at the scalars once per batch of `stride` iterations instead of twice per iteration.
 
@@ -1045,8 +1168,27 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
     (DESIGN.md section 5l): that start -- rz, rr0 = precond_start_vecc(r, dinv, p) behind the scrub of r --, then
     batches of ctx.pcg_vecc_iteration_until_dev over the preconditioned trail of four-double records, and x, b and
     dinv are scrubbed before returning.  A precond not marked protected is refused with vector_ecc, a protected one
-    without it (ValueError, before anything runs)."""
+    without it (ValueError, before anything runs).
+
+    check_every > 0 adds cg_solve's residual checks with rollback (check_tol, max_rollbacks,
+    x_ckpt, on_check and ResidualCheckFailed as there), the download after a batch still the only synchronisation.
+    No batch crosses a check position (_check_batch): a batch that ends on one has ctx.residual_check_dev enqueued
+    behind its last iteration -- w the scratch vector --, which forms the verdict on the device with the host's pass
+    rule (limit = check_tol^2 * rr0) and acts on it there: x_ckpt <- x when the check passed, x <- x_ckpt when not.
+    The trail has four more doubles behind the p.w pair for {gap^2, tt^2, verdict, events}; a batch of m iterations
+    uses records stride - m .. stride.  With graph=True the two recurring batches -- `stride` iterations, and
+    (check_every - 1) % stride + 1 iterations plus the check -- are captured once each; anything else is enqueued call
+    by call.  After the download on_iteration runs for the live iterations, then on_check(itr, gap, ok,
+    rolled_back_to) when the batch carried a check; a check behind a batch in which the loop froze has seen the final
+    state.  After a failed check the host restarts the recurrence (ctx.residual_restart, with precond
+    ctx.precond_start), reseeds record `stride` and goes on, the iteration count running on as in cg_solve.  When the
+    loop is about to stop on a state no check has seen, one check is enqueued on its own and its slot downloaded: the
+    one extra synchronisation of a solve.  precond (a plain dinv) is supported; vector_ecc=True with check_every > 0
+    is refused as in cg_solve.  With check_every=0 the calls are exactly those made without the arguments."""
     stride = _whole_stride(stride)
+    _check_args(check_every, check_tol, max_rollbacks)
+    if vector_ecc and check_every:
+        raise ValueError("vector_ecc with check_every > 0: the residual kernels write unencoded vectors")
     protected = _check_protected_precond(precond, vector_ecc)
     if vector_ecc:
         if not ctx.vecc_supported(A):
@@ -1095,6 +1237,28 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
             on_iteration(done, last_rr[0])
         return True
 
+    if check_every:
+        def restart():
+            last_rr[0] = ctx.residual_restart(A, b, x, r, p, w)
+            new = [last_rr[0]]
+            if precond is not None:
+                rz, last_rr[0] = ctx.precond_start(r, precond, p)  # p = z of the restarted r
+                new = [last_rr[0], 0.0, rz]
+            note_threshold(last_rr[0], conv_threshold, noted)
+            return new
+
+        own_ckpt = x_ckpt is None
+        if own_ckpt:
+            x_ckpt = ctx.create_vector(x.N)
+        try:
+            ctx.copy_vector(x_ckpt, x)
+            done = _device_batches_checked(ctx, A, b, x, r, w, x_ckpt, max_itrs, stride, graph, rec, seed, enqueue,
+                                           record, lambda: last_rr[0] > conv_threshold, restart, int(check_every),
+                                           check_tol, max_rollbacks, rr, on_check)  # bb = rr: r = b, ||b||^2
+        finally:
+            if own_ckpt:
+                ctx.destroy_vector(x_ckpt)
+        return done, last_rr[0]
     if max_itrs != 0 and rr > conv_threshold:
         done = _device_batches(ctx, max_itrs, stride, graph, rec, 2, seed, enqueue, record)
     if vector_ecc:

@@ -231,13 +231,14 @@ static int flush_deferred(abft_hip_ctx *ctx) {
 //                                  matrix_compact_stats, matrix_packed_stats, matrix_destroy, matrix_read_csr, _read_coo,
 //                                  _read_element, inject, inject_rowptr, vector_create, vector_map, vector_device_ptr,
 //                                  dot_dev, calc_xr_dev, calc_xr_ratio_dev, peer_exchange_begin, cg_iteration_until_dev,
-//                                  pcg_iteration_until_dev, cg_vecc_iteration_until_dev, pcg_vecc_iteration_until_dev, block_loop_reserve, graph_begin, drain_events, profile_*,
+//                                  pcg_iteration_until_dev, cg_vecc_iteration_until_dev, pcg_vecc_iteration_until_dev, block_loop_reserve, residual_check_reserve, graph_begin, drain_events, profile_*,
 //                                  stream_probe
 //   FORGET_FUSED                   vector_unmap, vector_copy, graph_launch
 //   FORGET_ITER                    dot_vecc
 //   OTHER_VECTORS                  vector_destroy, matrix_diag_inverse, vector_flip, vector_encode, vector_scrub,
 //    (= FORGET_FUSED | FORGET_ITER)  calc_xr_vecc, calc_p_vecc, calc_r_vecc, calc_px_vecc, precond_start_vecc, calc_r_precond_vecc, calc_px_precond_vecc, spmm, dot_block, calc_xr_block, calc_p_block, copy_block,
 //                                  residual_gap, residual_restart, residual_gap_block, residual_restart_block,
+//                                  residual_check_dev,
 //                                  spmm_dot, calc_r[_precond]_block, calc_px[_precond]_block, precond_start[_block],
 //                                  calc_xr_precond[_block], calc_p_precond_block, cg_block_iteration_until_dev
 //   KEEP_DEFERRED                  read_pair, write_pair, allreduce_pair_peers, calc_p_ratio_dev, peer_board_attach,
@@ -2842,6 +2843,52 @@ extern "C" int abft_hip_residual_restart(abft_hip_ctx *ctx, abft_hip_matrix *A, 
     HIPCHK(launch_residual_restart(b->d, scratch->d, r->d, p->d, r->n, o, ctx->stream));
   }
   return scalar_from_host_slot(ctx, o.seq, rr);
+}
+
+// ---- a whole check, verdict and rollback on the device ----------------
+// abft_hip_residual_gap without its way back to the host: the same SpMV, the same walk and sums (kernels.hip,
+// residual_check_kernel) with {gap2, tt2, verdict, queued events} left in dev_chk, then residual_guard_kernel, which
+// copies x to x_ckpt or x_ckpt to x by that verdict.  Enqueue-only; under capture nothing may be allocated, so the
+// K-wide partials must exist by then (abft_hip_residual_check_reserve).
+extern "C" int abft_hip_residual_check_reserve(abft_hip_ctx *ctx) {
+  if (int rc = enter(ctx, 0)) return rc;
+  if (ctx->capturing) return set_err(ABFT_ERR_INVALID, "residual_check_reserve: called under graph capture (it allocates)");
+  return block_slot(ctx);
+}
+
+extern "C" int abft_hip_residual_check_dev(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *b,
+                                           abft_hip_vector *x, const abft_hip_vector *r, abft_hip_vector *scratch,
+                                           abft_hip_vector *x_ckpt, double *dev_chk, double limit) {
+  const char *what = "residual_check_dev";
+  if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
+  if (!dev_chk || !x_ckpt) return set_err(ABFT_ERR_INVALID, "%s: null %s", what, dev_chk ? "checkpoint" : "device result");
+  if (int rc = check_residual_args(what, A, b, x, r, scratch, nullptr)) return rc;
+  if (x_ckpt->n != x->n)
+    return set_err(ABFT_ERR_INVALID, "%s: the checkpoint has %d entries, x %d", what, x_ckpt->n, x->n);
+  const std::initializer_list<const abft_hip_vector *> operands = {b, x, r, scratch};
+  for (const abft_hip_vector *v : operands)
+    if (!disjoint(x_ckpt, v)) return set_err(ABFT_ERR_INVALID, "%s: the checkpoint overlaps an operand", what);
+  const std::initializer_list<const abft_hip_vector *> vectors = {b, x, r, scratch, x_ckpt};
+  for (const abft_hip_vector *v : vectors)
+    if (dev_chk + 4 > v->d && dev_chk < v->d + v->n)
+      return set_err(ABFT_ERR_INVALID, "%s: the four result words lie inside a vector of the call", what);
+  if (ctx->capturing && !ctx->bslot)
+    return set_err(ABFT_ERR_INVALID, "%s: called under graph capture before the context's block partials exist; call "
+                   "abft_hip_residual_check_reserve first", what);
+  if (int rc = block_slot(ctx)) return rc;
+  if (int rc = spmv_common(ctx, A, x, scratch, 0, nullptr)) return rc;
+  forget_fused(*ctx);
+  ReduceOutB o{};
+  o.partials = ctx->bpartials;
+  o.ticket = ctx->ticket;
+  o.dev_out = dev_chk;
+  o.ev_count = ctx->ring.count;
+  {
+    KernelTimer t(ctx, ABFT_K_DOT);
+    HIPCHK(launch_residual_check(b->d, scratch->d, r->d, b->n, limit, o, ctx->stream));
+  }
+  HIPCHK(launch_residual_guard(x->d, x_ckpt->d, dev_chk, x->n, ctx->stream));
+  return ABFT_OK;
 }
 
 // the block vectors of a block check, against a matrix of N rows (spmm refuses what it cannot run

@@ -664,6 +664,12 @@ hipError_t launch_calc_r_block_vecc_until(double *r, const double *w, const doub
 hipError_t launch_calc_px_block_vecc_until(double *x, double *p, const double *r, const double *in, const double *out,
                                            double threshold, const double *alpha_ptr, int n, int k, EventRing ev,
                                            hipStream_t s);
+// launch_residual_gap with its two sums, the verdict and the events word left in out.dev_out[0..3] (device memory):
+// verdict 1.0 when gap2 <= limit and both sums are finite, else 2.0 (abft_hip_residual_check_dev)
+hipError_t launch_residual_check(const double *b, const double *y, const double *r, int n, double limit,
+                                 const ReduceOutB &out, hipStream_t s);
+// behind it: chk[2] == 1.0: x_ckpt <- x, else x <- x_ckpt (n doubles each, disjoint)
+hipError_t launch_residual_guard(double *x, double *x_ckpt, const double *chk, int n, hipStream_t s);
 hipError_t launch_precond_start_block(const double *r, const double *dinv, double *p, int n, int k, uint32_t mask,
                                       const ReduceOutW &out, hipStream_t s);
 hipError_t launch_calc_xr_precond_block(double *x, double *r, const double *p, const double *w, const double *dinv,

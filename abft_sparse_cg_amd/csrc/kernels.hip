@@ -4490,13 +4490,11 @@ __global__ void flip_vector_kernel(double *v, unsigned long long mask) {
 
 // {gap2, tt2} = {sum ((b - y) - r)^2, sum (b - y)^2}.  (b - y) - r in that order: with r equal to the
 // rounded b - y the gap of every element is exactly 0.
+// (the element walk, shared by residual_gap_kernel and residual_check_kernel as section 5i shares bodies: acc[0] +=
+// every gap squared, acc[1] += every (b - y) squared, a thread's elements in the order of dot_kernel<VEC>)
 template <int VEC>
-__global__ __launch_bounds__(ABFT_BLOCK) void residual_gap_kernel(const double *__restrict__ b,
-                                                                  const double *__restrict__ y,
-                                                                  const double *__restrict__ r, int n,
-                                                                  ReduceOutK out) {
-  __shared__ double s_w[16];
-  double acc[2] = {0.0, 0.0};
+__device__ __forceinline__ void residual_gap_walk(const double *__restrict__ b, const double *__restrict__ y,
+                                                  const double *__restrict__ r, int n, double *acc) {
   const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
   for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC; i < n; i += stride) {
     if (VEC == 2 && i + 1 < n) {
@@ -4516,10 +4514,67 @@ __global__ __launch_bounds__(ABFT_BLOCK) void residual_gap_kernel(const double *
       acc[1] += t * t;
     }
   }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void residual_gap_kernel(const double *__restrict__ b,
+                                                                  const double *__restrict__ y,
+                                                                  const double *__restrict__ r, int n,
+                                                                  ReduceOutK out) {
+  __shared__ double s_w[16];
+  double acc[2] = {0.0, 0.0};
+  residual_gap_walk<VEC>(b, y, r, n, acc);
   reduce_finish_k<2>(acc, out, s_w);
 }
 
-// r = b - y, p = r, and r.r.  VEC is the element walk of dot_kernel<VEC> on r (the grid too:
+// residual_gap_kernel with the verdict formed where the sums are: the last arriver folds the block partials in its
+// fixed order (the same two totals, bit for bit) and thread 0 leaves {gap2, tt2, verdict, queued events} in
+// out.dev_out, device memory, with vector stores -- verdict 1.0 when gap2 <= limit and both sums are finite (the
+// host's pass rule, context.py _check_passes, with limit = check_tol^2 ||b||^2 formed there: a NaN fails the
+// comparison), else 2.0.  residual_guard_kernel behind it acts on the word.
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void residual_check_kernel(const double *__restrict__ b,
+                                                                    const double *__restrict__ y,
+                                                                    const double *__restrict__ r, int n, double limit,
+                                                                    ReduceOutB out) {
+  __shared__ double s_w[16];
+  double acc[2] = {0.0, 0.0};
+  residual_gap_walk<VEC>(b, y, r, n, acc);
+  double tot[2];
+  if (!reduce_totals_k<2>(acc, out, s_w, tot) || threadIdx.x != 0) return;
+  const uint32_t nev = reduce_rearm(out);
+  const bool ok = tot[0] <= limit && __builtin_isfinite(tot[0]) && __builtin_isfinite(tot[1]);
+  out.dev_out[0] = tot[0];
+  out.dev_out[1] = tot[1];
+  out.dev_out[2] = ok ? 1.0 : 2.0;
+  out.dev_out[3] = (double)nev;
+}
+
+// the check's verdict acted on: chk[2] == 1.0 (passed): x_ckpt <- x; anything else: x <- x_ckpt.  Every thread reads
+// the word, which this kernel never writes: the decision is uniform over the grid and no workgroup waits for
+// another.  Plain copies, never a 0 / 1 mask (0 * inf is NaN; copy_block_kernel); PAIRS: both 16-byte aligned.
+template <bool PAIRS>
+__global__ __launch_bounds__(ABFT_BLOCK) void residual_guard_kernel(double *x, double *x_ckpt,
+                                                                    const double *__restrict__ chk, int n) {
+  const bool passed = chk[2] == 1.0;
+  double *dst = passed ? x_ckpt : x;
+  const double *src = passed ? x : x_ckpt;
+  const long stride = (long)gridDim.x * ABFT_BLOCK * 2;
+  for (long i = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * 2; i < n; i += stride) {
+    if (i + 1 < n) {
+      if (PAIRS) {
+        *reinterpret_cast<double2 *>(dst + i) = *reinterpret_cast<const double2 *>(src + i);
+      } else {
+        const double s0 = src[i], s1 = src[i + 1];
+        dst[i] = s0; dst[i + 1] = s1;
+      }
+    } else {
+      dst[i] = src[i];
+    }
+  }
+}
+
+// r = b - y, p = r, and r.r. VEC is the element walk of dot_kernel<VEC> on r (the grid too:
 // reduce_blocks(n)), so r.r is abft_hip_dot(r, r) bit for bit; PAIRS: every operand 16-byte
 // aligned (VEC = 2 without it loads the pairs one by one, same order of additions).
 template <int VEC, bool PAIRS>
@@ -4647,6 +4702,27 @@ hipError_t launch_residual_gap(const double *b, const double *y, const double *r
     hipLaunchKernelGGL(residual_gap_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, n, out);
   else
     hipLaunchKernelGGL(residual_gap_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, n, out);
+  return hipGetLastError();
+}
+
+// (grid and VEC exactly as launch_residual_gap chooses them: the two sums are its bits)
+hipError_t launch_residual_check(const double *b, const double *y, const double *r, int n, double limit,
+                                 const ReduceOutB &out, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  if (aligned16(b, y, r))
+    hipLaunchKernelGGL(residual_check_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, n, limit, out);
+  else
+    hipLaunchKernelGGL(residual_check_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, n, limit, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_residual_guard(double *x, double *x_ckpt, const double *chk, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+  if (aligned16(x, x_ckpt))
+    hipLaunchKernelGGL(residual_guard_kernel<true>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, x_ckpt, chk, n);
+  else
+    hipLaunchKernelGGL(residual_guard_kernel<false>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, x_ckpt, chk, n);
   return hipGetLastError();
 }
 

@@ -922,6 +922,27 @@ int abft_hip_cg_block_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matri
  * covered), so that the iteration can be captured on a fresh context.  Eager only: refused under graph capture. */
 int abft_hip_block_loop_reserve(abft_hip_ctx *ctx, abft_hip_matrix *mat, int k);
 
+/* ---- a residual check whose verdict is formed and acted on on the device ----
+ * abft_hip_residual_gap for the device-scalar loop: enqueue-only and capturable, nothing comes back to the host but
+ * what it downloads from dev_chk later.  Three things in a line on the context's stream:
+ *   1. scratch = A x, the SpMV of abft_hip_residual_gap (every format, layout and mode; its checks, repairs, events);
+ *   2. dev_chk[0..3] = {gap2, tt2, verdict, queued events}: gap2 = sum ((b - scratch) - r)^2 and tt2 =
+ *      sum (b - scratch)^2 are bit for bit what abft_hip_residual_gap returns for the same operands; verdict = 1.0
+ *      (passed) when gap2 <= limit and both sums are finite, else 2.0 (a NaN fails the comparison);
+ *   3. every thread of a third kernel reads the verdict: passed, x_ckpt <- x; failed, x <- x_ckpt (plain copies: an
+ *      inf or NaN moves as it is).  No workgroup waits for another.
+ * b and r are only read.  Starts like abft_hip_residual_gap (a pending x update applied, cached results forgotten).
+ * Refused before anything is enqueued: a null argument, what abft_hip_residual_gap refuses about the lengths and the
+ * scratch vector, an x_ckpt that has not x's length or overlaps b, x, r or scratch, and dev_chk within one of the
+ * vectors.  Under graph capture the context must hold the partials of a K-wide reduction: ABFT_ERR_INVALID naming
+ * abft_hip_residual_check_reserve otherwise; an eager call allocates them itself. */
+int abft_hip_residual_check_dev(abft_hip_ctx *ctx, abft_hip_matrix *A, const abft_hip_vector *b,
+                                abft_hip_vector *x, const abft_hip_vector *r, abft_hip_vector *scratch,
+                                abft_hip_vector *x_ckpt, double *dev_chk, double limit);
+/* Allocate what abft_hip_residual_check_dev needs, so that it can be captured on a fresh context.  Idempotent.
+ * Eager only: ABFT_ERR_INVALID under graph capture. */
+int abft_hip_residual_check_reserve(abft_hip_ctx *ctx);
+
 /* ---- graph replay ------------------------------------------------------ */
 
 /* Capture everything enqueued on the context's stream between begin and end -- the

@@ -11,6 +11,7 @@ laplace5:3162,3162 (config 2, 10 M rows), laplace5:1000,1000 and laplace5:316,31
                                       [--precond jacobi] [--rhs 4,8 [--modes none,secded]]
                                       [--vector-ecc [--precond jacobi] [--modes none,secded]]
                                       [--vector-ecc --rhs 4,8 [--modes none,secded]]
+                                      [--check-every 50 [--precond jacobi] [--modes none,secded]]
 
 --precond jacobi alternates cg_solve(precond=dinv) and cg_solve_device(precond=dinv) instead,
 dinv = ctx.jacobi(A); the JSON says so under `precond`, in the file and in every row.  The yardstick is then
@@ -43,6 +44,13 @@ the specs, strides and modes of --rhs; the per-column counts are asserted equal.
 block loop of the same build; both protected loops pay the same start and end inside the timed window.  --out defaults
 to profiles/device_loop_bench_block_vecc.json there.  --precond jacobi is refused: the protected block loops have no
 Jacobi form.
+
+--check-every N measures the cost of residual checks in the device-resident loop:
+cg_solve_device without checks and cg_solve_device(check_every=N) alternating in one process on the same matrix, in
+every mode of --modes, at the strides of --strides (default 16); the checkpoint vector is made once and passed in.  The
+yardstick is the same loop without checks of the same build; `ratio_check_over_plain` is the figure.  Every check
+must pass (asserted).  Matrices by default laplace5:3162,3162 and laplace5:1000,1000.  --out defaults to
+profiles/device_loop_bench_check.json there.  Without the flag nothing changes.
 
 Also reported per matrix: `best_stride`, the smallest stride within 2 % of the best device-loop time (what
 DEFAULT_STRIDE is to be on the 1 M-row matrix), and `frozen_spmv_worst`, stride - 1: the SpMVs a solve can waste
@@ -247,6 +255,64 @@ def vecc_main(a, res):
         del cols, rows, vals
 
 
+CHECK_SPECS = ("laplace5:3162,3162", "laplace5:1000,1000")
+CHECK_STRIDES = (16,)
+
+
+def check_main(a, res):
+    """--check-every N: cg_solve_device without and with residual checks, one row per (matrix, mode).  Kinds:
+    ("plain", stride) and ("check", stride), the checkpoint vector made once and passed in"""
+    strides = [int(s) for s in (a.strides or ",".join(str(s) for s in CHECK_STRIDES)).split(",")]
+    res["check_every"] = a.check_every
+    res["modes"] = a.modes.split(",")
+    for spec in (a.specs or ";".join(CHECK_SPECS)).split(";"):
+        cols, rows, vals, n = generators.generate(spec)
+        nnz = len(vals)
+        for mode in res["modes"]:
+            ctx = amd.HIPContext(mode, "csr", on_event=lambda ev, fatal: None)
+            A = ctx.create_matrix(cols, rows, vals, n, nnz)
+            vecs = [ctx.create_vector(n) for _ in range(5)]
+            ckpt = ctx.create_vector(n)
+            ctx.upload(vecs[0], generators.reference_rhs(n))
+            dinv = ctx.jacobi(A) if a.precond == "jacobi" else None
+            kinds = [(kind, st) for st in strides for kind in ("plain", "check")]
+            checks = []
+
+            def run(kind, its):
+                kw = dict(check_every=a.check_every, x_ckpt=ckpt, on_check=lambda *c: checks.append(c[2])) \
+                    if kind[0] == "check" else {}
+                ctx.upload(vecs[1], np.zeros(n))
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                itr, _ = amd.cg_solve_device(ctx, A, *vecs, max_itrs=its, conv_threshold=THRESHOLD, stride=kind[1],
+                                             precond=dinv, **kw)
+                ctx.synchronize()
+                return (time.perf_counter() - t0) * 1e3, itr
+            for kind in kinds:  # warm-up: first launches, the graphs' instantiation path
+                run(kind, max(kind[1], a.check_every, 5))
+            per = {kind: [] for kind in kinds}
+            n_checks = 0
+            for _ in range(a.blocks):
+                for kind in kinds:
+                    del checks[:]
+                    ms, itr = run(kind, a.iters)
+                    assert itr == a.iters and all(checks), (spec, mode, kind, itr, checks)  # all live, nothing rolled back
+                    n_checks = max(n_checks, len(checks))
+                    per[kind].append(ms / a.iters)
+            plain = {st: statistics.median(per[("plain", st)]) for st in strides}
+            chk = {st: statistics.median(per[("check", st)]) for st in strides}
+            row = dict(spec=spec, fmt="csr", mode=mode, layout=ctx.matrix_info(A)[0], precond=a.precond, n=n, nnz=nnz,
+                       check_every=a.check_every, checks_per_solve=n_checks,
+                       ms_per_iter_plain={str(st): v for st, v in plain.items()},
+                       ms_per_iter_check={str(st): v for st, v in chk.items()},
+                       ratio_check_over_plain={str(st): chk[st] / plain[st] for st in strides},
+                       blocks={"%s:%d" % kind: v for kind, v in per.items()})
+            res["rows"].append(row)
+            print(json.dumps(row), flush=True)
+            ctx.close()
+        del cols, rows, vals
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -258,12 +324,25 @@ def main():
     ap.add_argument("--rhs", default=None, help="K[,K...]: the block loops with K right-hand sides")
     ap.add_argument("--modes", default="none,secded", help="with --rhs or --vector-ecc: the ECC modes")
     ap.add_argument("--vector-ecc", action="store_true", help="the loops on protected vectors")
+    ap.add_argument("--check-every", type=int, default=0,
+                    help="N: cg_solve_device with a residual check every N iterations against the same loop without")
     a = ap.parse_args()
     if a.vector_ecc and a.rhs and a.precond == "jacobi":
         ap.error("--vector-ecc --rhs does not go with --precond jacobi: the protected block loops have no Jacobi form")
+    if a.check_every and (a.vector_ecc or a.rhs):
+        ap.error("--check-every goes with neither --vector-ecc nor --rhs: those loops have no residual checks")
+    if a.check_every < 0:
+        ap.error("--check-every must be >= 0")
     argv = [v for i, v in enumerate(sys.argv) if v != "--out" and (i == 0 or sys.argv[i - 1] != "--out")]
     res = {"cmd": " ".join(argv), "iters": a.iters, "blocks": a.blocks, "threshold": THRESHOLD,
            "precond": a.precond, "rows": []}
+    if a.check_every:
+        a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_check.json")
+        check_main(a, res)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        return 0
     if a.rhs and a.vector_ecc:
         a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_block_vecc.json")
         block_vecc_main(a, res)
