@@ -3665,27 +3665,74 @@ extern "C" int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat
 // Always the three-kernel route (fold, r half, x / p half), the two halves in their guarded forms
 // (kernels.hip, calc_r_until_kernel): cg_tail_kernel's hand-off words must grow by every launch's
 // amounts, and a launch that returned early would break the bases the next one starts from.
+//
+// iteration_until: the one body of the four single guarded entries below.  vecc: the operands hold codewords (the
+// protected SpMV and the protected halves); dinv: the preconditioned entries' (then the scalars are records of four
+// doubles, else pairs), nullptr for the plain ones.  Every refusal comes before anything is enqueued.
+static int iteration_until(abft_hip_ctx *ctx, const char *what, bool vecc, abft_hip_matrix *mat,
+                           const abft_hip_vector *vec, int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                           abft_hip_vector *p, abft_hip_vector *w, const abft_hip_vector *dinv, bool precond,
+                           const double *dev_in, double *dev_pw, double *dev_out, double threshold) {
+  if (int rc = enter(ctx, 0)) return rc;  // a pending x update applied, a speculation voided
+  if (int rc = check_guarded_iteration(ctx, what, mat, vec, vec_offset, part, x, r, p, w, precond, dinv, dev_in, dev_pw,
+                                       dev_out))
+    return rc;
+  // what spmv_vecc refuses, refused here under the entry's name: spmv_common would forget the learned iteration first,
+  // and a refused call leaves the state alone
+  if (vecc)
+    if (const char *layout = mat->fmt != ABFT_FMT_CSR ? "COO" : mat->streams() ? nullptr : layout_name(mat->layout))
+      return set_err(ABFT_ERR_INVALID, "%s: a matrix in the %s layout (protected vectors run on CSR matrices in the "
+                     "streaming layout only)", what, layout);
+  const int n = x->n;
+  if (precond) {
+    // the reduction's partials are allocated on first use, which a capturing stream does not allow
+    if (ctx->capturing && !ctx->bslot)
+      return set_err(ABFT_ERR_INVALID, "%s: called under graph capture before the context's block partials exist; make "
+                     "one eager %s", what,
+                     vecc ? "abft_hip_precond_start_vecc first (the loop needs it for its first record anyway)"
+                          : "preconditioned call first (abft_hip_precond_start, for example)");
+    if (int rc = block_slot(ctx)) return rc;
+    forget_iteration(*ctx);  // (as every preconditioned entry: the learned iteration names these vectors by handle)
+  }
+  HeldFold hold;
+  if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold, vecc)) return rc;
+  if (int rc = finish_held_fold(ctx, hold)) return rc;
+  const ReduceOut o = reduce_out(ctx, dev_out, false);
+  ReduceOutD od{};
+  od.partials = ctx->bpartials;
+  od.ticket = ctx->ticket;
+  od.dev_out = dev_out;
+  od.ev_count = ctx->ring.count;
+  double *alpha = ctx->alpha_dev;
+  {
+    KernelTimer t(ctx, ABFT_K_CALC_XR);
+    if (vecc && precond)
+      HIPCHK(launch_calc_r_precond_vecc_until(r->d, w->d, dinv->d, dev_in, dev_pw, threshold, alpha, n, od, ctx->ring, ctx->stream));
+    else if (vecc)
+      HIPCHK(launch_calc_r_vecc_until(r->d, w->d, dev_in, dev_pw, threshold, alpha, n, o, ctx->ring, ctx->stream));
+    else if (precond)
+      HIPCHK(launch_calc_r_precond_until(r->d, w->d, dinv->d, dev_in, dev_pw, threshold, alpha, n, od, ctx->stream));
+    else
+      HIPCHK(launch_calc_r_until(r->d, w->d, dev_in, dev_pw, threshold, alpha, n, o, ctx->stream, x->d, p->d));
+  }
+  KernelTimer t(ctx, ABFT_K_CALC_P);
+  if (vecc && precond)
+    HIPCHK(launch_calc_px_precond_vecc_until(x->d, p->d, r->d, dinv->d, dev_in, dev_out, threshold, alpha, n, ctx->ring, ctx->stream));
+  else if (vecc)
+    HIPCHK(launch_calc_px_vecc_until(x->d, p->d, r->d, dev_in, dev_out, threshold, alpha, n, ctx->ring, ctx->stream));
+  else if (precond)
+    HIPCHK(launch_calc_px_precond_until(p->d, r->d, dinv->d, x->d, dev_in, dev_out, threshold, alpha, n, ctx->stream));
+  else
+    HIPCHK(launch_calc_px_until(p->d, r->d, x->d, dev_in, dev_out, threshold, alpha, n, ctx->stream));
+  return ABFT_OK;
+}
+
 extern "C" int abft_hip_cg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
                                                int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
                                                abft_hip_vector *p, abft_hip_vector *w, const double *dev_rr,
                                                double *dev_pw, double *dev_rr_new, double threshold) {
-  const char *what = "cg_iteration_until";
-  if (int rc = enter(ctx, 0)) return rc;  // a pending x update applied, a speculation voided
-  if (int rc = check_guarded_iteration(ctx, what, mat, vec, vec_offset, part, x, r, p, w, false, nullptr, dev_rr, dev_pw,
-                                       dev_rr_new))
-    return rc;
-  const int n = x->n;
-  HeldFold hold;
-  if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold)) return rc;
-  if (int rc = finish_held_fold(ctx, hold)) return rc;
-  const ReduceOut o = reduce_out(ctx, dev_rr_new, false);
-  {
-    KernelTimer t(ctx, ABFT_K_CALC_XR);
-    HIPCHK(launch_calc_r_until(r->d, w->d, dev_rr, dev_pw, threshold, ctx->alpha_dev, n, o, ctx->stream, x->d, p->d));
-  }
-  KernelTimer t(ctx, ABFT_K_CALC_P);
-  HIPCHK(launch_calc_px_until(p->d, r->d, x->d, dev_rr, dev_rr_new, threshold, ctx->alpha_dev, n, ctx->stream));
-  return ABFT_OK;
+  return iteration_until(ctx, "cg_iteration_until", false, mat, vec, vec_offset, part, x, r, p, w, nullptr, false, dev_rr,
+                         dev_pw, dev_rr_new, threshold);
 }
 
 // ---- the guarded iteration with Jacobi preconditioning ----------------
@@ -3699,33 +3746,8 @@ extern "C" int abft_hip_pcg_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matr
                                                 abft_hip_vector *p, abft_hip_vector *w, const abft_hip_vector *dinv,
                                                 const double *dev_in, double *dev_pw, double *dev_out,
                                                 double threshold) {
-  const char *what = "pcg_iteration_until";
-  if (int rc = enter(ctx, 0)) return rc;  // a pending x update applied, a speculation voided
-  if (int rc = check_guarded_iteration(ctx, what, mat, vec, vec_offset, part, x, r, p, w, true, dinv, dev_in, dev_pw,
-                                       dev_out))
-    return rc;
-  const int n = x->n;
-  // the reduction's partials are allocated on first use, which a capturing stream does not allow
-  if (ctx->capturing && !ctx->bslot)
-    return set_err(ABFT_ERR_INVALID, "%s: called under graph capture before the context's block partials exist; make "
-                   "one eager preconditioned call first (abft_hip_precond_start, for example)", what);
-  if (int rc = block_slot(ctx)) return rc;
-  forget_iteration(*ctx);  // (as every preconditioned entry: the learned iteration names these vectors by handle)
-  HeldFold hold;
-  if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold)) return rc;
-  if (int rc = finish_held_fold(ctx, hold)) return rc;
-  ReduceOutD o{};
-  o.partials = ctx->bpartials;
-  o.ticket = ctx->ticket;
-  o.dev_out = dev_out;
-  o.ev_count = ctx->ring.count;
-  {
-    KernelTimer t(ctx, ABFT_K_CALC_XR);
-    HIPCHK(launch_calc_r_precond_until(r->d, w->d, dinv->d, dev_in, dev_pw, threshold, ctx->alpha_dev, n, o, ctx->stream));
-  }
-  KernelTimer t(ctx, ABFT_K_CALC_P);
-  HIPCHK(launch_calc_px_precond_until(p->d, r->d, dinv->d, x->d, dev_in, dev_out, threshold, ctx->alpha_dev, n, ctx->stream));
-  return ABFT_OK;
+  return iteration_until(ctx, "pcg_iteration_until", false, mat, vec, vec_offset, part, x, r, p, w, dinv, true, dev_in,
+                         dev_pw, dev_out, threshold);
 }
 
 // ---- the guarded iteration on protected vectors ----------------
@@ -3740,29 +3762,8 @@ extern "C" int abft_hip_cg_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_
                                                     int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
                                                     abft_hip_vector *p, abft_hip_vector *w, const double *dev_rr,
                                                     double *dev_pw, double *dev_rr_new, double threshold) {
-  const char *what = "cg_vecc_iteration_until";
-  if (int rc = enter(ctx, 0)) return rc;  // a pending x update applied, a speculation voided
-  if (int rc = check_guarded_iteration(ctx, what, mat, vec, vec_offset, part, x, r, p, w, false, nullptr, dev_rr, dev_pw,
-                                       dev_rr_new))
-    return rc;
-  // what spmv_vecc refuses, refused here under this entry's name: spmv_common would forget the learned iteration first,
-  // and a refused call leaves the state alone
-  if (const char *layout = mat->fmt != ABFT_FMT_CSR ? "COO" : mat->streams() ? nullptr : layout_name(mat->layout))
-    return set_err(ABFT_ERR_INVALID, "%s: a matrix in the %s layout (protected vectors run on CSR matrices in the "
-                   "streaming layout only)", what, layout);
-  const int n = x->n;
-  HeldFold hold;
-  if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold, /*vecc=*/true)) return rc;
-  if (int rc = finish_held_fold(ctx, hold)) return rc;
-  const ReduceOut o = reduce_out(ctx, dev_rr_new, false);
-  {
-    KernelTimer t(ctx, ABFT_K_CALC_XR);
-    HIPCHK(launch_calc_r_vecc_until(r->d, w->d, dev_rr, dev_pw, threshold, ctx->alpha_dev, n, o, ctx->ring, ctx->stream));
-  }
-  KernelTimer t(ctx, ABFT_K_CALC_P);
-  HIPCHK(launch_calc_px_vecc_until(x->d, p->d, r->d, dev_rr, dev_rr_new, threshold, ctx->alpha_dev, n, ctx->ring,
-                                   ctx->stream));
-  return ABFT_OK;
+  return iteration_until(ctx, "cg_vecc_iteration_until", true, mat, vec, vec_offset, part, x, r, p, w, nullptr, false,
+                         dev_rr, dev_pw, dev_rr_new, threshold);
 }
 
 // ---- the guarded Jacobi iteration on protected vectors ----------------
@@ -3777,39 +3778,8 @@ extern "C" int abft_hip_pcg_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip
                                                      abft_hip_vector *p, abft_hip_vector *w, abft_hip_vector *dinv,
                                                      const double *dev_in, double *dev_pw, double *dev_out,
                                                      double threshold) {
-  const char *what = "pcg_vecc_iteration_until";
-  if (int rc = enter(ctx, 0)) return rc;  // a pending x update applied, a speculation voided
-  if (int rc = check_guarded_iteration(ctx, what, mat, vec, vec_offset, part, x, r, p, w, true, dinv, dev_in, dev_pw,
-                                       dev_out))
-    return rc;
-  // what spmv_vecc refuses, refused here under this entry's name (as abft_hip_cg_vecc_iteration_until_dev)
-  if (const char *layout = mat->fmt != ABFT_FMT_CSR ? "COO" : mat->streams() ? nullptr : layout_name(mat->layout))
-    return set_err(ABFT_ERR_INVALID, "%s: a matrix in the %s layout (protected vectors run on CSR matrices in the "
-                   "streaming layout only)", what, layout);
-  const int n = x->n;
-  // the reduction's partials are allocated on first use, which a capturing stream does not allow
-  if (ctx->capturing && !ctx->bslot)
-    return set_err(ABFT_ERR_INVALID, "%s: called under graph capture before the context's block partials exist; make "
-                   "one eager abft_hip_precond_start_vecc first (the loop needs it for its first record anyway)", what);
-  if (int rc = block_slot(ctx)) return rc;
-  forget_iteration(*ctx);  // (as every preconditioned entry: the learned iteration names these vectors by handle)
-  HeldFold hold;
-  if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold, /*vecc=*/true)) return rc;
-  if (int rc = finish_held_fold(ctx, hold)) return rc;
-  ReduceOutD o{};
-  o.partials = ctx->bpartials;
-  o.ticket = ctx->ticket;
-  o.dev_out = dev_out;
-  o.ev_count = ctx->ring.count;
-  {
-    KernelTimer t(ctx, ABFT_K_CALC_XR);
-    HIPCHK(launch_calc_r_precond_vecc_until(r->d, w->d, dinv->d, dev_in, dev_pw, threshold, ctx->alpha_dev, n, o,
-                                            ctx->ring, ctx->stream));
-  }
-  KernelTimer t(ctx, ABFT_K_CALC_P);
-  HIPCHK(launch_calc_px_precond_vecc_until(x->d, p->d, r->d, dinv->d, dev_in, dev_out, threshold, ctx->alpha_dev, n,
-                                           ctx->ring, ctx->stream));
-  return ABFT_OK;
+  return iteration_until(ctx, "pcg_vecc_iteration_until", true, mat, vec, vec_offset, part, x, r, p, w, dinv, true, dev_in,
+                         dev_pw, dev_out, threshold);
 }
 
 // ---- the guarded block iteration: K right-hand sides, the column mask decided on the device ----------------

@@ -212,3 +212,27 @@ __device__ __forceinline__ uint64_t vecc_encode(double v) {
   const uint32_t par = popc(lo ^ hi ^ c) & 1u;
   return w | c | par;
 }
+
+__device__ __forceinline__ uint64_t vecc_bits(double v) { return (uint64_t)__double_as_longlong(v); }
+__device__ __forceinline__ double vecc_double(uint64_t w) { return __longlong_as_double((long long)w); }
+
+// what a cold decode hands back: the word as repaired and its verdict (below)
+struct VeccWord { uint64_t w; int rc; };
+
+// Cold path, the pure part (the device's vecc_cold and the host tests run this text): the word failed
+// vecc_suspect.  One flipped bit (odd parity) is located by the syndrome -- bit 0 itself when the syndrome is
+// clear --, flipped back: rc 1, `bit` the one.  A set syndrome under even parity is two flips: fatal, the word
+// stays as it is, rc -1.
+__device__ __forceinline__ void vecc_repair(uint64_t word, VeccWord &o, uint32_t &bit) {
+  o.w = word; o.rc = 0;
+  const uint32_t s = vecc_syndrome(word);
+  bit = 0u;
+  if (popc((uint32_t)word ^ (uint32_t)(word >> 32)) & 1u) {
+    bit = s ? vecc_position_to_bit(s) : 0u;
+    o.w = word ^ (1ull << bit);
+    o.rc = 1;
+  } else if (s) {
+    o.rc = -1;
+  }
+}
+

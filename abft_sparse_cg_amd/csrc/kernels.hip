@@ -16,6 +16,7 @@
 
 #include "abft_internal.h"
 #include "ecc_device.h"
+#include "vecc_walk.h"
 
 // native vector types (what __builtin_nontemporal_load accepts)
 typedef double f64x2 __attribute__((ext_vector_type(2)));
@@ -143,12 +144,10 @@ __device__ __forceinline__ uint32_t ecc_suspect(const uint32_t *w) {
 }
 
 // ---- protected vector elements (ecc_device.h "protected vector elements") ----
-// Cold path: the word failed vecc_suspect.  One flipped bit (odd parity) is located by the syndrome --
-// bit 0 itself when the syndrome is clear --, flipped back and reported: rc 1.  A set syndrome under even
-// parity is two flips: fatal, the word stays as it is, rc -1.  `operand`: the vector's ordinal in the
-// entry's argument list, `index` the element inside it.
-struct VeccWord { uint64_t w; int rc; };
-
+// Cold path: the word failed vecc_suspect.  vecc_repair (ecc_device.h) repairs what it can, here the outcome is
+// reported: rc 1 a flipped bit put back, rc -1 two flips, fatal, the word as it is.  `operand`: the vector's
+// ordinal in the entry's argument list, `index` the element inside it.
+//
 // A vector entry may be read by any number of threads -- every row of a dense column gathers the same
 // x[col] -- and each of them comes here with the same damaged word.  All repair it in their registers, but
 // only the first queues the event: a flipped word costs one slot of the queue however many threads see
@@ -173,22 +172,19 @@ __device__ __forceinline__ void push_vector_event(const EventRing &ev, uint32_t 
 
 __device__ __noinline__ VeccWord vecc_cold(uint64_t word, uint32_t index, uint32_t operand, EventRing ev) {
   VeccWord o;
-  o.w = word; o.rc = 0;
-  const uint32_t s = vecc_syndrome(word);
-  uint32_t bit = 0u;
-  if (popc((uint32_t)word ^ (uint32_t)(word >> 32)) & 1u) {
-    bit = s ? vecc_position_to_bit(s) : 0u;
-    o.w = word ^ (1ull << bit);
-    o.rc = 1;
-  } else if (s) {
-    o.rc = -1;
-  }
+  uint32_t bit;
+  vecc_repair(word, o, bit);
   if (o.rc) push_vector_event(ev, o.rc > 0 ? ABFT_EV_VEC_CORRECTED : ABFT_EV_VEC_DOUBLE, index, bit | (operand << 8));
   return o;
 }
 
-__device__ __forceinline__ uint64_t vecc_bits(double v) { return (uint64_t)__double_as_longlong(v); }
-__device__ __forceinline__ double vecc_double(uint64_t w) { return __longlong_as_double((long long)w); }
+// the cold decode as the walks of vecc_walk.h take it
+struct VeccColdDev {
+  EventRing ev;
+  __device__ __forceinline__ VeccWord operator()(uint64_t word, uint32_t index, uint32_t operand) const {
+    return vecc_cold(word, index, operand, ev);
+  }
+};
 
 // full decode of one word outside any load loop: check, repair in registers, event
 __device__ __forceinline__ double vecc_decode_cold_ok(const double *p, uint32_t index, uint32_t operand,
@@ -3556,6 +3552,18 @@ hipError_t launch_inject_coo(uint4 *elems, const uint32_t *pos_of_orig, uint32_t
 
 // ------------------------------------------------------------- vector kernels --
 
+// VEC by alignment: KERNEL<2 MORE> when every operand that enters the test VEC2 is 16-byte aligned, else KERNEL<1 MORE>
+// (MORE: the kernel's template arguments after VEC, in parentheses: `()` for none, `(, true)`).  Which operands enter
+// the test is each launcher's own matter -- the order a sum is formed in follows the walk.  s: the launcher's stream.
+#define ABFT_UNPAREN(...) __VA_ARGS__
+#define ABFT_VEC_DISPATCH(KERNEL, MORE, VEC2, NB, ...)                                                               \
+  do {                                                                                                               \
+    if (VEC2)                                                                                                        \
+      hipLaunchKernelGGL((KERNEL<2 ABFT_UNPAREN MORE>), dim3(NB), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);              \
+    else                                                                                                             \
+      hipLaunchKernelGGL((KERNEL<1 ABFT_UNPAREN MORE>), dim3(NB), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);              \
+  } while (0)
+
 int reduce_blocks(int n) {
   long per_block = (long)ABFT_BLOCK * 8;  // >= 8 elements per thread before adding blocks
   long nb = (n + per_block - 1) / per_block;
@@ -3882,20 +3890,14 @@ static inline bool aligned16(const void *a, const void *b = nullptr, const void 
 
 hipError_t launch_dot(const double *a, const double *b, int n, const ReduceOut &out, hipStream_t s) {
   const int nb = reduce_blocks(n);
-  if (aligned16(a, b))
-    hipLaunchKernelGGL(dot_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, a, b, n, out);
-  else
-    hipLaunchKernelGGL(dot_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, a, b, n, out);
+  ABFT_VEC_DISPATCH(dot_kernel, (), aligned16(a, b), nb, a, b, n, out);
   return hipGetLastError();
 }
 
 hipError_t launch_calc_xr(double *x, double *r, const double *p, const double *w, double alpha,
                           const double *num, const double *den, int n, const ReduceOut &out, hipStream_t s) {
   const int nb = reduce_blocks(n);
-  if (aligned16(x, r, p, w))
-    hipLaunchKernelGGL(calc_xr_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, r, p, w, alpha, num, den, n, out);
-  else
-    hipLaunchKernelGGL(calc_xr_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, r, p, w, alpha, num, den, n, out);
+  ABFT_VEC_DISPATCH(calc_xr_kernel, (), aligned16(x, r, p, w), nb, x, r, p, w, alpha, num, den, n, out);
   return hipGetLastError();
 }
 
@@ -3904,10 +3906,7 @@ hipError_t launch_calc_p(double *p, const double *r, double beta, const double *
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
   if (!p_out) p_out = p;
-  if (aligned16(p, r, p_out))
-    hipLaunchKernelGGL(calc_p_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, num, den, n, p_out);
-  else
-    hipLaunchKernelGGL(calc_p_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, num, den, n, p_out);
+  ABFT_VEC_DISPATCH(calc_p_kernel, (), aligned16(p, r, p_out), nb, p, r, beta, num, den, n, p_out);
   return hipGetLastError();
 }
 
@@ -3915,10 +3914,7 @@ hipError_t launch_calc_p(double *p, const double *r, double beta, const double *
 hipError_t launch_calc_p_head(const double *p, const double *r, const double *den, int n, hipStream_t s, double *p_out,
                               const ReduceOut &head, uint32_t nb) {
   const int g = reduce_blocks(n);
-  if (aligned16(p, r, p_out))
-    hipLaunchKernelGGL(calc_p_head_kernel<2>, dim3(g), dim3(ABFT_BLOCK), 0, s, p, r, den, n, p_out, head, nb);
-  else
-    hipLaunchKernelGGL(calc_p_head_kernel<1>, dim3(g), dim3(ABFT_BLOCK), 0, s, p, r, den, n, p_out, head, nb);
+  ABFT_VEC_DISPATCH(calc_p_head_kernel, (), aligned16(p, r, p_out), g, p, r, den, n, p_out, head, nb);
   return hipGetLastError();
 }
 
@@ -4122,10 +4118,8 @@ hipError_t launch_calc_r(double *r, const double *w, double alpha, const double 
     return launch_deferred_finish(out, (uint32_t)nb, s);
   }
 #endif
-  if (aligned16(r, w, r_out) && aligned16(x, p))
-    hipLaunchKernelGGL(calc_r_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, alpha, num, den, alpha_out, n, out, r_out);
-  else
-    hipLaunchKernelGGL(calc_r_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, alpha, num, den, alpha_out, n, out, r_out);
+  ABFT_VEC_DISPATCH(calc_r_kernel, (), aligned16(r, w, r_out) && aligned16(x, p), nb, r, w, alpha, num, den, alpha_out,
+                    n, out, r_out);
   return hipGetLastError();
 }
 
@@ -4139,14 +4133,13 @@ hipError_t launch_calc_r_defer(double *r, const double *w, double alpha, const d
   const int nb = reduce_blocks(n);
   if (!r_out) r_out = r;
   const bool vec2 = aligned16(r, w, r_out) && aligned16(x, p);
-  const dim3 g(nb), b(ABFT_BLOCK);
   if (head) {
-    if (vec2) hipLaunchKernelGGL((calc_r_defer_kernel<2, true>), g, b, 0, s, r, w, alpha, num, den, alpha_out, n, block_partials, r_out, *head, head_nb);
-    else hipLaunchKernelGGL((calc_r_defer_kernel<1, true>), g, b, 0, s, r, w, alpha, num, den, alpha_out, n, block_partials, r_out, *head, head_nb);
+    ABFT_VEC_DISPATCH(calc_r_defer_kernel, (, true), vec2, nb, r, w, alpha, num, den, alpha_out, n, block_partials, r_out,
+                      *head, head_nb);
   } else {
     const ReduceOut none{};
-    if (vec2) hipLaunchKernelGGL((calc_r_defer_kernel<2, false>), g, b, 0, s, r, w, alpha, num, den, alpha_out, n, block_partials, r_out, none, 0u);
-    else hipLaunchKernelGGL((calc_r_defer_kernel<1, false>), g, b, 0, s, r, w, alpha, num, den, alpha_out, n, block_partials, r_out, none, 0u);
+    ABFT_VEC_DISPATCH(calc_r_defer_kernel, (, false), vec2, nb, r, w, alpha, num, den, alpha_out, n, block_partials, r_out,
+                      none, 0u);
   }
   return hipGetLastError();
 }
@@ -4157,20 +4150,15 @@ hipError_t launch_calc_px(double *p, const double *r, double *x, double beta, co
   const int nb = reduce_blocks(n);
   if (!p_out) p_out = p;
   if (!x_out) x_out = x;
-  if (aligned16(p, r, x) && aligned16(p_out, x_out))
-    hipLaunchKernelGGL(calc_px_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, x, beta, num, den, alpha, alpha_ptr, n, p_out, x_out);
-  else
-    hipLaunchKernelGGL(calc_px_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, x, beta, num, den, alpha, alpha_ptr, n, p_out, x_out);
+  ABFT_VEC_DISPATCH(calc_px_kernel, (), aligned16(p, r, x) && aligned16(p_out, x_out), nb, p, r, x, beta, num, den,
+                    alpha, alpha_ptr, n, p_out, x_out);
   return hipGetLastError();
 }
 
 hipError_t launch_axpy(double *x, const double *p, double alpha, const double *alpha_ptr, int n, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
-  if (aligned16(x, p))
-    hipLaunchKernelGGL(axpy_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, alpha, alpha_ptr, n);
-  else
-    hipLaunchKernelGGL(axpy_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, alpha, alpha_ptr, n);
+  ABFT_VEC_DISPATCH(axpy_kernel, (), aligned16(x, p), nb, x, p, alpha, alpha_ptr, n);
   return hipGetLastError();
 }
 
@@ -4183,10 +4171,7 @@ hipError_t launch_axpy_chain(const XUpd &u, int n, hipStream_t s) {
     vec2 = vec2 && aligned16(u.u[k].p_old);
   }
   const int nb = reduce_blocks(n);
-  if (vec2)
-    hipLaunchKernelGGL(axpy_chain_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, u, n);
-  else
-    hipLaunchKernelGGL(axpy_chain_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, u, n);
+  ABFT_VEC_DISPATCH(axpy_chain_kernel, (), vec2, nb, u, n);
   return hipGetLastError();
 }
 
@@ -4237,10 +4222,7 @@ hipError_t launch_calc_r_until(double *r, const double *w, const double *rr, con
                                double *alpha_out, int n, const ReduceOut &out, hipStream_t s, const double *x,
                                const double *p) {
   const int nb = reduce_blocks(n);
-  if (aligned16(r, w, x, p))
-    hipLaunchKernelGGL(calc_r_until_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, rr, pw, threshold, alpha_out, n, out);
-  else
-    hipLaunchKernelGGL(calc_r_until_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, rr, pw, threshold, alpha_out, n, out);
+  ABFT_VEC_DISPATCH(calc_r_until_kernel, (), aligned16(r, w, x, p), nb, r, w, rr, pw, threshold, alpha_out, n, out);
   return hipGetLastError();
 }
 
@@ -4248,10 +4230,7 @@ hipError_t launch_calc_px_until(double *p, const double *r, double *x, const dou
                                 double threshold, const double *alpha_ptr, int n, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
-  if (aligned16(p, r, x))
-    hipLaunchKernelGGL(calc_px_until_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, x, rr, rr_new, threshold, alpha_ptr, n);
-  else
-    hipLaunchKernelGGL(calc_px_until_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, x, rr, rr_new, threshold, alpha_ptr, n);
+  ABFT_VEC_DISPATCH(calc_px_until_kernel, (), aligned16(p, r, x), nb, p, r, x, rr, rr_new, threshold, alpha_ptr, n);
   return hipGetLastError();
 }
 
@@ -4698,10 +4677,7 @@ hipError_t launch_flip_vector(double *v, unsigned long long mask, hipStream_t s)
 hipError_t launch_residual_gap(const double *b, const double *y, const double *r, int n, const ReduceOutK &out,
                                hipStream_t s) {
   const int nb = reduce_blocks(n);
-  if (aligned16(b, y, r))
-    hipLaunchKernelGGL(residual_gap_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, n, out);
-  else
-    hipLaunchKernelGGL(residual_gap_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, n, out);
+  ABFT_VEC_DISPATCH(residual_gap_kernel, (), aligned16(b, y, r), nb, b, y, r, n, out);
   return hipGetLastError();
 }
 
@@ -4709,10 +4685,7 @@ hipError_t launch_residual_gap(const double *b, const double *y, const double *r
 hipError_t launch_residual_check(const double *b, const double *y, const double *r, int n, double limit,
                                  const ReduceOutB &out, hipStream_t s) {
   const int nb = reduce_blocks(n);
-  if (aligned16(b, y, r))
-    hipLaunchKernelGGL(residual_check_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, n, limit, out);
-  else
-    hipLaunchKernelGGL(residual_check_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, b, y, r, n, limit, out);
+  ABFT_VEC_DISPATCH(residual_check_kernel, (), aligned16(b, y, r), nb, b, y, r, n, limit, out);
   return hipGetLastError();
 }
 
@@ -4912,7 +4885,6 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_p_precond_kernel(double *__re
 // VEC and PAIRS of one launch: `vec2` the alignment test of the plain kernel's operands, `pairs` that of the rest
 // (MORE: the kernel's template arguments after VEC and PAIRS, in parentheses: `(, true)` / `(, false)` for XHALF, `()`
 // for the guarded kernels, which have none)
-#define ABFT_UNPAREN(...) __VA_ARGS__
 #define ABFT_PRECOND_DISPATCH(KERNEL, MORE, ...)                                                            \
   do {                                                                                                      \
     if (!vec2)                                                                                              \
@@ -5038,7 +5010,6 @@ hipError_t launch_calc_px_precond_until(double *p, const double *r, const double
   return hipGetLastError();
 }
 #undef ABFT_PRECOND_DISPATCH
-#undef ABFT_UNPAREN
 
 // Block forms: one thread per row over the K columns, as the block kernels above; dinv[i] is loaded
 // once per row (one operator for all columns).  A column whose bit is clear keeps its bits (a
@@ -6198,10 +6169,7 @@ hipError_t launch_copy(double *dst, const double *src, int n, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   long nb = ((long)n + ABFT_BLOCK * 4 - 1) / (ABFT_BLOCK * 4);
   if (nb > 4096) nb = 4096;
-  if (aligned16(dst, src))
-    hipLaunchKernelGGL(copy_kernel<2>, dim3((unsigned)nb), dim3(ABFT_BLOCK), 0, s, dst, src, n);
-  else
-    hipLaunchKernelGGL(copy_kernel<1>, dim3((unsigned)nb), dim3(ABFT_BLOCK), 0, s, dst, src, n);
+  ABFT_VEC_DISPATCH(copy_kernel, (), aligned16(dst, src), (unsigned)nb, dst, src, n);
   return hipGetLastError();
 }
 
@@ -6265,6 +6233,12 @@ hipError_t launch_stream_read(const double *src, size_t n, double *sink, hipStre
 // the noted one: vecc_cold repairs its words in registers (an input that is only read is not written
 // back), the step is carried out and adds what it stores.  Same operands and the same order of adds as an
 // undamaged call, so every vector and the sum have the undamaged call's bits.
+//
+// That discipline is written ONCE, in vecc_walk.h: vecc_walk is the two walks, an operation
+// (VeccDot, VeccCalcXr, ...) states its arithmetic and its sums once, and a kernel here is vecc_grid_walk with its
+// operation, the operands in the order its entry reports them, and then its reduction.  vecc_walk.h includes nothing
+// of HIP: tests/test_vecc_walk_host.py runs the same text on a CPU.  Two walks keep their hand-written form
+// (calc_px_vecc_walk, precond_start_vecc_walk): section 5p says why.
 
 template <int VEC>
 __global__ __launch_bounds__(ABFT_BLOCK) void vector_encode_kernel(double *__restrict__ v, int n) {
@@ -6281,36 +6255,34 @@ __global__ __launch_bounds__(ABFT_BLOCK) void vector_encode_kernel(double *__res
   }
 }
 
+// A thread's chain in the grid of the vector kernels under vecc_walk (vecc_walk.h): the hot loop, and behind it the
+// second walk of a thread with a noted step
+template <int VEC, class OP, class COLD>
+__device__ __forceinline__ void vecc_grid_walk(const OP &op, const VeccOperands<OP> &o, int n, COLD &cold, double *acc) {
+  vecc_walk<VEC>(op, o, n, ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC, (long)gridDim.x * ABFT_BLOCK * VEC, cold,
+                 acc);
+}
+
+// the scrub's cold decode: vecc_cold, counted
+struct VeccColdScrub {
+  EventRing ev;
+  uint32_t fixed, lost;
+  __device__ __forceinline__ VeccWord operator()(uint64_t word, uint32_t index, uint32_t operand) {
+    const VeccWord o = vecc_cold(word, index, operand, ev);
+    if (o.rc > 0) fixed++;
+    else lost++;
+    return o;
+  }
+};
+
 // counts[0] += words repaired (and written back), counts[1] += words with two flipped bits (left as they are)
 template <int VEC>
 __global__ __launch_bounds__(ABFT_BLOCK) void vector_scrub_kernel(double *__restrict__ v, int n, uint32_t *counts,
                                                                   EventRing ev) {
-  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
-  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
-  uint32_t bad = 0u;
-  for (long i = first; i < n; i += stride) {
-    if (VEC == 2 && i + 1 < n) {
-      const double2 t = *reinterpret_cast<const double2 *>(v + i);
-      bad |= vecc_suspect(vecc_bits(t.x)) | vecc_suspect(vecc_bits(t.y));
-    } else {
-      bad |= vecc_suspect(vecc_bits(v[i]));
-    }
-  }
-  if (__builtin_expect(bad != 0u, 0)) {
-    uint32_t fixed = 0u, lost = 0u;
-    for (long i = first; i < n; i += stride) {
-      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
-      for (int k = 0; k < m; k++) {
-        const uint64_t w = vecc_bits(v[i + k]);
-        if (!vecc_suspect(w)) continue;
-        const VeccWord o = vecc_cold(w, (uint32_t)(i + k), 0u, ev);
-        if (o.rc > 0) { v[i + k] = vecc_double(o.w); fixed++; }
-        else lost++;
-      }
-    }
-    if (fixed) atomicAdd(counts, fixed);
-    if (lost) atomicAdd(counts + 1, lost);
-  }
+  VeccColdScrub cold{ev, 0u, 0u};
+  vecc_grid_walk<VEC>(VeccScrub{}, VeccOperands<VeccScrub>{{v}, {0u}}, n, cold, nullptr);
+  if (cold.fixed) atomicAdd(counts, cold.fixed);
+  if (cold.lost) atomicAdd(counts + 1, cold.lost);
 }
 
 // dot on protected vectors: operands 0 (a) and 1 (b), neither written back
@@ -6320,34 +6292,9 @@ __global__ __launch_bounds__(ABFT_BLOCK) void dot_vecc_kernel(const double *__re
                                                               ReduceOut out, EventRing ev) {
   __shared__ double s_w[4];
   double acc = 0.0;
-  uint32_t bad = 0u;
-  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
-  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
-  for (long i = first; i < n; i += stride) {
-    if (VEC == 2 && i + 1 < n) {
-      const double2 av = *reinterpret_cast<const double2 *>(a + i);
-      const double2 bv = *reinterpret_cast<const double2 *>(b + i);
-      const uint64_t a0 = vecc_bits(av.x), a1 = vecc_bits(av.y), b0 = vecc_bits(bv.x), b1 = vecc_bits(bv.y);
-      bad |= (vecc_suspect(a0) | vecc_suspect(a1)) | (vecc_suspect(b0) | vecc_suspect(b1));
-      acc += vecc_value(a0) * vecc_value(b0);
-      acc += vecc_value(a1) * vecc_value(b1);
-    } else {
-      const uint64_t a0 = vecc_bits(a[i]), b0 = vecc_bits(b[i]);
-      bad |= vecc_suspect(a0) | vecc_suspect(b0);
-      acc += vecc_value(a0) * vecc_value(b0);
-    }
-  }
-  if (__builtin_expect(bad != 0u, 0)) {  // nothing was stored: the whole chain again, with the repairs
-    acc = 0.0;
-    for (long i = first; i < n; i += stride) {
-      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
-      for (int k = 0; k < m; k++) {
-        const uint32_t j = (uint32_t)(i + k);
-        const double av = vecc_decode_cold_ok(a + i + k, j, 0u, ev);
-        acc += av * vecc_decode_cold_ok(b + i + k, j, 1u, ev);
-      }
-    }
-  }
+  VeccColdDev cold{ev};
+  vecc_grid_walk<VEC>(VeccDot{}, VeccOperands<VeccDot>{{const_cast<double *>(a), const_cast<double *>(b)}, {0u, 1u}}, n,
+                      cold, &acc);
   acc = block_sum(acc, s_w);
   reduce_finish(acc, out, s_w);
 }
@@ -6360,67 +6307,10 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_xr_vecc_kernel(double *__rest
                                                                   ReduceOut out, EventRing ev) {
   __shared__ double s_w[4];
   double acc = 0.0;
-  uint32_t bad = 0u;
-  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
-  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
-  for (long i = first; i < n; i += stride) {
-    if (VEC == 2 && i + 1 < n) {
-      const double2 xv = *reinterpret_cast<const double2 *>(x + i);
-      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
-      const double2 pv = *reinterpret_cast<const double2 *>(p + i);
-      const double2 wv = *reinterpret_cast<const double2 *>(w + i);
-      const uint64_t x0 = vecc_bits(xv.x), x1 = vecc_bits(xv.y), r0 = vecc_bits(rv.x), r1 = vecc_bits(rv.y);
-      const uint64_t p0 = vecc_bits(pv.x), p1 = vecc_bits(pv.y), w0 = vecc_bits(wv.x), w1 = vecc_bits(wv.y);
-      const uint32_t sus = (vecc_suspect(x0) | vecc_suspect(x1)) | (vecc_suspect(r0) | vecc_suspect(r1)) |
-                           (vecc_suspect(p0) | vecc_suspect(p1)) | (vecc_suspect(w0) | vecc_suspect(w1));
-      bad |= sus;
-      if (!sus) {
-        const uint64_t xs0 = vecc_encode(vecc_value(x0) + alpha * vecc_value(p0));
-        const uint64_t xs1 = vecc_encode(vecc_value(x1) + alpha * vecc_value(p1));
-        const uint64_t rs0 = vecc_encode(vecc_value(r0) - alpha * vecc_value(w0));
-        const uint64_t rs1 = vecc_encode(vecc_value(r1) - alpha * vecc_value(w1));
-        *reinterpret_cast<double2 *>(x + i) = make_double2(vecc_double(xs0), vecc_double(xs1));
-        *reinterpret_cast<double2 *>(r + i) = make_double2(vecc_double(rs0), vecc_double(rs1));
-        acc += vecc_value(rs0) * vecc_value(rs0);
-        acc += vecc_value(rs1) * vecc_value(rs1);
-      }
-    } else {
-      const uint64_t x0 = vecc_bits(x[i]), r0 = vecc_bits(r[i]), p0 = vecc_bits(p[i]), w0 = vecc_bits(w[i]);
-      const uint32_t sus = (vecc_suspect(x0) | vecc_suspect(r0)) | (vecc_suspect(p0) | vecc_suspect(w0));
-      bad |= sus;
-      if (!sus) {
-        const uint64_t xs = vecc_encode(vecc_value(x0) + alpha * vecc_value(p0));
-        const uint64_t rs = vecc_encode(vecc_value(r0) - alpha * vecc_value(w0));
-        x[i] = vecc_double(xs);
-        r[i] = vecc_double(rs);
-        acc += vecc_value(rs) * vecc_value(rs);
-      }
-    }
-  }
-  if (__builtin_expect(bad != 0u, 0)) {
-    acc = 0.0;
-    for (long i = first; i < n; i += stride) {
-      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
-      uint32_t sus = 0u;
-      for (int k = 0; k < m; k++)
-        sus |= (vecc_suspect(vecc_bits(x[i + k])) | vecc_suspect(vecc_bits(r[i + k]))) |
-               (vecc_suspect(vecc_bits(p[i + k])) | vecc_suspect(vecc_bits(w[i + k])));
-      for (int k = 0; k < m; k++) {
-        uint64_t rs = vecc_bits(r[i + k]);  // a step carried out above: what it stored
-        if (sus) {
-          const uint32_t j = (uint32_t)(i + k);
-          const double xo = vecc_decode_cold_ok(x + i + k, j, 0u, ev);
-          const double ro = vecc_decode_cold_ok(r + i + k, j, 1u, ev);
-          const double po = vecc_decode_cold_ok(p + i + k, j, 2u, ev);
-          const double wo = vecc_decode_cold_ok(w + i + k, j, 3u, ev);
-          rs = vecc_encode(ro - alpha * wo);
-          x[i + k] = vecc_double(vecc_encode(xo + alpha * po));
-          r[i + k] = vecc_double(rs);
-        }
-        acc += vecc_value(rs) * vecc_value(rs);
-      }
-    }
-  }
+  VeccColdDev cold{ev};
+  vecc_grid_walk<VEC>(VeccCalcXr{alpha},
+                      VeccOperands<VeccCalcXr>{{x, r, const_cast<double *>(p), const_cast<double *>(w)}, {0u, 1u, 2u, 3u}},
+                      n, cold, &acc);
   acc = block_sum(acc, s_w);
   reduce_finish(acc, out, s_w);
 }
@@ -6429,89 +6319,41 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_xr_vecc_kernel(double *__rest
 template <int VEC>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_p_vecc_kernel(double *__restrict__ p, const double *__restrict__ r,
                                                                  double beta, int n, EventRing ev) {
-  uint32_t bad = 0u;
-  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
-  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
-  for (long i = first; i < n; i += stride) {
-    if (VEC == 2 && i + 1 < n) {
-      const double2 pv = *reinterpret_cast<const double2 *>(p + i);
-      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
-      const uint64_t p0 = vecc_bits(pv.x), p1 = vecc_bits(pv.y), r0 = vecc_bits(rv.x), r1 = vecc_bits(rv.y);
-      const uint32_t sus = (vecc_suspect(p0) | vecc_suspect(p1)) | (vecc_suspect(r0) | vecc_suspect(r1));
-      bad |= sus;
-      if (!sus) {
-        const uint64_t q0 = vecc_encode(vecc_value(r0) + beta * vecc_value(p0));
-        const uint64_t q1 = vecc_encode(vecc_value(r1) + beta * vecc_value(p1));
-        *reinterpret_cast<double2 *>(p + i) = make_double2(vecc_double(q0), vecc_double(q1));
-      }
-    } else {
-      const uint64_t p0 = vecc_bits(p[i]), r0 = vecc_bits(r[i]);
-      const uint32_t sus = vecc_suspect(p0) | vecc_suspect(r0);
-      bad |= sus;
-      if (!sus) p[i] = vecc_double(vecc_encode(vecc_value(r0) + beta * vecc_value(p0)));
-    }
-  }
-  if (__builtin_expect(bad != 0u, 0)) {
-    for (long i = first; i < n; i += stride) {
-      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
-      uint32_t sus = 0u;
-      for (int k = 0; k < m; k++) sus |= vecc_suspect(vecc_bits(p[i + k])) | vecc_suspect(vecc_bits(r[i + k]));
-      if (!sus) continue;  // carried out above
-      for (int k = 0; k < m; k++) {
-        const uint32_t j = (uint32_t)(i + k);
-        const double po = vecc_decode_cold_ok(p + i + k, j, 0u, ev), ro = vecc_decode_cold_ok(r + i + k, j, 1u, ev);
-        p[i + k] = vecc_double(vecc_encode(ro + beta * po));
-      }
-    }
-  }
+  VeccColdDev cold{ev};
+  vecc_grid_walk<VEC>(VeccCalcP{beta}, VeccOperands<VeccCalcP>{{p, const_cast<double *>(r)}, {0u, 1u}}, n, cold, nullptr);
 }
 
 hipError_t launch_vector_encode(double *v, int n, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
-  if (aligned16(v))
-    hipLaunchKernelGGL(vector_encode_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, v, n);
-  else
-    hipLaunchKernelGGL(vector_encode_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, v, n);
+  ABFT_VEC_DISPATCH(vector_encode_kernel, (), aligned16(v), nb, v, n);
   return hipGetLastError();
 }
 
 hipError_t launch_vector_scrub(double *v, int n, uint32_t *counts, EventRing ev, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
-  if (aligned16(v))
-    hipLaunchKernelGGL(vector_scrub_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, v, n, counts, ev);
-  else
-    hipLaunchKernelGGL(vector_scrub_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, v, n, counts, ev);
+  ABFT_VEC_DISPATCH(vector_scrub_kernel, (), aligned16(v), nb, v, n, counts, ev);
   return hipGetLastError();
 }
 
 hipError_t launch_dot_vecc(const double *a, const double *b, int n, const ReduceOut &out, EventRing ev, hipStream_t s) {
   const int nb = reduce_blocks(n);
-  if (aligned16(a, b))
-    hipLaunchKernelGGL(dot_vecc_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, a, b, n, out, ev);
-  else
-    hipLaunchKernelGGL(dot_vecc_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, a, b, n, out, ev);
+  ABFT_VEC_DISPATCH(dot_vecc_kernel, (), aligned16(a, b), nb, a, b, n, out, ev);
   return hipGetLastError();
 }
 
 hipError_t launch_calc_xr_vecc(double *x, double *r, const double *p, const double *w, double alpha, int n,
                                const ReduceOut &out, EventRing ev, hipStream_t s) {
   const int nb = reduce_blocks(n);
-  if (aligned16(x, r, p, w))
-    hipLaunchKernelGGL(calc_xr_vecc_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, r, p, w, alpha, n, out, ev);
-  else
-    hipLaunchKernelGGL(calc_xr_vecc_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, r, p, w, alpha, n, out, ev);
+  ABFT_VEC_DISPATCH(calc_xr_vecc_kernel, (), aligned16(x, r, p, w), nb, x, r, p, w, alpha, n, out, ev);
   return hipGetLastError();
 }
 
 hipError_t launch_calc_p_vecc(double *p, const double *r, double beta, int n, EventRing ev, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
-  if (aligned16(p, r))
-    hipLaunchKernelGGL(calc_p_vecc_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, n, ev);
-  else
-    hipLaunchKernelGGL(calc_p_vecc_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, p, r, beta, n, ev);
+  ABFT_VEC_DISPATCH(calc_p_vecc_kernel, (), aligned16(p, r), nb, p, r, beta, n, ev);
   return hipGetLastError();
 }
 
@@ -6522,7 +6364,8 @@ hipError_t launch_calc_p_vecc(double *p, const double *r, double beta, int n, Ev
 // the hot loops, a step with a suspect word only noted, the chain walked once more behind the loop -- and per element
 // the same operands and roundings, per thread the same order of adds: with the walk chosen alike (VEC, by the
 // alignment of the operands) x, r and r.r have calc_xr_vecc's bits and p has calc_p_vecc's.
-// ONE body per pair (section 5i): the host-scalar kernel and the guarded one call the same walk.  op_*: the ordinal
+// ONE body per pair (section 5i): the host-scalar kernel and the guarded one call the same walk -- the r half
+// vecc_walk with VeccCalcR<false>, the x / p half written out (section 5p).  op_*: the ordinal
 // a repaired word of that vector is reported under -- the host-scalar entries count their own arguments, the guarded
 // entry counts vec, x, r, p, w as 0..4.
 
@@ -6531,56 +6374,13 @@ template <int VEC>
 __device__ __forceinline__ double calc_r_vecc_walk(double *__restrict__ r, const double *__restrict__ w, double alpha,
                                                    int n, uint32_t op_r, uint32_t op_w, EventRing ev) {
   double acc = 0.0;
-  uint32_t bad = 0u;
-  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
-  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
-  for (long i = first; i < n; i += stride) {
-    if (VEC == 2 && i + 1 < n) {
-      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
-      const double2 wv = *reinterpret_cast<const double2 *>(w + i);
-      const uint64_t r0 = vecc_bits(rv.x), r1 = vecc_bits(rv.y), w0 = vecc_bits(wv.x), w1 = vecc_bits(wv.y);
-      const uint32_t sus = (vecc_suspect(r0) | vecc_suspect(r1)) | (vecc_suspect(w0) | vecc_suspect(w1));
-      bad |= sus;
-      if (!sus) {
-        const uint64_t rs0 = vecc_encode(vecc_value(r0) - alpha * vecc_value(w0));
-        const uint64_t rs1 = vecc_encode(vecc_value(r1) - alpha * vecc_value(w1));
-        *reinterpret_cast<double2 *>(r + i) = make_double2(vecc_double(rs0), vecc_double(rs1));
-        acc += vecc_value(rs0) * vecc_value(rs0);
-        acc += vecc_value(rs1) * vecc_value(rs1);
-      }
-    } else {
-      const uint64_t r0 = vecc_bits(r[i]), w0 = vecc_bits(w[i]);
-      const uint32_t sus = vecc_suspect(r0) | vecc_suspect(w0);
-      bad |= sus;
-      if (!sus) {
-        const uint64_t rs = vecc_encode(vecc_value(r0) - alpha * vecc_value(w0));
-        r[i] = vecc_double(rs);
-        acc += vecc_value(rs) * vecc_value(rs);
-      }
-    }
-  }
-  if (__builtin_expect(bad != 0u, 0)) {
-    acc = 0.0;
-    for (long i = first; i < n; i += stride) {
-      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
-      uint32_t sus = 0u;
-      for (int k = 0; k < m; k++) sus |= vecc_suspect(vecc_bits(r[i + k])) | vecc_suspect(vecc_bits(w[i + k]));
-      for (int k = 0; k < m; k++) {
-        uint64_t rs = vecc_bits(r[i + k]);  // a step carried out above: what it stored
-        if (sus) {
-          const uint32_t j = (uint32_t)(i + k);
-          const double ro = vecc_decode_cold_ok(r + i + k, j, op_r, ev);
-          const double wo = vecc_decode_cold_ok(w + i + k, j, op_w, ev);
-          rs = vecc_encode(ro - alpha * wo);
-          r[i + k] = vecc_double(rs);
-        }
-        acc += vecc_value(rs) * vecc_value(rs);
-      }
-    }
-  }
+  VeccColdDev cold{ev};
+  vecc_grid_walk<VEC>(VeccCalcR<false>{alpha}, VeccOperands<VeccCalcR<false>>{{r, const_cast<double *>(w)}, {op_r, op_w}},
+                      n, cold, &acc);
   return acc;
 }
 
+// (this walk keeps its hand-written form: under vecc_walk its VEC == 2 instances took one VGPR more)
 // x <- enc(dec(x) + alpha dec(p)) and p <- enc(dec(r) + beta dec(p)) in one pass over p, both from the old p;
 // r is not written back
 template <int VEC>
@@ -6698,10 +6498,7 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_vecc_until_kernel(double *
 hipError_t launch_calc_r_vecc(double *r, const double *w, double alpha, int n, const ReduceOut &out, EventRing ev,
                               hipStream_t s) {
   const int nb = reduce_blocks(n);
-  if (aligned16(r, w))
-    hipLaunchKernelGGL(calc_r_vecc_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, alpha, n, out, ev);
-  else
-    hipLaunchKernelGGL(calc_r_vecc_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, alpha, n, out, ev);
+  ABFT_VEC_DISPATCH(calc_r_vecc_kernel, (), aligned16(r, w), nb, r, w, alpha, n, out, ev);
   return hipGetLastError();
 }
 
@@ -6709,20 +6506,14 @@ hipError_t launch_calc_px_vecc(double *x, double *p, const double *r, double alp
                                hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
-  if (aligned16(x, p, r))
-    hipLaunchKernelGGL(calc_px_vecc_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, alpha, beta, n, ev);
-  else
-    hipLaunchKernelGGL(calc_px_vecc_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, alpha, beta, n, ev);
+  ABFT_VEC_DISPATCH(calc_px_vecc_kernel, (), aligned16(x, p, r), nb, x, p, r, alpha, beta, n, ev);
   return hipGetLastError();
 }
 
 hipError_t launch_calc_r_vecc_until(double *r, const double *w, const double *rr, const double *pw, double threshold,
                                     double *alpha_out, int n, const ReduceOut &out, EventRing ev, hipStream_t s) {
   const int nb = reduce_blocks(n);
-  if (aligned16(r, w))
-    hipLaunchKernelGGL(calc_r_vecc_until_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, rr, pw, threshold, alpha_out, n, out, ev);
-  else
-    hipLaunchKernelGGL(calc_r_vecc_until_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, rr, pw, threshold, alpha_out, n, out, ev);
+  ABFT_VEC_DISPATCH(calc_r_vecc_until_kernel, (), aligned16(r, w), nb, r, w, rr, pw, threshold, alpha_out, n, out, ev);
   return hipGetLastError();
 }
 
@@ -6730,10 +6521,8 @@ hipError_t launch_calc_px_vecc_until(double *x, double *p, const double *r, cons
                                      double threshold, const double *alpha_ptr, int n, EventRing ev, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
-  if (aligned16(x, p, r))
-    hipLaunchKernelGGL(calc_px_vecc_until_kernel<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, rr, rr_new, threshold, alpha_ptr, n, ev);
-  else
-    hipLaunchKernelGGL(calc_px_vecc_until_kernel<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, rr, rr_new, threshold, alpha_ptr, n, ev);
+  ABFT_VEC_DISPATCH(calc_px_vecc_until_kernel, (), aligned16(x, p, r), nb, x, p, r, rr, rr_new, threshold, alpha_ptr, n,
+                    ev);
   return hipGetLastError();
 }
 
@@ -7088,7 +6877,8 @@ hipError_t launch_calc_px_block_vecc_until(double *x, double *p, const double *r
 // walked once more behind the loop.  One exception to "a vector that is only read is not written back": dinv outlives
 // the iteration -- no kernel ever rewrites it --, so the cold path stores a repaired dinv word back (the one lane that
 // owns the element: a flip in dinv is reported once and gone afterwards; two flips stay, fatal).
-// ONE body per pair (section 5i), the operand ordinals passed in as above.
+// ONE body per pair (section 5i), the operand ordinals passed in as above: the two halves are vecc_walk with
+// VeccCalcR<true> and VeccCalcPxPrecond, whose DINV operand is the one stored back; the start is written out (section 5p).
 
 // vecc_decode_cold_ok for a dinv word: the repaired word is stored back
 __device__ __forceinline__ double vecc_decode_cold_fix(double *p, uint32_t index, uint32_t operand, const EventRing &ev) {
@@ -7101,6 +6891,7 @@ __device__ __forceinline__ double vecc_decode_cold_fix(double *p, uint32_t index
   return vecc_value(w);
 }
 
+// (this walk keeps its hand-written form: under vecc_walk its VEC == 1 instance took two VGPRs more; section 5p)
 // p <- enc(z), z = dec(dinv) * dec(r); acc += {sum dec(r) z, sum dec(r)^2}.  r is not written back, p only written.
 template <int VEC>
 __device__ __forceinline__ void precond_start_vecc_walk(const double *__restrict__ r, double *__restrict__ dinv,
@@ -7158,66 +6949,9 @@ template <int VEC>
 __device__ __forceinline__ void calc_r_precond_vecc_walk(double *__restrict__ r, const double *__restrict__ w,
                                                          double *__restrict__ dinv, double alpha, int n, uint32_t op_r,
                                                          uint32_t op_w, uint32_t op_d, EventRing ev, double *acc) {
-  uint32_t bad = 0u;
-  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
-  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
-  for (long i = first; i < n; i += stride) {
-    if (VEC == 2 && i + 1 < n) {
-      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
-      const double2 wv = *reinterpret_cast<const double2 *>(w + i);
-      const double2 dv = *reinterpret_cast<const double2 *>(dinv + i);
-      const uint64_t r0 = vecc_bits(rv.x), r1 = vecc_bits(rv.y), w0 = vecc_bits(wv.x), w1 = vecc_bits(wv.y);
-      const uint64_t d0 = vecc_bits(dv.x), d1 = vecc_bits(dv.y);
-      const uint32_t sus = (vecc_suspect(r0) | vecc_suspect(r1)) | (vecc_suspect(w0) | vecc_suspect(w1)) |
-                           (vecc_suspect(d0) | vecc_suspect(d1));
-      bad |= sus;
-      if (!sus) {
-        const uint64_t rs0 = vecc_encode(vecc_value(r0) - alpha * vecc_value(w0));
-        const uint64_t rs1 = vecc_encode(vecc_value(r1) - alpha * vecc_value(w1));
-        *reinterpret_cast<double2 *>(r + i) = make_double2(vecc_double(rs0), vecc_double(rs1));
-        const double z0 = vecc_value(d0) * vecc_value(rs0), z1 = vecc_value(d1) * vecc_value(rs1);
-        acc[0] += vecc_value(rs0) * z0;
-        acc[0] += vecc_value(rs1) * z1;
-        acc[1] += vecc_value(rs0) * vecc_value(rs0);
-        acc[1] += vecc_value(rs1) * vecc_value(rs1);
-      }
-    } else {
-      const uint64_t r0 = vecc_bits(r[i]), w0 = vecc_bits(w[i]), d0 = vecc_bits(dinv[i]);
-      const uint32_t sus = vecc_suspect(r0) | vecc_suspect(w0) | vecc_suspect(d0);
-      bad |= sus;
-      if (!sus) {
-        const uint64_t rs = vecc_encode(vecc_value(r0) - alpha * vecc_value(w0));
-        r[i] = vecc_double(rs);
-        const double z = vecc_value(d0) * vecc_value(rs);
-        acc[0] += vecc_value(rs) * z;
-        acc[1] += vecc_value(rs) * vecc_value(rs);
-      }
-    }
-  }
-  if (__builtin_expect(bad != 0u, 0)) {
-    acc[0] = 0.0; acc[1] = 0.0;
-    for (long i = first; i < n; i += stride) {
-      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
-      uint32_t sus = 0u;
-      for (int k = 0; k < m; k++)
-        sus |= vecc_suspect(vecc_bits(r[i + k])) | vecc_suspect(vecc_bits(w[i + k])) | vecc_suspect(vecc_bits(dinv[i + k]));
-      for (int k = 0; k < m; k++) {
-        uint64_t rs = vecc_bits(r[i + k]);     // a step carried out above: what it stored ...
-        double d = vecc_value(vecc_bits(dinv[i + k]));  // ... and the clean word it multiplied with
-        if (sus) {
-          const uint32_t j = (uint32_t)(i + k);
-          const double ro = vecc_decode_cold_ok(r + i + k, j, op_r, ev);
-          const double wo = vecc_decode_cold_ok(w + i + k, j, op_w, ev);
-          d = vecc_decode_cold_fix(dinv + i + k, j, op_d, ev);
-          rs = vecc_encode(ro - alpha * wo);
-          r[i + k] = vecc_double(rs);
-        }
-        const double z = d * vecc_value(rs);
-        acc[0] += vecc_value(rs) * z;
-        acc[1] += vecc_value(rs) * vecc_value(rs);
-      }
-    }
-  }
+  VeccColdDev cold{ev};
+  vecc_grid_walk<VEC>(VeccCalcR<true>{alpha},
+                      VeccOperands<VeccCalcR<true>>{{r, const_cast<double *>(w), dinv}, {op_r, op_w, op_d}}, n, cold, acc);
 }
 
 // x <- enc(dec(x) + alpha dec(p)) and p <- enc(dec(dinv) dec(r) + beta dec(p)) in one pass over p, both from the
@@ -7227,59 +6961,10 @@ __device__ __forceinline__ void calc_px_precond_vecc_walk(double *__restrict__ x
                                                           const double *__restrict__ r, double *__restrict__ dinv,
                                                           double alpha, double beta, int n, uint32_t op_x,
                                                           uint32_t op_p, uint32_t op_r, uint32_t op_d, EventRing ev) {
-  uint32_t bad = 0u;
-  const long stride = (long)gridDim.x * ABFT_BLOCK * VEC;
-  const long first = ((long)blockIdx.x * ABFT_BLOCK + threadIdx.x) * VEC;
-  for (long i = first; i < n; i += stride) {
-    if (VEC == 2 && i + 1 < n) {
-      const double2 pv = *reinterpret_cast<const double2 *>(p + i);
-      const double2 xv = *reinterpret_cast<const double2 *>(x + i);
-      const double2 rv = *reinterpret_cast<const double2 *>(r + i);
-      const double2 dv = *reinterpret_cast<const double2 *>(dinv + i);
-      const uint64_t p0 = vecc_bits(pv.x), p1 = vecc_bits(pv.y), x0 = vecc_bits(xv.x), x1 = vecc_bits(xv.y);
-      const uint64_t r0 = vecc_bits(rv.x), r1 = vecc_bits(rv.y), d0 = vecc_bits(dv.x), d1 = vecc_bits(dv.y);
-      const uint32_t sus = (vecc_suspect(p0) | vecc_suspect(p1)) | (vecc_suspect(x0) | vecc_suspect(x1)) |
-                           (vecc_suspect(r0) | vecc_suspect(r1)) | (vecc_suspect(d0) | vecc_suspect(d1));
-      bad |= sus;
-      if (!sus) {
-        const uint64_t xs0 = vecc_encode(vecc_value(x0) + alpha * vecc_value(p0));
-        const uint64_t xs1 = vecc_encode(vecc_value(x1) + alpha * vecc_value(p1));
-        const double z0 = vecc_value(d0) * vecc_value(r0), z1 = vecc_value(d1) * vecc_value(r1);
-        const uint64_t q0 = vecc_encode(z0 + beta * vecc_value(p0));
-        const uint64_t q1 = vecc_encode(z1 + beta * vecc_value(p1));
-        *reinterpret_cast<double2 *>(x + i) = make_double2(vecc_double(xs0), vecc_double(xs1));
-        *reinterpret_cast<double2 *>(p + i) = make_double2(vecc_double(q0), vecc_double(q1));
-      }
-    } else {
-      const uint64_t p0 = vecc_bits(p[i]), x0 = vecc_bits(x[i]), r0 = vecc_bits(r[i]), d0 = vecc_bits(dinv[i]);
-      const uint32_t sus = (vecc_suspect(p0) | vecc_suspect(x0)) | (vecc_suspect(r0) | vecc_suspect(d0));
-      bad |= sus;
-      if (!sus) {
-        const double z = vecc_value(d0) * vecc_value(r0);
-        x[i] = vecc_double(vecc_encode(vecc_value(x0) + alpha * vecc_value(p0)));
-        p[i] = vecc_double(vecc_encode(z + beta * vecc_value(p0)));
-      }
-    }
-  }
-  if (__builtin_expect(bad != 0u, 0)) {
-    for (long i = first; i < n; i += stride) {
-      const int m = (VEC == 2 && i + 1 < n) ? 2 : 1;
-      uint32_t sus = 0u;
-      for (int k = 0; k < m; k++)
-        sus |= (vecc_suspect(vecc_bits(p[i + k])) | vecc_suspect(vecc_bits(x[i + k]))) |
-               (vecc_suspect(vecc_bits(r[i + k])) | vecc_suspect(vecc_bits(dinv[i + k])));
-      if (!sus) continue;  // carried out above
-      for (int k = 0; k < m; k++) {
-        const uint32_t j = (uint32_t)(i + k);
-        const double xo = vecc_decode_cold_ok(x + i + k, j, op_x, ev);
-        const double po = vecc_decode_cold_ok(p + i + k, j, op_p, ev);
-        const double ro = vecc_decode_cold_ok(r + i + k, j, op_r, ev);
-        const double z = vecc_decode_cold_fix(dinv + i + k, j, op_d, ev) * ro;
-        x[i + k] = vecc_double(vecc_encode(xo + alpha * po));
-        p[i + k] = vecc_double(vecc_encode(z + beta * po));
-      }
-    }
-  }
+  VeccColdDev cold{ev};
+  vecc_grid_walk<VEC>(VeccCalcPxPrecond{alpha, beta},
+                      VeccOperands<VeccCalcPxPrecond>{{x, p, const_cast<double *>(r), dinv}, {op_x, op_p, op_r, op_d}}, n,
+                      cold, nullptr);
 }
 
 // p = enc(dinv r); {r.z, r.r} (operands 0: r, 1: dinv, 2: p)
@@ -7363,25 +7048,17 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_precond_vecc_until_kernel(
 }
 
 // (each chooses its walk over its own operands, in the host-scalar and in the guarded form alike)
-#define ABFT_VECC_DISPATCH(KERNEL, VEC2, ...)                                                   \
-  do {                                                                                          \
-    if (VEC2)                                                                                   \
-      hipLaunchKernelGGL(KERNEL<2>, dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);             \
-    else                                                                                        \
-      hipLaunchKernelGGL(KERNEL<1>, dim3(nb), dim3(ABFT_BLOCK), 0, s, __VA_ARGS__);             \
-  } while (0)
-
 hipError_t launch_precond_start_vecc(const double *r, double *dinv, double *p, int n, const ReduceOutK &out,
                                      EventRing ev, hipStream_t s) {
   const int nb = reduce_blocks(n);
-  ABFT_VECC_DISPATCH(precond_start_vecc_kernel, aligned16(r, dinv, p), r, dinv, p, n, out, ev);
+  ABFT_VEC_DISPATCH(precond_start_vecc_kernel, (), aligned16(r, dinv, p), nb, r, dinv, p, n, out, ev);
   return hipGetLastError();
 }
 
 hipError_t launch_calc_r_precond_vecc(double *r, const double *w, double *dinv, double alpha, int n,
                                       const ReduceOutK &out, EventRing ev, hipStream_t s) {
   const int nb = reduce_blocks(n);
-  ABFT_VECC_DISPATCH(calc_r_precond_vecc_kernel, aligned16(r, w, dinv), r, w, dinv, alpha, n, out, ev);
+  ABFT_VEC_DISPATCH(calc_r_precond_vecc_kernel, (), aligned16(r, w, dinv), nb, r, w, dinv, alpha, n, out, ev);
   return hipGetLastError();
 }
 
@@ -7389,7 +7066,7 @@ hipError_t launch_calc_px_precond_vecc(double *x, double *p, const double *r, do
                                        int n, EventRing ev, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
-  ABFT_VECC_DISPATCH(calc_px_precond_vecc_kernel, aligned16(x, p, r, dinv), x, p, r, dinv, alpha, beta, n, ev);
+  ABFT_VEC_DISPATCH(calc_px_precond_vecc_kernel, (), aligned16(x, p, r, dinv), nb, x, p, r, dinv, alpha, beta, n, ev);
   return hipGetLastError();
 }
 
@@ -7397,8 +7074,8 @@ hipError_t launch_calc_r_precond_vecc_until(double *r, const double *w, double *
                                             const double *pw, double threshold, double *alpha_out, int n,
                                             const ReduceOutD &out, EventRing ev, hipStream_t s) {
   const int nb = reduce_blocks(n);
-  ABFT_VECC_DISPATCH(calc_r_precond_vecc_until_kernel, aligned16(r, w, dinv), r, w, dinv, in, pw, threshold, alpha_out,
-                     n, out, ev);
+  ABFT_VEC_DISPATCH(calc_r_precond_vecc_until_kernel, (), aligned16(r, w, dinv), nb, r, w, dinv, in, pw, threshold,
+                    alpha_out, n, out, ev);
   return hipGetLastError();
 }
 
@@ -7407,8 +7084,7 @@ hipError_t launch_calc_px_precond_vecc_until(double *x, double *p, const double 
                                              EventRing ev, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const int nb = reduce_blocks(n);
-  ABFT_VECC_DISPATCH(calc_px_precond_vecc_until_kernel, aligned16(x, p, r, dinv), x, p, r, dinv, in, out, threshold,
-                     alpha_ptr, n, ev);
+  ABFT_VEC_DISPATCH(calc_px_precond_vecc_until_kernel, (), aligned16(x, p, r, dinv), nb, x, p, r, dinv, in, out,
+                    threshold, alpha_ptr, n, ev);
   return hipGetLastError();
 }
-#undef ABFT_VECC_DISPATCH
