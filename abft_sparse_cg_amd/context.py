@@ -976,6 +976,7 @@ def _device_batches(ctx, max_itrs, stride, graph, rec, tail, seed, enqueue, reco
     short last one, enqueued call by call.  Then the trail is downloaded -- the one synchronisation, which drains
     the events -- and record(t, i, done) is called for i in order: true when iteration `done` was live (its
     bookkeeping done), false at the first frozen one, which ends the loop.  -> the count of live iterations."""
+    # (the records' lengths and word indices, here and in the callers, are those csrc/guard_protocol.h defines)
     pw_at = rec * (stride + 1)
     trail = ctx.create_vector(pw_at + tail)
     first, last = ctx.view_vector(trail, 0, rec), ctx.view_vector(trail, rec * stride, rec)

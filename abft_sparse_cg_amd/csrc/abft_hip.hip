@@ -20,6 +20,7 @@
 #include "abft_internal.h"
 // palettes the pool of a matrix holds beyond those of create (one per re-planned block at most)
 #define ABFT_PAL_SPARE 1024u
+#include "guard_protocol.h"
 #include "layout_plan.h"
 #include "loop_state.h"
 
@@ -3550,8 +3551,8 @@ static int check_guarded_iteration(abft_hip_ctx *ctx, const char *what, const ab
     return set_err(ABFT_ERR_INVALID, "%s: a peer board is attached; the guarded iteration runs on one rank", what);
   // two pairs (preconditioned: records of four doubles) and the pair of the SpMV
   auto apart = [](const double *a, int na, const double *b, int nb) { return a + na <= b || b + nb <= a; };
-  const int rec = precond ? 4 : 2;
-  if (!apart(dev_in, rec, dev_pw, 2) || !apart(dev_in, rec, dev_out, rec) || !apart(dev_pw, 2, dev_out, rec))
+  const int rec = precond ? GuardQuad::LEN : GuardPair::LEN, pwl = GuardPair::PW_LEN;
+  if (!apart(dev_in, rec, dev_pw, pwl) || !apart(dev_in, rec, dev_out, rec) || !apart(dev_pw, pwl, dev_out, rec))
     return set_err(ABFT_ERR_INVALID, "%s: the scalar %s overlap", what, precond ? "records" : "pairs");
   if (int rc = check_cg_vectors(x, r, p, w, what)) return rc;
   const int n = x->n;
@@ -3834,8 +3835,8 @@ static int block_iteration_until(abft_hip_ctx *ctx, const char *what, bool vecc,
     for (int b = a + 1; b < 4; b++)
       if (!disjoint(four[a], four[b])) return set_err(ABFT_ERR_INVALID, "%s: X, R, P and W overlap", what);
   auto apart = [](const double *a, int na, const double *b, int nb) { return a + na <= b || b + nb <= a; };
-  const int rec = 2 * k + 2;
-  if (!apart(dev_in, rec, dev_pw, k + 1) || !apart(dev_in, rec, dev_out, rec) || !apart(dev_pw, k + 1, dev_out, rec))
+  const int rec = guard_block_len(k), pwl = guard_block_pw_len(k);
+  if (!apart(dev_in, rec, dev_pw, pwl) || !apart(dev_in, rec, dev_out, rec) || !apart(dev_pw, pwl, dev_out, rec))
     return set_err(ABFT_ERR_INVALID, "%s: the scalar records overlap", what);
   if (ctx->capturing && !block_loop_ready(ctx, mat, k))
     return set_err(ABFT_ERR_INVALID, "%s: called under graph capture before the context holds the partials of this "

@@ -16,6 +16,7 @@
 
 #include "abft_internal.h"
 #include "ecc_device.h"
+#include "guard_protocol.h"
 #include "vecc_walk.h"
 
 // native vector types (what __builtin_nontemporal_load accepts)
@@ -4176,43 +4177,45 @@ hipError_t launch_axpy_chain(const XUpd &u, int n, hipStream_t s) {
 }
 
 // ---- the guarded iteration (abft_hip_cg_iteration_until_dev) ----
-// calc_r_kernel and calc_px_kernel with the stop test of cg.cpp:94 in front: the launch is LIVE when
-// *rr > threshold (false for NaN, as `while (rr > conv)` is) and then walks, computes and reduces exactly as
-// the unguarded kernel does on the same grid -- same bits everywhere.  Otherwise it is FROZEN: every thread
-// returns before it touches a vector, a partial or the ticket, and one thread of the r half writes the new
-// pair {the bits of *rr, queued events}.  Every thread of both launches reads the same word, which neither
-// writes, so the decision is uniform over the grid and the same in both; no workgroup waits for another.
+// calc_r_kernel and calc_px_kernel behind the stop test that guard_protocol.h states, on GuardPair records.  A live
+// launch walks, computes and reduces exactly as the unguarded kernel does on the same grid: same bits everywhere.
 // (Kernels with symbols of their own and not a template flag on the two above; the streaming loop is the one body
 // calc_r_walk / calc_px_walk, called with r_out = r, p_out = p, x_out = x.)
+
+// The head of every single r half (REC: GuardPair, GuardQuad; Out: ReduceOut, ReduceOutD): frozen -> false, the record
+// handed on by one thread; live -> true with alpha, which one thread leaves in *alpha_out for the x / p half.
+template <class REC, class Out>
+__device__ __forceinline__ bool guard_r_head(const double *in, const double *pw, double threshold, double *alpha_out,
+                                             const Out &out, double *alpha) {
+  if (!REC::live(in, threshold)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+      REC::hand_on(in, out.dev_out, __hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    return false;
+  }
+  *alpha = REC::alpha(in, *pw);
+  if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = *alpha;
+  return true;
+}
+
 template <int VEC>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_until_kernel(double *r, const double *__restrict__ w,
                                                                   const double *rr, const double *pw,
                                                                   double threshold, double *alpha_out, int n,
                                                                   ReduceOut out) {
   __shared__ double s_w[4];
-  if (!(*rr > threshold)) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      // the bits, whatever they are (a NaN's payload included): moved as an integer
-      *reinterpret_cast<unsigned long long *>(out.dev_out) = *reinterpret_cast<const unsigned long long *>(rr);
-      out.dev_out[1] = (double)__hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return;
-  }
-  const double alpha = *rr / *pw;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;  // for the x half
+  double alpha;
+  if (!guard_r_head<GuardPair>(rr, pw, threshold, alpha_out, out, &alpha)) return;
   double acc = calc_r_walk<VEC>(r, w, alpha, n, r);
   acc = block_sum(acc, s_w);
   reduce_finish(acc, out, s_w);
 }
 
-// (rr: the pair the iteration started from -- the guard, and beta's denominator; rr_new: what the r half left)
 template <int VEC>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_until_kernel(double *p, const double *__restrict__ r, double *x,
                                                                    const double *rr, const double *rr_new,
                                                                    double threshold, const double *alpha_ptr, int n) {
-  const double rr0 = *rr;
-  if (!(rr0 > threshold)) return;
-  const double beta = *rr_new / rr0;
+  if (!GuardPair::live(rr, threshold)) return;
+  const double beta = GuardPair::beta(rr, rr_new);
   const double alpha = *alpha_ptr;
   calc_px_walk<VEC>(p, r, x, beta, alpha, n, p, x);
 }
@@ -4939,13 +4942,9 @@ hipError_t launch_calc_p_precond(double *p, const double *r, const double *dinv,
 }
 
 // ---- the guarded preconditioned iteration (abft_hip_pcg_iteration_until_dev) ----
-// calc_xr_precond_kernel<VEC, PAIRS, false> and calc_p_precond_kernel<VEC, PAIRS, true> behind the stop test of
-// calc_r_until_kernel / calc_px_until_kernel above, their scalars formed from device records of four doubles
-// {r.r, queued events, r.z, 0.0}: LIVE when in[0] > threshold (false for NaN) -- then alpha = in[2] / *pw and
-// beta = out[2] / in[2], and the walk, the per-thread sums and the fold are those kernels', bit for bit --, else
-// FROZEN: every thread returns before it touches a vector, a partial or the ticket, and one thread of the r half
-// hands the record on.  Both launches read the same word in[0], which neither writes: the decision is uniform
-// over the grid and the same in both; no workgroup waits for another.
+// calc_xr_precond_kernel<VEC, PAIRS, false> and calc_p_precond_kernel<VEC, PAIRS, true> behind the stop test, records
+// of the GuardQuad shape (guard_protocol.h); the walk, the per-thread sums and the fold of a live launch are those
+// kernels', bit for bit.
 // (Symbols of their own, as the plain guarded pair; the streaming loops are calc_xr_precond_walk<.., false> and
 // calc_p_precond_walk<.., true>, and the sums meet through reduce_totals_k as the unguarded kernel's do.)
 template <int VEC, bool PAIRS>
@@ -4955,27 +4954,13 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_precond_until_kernel(double
                                                                           double threshold, double *alpha_out, int n,
                                                                           ReduceOutD out) {
   __shared__ double s_w[16];
-  if (!(in[0] > threshold)) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      // the bits, whatever they are (a NaN's payload included): moved as integers
-      const unsigned long long *src = reinterpret_cast<const unsigned long long *>(in);
-      unsigned long long *dst = reinterpret_cast<unsigned long long *>(out.dev_out);
-      const unsigned long long rr_bits = src[0], rz_bits = src[2];
-      dst[0] = rr_bits;
-      out.dev_out[1] = (double)__hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      dst[2] = rz_bits;
-      out.dev_out[3] = 0.0;
-    }
-    return;
-  }
-  const double alpha = in[2] / *pw;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;  // for the x / p half
+  double alpha;
+  if (!guard_r_head<GuardQuad>(in, pw, threshold, alpha_out, out, &alpha)) return;
   double acc[2] = {0.0, 0.0};
   calc_xr_precond_walk<VEC, PAIRS, false>(nullptr, r, nullptr, w, dinv, alpha, n, acc);
   reduce_finish_d(acc, out, s_w);
 }
 
-// (in: the record the iteration started from -- the guard, and beta's denominator; out: what the r half left)
 template <int VEC, bool PAIRS>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_precond_until_kernel(double *__restrict__ p,
                                                                            const double *__restrict__ r,
@@ -4983,8 +4968,8 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_precond_until_kernel(doubl
                                                                            double *__restrict__ x, const double *in,
                                                                            const double *out, double threshold,
                                                                            const double *alpha_ptr, int n) {
-  if (!(in[0] > threshold)) return;
-  const double beta = out[2] / in[2];
+  if (!GuardQuad::live(in, threshold)) return;
+  const double beta = GuardQuad::beta(in, out);
   const double alpha = *alpha_ptr;
   calc_p_precond_walk<VEC, PAIRS, true>(p, r, dinv, x, beta, alpha, n);
 }
@@ -5282,14 +5267,8 @@ hipError_t launch_calc_px_block(double *x, double *p, const double *r, const dou
 
 // ---- the guarded block iteration (abft_hip_cg_block_iteration_until_dev) ----
 // spmm_fold_kernel<K>, calc_r_block_kernel<K, PRECOND> and calc_px_block_kernel<K, PRECOND> with their scalars on the
-// device and the column mask decided there.  Records of 2K + 2 doubles: [j] = r.r of column j, [K + j] = its r.z (the
-// plain form: the bits of [j]), [2K] = queued events, [2K + 1] = 0.0; the SpMM's products as K doubles and the events
-// word.  Column j is LIVE when in[j] > threshold (false for NaN): then alpha[j] = in[K + j] / pw[j], beta[j] =
-// out[K + j] / in[K + j], and the walk, the selects, the per-thread sums and the folds are those kernels', bit for
-// bit.  A FROZEN column keeps its bits through the same selects and its record words are handed on as integers.
-// With no column live every thread returns before it touches a vector, a partial or the ticket, and one thread of
-// the r half hands the record on.  Both halves form the mask from the same words of `in`, which neither writes: the
-// decision is uniform over the grid and the same in both launches; no workgroup waits for another.
+// device and the column mask decided there, on GuardBlock<K> records (guard_protocol.h).  A live column's walk, selects,
+// sums and folds are those kernels', bit for bit; a frozen column keeps its bits through the same selects.
 // (Symbols of their own, as the single guarded pairs; the chunk sums are fold_chunk_sum, the streaming loops
 // calc_r_block_walk / calc_px_block_walk, and the sums meet through reduce_totals_k as the unguarded kernels' do.)
 
@@ -5322,11 +5301,50 @@ __device__ __forceinline__ double uniform_f64(double v) {
   return __hiloint2double(hi, lo);
 }
 
+// The r half of every guarded block iteration is head, walk, tail.  The head -> the mask; none live: 0, the record
+// handed on by one thread; else the K alphas, which one thread leaves in alpha_out for the x / p half.
+// (noescape: the compiler passes the walk its alphas by value, as the unguarded kernel's code has them, only when it
+// sees that no call kept the array's address -- and it decides before this head is inlined)
 template <int K>
-__device__ __forceinline__ uint32_t block_live_mask(const double *in, double threshold) {
-  uint32_t active = 0u;
+__device__ __forceinline__ uint32_t guard_block_r_head(const double *in, const double *pw, double threshold,
+                                                       double *alpha_out, const ReduceOutB &out,
+                                                       double *alpha __attribute__((noescape))) {
+  const uint32_t active = GuardBlock<K>::live_mask(in, threshold);
+  if (!active) {
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+      GuardBlock<K>::hand_on(in, out.dev_out, __hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    return 0u;
+  }
 #pragma unroll
-  for (int j = 0; j < K; j++) active |= in[j] > threshold ? 1u << j : 0u;
+  for (int j = 0; j < K; j++) alpha[j] = uniform_f64(GuardBlock<K>::alpha(in, pw, j));
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < K; j++) alpha_out[j] = alpha[j];
+  }
+  return active;
+}
+
+// The tail: the S = PRECOND ? 2K : K sums meet (s_w: 8 S doubles) and the last block's first thread publishes
+template <int K, bool PRECOND>
+__device__ __forceinline__ void guard_block_r_tail(const double *acc, uint32_t active, const double *in,
+                                                   const ReduceOutB &out, double *s_w) {
+  constexpr int S = PRECOND ? 2 * K : K;
+  double tot[S];
+  if (!reduce_totals_k<S, ReduceOutB, uint32_t>(acc, out, s_w, tot) || threadIdx.x != 0) return;
+  GuardBlock<K>::template publish<PRECOND>(tot, active, in, out.dev_out, reduce_rearm(out));
+}
+
+// The head of the x / p half -> the mask, and when it is not 0 the K alphas and betas (out: what the r half left)
+template <int K>
+__device__ __forceinline__ uint32_t guard_block_px_head(const double *in, const double *out, double threshold,
+                                                        const double *alpha_ptr, double *alpha, double *beta) {
+  const uint32_t active = GuardBlock<K>::live_mask(in, threshold);
+  if (!active) return 0u;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    alpha[j] = alpha_ptr[j];
+    beta[j] = uniform_f64(GuardBlock<K>::beta(in, out, j));
+  }
   return active;
 }
 
@@ -5339,52 +5357,13 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_until_kernel(double *
                                                                         ReduceOutB out) {
   constexpr int S = PRECOND ? 2 * K : K;
   __shared__ double s_w[8 * S];
-  const uint32_t active = block_live_mask<K>(in, threshold);
-  const unsigned long long *src = reinterpret_cast<const unsigned long long *>(in);
-  unsigned long long *dst = reinterpret_cast<unsigned long long *>(out.dev_out);
-  if (!active) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      // the bits, whatever they are (a NaN's payload included): moved as integers
-      unsigned long long b[2 * K];
-#pragma unroll
-      for (int j = 0; j < 2 * K; j++) b[j] = src[j];
-#pragma unroll
-      for (int j = 0; j < 2 * K; j++) dst[j] = b[j];
-      out.dev_out[2 * K] = (double)__hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      out.dev_out[2 * K + 1] = 0.0;
-    }
-    return;
-  }
-  double alpha[K];
-#pragma unroll
-  for (int j = 0; j < K; j++) alpha[j] = uniform_f64(in[K + j] / pw[j]);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {  // for the x / p half
-#pragma unroll
-    for (int j = 0; j < K; j++) alpha_out[j] = alpha[j];
-  }
-  double acc[S];
-#pragma unroll
-  for (int j = 0; j < S; j++) acc[j] = 0.0;
+  double alpha[K], acc[S] = {};
+  const uint32_t active = guard_block_r_head<K>(in, pw, threshold, alpha_out, out, alpha);
+  if (!active) return;
   calc_r_block_walk<K, PRECOND>(r, w, dinv, alpha, active, n, acc);
-  // the hand-off: the record of 2K + 2 words, which mixes new sums and old words by the mask, is this kernel's own
-  double tot[S];
-  if (!reduce_totals_k<S, ReduceOutB, uint32_t>(acc, out, s_w, tot) || threadIdx.x != 0) return;
-  const uint32_t nev = reduce_rearm(out);
-#pragma unroll
-  for (int j = 0; j < K; j++) {
-    // a live column's new sums; a frozen one's words as they were read, not the recomputed sums
-    const unsigned long long rr_new = __double_as_longlong(PRECOND ? tot[2 * j + 1] : tot[j]);
-    const unsigned long long rz_new = PRECOND ? (unsigned long long)__double_as_longlong(tot[2 * j]) : rr_new;
-    const bool on = (active >> j) & 1u;
-    const unsigned long long rr_old = src[j], rz_old = src[K + j];
-    dst[j] = on ? rr_new : rr_old;
-    dst[K + j] = on ? rz_new : rz_old;
-  }
-  out.dev_out[2 * K] = (double)nev;
-  out.dev_out[2 * K + 1] = 0.0;
+  guard_block_r_tail<K, PRECOND>(acc, active, in, out, s_w);
 }
 
-// (in: the record the iteration started from -- the mask, and beta's denominators; out: what the r half left)
 template <int K, bool PRECOND>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_until_kernel(double *__restrict__ x, double *__restrict__ p,
                                                                          const double *__restrict__ r,
@@ -5392,14 +5371,9 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_until_kernel(double 
                                                                          const double *in, const double *out,
                                                                          double threshold, const double *alpha_ptr,
                                                                          int n) {
-  const uint32_t active = block_live_mask<K>(in, threshold);
-  if (!active) return;
   double alpha[K], beta[K];
-#pragma unroll
-  for (int j = 0; j < K; j++) {
-    alpha[j] = alpha_ptr[j];
-    beta[j] = uniform_f64(out[K + j] / in[K + j]);
-  }
+  const uint32_t active = guard_block_px_head<K>(in, out, threshold, alpha_ptr, alpha, beta);
+  if (!active) return;
   calc_px_block_walk<K, PRECOND>(x, p, r, dinv, alpha, beta, active, n);
 }
 
@@ -6455,9 +6429,9 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_vecc_kernel(double *__rest
   calc_px_vecc_walk<VEC>(x, p, r, alpha, beta, n, 0u, 1u, 2u, ev);
 }
 
-// The guarded forms: calc_r_until_kernel's and calc_px_until_kernel's protocol, word for word, in front of the
-// protected walks.  Operands as the guarded entry counts them: x 1, r 2, p 3, w 4 (0 is the SpMV's gathered vector).
-// A frozen launch touches no vector: it repairs nothing and reports nothing.
+// The guarded forms: calc_r_until_kernel and calc_px_until_kernel with the protected walks.  Operands as the guarded
+// entry counts them: x 1, r 2, p 3, w 4 (0 is the SpMV's gathered vector).  A frozen launch touches no vector: it
+// repairs nothing and reports nothing.
 template <int VEC>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_vecc_until_kernel(double *__restrict__ r,
                                                                        const double *__restrict__ w, const double *rr,
@@ -6465,30 +6439,20 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_vecc_until_kernel(double *_
                                                                        double *alpha_out, int n, ReduceOut out,
                                                                        EventRing ev) {
   __shared__ double s_w[4];
-  if (!(*rr > threshold)) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      // the bits, whatever they are (a NaN's payload included): moved as an integer
-      *reinterpret_cast<unsigned long long *>(out.dev_out) = *reinterpret_cast<const unsigned long long *>(rr);
-      out.dev_out[1] = (double)__hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return;
-  }
-  const double alpha = *rr / *pw;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;  // for the x half
+  double alpha;
+  if (!guard_r_head<GuardPair>(rr, pw, threshold, alpha_out, out, &alpha)) return;
   double acc = calc_r_vecc_walk<VEC>(r, w, alpha, n, 2u, 4u, ev);
   acc = block_sum(acc, s_w);
   reduce_finish(acc, out, s_w);
 }
 
-// (rr: the pair the iteration started from -- the guard, and beta's denominator; rr_new: what the r half left)
 template <int VEC>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_vecc_until_kernel(double *__restrict__ x, double *__restrict__ p,
                                                                         const double *__restrict__ r, const double *rr,
                                                                         const double *rr_new, double threshold,
                                                                         const double *alpha_ptr, int n, EventRing ev) {
-  const double rr0 = *rr;
-  if (!(rr0 > threshold)) return;
-  const double beta = *rr_new / rr0;
+  if (!GuardPair::live(rr, threshold)) return;
+  const double beta = GuardPair::beta(rr, rr_new);
   const double alpha = *alpha_ptr;
   calc_px_vecc_walk<VEC>(x, p, r, alpha, beta, n, 1u, 3u, 2u, ev);
 }
@@ -6735,11 +6699,10 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_vecc_kernel(double *
   calc_px_block_vecc_walk<K>(x, p, r, alpha.v, beta.v, active, n, 0u, 1u, 2u, ev);
 }
 
-// The guarded forms (abft_hip_cg_block_vecc_iteration_until_dev): calc_r_block_until_kernel's
-// and calc_px_block_until_kernel's protocol, word for word, in front of the protected block walks.  Records, mask,
-// quotients and the hand-off are the plain guarded kernels' (PRECOND = false); records and dev_pw are plain doubles
-// outside any code.  Operands as the guarded entries count them: X 1, R 2, P 3, W 4 (0 is the SpMM's gathered P).
-// A launch with no live column touches no vector: it repairs nothing and reports nothing.
+// The guarded forms (abft_hip_cg_block_vecc_iteration_until_dev): the heads and the tail of
+// calc_r_block_until_kernel and calc_px_block_until_kernel (PRECOND = false) around the protected block walks; records
+// and dev_pw are plain doubles outside any code.  Operands as the guarded entries count them: X 1, R 2, P 3, W 4 (0 is
+// the SpMM's gathered P).  A launch with no live column touches no vector: it repairs nothing and reports nothing.
 template <int K>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_vecc_until_kernel(double *__restrict__ r,
                                                                              const double *__restrict__ w,
@@ -6747,50 +6710,13 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_vecc_until_kernel(dou
                                                                              double threshold, double *alpha_out,
                                                                              int n, ReduceOutB out, EventRing ev) {
   __shared__ double s_w[8 * K];
-  const uint32_t active = block_live_mask<K>(in, threshold);
-  const unsigned long long *src = reinterpret_cast<const unsigned long long *>(in);
-  unsigned long long *dst = reinterpret_cast<unsigned long long *>(out.dev_out);
-  if (!active) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      // the bits, whatever they are (a NaN's payload included): moved as integers
-      unsigned long long b[2 * K];
-#pragma unroll
-      for (int j = 0; j < 2 * K; j++) b[j] = src[j];
-#pragma unroll
-      for (int j = 0; j < 2 * K; j++) dst[j] = b[j];
-      out.dev_out[2 * K] = (double)__hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      out.dev_out[2 * K + 1] = 0.0;
-    }
-    return;
-  }
-  double alpha[K];
-#pragma unroll
-  for (int j = 0; j < K; j++) alpha[j] = uniform_f64(in[K + j] / pw[j]);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {  // for the x / p half
-#pragma unroll
-    for (int j = 0; j < K; j++) alpha_out[j] = alpha[j];
-  }
-  double acc[K];
-#pragma unroll
-  for (int j = 0; j < K; j++) acc[j] = 0.0;
+  double alpha[K], acc[K] = {};
+  const uint32_t active = guard_block_r_head<K>(in, pw, threshold, alpha_out, out, alpha);
+  if (!active) return;
   calc_r_block_vecc_walk<K>(r, w, alpha, active, n, 2u, 4u, ev, acc);
-  double tot[K];
-  if (!reduce_totals_k<K, ReduceOutB, uint32_t>(acc, out, s_w, tot) || threadIdx.x != 0) return;
-  const uint32_t nev = reduce_rearm(out);
-#pragma unroll
-  for (int j = 0; j < K; j++) {
-    // a live column's new sum in both words; a frozen one's words as they were read, not the recomputed sum
-    const unsigned long long rr_new = __double_as_longlong(tot[j]);
-    const bool on = (active >> j) & 1u;
-    const unsigned long long rr_old = src[j], rz_old = src[K + j];
-    dst[j] = on ? rr_new : rr_old;
-    dst[K + j] = on ? rr_new : rz_old;
-  }
-  out.dev_out[2 * K] = (double)nev;
-  out.dev_out[2 * K + 1] = 0.0;
+  guard_block_r_tail<K, false>(acc, active, in, out, s_w);
 }
 
-// (in: the record the iteration started from -- the mask, and beta's denominators; out: what the r half left)
 template <int K>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_vecc_until_kernel(double *__restrict__ x,
                                                                               double *__restrict__ p,
@@ -6798,14 +6724,9 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_vecc_until_kernel(do
                                                                               const double *in, const double *out,
                                                                               double threshold, const double *alpha_ptr,
                                                                               int n, EventRing ev) {
-  const uint32_t active = block_live_mask<K>(in, threshold);
-  if (!active) return;
   double alpha[K], beta[K];
-#pragma unroll
-  for (int j = 0; j < K; j++) {
-    alpha[j] = alpha_ptr[j];
-    beta[j] = uniform_f64(out[K + j] / in[K + j]);
-  }
+  const uint32_t active = guard_block_px_head<K>(in, out, threshold, alpha_ptr, alpha, beta);
+  if (!active) return;
   calc_px_block_vecc_walk<K>(x, p, r, alpha, beta, active, n, 1u, 3u, 2u, ev);
 }
 
@@ -7000,9 +6921,9 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_precond_vecc_kernel(double
   calc_px_precond_vecc_walk<VEC>(x, p, r, dinv, alpha, beta, n, 0u, 1u, 2u, 3u, ev);
 }
 
-// The guarded forms: calc_r_precond_until_kernel's and calc_px_precond_until_kernel's protocol, word for word, in
-// front of the protected walks.  Operands as the guarded entry counts them: x 1, r 2, p 3, w 4, dinv 5 (0 is the
-// SpMV's gathered vector).  A frozen launch touches no vector, dinv included: it repairs nothing and reports nothing.
+// The guarded forms: calc_r_precond_until_kernel and calc_px_precond_until_kernel with the protected walks.  Operands
+// as the guarded entry counts them: x 1, r 2, p 3, w 4, dinv 5 (0 is the SpMV's gathered vector).  A frozen launch
+// touches no vector, dinv included: it repairs nothing and reports nothing.
 template <int VEC>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_precond_vecc_until_kernel(double *__restrict__ r,
                                                                                const double *__restrict__ w,
@@ -7011,27 +6932,13 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_r_precond_vecc_until_kernel(d
                                                                                double threshold, double *alpha_out,
                                                                                int n, ReduceOutD out, EventRing ev) {
   __shared__ double s_w[16];
-  if (!(in[0] > threshold)) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      // the bits, whatever they are (a NaN's payload included): moved as integers
-      const unsigned long long *src = reinterpret_cast<const unsigned long long *>(in);
-      unsigned long long *dst = reinterpret_cast<unsigned long long *>(out.dev_out);
-      const unsigned long long rr_bits = src[0], rz_bits = src[2];
-      dst[0] = rr_bits;
-      out.dev_out[1] = (double)__hip_atomic_load(out.ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      dst[2] = rz_bits;
-      out.dev_out[3] = 0.0;
-    }
-    return;
-  }
-  const double alpha = in[2] / *pw;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;  // for the x / p half
+  double alpha;
+  if (!guard_r_head<GuardQuad>(in, pw, threshold, alpha_out, out, &alpha)) return;
   double acc[2] = {0.0, 0.0};
   calc_r_precond_vecc_walk<VEC>(r, w, dinv, alpha, n, 2u, 4u, 5u, ev, acc);
   reduce_finish_d(acc, out, s_w);
 }
 
-// (in: the record the iteration started from -- the guard, and beta's denominator; out: what the r half left)
 template <int VEC>
 __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_precond_vecc_until_kernel(double *__restrict__ x,
                                                                                 double *__restrict__ p,
@@ -7041,8 +6948,8 @@ __global__ __launch_bounds__(ABFT_BLOCK) void calc_px_precond_vecc_until_kernel(
                                                                                 double threshold,
                                                                                 const double *alpha_ptr, int n,
                                                                                 EventRing ev) {
-  if (!(in[0] > threshold)) return;
-  const double beta = out[2] / in[2];
+  if (!GuardQuad::live(in, threshold)) return;
+  const double beta = GuardQuad::beta(in, out);
   const double alpha = *alpha_ptr;
   calc_px_precond_vecc_walk<VEC>(x, p, r, dinv, alpha, beta, n, 1u, 3u, 2u, 5u, ev);
 }
