@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("ABFT_HIP_LIB") or os.path.join(_HERE, "libabft_hip.so
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "abft_hip.h")
 
 OK = 0
+ERR_RANGE = -4  # ABFT_ERR_RANGE
 MODES = ("none", "constraints", "sed", "sec7", "sec8", "secded")
 MODE_ID = {m: i for i, m in enumerate(MODES)}
 MODE_ID["sec"] = MODE_ID["sec7"]  # BASELINE.json config 5 spells sec7 "sec"
@@ -21,6 +22,8 @@ PART_ALL, PART_INTERIOR, PART_BOUNDARY = 0, 1, 2
 K_SPMV, K_DOT, K_CALC_XR, K_CALC_P = 0, 1, 2, 3
 EV_VEC_CORRECTED, EV_VEC_DOUBLE = 10, 11  # protected vectors: bit = word bit | operand << 8
 FMT_VECTOR = 2
+EV_STRUCT_CORRECTED, EV_STRUCT_DOUBLE = 12, 13  # protected row structure: bit = word bit | kind << 8, index = row or block
+STRUCT_ROW, STRUCT_BLOCK = 0, 1  # the kind of a structure word
 MAX_RHS = 8  # block right-hand sides per call (include/abft_hip.h)
 
 u32p = C.POINTER(C.c_uint32)
@@ -69,6 +72,12 @@ SIGNATURES = {
     "abft_hip_matrix_read_coo": (C.c_int, [vp, vp]),
     "abft_hip_inject": (C.c_int, [vp, C.c_uint32, i32p, C.c_int]),
     "abft_hip_inject_rowptr": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
+    "abft_hip_matrix_create_csr_protected": (C.c_int, [vp, C.c_int, u32p, u32p, f64p, C.c_int, C.c_int, vpp]),
+    "abft_hip_matrix_structure_info": (C.c_int, [vp, i32p, u32p, u32p]),
+    "abft_hip_matrix_read_structure": (C.c_int, [vp, vp, vp]),
+    "abft_hip_matrix_write_structure": (C.c_int, [vp, vp, vp]),
+    "abft_hip_inject_structure": (C.c_int, [vp, C.c_int, C.c_uint32, i32p, C.c_int]),
+    "abft_hip_matrix_scrub_structure": (C.c_int, [vp, vp, u32p, u32p]),
     "abft_hip_vector_create": (C.c_int, [vp, C.c_int, vpp]),
     "abft_hip_vector_view": (C.c_int, [vp, C.c_int, C.c_int, vpp]),
     "abft_hip_vector_destroy": (C.c_int, [vp]),
@@ -243,7 +252,7 @@ def check(rc):
 
 def is_fatal(kind):
     """same rule as abft_event_is_fatal"""
-    return kind in (1, 4, EV_VEC_DOUBLE) or 5 <= kind <= 9
+    return kind in (1, 4, EV_VEC_DOUBLE, EV_STRUCT_DOUBLE) or 5 <= kind <= 9
 
 
 def format_event(kind, index, bit, fmt):

@@ -72,11 +72,20 @@ Additional options of this build:
                               twice per iteration: same iterations, residuals and x; the
                               lines of a batch are printed after it.  Not with --rhs,
                               --precond, --check-every, --vector-ecc or --flip-vector
+      --structure-ecc   E     Protect the CSR row structure: none (default) or secded --
+                              row extents under a (64, 57) code, row-block descriptors
+                              under a (128, 120) code (CSR, one right-hand side)
+      --flip-structure I:K:J:B[,B...]
+                              After iteration I, flip bit(s) B of stored structure word
+                              J of kind K: row (a row extent, bits 0-63) or block (a
+                              row-block descriptor, bits 0-127); needs --structure-ecc
+                              secded (may be repeated)
 
 """
 
 
 FLIP_VECTOR_MSG = "Invalid --flip-vector (want ITER:VEC:INDEX:BIT[,BIT...], VEC one of x, r, p)"
+FLIP_STRUCTURE_MSG = "Invalid --flip-structure (want ITER:row|block:INDEX:BIT[,BIT...])"
 
 
 def fail(msg):
@@ -88,7 +97,7 @@ def parse(argv):
     o = dict(num_blocks=25, max_itrs=1000, conv=0.001, matrix_file=DEFAULT_MTX, synthetic=None, target="cpu",
              mode="none", flips=0, kind="ANY", seed=None, quiet=False, flip_at=None, fmt="csr", list=False,
              rhs=1, check_every=0, check_tol=1e-7, max_rollbacks=3, flip_vector=[], precond="none",
-             vector_ecc="none", block_fused=False, device_loop=0)
+             vector_ecc="none", block_fused=False, device_loop=0, structure_ecc="none", flip_structure=[])
 
     def num(s, conv):
         try:
@@ -188,6 +197,21 @@ def parse(argv):
             o["vector_ecc"] = arg("Invalid vector protection (want none or secded)")
             if o["vector_ecc"] not in ("none", "secded"):
                 fail("Invalid vector protection (want none or secded)")
+        elif a == "--structure-ecc":
+            o["structure_ecc"] = arg("Invalid structure protection (want none or secded)")
+            if o["structure_ecc"] not in ("none", "secded"):
+                fail("Invalid structure protection (want none or secded)")
+        elif a == "--flip-structure":
+            msg = FLIP_STRUCTURE_MSG
+            try:
+                itr, kind, idx, bits = arg(msg).split(":")
+                flip = (int(itr), kind, int(idx), [int(b) for b in bits.split(",")])
+            except ValueError:
+                fail(msg)
+            if flip[0] < 0 or flip[1] not in ("row", "block") or flip[2] < 0 or \
+                    not all(0 <= b < (64 if flip[1] == "row" else 128) for b in flip[3]):
+                fail(msg)
+            o["flip_structure"] = o["flip_structure"] + [flip]
         elif a == "--block-fused":
             o["block_fused"] = True
         elif a == "--device-loop":
@@ -218,6 +242,13 @@ def parse(argv):
                          ("--check-every", o["check_every"] > 0), ("--format coo", o["fmt"] != "csr")):
             if on:
                 fail("--vector-ecc secded cannot be combined with %s" % flag)
+    if o["structure_ecc"] == "none":
+        if o["flip_structure"]:
+            fail("--flip-structure needs --structure-ecc secded")
+    else:
+        for flag, on in (("--rhs", o["rhs"] > 1), ("--format coo", o["fmt"] != "csr")):
+            if on:
+                fail("--structure-ecc secded cannot be combined with %s" % flag)
     return o
 
 
@@ -266,6 +297,27 @@ def apply_vector_flips(ctx, flips, itr):
         for bit in bits:
             print("*** flipping bit %d of %s[%d] ***" % (bit, name, index))
         ctx.flip_vector(v, index, bits)
+
+
+def structure_flips(o, ctx, A):
+    """--flip-structure's flips as {iteration: [(kind, index, bits)]}, each index checked against the stored words"""
+    out = {}
+    if not o["flip_structure"]:
+        return out
+    ext, blk = ctx.read_structure(A)
+    for itr, kind, index, bits in o["flip_structure"]:
+        count = len(ext) if kind == "row" else len(blk)
+        if index >= count:
+            fail("Invalid --flip-structure: %s %d outside the matrix's %d" % (kind, index, count))
+        out.setdefault(itr, []).append((kind, index, bits))
+    return out
+
+
+def apply_structure_flips(ctx, A, flips, itr):
+    for kind, index, bits in flips.get(itr, ()):
+        for bit in bits:
+            print("*** flipping bit %d of row %s %d ***" % (bit, "extent" if kind == "row" else "block", index))
+        ctx.flip_structure(A, kind, index, bits)
 
 
 def report_check(checks, prefix, itr, gap, ok, back, bound):
@@ -339,13 +391,22 @@ def load_matrix(o, row0=0, row1=None):
 
 def run_single(o):
     from . import HIPContext, generators
+    from . import capi
     from .context import ResidualCheckFailed, cg_solve, cg_solve_device
     cols, rows, vals, n, block = load_matrix(o)
     nnz = len(vals)
     ctx = HIPContext(o["mode"], o["fmt"])
     ecc = o["vector_ecc"] == "secded"
-    # (protected vectors run on the streaming layout only)
-    A = ctx.create_matrix(cols, rows, vals, n, nnz, layout="stream" if ecc else None)
+    secc = o["structure_ecc"] == "secded"
+    # (protected vectors and a protected row structure run on the streaming layout only)
+    try:
+        A = ctx.create_matrix(cols, rows, vals, n, nnz, layout="stream" if ecc or secc else None,
+                              **({"structure_ecc": True} if secc else {}))
+    except capi.AbftError as e:
+        if not secc or e.code != capi.ERR_RANGE:
+            raise
+        ctx.close()
+        fail(str(e))
     del cols, rows, vals
     header(o, n, block, nnz)
     b, x, r, p, w = (ctx.create_vector(n) for _ in range(5))
@@ -356,9 +417,12 @@ def run_single(o):
             print("*** flipping bit %d at index %d ***" % (bit, index))
         ctx.inject_at(A, index, bits)
     vecs = vector_flips(o, n, {"x": x, "r": r, "p": p, "w": w, "b": b})
+    sflips = structure_flips(o, ctx, A)
     dinv = make_preconditioner(o, ctx, A)
     if ecc:
         print("vector protection: secded (64, 57)")
+    if secc:
+        print("structure protection: secded (row extents (64, 57), row blocks (128, 120))")
     bound = o["check_tol"] * float(np.linalg.norm(generators.reference_rhs(n)))
     checks = {}
 
@@ -366,6 +430,7 @@ def run_single(o):
         if not o["quiet"]:
             print("iteration %5u :  rr = %12.4f" % (itr, rr))
         apply_vector_flips(ctx, vecs, itr)
+        apply_structure_flips(ctx, A, sflips, itr)
 
     if o["device_loop"]:
         print("iteration loop: device scalars, stride %d" % o["device_loop"])
@@ -388,6 +453,8 @@ def run_single(o):
     print("\nran for %u iterations" % itr)
     if o["check_every"]:
         print_check_summary(checks)
+    if secc:  # every stored word once more, those no SpMV reads as well
+        print("structure scrub: %d corrected" % ctx.scrub_structure(A)[0])
     print("\ntime taken = %7.2f ms\n" % ms)
     if ecc:
         from .context import vecc_strip

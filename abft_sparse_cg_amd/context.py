@@ -41,6 +41,7 @@ class Matrix:
     def __init__(self, ctx, handle, fmt, mode, n_out, n_in, nnz):
         self.ctx, self.h, self.fmt, self.mode = ctx, handle, fmt, mode
         self.n_out, self.n_in, self.nnz = n_out, n_in, nnz
+        self.structure_ecc = False  # create_matrix(structure_ecc=True): the row structure is stored as codewords
 
 
 class Vector:
@@ -105,24 +106,30 @@ class HIPContext:
             pass
 
     # ---- matrix -----------------------------------------------------------
-    def create_matrix(self, columns, rows, values, N, nnz, n_in=None, index_base=0, layout=None):
+    def create_matrix(self, columns, rows, values, N, nnz, n_in=None, index_base=0, layout=None, structure_ecc=False):
         """reference CGContext.h:15-18.  n_in/index_base make a row-block shard.
         layout="stream": CSR, whole matrix, always in the streaming row-block layout -- the
-        one spmm runs on (abft_hip_matrix_create_csr_stream); None: the library's choice."""
+        one spmm runs on (abft_hip_matrix_create_csr_stream); None: the library's choice.
+        structure_ecc=True (with layout="stream" only): the row structure is stored as SECDED codewords
+        (abft_hip_matrix_create_csr_protected) -- the single-vector SpMV and everything
+        built on it run on such a matrix, the block entries refuse it."""
         columns = np.ascontiguousarray(columns, dtype=np.uint32)
         rows = np.ascontiguousarray(rows, dtype=np.uint32)
         values = np.ascontiguousarray(values, dtype=np.float64)
         assert len(columns) >= nnz and len(rows) >= nnz and len(values) >= nnz
         if layout not in (None, "stream"):
             raise ValueError("layout must be None or 'stream', not %r" % (layout,))
+        if structure_ecc and (layout != "stream" or self.fmt != FMT_CSR or (n_in is not None and n_in != N) or index_base):
+            raise ValueError("structure_ecc=True takes a whole CSR matrix with layout='stream'")
         h = C.c_void_p()
         if layout == "stream":
             if self.fmt != FMT_CSR or (n_in is not None and n_in != N) or index_base:
                 raise ValueError("layout='stream' takes a whole CSR matrix")
-            check(self.L.abft_hip_matrix_create_csr_stream(
-                self.h, self.mode_id, columns.ctypes.data_as(capi.u32p), rows.ctypes.data_as(capi.u32p),
-                values.ctypes.data_as(capi.f64p), N, nnz, C.byref(h)))
+            create = self.L.abft_hip_matrix_create_csr_protected if structure_ecc else self.L.abft_hip_matrix_create_csr_stream
+            check(create(self.h, self.mode_id, columns.ctypes.data_as(capi.u32p), rows.ctypes.data_as(capi.u32p),
+                         values.ctypes.data_as(capi.f64p), N, nnz, C.byref(h)))
             m = Matrix(self, h, self.fmt, self.mode, N, N, nnz)
+            m.structure_ecc = bool(structure_ecc)
             self._live.append(m)
             return m
         n_in = N if n_in is None else n_in
@@ -157,6 +164,49 @@ class HIPContext:
         rp = np.empty(mat.n_out + 1, dtype=np.uint32)
         check(self.L.abft_hip_matrix_read_csr(mat.h, None, rp.ctypes.data, None))
         return rp
+
+    # ---- the protected row structure (include/abft_hip.h) ----
+    def structure_protected(self, mat):
+        """was the matrix created with structure_ecc=True?"""
+        return self._structure_info(mat)[0]
+
+    def _structure_info(self, mat):
+        on, rows, blocks = C.c_int(0), C.c_uint32(0), C.c_uint32(0)
+        check(self.L.abft_hip_matrix_structure_info(mat.h, C.byref(on), C.byref(rows), C.byref(blocks)))
+        return bool(on.value), rows.value, blocks.value
+
+    def read_structure(self, mat):
+        """-> (row extent words: uint64[N], row-block descriptors: uint32[nblk, 4]), the stored codewords as they are"""
+        _, rows, blocks = self._structure_info(mat)
+        ext = np.zeros(rows, dtype=np.uint64)
+        blk = np.zeros((blocks, 4), dtype=np.uint32)
+        check(self.L.abft_hip_matrix_read_structure(mat.h, ext.ctypes.data, blk.ctypes.data))
+        return ext, blk
+
+    def write_structure(self, mat, rowext=None, blk=None):
+        """store the given words as they are (the shapes read_structure returns): a fault injector for whole sweeps"""
+        _, rows, blocks = self._structure_info(mat)
+        ext = None if rowext is None else np.ascontiguousarray(rowext, dtype=np.uint64)
+        b4 = None if blk is None else np.ascontiguousarray(blk, dtype=np.uint32)
+        if (ext is not None and ext.shape != (rows,)) or (b4 is not None and b4.shape != (blocks, 4)):
+            raise ValueError("write_structure wants %d row words and (%d, 4) descriptor words" % (rows, blocks))
+        check(self.L.abft_hip_matrix_write_structure(mat.h, None if ext is None else ext.ctypes.data,
+                                                     None if b4 is None else b4.ctypes.data))
+
+    def flip_structure(self, mat, kind, index, bits):
+        """XOR `bits` into one stored word: kind capi.STRUCT_ROW / "row" (bits 0..63 of row `index`'s word) or
+        capi.STRUCT_BLOCK / "block" (bits 0..127 of descriptor `index`)"""
+        kind = {"row": capi.STRUCT_ROW, "block": capi.STRUCT_BLOCK}.get(kind, kind)
+        b = np.ascontiguousarray(bits, dtype=np.int32)
+        check(self.L.abft_hip_inject_structure(mat.h, int(kind), int(index), b.ctypes.data_as(capi.i32p), len(b)))
+
+    def scrub_structure(self, mat):
+        """check every row word and every descriptor and write repaired ones back; -> (corrected, uncorrectable).
+        Events as after any call that reads a result (FatalEvent on an uncorrectable word)."""
+        c, u = C.c_uint32(0), C.c_uint32(0)
+        check(self.L.abft_hip_matrix_scrub_structure(self.h, mat.h, C.byref(c), C.byref(u)))
+        self._drain()
+        return c.value, u.value
 
     # ---- vectors ----------------------------------------------------------
     def create_vector(self, N):
@@ -821,6 +871,14 @@ def _check_protected_precond(precond, vector_ecc):
     return protected
 
 
+def _refuse_structure_ecc(ctx, A, what):
+    """the block solvers read plain row structure (the SpMM kernels): refused before anything runs, and without a call
+    on the context (the matrix carries the mark create_matrix gave it; the library refuses such a matrix as well)"""
+    if getattr(A, "structure_ecc", False):
+        raise ValueError("%s: the matrix was created with structure_ecc=True; block right-hand sides run on "
+                         "matrices with a plain row structure" % what)
+
+
 def _check_args(check_every, check_tol, max_rollbacks):
     if check_every < 0 or int(check_every) != check_every:
         raise ValueError("check_every must be a whole number >= 0, not %r" % (check_every,))
@@ -1299,6 +1357,7 @@ def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1
     return value are as above.  Refused (ValueError, before anything runs) with any precond and for a matrix
     ctx.vecc_supported refuses.  With vector_ecc=False the calls are exactly those made without the argument.
     No check_every, one GPU."""
+    _refuse_structure_ecc(ctx, A, "cg_solve_block_device")
     stride = _whole_stride(stride)
     if vector_ecc:
         if precond is not None:
@@ -1472,6 +1531,7 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
     column's words are stored back repaired.  Control flow, masks, on_iteration and the return value are as
     without it.  Refused (ValueError, before anything runs) with check_every > 0, with any precond, and for a matrix
     ctx.vecc_supported refuses.  With vector_ecc=False the calls are exactly those made without the argument."""
+    _refuse_structure_ecc(ctx, A, "cg_solve_block")
     _check_args(check_every, check_tol, max_rollbacks)
     if vector_ecc:
         if check_every:

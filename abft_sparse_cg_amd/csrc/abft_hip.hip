@@ -23,6 +23,7 @@
 #include "guard_protocol.h"
 #include "layout_plan.h"
 #include "loop_state.h"
+#include "struct_ecc.h"
 
 // ------------------------------------------------------------------ errors --
 
@@ -171,6 +172,10 @@ struct abft_hip_matrix {
   std::vector<uint32_t> fast_host;
   size_t codes_len = 0;  // codes allocated behind packed.code16 (packed_fast_word's window condition)
   bool fast_on = false;  // ABFT_HIP_PACKED_FAST as create read it: off, every word is and stays 0
+  // a structure-protected matrix (abft_hip_matrix_create_csr_protected; struct_ecc.h): the row structure as codewords.
+  // Then csr.rowptr and csr.blk are NULL, and so are compact, packed and packed_fast: no plain copy of the structure exists.
+  bool protects = false;
+  CsrStruct prot{};
   std::vector<void *> allocs;
   bool streams() const { return layout == Layout::Stream; }
 };
@@ -891,9 +896,19 @@ static int packed_after_inject(abft_hip_matrix *m, uint32_t pos) {
 
 // validate, plan (layout_plan.h), upload, attach, encode
 static int create_csr(abft_hip_matrix *m, const LayoutKnobs &knobs, const uint32_t *columns, const uint32_t *rows,
-                      const double *values, int n_out, int n_in, int nnz, uint32_t index_base, bool force_stream) {
+                      const double *values, int n_out, int n_in, int nnz, uint32_t index_base, bool force_stream,
+                      bool protect = false) {
   abft_hip_ctx *ctx = m->ctx;
   const int mode = m->mode;
+  if (protect) {  // the fields of the stored words: checked before anything is uploaded
+    const int over = struct_limit((uint64_t)n_out, (uint64_t)nnz);
+    if (over == 1)
+      return set_err(ABFT_ERR_RANGE, "%d non-zeros do not fit a protected row structure: a row extent word holds row "
+                     "pointers below 2^28 (nnz < 2^28 = %u)", nnz, ABFT_STRUCT_MAX_NNZ);
+    if (over)
+      return set_err(ABFT_ERR_RANGE, "%d rows do not fit a protected row structure: a row-block descriptor keeps its "
+                     "check byte above a 24-bit first row (N <= 2^24 = %u)", n_out, ABFT_STRUCT_MAX_ROWS);
+  }
   // a bad index must fail here, loudly, not fault a kernel later
   for (int i = 0; i < nnz; i++) {
     if (rows[i] >= (uint32_t)n_out)
@@ -909,8 +924,10 @@ static int create_csr(abft_hip_matrix *m, const LayoutKnobs &knobs, const uint32
   auto slice_waves = [&](uint32_t lg) { return (uint64_t)spmv_slice_blocks_per_cu(mode, lg) * 4u * (uint64_t)ctx->num_cus; };
   auto sweep_cap = [&](int rpt) { return (uint64_t)spmv_sweep_blocks_per_cu(mode, rpt) * (uint64_t)ctx->num_cus; };
   CsrPlan plan;
-  plan_csr(g_geometry, knobs, mode == ABFT_MODE_NONE, mode == ABFT_MODE_CONSTRAINTS, force_stream, columns, rows, values, n_out,
-           n_in, nnz, slice_waves, sweep_cap, m->pool, plan);
+  LayoutKnobs planned = knobs;
+  if (protect) planned.compact = planned.packed = false;  // cbase, cols16, code16, pdesc, pal and the fast records are unprotected copies of the structure
+  plan_csr(g_geometry, planned, mode == ABFT_MODE_NONE, mode == ABFT_MODE_CONSTRAINTS, force_stream || protect, columns, rows,
+           values, n_out, n_in, nnz, slice_waves, sweep_cap, m->pool, plan);
 
   CsrDev &A = m->csr;
   A.n_out = (uint32_t)n_out; A.n_in = (uint32_t)n_in; A.nnz = (uint32_t)nnz; A.index_base = index_base;
@@ -930,9 +947,25 @@ static int create_csr(abft_hip_matrix *m, const LayoutKnobs &knobs, const uint32
   }
   uint32_t *d_rowptr = nullptr;
   Blk *d_blk = nullptr;
-  if ((rc = upload_all(m, &d_rowptr, plan.rowptr)) || (rc = upload_all(m, &d_blk, plan.blk))) return rc;
-  A.rowptr = d_rowptr;
-  A.blk = reinterpret_cast<const uint4 *>(d_blk);
+  if (protect) {
+    // the packed row words and the plain descriptors go up; struct_encode_kernel gives both their codes in place
+    std::vector<uint64_t> ext((size_t)n_out);
+    for (int r = 0; r < n_out; r++) ext[(size_t)r] = rowext_pack(plan.rowptr[(size_t)r], plan.rowptr[(size_t)r + 1]);
+    uint64_t *d_ext = nullptr;
+    if ((rc = upload_all(m, &d_ext, ext)) || (rc = upload_all(m, &d_blk, plan.blk))) return rc;
+    m->prot.rowext = d_ext;
+    m->prot.blk = reinterpret_cast<uint4 *>(d_blk);
+    m->protects = true;
+    hipError_t e = launch_struct_encode(m->prot, A.n_out, A.nblk, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // `ext` goes out of scope
+    if (e != hipSuccess) return set_err(ABFT_ERR_HIP, "structure upload/encode failed: %s", hipGetErrorString(e));
+    A.rowptr = nullptr;
+    A.blk = nullptr;
+  } else {
+    if ((rc = upload_all(m, &d_rowptr, plan.rowptr)) || (rc = upload_all(m, &d_blk, plan.blk))) return rc;
+    A.rowptr = d_rowptr;
+    A.blk = reinterpret_cast<const uint4 *>(d_blk);
+  }
   if (plan.layout == Layout::Stream) {
     m->blk_host = plan.blk;
     if ((rc = attach_compact(m, plan.compact)) || (rc = attach_packed(m, plan.packed, *knobs.packed_fast))) return rc;
@@ -990,7 +1023,7 @@ static int create_coo(abft_hip_matrix *m, const LayoutKnobs &knobs, const uint32
 
 static int create_any(abft_hip_ctx *ctx, int format, int mode, const uint32_t *columns,
                       const uint32_t *rows, const double *values, int n_out, int n_in, int nnz,
-                      uint32_t index_base, abft_hip_matrix **out, bool force_stream = false) {
+                      uint32_t index_base, abft_hip_matrix **out, bool force_stream = false, bool protect = false) {
   if (int rc = enter(ctx, 0)) return rc;
   if (!out) return set_err(ABFT_ERR_INVALID, "null out");
   *out = nullptr;
@@ -1005,7 +1038,7 @@ static int create_any(abft_hip_ctx *ctx, int format, int mode, const uint32_t *c
   if (!m) return set_err(ABFT_ERR_NOMEM, "matrix allocation failed");
   m->ctx = ctx; m->fmt = format; m->mode = mode;
   if (int rc = coo ? create_coo(m, knobs, columns, rows, values, n_out, n_in, nnz, index_base)
-                   : create_csr(m, knobs, columns, rows, values, n_out, n_in, nnz, index_base, force_stream))
+                   : create_csr(m, knobs, columns, rows, values, n_out, n_in, nnz, index_base, force_stream, protect))
     return rc;
   const uint32_t nblk = coo ? m->coo.nblk : m->csr.nblk;
   if (m->layout == Layout::Panels) {
@@ -1047,6 +1080,12 @@ extern "C" int abft_hip_matrix_create_csr_stream(abft_hip_ctx *ctx, int mode, co
                                                  const uint32_t *rows, const double *values, int N, int nnz,
                                                  abft_hip_matrix **mat) {
   return create_any(ctx, ABFT_FMT_CSR, mode, columns, rows, values, N, N, nnz, 0, mat, true);
+}
+
+extern "C" int abft_hip_matrix_create_csr_protected(abft_hip_ctx *ctx, int mode, const uint32_t *columns,
+                                                    const uint32_t *rows, const double *values, int N, int nnz,
+                                                    abft_hip_matrix **mat) {
+  return create_any(ctx, ABFT_FMT_CSR, mode, columns, rows, values, N, N, nnz, 0, mat, true, true);
 }
 
 extern "C" int abft_hip_matrix_create_coo(abft_hip_ctx *ctx, int mode, const uint32_t *columns,
@@ -1220,7 +1259,17 @@ extern "C" int abft_hip_matrix_read_csr(abft_hip_matrix *mat, uint32_t *cols, ui
   if (int rc = enter(mat->ctx, 0)) return rc;
   hipStream_t s = mat->ctx->stream;
   const CsrDev &A = mat->csr;
-  if (rowptr) HIPCHK(hipMemcpyAsync(rowptr, A.rowptr, ((size_t)A.n_out + 1) * 4, hipMemcpyDeviceToHost, s));
+  if (rowptr && mat->protects) {
+    // from the row words, the code bits stripped and nothing checked: row r's start, and the last row's end
+    std::vector<uint64_t> ext(A.n_out);
+    if (A.n_out) HIPCHK(hipMemcpyAsync(ext.data(), mat->prot.rowext, (size_t)A.n_out * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    rowptr[0] = 0;
+    for (uint32_t r = 0; r < A.n_out; r++) rowptr[r] = rowext_start(ext[r]);
+    if (A.n_out) rowptr[A.n_out] = rowext_end(ext[A.n_out - 1]);
+  } else if (rowptr) {
+    HIPCHK(hipMemcpyAsync(rowptr, A.rowptr, ((size_t)A.n_out + 1) * 4, hipMemcpyDeviceToHost, s));
+  }
   if (mat->streams()) {
     if (cols && A.nnz) HIPCHK(hipMemcpyAsync(cols, A.cols, (size_t)A.nnz * 4, hipMemcpyDeviceToHost, s));
     if (values && A.nnz) HIPCHK(hipMemcpyAsync(values, A.vals, (size_t)A.nnz * 8, hipMemcpyDeviceToHost, s));
@@ -1312,6 +1361,9 @@ extern "C" int abft_hip_inject(abft_hip_matrix *mat, uint32_t index, const int *
 // additive entry XORs `mask` into rowptr[row] so that those two checks can be exercised.
 extern "C" int abft_hip_inject_rowptr(abft_hip_matrix *mat, uint32_t row, uint32_t mask) {
   if (!mat || mat->fmt != ABFT_FMT_CSR) return set_err(ABFT_ERR_INVALID, "not a CSR matrix");
+  if (mat->protects)
+    return set_err(ABFT_ERR_INVALID, "inject_rowptr: the matrix stores no plain row pointers (its row structure is "
+                   "protected); flip a stored word with abft_hip_inject_structure");
   if (int rc = enter(mat->ctx, 0)) return rc;
   if (row > mat->csr.n_out) return set_err(ABFT_ERR_INVALID, "row pointer %u outside [0,%u]", row, mat->csr.n_out);
   hipStream_t s = mat->ctx->stream;
@@ -1322,6 +1374,99 @@ extern "C" int abft_hip_inject_rowptr(abft_hip_matrix *mat, uint32_t row, uint32
   v ^= mask;
   HIPCHK(hipMemcpyAsync(p, &v, sizeof(v), hipMemcpyHostToDevice, s));
   HIPCHK(hipStreamSynchronize(s));
+  return ABFT_OK;
+}
+
+// ---- the protected row structure (struct_ecc.h) ----
+
+// the entries that read plain row pointers or descriptors on the device refuse a structure-protected matrix, before
+// anything is enqueued
+static int refuse_protected(const char *what, const abft_hip_matrix *mat) {
+  if (mat && mat->protects)
+    return set_err(ABFT_ERR_INVALID, "%s: the matrix's row structure is protected (abft_hip_matrix_create_csr_protected); "
+                   "only the single-vector SpMV reads the protected form", what);
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_matrix_structure_info(abft_hip_matrix *mat, int *is_protected, uint32_t *row_words, uint32_t *blocks) {
+  if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
+  if (is_protected) *is_protected = mat->protects ? 1 : 0;
+  if (row_words) *row_words = mat->protects ? mat->csr.n_out : 0u;
+  if (blocks) *blocks = mat->protects ? mat->csr.nblk : 0u;
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_matrix_read_structure(abft_hip_matrix *mat, uint64_t *rowext, uint32_t *blk4) {
+  if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
+  if (!mat->protects) return set_err(ABFT_ERR_INVALID, "read_structure: the matrix's row structure is not protected");
+  if (int rc = enter(mat->ctx, 0)) return rc;
+  hipStream_t s = mat->ctx->stream;
+  const CsrDev &A = mat->csr;
+  if (rowext && A.n_out) HIPCHK(hipMemcpyAsync(rowext, mat->prot.rowext, (size_t)A.n_out * 8, hipMemcpyDeviceToHost, s));
+  if (blk4 && A.nblk) HIPCHK(hipMemcpyAsync(blk4, mat->prot.blk, (size_t)A.nblk * 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_matrix_write_structure(abft_hip_matrix *mat, const uint64_t *rowext, const uint32_t *blk4) {
+  if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
+  if (!mat->protects) return set_err(ABFT_ERR_INVALID, "write_structure: the matrix's row structure is not protected");
+  if (int rc = enter(mat->ctx, 0)) return rc;
+  hipStream_t s = mat->ctx->stream;
+  const CsrDev &A = mat->csr;
+  if (rowext && A.n_out) HIPCHK(hipMemcpyAsync(mat->prot.rowext, rowext, (size_t)A.n_out * 8, hipMemcpyHostToDevice, s));
+  if (blk4 && A.nblk) HIPCHK(hipMemcpyAsync(mat->prot.blk, blk4, (size_t)A.nblk * 16, hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));  // the caller's arrays
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_inject_structure(abft_hip_matrix *mat, int kind, uint32_t index, const int *bits, int nbits) {
+  if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
+  if (!mat->protects) return set_err(ABFT_ERR_INVALID, "inject_structure: the matrix's row structure is not protected");
+  if (int rc = enter(mat->ctx, 0)) return rc;
+  if (kind != ABFT_STRUCT_ROW_EXTENT && kind != ABFT_STRUCT_ROW_BLOCK)
+    return set_err(ABFT_ERR_INVALID, "inject_structure: unknown kind %d", kind);
+  const bool row = kind == ABFT_STRUCT_ROW_EXTENT;
+  const uint32_t count = row ? mat->csr.n_out : mat->csr.nblk;
+  const int width = row ? 64 : 128;
+  if (index >= count)
+    return set_err(ABFT_ERR_INVALID, "inject_structure: %s %u outside [0,%u)", row ? "row extent" : "row block", index, count);
+  if (nbits < 0 || nbits > 32 || (nbits && !bits)) return set_err(ABFT_ERR_INVALID, "bad bit list");
+  uint32_t mask[4] = {0u, 0u, 0u, 0u};
+  for (int k = 0; k < nbits; k++) {
+    if (bits[k] < 0 || bits[k] >= width) return set_err(ABFT_ERR_INVALID, "bit %d outside [0,%d)", bits[k], width);
+    mask[bits[k] >> 5] ^= 1u << (bits[k] & 31);
+  }
+  if (!nbits) return ABFT_OK;
+  // (the stored word through the host: nothing of the hot path; a row word's 32-bit halves lie low first)
+  hipStream_t s = mat->ctx->stream;
+  void *at = row ? (void *)(mat->prot.rowext + index) : (void *)(mat->prot.blk + index);
+  const size_t bytes = row ? 8 : 16;
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  HIPCHK(hipMemcpyAsync(w, at, bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  for (int k = 0; k < 4; k++) w[k] ^= mask[k];
+  HIPCHK(hipMemcpyAsync(at, w, bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_matrix_scrub_structure(abft_hip_ctx *ctx, abft_hip_matrix *mat, uint32_t *corrected,
+                                               uint32_t *uncorrectable) {
+  if (!mat) return set_err(ABFT_ERR_INVALID, "null matrix");
+  if (!mat->protects) return set_err(ABFT_ERR_INVALID, "scrub_structure: the matrix's row structure is not protected");
+  if (ctx != mat->ctx) return set_err(ABFT_ERR_INVALID, "scrub_structure: the matrix belongs to another context");
+  if (int rc = enter(ctx, 0)) return rc;
+  if (ctx->capturing) return set_err(ABFT_ERR_INVALID, "scrub_structure: called under graph capture (it waits for its counts)");
+  hipStream_t s = ctx->stream;
+  uint32_t *counts = reinterpret_cast<uint32_t *>(ctx->bits_dev);  // inject's scratch words: free between calls
+  uint32_t got[2] = {0u, 0u};
+  HIPCHK(hipMemsetAsync(counts, 0, sizeof(got), s));
+  HIPCHK(launch_struct_scrub(mat->prot, mat->csr.n_out, mat->csr.nblk, counts, ctx->ring, s));
+  HIPCHK(hipMemcpyAsync(got, counts, sizeof(got), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (corrected) *corrected = got[0];
+  if (uncorrectable) *uncorrectable = got[1];
   return ABFT_OK;
 }
 
@@ -2369,7 +2514,7 @@ static bool spmv_can_absorb(const abft_hip_ctx *ctx, const abft_hip_matrix *mat,
                             bool vecc) {
   if (!mat || !vec || !result) return false;
   if (!pending_path_on(*ctx, (unsigned)mat->mode)) return false;  // (not a mode it pays on: a pending update, left by a matrix of another mode, is applied first)
-  if (mat->fmt != ABFT_FMT_CSR || !mat->streams()) return false;
+  if (mat->fmt != ABFT_FMT_CSR || !mat->streams() || mat->protects) return false;  // (protected structure: no NUPD instantiation)
   if (part != ABFT_PART_ALL || c1 >= 0 || dev_pair || held || vecc) return false;
   const uint32_t n = mat->csr.n_out;
   return mat->fuse_partials && n != 0 && mat->csr.n_in == n && mat->csr.nblk != 0 &&
@@ -2470,6 +2615,11 @@ static int spmv_common(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_v
       else
         HIPCHK(launch_spmv_coo_panels(mat->mode, mat->coo, mat->panels, vec->d, result->d, ctx->ring,
                                       do_fuse ? &fuse : nullptr, mat->panel_grid, mat->panel_chunk, ctx->stream));
+    } else if (mat->fmt == ABFT_FMT_CSR && mat->protects) {
+      // the row structure as codewords: the sibling kernel, the same spans and the same fused product; never with an
+      // x update (spmv_can_absorb)
+      HIPCHK(launch_spmv_csr_struct(mat->mode, mat->csr, mat->prot, span, vec->d, result->d, ctx->ring,
+                                    do_fuse ? &fuse : nullptr, ctx->stream, vecc));
     } else if (mat->fmt == ABFT_FMT_CSR) {
       // the update pending on the old p: this launch applies it (depth 1), queues it and applies nothing, or applies
       // the whole queue and it (loop_state.h, LazyUpdates)
@@ -2597,6 +2747,7 @@ static int results_from_block_slot(abft_hip_ctx *ctx, uint32_t seq, int k, doubl
 
 extern "C" int abft_hip_spmm(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *X, abft_hip_vector *Y,
                              int k) {
+  if (int rc = refuse_protected("spmm", mat)) return rc;
   if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!mat || !X || !Y) return set_err(ABFT_ERR_INVALID, "spmm: null argument");
   if (mat->fmt != ABFT_FMT_CSR)
@@ -3016,7 +3167,7 @@ extern "C" int abft_hip_matrix_diag_inverse(abft_hip_ctx *ctx, abft_hip_matrix *
   if (!N) return ABFT_OK;
   hipStream_t s = ctx->stream;
   const uint32_t colmask = mat->mode >= ABFT_MODE_SED ? ABFT_COLMASK_HOST : 0xFFFFFFFFu;
-  if (!mat->streams()) {
+  if (!mat->streams() || mat->protects) {  // (a protected structure: the read-back forms rowptr from the row words, unchecked)
     std::vector<double> d(N, 0.0);
     if (int rc = diag_from_readback(mat, colmask, d)) return rc;
     uint32_t nbad = 0;
@@ -3292,6 +3443,7 @@ static int dotparts_reserve(abft_hip_ctx *ctx, const abft_hip_matrix *mat, int k
 
 extern "C" int abft_hip_spmm_dot(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *P,
                                  abft_hip_vector *W, int k, double *out) {
+  if (int rc = refuse_protected("spmm_dot", mat)) return rc;
   if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!mat || !P || !W || !out) return set_err(ABFT_ERR_INVALID, "spmm_dot: null argument");
   if (int rc = check_spmm_dot("spmm_dot", mat, P, W, k)) return rc;
@@ -3404,6 +3556,7 @@ extern "C" int abft_hip_calc_px_precond_block(abft_hip_ctx *ctx, abft_hip_vector
 
 extern "C" int abft_hip_spmm_dot_vecc(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *P,
                                       abft_hip_vector *W, int k, double *out) {
+  if (int rc = refuse_protected("spmm_dot_vecc", mat)) return rc;
   if (int rc = enter(ctx, OTHER_VECTORS)) return rc;
   if (!mat || !P || !W || !out) return set_err(ABFT_ERR_INVALID, "spmm_dot_vecc: null argument");
   if (int rc = check_spmm_dot("spmm_dot_vecc", mat, P, W, k)) return rc;
@@ -3478,6 +3631,7 @@ extern "C" int abft_hip_matrix_panels(abft_hip_matrix *mat, int *npanels, int *w
 extern "C" int abft_hip_spmv_dot_range_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
                                            abft_hip_vector *result, int vec_offset, double *dev_result, int c0, int c1) {
   if (c1 < 0) return set_err(ABFT_ERR_INVALID, "spmv range: bad panel range");
+  if (int rc = refuse_protected("spmv range", mat)) return rc;
   return spmv_common(ctx, mat, vec, result, vec_offset, dev_result, ABFT_PART_ALL, c0, c1);
 }
 
@@ -3806,6 +3960,7 @@ static int block_loop_alloc(abft_hip_ctx *ctx, const abft_hip_matrix *mat, int k
 
 extern "C" int abft_hip_block_loop_reserve(abft_hip_ctx *ctx, abft_hip_matrix *mat, int k) {
   const char *what = "block_loop_reserve";
+  if (int rc = refuse_protected(what, mat)) return rc;
   if (int rc = enter(ctx, 0)) return rc;
   if (!mat) return set_err(ABFT_ERR_INVALID, "%s: null matrix", what);
   if (ctx->capturing) return set_err(ABFT_ERR_INVALID, "%s: called under graph capture (it allocates)", what);
@@ -3822,6 +3977,7 @@ static int block_iteration_until(abft_hip_ctx *ctx, const char *what, bool vecc,
                                  abft_hip_vector *X, abft_hip_vector *R, abft_hip_vector *P, abft_hip_vector *W,
                                  const abft_hip_vector *dinv, int k, const double *dev_in, double *dev_pw,
                                  double *dev_out, double threshold) {
+  if (int rc = refuse_protected(what, mat)) return rc;
   if (int rc = enter(ctx, OTHER_VECTORS)) return rc;  // a pending x update applied, the fused product and the learned iteration forgotten
   if (!mat || !X || !R || !P || !W) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
   if (!dev_in || !dev_pw || !dev_out) return set_err(ABFT_ERR_INVALID, "%s: null device scalar", what);
@@ -3994,7 +4150,7 @@ extern "C" int abft_hip_graph_destroy(abft_hip_graph *g) {
 // ------------------------------------------------------------------- events --
 
 extern "C" int abft_event_is_fatal(uint32_t kind) {
-  return kind == ABFT_EV_SED_DETECTED || kind == ABFT_EV_DOUBLE_BIT || kind == ABFT_EV_VEC_DOUBLE ||
+  return kind == ABFT_EV_SED_DETECTED || kind == ABFT_EV_DOUBLE_BIT || kind == ABFT_EV_VEC_DOUBLE || kind == ABFT_EV_STRUCT_DOUBLE ||
          (kind >= ABFT_EV_ROW_SIZE && kind <= ABFT_EV_MOVED_OVERFLOW);
 }
 
@@ -4027,6 +4183,12 @@ extern "C" int abft_format_event(const abft_event *ev, char *buf, size_t cap) {
     case ABFT_EV_VEC_DOUBLE:
       return snprintf(buf, cap, "[ECC] double-bit error detected in vector operand %u at index %d\n",
                       (ev->bit >> 8) & 0xffu, i);
+    case ABFT_EV_STRUCT_CORRECTED:
+      return snprintf(buf, cap, "[ECC] corrected bit %u of %s %d\n", ev->bit & 0xffu,
+                      ((ev->bit >> 8) & 0xffu) == ABFT_STRUCT_ROW_BLOCK ? "row block" : "row extent", i);
+    case ABFT_EV_STRUCT_DOUBLE:
+      return snprintf(buf, cap, "[ECC] double-bit error detected in %s %d\n",
+                      ((ev->bit >> 8) & 0xffu) == ABFT_STRUCT_ROW_BLOCK ? "row block" : "row extent", i);
     default: return snprintf(buf, cap, "unknown event %u\n", ev->kind);
   }
 }
@@ -4067,7 +4229,7 @@ extern "C" int abft_hip_drain_events(abft_hip_ctx *ctx, abft_event *buf, int cap
   // constraint checks: by element index.  The CSR constraint checks are made row by row --
   // a row's two row-pointer checks, then its elements in order (CSR/CPUContext.cpp:173-200) --
   // and their events arrive with that row in `bit` (cleared again below).
-  auto csr_check = [](const abft_event &e) { return e.fmt == ABFT_FMT_CSR && e.kind >= ABFT_EV_ROW_SIZE; };
+  auto csr_check = [](const abft_event &e) { return e.fmt == ABFT_FMT_CSR && e.kind >= ABFT_EV_ROW_SIZE && e.kind <= ABFT_EV_COL_ORDER; };
   std::sort(ev.begin(), ev.end(), [&](const abft_event &a, const abft_event &b) {
     if (csr_check(a) && csr_check(b)) {
       if (a.bit != b.bit) return a.bit < b.bit;

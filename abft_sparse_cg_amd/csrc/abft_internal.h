@@ -78,6 +78,14 @@ struct CsrPackedFast {
   const uint4 *rec;  // nblk records, or NULL: nothing packed
 };
 
+// A structure-protected matrix (struct_ecc.h; abft_hip_matrix_create_csr_protected): the row structure as codewords.
+// CsrDev::rowptr and CsrDev::blk are NULL on such a matrix -- no plain copy exists --, and only the kernels that take
+// this struct run on it.  Not const: a cold path stores a repaired word back.
+struct CsrStruct {
+  uint64_t *rowext;  // n_out row extent words
+  uint4 *blk;        // nblk stored descriptors
+};
+
 // Panel ("column-blocked") layout for matrices whose columns are scattered over
 // a vector much larger than an XCD's 4 MB L2 (random / unstructured).  Rows are
 // cut into groups of ABFT_PANEL_ROWS, columns into panels of `width` entries
@@ -408,6 +416,13 @@ uint32_t fold_grid(uint32_t nblk, uint32_t *chunk);
 hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, const CsrPacked &cp, const TileSpan &span,
                            const double *x, double *y, EventRing ev, const FuseOut *fuse, hipStream_t s,
                            bool vecc = false, const XUpd *xu = nullptr, CsrPackedFast pf = CsrPackedFast{nullptr});
+// the same on a structure-protected matrix (never with compact or packed blocks, never with an x update)
+hipError_t launch_spmv_csr_struct(int mode, const CsrDev &A, const CsrStruct &S, const TileSpan &span, const double *x,
+                                  double *y, EventRing ev, const FuseOut *fuse, hipStream_t s, bool vecc);
+// S as uploaded (packed row words, plain descriptors) -> the stored codewords, in place
+hipError_t launch_struct_encode(const CsrStruct &S, uint32_t n, uint32_t nblk, hipStream_t s);
+// counts[0] += repaired words, counts[1] += uncorrectable ones
+hipError_t launch_struct_scrub(const CsrStruct &S, uint32_t n, uint32_t nblk, uint32_t *counts, EventRing ev, hipStream_t s);
 hipError_t launch_spmv_coo(int mode, const CooDev &A, const double *x, double *y, EventRing ev,
                            const FuseOut *fuse, hipStream_t s);
 // behind every COO SpMV: see MovedList.  With a fused product the fix-up runs inside the fold

@@ -17,6 +17,7 @@
 #include "abft_internal.h"
 #include "ecc_device.h"
 #include "guard_protocol.h"
+#include "struct_ecc.h"
 #include "vecc_walk.h"
 
 // native vector types (what __builtin_nontemporal_load accepts)
@@ -1260,6 +1261,243 @@ hipError_t launch_spmv_csr(int mode, const CsrDev &A, const CsrCompact &cc, cons
     case MODE_SECDED: return launch_spmv_csr_mode<MODE_SECDED>(A, cc, cp, span, x, y, ev, fuse, s, vecc, xu, pf);
     default: return hipErrorInvalidValue;
   }
+}
+
+// ------------------------------------------------- protected row structure --
+// The streaming kernel on a structure-protected matrix (struct_ecc.h): no plain row pointers and
+// no plain descriptors exist.  A sibling of spmv_csr_kernel, not a further flag of it, so that none of its
+// instantiations moves; csr_stage, csr_row_sum, fused_dot_finish and the vector-ECC pieces are shared.  Such a matrix
+// has neither compact nor packed blocks and is never a partner of the x-update fusions.
+//
+// Cold paths, out of line.  Every stored word has ONE owner per launch -- a row word the lane that sums the row
+// (thread 0 in the long-row branch, where all threads read it), a descriptor thread 0 of its workgroup --, and only the
+// owner stores the repaired word back (a plain vector store) and queues the event.
+__device__ __noinline__ VeccWord rowext_cold(uint64_t word, uint64_t *at, uint32_t row, bool owner, EventRing ev) {
+  VeccWord o;
+  uint32_t bit;
+  vecc_repair(word, o, bit);
+  if (owner && o.rc) {
+    if (o.rc > 0) *at = o.w;
+    push_event(ev, o.rc > 0 ? ABFT_EV_STRUCT_CORRECTED : ABFT_EV_STRUCT_DOUBLE, row, bit | (ABFT_STRUCT_ROW << 8), ABFT_FMT_CSR);
+  }
+  return o;
+}
+
+__device__ __noinline__ StructBlk blk_cold(uint4 d, uint4 *at, uint32_t t, bool owner, EventRing ev) {
+  const uint32_t w[4] = {d.x, d.y, d.z, d.w};
+  StructBlk o;
+  uint32_t bit;
+  blk_repair(w, o, bit);
+  if (owner && o.rc) {
+    if (o.rc > 0) *at = make_uint4(o.w[0], o.w[1], o.w[2], o.w[3]);
+    push_event(ev, o.rc > 0 ? ABFT_EV_STRUCT_CORRECTED : ABFT_EV_STRUCT_DOUBLE, t, (o.rc > 0 ? bit : 0u) | (ABFT_STRUCT_BLOCK << 8),
+               ABFT_FMT_CSR);
+  }
+  return o;
+}
+
+template <int MODE, int EPT, bool FUSE, bool VECC>
+__global__ __launch_bounds__(ABFT_BLOCK) void spmv_csr_struct_kernel(CsrDev A, CsrStruct S, const double *__restrict__ x,
+                                                                     double *__restrict__ y, EventRing ev, FuseOut fuse,
+                                                                     TileSpan span) {
+  constexpr uint32_t TILE = ABFT_BLOCK * EPT;
+  __shared__ __attribute__((aligned(16))) double s_prod[TILE];
+  __shared__ __attribute__((aligned(16))) uint32_t s_col[MODE == MODE_CONSTRAINTS ? TILE : 2];
+  const uint32_t b = xcd_tile(blockIdx.x, span.count);
+  const uint32_t t = span.first + b + (b >= span.cut ? span.skip : 0u);
+  uint4 desc = S.blk[t];  // uniform, 16 bytes, as in spmv_csr_kernel
+  bool dead = false;      // two flips in the descriptor: nothing derived from it is used (uniform)
+  {
+    const uint32_t w[4] = {desc.x, desc.y, desc.z, desc.w};
+    if (__builtin_expect(blk_suspect(w) != 0u, 0)) {
+      const StructBlk o = blk_cold(desc, S.blk + t, t, threadIdx.x == 0, ev);
+      dead = o.rc < 0;
+      desc = make_uint4(o.w[0], o.w[1], o.w[2], o.w[3]);
+    }
+  }
+  const bool uniform = ABFT_CFG_UNIFORM_ROWS && MODE != MODE_CONSTRAINTS && (desc.y >> 31) != 0u;
+  // (a descriptor that passed its check holds what create stored; the clamps cost two scalar instructions and keep a
+  // mis-decoded word of three or more flips inside the arrays)
+  const uint32_t row1 = min(desc.y & 0x7fffffffu, A.n_out), row0 = min(blk_first_row(desc.x), row1);
+  const uint32_t e1 = min(desc.w, A.nnz), e0 = desc.z;
+  const uint32_t base = e0 & ~1u;
+  double dsum = 0.0;  // FUSE: this thread's share of sum x[row] * y[row]; a dead workgroup leaves a zero partial
+
+  if (dead) {
+  } else if (e1 >= e0 && e1 - base <= TILE) {
+    // the first row's word for phase 2, requested before the tile so its latency overlaps
+    const uint32_t r = row0 + threadIdx.x;
+    uint32_t rs = 0, re = 0;
+    uint64_t rw = 0;
+    double xr = 0.0;
+    if (r < row1) {
+      if (uniform) {
+        const uint32_t len = (e1 - e0) / (row1 - row0);  // scalar: from the checked descriptor, no row word is read
+        rs = e0 + len * threadIdx.x; re = rs + len;
+      } else {
+        rw = S.rowext[r];
+      }
+      if (FUSE) xr = x[fuse.x_off + r];
+    }
+    csr_stage<MODE, EPT, VECC>(A, x, ev, base, e0, e1, s_prod, s_col);
+    __syncthreads();
+    for (uint32_t row = r; row < row1; row += ABFT_BLOCK) {
+      if (row != r) {
+        rw = S.rowext[row];
+        if (FUSE) xr = x[fuse.x_off + row];
+      }
+      if (!uniform || row != r) {
+        if (__builtin_expect(vecc_suspect(rw) != 0u, 0)) {
+          const VeccWord o = rowext_cold(rw, S.rowext + row, row, true, ev);
+          if (o.rc < 0) continue;  // two flips: y[row] is not written
+          rw = o.w;
+        }
+        rs = rowext_start(rw); re = rowext_end(rw);
+      }
+      if (MODE == MODE_CONSTRAINTS) {  // reference CSR/CPUContext.cpp:173-182
+        if (re > A.nnz) { push_event(ev, ABFT_EV_ROW_SIZE, row, row, FMT_CSR); continue; }
+        if (re < rs) { push_event(ev, ABFT_EV_ROW_ORDER, row, row, FMT_CSR); continue; }
+      }
+      if (rs < e0 || re > e1 || re < rs) continue;  // inconsistent extents: never touch LDS out of range
+      double acc = 0.0;
+      if (csr_row_sum<MODE>(A, ev, base, rs, re, re, s_prod, s_col, acc, row)) {
+        if (VECC) {
+          const uint64_t yw = vecc_encode(acc);
+          y[row] = vecc_double(yw);
+          if (FUSE) {
+            uint64_t xw = vecc_bits(xr);
+            if (__builtin_expect(vecc_suspect(xw) != 0u, 0)) xw = vecc_cold(xw, fuse.x_off + row, 0u, ev).w;
+            dsum += vecc_value(xw) * vecc_value(yw);
+          }
+        } else {
+          y[row] = acc;
+          if (FUSE) dsum += xr * acc;
+        }
+      }
+    }
+  } else {
+    // long row (or inconsistent element bounds): rows of this block one at a time, tile by tile.  Every thread reads
+    // the row's word, uniformly; thread 0 alone reports and stores back.
+    for (uint32_t row = row0; row < row1; row++) {
+      uint64_t rw = S.rowext[row];
+      if (__builtin_expect(vecc_suspect(rw) != 0u, 0)) {
+        const VeccWord o = rowext_cold(rw, S.rowext + row, row, threadIdx.x == 0, ev);
+        if (o.rc < 0) continue;
+        rw = o.w;
+      }
+      const uint32_t rs = rowext_start(rw), re = rowext_end(rw);
+      if (MODE == MODE_CONSTRAINTS) {
+        if (re > A.nnz) { if (threadIdx.x == 0) push_event(ev, ABFT_EV_ROW_SIZE, row, row, FMT_CSR); continue; }
+        if (re < rs) { if (threadIdx.x == 0) push_event(ev, ABFT_EV_ROW_ORDER, row, row, FMT_CSR); continue; }
+      }
+      if (re > A.nnz || re < rs) continue;
+      double acc = 0.0;
+      bool ok = true;
+      for (uint32_t lo = rs; lo < re;) {
+        const uint32_t b = lo & ~1u;
+        const uint32_t hi = min(re, b + TILE);
+        __syncthreads();
+        csr_stage<MODE, EPT, VECC>(A, x, ev, b, lo, hi, s_prod, s_col);
+        __syncthreads();
+        if (threadIdx.x == 0 && ok) ok = csr_row_sum<MODE>(A, ev, b, lo, hi, re, s_prod, s_col, acc, row);
+        lo = hi;
+      }
+      if (threadIdx.x == 0 && ok) {
+        if (VECC) {
+          const uint64_t yw = vecc_encode(acc);
+          y[row] = vecc_double(yw);
+          if (FUSE) dsum += vecc_decode_cold_ok(x + fuse.x_off + row, fuse.x_off + row, 0u, ev) * vecc_value(yw);
+        } else {
+          y[row] = acc;
+          if (FUSE) dsum += x[fuse.x_off + row] * acc;
+        }
+      }
+    }
+  }
+  if (FUSE) fused_dot_finish(dsum, fuse, t);
+}
+
+template <int MODE>
+static hipError_t launch_spmv_csr_struct_mode(const CsrDev &A, const CsrStruct &S, const TileSpan &span, const double *x,
+                                              double *y, EventRing ev, const FuseOut *fuse, hipStream_t s, bool vecc) {
+  const dim3 grid(span.count), block(ABFT_BLOCK);
+  if (vecc && fuse)
+    hipLaunchKernelGGL((spmv_csr_struct_kernel<MODE, ABFT_CSR_EPT, true, true>), grid, block, 0, s, A, S, x, y, ev, *fuse, span);
+  else if (vecc)
+    hipLaunchKernelGGL((spmv_csr_struct_kernel<MODE, ABFT_CSR_EPT, false, true>), grid, block, 0, s, A, S, x, y, ev, FuseOut{}, span);
+  else if (fuse)
+    hipLaunchKernelGGL((spmv_csr_struct_kernel<MODE, ABFT_CSR_EPT, true, false>), grid, block, 0, s, A, S, x, y, ev, *fuse, span);
+  else
+    hipLaunchKernelGGL((spmv_csr_struct_kernel<MODE, ABFT_CSR_EPT, false, false>), grid, block, 0, s, A, S, x, y, ev, FuseOut{}, span);
+  return hipGetLastError();
+}
+
+hipError_t launch_spmv_csr_struct(int mode, const CsrDev &A, const CsrStruct &S, const TileSpan &span, const double *x,
+                                  double *y, EventRing ev, const FuseOut *fuse, hipStream_t s, bool vecc) {
+  if (!S.rowext || !S.blk) return hipErrorInvalidValue;
+  // every tile the span maps to must exist: checked here, on the host
+  if (span.count == 0) return hipSuccess;
+  if ((uint64_t)span.first + span.count + span.skip > A.nblk || span.cut > span.count) return hipErrorInvalidValue;
+  switch (mode) {
+    case MODE_NONE: return launch_spmv_csr_struct_mode<MODE_NONE>(A, S, span, x, y, ev, fuse, s, vecc);
+    case MODE_CONSTRAINTS: return launch_spmv_csr_struct_mode<MODE_CONSTRAINTS>(A, S, span, x, y, ev, fuse, s, vecc);
+    case MODE_SED: return launch_spmv_csr_struct_mode<MODE_SED>(A, S, span, x, y, ev, fuse, s, vecc);
+    case MODE_SEC7: return launch_spmv_csr_struct_mode<MODE_SEC7>(A, S, span, x, y, ev, fuse, s, vecc);
+    case MODE_SEC8: return launch_spmv_csr_struct_mode<MODE_SEC8>(A, S, span, x, y, ev, fuse, s, vecc);
+    case MODE_SECDED: return launch_spmv_csr_struct_mode<MODE_SECDED>(A, S, span, x, y, ev, fuse, s, vecc);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// create: the packed row words and the plain descriptors, as uploaded, get their codes in place
+__global__ __launch_bounds__(ABFT_BLOCK) void struct_encode_kernel(CsrStruct S, uint32_t n, uint32_t nblk) {
+  const uint32_t stride = gridDim.x * ABFT_BLOCK;
+  for (uint32_t i = blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) S.rowext[i] = rowext_code(S.rowext[i]);
+  for (uint32_t i = blockIdx.x * ABFT_BLOCK + threadIdx.x; i < nblk; i += stride) {
+    const uint4 d = S.blk[i];
+    uint32_t w[4] = {d.x, d.y, d.z, d.w};
+    blk_encode(w);
+    S.blk[i] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
+// Scrub: every row word and every descriptor -- the row words of uniform blocks too, which no SpMV reads --, one
+// thread each: single flips repaired in place and reported like the SpMV does, counts[0] += repaired words,
+// counts[1] += uncorrectable ones.
+__global__ __launch_bounds__(ABFT_BLOCK) void struct_scrub_kernel(CsrStruct S, uint32_t n, uint32_t nblk, uint32_t *counts,
+                                                                  EventRing ev) {
+  const uint32_t stride = gridDim.x * ABFT_BLOCK;
+  for (uint32_t i = blockIdx.x * ABFT_BLOCK + threadIdx.x; i < n; i += stride) {
+    const uint64_t w = S.rowext[i];
+    if (__builtin_expect(vecc_suspect(w) != 0u, 0)) {
+      const VeccWord o = rowext_cold(w, S.rowext + i, i, true, ev);
+      if (o.rc) atomicAdd(counts + (o.rc > 0 ? 0 : 1), 1u);
+    }
+  }
+  for (uint32_t i = blockIdx.x * ABFT_BLOCK + threadIdx.x; i < nblk; i += stride) {
+    const uint4 d = S.blk[i];
+    const uint32_t w[4] = {d.x, d.y, d.z, d.w};
+    if (__builtin_expect(blk_suspect(w) != 0u, 0)) {
+      const StructBlk o = blk_cold(d, S.blk + i, i, true, ev);
+      if (o.rc) atomicAdd(counts + (o.rc > 0 ? 0 : 1), 1u);
+    }
+  }
+}
+
+static uint32_t struct_grid(uint32_t n, uint32_t nblk) {
+  const uint32_t most = n > nblk ? n : nblk;
+  const uint32_t nb = (most + ABFT_BLOCK - 1) / ABFT_BLOCK;
+  return nb < 1u ? 1u : nb > 4096u ? 4096u : nb;
+}
+
+hipError_t launch_struct_encode(const CsrStruct &S, uint32_t n, uint32_t nblk, hipStream_t s) {
+  hipLaunchKernelGGL(struct_encode_kernel, dim3(struct_grid(n, nblk)), dim3(ABFT_BLOCK), 0, s, S, n, nblk);
+  return hipGetLastError();
+}
+
+hipError_t launch_struct_scrub(const CsrStruct &S, uint32_t n, uint32_t nblk, uint32_t *counts, EventRing ev, hipStream_t s) {
+  hipLaunchKernelGGL(struct_scrub_kernel, dim3(struct_grid(n, nblk)), dim3(ABFT_BLOCK), 0, s, S, n, nblk, counts, ev);
+  return hipGetLastError();
 }
 
 // ------------------------------------------------------- CSR block SpMV (SpMM) --

@@ -72,8 +72,15 @@ typedef enum {
    * inside the operand, `bit` holds the word bit in bits 0..7 and the operand's ordinal among the
    * entry's vector arguments, from 0, in bits 8..15 */
   ABFT_EV_VEC_CORRECTED = 10, /* "[ECC] corrected bit %u of vector operand %u at index %d"            */
-  ABFT_EV_VEC_DOUBLE = 11     /* "[ECC] double-bit error detected in vector operand %u at index %d" fatal */
+  ABFT_EV_VEC_DOUBLE = 11,    /* "[ECC] double-bit error detected in vector operand %u at index %d" fatal */
+  /* the protected row structure (abft_hip_matrix_create_csr_protected; fmt = ABFT_FMT_CSR): `bit` holds the
+   * word bit in bits 0..7 (a row block's numbered as a COO element's 128) and the kind of word in bits 8..15
+   * -- ABFT_STRUCT_ROW_EXTENT or ABFT_STRUCT_ROW_BLOCK --, `index` is the row or the block number */
+  ABFT_EV_STRUCT_CORRECTED = 12, /* "[ECC] corrected bit %u of row extent %d" / "... of row block %d"              */
+  ABFT_EV_STRUCT_DOUBLE = 13     /* "[ECC] double-bit error detected in row extent %d" / "... in row block %d" fatal */
 } abft_event_kind;
+#define ABFT_STRUCT_ROW_EXTENT 0
+#define ABFT_STRUCT_ROW_BLOCK 1
 #define ABFT_FMT_VECTOR 2 /* abft_event.fmt of the two vector events */
 
 typedef struct {
@@ -184,6 +191,35 @@ int abft_hip_inject(abft_hip_matrix *mat, uint32_t index, const int *bits, int n
 /* XOR `mask` into row pointer `row` (0..N) of a CSR matrix: the array constraints mode checks
  * at reference CSR/CPUContext.cpp:173-182 and the reference's own injector never touches. */
 int abft_hip_inject_rowptr(abft_hip_matrix *mat, uint32_t row, uint32_t mask);
+
+/* ---- the protected row structure -----------------
+ * Like abft_hip_matrix_create_csr_stream, but the matrix stores no plain row pointers and no plain
+ * row-block descriptors: one 64-bit row extent word per row {code, rowptr[r], rowptr[r + 1]} under the
+ * (64, 57) code of the protected vectors, and the descriptors under the 128-bit COO element code in
+ * secded form -- both SECDED whatever `mode` is.  Every SpMV checks each word it reads: one flipped bit
+ * is repaired, stored back and reported (ABFT_EV_STRUCT_CORRECTED), two are ABFT_EV_STRUCT_DOUBLE, fatal,
+ * and the rows the word owns are not written.  Limits (ABFT_ERR_RANGE): nnz < 2^28, N <= 2^24.
+ * abft_hip_spmv, _spmv_part, _spmv_dot_dev, _spmv_vecc, the residual and restart entries, cg_iteration_dev
+ * and the four single guarded iterations run on such a matrix as on any other; read_csr and diag_inverse
+ * strip the codes.  abft_hip_inject_rowptr, the block entries (spmm, spmm_dot, spmm_dot_vecc, both block
+ * guarded iterations, block_loop_reserve) and abft_hip_spmv_dot_range_dev refuse it (ABFT_ERR_INVALID). */
+int abft_hip_matrix_create_csr_protected(abft_hip_ctx *ctx, int mode, const uint32_t *columns,
+                                         const uint32_t *rows, const double *values, int N, int nnz,
+                                         abft_hip_matrix **mat);
+/* is_protected: 0 / 1; row_words and blocks: how many words of each kind it stores (0 when not protected) */
+int abft_hip_matrix_structure_info(abft_hip_matrix *mat, int *is_protected, uint32_t *row_words, uint32_t *blocks);
+/* the stored codewords as they are: row_words 64-bit words, 4 * blocks 32-bit words.  Either may be NULL. */
+int abft_hip_matrix_read_structure(abft_hip_matrix *mat, uint64_t *rowext, uint32_t *blk4);
+/* the inverse: store the given words as they are, codewords or not (a fault injector for whole sweeps: one
+ * copy instead of one abft_hip_inject_structure per word).  Either may be NULL. */
+int abft_hip_matrix_write_structure(abft_hip_matrix *mat, const uint64_t *rowext, const uint32_t *blk4);
+/* XOR bits into ONE stored word: kind ABFT_STRUCT_ROW_EXTENT (bits 0..63 of row `index`'s word) or
+ * ABFT_STRUCT_ROW_BLOCK (bits 0..127 of descriptor `index`, numbered as a COO element's) */
+int abft_hip_inject_structure(abft_hip_matrix *mat, int kind, uint32_t index, const int *bits, int nbits);
+/* walk every row word and every descriptor -- those of uniform blocks too, which no SpMV reads --, repair
+ * single flips in place and report like the SpMV; the counts of this call (either may be NULL) */
+int abft_hip_matrix_scrub_structure(abft_hip_ctx *ctx, abft_hip_matrix *mat, uint32_t *corrected,
+                                    uint32_t *uncorrectable);
 
 /* ---- vectors ----------------------------------------------------------- */
 
