@@ -24,6 +24,8 @@ EV_VEC_CORRECTED, EV_VEC_DOUBLE = 10, 11  # protected vectors: bit = word bit | 
 FMT_VECTOR = 2
 EV_STRUCT_CORRECTED, EV_STRUCT_DOUBLE = 12, 13  # protected row structure: bit = word bit | kind << 8, index = row or block
 STRUCT_ROW, STRUCT_BLOCK = 0, 1  # the kind of a structure word
+EV_TRAIL_CORRECTED, EV_TRAIL_DOUBLE = 14, 15  # protected scalar trail: index = ordinal, bit = slot bit | record << 8
+TRAIL_START, TRAIL_PW, TRAIL_NEXT = 0, 1, 2  # the record of a trail event
 MAX_RHS = 8  # block right-hand sides per call (include/abft_hip.h)
 
 u32p = C.POINTER(C.c_uint32)
@@ -151,6 +153,18 @@ SIGNATURES = {
                                                        C.c_double]),
     "abft_hip_pcg_iteration_until_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
                                                    C.c_double]),
+    "abft_hip_cg_trail_iteration_until_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
+                                                       C.c_double]),
+    "abft_hip_pcg_trail_iteration_until_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                        C.c_double]),
+    "abft_hip_cg_vecc_trail_iteration_until_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
+                                                            C.c_double]),
+    "abft_hip_pcg_vecc_trail_iteration_until_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
+                                                             vp, C.c_double]),
+    "abft_hip_trail_encode": (C.c_int, [f64p, C.c_int, C.c_int, f64p]),
+    "abft_hip_trail_decode": (C.c_int, [f64p, C.c_int, f64p, i32p, i32p]),
+    "abft_hip_trail_flip": (C.c_int, [vp, vp, C.c_int, i32p, C.c_int]),
+    "abft_hip_trail_inject_at": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i32p, C.c_int]),
     "abft_hip_cg_block_iteration_until_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_double]),
     "abft_hip_cg_block_vecc_iteration_until_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_double]),
     "abft_hip_block_loop_reserve": (C.c_int, [vp, vp, C.c_int]),
@@ -252,7 +266,7 @@ def check(rc):
 
 def is_fatal(kind):
     """same rule as abft_event_is_fatal"""
-    return kind in (1, 4, EV_VEC_DOUBLE, EV_STRUCT_DOUBLE) or 5 <= kind <= 9
+    return kind in (1, 4, EV_VEC_DOUBLE, EV_STRUCT_DOUBLE, EV_TRAIL_DOUBLE) or 5 <= kind <= 9
 
 
 def format_event(kind, index, bit, fmt):

@@ -80,12 +80,20 @@ Additional options of this build:
                               J of kind K: row (a row extent, bits 0-63) or block (a
                               row-block descriptor, bits 0-127); needs --structure-ecc
                               secded (may be repeated)
+      --trail-ecc       E     Protect the device loop's scalar trail: none (default) or
+                              secded -- every word a slot under the (128, 120) code;
+                              needs --device-loop S
+      --flip-trail I:W:B[,B...]
+                              Flip bit(s) B (0-127) of word W (0 r.r, 1 events) of the
+                              record handed to the batch after iteration I's; needs
+                              --trail-ecc secded (may be repeated)
 
 """
 
 
 FLIP_VECTOR_MSG = "Invalid --flip-vector (want ITER:VEC:INDEX:BIT[,BIT...], VEC one of x, r, p)"
 FLIP_STRUCTURE_MSG = "Invalid --flip-structure (want ITER:row|block:INDEX:BIT[,BIT...])"
+FLIP_TRAIL_MSG = "Invalid --flip-trail (want ITER:WORD:BIT[,BIT...], WORD 0 or 1, bits 0-127)"
 
 
 def fail(msg):
@@ -97,7 +105,8 @@ def parse(argv):
     o = dict(num_blocks=25, max_itrs=1000, conv=0.001, matrix_file=DEFAULT_MTX, synthetic=None, target="cpu",
              mode="none", flips=0, kind="ANY", seed=None, quiet=False, flip_at=None, fmt="csr", list=False,
              rhs=1, check_every=0, check_tol=1e-7, max_rollbacks=3, flip_vector=[], precond="none",
-             vector_ecc="none", block_fused=False, device_loop=0, structure_ecc="none", flip_structure=[])
+             vector_ecc="none", block_fused=False, device_loop=0, structure_ecc="none", flip_structure=[],
+             trail_ecc="none", flip_trail=[])
 
     def num(s, conv):
         try:
@@ -212,6 +221,19 @@ def parse(argv):
                     not all(0 <= b < (64 if flip[1] == "row" else 128) for b in flip[3]):
                 fail(msg)
             o["flip_structure"] = o["flip_structure"] + [flip]
+        elif a == "--trail-ecc":
+            o["trail_ecc"] = arg("Invalid trail protection (want none or secded)")
+            if o["trail_ecc"] not in ("none", "secded"):
+                fail("Invalid trail protection (want none or secded)")
+        elif a == "--flip-trail":
+            try:
+                itr, word, bits = arg(FLIP_TRAIL_MSG).split(":")
+                flip = (int(itr), int(word), [int(b) for b in bits.split(",")])
+            except ValueError:
+                fail(FLIP_TRAIL_MSG)
+            if flip[0] < 0 or flip[1] not in (0, 1) or not all(0 <= b < 128 for b in flip[2]):
+                fail(FLIP_TRAIL_MSG)
+            o["flip_trail"] = o["flip_trail"] + [flip]
         elif a == "--block-fused":
             o["block_fused"] = True
         elif a == "--device-loop":
@@ -234,6 +256,10 @@ def parse(argv):
                          ("--flip-vector", bool(o["flip_vector"]))):
             if on:
                 fail("--device-loop cannot be combined with %s" % flag)
+    if o["trail_ecc"] == "secded" and not o["device_loop"]:
+        fail("--trail-ecc secded needs --device-loop S: it protects the scalar trail of the device loop")
+    if o["flip_trail"] and o["trail_ecc"] != "secded":
+        fail("--flip-trail needs --trail-ecc secded")
     if o["vector_ecc"] == "none":
         if any(f[1] in ("w", "b") for f in o["flip_vector"]):
             fail(FLIP_VECTOR_MSG)  # (known only here: --vector-ecc may follow --flip-vector)
@@ -434,11 +460,23 @@ def run_single(o):
 
     if o["device_loop"]:
         print("iteration loop: device scalars, stride %d" % o["device_loop"])
+    tecc = o["trail_ecc"] == "secded"
+    if tecc:
+        print("scalar trail: secded (128, 120)")
+    tflips = sorted(o["flip_trail"])
+
+    def flip_trail(done, trail):
+        # the record handed to the batch after iteration I's: record `stride` of pairs, once I's batch is behind us
+        while tflips and tflips[0][0] < done:
+            _, word, bits = tflips.pop(0)
+            ctx.flip_trail(trail, 2 * o["device_loop"] + word, bits)
+
     t0 = time.perf_counter()
     try:
         if o["device_loop"]:
             itr, rr = cg_solve_device(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
-                                      stride=o["device_loop"])
+                                      stride=o["device_loop"],
+                                      **({"trail_ecc": True, "on_batch": flip_trail} if tecc else {}))
         else:
             itr, rr = cg_solve(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
                                check_every=o["check_every"], check_tol=o["check_tol"],

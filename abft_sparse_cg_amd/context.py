@@ -8,6 +8,8 @@ include/abft_hip.h; the C++ HIPContext under host/ binds the same ABI for the
 cg-csr / cg-coo executables.
 """
 import ctypes as C
+import functools
+import inspect
 import math
 import sys
 
@@ -640,6 +642,11 @@ class HIPContext:
 
     def _drain(self):
         events, fatal = self.drain_events()
+        self._report(events, fatal)
+
+    def _report(self, events, fatal):
+        """events [(kind, index, bit)] as a drain hands them over: logged, then on_event's, or printed (FatalEvent on
+        a fatal one)"""
         if not events:
             return
         self.event_log.extend(events)
@@ -744,6 +751,100 @@ class HIPContext:
         check(self.L.abft_hip_pcg_iteration_until_dev(self.h, mat.h, vec.h, vec_offset, part, x.h, r.h, p.h, w.h,
                                                       dinv.h, base + 8 * in_at, base + 8 * pw_at, base + 8 * out_at,
                                                       threshold))
+
+    # ---- the device-scalar loop on a protected trail (include/abft_hip.h) ----
+    # The four guarded iterations with their scalars as SECDED slots of two doubles: records of 4 doubles (8 with
+    # dinv), the pair 4; rr_at / in_at, pw_at, rr_new_at / out_at count doubles and must be even.
+    def cg_trail_iteration_until_dev(self, mat, vec, x, r, p, w, scalars, rr_at, pw_at, rr_new_at, threshold,
+                                     vec_offset=0, part=capi.PART_ALL):
+        """cg_iteration_until_dev on a protected trail (abft_hip_cg_trail_iteration_until_dev)"""
+        base = scalars.device_ptr
+        check(self.L.abft_hip_cg_trail_iteration_until_dev(self.h, mat.h, vec.h, vec_offset, part, x.h, r.h, p.h, w.h,
+                                                           base + 8 * rr_at, base + 8 * pw_at, base + 8 * rr_new_at,
+                                                           threshold))
+
+    def pcg_trail_iteration_until_dev(self, mat, vec, x, r, p, w, dinv, scalars, in_at, pw_at, out_at, threshold,
+                                      vec_offset=0, part=capi.PART_ALL):
+        """pcg_iteration_until_dev on a protected trail (abft_hip_pcg_trail_iteration_until_dev)"""
+        base = scalars.device_ptr
+        check(self.L.abft_hip_pcg_trail_iteration_until_dev(self.h, mat.h, vec.h, vec_offset, part, x.h, r.h, p.h, w.h,
+                                                            dinv.h, base + 8 * in_at, base + 8 * pw_at,
+                                                            base + 8 * out_at, threshold))
+
+    def cg_vecc_trail_iteration_until_dev(self, mat, vec, x, r, p, w, scalars, rr_at, pw_at, rr_new_at, threshold,
+                                          vec_offset=0, part=capi.PART_ALL):
+        """cg_vecc_iteration_until_dev on a protected trail (abft_hip_cg_vecc_trail_iteration_until_dev)"""
+        base = scalars.device_ptr
+        check(self.L.abft_hip_cg_vecc_trail_iteration_until_dev(self.h, mat.h, vec.h, vec_offset, part, x.h, r.h, p.h,
+                                                                w.h, base + 8 * rr_at, base + 8 * pw_at,
+                                                                base + 8 * rr_new_at, threshold))
+
+    def pcg_vecc_trail_iteration_until_dev(self, mat, vec, x, r, p, w, dinv, scalars, in_at, pw_at, out_at, threshold,
+                                           vec_offset=0, part=capi.PART_ALL):
+        """pcg_vecc_iteration_until_dev on a protected trail (abft_hip_pcg_vecc_trail_iteration_until_dev)"""
+        base = scalars.device_ptr
+        check(self.L.abft_hip_pcg_vecc_trail_iteration_until_dev(self.h, mat.h, vec.h, vec_offset, part, x.h, r.h, p.h,
+                                                                 w.h, dinv.h, base + 8 * in_at, base + 8 * pw_at,
+                                                                 base + 8 * out_at, threshold))
+
+    def encode_trail(self, values, first_ordinal=0):
+        """n values -> their n slots as 2 n doubles, value i under ordinal first_ordinal + i (abft_hip_trail_encode)"""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        out = np.zeros(2 * len(v))
+        check(self.L.abft_hip_trail_encode(v.ctypes.data_as(capi.f64p), len(v), int(first_ordinal),
+                                           out.ctypes.data_as(capi.f64p)))
+        return out
+
+    def decode_trail(self, slots):
+        """2 n doubles -> (values[n], status[n], bits[n]): status 0 clean, 1 one flipped bit repaired (bits: which),
+        -1 two flips, the value as stored (abft_hip_trail_decode)"""
+        s = np.ascontiguousarray(slots, dtype=np.float64)
+        n = len(s) // 2
+        values, status, bits = np.zeros(n), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        check(self.L.abft_hip_trail_decode(s.ctypes.data_as(capi.f64p), n, values.ctypes.data_as(capi.f64p),
+                                           status.ctypes.data_as(capi.i32p), bits.ctypes.data_as(capi.i32p)))
+        return values, status, bits
+
+    def flip_trail(self, trail, slot, bits):
+        """XOR the given bits (0-127, numbered as the COO element's) into slot `slot` of the trail vector"""
+        b = np.ascontiguousarray(bits, dtype=np.int32)
+        check(self.L.abft_hip_trail_flip(self.h, trail.device_ptr, int(slot), b.ctypes.data_as(capi.i32p), len(b)))
+
+    def trail_inject_at(self, stage, record, ordinal, bits):
+        """arm one flip of a slot that lives inside an iteration: the next eager protected guarded call XORs `bits`
+        into slot `ordinal` of `record` (capi.TRAIL_START / TRAIL_PW / TRAIL_NEXT) behind its fold (stage 1) or its r
+        half (stage 2)"""
+        b = np.ascontiguousarray(bits, dtype=np.int32)
+        check(self.L.abft_hip_trail_inject_at(self.h, int(stage), int(record), int(ordinal),
+                                              b.ctypes.data_as(capi.i32p), len(b)))
+
+    def report_trail(self, slots, rec, stride):
+        """the host's view of a downloaded trail of stride + 1 records of `rec` slots and the pair: -> the values, in
+        the unprotected trail's layout.  A slot with one flipped bit is reported once, with the device's line (record:
+        the pair, else the start record); two flips raise FatalEvent"""
+        values, status, bits = self.decode_trail(slots)
+        # a codeword in the wrong place -- the ordinal under the code is not the slot's, or word 1 is set --: as two flips
+        words = np.ascontiguousarray(slots, dtype=np.float64).view(np.uint32).reshape(-1, 4)
+        j = np.arange(len(values))
+        ordinals = np.where(j >= rec * (stride + 1), j - rec * (stride + 1), j % rec)
+        status = np.where((status == 0) & (((words[:, 0] & 0xFFFFFF) != ordinals) | (words[:, 1] != 0)), -1, status)
+        bad = np.flatnonzero(status)
+        if len(bad):
+            events = []
+            for j in bad.tolist():
+                pair = j >= rec * (stride + 1)
+                ordinal = j - rec * (stride + 1) if pair else j % rec
+                where = (capi.TRAIL_PW if pair else capi.TRAIL_START) << 8
+                if status[j] > 0:
+                    events.append((capi.EV_TRAIL_CORRECTED, ordinal, int(bits[j]) | where))
+                else:
+                    events.append((capi.EV_TRAIL_DOUBLE, ordinal, where))
+                    break
+            fatal = events[-1][0] == capi.EV_TRAIL_DOUBLE
+            self._report(events, fatal)
+            if fatal:
+                raise FatalEvent(events)
+        return values
 
     def cg_block_iteration_until_dev(self, mat, X, R, P, W, k, scalars, in_at, pw_at, out_at, threshold, dinv=None):
         """one guarded iteration of the fused block loop, enqueue-only (abft_hip_cg_block_iteration_until_dev; DESIGN.md
@@ -1026,20 +1127,33 @@ def _whole_stride(stride):
     return int(stride)
 
 
-def _device_batches(ctx, max_itrs, stride, graph, rec, tail, seed, enqueue, record, before_capture=None):
+def _device_batches(ctx, max_itrs, stride, graph, rec, tail, seed, enqueue, record, before_capture=None,
+                    slots=False, on_batch=None):
     """The batch loop of cg_solve_device and cg_solve_block_device: a trail of stride + 1 records of `rec` doubles
     with `tail` doubles behind them (at pw_at = rec * (stride + 1): the SpMV's product), record `stride` starting
     with `seed`.  A batch copies record `stride` to record 0 and calls enqueue(trail, i, pw_at) for its iterations
     i = 0 .. m - 1; a full batch is captured once (behind before_capture()) and replayed when `graph`, else, and a
     short last one, enqueued call by call.  Then the trail is downloaded -- the one synchronisation, which drains
     the events -- and record(t, i, done) is called for i in order: true when iteration `done` was live (its
-    bookkeeping done), false at the first frozen one, which ends the loop.  -> the count of live iterations."""
+    bookkeeping done), false at the first frozen one, which ends the loop.  -> the count of live iterations.
+    slots: a protected trail -- every word a SECDED slot of two doubles, so all offsets double
+    (pw_at included), the seed record is encoded, and what is downloaded is decoded on the host (ctx.report_trail)
+    before record() sees it, in the unprotected layout.  on_batch(done, trail): called after a batch's callbacks with
+    the trail vector, whose record `stride` starts the next batch."""
     # (the records' lengths and word indices, here and in the callers, are those csrc/guard_protocol.h defines)
-    pw_at = rec * (stride + 1)
-    trail = ctx.create_vector(pw_at + tail)
-    first, last = ctx.view_vector(trail, 0, rec), ctx.view_vector(trail, rec * stride, rec)
-    start = np.zeros(pw_at + tail)
-    start[rec * stride:rec * stride + len(seed)] = seed  # where the first batch's copy finds it
+    wide = 2 if slots else 1  # doubles per trail word
+    pw_at = wide * rec * (stride + 1)
+    trail = ctx.create_vector(pw_at + wide * tail)
+    first, last = ctx.view_vector(trail, 0, wide * rec), ctx.view_vector(trail, wide * rec * stride, wide * rec)
+    start = np.zeros(pw_at + wide * tail)
+    if slots:  # every slot a codeword of its ordinal from the start: +0.0 everywhere, the seed in record `stride`
+        whole = np.zeros(rec)
+        start[:pw_at] = np.tile(ctx.encode_trail(whole, 0), stride + 1)
+        start[pw_at:] = ctx.encode_trail(np.zeros(tail), 0)
+        whole[:len(seed)] = seed
+        start[wide * rec * stride:wide * rec * (stride + 1)] = ctx.encode_trail(whole, 0)
+    else:
+        start[rec * stride:rec * stride + len(seed)] = seed  # where the first batch's copy finds it
     ctx.upload(trail, start)
 
     def batch(m):
@@ -1064,12 +1178,16 @@ def _device_batches(ctx, max_itrs, stride, graph, rec, tail, seed, enqueue, reco
             else:
                 batch(m)
             t = ctx.download(trail)  # synchronises, then drains the events
+            if slots:
+                t = ctx.report_trail(t, rec, stride)
             stopped = False
             for i in range(m):
                 if not record(t, i, done):
                     stopped = True
                     break
                 done += 1
+            if on_batch is not None:
+                on_batch(done, trail)
             if stopped or done >= max_itrs:
                 break
     finally:
@@ -1093,7 +1211,7 @@ def _check_batch(done, max_itrs, stride, check_every):
 
 
 def _device_batches_checked(ctx, A, b, x, r, w, x_ckpt, max_itrs, stride, graph, rec, seed, enqueue, record, goes_on,
-                            restart, check_every, check_tol, max_rollbacks, bb, on_check):
+                            restart, check_every, check_tol, max_rollbacks, bb, on_check, on_batch=None):
     """_device_batches with residual checks.  The trail has four more doubles behind the p.w
     pair (at chk_at = pw_at + 2) for ctx.residual_check_dev.  A batch of m iterations uses records stride - m ..
     stride, so that record `stride` holds the latest scalars after every batch, whatever its length: it copies
@@ -1180,6 +1298,8 @@ def _device_batches_checked(ctx, A, b, x, r, w, x_ckpt, max_itrs, stride, graph,
                 st["checked"] = False
             if check:
                 verdict(t[chk_at:chk_at + 4])
+            if on_batch is not None:  # behind the batch's callbacks, on_check included
+                on_batch(done, trail)
     finally:
         for g in graphs.values():
             ctx.graph_destroy(g)
@@ -1191,7 +1311,33 @@ def _device_batches_checked(ctx, A, b, x, r, w, x_ckpt, max_itrs, stride, graph,
 def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
                     stride=DEFAULT_STRIDE, graph=True, precond=None, vector_ecc=False, check_every=0,
                     check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None):
-    """cg_solve's loop (cg.cpp:87-118) with alpha, beta and the stop test on the device:
+    """The parameters cg_solve_device takes by position or by name, in the order they have always had (the residual
+    checks' five stay the last of them: tests/test_device_loop_check_host.py pins that).  The public cg_solve_device
+    below wraps this function and adds two KEYWORD-ONLY arguments behind them, trail_ecc=False and on_batch=None;
+    inspect.signature follows the wrapper to this list, so look there for those two."""
+    return _cg_solve_device(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, stride, graph, precond,
+                            vector_ecc, check_every, check_tol, max_rollbacks, x_ckpt, on_check, False, None)
+
+
+_cg_solve_device_positional = cg_solve_device
+
+
+@functools.wraps(_cg_solve_device_positional, assigned=("__module__", "__name__", "__qualname__"))
+def cg_solve_device(*args, trail_ecc=False, on_batch=None, **kw):
+    if not trail_ecc and on_batch is None:
+        return _cg_solve_device_positional(*args, **kw)
+    bound = inspect.signature(_cg_solve_device_positional).bind(*args, **kw)
+    bound.apply_defaults()
+    return _cg_solve_device(*bound.args, trail_ecc, on_batch)
+
+
+def _cg_solve_device(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, stride, graph, precond, vector_ecc,
+                     check_every, check_tol, max_rollbacks, x_ckpt, on_check, trail_ecc, on_batch):
+    """cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
+    stride=DEFAULT_STRIDE, graph=True, precond=None, vector_ecc=False, check_every=0, check_tol=1e-7, max_rollbacks=3,
+    x_ckpt=None, on_check=None, *, trail_ecc=False, on_batch=None)
+
+    cg_solve's loop (cg.cpp:87-118) with alpha, beta and the stop test on the device:
     the host looks at the scalars once per batch of `stride` iterations instead of twice per iteration.
 
     copy r <- b, copy p <- r and rr0 = dot(r, r) as cg_solve; with max_itrs == 0 or not rr0 > conv_threshold
@@ -1243,9 +1389,26 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
     ctx.precond_start), reseeds record `stride` and goes on, the iteration count running on as in cg_solve.  When the
     loop is about to stop on a state no check has seen, one check is enqueued on its own and its slot downloaded: the
     one extra synchronisation of a solve.  precond (a plain dinv) is supported; vector_ecc=True with check_every > 0
-    is refused as in cg_solve.  With check_every=0 the calls are exactly those made without the arguments."""
+    is refused as in cg_solve.  With check_every=0 the calls are exactly those made without the arguments.
+
+    trail_ecc=True (keyword-only, as on_batch is) keeps the scalar trail under a SECDED code:
+    every word of every record and
+    of the p.w pair is a slot of two doubles, the seed is encoded (ctx.encode_trail), the batches are made of
+    ctx.cg_trail_iteration_until_dev / pcg_trail_ / cg_vecc_trail_ / pcg_vecc_trail_ -- the same loops, the same bits
+    --, and after every download the trail is decoded on the host (ctx.report_trail): a slot found with one flipped bit
+    there is reported once, with the device's line, two flips raise FatalEvent.  On the device one flipped bit in a
+    slot a launch reads is repaired, stored back and reported; two flips in a slot a decision depends on are fatal,
+    and x, r and p keep every bit from that iteration on (FatalEvent at that batch's download, before its callbacks).
+    Works with precond, vector_ecc, a structure-protected matrix, graph on or off, every stride.  Refused (ValueError,
+    before anything runs) with check_every > 0: the check's four words are not under the code.
+    on_batch(done, trail) runs after a batch's callbacks with the trail vector; its record `stride` starts the next
+    batch (with trail_ecc: ctx.flip_trail(trail, slot, bits) flips a bit of it); with check_every > 0 it runs behind
+    on_check as well, and the latest record is still record `stride`.  With trail_ecc=False and
+    on_batch=None the calls are exactly those made without the arguments."""
     stride = _whole_stride(stride)
     _check_args(check_every, check_tol, max_rollbacks)
+    if trail_ecc and check_every:
+        raise ValueError("trail_ecc with check_every > 0: the residual check's four words are not under the code")
     if vector_ecc and check_every:
         raise ValueError("vector_ecc with check_every > 0: the residual kernels write unencoded vectors")
     protected = _check_protected_precond(precond, vector_ecc)
@@ -1277,7 +1440,18 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
     done, last_rr = 0, [rr]
 
     def enqueue(trail, k, pw_at):
-        if protected:
+        if trail_ecc:  # the same four loops on slots of two doubles
+            if protected:
+                ctx.pcg_vecc_trail_iteration_until_dev(A, p, x, r, p, w, precond, trail, 8 * k, pw_at, 8 * k + 8,
+                                                       conv_threshold)
+            elif vector_ecc:
+                ctx.cg_vecc_trail_iteration_until_dev(A, p, x, r, p, w, trail, 4 * k, pw_at, 4 * k + 4, conv_threshold)
+            elif precond is None:
+                ctx.cg_trail_iteration_until_dev(A, p, x, r, p, w, trail, 4 * k, pw_at, 4 * k + 4, conv_threshold)
+            else:
+                ctx.pcg_trail_iteration_until_dev(A, p, x, r, p, w, precond, trail, 8 * k, pw_at, 8 * k + 8,
+                                                  conv_threshold)
+        elif protected:
             ctx.pcg_vecc_iteration_until_dev(A, p, x, r, p, w, precond, trail, 4 * k, pw_at, 4 * k + 4,
                                              conv_threshold)
         elif vector_ecc:
@@ -1313,19 +1487,24 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
             ctx.copy_vector(x_ckpt, x)
             done = _device_batches_checked(ctx, A, b, x, r, w, x_ckpt, max_itrs, stride, graph, rec, seed, enqueue,
                                            record, lambda: last_rr[0] > conv_threshold, restart, int(check_every),
-                                           check_tol, max_rollbacks, rr, on_check)  # bb = rr: r = b, ||b||^2
+                                           check_tol, max_rollbacks, rr, on_check,  # bb = rr: r = b, ||b||^2
+                                           **({} if on_batch is None else {"on_batch": on_batch}))
         finally:
             if own_ckpt:
                 ctx.destroy_vector(x_ckpt)
         return done, last_rr[0]
     if max_itrs != 0 and rr > conv_threshold:
-        done = _device_batches(ctx, max_itrs, stride, graph, rec, 2, seed, enqueue, record)
+        done = _device_batches(ctx, max_itrs, stride, graph, rec, 2, seed, enqueue, record, slots=bool(trail_ecc),
+                               on_batch=on_batch)
     if vector_ecc:
         ctx.scrub_vector(x)
         ctx.scrub_vector(b)
         if protected:
             ctx.scrub_vector(precond)
     return done, last_rr[0]
+
+
+cg_solve_device.__doc__ = _cg_solve_device.__doc__
 
 
 def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,

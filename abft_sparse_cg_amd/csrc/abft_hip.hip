@@ -24,6 +24,7 @@
 #include "layout_plan.h"
 #include "loop_state.h"
 #include "struct_ecc.h"
+#include "trail_ecc.h"
 
 // ------------------------------------------------------------------ errors --
 
@@ -59,6 +60,13 @@ static constexpr uint32_t ABFT_HOST_SLOTS = 4;  // result slots in the pinned ri
 
 // (LoopState, loop_state.h: what the context keeps between the calls of the host-scalar CG loop -- the fused product,
 // the deferred and the pending x update, the caller's iteration, the speculation, the run-ahead -- and the switches)
+// abft_hip_trail_inject_at: one XOR into a slot that lives inside an iteration, enqueued by the next eager protected
+// guarded call behind its fold (stage 1) or its r half (stage 2)
+struct TrailInjection {
+  int stage = 0, record = 0, ordinal = 0, nbits = 0;
+  uint32_t mask[4] = {0u, 0u, 0u, 0u};
+};
+
 struct abft_hip_ctx : LoopState {
   abft_hip_ctx() {
     xin_modes = ABFT_X_IN_SPMV_MODES;
@@ -94,6 +102,7 @@ struct abft_hip_ctx : LoopState {
   MovedList moved{};                  // COO elements with a silently corrupted column (device memory)
   int *bits_dev = nullptr;            // scratch for inject (32 ints)
   double *alpha_dev = nullptr;  // alpha of the deferred update when it was formed on the device
+  TrailInjection trail_inject;  // abft_hip_trail_inject_at: armed while nbits != 0
   // block right-hand sides (abft_hip_dot_block, abft_hip_calc_xr_block): allocated by the first such call
   double *bpartials = nullptr;          // 2 * ABFT_MAX_RHS * ABFT_MAX_PARTIALS doubles (the 2K sums of a block check)
   HostSlotK *bslot = nullptr, *bslot_dev = nullptr;  // pinned K-wide result slot, its device alias
@@ -3678,13 +3687,86 @@ static int check_cg_vectors(const abft_hip_vector *x, const abft_hip_vector *r, 
 }
 
 // the fold of its fused product that an SpMV held back (spmv_common's `hold`), launched now
-static int finish_held_fold(abft_hip_ctx *ctx, const HeldFold &hold) {
+// (trail: the pair is published as slots, trail_ecc.h)
+static int finish_held_fold(abft_hip_ctx *ctx, const HeldFold &hold, bool trail = false) {
   if (!hold.held) return ABFT_OK;
   KernelTimer t(ctx, ABFT_K_DOT);
   ReduceOut big{};
   big.partials = ctx->partials; big.ticket = ctx->ticket; big.dev_out = hold.fuse.dev_out; big.host = hold.fuse.host;
   big.ev_count = hold.fuse.ev_count; big.seq = hold.fuse.seq; big.peers = hold.fuse.peers;
-  HIPCHK(launch_fuse_finalize(hold.fuse, hold.nparts, big, hold.fix.on ? &hold.fix : nullptr, ctx->stream));
+  if (trail)
+    HIPCHK(launch_fuse_finalize_trail(hold.fuse, hold.nparts, big, hold.fix.on ? &hold.fix : nullptr, ctx->stream));
+  else
+    HIPCHK(launch_fuse_finalize(hold.fuse, hold.nparts, big, hold.fix.on ? &hold.fix : nullptr, ctx->stream));
+  return ABFT_OK;
+}
+
+// ---- the protected trail (trail_ecc.h): the host's view and fault injection ----
+void trail_host_encode(const double *values, int n, int first_ordinal, double *slots);  // trail_host.cpp
+void trail_host_decode(const double *slots, int n, double *values, int *status, int *bits);
+
+extern "C" int abft_hip_trail_encode(const double *values, int n, int first_ordinal, double *slots) {
+  if (n < 0 || (n && (!values || !slots))) return set_err(ABFT_ERR_INVALID, "trail_encode: bad arguments");
+  if (first_ordinal < 0 || (int64_t)first_ordinal + n > (int64_t)ABFT_TRAIL_ORDINAL_MASK + 1)
+    return set_err(ABFT_ERR_INVALID, "trail_encode: ordinals [%d,%lld) outside 24 bits", first_ordinal, (long long)first_ordinal + n);
+  trail_host_encode(values, n, first_ordinal, slots);
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_trail_decode(const double *slots, int n, double *values, int *status, int *bits) {
+  if (n < 0 || (n && (!slots || !values))) return set_err(ABFT_ERR_INVALID, "trail_decode: bad arguments");
+  trail_host_decode(slots, n, values, status, bits);
+  return ABFT_OK;
+}
+
+// bits (0..127) -> the XOR mask of a slot
+static int trail_mask(const char *what, const int *bits, int nbits, uint32_t mask[4]) {
+  if (nbits < 0 || nbits > 128 || (nbits && !bits)) return set_err(ABFT_ERR_INVALID, "%s: bad bit list", what);
+  mask[0] = mask[1] = mask[2] = mask[3] = 0u;
+  for (int k = 0; k < nbits; k++) {
+    if (bits[k] < 0 || bits[k] >= 128) return set_err(ABFT_ERR_INVALID, "%s: bit %d outside [0,128)", what, bits[k]);
+    mask[bits[k] >> 5] ^= 1u << (bits[k] & 31);
+  }
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_trail_flip(abft_hip_ctx *ctx, double *dev_slots, int slot, const int *bits, int nbits) {
+  if (int rc = enter(ctx, 0)) return rc;
+  if (!dev_slots || slot < 0 || ((uintptr_t)dev_slots & 15u))
+    return set_err(ABFT_ERR_INVALID, "trail_flip: null or misaligned slots, or a negative slot");
+  uint32_t mask[4];
+  if (int rc = trail_mask("trail_flip", bits, nbits, mask)) return rc;
+  if (!(mask[0] | mask[1] | mask[2] | mask[3])) return ABFT_OK;
+  HIPCHK(launch_flip_trail(dev_slots + (size_t)ABFT_TRAIL_SLOT * slot, mask, ctx->stream));
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_trail_inject_at(abft_hip_ctx *ctx, int stage, int record, int ordinal, const int *bits, int nbits) {
+  if (int rc = enter(ctx, 0)) return rc;
+  if (nbits == 0) {
+    ctx->trail_inject = TrailInjection{};
+    return ABFT_OK;
+  }
+  if (stage != 1 && stage != 2) return set_err(ABFT_ERR_INVALID, "trail_inject_at: stage %d (1: behind the fold, 2: behind the r half)", stage);
+  if (record < 0 || record > (int)ABFT_TRAIL_NEXT) return set_err(ABFT_ERR_INVALID, "trail_inject_at: record %d", record);
+  if (ordinal < 0 || ordinal > 3) return set_err(ABFT_ERR_INVALID, "trail_inject_at: ordinal %d outside [0,4)", ordinal);
+  TrailInjection inj{};
+  if (int rc = trail_mask("trail_inject_at", bits, nbits, inj.mask)) return rc;
+  inj.stage = stage; inj.record = record; inj.ordinal = ordinal; inj.nbits = nbits;
+  ctx->trail_inject = inj;
+  return ABFT_OK;
+}
+
+// the armed injection, when this is its stage: enqueued once, then disarmed (iteration_until has refused an ordinal
+// the record does not have, with its other refusals: the slot lies inside the record)
+static int trail_injection(abft_hip_ctx *ctx, int stage, const TrailIter &t) {
+  TrailInjection &inj = ctx->trail_inject;
+  if (!inj.nbits || inj.stage != stage) return ABFT_OK;
+  double *rec = inj.record == (int)ABFT_TRAIL_START ? t.in : inj.record == (int)ABFT_TRAIL_PW ? t.pw : t.out;
+  const uint32_t mask[4] = {inj.mask[0], inj.mask[1], inj.mask[2], inj.mask[3]};
+  const int ordinal = inj.ordinal;
+  inj = TrailInjection{};
+  HIPCHK(launch_flip_trail(rec + (size_t)ABFT_TRAIL_SLOT * ordinal, mask, ctx->stream));
   return ABFT_OK;
 }
 
@@ -3695,7 +3777,7 @@ static int check_guarded_iteration(abft_hip_ctx *ctx, const char *what, const ab
                                    const abft_hip_vector *vec, int vec_offset, int part, const abft_hip_vector *x,
                                    const abft_hip_vector *r, const abft_hip_vector *p, const abft_hip_vector *w,
                                    bool precond, const abft_hip_vector *dinv, const double *dev_in,
-                                   const double *dev_pw, const double *dev_out) {
+                                   const double *dev_pw, const double *dev_out, bool trail = false) {
   if (!mat || !vec || !x || !r || !p || !w || (precond && !dinv)) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
   if (!dev_in || !dev_pw || !dev_out) return set_err(ABFT_ERR_INVALID, "%s: null device scalar", what);
   if (part != ABFT_PART_ALL && part != ABFT_PART_BOUNDARY)
@@ -3705,7 +3787,11 @@ static int check_guarded_iteration(abft_hip_ctx *ctx, const char *what, const ab
     return set_err(ABFT_ERR_INVALID, "%s: a peer board is attached; the guarded iteration runs on one rank", what);
   // two pairs (preconditioned: records of four doubles) and the pair of the SpMV
   auto apart = [](const double *a, int na, const double *b, int nb) { return a + na <= b || b + nb <= a; };
-  const int rec = precond ? GuardQuad::LEN : GuardPair::LEN, pwl = GuardPair::PW_LEN;
+  // (a protected trail: every word a slot of two doubles, 16-byte aligned -- the kernels load a slot at once)
+  const int rec = trail ? (precond ? TrailQuad::DOUBLES : TrailPair::DOUBLES) : precond ? GuardQuad::LEN : GuardPair::LEN;
+  const int pwl = trail ? TrailPair::PW_DOUBLES : GuardPair::PW_LEN;
+  if (trail && (((uintptr_t)dev_in | (uintptr_t)dev_pw | (uintptr_t)dev_out) & 15u))
+    return set_err(ABFT_ERR_INVALID, "%s: a trail slot is not 16-byte aligned", what);
   if (!apart(dev_in, rec, dev_pw, pwl) || !apart(dev_in, rec, dev_out, rec) || !apart(dev_pw, pwl, dev_out, rec))
     return set_err(ABFT_ERR_INVALID, "%s: the scalar %s overlap", what, precond ? "records" : "pairs");
   if (int rc = check_cg_vectors(x, r, p, w, what)) return rc;
@@ -3827,11 +3913,24 @@ extern "C" int abft_hip_cg_iteration_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat
 static int iteration_until(abft_hip_ctx *ctx, const char *what, bool vecc, abft_hip_matrix *mat,
                            const abft_hip_vector *vec, int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
                            abft_hip_vector *p, abft_hip_vector *w, const abft_hip_vector *dinv, bool precond,
-                           const double *dev_in, double *dev_pw, double *dev_out, double threshold) {
+                           const double *dev_in, double *dev_pw, double *dev_out, double threshold,
+                           bool trail = false) {
   if (int rc = enter(ctx, 0)) return rc;  // a pending x update applied, a speculation voided
   if (int rc = check_guarded_iteration(ctx, what, mat, vec, vec_offset, part, x, r, p, w, precond, dinv, dev_in, dev_pw,
-                                       dev_out))
+                                       dev_out, trail))
     return rc;
+  if (trail && ctx->capturing && ctx->trail_inject.nbits)
+    return set_err(ABFT_ERR_INVALID, "%s: called under graph capture with a trail injection armed (abft_hip_trail_inject_at "
+                   "reaches eager calls only)", what);
+  // an armed injection names a slot the records of THIS entry must have: the pair has two, a record two or four.
+  // Refused here with the other refusals, before anything is enqueued; it stays armed
+  if (trail && ctx->trail_inject.nbits) {
+    const TrailInjection &inj = ctx->trail_inject;
+    const int len = inj.record == (int)ABFT_TRAIL_PW ? (int)TrailPair::PW_LEN : precond ? (int)TrailQuad::LEN : (int)TrailPair::LEN;
+    if (inj.ordinal >= len)
+      return set_err(ABFT_ERR_INVALID, "%s: the armed trail injection names word %d of a record of %d words", what,
+                     inj.ordinal, len);
+  }
   // what spmv_vecc refuses, refused here under the entry's name: spmv_common would forget the learned iteration first,
   // and a refused call leaves the state alone
   if (vecc)
@@ -3851,13 +3950,27 @@ static int iteration_until(abft_hip_ctx *ctx, const char *what, bool vecc, abft_
   }
   HeldFold hold;
   if (int rc = spmv_common(ctx, mat, vec, w, vec_offset, dev_pw, part, 0, -1, &hold, vecc)) return rc;
-  if (int rc = finish_held_fold(ctx, hold)) return rc;
+  if (int rc = finish_held_fold(ctx, hold, trail)) return rc;
   const ReduceOut o = reduce_out(ctx, dev_out, false);
   ReduceOutD od{};
   od.partials = ctx->bpartials;
   od.ticket = ctx->ticket;
   od.dev_out = dev_out;
   od.ev_count = ctx->ring.count;
+  if (trail) {
+    // the protected siblings: the same three kernels behind the SpMV, the scalars as slots, no alpha scratch word
+    const TrailIter t{const_cast<double *>(dev_in), dev_pw, dev_out, threshold, ctx->ring};
+    double *dv = dinv ? dinv->d : nullptr;
+    if (int rc = trail_injection(ctx, 1, t)) return rc;
+    {
+      KernelTimer kt(ctx, ABFT_K_CALC_XR);
+      HIPCHK(launch_trail_r_until(vecc, precond, r->d, w->d, dv, x->d, p->d, t, n, o, od, ctx->stream));
+    }
+    if (int rc = trail_injection(ctx, 2, t)) return rc;
+    KernelTimer kt(ctx, ABFT_K_CALC_P);
+    HIPCHK(launch_trail_px_until(vecc, precond, x->d, p->d, r->d, dv, t, n, ctx->stream));
+    return ABFT_OK;
+  }
   double *alpha = ctx->alpha_dev;
   {
     KernelTimer t(ctx, ABFT_K_CALC_XR);
@@ -3935,6 +4048,43 @@ extern "C" int abft_hip_pcg_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip
                                                      double threshold) {
   return iteration_until(ctx, "pcg_vecc_iteration_until", true, mat, vec, vec_offset, part, x, r, p, w, dinv, true, dev_in,
                          dev_pw, dev_out, threshold);
+}
+
+// ---- the four single guarded iterations on a protected trail ----------------
+// iteration_until with trail = true: the records and the pair are SECDED slots (trail_ecc.h), the fold and the two
+// halves are the protected siblings, ctx->alpha_dev is not used.  The start record is repaired in place: not const.
+extern "C" int abft_hip_cg_trail_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                                     int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                                     abft_hip_vector *p, abft_hip_vector *w, double *dev_rr,
+                                                     double *dev_pw, double *dev_rr_new, double threshold) {
+  return iteration_until(ctx, "cg_trail_iteration_until", false, mat, vec, vec_offset, part, x, r, p, w, nullptr, false,
+                         dev_rr, dev_pw, dev_rr_new, threshold, true);
+}
+
+extern "C" int abft_hip_pcg_trail_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                                      int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                                      abft_hip_vector *p, abft_hip_vector *w, const abft_hip_vector *dinv,
+                                                      double *dev_in, double *dev_pw, double *dev_out, double threshold) {
+  return iteration_until(ctx, "pcg_trail_iteration_until", false, mat, vec, vec_offset, part, x, r, p, w, dinv, true,
+                         dev_in, dev_pw, dev_out, threshold, true);
+}
+
+extern "C" int abft_hip_cg_vecc_trail_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat,
+                                                          const abft_hip_vector *vec, int vec_offset, int part,
+                                                          abft_hip_vector *x, abft_hip_vector *r, abft_hip_vector *p,
+                                                          abft_hip_vector *w, double *dev_rr, double *dev_pw,
+                                                          double *dev_rr_new, double threshold) {
+  return iteration_until(ctx, "cg_vecc_trail_iteration_until", true, mat, vec, vec_offset, part, x, r, p, w, nullptr,
+                         false, dev_rr, dev_pw, dev_rr_new, threshold, true);
+}
+
+extern "C" int abft_hip_pcg_vecc_trail_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat,
+                                                           const abft_hip_vector *vec, int vec_offset, int part,
+                                                           abft_hip_vector *x, abft_hip_vector *r, abft_hip_vector *p,
+                                                           abft_hip_vector *w, abft_hip_vector *dinv, double *dev_in,
+                                                           double *dev_pw, double *dev_out, double threshold) {
+  return iteration_until(ctx, "pcg_vecc_trail_iteration_until", true, mat, vec, vec_offset, part, x, r, p, w, dinv, true,
+                         dev_in, dev_pw, dev_out, threshold, true);
 }
 
 // ---- the guarded block iteration: K right-hand sides, the column mask decided on the device ----------------
@@ -4151,7 +4301,12 @@ extern "C" int abft_hip_graph_destroy(abft_hip_graph *g) {
 
 extern "C" int abft_event_is_fatal(uint32_t kind) {
   return kind == ABFT_EV_SED_DETECTED || kind == ABFT_EV_DOUBLE_BIT || kind == ABFT_EV_VEC_DOUBLE || kind == ABFT_EV_STRUCT_DOUBLE ||
+         kind == ABFT_EV_TRAIL_DOUBLE ||
          (kind >= ABFT_EV_ROW_SIZE && kind <= ABFT_EV_MOVED_OVERFLOW);
+}
+
+static const char *trail_record_name(uint32_t record) {
+  return record == ABFT_TRAIL_START ? "start record" : record == ABFT_TRAIL_PW ? "p.w pair" : "next record";
 }
 
 extern "C" int abft_format_event(const abft_event *ev, char *buf, size_t cap) {
@@ -4189,6 +4344,12 @@ extern "C" int abft_format_event(const abft_event *ev, char *buf, size_t cap) {
     case ABFT_EV_STRUCT_DOUBLE:
       return snprintf(buf, cap, "[ECC] double-bit error detected in %s %d\n",
                       ((ev->bit >> 8) & 0xffu) == ABFT_STRUCT_ROW_BLOCK ? "row block" : "row extent", i);
+    case ABFT_EV_TRAIL_CORRECTED:
+      return snprintf(buf, cap, "[ECC] corrected bit %u of trail word %d (%s)\n", ev->bit & 0xffu, i,
+                      trail_record_name((ev->bit >> 8) & 0xffu));
+    case ABFT_EV_TRAIL_DOUBLE:
+      return snprintf(buf, cap, "[ECC] double-bit error detected in trail word %d (%s)\n", i,
+                      trail_record_name((ev->bit >> 8) & 0xffu));
     default: return snprintf(buf, cap, "unknown event %u\n", ev->kind);
   }
 }

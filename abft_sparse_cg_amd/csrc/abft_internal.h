@@ -516,6 +516,27 @@ hipError_t launch_calc_r_until(double *r, const double *w, const double *rr, con
 hipError_t launch_calc_px_until(double *p, const double *r, double *x, const double *rr, const double *rr_new,
                                 double threshold, const double *alpha_ptr, int n, hipStream_t s);
 
+// ---- the guarded iteration on a protected trail (trail_ecc.h; abft_hip_*_trail_iteration_until_dev) ----
+// the scalars of one iteration: records and pair as SECDED slots, 16-byte aligned; `in` is repaired in place
+struct TrailIter {
+  double *in, *pw, *out;
+  double threshold;
+  EventRing ev;
+};
+struct ReduceOutD;
+// launch_fuse_finalize with {p.w, events} published as slots (no peers, no pinned slot)
+hipError_t launch_fuse_finalize_trail(const FuseOut &f, uint32_t nblk, const ReduceOut &big, const FixArgs *fix,
+                                      hipStream_t s);
+// the two halves of the four loops (vecc: codewords; precond: dinv and records of four slots, reduced through od, else
+// pairs through o); x, p of the r half: for the plain loop's choice of walk only
+hipError_t launch_trail_r_until(bool vecc, bool precond, double *r, const double *w, double *dinv, const double *x,
+                                const double *p, const TrailIter &t, int n, const ReduceOut &o, const ReduceOutD &od,
+                                hipStream_t s);
+hipError_t launch_trail_px_until(bool vecc, bool precond, double *x, double *p, const double *r, double *dinv,
+                                 const TrailIter &t, int n, hipStream_t s);
+// XOR mask[4] into the slot at `slot`
+hipError_t launch_flip_trail(double *slot, const uint32_t mask[4], hipStream_t s);
+
 // ---- block right-hand sides (abft_hip_spmm and the *_block vector calls; 1 <= K <= 8) ----
 #define ABFT_MAX_RHS 8
 // the K-wide form of HostSlot: K results of one reduction, published by `seq`

@@ -18,6 +18,7 @@
 #include "ecc_device.h"
 #include "guard_protocol.h"
 #include "struct_ecc.h"
+#include "trail_ecc.h"
 #include "vecc_walk.h"
 
 // native vector types (what __builtin_nontemporal_load accepts)
@@ -5232,7 +5233,6 @@ hipError_t launch_calc_px_precond_until(double *p, const double *r, const double
   ABFT_PRECOND_DISPATCH(calc_px_precond_until_kernel, (), p, r, dinv, x, in, out, threshold, alpha_ptr, n);
   return hipGetLastError();
 }
-#undef ABFT_PRECOND_DISPATCH
 
 // Block forms: one thread per row over the K columns, as the block kernels above; dinv[i] is loaded
 // once per row (one operator for all columns).  A column whose bit is clear keeps its bits (a
@@ -7231,5 +7231,304 @@ hipError_t launch_calc_px_precond_vecc_until(double *x, double *p, const double 
   const int nb = reduce_blocks(n);
   ABFT_VEC_DISPATCH(calc_px_precond_vecc_until_kernel, (), aligned16(x, p, r, dinv), nb, x, p, r, dinv, in, out,
                     threshold, alpha_ptr, n, ev);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------ the protected trail --
+// The guarded iteration on a trail of SECDED slots (trail_ecc.h): siblings of the fold kernels
+// and of the eight guarded halves above, with symbols of their own, so that no instantiation of those moves.  The
+// walks, block_sum, the ticket protocol and the fixed-order folds are the unprotected kernels' own bodies; what
+// differs is the head -- every slot a launch reads is checked -- and the publication, which writes slots.
+// Reduction partials and tickets stay plain: they are written and consumed inside one iteration.
+//
+// A slot is read by every thread of a launch, uniformly.  Its one OWNER per launch is thread 0 of workgroup 0: all
+// repair a flipped bit in their registers, the owner alone stores the clean slot back (a plain store) and queues the
+// event.  A workgroup that loads behind the store-back sees the clean word and decodes the same value.
+
+struct TrailGot { uint64_t bits; int rc; };  // the value of a slot; rc 0 clean, 1 repaired, -1 two flips
+
+__device__ __noinline__ TrailGot trail_cold(uint4 d, uint4 *at, uint32_t ordinal, uint32_t record, bool owner,
+                                            EventRing ev) {
+  const uint32_t w[4] = {d.x, d.y, d.z, d.w};
+  const TrailWord t = trail_decode_at(w, ordinal);  // (a codeword of another ordinal, or word 1 set: as two flips)
+  if (owner && t.rc) {
+    if (t.rc > 0) *at = make_uint4(t.w[0], t.w[1], t.w[2], t.w[3]);
+    push_event(ev, t.rc > 0 ? ABFT_EV_TRAIL_CORRECTED : ABFT_EV_TRAIL_DOUBLE, ordinal,
+               (t.rc > 0 ? t.bit : 0u) | (record << 8), ABFT_FMT_CSR);
+  }
+  return TrailGot{t.bits, t.rc};
+}
+
+// slot `ordinal` of the record at rec (16-byte aligned: the entries check it), checked
+__device__ __forceinline__ TrailGot trail_get(double *rec, int ordinal, uint32_t record, bool owner, EventRing ev) {
+  uint4 *at = reinterpret_cast<uint4 *>(rec) + ordinal;
+  const uint4 d = *at;  // uniform, 16 bytes
+  const uint32_t w[4] = {d.x, d.y, d.z, d.w};
+  if (__builtin_expect((blk_suspect(w) | trail_misplaced(w, (uint32_t)ordinal)) != 0u, 0))
+    return trail_cold(d, at, (uint32_t)ordinal, record, owner, ev);
+  return TrailGot{trail_bits(w), 0};
+}
+
+// The head of every r half on a protected trail (T: TrailPair, TrailQuad): true -> live, with alpha.  false -> the
+// launch ends here, before it touches a vector, a partial or the ticket: frozen, the record handed on repaired and
+// re-encoded by the owner; or two flips in a slot the decision depends on, the record handed on word for word.
+template <class T>
+__device__ __forceinline__ bool trail_r_head(double *in, double *pw, double threshold, double *out, const uint32_t *ev_count,
+                                             EventRing ev, double *alpha) {
+  const bool owner = blockIdx.x == 0 && threadIdx.x == 0;
+  const TrailGot rr = trail_get(in, T::RR, ABFT_TRAIL_START, owner, ev);
+  TrailGot rz = rr;
+  if (T::RZ != T::RR && rr.rc >= 0) rz = trail_get(in, T::RZ, ABFT_TRAIL_START, owner, ev);
+  if (rr.rc < 0 || rz.rc < 0) {
+    if (owner) T::hand_on_raw(in, out);
+    return false;
+  }
+  if (!T::live(rr.bits, threshold)) {
+    if (owner) T::hand_on(rr.bits, rz.bits, out, __hip_atomic_load(ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    return false;
+  }
+  const TrailGot pv = trail_get(pw, 0, ABFT_TRAIL_PW, owner, ev);
+  if (pv.rc < 0) {
+    if (owner) T::hand_on_raw(in, out);
+    return false;
+  }
+  *alpha = T::alpha(rr.bits, rz.bits, pv.bits);
+  return true;
+}
+
+// The head of every x / p half: true -> live, with alpha -- formed from the same two checked slots as the r half's,
+// the same IEEE quotient: there is no alpha scratch word -- and beta.  false: frozen, or two flips in a slot the
+// decision depends on (the new record's r.z among them): x and p keep every bit.
+template <class T>
+__device__ __forceinline__ bool trail_px_head(double *in, double *pw, double *out, double threshold, EventRing ev,
+                                              double *alpha, double *beta) {
+  const bool owner = blockIdx.x == 0 && threadIdx.x == 0;
+  const TrailGot rr = trail_get(in, T::RR, ABFT_TRAIL_START, owner, ev);
+  if (rr.rc < 0 || !T::live(rr.bits, threshold)) return false;
+  TrailGot rz = rr;
+  if (T::RZ != T::RR) rz = trail_get(in, T::RZ, ABFT_TRAIL_START, owner, ev);
+  if (rz.rc < 0) return false;
+  const TrailGot pv = trail_get(pw, 0, ABFT_TRAIL_PW, owner, ev);
+  if (pv.rc < 0) return false;
+  const TrailGot nz = trail_get(out, T::RZ, ABFT_TRAIL_NEXT, owner, ev);
+  if (nz.rc < 0) return false;
+  *alpha = T::alpha(rr.bits, rz.bits, pv.bits);
+  *beta = T::beta(rr.bits, rz.bits, nz.bits);
+  return true;
+}
+
+// reduce_finish with the pair {sum, queued events} published as slots (no peers, no pinned slot: one rank, device
+// scalars): the partial stores, the ticket and the last arriver's fixed-order fold are reduce_finish's
+__device__ __forceinline__ void reduce_finish_trail(double block_value, const ReduceOut &o, double *s_w) {
+  __shared__ uint32_t s_last;
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(o.partials + blockIdx.x, block_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    s_last = reduce_take_ticket(o.ticket);
+  }
+  __syncthreads();
+  if (!s_last) return;
+  const double acc = fold_block_partials<true>(o.partials, gridDim.x, s_w);
+  if (threadIdx.x == 0) {
+    const uint32_t nev = reduce_rearm(o);
+    TrailPair::publish(acc, acc, o.dev_out, nev);
+  }
+}
+
+// reduce_finish_d with the record {r.r, queued events, r.z, 0.0} published as slots
+__device__ __forceinline__ void reduce_finish_d_trail(const double *value, const ReduceOutD &o, double *s_w) {
+  double tot[2];
+  if (!reduce_totals_k<2>(value, o, s_w, tot) || threadIdx.x != 0) return;
+  const uint32_t nev = reduce_rearm(o);
+  TrailQuad::publish(tot[1], tot[0], o.dev_out, nev);
+}
+
+// ---- the folds of the SpMV's fused product: fuse_finalize_kernel and fold_partials_kernel, {p.w, events} as slots ----
+// (fuse_finalize_kernel's sum is restated here, line for line -- the same order and shape, so the same bits, which the
+// clean-parity tests hold --: sharing one inlined body moved an instruction of that kernel)
+__global__ __launch_bounds__(1024) void fuse_finalize_trail_kernel(FuseOut f, uint32_t nblk, FixArgs fx) {
+  __shared__ double s_w[16];
+  if (fx.on) coo_fixup_body(fx);
+  double acc = 0.0;
+  for (uint32_t i = threadIdx.x; i < nblk; i += 16u * 1024u) {
+    double v[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      const uint32_t j = i + (uint32_t)k * 1024u;
+      v[k] = j < nblk ? f.partials[j] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; k += 4) acc += (v[k] + v[k + 1]) + (v[k + 2] + v[k + 3]);
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63u) == 63u) s_w[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    for (int k = 0; k < 16; k++) tot += s_w[k];
+    TrailPair::publish_pw(tot, f.dev_out, *f.ev_count);
+  }
+}
+
+__global__ __launch_bounds__(ABFT_BLOCK) void fold_partials_trail_kernel(const double *__restrict__ parts, uint32_t n,
+                                                                         uint32_t chunk, ReduceOut out, FixArgs fx) {
+  __shared__ double s_w[4];
+  if (fx.on && blockIdx.x == 0) coo_fixup_body(fx);
+  const uint32_t lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
+  double acc = fold_chunk_sum(parts, lo, hi);
+  acc = block_sum(acc, s_w);
+  reduce_finish_trail(acc, out, s_w);
+}
+
+// launch_fuse_finalize's rule: one workgroup up to 8192 partials, the multi-workgroup fold above
+hipError_t launch_fuse_finalize_trail(const FuseOut &f, uint32_t nblk, const ReduceOut &big, const FixArgs *fix,
+                                      hipStream_t s) {
+  FixArgs fx{};
+  if (fix) fx = *fix;
+  if (!fuse_finalize_folds(nblk) || !big.partials) {
+    hipLaunchKernelGGL(fuse_finalize_trail_kernel, dim3(1), dim3(1024), 0, s, f, nblk, fx);
+    return hipGetLastError();
+  }
+  uint32_t chunk;
+  const uint32_t nb = fold_grid(nblk, &chunk);
+  hipLaunchKernelGGL(fold_partials_trail_kernel, dim3(nb), dim3(ABFT_BLOCK), 0, s, f.partials, nblk, chunk, big, fx);
+  return hipGetLastError();
+}
+
+// ---- the eight guarded halves ----
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_trail_until_kernel(double *r, const double *__restrict__ w,
+                                                                        TrailIter t, int n, ReduceOut out) {
+  __shared__ double s_w[4];
+  double alpha;
+  if (!trail_r_head<TrailPair>(t.in, t.pw, t.threshold, t.out, out.ev_count, t.ev, &alpha)) return;
+  double acc = calc_r_walk<VEC>(r, w, alpha, n, r);
+  acc = block_sum(acc, s_w);
+  reduce_finish_trail(acc, out, s_w);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_trail_until_kernel(double *p, const double *__restrict__ r,
+                                                                         double *x, TrailIter t, int n) {
+  double alpha, beta;
+  if (!trail_px_head<TrailPair>(t.in, t.pw, t.out, t.threshold, t.ev, &alpha, &beta)) return;
+  calc_px_walk<VEC>(p, r, x, beta, alpha, n, p, x);
+}
+
+template <int VEC, bool PAIRS>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_precond_trail_until_kernel(double *r, const double *w,
+                                                                                const double *__restrict__ dinv,
+                                                                                TrailIter t, int n, ReduceOutD out) {
+  __shared__ double s_w[16];
+  double alpha;
+  if (!trail_r_head<TrailQuad>(t.in, t.pw, t.threshold, t.out, out.ev_count, t.ev, &alpha)) return;
+  double acc[2] = {0.0, 0.0};
+  calc_xr_precond_walk<VEC, PAIRS, false>(nullptr, r, nullptr, w, dinv, alpha, n, acc);
+  reduce_finish_d_trail(acc, out, s_w);
+}
+
+template <int VEC, bool PAIRS>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_precond_trail_until_kernel(double *__restrict__ p,
+                                                                                 const double *__restrict__ r,
+                                                                                 const double *__restrict__ dinv,
+                                                                                 double *__restrict__ x, TrailIter t,
+                                                                                 int n) {
+  double alpha, beta;
+  if (!trail_px_head<TrailQuad>(t.in, t.pw, t.out, t.threshold, t.ev, &alpha, &beta)) return;
+  calc_p_precond_walk<VEC, PAIRS, true>(p, r, dinv, x, beta, alpha, n);
+}
+
+// on protected vectors: operands as the guarded entries count them (x 1, r 2, p 3, w 4, dinv 5)
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_vecc_trail_until_kernel(double *__restrict__ r,
+                                                                             const double *__restrict__ w, TrailIter t,
+                                                                             int n, ReduceOut out) {
+  __shared__ double s_w[4];
+  double alpha;
+  if (!trail_r_head<TrailPair>(t.in, t.pw, t.threshold, t.out, out.ev_count, t.ev, &alpha)) return;
+  double acc = calc_r_vecc_walk<VEC>(r, w, alpha, n, 2u, 4u, t.ev);
+  acc = block_sum(acc, s_w);
+  reduce_finish_trail(acc, out, s_w);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_vecc_trail_until_kernel(double *__restrict__ x,
+                                                                              double *__restrict__ p,
+                                                                              const double *__restrict__ r, TrailIter t,
+                                                                              int n) {
+  double alpha, beta;
+  if (!trail_px_head<TrailPair>(t.in, t.pw, t.out, t.threshold, t.ev, &alpha, &beta)) return;
+  calc_px_vecc_walk<VEC>(x, p, r, alpha, beta, n, 1u, 3u, 2u, t.ev);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_precond_vecc_trail_until_kernel(double *__restrict__ r,
+                                                                                     const double *__restrict__ w,
+                                                                                     double *__restrict__ dinv,
+                                                                                     TrailIter t, int n,
+                                                                                     ReduceOutD out) {
+  __shared__ double s_w[16];
+  double alpha;
+  if (!trail_r_head<TrailQuad>(t.in, t.pw, t.threshold, t.out, out.ev_count, t.ev, &alpha)) return;
+  double acc[2] = {0.0, 0.0};
+  calc_r_precond_vecc_walk<VEC>(r, w, dinv, alpha, n, 2u, 4u, 5u, t.ev, acc);
+  reduce_finish_d_trail(acc, out, s_w);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_precond_vecc_trail_until_kernel(double *__restrict__ x,
+                                                                                      double *__restrict__ p,
+                                                                                      const double *__restrict__ r,
+                                                                                      double *__restrict__ dinv,
+                                                                                      TrailIter t, int n) {
+  double alpha, beta;
+  if (!trail_px_head<TrailQuad>(t.in, t.pw, t.out, t.threshold, t.ev, &alpha, &beta)) return;
+  calc_px_precond_vecc_walk<VEC>(x, p, r, dinv, alpha, beta, n, 1u, 3u, 2u, 5u, t.ev);
+}
+
+// The r half.  VEC (and PAIRS) as the unprotected guarded launcher of the same loop chooses them, so that the sums
+// are added in the same order.  o: the pair loops' reduction, od: the record loops'.
+hipError_t launch_trail_r_until(bool vecc, bool precond, double *r, const double *w, double *dinv, const double *x,
+                                const double *p, const TrailIter &t, int n, const ReduceOut &o, const ReduceOutD &od,
+                                hipStream_t s) {
+  const int nb = reduce_blocks(n);
+  if (vecc && precond)
+    ABFT_VEC_DISPATCH(calc_r_precond_vecc_trail_until_kernel, (), aligned16(r, w, dinv), nb, r, w, dinv, t, n, od);
+  else if (vecc)
+    ABFT_VEC_DISPATCH(calc_r_vecc_trail_until_kernel, (), aligned16(r, w), nb, r, w, t, n, o);
+  else if (precond) {
+    const bool vec2 = aligned16(r, w), pairs = aligned16(dinv);
+    ABFT_PRECOND_DISPATCH(calc_r_precond_trail_until_kernel, (), r, w, dinv, t, n, od);
+  } else
+    ABFT_VEC_DISPATCH(calc_r_trail_until_kernel, (), aligned16(r, w, x, p), nb, r, w, t, n, o);
+  return hipGetLastError();
+}
+
+hipError_t launch_trail_px_until(bool vecc, bool precond, double *x, double *p, const double *r, double *dinv,
+                                 const TrailIter &t, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+  if (vecc && precond)
+    ABFT_VEC_DISPATCH(calc_px_precond_vecc_trail_until_kernel, (), aligned16(x, p, r, dinv), nb, x, p, r, dinv, t, n);
+  else if (vecc)
+    ABFT_VEC_DISPATCH(calc_px_vecc_trail_until_kernel, (), aligned16(x, p, r), nb, x, p, r, t, n);
+  else if (precond) {
+    const bool vec2 = aligned16(p, r, x), pairs = aligned16(dinv);
+    ABFT_PRECOND_DISPATCH(calc_px_precond_trail_until_kernel, (), p, r, dinv, x, t, n);
+  } else
+    ABFT_VEC_DISPATCH(calc_px_trail_until_kernel, (), aligned16(p, r, x), nb, p, r, x, t, n);
+  return hipGetLastError();
+}
+#undef ABFT_PRECOND_DISPATCH
+
+// XOR `mask` into one stored slot (fault injection into the trail: tests and the CLI's --flip-trail)
+__global__ void flip_trail_kernel(uint4 *slot, uint4 mask) {
+  const uint4 d = *slot;
+  *slot = make_uint4(d.x ^ mask.x, d.y ^ mask.y, d.z ^ mask.z, d.w ^ mask.w);
+}
+
+hipError_t launch_flip_trail(double *slot, const uint32_t mask[4], hipStream_t s) {
+  hipLaunchKernelGGL(flip_trail_kernel, dim3(1), dim3(1), 0, s, reinterpret_cast<uint4 *>(slot),
+                     make_uint4(mask[0], mask[1], mask[2], mask[3]));
   return hipGetLastError();
 }

@@ -77,7 +77,12 @@ typedef enum {
    * word bit in bits 0..7 (a row block's numbered as a COO element's 128) and the kind of word in bits 8..15
    * -- ABFT_STRUCT_ROW_EXTENT or ABFT_STRUCT_ROW_BLOCK --, `index` is the row or the block number */
   ABFT_EV_STRUCT_CORRECTED = 12, /* "[ECC] corrected bit %u of row extent %d" / "... of row block %d"              */
-  ABFT_EV_STRUCT_DOUBLE = 13     /* "[ECC] double-bit error detected in row extent %d" / "... in row block %d" fatal */
+  ABFT_EV_STRUCT_DOUBLE = 13,    /* "[ECC] double-bit error detected in row extent %d" / "... in row block %d" fatal */
+  /* the protected scalar trail (the abft_hip_*_trail_iteration_until_dev entries; fmt = ABFT_FMT_CSR): `index` is
+   * the word's ordinal in its record, `bit` holds the slot's bit in bits 0..7 (numbered as a COO element's 128, the
+   * parity bit 24) and the record in bits 8..15 -- ABFT_TRAIL_START, ABFT_TRAIL_PW or ABFT_TRAIL_NEXT */
+  ABFT_EV_TRAIL_CORRECTED = 14, /* "[ECC] corrected bit %u of trail word %d (start record|p.w pair|next record)"        */
+  ABFT_EV_TRAIL_DOUBLE = 15     /* "[ECC] double-bit error detected in trail word %d (...)"                        fatal */
 } abft_event_kind;
 #define ABFT_STRUCT_ROW_EXTENT 0
 #define ABFT_STRUCT_ROW_BLOCK 1
@@ -894,6 +899,62 @@ int abft_hip_pcg_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *ma
                                           int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
                                           abft_hip_vector *p, abft_hip_vector *w, abft_hip_vector *dinv,
                                           const double *dev_in, double *dev_pw, double *dev_out, double threshold);
+
+/* ---- the guarded iterations on a PROTECTED TRAIL ----
+ * The four single guarded entries above with their scalars under a SECDED code.  A trail word is a SLOT of 128 bits,
+ * two doubles: the COO element {word 0, word 1, value = words 2, 3} of the reference's code in secded form, word 0
+ * holding the word's ordinal in its record in bits 0..23 (record: 0 r.r, 1 events, 2 r.z, 3 the trailing 0.0; the
+ * SpMV's pair: 0 p.w, 1 events) and the check byte in bits 24..31, word 1 zero, words 2 and 3 the double, every bit.
+ * So the records are 4 doubles (the plain loops) or 8 (the preconditioned ones) and the pair is 4; all three must be
+ * 16-byte aligned.  abft_hip_trail_encode / abft_hip_trail_decode are the host's view of them.
+ *
+ * Contracts as the unprotected twin's -- live / frozen on r.r, three kernels behind the SpMV, every refusal before
+ * anything is enqueued, capturable under the same conditions, every matrix the twin accepts -- with these rules:
+ *   - every launch checks every slot it reads, the ordinal under the code against the word's place included (a clean
+ *     codeword in the wrong place, or with word 1 set, counts as two flips).  One flipped bit is repaired in registers by every thread; thread 0 of
+ *     workgroup 0 stores the clean slot back and queues ABFT_EV_TRAIL_CORRECTED.  Hence dev_in is not const.
+ *   - every slot written is a fresh encode of a value moved as an integer (the frozen hand-on included: it hands on
+ *     the repaired bits, re-encoded).  For slots that decode clean the values are the unprotected twin's bits.
+ *   - two flips in a slot the decision depends on (r.r; of a live record r.z; p.w; in the x / p half also the new
+ *     record's r.z) queue ABFT_EV_TRAIL_DOUBLE, fatal, and the launch returns before it touches a vector, a partial or
+ *     the ticket; the r half then hands the record on word for word, unrepaired.  x, r and p keep every bit.
+ *   - no alpha scratch word: the x / p half forms alpha from the same two checked slots as the r half.
+ * The events word and the trailing word of a record are not read on the device; abft_hip_trail_decode checks them.
+ * Reduction partials and tickets stay plain: they live inside one iteration.  A peer board is refused. */
+#define ABFT_TRAIL_START 0u /* the record the iteration starts from */
+#define ABFT_TRAIL_PW 1u    /* the SpMV's pair */
+#define ABFT_TRAIL_NEXT 2u  /* the record the iteration leaves */
+int abft_hip_cg_trail_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                          int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                          abft_hip_vector *p, abft_hip_vector *w, double *dev_rr, double *dev_pw,
+                                          double *dev_rr_new, double threshold);
+int abft_hip_pcg_trail_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                           int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                           abft_hip_vector *p, abft_hip_vector *w, const abft_hip_vector *dinv,
+                                           double *dev_in, double *dev_pw, double *dev_out, double threshold);
+int abft_hip_cg_vecc_trail_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                               int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                               abft_hip_vector *p, abft_hip_vector *w, double *dev_rr, double *dev_pw,
+                                               double *dev_rr_new, double threshold);
+int abft_hip_pcg_vecc_trail_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, const abft_hip_vector *vec,
+                                                int vec_offset, int part, abft_hip_vector *x, abft_hip_vector *r,
+                                                abft_hip_vector *p, abft_hip_vector *w, abft_hip_vector *dinv,
+                                                double *dev_in, double *dev_pw, double *dev_out, double threshold);
+
+/* Host functions: n values -> n slots (2 n doubles), value i with ordinal first_ordinal + i; and back.
+ * decode: values[i] the value (repaired when one bit was flipped), status[i] 0 clean, 1 one flip repaired, -1 two
+ * flips (the value as stored), bits[i] the flipped bit (0..127) when status[i] == 1.  status and bits may be NULL. */
+int abft_hip_trail_encode(const double *values, int n, int first_ordinal, double *slots);
+int abft_hip_trail_decode(const double *slots, int n, double *values, int *status, int *bits);
+/* enqueue an XOR of the given bits (0..127, numbered as the COO element's) into slot `slot` of the device slots at
+ * dev_slots (16-byte aligned), like abft_hip_vector_flip */
+int abft_hip_trail_flip(abft_hip_ctx *ctx, double *dev_slots, int slot, const int *bits, int nbits);
+/* Reach a slot that lives only inside an iteration.  One shot: the next eager protected guarded call enqueues the XOR
+ * of the given bits into slot `ordinal` of `record` (ABFT_TRAIL_START, ABFT_TRAIL_PW, ABFT_TRAIL_NEXT) behind the fold
+ * (stage 1) or behind the r half (stage 2).  A capturing call with an injection armed returns ABFT_ERR_INVALID (and
+ * leaves it armed), and so does a call whose record does not have that ordinal -- the pair has two words, a record of
+ * the plain loops two, of the preconditioned ones four --, before anything is enqueued.  nbits == 0 disarms. */
+int abft_hip_trail_inject_at(abft_hip_ctx *ctx, int stage, int record, int ordinal, const int *bits, int nbits);
 
 /* The guarded iteration for k right-hand sides (block vectors, 1 <= k <= ABFT_MAX_RHS): one iteration of the fused
  * block loop -- W = A P with the k products P . W, then per column r -= alpha w, x += alpha p, p = r + beta p (with

@@ -56,6 +56,12 @@ Also reported per matrix: `best_stride`, the smallest stride within 2 % of the b
 DEFAULT_STRIDE is to be on the 1 M-row matrix), and `frozen_spmv_worst`, stride - 1: the SpMVs a solve can waste
 behind convergence.
 
+--trail-ecc measures what the protected scalar trail costs: cg_solve_device without and with
+trail_ecc=True alternating in one process on the same matrix, in every mode of --modes, at every stride of --strides
+(default 4,16), on the 1 M-row and 10 M-row Laplacians unless --specs says otherwise; ratio_trail_over_plain is against
+the same loop without the keyword.  Goes with --precond jacobi and with --vector-ecc; --out defaults to
+profiles/device_loop_bench_trail.json there.  Without the flag nothing changes.
+
 One JSON file; a line per measurement on stdout as it goes.  Measurement only: nothing here is checked
 (tests/test_gpu_device_loop.py is the check).
 """
@@ -313,6 +319,61 @@ def check_main(a, res):
         del cols, rows, vals
 
 
+TRAIL_SPECS = ("laplace5:1000,1000", "laplace5:3162,3162")
+TRAIL_STRIDES = (4, 16)
+
+
+def trail_main(a, res):
+    """--trail-ecc: cg_solve_device without and with trail_ecc=True, one row per (matrix, mode).  Kinds: ("plain",
+    stride) and ("trail", stride)"""
+    strides = [int(s) for s in (a.strides or ",".join(str(s) for s in TRAIL_STRIDES)).split(",")]
+    res["trail_ecc"] = True
+    res["vector_ecc"] = bool(a.vector_ecc)
+    res["modes"] = a.modes.split(",")
+    for spec in (a.specs or ";".join(TRAIL_SPECS)).split(";"):
+        cols, rows, vals, n = generators.generate(spec)
+        nnz = len(vals)
+        for mode in res["modes"]:
+            ctx = amd.HIPContext(mode, "csr", on_event=lambda ev, fatal: None)
+            A = ctx.create_matrix(cols, rows, vals, n, nnz, layout="stream" if a.vector_ecc else None)
+            vecs = [ctx.create_vector(n) for _ in range(5)]
+            dinv = ctx.jacobi(A, protected=a.vector_ecc) if a.precond == "jacobi" else None
+            kinds = [(kind, st) for st in strides for kind in ("plain", "trail")]
+
+            def run(kind, its):
+                kw = {"trail_ecc": True} if kind[0] == "trail" else {}
+                if a.vector_ecc:
+                    kw["vector_ecc"] = True
+                ctx.upload(vecs[0], generators.reference_rhs(n))  # (a protected solve leaves codewords in b)
+                ctx.upload(vecs[1], np.zeros(n))
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                itr, _ = amd.cg_solve_device(ctx, A, *vecs, max_itrs=its, conv_threshold=THRESHOLD, stride=kind[1],
+                                             precond=dinv, **kw)
+                ctx.synchronize()
+                return (time.perf_counter() - t0) * 1e3, itr
+            for kind in kinds:  # warm-up: first launches, the graphs' instantiation path
+                run(kind, max(kind[1], 5))
+            per = {kind: [] for kind in kinds}
+            for _ in range(a.blocks):
+                for kind in kinds:
+                    ms, itr = run(kind, a.iters)
+                    assert itr == a.iters, (spec, mode, kind, itr)  # every iteration live in both loops
+                    per[kind].append(ms / a.iters)
+            plain = {st: statistics.median(per[("plain", st)]) for st in strides}
+            trail = {st: statistics.median(per[("trail", st)]) for st in strides}
+            row = dict(spec=spec, fmt="csr", mode=mode, layout=ctx.matrix_info(A)[0], precond=a.precond,
+                       vector_ecc=bool(a.vector_ecc), n=n, nnz=nnz,
+                       ms_per_iter_plain={str(st): v for st, v in plain.items()},
+                       ms_per_iter_trail={str(st): v for st, v in trail.items()},
+                       ratio_trail_over_plain={str(st): trail[st] / plain[st] for st in strides},
+                       blocks={"%s:%d" % kind: v for kind, v in per.items()})
+            res["rows"].append(row)
+            print(json.dumps(row), flush=True)
+            ctx.close()
+        del cols, rows, vals
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -326,7 +387,11 @@ def main():
     ap.add_argument("--vector-ecc", action="store_true", help="the loops on protected vectors")
     ap.add_argument("--check-every", type=int, default=0,
                     help="N: cg_solve_device with a residual check every N iterations against the same loop without")
+    ap.add_argument("--trail-ecc", action="store_true",
+                    help="cg_solve_device(trail_ecc=True) against the same loop without the keyword")
     a = ap.parse_args()
+    if a.trail_ecc and (a.rhs or a.check_every):
+        ap.error("--trail-ecc goes with neither --rhs nor --check-every: those loops have no protected trail")
     if a.vector_ecc and a.rhs and a.precond == "jacobi":
         ap.error("--vector-ecc --rhs does not go with --precond jacobi: the protected block loops have no Jacobi form")
     if a.check_every and (a.vector_ecc or a.rhs):
@@ -336,6 +401,13 @@ def main():
     argv = [v for i, v in enumerate(sys.argv) if v != "--out" and (i == 0 or sys.argv[i - 1] != "--out")]
     res = {"cmd": " ".join(argv), "iters": a.iters, "blocks": a.blocks, "threshold": THRESHOLD,
            "precond": a.precond, "rows": []}
+    if a.trail_ecc:
+        a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_trail.json")
+        trail_main(a, res)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        return 0
     if a.check_every:
         a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_check.json")
         check_main(a, res)
