@@ -168,6 +168,11 @@ SIGNATURES = {
     "abft_hip_cg_block_iteration_until_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_double]),
     "abft_hip_cg_block_vecc_iteration_until_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_double]),
     "abft_hip_block_loop_reserve": (C.c_int, [vp, vp, C.c_int]),
+    "abft_hip_cg_block_trail_iteration_until_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
+                                                              C.c_double]),
+    "abft_hip_cg_block_vecc_trail_iteration_until_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
+                                                                   C.c_double]),
+    "abft_hip_block_trail_inject_at": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i32p, C.c_int]),
     "abft_hip_residual_check_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_double]),
     "abft_hip_residual_check_reserve": (C.c_int, [vp]),
     "abft_hip_write_pair": (C.c_int, [vp, vp, C.c_double, C.c_double]),

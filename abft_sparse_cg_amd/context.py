@@ -872,6 +872,34 @@ class HIPContext:
         that has not run it yet (abft_hip_block_loop_reserve); not under capture"""
         check(self.L.abft_hip_block_loop_reserve(self.h, mat.h, k))
 
+    # ---- the block loop on a protected trail (include/abft_hip.h; DESIGN.md section 5t) ----
+    # Records of 2 (2k + 2) doubles, the tail 2 (k + 1): every word a SECDED slot of two doubles under its ordinal in
+    # the record; in_at, pw_at, out_at count doubles and must be even.
+    def cg_block_trail_iteration_until_dev(self, mat, X, R, P, W, k, scalars, in_at, pw_at, out_at, threshold,
+                                           dinv=None):
+        """cg_block_iteration_until_dev on a protected trail (abft_hip_cg_block_trail_iteration_until_dev)"""
+        base = scalars.device_ptr
+        check(self.L.abft_hip_cg_block_trail_iteration_until_dev(self.h, mat.h, X.h, R.h, P.h, W.h,
+                                                                 None if dinv is None else dinv.h, k,
+                                                                 base + 8 * in_at, base + 8 * pw_at,
+                                                                 base + 8 * out_at, threshold))
+
+    def cg_block_vecc_trail_iteration_until_dev(self, mat, X, R, P, W, k, scalars, in_at, pw_at, out_at, threshold):
+        """cg_block_vecc_iteration_until_dev on a protected trail
+        (abft_hip_cg_block_vecc_trail_iteration_until_dev)"""
+        base = scalars.device_ptr
+        check(self.L.abft_hip_cg_block_vecc_trail_iteration_until_dev(self.h, mat.h, X.h, R.h, P.h, W.h, k,
+                                                                      base + 8 * in_at, base + 8 * pw_at,
+                                                                      base + 8 * out_at, threshold))
+
+    def block_trail_inject_at(self, stage, record, ordinal, bits):
+        """trail_inject_at for the two block trail calls, armed apart from it: the next eager one XORs `bits` into
+        slot `ordinal` (r.r[j]: j, r.z[j]: k + j, events: 2k; in the tail P.W[j]: j, events: k) of `record` behind
+        its fold (stage 1) or its r half (stage 2)"""
+        b = np.ascontiguousarray(bits, dtype=np.int32)
+        check(self.L.abft_hip_block_trail_inject_at(self.h, int(stage), int(record), int(ordinal),
+                                                    b.ctypes.data_as(capi.i32p), len(b)))
+
     def residual_check_dev(self, mat, b, x, r, scratch, x_ckpt, trail, chk_at, limit):
         """a whole residual check, enqueue-only, its verdict formed and acted on on the device
         (abft_hip_residual_check_dev): scratch = A x, then trail[chk_at .. chk_at + 3] =
@@ -1509,7 +1537,32 @@ cg_solve_device.__doc__ = _cg_solve_device.__doc__
 
 def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
                           stride=DEFAULT_STRIDE, graph=True, precond=None, vector_ecc=False):
-    """cg_solve_block(fused=True)'s loop with the K alphas, the K betas and the column mask on the device (DESIGN.md
+    """The parameters cg_solve_block_device takes by position or by name, in the order they have always had
+    (tests/test_device_loop_block_vecc_host.py pins the last two).  The public cg_solve_block_device below wraps this
+    function and adds two KEYWORD-ONLY arguments behind them, trail_ecc=False and on_batch=None, the way
+    cg_solve_device does; inspect.signature follows the wrapper to this list."""
+    return _cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs, conv_threshold, on_iteration, stride, graph, precond,
+                                  vector_ecc, False, None)
+
+
+_cg_solve_block_device_positional = cg_solve_block_device
+
+
+@functools.wraps(_cg_solve_block_device_positional, assigned=("__module__", "__name__", "__qualname__"))
+def cg_solve_block_device(*args, trail_ecc=False, on_batch=None, **kw):
+    if not trail_ecc and on_batch is None:
+        return _cg_solve_block_device_positional(*args, **kw)
+    bound = inspect.signature(_cg_solve_block_device_positional).bind(*args, **kw)
+    bound.apply_defaults()
+    return _cg_solve_block_device(*bound.args, trail_ecc, on_batch)
+
+
+def _cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs, conv_threshold, on_iteration, stride, graph, precond,
+                           vector_ecc, trail_ecc, on_batch):
+    """cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
+    stride=DEFAULT_STRIDE, graph=True, precond=None, vector_ecc=False, *, trail_ecc=False, on_batch=None)
+
+    cg_solve_block(fused=True)'s loop with the K alphas, the K betas and the column mask on the device (DESIGN.md
     section 5h): the host looks at the scalars once per batch of `stride` iterations instead of twice per iteration.
 
     The start is cg_solve_block's: copy R <- B, then copy P <- R and dot_block, or with precond (ctx.jacobi(A))
@@ -1535,6 +1588,19 @@ def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1
     hold codewords then: vecc_strip what is downloaded).  Batches, the graph, the download, events, callbacks and the
     return value are as above.  Refused (ValueError, before anything runs) with any precond and for a matrix
     ctx.vecc_supported refuses.  With vector_ecc=False the calls are exactly those made without the argument.
+
+    trail_ecc=True (keyword-only, as on_batch is) keeps the scalar trail under a SECDED code:
+    every word of the records and of the {P.W[K], events} tail is a slot of two doubles under its ordinal in the
+    record, the seed is encoded (ctx.encode_trail), the batches are made of ctx.cg_block_trail_iteration_until_dev /
+    ctx.cg_block_vecc_trail_iteration_until_dev -- the same loops, the same bits --, and after every download the
+    trail is decoded on the host (ctx.report_trail): a slot found with one flipped bit is reported once, two flips
+    raise FatalEvent, and the records are then read in the plain layout.  The device repairs one flipped bit in a
+    slot it reads and reports it (event 14); two flips stop the batch's remaining launches and raise FatalEvent at
+    the download (event 15).  It works with precond, with vector_ecc, with the graph on or off, at every stride;
+    the refusals are those above.
+    on_batch(done, trail) runs after a batch's callbacks with the trail vector; its record `stride` starts the next
+    batch (with trail_ecc: ctx.flip_trail(trail, slot, bits) flips a bit of it).  With trail_ecc=False and
+    on_batch=None the calls are exactly those made without the two arguments.
     No check_every, one GPU."""
     _refuse_structure_ecc(ctx, A, "cg_solve_block_device")
     stride = _whole_stride(stride)
@@ -1577,6 +1643,14 @@ def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1
     last_rr = [rr]
 
     def enqueue(trail, i, pw_at):
+        if trail_ecc:  # the same two loops on slots of two doubles
+            if vector_ecc:
+                ctx.cg_block_vecc_trail_iteration_until_dev(A, X, R, P, W, k, trail, 2 * rec * i, pw_at,
+                                                            2 * rec * (i + 1), conv_threshold)
+            else:
+                ctx.cg_block_trail_iteration_until_dev(A, X, R, P, W, k, trail, 2 * rec * i, pw_at, 2 * rec * (i + 1),
+                                                       conv_threshold, dinv=precond)
+            return
         if vector_ecc:
             ctx.cg_block_vecc_iteration_until_dev(A, X, R, P, W, k, trail, rec * i, pw_at, rec * (i + 1),
                                                   conv_threshold)
@@ -1598,11 +1672,14 @@ def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1
         return True
 
     _device_batches(ctx, max_itrs, stride, graph, rec, k + 1, np.concatenate([rr, rz]), enqueue, record,
-                    before_capture=lambda: ctx.block_loop_reserve(A, k))
+                    before_capture=lambda: ctx.block_loop_reserve(A, k), slots=bool(trail_ecc), on_batch=on_batch)
     if vector_ecc:
         ctx.scrub_vector(X)
         ctx.scrub_vector(B)
     return itrs, last_rr[0]
+
+
+cg_solve_block_device.__doc__ = _cg_solve_block_device.__doc__
 
 
 def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, precond=None):

@@ -103,6 +103,7 @@ struct abft_hip_ctx : LoopState {
   int *bits_dev = nullptr;            // scratch for inject (32 ints)
   double *alpha_dev = nullptr;  // alpha of the deferred update when it was formed on the device
   TrailInjection trail_inject;  // abft_hip_trail_inject_at: armed while nbits != 0
+  TrailInjection block_trail_inject;  // abft_hip_block_trail_inject_at: the block trail calls' own, apart from it
   // block right-hand sides (abft_hip_dot_block, abft_hip_calc_xr_block): allocated by the first such call
   double *bpartials = nullptr;          // 2 * ABFT_MAX_RHS * ABFT_MAX_PARTIALS doubles (the 2K sums of a block check)
   HostSlotK *bslot = nullptr, *bslot_dev = nullptr;  // pinned K-wide result slot, its device alias
@@ -3757,10 +3758,30 @@ extern "C" int abft_hip_trail_inject_at(abft_hip_ctx *ctx, int stage, int record
   return ABFT_OK;
 }
 
+// the block trail calls' injection (abft_hip_cg_block[_vecc]_trail_iteration_until_dev): state of its own, so that an
+// armed single injection never fires in a block call or the other way round.  The ordinal is held against the
+// longest record here (k = ABFT_MAX_RHS) and against the call's own k by the iteration entry
+extern "C" int abft_hip_block_trail_inject_at(abft_hip_ctx *ctx, int stage, int record, int ordinal, const int *bits,
+                                              int nbits) {
+  if (int rc = enter(ctx, 0)) return rc;
+  if (nbits == 0) {
+    ctx->block_trail_inject = TrailInjection{};
+    return ABFT_OK;
+  }
+  if (stage != 1 && stage != 2) return set_err(ABFT_ERR_INVALID, "block_trail_inject_at: stage %d (1: behind the fold, 2: behind the r half)", stage);
+  if (record < 0 || record > (int)ABFT_TRAIL_NEXT) return set_err(ABFT_ERR_INVALID, "block_trail_inject_at: record %d", record);
+  if (ordinal < 0 || ordinal >= guard_block_len(ABFT_MAX_RHS))
+    return set_err(ABFT_ERR_INVALID, "block_trail_inject_at: ordinal %d outside [0,%d)", ordinal, guard_block_len(ABFT_MAX_RHS));
+  TrailInjection inj{};
+  if (int rc = trail_mask("block_trail_inject_at", bits, nbits, inj.mask)) return rc;
+  inj.stage = stage; inj.record = record; inj.ordinal = ordinal; inj.nbits = nbits;
+  ctx->block_trail_inject = inj;
+  return ABFT_OK;
+}
+
 // the armed injection, when this is its stage: enqueued once, then disarmed (iteration_until has refused an ordinal
 // the record does not have, with its other refusals: the slot lies inside the record)
-static int trail_injection(abft_hip_ctx *ctx, int stage, const TrailIter &t) {
-  TrailInjection &inj = ctx->trail_inject;
+static int trail_injection(abft_hip_ctx *ctx, TrailInjection &inj, int stage, const TrailIter &t) {
   if (!inj.nbits || inj.stage != stage) return ABFT_OK;
   double *rec = inj.record == (int)ABFT_TRAIL_START ? t.in : inj.record == (int)ABFT_TRAIL_PW ? t.pw : t.out;
   const uint32_t mask[4] = {inj.mask[0], inj.mask[1], inj.mask[2], inj.mask[3]};
@@ -3961,12 +3982,12 @@ static int iteration_until(abft_hip_ctx *ctx, const char *what, bool vecc, abft_
     // the protected siblings: the same three kernels behind the SpMV, the scalars as slots, no alpha scratch word
     const TrailIter t{const_cast<double *>(dev_in), dev_pw, dev_out, threshold, ctx->ring};
     double *dv = dinv ? dinv->d : nullptr;
-    if (int rc = trail_injection(ctx, 1, t)) return rc;
+    if (int rc = trail_injection(ctx, ctx->trail_inject, 1, t)) return rc;
     {
       KernelTimer kt(ctx, ABFT_K_CALC_XR);
       HIPCHK(launch_trail_r_until(vecc, precond, r->d, w->d, dv, x->d, p->d, t, n, o, od, ctx->stream));
     }
-    if (int rc = trail_injection(ctx, 2, t)) return rc;
+    if (int rc = trail_injection(ctx, ctx->trail_inject, 2, t)) return rc;
     KernelTimer kt(ctx, ABFT_K_CALC_P);
     HIPCHK(launch_trail_px_until(vecc, precond, x->d, p->d, r->d, dv, t, n, ctx->stream));
     return ABFT_OK;
@@ -4126,7 +4147,7 @@ extern "C" int abft_hip_block_loop_reserve(abft_hip_ctx *ctx, abft_hip_matrix *m
 static int block_iteration_until(abft_hip_ctx *ctx, const char *what, bool vecc, abft_hip_matrix *mat,
                                  abft_hip_vector *X, abft_hip_vector *R, abft_hip_vector *P, abft_hip_vector *W,
                                  const abft_hip_vector *dinv, int k, const double *dev_in, double *dev_pw,
-                                 double *dev_out, double threshold) {
+                                 double *dev_out, double threshold, bool trail = false) {
   if (int rc = refuse_protected(what, mat)) return rc;
   if (int rc = enter(ctx, OTHER_VECTORS)) return rc;  // a pending x update applied, the fused product and the learned iteration forgotten
   if (!mat || !X || !R || !P || !W) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
@@ -4141,12 +4162,27 @@ static int block_iteration_until(abft_hip_ctx *ctx, const char *what, bool vecc,
     for (int b = a + 1; b < 4; b++)
       if (!disjoint(four[a], four[b])) return set_err(ABFT_ERR_INVALID, "%s: X, R, P and W overlap", what);
   auto apart = [](const double *a, int na, const double *b, int nb) { return a + na <= b || b + nb <= a; };
-  const int rec = guard_block_len(k), pwl = guard_block_pw_len(k);
+  // (a protected trail: every word a slot of two doubles, 16-byte aligned -- the kernels load a slot at once)
+  const int wide = trail ? ABFT_TRAIL_SLOT : 1;
+  const int rec = wide * guard_block_len(k), pwl = wide * guard_block_pw_len(k);
+  if (trail && (((uintptr_t)dev_in | (uintptr_t)dev_pw | (uintptr_t)dev_out) & 15u))
+    return set_err(ABFT_ERR_INVALID, "%s: a trail slot is not 16-byte aligned", what);
   if (!apart(dev_in, rec, dev_pw, pwl) || !apart(dev_in, rec, dev_out, rec) || !apart(dev_pw, pwl, dev_out, rec))
     return set_err(ABFT_ERR_INVALID, "%s: the scalar records overlap", what);
   if (ctx->capturing && !block_loop_ready(ctx, mat, k))
     return set_err(ABFT_ERR_INVALID, "%s: called under graph capture before the context holds the partials of this "
                    "matrix and k; call abft_hip_block_loop_reserve first", what);
+  if (trail && ctx->capturing && ctx->block_trail_inject.nbits)
+    return set_err(ABFT_ERR_INVALID, "%s: called under graph capture with a trail injection armed "
+                   "(abft_hip_block_trail_inject_at reaches eager calls only)", what);
+  // an armed injection names a slot the records of THIS k must have (record 2k + 2 words, tail k + 1); it stays armed
+  if (trail && ctx->block_trail_inject.nbits) {
+    const TrailInjection &inj = ctx->block_trail_inject;
+    const int len = inj.record == (int)ABFT_TRAIL_PW ? guard_block_pw_len(k) : guard_block_len(k);
+    if (inj.ordinal >= len)
+      return set_err(ABFT_ERR_INVALID, "%s: the armed trail injection names word %d of a record of %d words", what,
+                     inj.ordinal, len);
+  }
   if (int rc = block_loop_alloc(ctx, mat, k)) return rc;
   const int N = (int)mat->csr.n_out;
   {
@@ -4161,12 +4197,30 @@ static int block_iteration_until(abft_hip_ctx *ctx, const char *what, bool vecc,
   o.ticket = ctx->ticket;
   o.ev_count = ctx->ring.count;
   o.dev_out = dev_pw;
+  const double *dv = dinv ? dinv->d : nullptr;
+  if (trail) {
+    // the protected siblings: the same three kernels behind the SpMM, the scalars as slots, no alpha scratch
+    const TrailIter ti{const_cast<double *>(dev_in), dev_pw, dev_out, threshold, ctx->ring};
+    {
+      KernelTimer t(ctx, ABFT_K_DOT);
+      HIPCHK(launch_spmm_fold_trail(ctx->dotparts, mat->csr.nblk, k, o, ctx->stream));
+    }
+    if (int rc = trail_injection(ctx, ctx->block_trail_inject, 1, ti)) return rc;
+    o.dev_out = dev_out;
+    {
+      KernelTimer t(ctx, ABFT_K_CALC_XR);
+      HIPCHK(launch_block_trail_r_until(vecc, R->d, W->d, dv, ti, N, k, o, ctx->stream));
+    }
+    if (int rc = trail_injection(ctx, ctx->block_trail_inject, 2, ti)) return rc;
+    KernelTimer t(ctx, ABFT_K_CALC_P);
+    HIPCHK(launch_block_trail_px_until(vecc, X->d, P->d, R->d, dv, ti, N, k, ctx->stream));
+    return ABFT_OK;
+  }
   {
     KernelTimer t(ctx, ABFT_K_DOT);
     HIPCHK(launch_spmm_fold_dev(ctx->dotparts, mat->csr.nblk, k, o, ctx->stream));
   }
   o.dev_out = dev_out;
-  const double *dv = dinv ? dinv->d : nullptr;
   {
     KernelTimer t(ctx, ABFT_K_CALC_XR);
     if (vecc)
@@ -4206,6 +4260,27 @@ extern "C" int abft_hip_cg_block_vecc_iteration_until_dev(abft_hip_ctx *ctx, abf
                                                           double threshold) {
   return block_iteration_until(ctx, "cg_block_vecc_iteration_until", true, mat, X, R, P, W, nullptr, k, dev_in, dev_pw,
                                dev_out, threshold);
+}
+
+// ---- the two guarded block iterations on a protected trail ----------------
+// block_iteration_until with trail = true: records of 2 (2k + 2) doubles and the tail of 2 (k + 1) are SECDED slots
+// (trail_ecc.h, TrailBlock<K>), the fold and the two halves are the protected siblings, ctx->balpha_dev is neither
+// read nor written.  The start record is repaired in place: not const.
+extern "C" int abft_hip_cg_block_trail_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, abft_hip_vector *X,
+                                                           abft_hip_vector *R, abft_hip_vector *P, abft_hip_vector *W,
+                                                           const abft_hip_vector *dinv, int k, double *dev_in,
+                                                           double *dev_pw, double *dev_out, double threshold) {
+  return block_iteration_until(ctx, "cg_block_trail_iteration_until", false, mat, X, R, P, W, dinv, k, dev_in, dev_pw,
+                               dev_out, threshold, true);
+}
+
+extern "C" int abft_hip_cg_block_vecc_trail_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat,
+                                                                abft_hip_vector *X, abft_hip_vector *R,
+                                                                abft_hip_vector *P, abft_hip_vector *W, int k,
+                                                                double *dev_in, double *dev_pw, double *dev_out,
+                                                                double threshold) {
+  return block_iteration_until(ctx, "cg_block_vecc_trail_iteration_until", true, mat, X, R, P, W, nullptr, k, dev_in,
+                               dev_pw, dev_out, threshold, true);
 }
 
 // what became of the calc_p and calc_r launched ahead: taken over by the caller's calls, or dropped

@@ -700,6 +700,14 @@ hipError_t launch_calc_r_block_vecc_until(double *r, const double *w, const doub
 hipError_t launch_calc_px_block_vecc_until(double *x, double *p, const double *r, const double *in, const double *out,
                                            double threshold, const double *alpha_ptr, int n, int k, EventRing ev,
                                            hipStream_t s);
+// the same four on a protected trail (trail_ecc.h, TrailBlock<K>; abft_hip_cg_block[_vecc]_trail_iteration_until_dev):
+// records of 2 (2k + 2) doubles, the tail 2 (k + 1), 16-byte aligned; t.in is repaired in place; out.dev_out: the tail
+// for the fold, t.out for the r half.  No alpha scratch.  vecc: codewords, no dinv
+hipError_t launch_spmm_fold_trail(const double *parts, uint32_t nblk, int k, const ReduceOutB &out, hipStream_t s);
+hipError_t launch_block_trail_r_until(bool vecc, double *r, const double *w, const double *dinv, const TrailIter &t,
+                                      int n, int k, const ReduceOutB &out, hipStream_t s);
+hipError_t launch_block_trail_px_until(bool vecc, double *x, double *p, const double *r, const double *dinv,
+                                       const TrailIter &t, int n, int k, hipStream_t s);
 // launch_residual_gap with its two sums, the verdict and the events word left in out.dev_out[0..3] (device memory):
 // verdict 1.0 when gap2 <= limit and both sums are finite, else 2.0 (abft_hip_residual_check_dev)
 hipError_t launch_residual_check(const double *b, const double *y, const double *r, int n, double limit,

@@ -7521,6 +7521,244 @@ hipError_t launch_trail_px_until(bool vecc, bool precond, double *x, double *p, 
 }
 #undef ABFT_PRECOND_DISPATCH
 
+// ---- the guarded block iteration on a protected trail ----
+// spmm_fold_dev_kernel<K>, calc_r_block_until_kernel<K, PRECOND>, calc_px_block_until_kernel<K, PRECOND> and the two
+// protected-vector halves on TrailBlock<K> slots (trail_ecc.h): symbols of their own again.  fold_chunk_sum, the four
+// block walks, reduce_totals_k and the ticket are the unprotected kernels' bodies; the heads read slots through
+// trail_get and the publications write slots.  What a launch reads is TrailBlock's read_start / read_scalars: all 2K
+// value slots of the start record; of a live launch P.W[j] -- in the x / p half also the next record's r.z[j] -- of
+// the live columns only.  No alpha scratch: both halves form alpha_j from the same two checked slots.
+
+// trail_get as TrailBlock's reader: (record, ordinal) -> the checked slot of that record, owning nothing (the tail)
+struct TrailBlockGet {
+  double *in, *pw, *out;
+  EventRing ev;
+  __device__ __forceinline__ TrailGot operator()(uint32_t record, int ordinal) const {
+    return trail_get(record == ABFT_TRAIL_START ? in : record == ABFT_TRAIL_PW ? pw : out, ordinal, record, false, ev);
+  }
+};
+
+// The heads spread their slots over the lanes of every wave: ONE LANE, ONE SLOT.  Lane l loads and checks the slot of
+// ordinal l -- the hot test, and trail_cold for the lanes whose slot fails it --, so that all slots of a phase are in
+// flight at once and a head holds four words a lane whatever K is (read one after the other by every thread, the 2K
+// to 4K checked slots of a K = 8 head cost the walks behind them their occupancy).  The values then go to every lane
+// through readlane, into scalar registers, and TrailBlock's rules run on them: the decision is uniform over the
+// wave, and over the grid because every wave decodes the same words.  Each slot keeps one owner per launch: the lane
+// that reads it in wave 0 of workgroup 0 stores a repair back and queues the event.
+struct TrailLane { uint64_t bits; int rc; };  // what a lane holds of its slot (a lane without one: 0, clean)
+
+__device__ __forceinline__ TrailLane trail_lane_get(bool want, double *rec, int ordinal, uint32_t record, bool owner,
+                                                    EventRing ev) {
+  TrailLane g{0u, 0};
+  if (want) {
+    const TrailGot t = trail_get(rec, ordinal, record, owner, ev);
+    g.bits = t.bits;
+    g.rc = t.rc;
+  }
+  return g;
+}
+
+// TrailBlock's reader over the lanes: the slot of ordinal o sits in lane o -- the start record's 2K values in lanes
+// 0 .. 2K - 1; then P.W[j] in lane j and the next record's r.z[j], whose ordinal is K + j, in lane K + j
+struct TrailLaneGet {
+  TrailLane lane;
+  __device__ __forceinline__ TrailGot operator()(uint32_t, int ordinal) const {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)lane.bits, ordinal);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(lane.bits >> 32), ordinal);
+    return TrailGot{(uint64_t)lo | ((uint64_t)hi << 32), __builtin_amdgcn_readlane(lane.rc, ordinal)};
+  }
+};
+
+// spmm_fold_dev_kernel<K> with the last arriver publishing {P.W[K], queued events} as K + 1 fresh slots
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void spmm_fold_trail_kernel(const double *__restrict__ parts, uint32_t n,
+                                                                     uint32_t chunk, ReduceOutB out) {
+  __shared__ double s_w[8 * K];
+  const uint32_t lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
+  double acc[K], tot[K];
+#pragma unroll
+  for (int j = 0; j < K; j++) acc[j] = fold_chunk_sum(parts + (size_t)j * n, lo, hi);
+  if (!reduce_totals_k<K, ReduceOutB, uint32_t>(acc, out, s_w, tot)) return;
+  if (threadIdx.x == 0) {
+    const uint32_t nev = reduce_rearm(out);
+    TrailBlock<K>::publish_pw(tot, out.dev_out, nev);
+  }
+}
+
+hipError_t launch_spmm_fold_trail(const double *parts, uint32_t nblk, int k, const ReduceOutB &out, hipStream_t s) {
+  uint32_t chunk;
+  const uint32_t nb = fold_grid(nblk, &chunk);  // launch_spmm_fold's grid and chunks
+#define ABFT_OP(K) hipLaunchKernelGGL(spmm_fold_trail_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, parts, nblk, chunk, out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+// The head of the r half -> the mask, uniform over the grid, and the K alphas (a frozen column's:
+// +0.0, which the walk's select drops).  0: the launch ends here, before it touches a vector, a partial or the
+// ticket -- no column live, the record handed on repaired and re-encoded by the owner; or two flips in a slot read,
+// the record handed on word for word.  (noescape: as guard_block_r_head)
+template <int K>
+__device__ __forceinline__ uint32_t trail_block_r_head(const TrailIter &t, const uint32_t *ev_count,
+                                                       double *alpha __attribute__((noescape))) {
+  using T = TrailBlock<K>;
+  const bool owner = blockIdx.x == 0 && threadIdx.x == 0, own = blockIdx.x == 0 && threadIdx.x < 64u;
+  const int lane = (int)(threadIdx.x & 63u);
+  const TrailLane start = trail_lane_get(lane < T::VALUES, t.in, lane, ABFT_TRAIL_START, own, t.ev);
+  uint64_t v[T::VALUES];
+  if (!T::read_start(TrailLaneGet{start}, v)) {
+    if (owner) T::hand_on_raw(t.in, t.out);
+    return 0u;
+  }
+  const uint32_t active = (uint32_t)__builtin_amdgcn_readfirstlane((int)T::live_mask(v, t.threshold));
+  if (!active) {
+    if (owner) T::hand_on(v, t.out, __hip_atomic_load(ev_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    return 0u;
+  }
+  const TrailLane live = trail_lane_get(lane < K && ((active >> (lane & 31)) & 1u), t.pw, lane, ABFT_TRAIL_PW, own, t.ev);
+  if (!T::template read_scalars<false>(TrailLaneGet{live}, v, active, alpha, nullptr)) {
+    if (owner) T::hand_on_raw(t.in, t.out);
+    return 0u;
+  }
+  return active;
+}
+
+// The K scalars of a live launch into scalar registers, as guard_block_r_head has them.  The kernels do this behind
+// their `if (!active) return`: done inside the heads, the paths that return 0 with some scalars already formed meet
+// the live path first, and the compiler keeps all of them in vector registers across the walk.
+template <int K>
+__device__ __forceinline__ void trail_block_uniform(double *s __attribute__((noescape))) {
+#pragma unroll
+  for (int j = 0; j < K; j++) s[j] = uniform_f64(s[j]);
+}
+
+// The tail: the sums meet as in guard_block_r_tail; the last block's first thread decodes the start record's value
+// slots again -- owning nothing: no store, no event; a slot the head repaired decodes to the same bits whether or not
+// the owner's store-back is visible yet -- and publishes slots.  (Decoded again instead of kept: 4K registers that
+// would otherwise live across the walk.)
+template <int K, bool PRECOND>
+__device__ __forceinline__ void trail_block_r_tail(const double *acc, uint32_t active, const TrailIter &t,
+                                                   const ReduceOutB &out, double *s_w) {
+  constexpr int S = PRECOND ? 2 * K : K;
+  double tot[S];
+  if (!reduce_totals_k<S, ReduceOutB, uint32_t>(acc, out, s_w, tot) || threadIdx.x != 0) return;
+  uint64_t v[TrailBlock<K>::VALUES];
+  TrailBlock<K>::read_start(TrailBlockGet{t.in, t.pw, t.out, t.ev}, v);
+  TrailBlock<K>::template publish<PRECOND>(tot, active, v, out.dev_out, reduce_rearm(out));
+}
+
+// The head of the x / p half -> the mask, and when it is not 0 the K alphas and betas.  0: nothing live, or two flips
+// in a slot read (the next record's r.z of a live column among them): X and P keep every bit.
+template <int K>
+__device__ __forceinline__ uint32_t trail_block_px_head(const TrailIter &t, double *alpha __attribute__((noescape)),
+                                                        double *beta __attribute__((noescape))) {
+  using T = TrailBlock<K>;
+  const bool own = blockIdx.x == 0 && threadIdx.x < 64u;
+  const int lane = (int)(threadIdx.x & 63u);
+  const TrailLane start = trail_lane_get(lane < T::VALUES, t.in, lane, ABFT_TRAIL_START, own, t.ev);
+  uint64_t v[T::VALUES];
+  if (!T::read_start(TrailLaneGet{start}, v)) return 0u;
+  const uint32_t active = (uint32_t)__builtin_amdgcn_readfirstlane((int)T::live_mask(v, t.threshold));
+  if (!active) return 0u;
+  const bool tail = lane < K;  // lanes 0 .. K - 1: P.W[lane]; lanes K .. 2K - 1: the next record's r.z[lane - K]
+  const bool want = lane < T::VALUES && ((active >> ((tail ? lane : lane - K) & 31)) & 1u);
+  const TrailLane live = trail_lane_get(want, tail ? t.pw : t.out, lane, tail ? ABFT_TRAIL_PW : ABFT_TRAIL_NEXT, own, t.ev);
+  if (!T::template read_scalars<true>(TrailLaneGet{live}, v, active, alpha, beta)) return 0u;
+  return active;
+}
+
+template <int K, bool PRECOND>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_trail_until_kernel(double *__restrict__ r,
+                                                                              const double *__restrict__ w,
+                                                                              const double *__restrict__ dinv,
+                                                                              TrailIter t, int n, ReduceOutB out) {
+  constexpr int S = PRECOND ? 2 * K : K;
+  __shared__ double s_w[8 * S];
+  double alpha[K], acc[S] = {};
+  const uint32_t active = trail_block_r_head<K>(t, out.ev_count, alpha);
+  if (!active) return;
+  trail_block_uniform<K>(alpha);
+  calc_r_block_walk<K, PRECOND>(r, w, dinv, alpha, active, n, acc);
+  trail_block_r_tail<K, PRECOND>(acc, active, t, out, s_w);
+}
+
+template <int K, bool PRECOND>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_trail_until_kernel(double *__restrict__ x,
+                                                                               double *__restrict__ p,
+                                                                               const double *__restrict__ r,
+                                                                               const double *__restrict__ dinv,
+                                                                               TrailIter t, int n) {
+  double alpha[K], beta[K];
+  const uint32_t active = trail_block_px_head<K>(t, alpha, beta);
+  if (!active) return;
+  trail_block_uniform<K>(alpha);
+  trail_block_uniform<K>(beta);
+  calc_px_block_walk<K, PRECOND>(x, p, r, dinv, alpha, beta, active, n);
+}
+
+// on protected block vectors: operands X 1, R 2, P 3, W 4, as calc_r_block_vecc_until_kernel counts them
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_r_block_vecc_trail_until_kernel(double *__restrict__ r,
+                                                                                   const double *__restrict__ w,
+                                                                                   TrailIter t, int n, ReduceOutB out) {
+  __shared__ double s_w[8 * K];
+  double alpha[K], acc[K] = {};
+  const uint32_t active = trail_block_r_head<K>(t, out.ev_count, alpha);
+  if (!active) return;
+  trail_block_uniform<K>(alpha);
+  calc_r_block_vecc_walk<K>(r, w, alpha, active, n, 2u, 4u, t.ev, acc);
+  trail_block_r_tail<K, false>(acc, active, t, out, s_w);
+}
+
+template <int K>
+__global__ __launch_bounds__(ABFT_BLOCK) void calc_px_block_vecc_trail_until_kernel(double *__restrict__ x,
+                                                                                    double *__restrict__ p,
+                                                                                    const double *__restrict__ r,
+                                                                                    TrailIter t, int n) {
+  double alpha[K], beta[K];
+  const uint32_t active = trail_block_px_head<K>(t, alpha, beta);
+  if (!active) return;
+  trail_block_uniform<K>(alpha);
+  trail_block_uniform<K>(beta);
+  calc_px_block_vecc_walk<K>(x, p, r, alpha, beta, active, n, 1u, 3u, 2u, t.ev);
+}
+
+// out.dev_out is t.out.  dinv == nullptr: the plain form; vecc: codewords (no dinv)
+hipError_t launch_block_trail_r_until(bool vecc, double *r, const double *w, const double *dinv, const TrailIter &t,
+                                      int n, int k, const ReduceOutB &out, hipStream_t s) {
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K)                                                                                                     \
+  if (vecc)                                                                                                            \
+    hipLaunchKernelGGL(calc_r_block_vecc_trail_until_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, t, n, out);    \
+  else if (dinv)                                                                                                       \
+    hipLaunchKernelGGL((calc_r_block_trail_until_kernel<K, true>), dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, dinv, t, n, \
+                       out);                                                                                           \
+  else                                                                                                                 \
+    hipLaunchKernelGGL((calc_r_block_trail_until_kernel<K, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, r, w, dinv, t, n, \
+                       out)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
+hipError_t launch_block_trail_px_until(bool vecc, double *x, double *p, const double *r, const double *dinv,
+                                       const TrailIter &t, int n, int k, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int nb = reduce_blocks(n);
+#define ABFT_OP(K)                                                                                                     \
+  if (vecc)                                                                                                            \
+    hipLaunchKernelGGL(calc_px_block_vecc_trail_until_kernel<K>, dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, t, n);     \
+  else if (dinv)                                                                                                       \
+    hipLaunchKernelGGL((calc_px_block_trail_until_kernel<K, true>), dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, dinv, t, \
+                       n);                                                                                             \
+  else                                                                                                                 \
+    hipLaunchKernelGGL((calc_px_block_trail_until_kernel<K, false>), dim3(nb), dim3(ABFT_BLOCK), 0, s, x, p, r, dinv, t, \
+                       n)
+  ABFT_BLOCK_K_DISPATCH(ABFT_OP)
+#undef ABFT_OP
+  return hipGetLastError();
+}
+
 // XOR `mask` into one stored slot (fault injection into the trail: tests and the CLI's --flip-trail)
 __global__ void flip_trail_kernel(uint4 *slot, uint4 mask) {
   const uint4 d = *slot;

@@ -16,7 +16,12 @@
 // On top of the slot: TrailSingle<QUAD>, the protected twin of GuardSingle<QUAD> (guard_protocol.h).  It decodes the
 // slots a decision depends on and answers with GuardSingle's own functions on the decoded values, so for values that
 // decode clean it gives guard_protocol.h's bits by construction; every slot it writes is a fresh encode of a value
-// that is moved as an integer (a NaN's payload and -0.0 survive).  The block record is out of scope.
+// that is moved as an integer (a NaN's payload and -0.0 survive).
+//
+// TrailBlock<K> is the same twin of GuardBlock<K>: every word of the block record {r.r[K],
+// r.z[K], events, 0.0} a slot under GuardBlock's own ordinal (RR + j = j, RZ + j = K + j, EV = 2K, the trailing word
+// 2K + 1), in the SpMM's tail P.W[j] under j and the events word under K.  A record is 2 (2K + 2) doubles, the tail
+// 2 (K + 1).
 #pragma once
 #include <stdint.h>
 
@@ -165,3 +170,116 @@ template <bool QUAD> struct TrailSingle {
 };
 using TrailPair = TrailSingle<false>;
 using TrailQuad = TrailSingle<true>;
+
+// ---- the protected twin of GuardBlock<K> ----
+// What a launch knows of its start record once the slots are decoded: v[2K], the bits of r.r[K] then r.z[K] (the
+// record's own order).  GuardBlock's functions answer on a plain record rebuilt from them.
+// Slots come through get(record, ordinal) -> {bits, rc} (rc < 0: two flips): the kernels' checked loads (one lane a
+// slot, the values broadcast: kernels.hip), a host's decode.  The read_* rules are the whole of what a launch reads: all 2K value slots of the start record,
+// whatever is live; of the P.W tail and of the next record only a LIVE column's slot -- a frozen column's P.W is
+// not a decision (the next fold overwrites it with a fresh encode), so damage there must not stop anything.
+template <int K> struct TrailBlock {
+  using G = GuardBlock<K>;
+  enum { RR = G::RR, RZ = G::RZ, EV = G::EV, LEN = G::LEN, PW_LEN = G::PW_LEN, VALUES = 2 * K,
+         DOUBLES = ABFT_TRAIL_SLOT * G::LEN, PW_DOUBLES = ABFT_TRAIL_SLOT * G::PW_LEN };
+  // false: two flips in one of them; reading stops there (one event)
+  template <class Get> static __device__ __forceinline__ bool read_start(Get &&get, uint64_t *v) {
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < VALUES; i++) {
+      v[i] = 0u;
+      if (ok) {
+        const auto g = get(ABFT_TRAIL_START, i);
+        v[i] = g.bits;
+        ok = g.rc >= 0;
+      }
+    }
+    return ok;
+  }
+  // The scalars of a launch with a live column, column by column: P.W[j] -- BETAS (the x / p half): then the next
+  // record's r.z[j] -- of a LIVE column j, and its alpha_j (beta_j) at once: the slots' values need not be kept.  A frozen column's slots are not read; its alpha and beta are +0.0, which the walks' selects
+  // drop.  false: two flips in a slot read; reading stops there (one event).
+  template <bool BETAS, class Get>
+  static __device__ __forceinline__ bool read_scalars(Get &&get, const uint64_t *v, uint32_t active, double *alpha,
+                                                      double *beta) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      alpha[j] = 0.0;
+      if (BETAS) beta[j] = 0.0;
+      if (ok && ((active >> j) & 1u)) {
+        const auto pw = get(ABFT_TRAIL_PW, j);
+        ok = pw.rc >= 0;
+        if (ok) alpha[j] = TrailBlock::alpha(v, pw.bits, j);
+        if (BETAS && ok) {
+          const auto nz = get(ABFT_TRAIL_NEXT, RZ + j);
+          ok = nz.rc >= 0;
+          if (ok) beta[j] = TrailBlock::beta(v, nz.bits, j);
+        }
+      }
+    }
+    return ok;
+  }
+  // decoded values -> a plain record GuardBlock reads (the events and trailing words are not decisions: 0)
+  static __device__ __forceinline__ void plain(const uint64_t *v, double *rec) {
+#pragma unroll
+    for (int i = 0; i < VALUES; i++) guard_put(rec, i, v[i]);
+    rec[EV] = 0.0;
+    rec[LEN - 1] = 0.0;
+  }
+  static __device__ __forceinline__ uint32_t live_mask(const uint64_t *v, double threshold) {
+    double rec[LEN];
+    plain(v, rec);
+    return G::live_mask(rec, threshold);
+  }
+  // alpha_j = r.z[j] / P.W[j], beta_j = the next record's r.z[j] / r.z[j]: GuardBlock's quotients, the same in both halves
+  static __device__ __forceinline__ double alpha(const uint64_t *v, uint64_t pw, int j) {
+    double rec[LEN], p[K];
+    plain(v, rec);
+#pragma unroll
+    for (int i = 0; i < K; i++) guard_put(p, i, pw);
+    return G::alpha(rec, p, j);
+  }
+  static __device__ __forceinline__ double beta(const uint64_t *v, uint64_t next_rz, int j) {
+    double in[LEN], out[LEN];
+    plain(v, in);
+#pragma unroll
+    for (int i = 0; i < LEN; i++) guard_put(out, i, next_rz);
+    return G::beta(in, out, j);
+  }
+  // a plain record as GuardBlock left it -> slots, every word a fresh encode of its bits
+  static __device__ __forceinline__ void put_record(const double *plain_out, double *out) {
+#pragma unroll
+    for (int i = 0; i < LEN; i++) {
+      const uint64_t word = guard_word(plain_out, i);
+      trail_put(out, i, word);
+    }
+  }
+  // no column live: the decoded (repaired) words through GuardBlock::hand_on
+  static __device__ __forceinline__ void hand_on(const uint64_t *v, double *out, uint32_t nev) {
+    double in[LEN], plain_out[LEN];
+    plain(v, in);
+    G::hand_on(in, plain_out, nev);
+    put_record(plain_out, out);
+  }
+  // two flips in a slot the decision depends on: the record word for word, unrepaired
+  static __device__ __forceinline__ void hand_on_raw(const double *in, double *out) {
+    for (int i = 0; i < DOUBLES; i++) guard_put(out, i, guard_word(in, i));
+  }
+  // the record behind a live launch: GuardBlock::publish<PRECOND> (tot as there), a frozen column's words the
+  // repaired integers
+  template <bool PRECOND>
+  static __device__ __forceinline__ void publish(const double *tot, uint32_t active, const uint64_t *v, double *out,
+                                                 uint32_t nev) {
+    double in[LEN], plain_out[LEN];
+    plain(v, in);
+    G::template publish<PRECOND>(tot, active, in, plain_out, nev);
+    put_record(plain_out, out);
+  }
+  // the SpMM's tail {P.W[K], queued events}
+  static __device__ __forceinline__ void publish_pw(const double *tot, double *out, uint32_t nev) {
+#pragma unroll
+    for (int j = 0; j < K; j++) trail_put_value(out, j, tot[j]);
+    trail_put_value(out, K, (double)nev);
+  }
+};

@@ -1019,6 +1019,35 @@ int abft_hip_cg_block_vecc_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matri
  * covered), so that the iteration can be captured on a fresh context.  Eager only: refused under graph capture. */
 int abft_hip_block_loop_reserve(abft_hip_ctx *ctx, abft_hip_matrix *mat, int k);
 
+/* The two guarded block iterations on a PROTECTED TRAIL: abft_hip_cg_block_iteration_until_dev
+ * and abft_hip_cg_block_vecc_iteration_until_dev with every scalar word a SECDED slot of two doubles, as in the single
+ * trail entries above.  A slot holds the word's ordinal in its record -- r.r of column j: j, its r.z: k + j, the
+ * events word 2k, the trailing word 2k + 1; in dev_pw P.W of column j: j, the events word k -- so a record is
+ * 2 (2k + 2) doubles and dev_pw 2 (k + 1); all three must be 16-byte aligned (ABFT_ERR_INVALID otherwise) and apart.
+ * Every launch of both halves checks all 2k value slots of the start record; a launch with a live column also P.W of
+ * the LIVE columns and, in the x / p half, the next record's r.z of the live columns.  A frozen column's P.W slot is
+ * not read.  One flipped bit: repaired by every thread in registers, stored back by one, one ABFT_EV_TRAIL_CORRECTED
+ * event (index the ordinal, bit | record << 8); outputs are the clean call's.  Two flips in a slot read (a codeword
+ * under the wrong ordinal counts as two): one ABFT_EV_TRAIL_DOUBLE event, the launch returns before it touches a
+ * vector, a partial or the ticket, the r half hands the start record on word for word.  No column live: the record is
+ * handed on repaired and re-encoded, nothing else is touched.  dev_in is repaired in place, hence not const.  The
+ * context's alpha scratch is not used: the x / p half forms alpha_j from the same two checked slots.
+ * Refusals are those of the plain entries, all before anything is enqueued; under capture
+ * abft_hip_block_loop_reserve comes first. */
+int abft_hip_cg_block_trail_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, abft_hip_vector *X,
+                                                abft_hip_vector *R, abft_hip_vector *P, abft_hip_vector *W,
+                                                const abft_hip_vector *dinv, int k, double *dev_in, double *dev_pw,
+                                                double *dev_out, double threshold);
+int abft_hip_cg_block_vecc_trail_iteration_until_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat, abft_hip_vector *X,
+                                                     abft_hip_vector *R, abft_hip_vector *P, abft_hip_vector *W, int k,
+                                                     double *dev_in, double *dev_pw, double *dev_out, double threshold);
+/* abft_hip_trail_inject_at for the two entries above, with state of its own: armed for the next eager block trail
+ * call, stage 1 behind the fold, stage 2 behind the r half.  ordinal in [0, 2 ABFT_MAX_RHS + 2); the iteration entry
+ * refuses an ordinal its records do not have for its k (record 2k + 2 words, dev_pw k + 1), naming the word and the
+ * record length, and any armed injection under capture; it stays armed then.  nbits == 0 disarms.  An injection
+ * armed through abft_hip_trail_inject_at does not fire in a block call, nor this one in a single call. */
+int abft_hip_block_trail_inject_at(abft_hip_ctx *ctx, int stage, int record, int ordinal, const int *bits, int nbits);
+
 /* ---- a residual check whose verdict is formed and acted on on the device ----
  * abft_hip_residual_gap for the device-scalar loop: enqueue-only and capturable, nothing comes back to the host but
  * what it downloads from dev_chk later.  Three things in a line on the context's stream:

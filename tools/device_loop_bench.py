@@ -62,6 +62,11 @@ trail_ecc=True alternating in one process on the same matrix, in every mode of -
 the same loop without the keyword.  Goes with --precond jacobi and with --vector-ecc; --out defaults to
 profiles/device_loop_bench_trail.json there.  Without the flag nothing changes.
 
+--trail-ecc --rhs K[,K...] [--vector-ecc] measures the same for the block loop:
+cg_solve_block_device without and with trail_ecc=True alternating in one process, on the K seeded right-hand sides of
+--rhs and the streaming layout, with the kinds, strides, specs and modes of --trail-ecc; the per-column counts are
+asserted equal.  --out defaults to profiles/device_loop_bench_block_trail.json there.  --check-every stays refused.
+
 One JSON file; a line per measurement on stdout as it goes.  Measurement only: nothing here is checked
 (tests/test_gpu_device_loop.py is the check).
 """
@@ -374,6 +379,62 @@ def trail_main(a, res):
         del cols, rows, vals
 
 
+def block_trail_main(a, res):
+    """--trail-ecc --rhs: cg_solve_block_device without and with trail_ecc=True, one row per (matrix, mode, K).  Kinds,
+    strides, specs and modes as trail_main's"""
+    strides = [int(s) for s in (a.strides or ",".join(str(s) for s in TRAIL_STRIDES)).split(",")]
+    res["trail_ecc"] = True
+    res["vector_ecc"] = bool(a.vector_ecc)
+    res["rhs"] = [int(k) for k in a.rhs.split(",")]
+    res["modes"] = a.modes.split(",")
+    for spec in (a.specs or ";".join(TRAIL_SPECS)).split(";"):
+        cols, rows, vals, n = generators.generate(spec)
+        nnz = len(vals)
+        for mode in res["modes"]:
+            ctx = amd.HIPContext(mode, "csr", on_event=lambda ev, fatal: None)
+            A = ctx.create_matrix(cols, rows, vals, n, nnz, layout="stream")
+            dinv = ctx.jacobi(A) if a.precond == "jacobi" else None
+            for k in res["rhs"]:
+                vecs = [ctx.create_block(n, k) for _ in range(5)]
+                b = np.random.default_rng(7).random((n, k)) + 0.5
+                kinds = [(kind, st) for st in strides for kind in ("plain", "trail")]
+
+                def run(kind, its):
+                    kw = {"trail_ecc": True} if kind[0] == "trail" else {}
+                    if a.vector_ecc:
+                        kw["vector_ecc"] = True
+                    ctx.upload(vecs[0], b)  # (a protected solve leaves codewords in B)
+                    ctx.upload(vecs[1], np.zeros((n, k)))
+                    ctx.synchronize()
+                    t0 = time.perf_counter()
+                    itrs, _ = amd.cg_solve_block_device(ctx, A, *vecs, max_itrs=its, conv_threshold=THRESHOLD,
+                                                        stride=kind[1], precond=dinv, **kw)
+                    ctx.synchronize()
+                    return (time.perf_counter() - t0) * 1e3, list(itrs)
+                for kind in kinds:  # warm-up: first launches, the graphs' instantiation path
+                    run(kind, max(kind[1], 5))
+                per = {kind: [] for kind in kinds}
+                for _ in range(a.blocks):
+                    for kind in kinds:
+                        ms, itrs = run(kind, a.iters)
+                        assert itrs == [a.iters] * k, (spec, mode, k, kind, itrs)  # every column live in both loops
+                        per[kind].append(ms / a.iters)
+                plain = {st: statistics.median(per[("plain", st)]) for st in strides}
+                trail = {st: statistics.median(per[("trail", st)]) for st in strides}
+                row = dict(spec=spec, fmt="csr", mode=mode, layout=ctx.matrix_info(A)[0], precond=a.precond,
+                           vector_ecc=bool(a.vector_ecc), rhs=k, n=n, nnz=nnz,
+                           ms_per_iter_plain={str(st): v for st, v in plain.items()},
+                           ms_per_iter_trail={str(st): v for st, v in trail.items()},
+                           ratio_trail_over_plain={str(st): trail[st] / plain[st] for st in strides},
+                           blocks={"%s:%d" % kind: v for kind, v in per.items()})
+                res["rows"].append(row)
+                print(json.dumps(row), flush=True)
+                for v in vecs:
+                    ctx.destroy_vector(v)
+            ctx.close()
+        del cols, rows, vals
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -390,8 +451,8 @@ def main():
     ap.add_argument("--trail-ecc", action="store_true",
                     help="cg_solve_device(trail_ecc=True) against the same loop without the keyword")
     a = ap.parse_args()
-    if a.trail_ecc and (a.rhs or a.check_every):
-        ap.error("--trail-ecc goes with neither --rhs nor --check-every: those loops have no protected trail")
+    if a.trail_ecc and a.check_every:
+        ap.error("--trail-ecc does not go with --check-every: the checked loop has no protected trail")
     if a.vector_ecc and a.rhs and a.precond == "jacobi":
         ap.error("--vector-ecc --rhs does not go with --precond jacobi: the protected block loops have no Jacobi form")
     if a.check_every and (a.vector_ecc or a.rhs):
@@ -401,6 +462,13 @@ def main():
     argv = [v for i, v in enumerate(sys.argv) if v != "--out" and (i == 0 or sys.argv[i - 1] != "--out")]
     res = {"cmd": " ".join(argv), "iters": a.iters, "blocks": a.blocks, "threshold": THRESHOLD,
            "precond": a.precond, "rows": []}
+    if a.trail_ecc and a.rhs:
+        a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_block_trail.json")
+        block_trail_main(a, res)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        return 0
     if a.trail_ecc:
         a.out = a.out or os.path.join(ROOT, "profiles", "device_loop_bench_trail.json")
         trail_main(a, res)
