@@ -26,6 +26,7 @@ EV_STRUCT_CORRECTED, EV_STRUCT_DOUBLE = 12, 13  # protected row structure: bit =
 STRUCT_ROW, STRUCT_BLOCK = 0, 1  # the kind of a structure word
 EV_TRAIL_CORRECTED, EV_TRAIL_DOUBLE = 14, 15  # protected scalar trail: index = ordinal, bit = slot bit | record << 8
 TRAIL_START, TRAIL_PW, TRAIL_NEXT = 0, 1, 2  # the record of a trail event
+EV_MATRIX_DIGEST = 16  # a stored array of the matrix lost its armed digest: index = the segment kind, fatal
 MAX_RHS = 8  # block right-hand sides per call (include/abft_hip.h)
 
 u32p = C.POINTER(C.c_uint32)
@@ -209,6 +210,14 @@ SIGNATURES = {
     "abft_hip_graph_end": (C.c_int, [vp, vpp]),
     "abft_hip_graph_launch": (C.c_int, [vp]),
     "abft_hip_graph_destroy": (C.c_int, [vp]),
+    "abft_hip_segment_name": (C.c_char_p, [C.c_uint32]),
+    "abft_hip_matrix_segments": (C.c_int, [vp, u32p, C.POINTER(C.c_uint64), C.c_int, i32p]),
+    "abft_hip_matrix_digest": (C.c_int, [vp, vp, C.POINTER(C.c_uint64), C.c_int]),
+    "abft_hip_matrix_digest_arm": (C.c_int, [vp, vp]),
+    "abft_hip_matrix_verify": (C.c_int, [vp, vp, i32p, u32p, C.c_int]),
+    "abft_hip_matrix_verify_dev": (C.c_int, [vp, vp]),
+    "abft_hip_matrix_read_segment": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64]),
+    "abft_hip_matrix_flip_segment": (C.c_int, [vp, vp, C.c_uint32, C.c_uint64, i32p, C.c_int]),
     "abft_hip_drain_events": (C.c_int, [vp, C.POINTER(Event), C.c_int, i32p, i32p]),
     "abft_hip_event_capacity": (C.c_int, []),
     "abft_hip_pending_events": (C.c_int, [vp]),
@@ -271,7 +280,39 @@ def check(rc):
 
 def is_fatal(kind):
     """same rule as abft_event_is_fatal"""
-    return kind in (1, 4, EV_VEC_DOUBLE, EV_STRUCT_DOUBLE, EV_TRAIL_DOUBLE) or 5 <= kind <= 9
+    return kind in (1, 4, EV_VEC_DOUBLE, EV_STRUCT_DOUBLE, EV_TRAIL_DOUBLE, EV_MATRIX_DIGEST) or 5 <= kind <= 9
+
+
+# the segment kinds of the matrix digests (csrc/matrix_digest.h, ABFT_SEG_*), by name: asked of the library once
+SEG_COUNT = 64  # room for every kind the list can hold
+_seg_names = None
+
+
+def segment_names():
+    """-> the names of the segment kinds, kind k at index k ("none" at 0)"""
+    global _seg_names
+    if _seg_names is None:
+        names, k = [], 0
+        while True:
+            s = load().abft_hip_segment_name(k)
+            if s is None:
+                break
+            names.append(s.decode())
+            k += 1
+        _seg_names = names
+    return _seg_names
+
+
+def segment_name(kind):
+    names = segment_names()
+    return names[kind] if 0 <= kind < len(names) else "?"
+
+
+def segment_kind(name):
+    names = segment_names()
+    if name not in names or name == "none":
+        raise ValueError("unknown matrix segment %r (one of %s)" % (name, ", ".join(names[1:])))
+    return names.index(name)
 
 
 def format_event(kind, index, bit, fmt):

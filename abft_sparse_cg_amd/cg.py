@@ -87,12 +87,22 @@ Additional options of this build:
                               Flip bit(s) B (0-127) of word W (0 r.r, 1 events) of the
                               record handed to the batch after iteration I's; needs
                               --trail-ecc secded (may be repeated)
+      --verify-matrix   M     Verify the digests of every stored array of the matrix
+                              every M iterations (M >= 1) and before stopping; a
+                              mismatch prints its line and exits 1
+      --flip-matrix I:S:W:B[,B...]
+                              After iteration I (with --device-loop: after I's batch),
+                              flip bit(s) B of the stored array S (cols, vals, pal,
+                              wbase, ...: a segment the matrix has), counted from bit 0
+                              of its 32-bit word W (bit 40 is bit 8 of word W + 1) (may
+                              be repeated)
 
 """
 
 
 FLIP_VECTOR_MSG = "Invalid --flip-vector (want ITER:VEC:INDEX:BIT[,BIT...], VEC one of x, r, p)"
 FLIP_STRUCTURE_MSG = "Invalid --flip-structure (want ITER:row|block:INDEX:BIT[,BIT...])"
+FLIP_MATRIX_MSG = "Invalid --flip-matrix (want ITER:SEGMENT:WORD:BIT[,BIT...])"
 FLIP_TRAIL_MSG = "Invalid --flip-trail (want ITER:WORD:BIT[,BIT...], WORD 0 or 1, bits 0-127)"
 
 
@@ -106,7 +116,7 @@ def parse(argv):
              mode="none", flips=0, kind="ANY", seed=None, quiet=False, flip_at=None, fmt="csr", list=False,
              rhs=1, check_every=0, check_tol=1e-7, max_rollbacks=3, flip_vector=[], precond="none",
              vector_ecc="none", block_fused=False, device_loop=0, structure_ecc="none", flip_structure=[],
-             trail_ecc="none", flip_trail=[])
+             trail_ecc="none", flip_trail=[], verify_matrix=0, flip_matrix=[])
 
     def num(s, conv):
         try:
@@ -234,6 +244,19 @@ def parse(argv):
             if flip[0] < 0 or flip[1] not in (0, 1) or not all(0 <= b < 128 for b in flip[2]):
                 fail(FLIP_TRAIL_MSG)
             o["flip_trail"] = o["flip_trail"] + [flip]
+        elif a == "--verify-matrix":
+            o["verify_matrix"] = num(arg("Invalid --verify-matrix interval (want a whole number >= 1)"), int)
+            if o["verify_matrix"] < 1:
+                fail("Invalid --verify-matrix interval (want a whole number >= 1)")
+        elif a == "--flip-matrix":
+            try:
+                itr, seg, word, bits = arg(FLIP_MATRIX_MSG).split(":")
+                flip = (int(itr), seg, int(word), [int(b) for b in bits.split(",")])
+            except ValueError:
+                fail(FLIP_MATRIX_MSG)
+            if flip[0] < 0 or not flip[1] or flip[2] < 0 or not all(b >= 0 for b in flip[3]):
+                fail(FLIP_MATRIX_MSG)
+            o["flip_matrix"] = o["flip_matrix"] + [flip]
         elif a == "--block-fused":
             o["block_fused"] = True
         elif a == "--device-loop":
@@ -346,6 +369,43 @@ def apply_structure_flips(ctx, A, flips, itr):
         ctx.flip_structure(A, kind, index, bits)
 
 
+def matrix_flips(o, ctx, A):
+    """--flip-matrix's flips in the order of their iterations, [(iteration, segment, {word: [bits 0..31]})], each
+    checked against the segments the matrix has"""
+    out = []
+    if not o["flip_matrix"]:
+        return out
+    sizes = dict(ctx.matrix_segments(A))
+    for itr, seg, word, bits in o["flip_matrix"]:
+        if seg not in sizes:
+            fail("Invalid --flip-matrix: the matrix has no segment '%s' (it has %s)" % (seg, ", ".join(sizes)))
+        words = {}
+        for b in bits:  # a bit past 31 lies in a following word
+            words.setdefault(word + b // 32, []).append(b % 32)
+        if 4 * max(words) >= sizes[seg]:
+            fail("Invalid --flip-matrix: word %d outside segment '%s' of %d bytes" % (max(words), seg, sizes[seg]))
+        out.append((itr, seg, words))
+    return sorted(out, key=lambda f: f[0])
+
+
+def apply_matrix_flips(ctx, A, flips, reached):
+    """the flips whose iteration `reached` says has been run, taken off the list"""
+    while flips and reached(flips[0][0]):
+        _, seg, words = flips.pop(0)
+        for word, bits in sorted(words.items()):
+            for bit in bits:
+                print("*** flipping bit %d of word %d of matrix segment %s ***" % (bit, word, seg))
+            ctx.flip_segment(A, seg, word, bits)
+
+
+def print_matrix_digests(o, ctx, A):
+    if o["verify_matrix"]:
+        ctx.arm_matrix(A)  # behind the injected element flips, as the preconditioner: the matrix the solve runs on
+        segs = ctx.matrix_segments(A)
+        print("matrix digests: %d segments, %d bytes, every %d iterations"
+              % (len(segs), sum(size for _, size in segs), o["verify_matrix"]))
+
+
 def report_check(checks, prefix, itr, gap, ok, back, bound):
     """one line per failed residual check; the counts for print_check_summary"""
     checks[ok] = checks.get(ok, 0) + 1
@@ -444,6 +504,7 @@ def run_single(o):
         ctx.inject_at(A, index, bits)
     vecs = vector_flips(o, n, {"x": x, "r": r, "p": p, "w": w, "b": b})
     sflips = structure_flips(o, ctx, A)
+    mflips = matrix_flips(o, ctx, A)
     dinv = make_preconditioner(o, ctx, A)
     if ecc:
         print("vector protection: secded (64, 57)")
@@ -457,6 +518,8 @@ def run_single(o):
             print("iteration %5u :  rr = %12.4f" % (itr, rr))
         apply_vector_flips(ctx, vecs, itr)
         apply_structure_flips(ctx, A, sflips, itr)
+        if not o["device_loop"]:
+            apply_matrix_flips(ctx, A, mflips, lambda i: i <= itr)
 
     if o["device_loop"]:
         print("iteration loop: device scalars, stride %d" % o["device_loop"])
@@ -471,18 +534,26 @@ def run_single(o):
             _, word, bits = tflips.pop(0)
             ctx.flip_trail(trail, 2 * o["device_loop"] + word, bits)
 
+    def after_batch(done, trail):
+        if tecc:
+            flip_trail(done, trail)
+        apply_matrix_flips(ctx, A, mflips, lambda i: i < done)  # after iteration I's batch, as --flip-trail
+
+    print_matrix_digests(o, ctx, A)
+    mcheck = {"matrix_check_every": o["verify_matrix"]} if o["verify_matrix"] else {}
     t0 = time.perf_counter()
     try:
         if o["device_loop"]:
             itr, rr = cg_solve_device(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
-                                      stride=o["device_loop"],
-                                      **({"trail_ecc": True, "on_batch": flip_trail} if tecc else {}))
+                                      stride=o["device_loop"], **mcheck,
+                                      **({"trail_ecc": True} if tecc else {}),
+                                      **({"on_batch": after_batch} if tecc or mflips else {}))
         else:
             itr, rr = cg_solve(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
                                check_every=o["check_every"], check_tol=o["check_tol"],
                                max_rollbacks=o["max_rollbacks"],
                                on_check=lambda i, gap, ok, back: report_check(checks, "", i, gap, ok, back, bound),
-                               precond=dinv, **({"vector_ecc": True} if ecc else {}))
+                               precond=dinv, **({"vector_ecc": True} if ecc else {}), **mcheck)
     except ResidualCheckFailed as e:
         print("[ABFT] %s" % e)
         ctx.close()
@@ -491,6 +562,8 @@ def run_single(o):
     print("\nran for %u iterations" % itr)
     if o["check_every"]:
         print_check_summary(checks)
+    if o["verify_matrix"]:
+        print("matrix verifications: %d passed" % ctx.matrix_verifications)
     if secc:  # every stored word once more, those no SpMV reads as well
         print("structure scrub: %d corrected" % ctx.scrub_structure(A)[0])
     print("\ntime taken = %7.2f ms\n" % ms)
@@ -530,6 +603,7 @@ def run_block(o):
         ctx.inject_at(A, index, bits)
 
     vecs = vector_flips(o, n * K, {"x": x, "r": r, "p": p})
+    mflips = matrix_flips(o, ctx, A)
     dinv = make_preconditioner(o, ctx, A)
     if o["block_fused"]:
         print("block iteration: fused")
@@ -540,16 +614,19 @@ def run_block(o):
         if not o["quiet"]:
             print("iteration %5u :  rr = %s" % (itr, " ".join("%12.4f" % v for v in rr)))
         apply_vector_flips(ctx, vecs, itr)
+        apply_matrix_flips(ctx, A, mflips, lambda i: i <= itr)
 
     def on_check(i, gap, ok, back, j):
         report_check(checks, "rhs %u: " % j, i, gap, ok, back, bounds[j])
 
+    print_matrix_digests(o, ctx, A)
     t0 = time.perf_counter()
     try:
         itrs, _ = cg_solve_block(ctx, A, b, x, r, p, w, o["max_itrs"], o["conv"], on_iteration=line,
                                  check_every=o["check_every"], check_tol=o["check_tol"],
                                  max_rollbacks=o["max_rollbacks"], on_check=on_check, precond=dinv,
-                                 **({"fused": True} if o["block_fused"] else {}))
+                                 **({"fused": True} if o["block_fused"] else {}),
+                                 **({"matrix_check_every": o["verify_matrix"]} if o["verify_matrix"] else {}))
     except ResidualCheckFailed as e:
         print("[ABFT] %s" % e)
         ctx.close()
@@ -560,6 +637,8 @@ def run_block(o):
         print("rhs %u: ran for %u iterations" % (j, itrs[j]))
     if o["check_every"]:
         print_check_summary(checks)
+    if o["verify_matrix"]:
+        print("matrix verifications: %d passed" % ctx.matrix_verifications)
     print("\ntime taken = %7.2f ms (%u right-hand sides)\n" % (ms, K))
     ctx.spmm(A, x, r, K)
     err = np.abs(ctx.download(b) - ctx.download(r))

@@ -44,6 +44,7 @@ class Matrix:
         self.ctx, self.h, self.fmt, self.mode = ctx, handle, fmt, mode
         self.n_out, self.n_in, self.nnz = n_out, n_in, nnz
         self.structure_ecc = False  # create_matrix(structure_ecc=True): the row structure is stored as codewords
+        self.digest_armed = False  # arm_matrix has taken its reference digests
 
 
 class Vector:
@@ -84,6 +85,7 @@ class HIPContext:
         self.event_log = []
         self._evbuf, self._evcap = None, 0
         self.prof_mask = 0
+        self.matrix_verifications = 0  # verify_matrix / verify_matrix_dev calls made so far
         self._live = []  # matrices and vectors not yet destroyed, in creation order
 
     def close(self):
@@ -209,6 +211,64 @@ class HIPContext:
         check(self.L.abft_hip_matrix_scrub_structure(self.h, mat.h, C.byref(c), C.byref(u)))
         self._drain()
         return c.value, u.value
+
+    # ---- matrix digests (include/abft_hip.h) ----
+    def matrix_segments(self, mat):
+        """-> [(name, bytes)]: the stored arrays of the matrix that kernels only read or only repair, in the order
+        matrix_digest reports them"""
+        n = C.c_int(0)
+        check(self.L.abft_hip_matrix_segments(mat.h, None, None, 0, C.byref(n)))
+        kinds, nbytes = (C.c_uint32 * max(n.value, 1))(), (C.c_uint64 * max(n.value, 1))()
+        check(self.L.abft_hip_matrix_segments(mat.h, kinds, nbytes, n.value, C.byref(n)))
+        return [(capi.segment_name(kinds[k]), int(nbytes[k])) for k in range(n.value)]
+
+    def matrix_digest(self, mat):
+        """-> {name: digest}, the current D = sum w[i] (2 i + 1) mod 2^64 of every segment (synchronous)"""
+        names = [s for s, _ in self.matrix_segments(mat)]
+        out = (C.c_uint64 * max(len(names), 1))()
+        check(self.L.abft_hip_matrix_digest(self.h, mat.h, out, len(names)))
+        return {s: int(out[k]) for k, s in enumerate(names)}
+
+    def arm_matrix(self, mat):
+        """take the current digests as the reference verify_matrix / verify_matrix_dev compare with; arming again
+        takes a new reference"""
+        check(self.L.abft_hip_matrix_digest_arm(self.h, mat.h))
+        mat.digest_armed = True
+
+    def verify_matrix(self, mat):
+        """recompute the digests and compare (synchronous) -> the names of the segments that differ, [] when clean;
+        AbftError on a matrix that is not armed"""
+        n = C.c_int(0)
+        bad = (C.c_uint32 * capi.SEG_COUNT)()
+        check(self.L.abft_hip_matrix_verify(self.h, mat.h, C.byref(n), bad, capi.SEG_COUNT))
+        self.matrix_verifications += 1
+        return [capi.segment_name(bad[k]) for k in range(min(n.value, capi.SEG_COUNT))]
+
+    def verify_matrix_dev(self, mat):
+        """the same as two launches on the stream, nothing else (capturable): one (EV_MATRIX_DIGEST, segment kind, 0)
+        event per differing segment arrives with the next drain, fatal"""
+        self._enqueue_verify(mat)
+        self.matrix_verifications += 1
+
+    def _enqueue_verify(self, mat):
+        # not counted: the device loops count per batch (a captured call runs once per replay, not once per call)
+        check(self.L.abft_hip_matrix_verify_dev(self.h, mat.h))
+
+    def read_segment(self, mat, name):
+        """-> the segment's bytes as stored (uint8[bytes], padding included)"""
+        size = dict(self.matrix_segments(mat)).get(name)
+        if size is None:
+            raise ValueError("the matrix has no segment %r" % (name,))
+        buf = np.zeros(size, dtype=np.uint8)
+        check(self.L.abft_hip_matrix_read_segment(self.h, mat.h, capi.segment_kind(name), buf.ctypes.data, size))
+        return buf
+
+    def flip_segment(self, mat, name, word, bits):
+        """XOR `bits` (0..31) into stored 32-bit word `word` of the segment: the injector for arrays no other
+        injector reaches.  A raw write: nothing else follows it, the armed digests least of all"""
+        b = np.ascontiguousarray(bits, dtype=np.int32)
+        check(self.L.abft_hip_matrix_flip_segment(self.h, mat.h, capi.segment_kind(name), int(word),
+                                                  b.ctypes.data_as(capi.i32p), len(b)))
 
     # ---- vectors ----------------------------------------------------------
     def create_vector(self, N):
@@ -1017,9 +1077,115 @@ def _check_args(check_every, check_tol, max_rollbacks):
         raise ValueError("max_rollbacks must be >= 0, not %r" % (max_rollbacks,))
 
 
+class _NoWatch:
+    """matrix_check_every=0: the solvers make exactly the calls they make without the keyword"""
+    every = 0
+
+    def ran(self, count):
+        pass
+
+    def before_check(self):
+        pass
+
+    def final(self):
+        pass
+
+    def due(self, done, m):
+        return False
+
+    def enqueued(self):
+        pass
+
+    def final_dev(self):
+        pass
+
+
+_NO_WATCH = _NoWatch()
+
+
+class _MatrixWatch(_NoWatch):
+    """matrix_check_every=M > 0 of the four solvers: the matrix is armed if it is not, and its
+    digests are verified on the schedule below.  The hook never looks inside the iteration: it touches no vector and
+    no scalar, and the library's digest entries leave the loop's state between calls alone, so a clean run makes the
+    launches and computes the bits of the run without it.  `fresh`: a verification has seen the matrix since the last
+    iteration ran.
+
+    Host loops: ran(count) behind every iteration (count iterations run so far) verifies when count % M == 0;
+    before_check() in front of every residual check, before the checkpoint copy; final() before the solver returns --
+    the last two only on a state no verification has seen.  A mismatch is reported as the fatal events
+    (EV_MATRIX_DIGEST, segment kind, 0), behind whatever else is queued: FatalEvent, nothing restored.
+    Device loops (_device_batches): due(done, m) -- does the batch of m iterations that starts at count `done` reach
+    or pass the next multiple of M? -- is known before the batch is enqueued; such a batch has verify_matrix_dev
+    behind its last iteration (enqueued() notes it), and its verdict arrives with the batch's download."""
+
+    def __init__(self, ctx, A, every):
+        if int(every) != every or every < 0:
+            raise ValueError("matrix_check_every must be a whole number >= 0, not %r" % (every,))
+        self.ctx, self.A, self.every = ctx, A, int(every)
+        self.fresh = False
+        if not getattr(A, "digest_armed", False):
+            ctx.arm_matrix(A)
+
+    def verify(self):
+        bad = self.ctx.verify_matrix(self.A)
+        if bad:
+            self.ctx._drain()  # what the kernels queued comes first
+            self.ctx._report([(capi.EV_MATRIX_DIGEST, capi.segment_kind(s), 0) for s in bad], True)
+        self.fresh = True
+
+    def ran(self, count):
+        self.fresh = False
+        if count % self.every == 0:
+            self.verify()
+
+    def before_check(self):
+        if not self.fresh:
+            self.verify()
+
+    def final(self):
+        if not self.fresh:
+            self.verify()
+
+    def due(self, done, m):
+        self.fresh = False  # a batch of iterations is about to run
+        return done + m >= (done // self.every + 1) * self.every
+
+    def enqueued(self):
+        self.fresh = True  # (the download behind the batch raises FatalEvent on a mismatch)
+        self.ctx.matrix_verifications += 1
+
+    def final_dev(self):
+        """a device loop's last batch had no verification: one is enqueued and waited for"""
+        if not self.fresh:
+            self.ctx.verify_matrix_dev(self.A)
+            self.ctx._drain()
+            self.fresh = True
+
+
+def _watch(ctx, A, matrix_check_every):
+    return _MatrixWatch(ctx, A, matrix_check_every) if matrix_check_every else _NO_WATCH
+
+
+def _with_matrix_check(positional, impl):
+    """the public form of a host-loop solver: `positional`'s parameters by position or by name, as they have always
+    been, and behind them the KEYWORD-ONLY matrix_check_every=0.  inspect.signature follows the wrapper to
+    `positional`'s list."""
+    @functools.wraps(positional, assigned=("__module__", "__name__", "__qualname__", "__doc__"))
+    def solver(*args, matrix_check_every=0, **kw):
+        if not matrix_check_every:
+            return positional(*args, **kw)
+        bound = inspect.signature(positional).bind(*args, **kw)
+        bound.apply_defaults()
+        return impl(*bound.args, _watch(bound.arguments["ctx"], bound.arguments["A"], matrix_check_every))
+    return solver
+
+
 def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None, check_every=0,
              check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None, precond=None, vector_ecc=False):
-    """The reference driver's CG loop, call for call (cg.cpp:87-118).
+    """cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None, check_every=0,
+    check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None, precond=None, vector_ecc=False, *, matrix_check_every=0)
+
+    The reference driver's CG loop, call for call (cg.cpp:87-118).
 
     check_every > 0 adds residual checks: after iteration i when (i + 1) %
     check_every == 0, and whenever the loop is about to stop on a state no check has seen, the
@@ -1054,7 +1220,25 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
     rz_new, rr = calc_r_precond_vecc(r, w, dinv, rz / pw) and calc_px_precond_vecc(x, p, r, dinv, alpha, rz_new / rz);
     x, b and dinv are scrubbed before returning.  A precond that is not marked protected is refused with
     vector_ecc (its plain doubles would be misread as codewords), a protected one without it (ValueError, before
-    anything runs)."""
+    anything runs).
+
+    matrix_check_every=M > 0 (keyword-only) verifies the matrix's digests as the loop runs:
+    the residual checks compare r with b - A x through the same A, so they cannot see a damaged A; this can.  The
+    matrix is armed (ctx.arm_matrix) if it is not.  A verification (ctx.verify_matrix) follows every iteration i with
+    (i + 1) % M == 0, behind on_iteration; with check_every > 0 one also runs in front of EVERY residual check, before
+    the checkpoint copy; and one runs before the solver returns -- the last two on a state no verification has seen
+    yet.  So no checkpoint is taken and no check trusted on a matrix that has not just been verified.  A mismatch is
+    fatal like a double-bit error: the line "[ABFT] matrix digest mismatch in segment NAME" per segment and
+    FatalEvent; nothing is restored, the caller re-creates the matrix.  Works with precond and vector_ecc, on every
+    layout, format and mode.  ctx.matrix_verifications counts the verifications.  With matrix_check_every=0 the calls
+    are exactly those made without the keyword."""
+    return _cg_solve(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, check_every, check_tol, max_rollbacks,
+                     x_ckpt, on_check, precond, vector_ecc, _NO_WATCH)
+
+
+def _cg_solve(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, check_every, check_tol, max_rollbacks,
+              x_ckpt, on_check, precond, vector_ecc, watch):
+    """cg_solve's body; watch: _NO_WATCH, or the _MatrixWatch of matrix_check_every"""
     _check_args(check_every, check_tol, max_rollbacks)
     if vector_ecc and check_every:
         raise ValueError("vector_ecc with check_every > 0: the residual kernels write unencoded vectors")
@@ -1063,7 +1247,7 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
         if not ctx.vecc_supported(A):
             raise ValueError("vector_ecc needs a CSR matrix in the streaming layout (this one: %s)"
                              % ("COO" if A.fmt != FMT_CSR else ctx.matrix_info(A)[0]))
-        return _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, precond)
+        return _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, precond, watch)
     ctx.copy_vector(r, b)
     rz = None
     if precond is None:
@@ -1084,6 +1268,7 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
 
         def check():
             nonlocal rr, rz
+            watch.before_check()
             gap2, tt2 = ctx.residual_gap(A, b, x, r, w)
             ok = _check_passes(gap2, tt2, bb, check_tol)
             gap = math.sqrt(gap2) if gap2 >= 0 else gap2
@@ -1133,14 +1318,19 @@ def cg_solve(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_itera
             if on_iteration is not None:
                 on_iteration(itr, rr)
             itr += 1
+            watch.ran(itr)
             if check_every:
                 st["checked"] = False
                 if itr % check_every == 0:
                     check()
+        watch.final()
     finally:
         if check_every and own_ckpt:
             ctx.destroy_vector(x_ckpt)
     return itr, rr
+
+
+cg_solve = _with_matrix_check(cg_solve, _cg_solve)
 
 
 # iterations per look at the scalars in cg_solve_device.  Not measured: the smallest stride within 2 % of the best
@@ -1156,7 +1346,7 @@ def _whole_stride(stride):
 
 
 def _device_batches(ctx, max_itrs, stride, graph, rec, tail, seed, enqueue, record, before_capture=None,
-                    slots=False, on_batch=None):
+                    slots=False, on_batch=None, watch=_NO_WATCH):
     """The batch loop of cg_solve_device and cg_solve_block_device: a trail of stride + 1 records of `rec` doubles
     with `tail` doubles behind them (at pw_at = rec * (stride + 1): the SpMV's product), record `stride` starting
     with `seed`.  A batch copies record `stride` to record 0 and calls enqueue(trail, i, pw_at) for its iterations
@@ -1167,7 +1357,13 @@ def _device_batches(ctx, max_itrs, stride, graph, rec, tail, seed, enqueue, reco
     slots: a protected trail -- every word a SECDED slot of two doubles, so all offsets double
     (pw_at included), the seed record is encoded, and what is downloaded is decoded on the host (ctx.report_trail)
     before record() sees it, in the unprotected layout.  on_batch(done, trail): called after a batch's callbacks with
-    the trail vector, whose record `stride` starts the next batch."""
+    the trail vector, whose record `stride` starts the next batch.
+    watch: the _MatrixWatch of matrix_check_every=M.  A batch whose end count reaches or passes
+    the next multiple of M -- known before it is enqueued, from `done` and m -- has ctx.verify_matrix_dev enqueued
+    behind its last iteration; the two shapes of a full batch, with and without it, are captured once each.  The
+    verdict arrives with the batch's download, which drains the events: FatalEvent there, before the batch's
+    callbacks.  When the last batch had none, one verification is enqueued and waited for behind the loop.  A flip is
+    therefore seen at most M + stride - 1 iterations after it happened."""
     # (the records' lengths and word indices, here and in the callers, are those csrc/guard_protocol.h defines)
     wide = 2 if slots else 1  # doubles per trail word
     pw_at = wide * rec * (stride + 1)
@@ -1184,27 +1380,32 @@ def _device_batches(ctx, max_itrs, stride, graph, rec, tail, seed, enqueue, reco
         start[rec * stride:rec * stride + len(seed)] = seed  # where the first batch's copy finds it
     ctx.upload(trail, start)
 
-    def batch(m):
+    def batch(m, verify):
         ctx.copy_vector(first, last)
         for i in range(m):
             enqueue(trail, i, pw_at)
+        if verify:
+            ctx._enqueue_verify(watch.A)  # counted by watch.enqueued(), per batch: captured or not
 
-    done, g = 0, None
+    done, graphs = 0, {}
     try:
         while True:
             m = min(stride, max_itrs - done)
+            verify = watch.due(done, m)
             if graph and m == stride:
-                if g is None:
-                    if before_capture is not None:
+                if verify not in graphs:
+                    if before_capture is not None and not graphs:
                         before_capture()
                     ctx.graph_begin()
                     try:
-                        batch(m)
+                        batch(m, verify)
                     finally:
-                        g = ctx.graph_end()
-                ctx.graph_launch(g)
+                        graphs[verify] = ctx.graph_end()
+                ctx.graph_launch(graphs[verify])
             else:
-                batch(m)
+                batch(m, verify)
+            if verify:
+                watch.enqueued()
             t = ctx.download(trail)  # synchronises, then drains the events
             if slots:
                 t = ctx.report_trail(t, rec, stride)
@@ -1218,8 +1419,9 @@ def _device_batches(ctx, max_itrs, stride, graph, rec, tail, seed, enqueue, reco
                 on_batch(done, trail)
             if stopped or done >= max_itrs:
                 break
+        watch.final_dev()
     finally:
-        if g is not None:
+        for g in graphs.values():
             ctx.graph_destroy(g)
         for v in (first, last, trail):
             ctx.destroy_vector(v)
@@ -1344,7 +1546,7 @@ def cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, o
     below wraps this function and adds two KEYWORD-ONLY arguments behind them, trail_ecc=False and on_batch=None;
     inspect.signature follows the wrapper to this list, so look there for those two."""
     return _cg_solve_device(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, stride, graph, precond,
-                            vector_ecc, check_every, check_tol, max_rollbacks, x_ckpt, on_check, False, None)
+                            vector_ecc, check_every, check_tol, max_rollbacks, x_ckpt, on_check, False, None, 0)
 
 
 _cg_solve_device_positional = cg_solve_device
@@ -1352,18 +1554,21 @@ _cg_solve_device_positional = cg_solve_device
 
 @functools.wraps(_cg_solve_device_positional, assigned=("__module__", "__name__", "__qualname__"))
 def cg_solve_device(*args, trail_ecc=False, on_batch=None, **kw):
-    if not trail_ecc and on_batch is None:
+    # (matrix_check_every=0, keyword-only like the two above, is taken out of **kw: the wrapper's own keyword defaults
+    # stay the pair tests/test_trail_ecc_host.py pins)
+    matrix_check_every = kw.pop("matrix_check_every", 0)
+    if not trail_ecc and on_batch is None and not matrix_check_every:
         return _cg_solve_device_positional(*args, **kw)
     bound = inspect.signature(_cg_solve_device_positional).bind(*args, **kw)
     bound.apply_defaults()
-    return _cg_solve_device(*bound.args, trail_ecc, on_batch)
+    return _cg_solve_device(*bound.args, trail_ecc, on_batch, matrix_check_every)
 
 
 def _cg_solve_device(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, stride, graph, precond, vector_ecc,
-                     check_every, check_tol, max_rollbacks, x_ckpt, on_check, trail_ecc, on_batch):
+                     check_every, check_tol, max_rollbacks, x_ckpt, on_check, trail_ecc, on_batch, matrix_check_every):
     """cg_solve_device(ctx, A, b, x, r, p, w, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
     stride=DEFAULT_STRIDE, graph=True, precond=None, vector_ecc=False, check_every=0, check_tol=1e-7, max_rollbacks=3,
-    x_ckpt=None, on_check=None, *, trail_ecc=False, on_batch=None)
+    x_ckpt=None, on_check=None, *, trail_ecc=False, on_batch=None, matrix_check_every=0)
 
     cg_solve's loop (cg.cpp:87-118) with alpha, beta and the stop test on the device:
     the host looks at the scalars once per batch of `stride` iterations instead of twice per iteration.
@@ -1432,9 +1637,24 @@ def _cg_solve_device(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iterati
     on_batch(done, trail) runs after a batch's callbacks with the trail vector; its record `stride` starts the next
     batch (with trail_ecc: ctx.flip_trail(trail, slot, bits) flips a bit of it); with check_every > 0 it runs behind
     on_check as well, and the latest record is still record `stride`.  With trail_ecc=False and
-    on_batch=None the calls are exactly those made without the arguments."""
+    on_batch=None the calls are exactly those made without the arguments.
+
+    matrix_check_every=M > 0 (keyword-only) verifies the matrix's digests as the loop runs (what
+    it is for: cg_solve).  The matrix is armed if it is not.  A batch whose end count reaches or passes the next
+    multiple of M has ctx.verify_matrix_dev enqueued behind its last iteration; with graph=True the two shapes of a
+    full batch, with and without the verification, are captured once each.  The verdict arrives with the batch's
+    download: a mismatch raises FatalEvent there, before the batch's callbacks, with the line "[ABFT] matrix digest
+    mismatch in segment NAME"; nothing is restored.  One final verification is enqueued and waited for when the last
+    batch had none.  A flip is seen at most M + stride - 1 iterations after it happened.  Works with precond,
+    vector_ecc, trail_ecc and structure_ecc matrices.  Refused (ValueError, before anything runs) with
+    check_every > 0.  With matrix_check_every=0 the calls are exactly those made without the keyword."""
     stride = _whole_stride(stride)
     _check_args(check_every, check_tol, max_rollbacks)
+    if matrix_check_every and check_every:
+        raise ValueError("cg_solve_device with check_every > 0 and matrix_check_every > 0: the device loop does not "
+                         "verify the matrix in front of its residual checks yet; use cg_solve, or one of the two")
+    if int(matrix_check_every) != matrix_check_every or matrix_check_every < 0:
+        raise ValueError("matrix_check_every must be a whole number >= 0, not %r" % (matrix_check_every,))
     if trail_ecc and check_every:
         raise ValueError("trail_ecc with check_every > 0: the residual check's four words are not under the code")
     if vector_ecc and check_every:
@@ -1466,6 +1686,7 @@ def _cg_solve_device(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iterati
     noted = {}
     note_threshold(rr, conv_threshold, noted)
     done, last_rr = 0, [rr]
+    watch = _watch(ctx, A, matrix_check_every)
 
     def enqueue(trail, k, pw_at):
         if trail_ecc:  # the same four loops on slots of two doubles
@@ -1523,7 +1744,8 @@ def _cg_solve_device(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iterati
         return done, last_rr[0]
     if max_itrs != 0 and rr > conv_threshold:
         done = _device_batches(ctx, max_itrs, stride, graph, rec, 2, seed, enqueue, record, slots=bool(trail_ecc),
-                               on_batch=on_batch)
+                               on_batch=on_batch, **({"watch": watch} if watch.every else {}))
+    watch.final_dev()
     if vector_ecc:
         ctx.scrub_vector(x)
         ctx.scrub_vector(b)
@@ -1542,7 +1764,7 @@ def cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1
     function and adds two KEYWORD-ONLY arguments behind them, trail_ecc=False and on_batch=None, the way
     cg_solve_device does; inspect.signature follows the wrapper to this list."""
     return _cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs, conv_threshold, on_iteration, stride, graph, precond,
-                                  vector_ecc, False, None)
+                                  vector_ecc, False, None, 0)
 
 
 _cg_solve_block_device_positional = cg_solve_block_device
@@ -1550,17 +1772,19 @@ _cg_solve_block_device_positional = cg_solve_block_device
 
 @functools.wraps(_cg_solve_block_device_positional, assigned=("__module__", "__name__", "__qualname__"))
 def cg_solve_block_device(*args, trail_ecc=False, on_batch=None, **kw):
-    if not trail_ecc and on_batch is None:
+    matrix_check_every = kw.pop("matrix_check_every", 0)  # keyword-only, as in cg_solve_device
+    if not trail_ecc and on_batch is None and not matrix_check_every:
         return _cg_solve_block_device_positional(*args, **kw)
     bound = inspect.signature(_cg_solve_block_device_positional).bind(*args, **kw)
     bound.apply_defaults()
-    return _cg_solve_block_device(*bound.args, trail_ecc, on_batch)
+    return _cg_solve_block_device(*bound.args, trail_ecc, on_batch, matrix_check_every)
 
 
 def _cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs, conv_threshold, on_iteration, stride, graph, precond,
-                           vector_ecc, trail_ecc, on_batch):
+                           vector_ecc, trail_ecc, on_batch, matrix_check_every):
     """cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None,
-    stride=DEFAULT_STRIDE, graph=True, precond=None, vector_ecc=False, *, trail_ecc=False, on_batch=None)
+    stride=DEFAULT_STRIDE, graph=True, precond=None, vector_ecc=False, *, trail_ecc=False, on_batch=None,
+    matrix_check_every=0)
 
     cg_solve_block(fused=True)'s loop with the K alphas, the K betas and the column mask on the device (DESIGN.md
     section 5h): the host looks at the scalars once per batch of `stride` iterations instead of twice per iteration.
@@ -1601,9 +1825,14 @@ def _cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs, conv_threshold, on_i
     on_batch(done, trail) runs after a batch's callbacks with the trail vector; its record `stride` starts the next
     batch (with trail_ecc: ctx.flip_trail(trail, slot, bits) flips a bit of it).  With trail_ecc=False and
     on_batch=None the calls are exactly those made without the two arguments.
+    matrix_check_every=M > 0 (keyword-only): as in cg_solve_device -- ctx.verify_matrix_dev behind the last iteration of
+    every batch that reaches or passes a multiple of M, FatalEvent at that batch's download on a mismatch, one final
+    verification when the last batch had none.  With 0 the calls are exactly those made without the keyword.
     No check_every, one GPU."""
     _refuse_structure_ecc(ctx, A, "cg_solve_block_device")
     stride = _whole_stride(stride)
+    if int(matrix_check_every) != matrix_check_every or matrix_check_every < 0:
+        raise ValueError("matrix_check_every must be a whole number >= 0, not %r" % (matrix_check_every,))
     if vector_ecc:
         if precond is not None:
             raise ValueError("vector_ecc with a precond: the protected block loop has no Jacobi form")
@@ -1634,7 +1863,9 @@ def _cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs, conv_threshold, on_i
     noted = {}
     for j in range(k):
         note_threshold(rr[j], conv_threshold, noted)
+    watch = _watch(ctx, A, matrix_check_every)
     if max_itrs == 0 or not any(rr[j] > conv_threshold for j in range(k)):
+        watch.final_dev()
         if vector_ecc:
             ctx.scrub_vector(X)
             ctx.scrub_vector(B)
@@ -1672,7 +1903,8 @@ def _cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs, conv_threshold, on_i
         return True
 
     _device_batches(ctx, max_itrs, stride, graph, rec, k + 1, np.concatenate([rr, rz]), enqueue, record,
-                    before_capture=lambda: ctx.block_loop_reserve(A, k), slots=bool(trail_ecc), on_batch=on_batch)
+                    before_capture=lambda: ctx.block_loop_reserve(A, k), slots=bool(trail_ecc), on_batch=on_batch,
+                    **({"watch": watch} if watch.every else {}))
     if vector_ecc:
         ctx.scrub_vector(X)
         ctx.scrub_vector(B)
@@ -1682,7 +1914,7 @@ def _cg_solve_block_device(ctx, A, B, X, R, P, W, max_itrs, conv_threshold, on_i
 cg_solve_block_device.__doc__ = _cg_solve_block_device.__doc__
 
 
-def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, precond=None):
+def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration, precond=None, watch=_NO_WATCH):
     """cg_solve(vector_ecc=True): the loop of cg_solve on protected vectors; precond: a protected dinv"""
     ctx.encode_vector(b)
     ctx.encode_vector(x)
@@ -1712,6 +1944,8 @@ def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration
         if on_iteration is not None:
             on_iteration(itr, rr)
         itr += 1
+        watch.ran(itr)
+    watch.final()
     ctx.scrub_vector(x)
     ctx.scrub_vector(b)
     if precond is not None:
@@ -1719,7 +1953,7 @@ def _cg_solve_vecc(ctx, A, b, x, r, p, w, max_itrs, conv_threshold, on_iteration
     return itr, rr
 
 
-def _cg_solve_block_vecc(ctx, A, B, X, R, P, W, k, max_itrs, conv_threshold, on_iteration):
+def _cg_solve_block_vecc(ctx, A, B, X, R, P, W, k, max_itrs, conv_threshold, on_iteration, watch=_NO_WATCH):
     """cg_solve_block(vector_ecc=True): the fused block loop on protected block vectors"""
     ctx.encode_vector(B)
     ctx.encode_vector(X)
@@ -1750,6 +1984,8 @@ def _cg_solve_block_vecc(ctx, A, B, X, R, P, W, k, max_itrs, conv_threshold, on_
         if on_iteration is not None:
             on_iteration(itr, rr.copy(), active)
         itr += 1
+        watch.ran(itr)
+    watch.final()
     ctx.scrub_vector(X)
     ctx.scrub_vector(B)
     return itrs, rr
@@ -1758,7 +1994,11 @@ def _cg_solve_block_vecc(ctx, A, B, X, R, P, W, k, max_itrs, conv_threshold, on_
 def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None, check_every=0,
                    check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None, precond=None, fused=False,
                    vector_ecc=False):
-    """cg_solve for the K columns of block vectors (ctx.create_block) at once: per column j exactly
+    """cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on_iteration=None, check_every=0,
+    check_tol=1e-7, max_rollbacks=3, x_ckpt=None, on_check=None, precond=None, fused=False, vector_ecc=False, *,
+    matrix_check_every=0)
+
+    cg_solve for the K columns of block vectors (ctx.create_block) at once: per column j exactly
     cg_solve's control flow -- column j iterates while itrs[j] < max_itrs and rr[j] > conv_threshold --
     on one spmm / dot_block / calc_xr_block / calc_p_block per iteration.  A column that has stopped
     is frozen through the active mask (its x, r, p are not touched again); the loop ends when no
@@ -1786,7 +2026,18 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
     returning.  Every word of every column is checked by every call, stopped columns included, and a stopped
     column's words are stored back repaired.  Control flow, masks, on_iteration and the return value are as
     without it.  Refused (ValueError, before anything runs) with check_every > 0, with any precond, and for a matrix
-    ctx.vecc_supported refuses.  With vector_ecc=False the calls are exactly those made without the argument."""
+    ctx.vecc_supported refuses.  With vector_ecc=False the calls are exactly those made without the argument.
+
+    matrix_check_every=M > 0 (keyword-only): as in cg_solve, the loop's iterations counted whatever columns they
+    update -- a verification of the matrix's digests behind every M-th iteration, in front of every residual check
+    and before returning; a mismatch raises FatalEvent.  With 0 the calls are exactly those made without it."""
+    return _cg_solve_block(ctx, A, B, X, R, P, W, max_itrs, conv_threshold, on_iteration, check_every, check_tol,
+                           max_rollbacks, x_ckpt, on_check, precond, fused, vector_ecc, _NO_WATCH)
+
+
+def _cg_solve_block(ctx, A, B, X, R, P, W, max_itrs, conv_threshold, on_iteration, check_every, check_tol, max_rollbacks,
+                    x_ckpt, on_check, precond, fused, vector_ecc, watch):
+    """cg_solve_block's body; watch: _NO_WATCH, or the _MatrixWatch of matrix_check_every"""
     _refuse_structure_ecc(ctx, A, "cg_solve_block")
     _check_args(check_every, check_tol, max_rollbacks)
     if vector_ecc:
@@ -1802,7 +2053,7 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
     if not k:
         raise ValueError("cg_solve_block wants block vectors (create_block)")
     if vector_ecc:
-        return _cg_solve_block_vecc(ctx, A, B, X, R, P, W, k, max_itrs, conv_threshold, on_iteration)
+        return _cg_solve_block_vecc(ctx, A, B, X, R, P, W, k, max_itrs, conv_threshold, on_iteration, watch)
     ctx.copy_vector(R, B)
     rz = None
     if precond is None:
@@ -1828,6 +2079,7 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
         checked, ckpt, fails, records = [False] * k, [-1] * k, [0] * k, []
 
         def check(due):
+            watch.before_check()
             gap2, tt2 = ctx.residual_gap_block(A, B, X, R, W, k, due)
             passed = failed = 0
             events = []
@@ -1920,7 +2172,12 @@ def cg_solve_block(ctx, A, B, X, R, P, W, max_itrs=1000, conv_threshold=1e-3, on
             if on_iteration is not None:
                 on_iteration(itr, rr.copy(), active)
             itr += 1
+            watch.ran(itr)
+        watch.final()
     finally:
         if check_every and own_ckpt:
             ctx.destroy_vector(x_ckpt)
     return itrs, rr
+
+
+cg_solve_block = _with_matrix_check(cg_solve_block, _cg_solve_block)

@@ -23,6 +23,7 @@
 #include "guard_protocol.h"
 #include "layout_plan.h"
 #include "loop_state.h"
+#include "matrix_digest.h"
 #include "struct_ecc.h"
 #include "trail_ecc.h"
 
@@ -186,6 +187,19 @@ struct abft_hip_matrix {
   // Then csr.rowptr and csr.blk are NULL, and so are compact, packed and packed_fast: no plain copy of the structure exists.
   bool protects = false;
   CsrStruct prot{};
+  // matrix digests (matrix_digest.h): every upload that kernels only read, or only repair, as {kind, pointer, bytes} in
+  // upload order -- no entry ever reallocates one, so the pointers and lengths hold for the matrix's life --, and what
+  // the first digest call allocates: the table the kernel walks, the accumulators (zero between uses), the armed
+  // reference and the {current, reference} pairs of the last verification
+  struct Segment { uint32_t kind; void *ptr; size_t bytes; };
+  std::vector<Segment> segments;
+  struct {
+    DigestSeg *table = nullptr;
+    unsigned long long *acc = nullptr, *ref = nullptr, *pairs = nullptr;
+    uint32_t nseg = 0;
+    bool armed = false;
+    std::vector<uint64_t> ref_host;
+  } digest;
   std::vector<void *> allocs;
   bool streams() const { return layout == Layout::Stream; }
 };
@@ -271,6 +285,8 @@ static int flush_deferred(abft_hip_ctx *ctx) {
 //    fused product, the calc_xr that defers onto the queue's x, or the calc_p that takes that update along)
 //   no prologue                    init, shutdown, the getters and counters, vector_view, matrix_set_interior,
 //                                  matrix_info, matrix_panels, graph_end, graph_destroy, the detach and *_failed calls
+//                                  the matrix digest entries (matrix_segments, _digest, _digest_arm, _verify, _verify_dev,
+//                                  _read_segment, _flip_segment): they touch no vector and no scalar of the loop
 //
 // An entry that forgets only once its arguments have passed (a refused call leaves the state alone) does so by hand,
 // with forget_fused / forget_iteration behind its checks.
@@ -564,13 +580,14 @@ extern "C" int abft_hip_synchronize_timeout(abft_hip_ctx *ctx, double seconds) {
 // ------------------------------------------------------------------- matrix --
 
 template <typename T>
-static int dev_upload(abft_hip_matrix *m, T **dst, const T *src, size_t count, size_t alloc_count) {
+static int dev_upload(abft_hip_matrix *m, T **dst, const T *src, size_t count, size_t alloc_count, uint32_t kind) {
   T *p = nullptr;
   if (alloc_count < count) alloc_count = count;
   if (alloc_count == 0) alloc_count = 1;
   if (hipMalloc((void **)&p, alloc_count * sizeof(T)) != hipSuccess)
     return set_err(ABFT_ERR_NOMEM, "hipMalloc of %zu bytes failed", alloc_count * sizeof(T));
   m->allocs.push_back(p);
+  if (kind != ABFT_SEG_NONE) m->segments.push_back({kind, p, alloc_count * sizeof(T)});  // the whole allocation, padding included
   if (alloc_count > count)
     HIPCHK(hipMemsetAsync(p + count, 0, (alloc_count - count) * sizeof(T), m->ctx->stream));
   if (count) HIPCHK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, m->ctx->stream));
@@ -703,14 +720,14 @@ static LayoutKnobs from_env() {
 }
 
 template <typename T>
-static int upload_all(abft_hip_matrix *m, T **dst, const std::vector<T> &v) {
-  return dev_upload(m, dst, v.data(), v.size(), v.size());
+static int upload_all(abft_hip_matrix *m, T **dst, const std::vector<T> &v, uint32_t kind) {
+  return dev_upload(m, dst, v.data(), v.size(), v.size(), kind);
 }
 
 // a progress board per XCD: 8 boards of PACE_SLOTS "nobody here" (kernels.hip: PACE_*)
 static int pace_board(abft_hip_matrix *m, uint32_t **board) {
   const std::vector<uint32_t> init(8 * 256, 0xffffffffu);
-  if (int rc = upload_all(m, board, init)) return rc;
+  if (int rc = upload_all(m, board, init, ABFT_SEG_NONE)) return rc;
   HIPCHK(hipStreamSynchronize(m->ctx->stream));  // `init` goes out of scope
   return ABFT_OK;
 }
@@ -719,7 +736,7 @@ static int pace_board(abft_hip_matrix *m, uint32_t **board) {
 template <typename T>
 static int debug_buffer(abft_hip_matrix *m, T **buf, size_t count) {
   const std::vector<T> zero(count, 0);
-  if (int rc = upload_all(m, buf, zero)) return rc;
+  if (int rc = upload_all(m, buf, zero, ABFT_SEG_NONE)) return rc;
   HIPCHK(hipStreamSynchronize(m->ctx->stream));
   return ABFT_OK;
 }
@@ -737,8 +754,10 @@ static int upload_permuted(abft_hip_matrix *m, const std::vector<uint32_t> &pos,
   }
   uint32_t *d_orig = nullptr, *d_pos = nullptr;
   int rc;
-  if ((rc = dev_upload(m, &A.cols, pcols.data(), nnz, padded)) || (rc = dev_upload(m, &A.vals, pvals.data(), nnz, padded)) ||
-      (rc = dev_upload(m, &d_orig, orig.data(), nnz, nnz)) || (rc = dev_upload(m, &d_pos, pos.data(), nnz, nnz)))
+  if ((rc = dev_upload(m, &A.cols, pcols.data(), nnz, padded, ABFT_SEG_COLS)) ||
+      (rc = dev_upload(m, &A.vals, pvals.data(), nnz, padded, ABFT_SEG_VALS)) ||
+      (rc = dev_upload(m, &d_orig, orig.data(), nnz, nnz, ABFT_SEG_ORIG_INDEX)) ||
+      (rc = dev_upload(m, &d_pos, pos.data(), nnz, nnz, ABFT_SEG_POS_OF_ORIG)))
     return rc;
   HIPCHK(hipStreamSynchronize(m->ctx->stream));  // pcols/pvals go out of scope
   A.orig_index = d_orig;
@@ -751,7 +770,7 @@ static int attach_panels(abft_hip_matrix *m, const PanelBuild &pb, const LayoutK
   uint32_t *d_segbase = nullptr;
   uint16_t *d_segptr = nullptr;
   int rc;
-  if ((rc = upload_all(m, &d_segbase, pb.seg_base)) || (rc = upload_all(m, &d_segptr, pb.seg_ptr))) return rc;
+  if ((rc = upload_all(m, &d_segbase, pb.seg_base, ABFT_SEG_SEG_BASE)) || (rc = upload_all(m, &d_segptr, pb.seg_ptr, ABFT_SEG_SEG_PTR))) return rc;
   m->layout = Layout::Panels;
   m->panels.seg_base = d_segbase;
   m->panels.seg_ptr = d_segptr;
@@ -768,7 +787,7 @@ static int attach_sweep(abft_hip_matrix *m, const SweepBuild &sb, uint32_t capac
   int rc;
   uint32_t *d_wbase = nullptr;
   uint8_t *d_counts = nullptr;
-  if ((rc = upload_all(m, &d_wbase, sb.wbase)) || (rc = upload_all(m, &d_counts, sb.counts)) || (rc = pace_board(m, &m->sweep.pace)))
+  if ((rc = upload_all(m, &d_wbase, sb.wbase, ABFT_SEG_WBASE)) || (rc = upload_all(m, &d_counts, sb.counts, ABFT_SEG_COUNTS)) || (rc = pace_board(m, &m->sweep.pace)))
     return rc;
   m->layout = Layout::Sweep;
   m->sweep_grid = sweep_grid(sb.ngroups, capacity);
@@ -790,7 +809,7 @@ static int attach_slice(abft_hip_matrix *m, const SliceBuild &sb, uint32_t waves
   int rc;
   uint32_t *d_sub = nullptr;
   uint16_t *d_rid = nullptr;
-  if ((rc = upload_all(m, &d_sub, sb.sub)) || (rc = upload_all(m, &d_rid, sb.rid)) || (rc = pace_board(m, &m->slice.pace))) return rc;
+  if ((rc = upload_all(m, &d_sub, sb.sub, ABFT_SEG_SUB)) || (rc = upload_all(m, &d_rid, sb.rid, ABFT_SEG_RID)) || (rc = pace_board(m, &m->slice.pace))) return rc;
   m->layout = Layout::Slice;
   m->slice_grid = slice_grid(sb.nslices, waves);
   m->slice_width = sb.width;
@@ -810,7 +829,7 @@ static int attach_compact(abft_hip_matrix *m, CompactBuild &cb) {
   uint16_t *d16 = nullptr;
   uint32_t *dbase = nullptr;
   int rc;
-  if ((rc = upload_all(m, &d16, cb.c16)) || (rc = upload_all(m, &dbase, cb.cbase))) return rc;
+  if ((rc = upload_all(m, &d16, cb.c16, ABFT_SEG_COLS16)) || (rc = upload_all(m, &dbase, cb.cbase, ABFT_SEG_CBASE))) return rc;
   HIPCHK(hipStreamSynchronize(m->ctx->stream));  // cbase moves
   m->compact.cols16 = d16;
   m->compact.cbase = dbase;
@@ -827,14 +846,14 @@ static int attach_packed(abft_hip_matrix *m, PackedBuild &pk, bool fast) {
   uint64_t *dpal = nullptr;
   Blk *dfast = nullptr;
   int rc;
-  if ((rc = upload_all(m, &dcode, pk.codes)) || (rc = upload_all(m, &ddesc, pk.pdesc)) ||
-      (rc = dev_upload(m, &dpal, m->pool.host.data(), m->pool.host.size(), m->pool.cap)))
+  if ((rc = upload_all(m, &dcode, pk.codes, ABFT_SEG_CODE16)) || (rc = upload_all(m, &ddesc, pk.pdesc, ABFT_SEG_PDESC)) ||
+      (rc = dev_upload(m, &dpal, m->pool.host.data(), m->pool.host.size(), m->pool.cap, ABFT_SEG_PAL)))
     return rc;
   // one record per block, {descriptor, fast word, 0}: what the mode-none SpMV on plain vectors loads instead of the
   // descriptor (ABFT_HIP_PACKED_FAST=0: the planner has left every word 0, and `fast_on` keeps a re-plan from setting one)
   std::vector<Blk> rec(pk.pdesc.size());
   for (size_t b = 0; b < rec.size(); b++) rec[b] = Blk{pk.pdesc[b].x, pk.pdesc[b].y, pk.fast[b], 0u};
-  if ((rc = upload_all(m, &dfast, rec))) return rc;
+  if ((rc = upload_all(m, &dfast, rec, ABFT_SEG_FAST))) return rc;
   HIPCHK(hipStreamSynchronize(m->ctx->stream));  // pdesc moves, rec goes out of scope
   m->packed_fast.rec = reinterpret_cast<const uint4 *>(dfast);
   m->fast_on = fast;
@@ -946,7 +965,8 @@ static int create_csr(abft_hip_matrix *m, const LayoutKnobs &knobs, const uint32
   A.pos_of_orig = nullptr;
   int rc;
   if (plan.layout == Layout::Stream) {
-    if ((rc = dev_upload(m, &A.cols, columns, (size_t)nnz, plan.padded)) || (rc = dev_upload(m, &A.vals, values, (size_t)nnz, plan.padded)))
+    if ((rc = dev_upload(m, &A.cols, columns, (size_t)nnz, plan.padded, ABFT_SEG_COLS)) ||
+        (rc = dev_upload(m, &A.vals, values, (size_t)nnz, plan.padded, ABFT_SEG_VALS)))
       return rc;
   } else {
     if ((rc = upload_permuted(m, plan.pos(), plan.orig(), columns, values, plan.padded))) return rc;
@@ -962,7 +982,7 @@ static int create_csr(abft_hip_matrix *m, const LayoutKnobs &knobs, const uint32
     std::vector<uint64_t> ext((size_t)n_out);
     for (int r = 0; r < n_out; r++) ext[(size_t)r] = rowext_pack(plan.rowptr[(size_t)r], plan.rowptr[(size_t)r + 1]);
     uint64_t *d_ext = nullptr;
-    if ((rc = upload_all(m, &d_ext, ext)) || (rc = upload_all(m, &d_blk, plan.blk))) return rc;
+    if ((rc = upload_all(m, &d_ext, ext, ABFT_SEG_ROWEXT)) || (rc = upload_all(m, &d_blk, plan.blk, ABFT_SEG_SBLK))) return rc;
     m->prot.rowext = d_ext;
     m->prot.blk = reinterpret_cast<uint4 *>(d_blk);
     m->protects = true;
@@ -972,7 +992,7 @@ static int create_csr(abft_hip_matrix *m, const LayoutKnobs &knobs, const uint32
     A.rowptr = nullptr;
     A.blk = nullptr;
   } else {
-    if ((rc = upload_all(m, &d_rowptr, plan.rowptr)) || (rc = upload_all(m, &d_blk, plan.blk))) return rc;
+    if ((rc = upload_all(m, &d_rowptr, plan.rowptr, ABFT_SEG_ROWPTR)) || (rc = upload_all(m, &d_blk, plan.blk, ABFT_SEG_BLK))) return rc;
     A.rowptr = d_rowptr;
     A.blk = reinterpret_cast<const uint4 *>(d_blk);
   }
@@ -1011,15 +1031,15 @@ static int create_coo(abft_hip_matrix *m, const LayoutKnobs &knobs, const uint32
   uint32_t *d_grp = nullptr, *d_orig = nullptr, *d_pos = nullptr;
   uint4 *d_el = nullptr;
   Blk *d_blk = nullptr;
-  if ((rc = dev_upload(m, &d_el, reinterpret_cast<const uint4 *>(elems.data()), (size_t)nnz, (size_t)nnz + 1)) ||
-      (rc = upload_all(m, &d_grp, plan.grp)) || (rc = upload_all(m, &d_blk, plan.blk)) ||
-      (rc = dev_upload(m, &d_orig, plan.orig.data(), (size_t)nnz, (size_t)nnz)) ||
-      (rc = dev_upload(m, &d_pos, plan.pos.data(), (size_t)nnz, (size_t)nnz)))
+  if ((rc = dev_upload(m, &d_el, reinterpret_cast<const uint4 *>(elems.data()), (size_t)nnz, (size_t)nnz + 1, ABFT_SEG_ELEMS)) ||
+      (rc = upload_all(m, &d_grp, plan.grp, ABFT_SEG_GRP_PTR)) || (rc = upload_all(m, &d_blk, plan.blk, ABFT_SEG_COO_BLK)) ||
+      (rc = dev_upload(m, &d_orig, plan.orig.data(), (size_t)nnz, (size_t)nnz, ABFT_SEG_COO_ORIG_INDEX)) ||
+      (rc = dev_upload(m, &d_pos, plan.pos.data(), (size_t)nnz, (size_t)nnz, ABFT_SEG_COO_POS_OF_ORIG)))
     return rc;
   A.elems = d_el; A.grp_ptr = d_grp; A.blk = reinterpret_cast<const uint4 *>(d_blk); A.orig_index = d_orig; A.pos_of_orig = d_pos;
   if (mode == ABFT_MODE_CONSTRAINTS) {
     Pair *d_made = nullptr;
-    if ((rc = upload_all(m, &d_made, plan.as_created))) return rc;
+    if ((rc = upload_all(m, &d_made, plan.as_created, ABFT_SEG_AS_CREATED))) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     A.as_created = reinterpret_cast<const uint2 *>(d_made);
   }
@@ -1119,7 +1139,7 @@ extern "C" int abft_hip_matrix_create_shard_indexed(abft_hip_ctx *ctx, int forma
   if (!global_index || nnz == 0) return ABFT_OK;
   abft_hip_matrix *m = *mat;
   uint32_t *d = nullptr;
-  if (int rc = dev_upload(m, &d, global_index, (size_t)nnz, (size_t)nnz)) {
+  if (int rc = dev_upload(m, &d, global_index, (size_t)nnz, (size_t)nnz, format == ABFT_FMT_CSR ? ABFT_SEG_GIDX : ABFT_SEG_COO_GIDX)) {
     matrix_free(m);
     *mat = nullptr;
     return rc;
@@ -1477,6 +1497,194 @@ extern "C" int abft_hip_matrix_scrub_structure(abft_hip_ctx *ctx, abft_hip_matri
   HIPCHK(hipStreamSynchronize(s));
   if (corrected) *corrected = got[0];
   if (uncorrectable) *uncorrectable = got[1];
+  return ABFT_OK;
+}
+
+// ---- matrix digests (matrix_digest.h) ----
+// These entries read the matrix's arrays and nothing else: no vector, no scalar of the loop.  They run without the
+// prologue (`enter`), so a verification between two calls of the CG loop leaves the fused product, the deferred and
+// queued x updates and the run-ahead exactly as they were: the loop makes the launches it makes without it.
+
+extern "C" const char *abft_hip_segment_name(uint32_t kind) { return kind < ABFT_SEG_COUNT ? abft_seg_name(kind) : nullptr; }
+
+extern "C" int abft_hip_matrix_segments(abft_hip_matrix *mat, uint32_t *kinds, uint64_t *bytes, int cap, int *count) {
+  if (!mat || !count || cap < 0) return set_err(ABFT_ERR_INVALID, "matrix_segments: bad arguments");
+  const int n = (int)mat->segments.size();
+  for (int k = 0; k < std::min(n, cap); k++) {
+    if (kinds) kinds[k] = mat->segments[(size_t)k].kind;
+    if (bytes) bytes[k] = (uint64_t)mat->segments[(size_t)k].bytes;
+  }
+  *count = n;
+  return ABFT_OK;
+}
+
+static int digest_check(const char *what, abft_hip_ctx *ctx, abft_hip_matrix *mat) {
+  if (!ctx || !mat) return set_err(ABFT_ERR_INVALID, "%s: null argument", what);
+  if (ctx != mat->ctx) return set_err(ABFT_ERR_INVALID, "%s: the matrix belongs to another context", what);
+  HIPCHK(hipSetDevice(ctx->device));
+  return ABFT_OK;
+}
+
+// the table and the accumulators: allocated by the first digest call, rebuilt when a segment has been added since
+// (the global index map of a shard is uploaded behind create)
+static int digest_prepare(const char *what, abft_hip_matrix *m) {
+  auto &D = m->digest;
+  const uint32_t n = (uint32_t)m->segments.size();
+  if (D.table && D.nseg == n) return ABFT_OK;
+  if (m->ctx->capturing) return set_err(ABFT_ERR_INVALID, "%s: called under graph capture (it allocates)", what);
+  if (n > ABFT_DIGEST_MAX_SEGS) return set_err(ABFT_ERR_INVALID, "%s: %u segments, the table holds %u", what, n, ABFT_DIGEST_MAX_SEGS);
+  std::vector<DigestSeg> rows(std::max<uint32_t>(n, 1u));
+  for (uint32_t k = 0; k < n; k++) {
+    const auto &sg = m->segments[k];
+    uint64_t words;
+    if (!digest_word_count((uint64_t)sg.bytes, &words))
+      return set_err(ABFT_ERR_RANGE, "%s: segment %s has %zu bytes; a digest covers at most 2^31 words", what,
+                     abft_seg_name(sg.kind), sg.bytes);
+    rows[k] = DigestSeg{sg.ptr, (uint32_t)(sg.bytes >> 4), (uint32_t)(sg.bytes & 15u), sg.kind, 0u};
+  }
+  if (!D.table) {
+    // one allocation: the table, then ABFT_DIGEST_MAX_SEGS accumulators, references and pairs
+    const size_t words = 4u * ABFT_DIGEST_MAX_SEGS;
+    unsigned char *p = nullptr;
+    const size_t bytes = ABFT_DIGEST_MAX_SEGS * sizeof(DigestSeg) + words * sizeof(unsigned long long);
+    if (hipMalloc((void **)&p, bytes) != hipSuccess) return set_err(ABFT_ERR_NOMEM, "%s: hipMalloc of %zu bytes failed", what, bytes);
+    m->allocs.push_back(p);
+    HIPCHK(hipMemsetAsync(p, 0, bytes, m->ctx->stream));
+    D.table = reinterpret_cast<DigestSeg *>(p);
+    D.acc = reinterpret_cast<unsigned long long *>(p + ABFT_DIGEST_MAX_SEGS * sizeof(DigestSeg));
+    D.ref = D.acc + ABFT_DIGEST_MAX_SEGS;
+    D.pairs = D.ref + ABFT_DIGEST_MAX_SEGS;
+  }
+  HIPCHK(hipMemcpyAsync(D.table, rows.data(), (size_t)n * sizeof(DigestSeg), hipMemcpyHostToDevice, m->ctx->stream));
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));  // `rows` goes out of scope
+  D.nseg = n;
+  D.armed = false;  // a reference taken over fewer segments says nothing about this table
+  return ABFT_OK;
+}
+
+// as the other streaming kernels: from the CU count, capped by the work (one workgroup per step of the largest segment)
+static uint32_t digest_grid(const abft_hip_matrix *m) {
+  size_t most = 0;
+  for (const auto &sg : m->segments) most = std::max(most, sg.bytes);
+  const size_t steps = (most / 16u + 4u * ABFT_BLOCK - 1u) / (4u * ABFT_BLOCK);
+  return (uint32_t)std::max<size_t>(1u, std::min<size_t>((size_t)m->ctx->num_cus * 8u, steps));
+}
+
+// the current digests -> out[0 .. nseg), synchronously; the accumulators are zero again behind it
+static int digest_now(const char *what, abft_hip_matrix *m, uint64_t *out) {
+  if (int rc = digest_prepare(what, m)) return rc;
+  auto &D = m->digest;
+  if (!D.nseg) return ABFT_OK;
+  hipStream_t s = m->ctx->stream;
+  HIPCHK(launch_matrix_digest(D.table, D.nseg, D.acc, digest_grid(m), s));
+  HIPCHK(hipMemcpyAsync(out, D.acc, (size_t)D.nseg * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemsetAsync(D.acc, 0, (size_t)D.nseg * sizeof(uint64_t), s));
+  HIPCHK(hipStreamSynchronize(s));
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_matrix_digest(abft_hip_ctx *ctx, abft_hip_matrix *mat, uint64_t *out, int cap) {
+  if (int rc = digest_check("matrix_digest", ctx, mat)) return rc;
+  if (ctx->capturing) return set_err(ABFT_ERR_INVALID, "matrix_digest: called under graph capture (it waits for its result)");
+  if (cap < (int)mat->segments.size() || (!out && !mat->segments.empty()))
+    return set_err(ABFT_ERR_INVALID, "matrix_digest: room for %d digests, the matrix has %zu segments", cap, mat->segments.size());
+  return digest_now("matrix_digest", mat, out);
+}
+
+extern "C" int abft_hip_matrix_digest_arm(abft_hip_ctx *ctx, abft_hip_matrix *mat) {
+  if (int rc = digest_check("matrix_digest_arm", ctx, mat)) return rc;
+  if (ctx->capturing) return set_err(ABFT_ERR_INVALID, "matrix_digest_arm: called under graph capture (it allocates and waits)");
+  auto &D = mat->digest;
+  std::vector<uint64_t> now(std::max<size_t>(mat->segments.size(), 1u));
+  if (int rc = digest_now("matrix_digest_arm", mat, now.data())) return rc;
+  now.resize(D.nseg);
+  if (D.nseg) {
+    HIPCHK(hipMemcpyAsync(D.ref, now.data(), (size_t)D.nseg * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  D.ref_host = now;
+  D.armed = true;
+  return ABFT_OK;
+}
+
+static int refuse_unarmed(const char *what, const abft_hip_matrix *mat) {
+  if (mat->digest.armed && mat->digest.nseg == mat->segments.size()) return ABFT_OK;
+  return set_err(ABFT_ERR_INVALID, "%s: the matrix is not armed; take its reference digests with abft_hip_matrix_digest_arm first", what);
+}
+
+extern "C" int abft_hip_matrix_verify(abft_hip_ctx *ctx, abft_hip_matrix *mat, int *bad_count, uint32_t *bad_kinds, int cap) {
+  if (int rc = digest_check("matrix_verify", ctx, mat)) return rc;
+  if (!bad_count || cap < 0 || (cap && !bad_kinds)) return set_err(ABFT_ERR_INVALID, "matrix_verify: bad arguments");
+  if (ctx->capturing) return set_err(ABFT_ERR_INVALID, "matrix_verify: called under graph capture (it waits for its verdict); capture abft_hip_matrix_verify_dev");
+  if (int rc = refuse_unarmed("matrix_verify", mat)) return rc;
+  auto &D = mat->digest;
+  std::vector<uint64_t> now(std::max<uint32_t>(D.nseg, 1u));
+  if (int rc = digest_now("matrix_verify", mat, now.data())) return rc;
+  int bad = 0;
+  for (uint32_t k = 0; k < D.nseg; k++)
+    if (now[k] != D.ref_host[k]) {
+      if (bad < cap) bad_kinds[bad] = mat->segments[k].kind;
+      bad++;
+    }
+  *bad_count = bad;
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_matrix_verify_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat) {
+  if (int rc = digest_check("matrix_verify_dev", ctx, mat)) return rc;
+  if (int rc = refuse_unarmed("matrix_verify_dev", mat)) return rc;
+  auto &D = mat->digest;
+  if (!D.nseg) return ABFT_OK;
+  HIPCHK(launch_matrix_digest(D.table, D.nseg, D.acc, digest_grid(mat), ctx->stream));
+  HIPCHK(launch_matrix_digest_finish(D.table, D.nseg, D.acc, D.ref, D.pairs, ctx->ring, (uint32_t)mat->fmt, ctx->stream));
+  return ABFT_OK;
+}
+
+static const abft_hip_matrix::Segment *segment_of(const abft_hip_matrix *mat, uint32_t kind) {
+  for (const auto &sg : mat->segments)
+    if (sg.kind == kind) return &sg;
+  return nullptr;
+}
+
+extern "C" int abft_hip_matrix_read_segment(abft_hip_ctx *ctx, abft_hip_matrix *mat, uint32_t kind, void *buf, uint64_t bytes) {
+  if (int rc = digest_check("matrix_read_segment", ctx, mat)) return rc;
+  if (ctx->capturing) return set_err(ABFT_ERR_INVALID, "matrix_read_segment: called under graph capture");
+  const auto *sg = segment_of(mat, kind);
+  if (!sg) return set_err(ABFT_ERR_INVALID, "matrix_read_segment: the matrix has no segment of kind %u (%s)", kind, abft_seg_name(kind));
+  if (bytes > sg->bytes || (bytes && !buf))
+    return set_err(ABFT_ERR_INVALID, "matrix_read_segment: %llu bytes asked of segment %s, which has %zu",
+                   (unsigned long long)bytes, abft_seg_name(kind), sg->bytes);
+  if (bytes) HIPCHK(hipMemcpyAsync(buf, sg->ptr, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return ABFT_OK;
+}
+
+extern "C" int abft_hip_matrix_flip_segment(abft_hip_ctx *ctx, abft_hip_matrix *mat, uint32_t kind, uint64_t word, const int *bits,
+                                            int nbits) {
+  if (int rc = digest_check("matrix_flip_segment", ctx, mat)) return rc;
+  if (ctx->capturing) return set_err(ABFT_ERR_INVALID, "matrix_flip_segment: called under graph capture");
+  const auto *sg = segment_of(mat, kind);
+  if (!sg) return set_err(ABFT_ERR_INVALID, "matrix_flip_segment: the matrix has no segment of kind %u (%s)", kind, abft_seg_name(kind));
+  if (word >= ((uint64_t)sg->bytes + 3u) / 4u)
+    return set_err(ABFT_ERR_INVALID, "matrix_flip_segment: word %llu outside segment %s of %zu bytes", (unsigned long long)word,
+                   abft_seg_name(kind), sg->bytes);
+  if (nbits < 0 || nbits > 32 || (nbits && !bits)) return set_err(ABFT_ERR_INVALID, "bad bit list");
+  const size_t have = std::min<size_t>(4u, sg->bytes - (size_t)word * 4u);  // stored bytes of the word (a last word may be short)
+  uint32_t mask = 0u;
+  for (int k = 0; k < nbits; k++) {
+    if (bits[k] < 0 || bits[k] >= (int)(8u * have)) return set_err(ABFT_ERR_INVALID, "bit %d outside [0,%zu)", bits[k], 8u * have);
+    mask ^= 1u << bits[k];
+  }
+  if (!mask) return ABFT_OK;
+  // (the stored word through the host, byte by byte where it is short: nothing of the hot path)
+  hipStream_t s = ctx->stream;
+  unsigned char *at = static_cast<unsigned char *>(sg->ptr) + (size_t)word * 4u;
+  unsigned char b[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(b, at, have, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  for (size_t k = 0; k < have; k++) b[k] ^= (unsigned char)(mask >> (8u * k));
+  HIPCHK(hipMemcpyAsync(at, b, have, hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
   return ABFT_OK;
 }
 
@@ -4376,7 +4584,7 @@ extern "C" int abft_hip_graph_destroy(abft_hip_graph *g) {
 
 extern "C" int abft_event_is_fatal(uint32_t kind) {
   return kind == ABFT_EV_SED_DETECTED || kind == ABFT_EV_DOUBLE_BIT || kind == ABFT_EV_VEC_DOUBLE || kind == ABFT_EV_STRUCT_DOUBLE ||
-         kind == ABFT_EV_TRAIL_DOUBLE ||
+         kind == ABFT_EV_TRAIL_DOUBLE || kind == ABFT_EV_MATRIX_DIGEST ||
          (kind >= ABFT_EV_ROW_SIZE && kind <= ABFT_EV_MOVED_OVERFLOW);
 }
 
@@ -4425,6 +4633,8 @@ extern "C" int abft_format_event(const abft_event *ev, char *buf, size_t cap) {
     case ABFT_EV_TRAIL_DOUBLE:
       return snprintf(buf, cap, "[ECC] double-bit error detected in trail word %d (%s)\n", i,
                       trail_record_name((ev->bit >> 8) & 0xffu));
+    case ABFT_EV_MATRIX_DIGEST:
+      return snprintf(buf, cap, "[ABFT] matrix digest mismatch in segment %s\n", abft_seg_name(ev->index));
     default: return snprintf(buf, cap, "unknown event %u\n", ev->kind);
   }
 }
@@ -4467,6 +4677,9 @@ extern "C" int abft_hip_drain_events(abft_hip_ctx *ctx, abft_event *buf, int cap
   // and their events arrive with that row in `bit` (cleared again below).
   auto csr_check = [](const abft_event &e) { return e.fmt == ABFT_FMT_CSR && e.kind >= ABFT_EV_ROW_SIZE && e.kind <= ABFT_EV_COL_ORDER; };
   std::sort(ev.begin(), ev.end(), [&](const abft_event &a, const abft_event &b) {
+    // a digest mismatch speaks of the matrix as a whole: behind the ECC events of the same drain, by segment kind
+    const bool da = a.kind == ABFT_EV_MATRIX_DIGEST, db = b.kind == ABFT_EV_MATRIX_DIGEST;
+    if (da != db) return db;
     if (csr_check(a) && csr_check(b)) {
       if (a.bit != b.bit) return a.bit < b.bit;
       const bool ea = a.kind >= ABFT_EV_COL_SIZE, eb = b.kind >= ABFT_EV_COL_SIZE;
@@ -4494,7 +4707,12 @@ extern "C" int abft_hip_drain_events(abft_hip_ctx *ctx, abft_event *buf, int cap
   // hand over what precedes it (a short caller buffer must not hide a fatal event)
   uint32_t want = n;
   for (uint32_t i = 0; i < n; i++)
-    if (abft_event_is_fatal(ev[i].kind)) { want = i + 1; if (fatal) *fatal = 1; break; }
+    if (abft_event_is_fatal(ev[i].kind)) {
+      // (a digest mismatch sorts last, so only its like follow it: all of them are handed over, one line per segment)
+      want = ev[i].kind == ABFT_EV_MATRIX_DIGEST ? n : i + 1;
+      if (fatal) *fatal = 1;
+      break;
+    }
   const uint32_t out = std::min<uint32_t>(want, (uint32_t)cap);
   for (uint32_t i = 0; i < out; i++) buf[i] = ev[i];
   *count = (int)out;

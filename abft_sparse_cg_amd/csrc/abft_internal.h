@@ -754,3 +754,13 @@ hipError_t launch_peer_allreduce(double *pair, const PeerArgs &P, hipStream_t s)
 hipError_t launch_copy(double *dst, const double *src, int n, hipStream_t s);
 hipError_t launch_stream_copy(double *dst, const double *src, size_t n, hipStream_t s);
 hipError_t launch_stream_read(const double *src, size_t n, double *sink, hipStream_t s);
+
+// ---- matrix digests (matrix_digest.h; abft_hip_matrix_digest / _arm / _verify / _verify_dev) ----
+struct DigestSeg;
+// acc[k] += D(segment k) for the nseg rows of `table` (device memory), one launch of `grid` workgroups over all of them
+hipError_t launch_matrix_digest(const DigestSeg *table, uint32_t nseg, unsigned long long *acc, uint32_t grid, hipStream_t s);
+// behind it, one workgroup: pairs[2k] = acc[k], pairs[2k + 1] = ref[k]; one ABFT_EV_MATRIX_DIGEST event per k where they
+// differ (index = the segment's kind); acc[k] = 0
+hipError_t launch_matrix_digest_finish(const DigestSeg *table, uint32_t nseg, unsigned long long *acc,
+                                       const unsigned long long *ref, unsigned long long *pairs, EventRing ev, uint32_t fmt,
+                                       hipStream_t s);

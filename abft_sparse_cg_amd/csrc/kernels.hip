@@ -17,6 +17,7 @@
 #include "abft_internal.h"
 #include "ecc_device.h"
 #include "guard_protocol.h"
+#include "matrix_digest.h"
 #include "struct_ecc.h"
 #include "trail_ecc.h"
 #include "vecc_walk.h"
@@ -6429,6 +6430,100 @@ hipError_t launch_stream_copy(double *dst, const double *src, size_t n, hipStrea
 hipError_t launch_stream_read(const double *src, size_t n, double *sink, hipStream_t s) {
   hipLaunchKernelGGL(stream_read_kernel, dim3(256 * 8), dim3(ABFT_BLOCK), 0, s, (const double2 *)src, n / 2,
                      sink);
+  return hipGetLastError();
+}
+
+// ----------------------------------------------------------- matrix digests --
+// D(segment) = sum w[i] (2 i + 1) mod 2^64 over every segment of a matrix in ONE launch (matrix_digest.h, DESIGN.md
+// section 5u).  A plain read stream: every workgroup walks the table; per segment it takes its grid-stride share of
+// the 16-byte groups, four loads in flight per lane, one 32 x 32 -> 64 multiply-add per word into a 64-bit register
+// pair, folds the lanes over DPP and the four waves through LDS, and thread 0 adds the workgroup's share onto the
+// segment's accumulator with one 64-bit integer atomic.  Integer addition commutes, so the accumulator holds the same
+// bits whatever the order.  A workgroup with no share of a segment (most of them, on the small tables) skips it
+// without a barrier or an atomic: the test is uniform over the workgroup.  The bytes behind the last full group
+// (0..15, the last word zero-extended) are workgroup 0's, read byte by byte: nothing is loaded past the segment.
+typedef __attribute__((address_space(1))) u32x4 GlobalQuad;
+__device__ __forceinline__ unsigned long long digest_quad(unsigned long long acc, u32x4 v, uint32_t q) {
+  acc = digest_term(acc, v.x, 4u * q);
+  acc = digest_term(acc, v.y, 4u * q + 1u);
+  acc = digest_term(acc, v.z, 4u * q + 2u);
+  return digest_term(acc, v.w, 4u * q + 3u);
+}
+
+__global__ __launch_bounds__(ABFT_BLOCK) void matrix_digest_kernel(const DigestSeg *__restrict__ table, uint32_t nseg,
+                                                                   unsigned long long *__restrict__ acc) {
+  __shared__ unsigned long long wave_sum[ABFT_BLOCK / 64];
+  constexpr uint32_t PER_BLOCK = 4u * ABFT_BLOCK;  // groups a workgroup takes per step
+  const uint32_t first = blockIdx.x * PER_BLOCK, step = gridDim.x * PER_BLOCK;
+  for (uint32_t s = 0; s < nseg; s++) {
+    const DigestSeg seg = table[s];
+    const bool tail_here = blockIdx.x == 0u && seg.tail != 0u;
+    if (first >= seg.quads && !tail_here) continue;  // uniform over the workgroup
+    // (the table hands the pointer over as a generic one: say that it is device memory, for global loads)
+    const GlobalQuad *src = (const GlobalQuad *)seg.base;
+    unsigned long long sum = 0ull;
+    // whole steps, nothing predicated (quads <= 2^29 and step <= 2^21: base never wraps) ...
+    uint32_t base = first + threadIdx.x;
+    for (; base + 3u * ABFT_BLOCK < seg.quads; base += step) {
+      u32x4 v[4];
+#pragma unroll
+      for (uint32_t k = 0; k < 4u; k++) v[k] = STREAM_LOAD(src + base + k * ABFT_BLOCK);
+#pragma unroll
+      for (uint32_t k = 0; k < 4u; k++) sum = digest_quad(sum, v[k], base + k * ABFT_BLOCK);
+    }
+    // ... and the one step that is cut short (base + step lies past the end: base + 3 * ABFT_BLOCK did already)
+    if (base < seg.quads) {
+      u32x4 v[4];
+#pragma unroll
+      for (uint32_t k = 0; k < 4u; k++) {
+        const uint32_t q = base + k * ABFT_BLOCK;
+        v[k] = q < seg.quads ? STREAM_LOAD(src + q) : u32x4{0u, 0u, 0u, 0u};
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < 4u; k++) sum = digest_quad(sum, v[k], base + k * ABFT_BLOCK);  // (a zero word adds nothing)
+    }
+    if (tail_here && threadIdx.x < (seg.tail + 3u) / 4u) {
+      const unsigned char *p = static_cast<const unsigned char *>(seg.base) + (size_t)seg.quads * 16u + 4u * threadIdx.x;
+      const uint32_t left = seg.tail - 4u * threadIdx.x;
+      sum = digest_term(sum, digest_tail_word(p, left < 4u ? left : 4u), 4u * seg.quads + threadIdx.x);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    __syncthreads();  // the previous segment's sums have been read
+    if ((threadIdx.x & 63u) == 0u) wave_sum[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+      unsigned long long total = 0ull;
+#pragma unroll
+      for (int w = 0; w < ABFT_BLOCK / 64; w++) total += wave_sum[w];
+      atomicAdd(acc + s, total);
+    }
+  }
+}
+
+// One workgroup, in stream order behind matrix_digest_kernel: that order is all the ordering there is.
+__global__ __launch_bounds__(64) void matrix_digest_finish_kernel(const DigestSeg *__restrict__ table, uint32_t nseg,
+                                                                  unsigned long long *__restrict__ acc,
+                                                                  const unsigned long long *__restrict__ ref,
+                                                                  unsigned long long *__restrict__ pairs, EventRing ev,
+                                                                  uint32_t fmt) {
+  const uint32_t s = threadIdx.x;
+  if (s >= nseg) return;
+  const unsigned long long now = acc[s], armed = ref[s];
+  pairs[2u * s] = now;
+  pairs[2u * s + 1u] = armed;
+  if (now != armed) push_event(ev, ABFT_EV_MATRIX_DIGEST, table[s].kind, 0u, fmt);
+  acc[s] = 0ull;
+}
+
+hipError_t launch_matrix_digest(const DigestSeg *table, uint32_t nseg, unsigned long long *acc, uint32_t grid, hipStream_t s) {
+  hipLaunchKernelGGL(matrix_digest_kernel, dim3(grid), dim3(ABFT_BLOCK), 0, s, table, nseg, acc);
+  return hipGetLastError();
+}
+hipError_t launch_matrix_digest_finish(const DigestSeg *table, uint32_t nseg, unsigned long long *acc,
+                                       const unsigned long long *ref, unsigned long long *pairs, EventRing ev, uint32_t fmt,
+                                       hipStream_t s) {
+  hipLaunchKernelGGL(matrix_digest_finish_kernel, dim3(1), dim3(64), 0, s, table, nseg, acc, ref, pairs, ev, fmt);
   return hipGetLastError();
 }
 

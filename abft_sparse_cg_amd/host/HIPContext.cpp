@@ -394,6 +394,10 @@ void HIPContextBase::check(int rc, const char *what)
 // which is what a single-process run prints; all ranks then stop together.
 static bool event_before(const abft_event &a, const abft_event &b)
 {
+  // as the library's drain: a matrix digest mismatch (its index is a segment kind) behind every other event
+  const bool da = a.kind == ABFT_EV_MATRIX_DIGEST, db = b.kind == ABFT_EV_MATRIX_DIGEST;
+  if (da != db)
+    return db;
   return a.index != b.index ? a.index < b.index : a.kind < b.kind;
 }
 

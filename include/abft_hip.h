@@ -82,7 +82,12 @@ typedef enum {
    * the word's ordinal in its record, `bit` holds the slot's bit in bits 0..7 (numbered as a COO element's 128, the
    * parity bit 24) and the record in bits 8..15 -- ABFT_TRAIL_START, ABFT_TRAIL_PW or ABFT_TRAIL_NEXT */
   ABFT_EV_TRAIL_CORRECTED = 14, /* "[ECC] corrected bit %u of trail word %d (start record|p.w pair|next record)"        */
-  ABFT_EV_TRAIL_DOUBLE = 15     /* "[ECC] double-bit error detected in trail word %d (...)"                        fatal */
+  ABFT_EV_TRAIL_DOUBLE = 15,    /* "[ECC] double-bit error detected in trail word %d (...)"                        fatal */
+  /* matrix digests (abft_hip_matrix_verify, abft_hip_matrix_verify_dev; fmt = the matrix's): a stored array of the
+   * matrix no longer has the digest it was armed with.  `index` is the segment kind (abft_hip_segment_name), `bit` 0.
+   * A drain hands these over behind every other event of the same drain, and where the first fatal event of a drain
+   * is one of them, all of them: one line per differing segment. */
+  ABFT_EV_MATRIX_DIGEST = 16    /* "[ABFT] matrix digest mismatch in segment NAME"                                fatal */
 } abft_event_kind;
 #define ABFT_STRUCT_ROW_EXTENT 0
 #define ABFT_STRUCT_ROW_BLOCK 1
@@ -1084,6 +1089,54 @@ int abft_hip_graph_begin(abft_hip_ctx *ctx);
 int abft_hip_graph_end(abft_hip_ctx *ctx, abft_hip_graph **graph);
 int abft_hip_graph_launch(abft_hip_graph *graph);
 int abft_hip_graph_destroy(abft_hip_graph *graph);
+
+/* ---- matrix digests ---------------------------------------------------- */
+
+/* Once abft_hip_matrix_create_* returns, the arrays of a matrix that kernels read are constant for its life: the only
+ * legitimate writes are ECC repairs, which store the original word back.  A SEGMENT is one such device allocation,
+ * viewed as little-endian 32-bit words w[0..n) over the whole allocation, padding included (the last word
+ * zero-extended when the byte length is no multiple of 4), n <= 2^31, and its digest is
+ *     D = sum of w[i] * (2 i + 1)  mod 2^64,
+ * which every single and every double bit flip inside the segment changes (csrc/matrix_digest.h has the argument;
+ * three or more flips can cancel).  A digest taken once (arm) and recomputed now and then (verify) therefore detects
+ * corruption of any stored array, in every mode, format and layout, for one streaming read of the matrix per
+ * verification.  It detects, it does not repair: after a mismatch the caller re-creates the matrix.  Not covered:
+ * compute faults, the vectors, a flip that an ECC mode repairs between two verifications.  The reference digests
+ * sit unprotected in device memory: a flip there is a false alarm, never a miss.
+ *
+ * The segment kinds are a fixed list (csrc/matrix_digest.h, ABFT_SEG_*); abft_hip_segment_name gives a kind's name
+ * ("cols", "pal", "wbase", ...; NULL past the end of the list).  The progress boards, debug buffers, the moved list
+ * and the fused product's partials are written by kernels and are no segments.  The entries that rewrite matrix
+ * arrays on purpose (abft_hip_inject and the re-planning behind it, abft_hip_inject_rowptr, abft_hip_inject_structure,
+ * abft_hip_matrix_write_structure, abft_hip_matrix_flip_segment) leave the armed digests alone: an injected flip is
+ * the fault to be found. */
+const char *abft_hip_segment_name(uint32_t kind);
+/* Which segments this matrix has, in the order every other entry here uses: kinds[k], bytes[k] for k < min(cap, *count);
+ * *count = how many there are (kinds / bytes may be NULL with cap 0). */
+int abft_hip_matrix_segments(abft_hip_matrix *mat, uint32_t *kinds, uint64_t *bytes, int cap, int *count);
+/* The current digests, out[k] for segment k (cap >= the segment count, else ABFT_ERR_INVALID).  Synchronous; not under
+ * graph capture.  The first digest call on a matrix allocates its segment table and accumulators. */
+int abft_hip_matrix_digest(abft_hip_ctx *ctx, abft_hip_matrix *mat, uint64_t *out, int cap);
+/* Compute the digests and keep them as the reference, on the host and in device memory.  Arming again takes a new
+ * reference.  Nothing is armed at create: a matrix that is never armed makes exactly the launches and allocations
+ * it made before these entries existed.  Synchronous; not under graph capture. */
+int abft_hip_matrix_digest_arm(abft_hip_ctx *ctx, abft_hip_matrix *mat);
+/* Recompute and compare: *bad_count segments differ, bad_kinds[0 .. min(cap, *bad_count)) name them in segment
+ * order.  Synchronous; queues no event.  ABFT_ERR_INVALID on a matrix that is not armed (the message names
+ * abft_hip_matrix_digest_arm). */
+int abft_hip_matrix_verify(abft_hip_ctx *ctx, abft_hip_matrix *mat, int *bad_count, uint32_t *bad_kinds, int cap);
+/* The same as two launches enqueued on the context's stream, nothing else: matrix_digest_kernel over all segments, and
+ * behind it one workgroup that compares, queues one ABFT_EV_MATRIX_DIGEST event per differing segment and zeroes the
+ * accumulators.  It allocates nothing and waits for nothing, so it can be captured into a graph; the verdict arrives
+ * with the next drain.  ABFT_ERR_INVALID on a matrix that is not armed. */
+int abft_hip_matrix_verify_dev(abft_hip_ctx *ctx, abft_hip_matrix *mat);
+/* The tests' and the command line's injector for arrays no other injector reaches.  read_segment copies the first
+ * `bytes` bytes of the segment of that kind to buf (bytes <= the segment's).  flip_segment XORs the listed bits
+ * (0..31, nbits <= 32) into stored word `word` of the segment, as the digest numbers the words; in a zero-extended
+ * last word only the bits of stored bytes may be named.  Raw writes: no copy of the array anywhere else follows. */
+int abft_hip_matrix_read_segment(abft_hip_ctx *ctx, abft_hip_matrix *mat, uint32_t kind, void *buf, uint64_t bytes);
+int abft_hip_matrix_flip_segment(abft_hip_ctx *ctx, abft_hip_matrix *mat, uint32_t kind, uint64_t word, const int *bits,
+                                 int nbits);
 
 /* ---- events ------------------------------------------------------------ */
 
